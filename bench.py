@@ -6,7 +6,7 @@ A "step" is one smoothing iteration over the whole (per-rank) mesh.  Default wor
 configs[1]: 1M-cell uniform hex block (100^3, interior jitter 0.2 h, seed 12345), constraints off,
 relTol 0 (exactly K iterations run).  Inputs are device-resident when the timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W [--workload hex100|hex100c|hexN[c]]
+  python bench.py --gpus N --steps K --warmup W [--workload hex100|hex100c|hexN[c]] [--dump-outputs DIR]
 
 N > 1, one rank per GPU (started by torch.distributed.run, or by this script itself when WORLD_SIZE is unset): weak
 scaling -- hexN: every rank owns an N^3 sub-block of a (Px*N, Py*N, Pz*N) block; cavityN: the castellated polyhedral
@@ -364,10 +364,36 @@ def clock_warm(iterate, engine, sync, fixed=0):
     return done
 
 
-def run_single(workload, K, W, device, oracle=True, oracle_budget_s=12.0, nominal100=False):
+DUMP_LIMIT_BYTES = 64 * 2**20     # --dump-outputs: all arrays together
+
+
+def dump_outputs(path, points, res, frz):
+    """--dump-outputs DIR: what the timed iterate() call handed its caller after the last timed step -- the coordinates
+    (smgpu_get_points), the per-iteration residual and nFrozenPoints -- as DIR/<name>.npy in float64.  Coordinates larger than
+    DUMP_LIMIT_BYTES are written as a fixed sample of points (seed 0, ascending rows) with the row numbers beside them."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name in ("points", "points_sample", "points_sample_index", "residual", "nFrozenPoints"):     # nothing stale from an earlier run
+        if os.path.exists(os.path.join(path, name + ".npy")):
+            os.remove(os.path.join(path, name + ".npy"))
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    out = {"residual": np.asarray(res, dtype=np.float64), "nFrozenPoints": np.asarray(frz, dtype=np.float64)}
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values()) - 4096
+    if pts.nbytes <= room:
+        out["points"] = pts
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(len(pts), size=room // (pts.itemsize * 4), replace=False))
+        out["points_sample"] = pts[idx]
+        out["points_sample_index"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def run_single(workload, K, W, device, oracle=True, oracle_budget_s=12.0, nominal100=False, keep_points=False):
     """one GPU, one workload: W warm-up + K timed steps on a cold GPU (ms_per_step_cold), the clock pre-run, W + K again (the
     reported value; inputs resident), the same K steps with per-kernel hipEvents, and -- outside every timed region -- the
-    oracle leg (parity_check + cpu_baseline on this workload's own mesh)"""
+    oracle leg (parity_check + cpu_baseline on this workload's own mesh).  keep_points: also return the coordinates the
+    timed steps left (read after the clock has stopped)"""
     import torch
     from smoothmesh_amd import SmoothEngine, default_params
     kind, n_side, constraints = parse_workload(workload)
@@ -400,6 +426,7 @@ def run_single(workload, K, W, device, oracle=True, oracle_budget_s=12.0, nomina
     eng.set_points(mesh.points)
     pre = clock_warm(lambda k: eng.iterate(k, 0.0), eng, torch.cuda.synchronize)
     dt, res, frz = timed()
+    points = eng.get_points() if keep_points else None
     near_timed = eng.last_near_ties.sum() if hasattr(eng, "last_near_ties") else 0
     # the metric says "(100 iters)": when the contract's K is shorter (the driver runs 20 steps = 1.7 ms on the hex block), the same
     # loop once more over 100 steps from the initial coordinates, reported beside the K-step value
@@ -436,8 +463,8 @@ def run_single(workload, K, W, device, oracle=True, oracle_budget_s=12.0, nomina
     eng.close()
     del eng
     return dict(kind=kind, n_side=n_side, constraints=constraints, layers=layers, boundary=boundary, dt=dt, dt_cold=dt_cold, dt_ev=dt_ev,
-                ctr=ctr, sizes=sizes, total_points=nPoints, res=res, frz=frz, pre=pre, cpu_baseline=base, parity_check=par, near_ties=near, dt100=dt100,
-                phases={"mesh_generation_s": t_mesh, "engine_setup_s": t_create, "oracle_leg_s": t_oracle})
+                ctr=ctr, sizes=sizes, total_points=nPoints, res=res, frz=frz, points=points, pre=pre, cpu_baseline=base, parity_check=par, near_ties=near,
+                dt100=dt100, phases={"mesh_generation_s": t_mesh, "engine_setup_s": t_create, "oracle_leg_s": t_oracle})
 
 
 def make_subdomain(kind, n_side, grid, rank, world):
@@ -566,11 +593,13 @@ def rank0_cpu_baseline(sub, prm, budget_s, rank, world):
             "host_cpus": os.cpu_count(), "oracle_setup_s": setup_s}
 
 
-def run_distributed(workload, K, W, rank, world, local_rank, backend, oracle=True, force_dist=False, oracle_budget_s=12.0):
+def run_distributed(workload, K, W, rank, world, local_rank, backend, oracle=True, force_dist=False, oracle_budget_s=12.0,
+                    keep_points=False):
     """N ranks, one workload: per-rank sub-domain, exchange arrangement autotuned, clock pre-run, W warm-up + K timed steps between
     barriers (max over ranks), the same K steps with per-kernel hipEvents; outside the timed region: parity_check (a) copies of
     shared points identical across ranks, (b) a down-scaled case through the same transport against the oracle's MultiDomain;
-    cpu_baseline = rank 0's oracle on its own sub-domain; transport = how the records travelled (communicator size included)"""
+    cpu_baseline = rank 0's oracle on its own sub-domain; transport = how the records travelled (communicator size included);
+    keep_points: also return this rank's coordinates after the timed steps"""
     import torch
     import torch.distributed as dist
     from smoothmesh_amd import default_params
@@ -687,6 +716,7 @@ def run_distributed(workload, K, W, rank, world, local_rank, backend, oracle=Tru
     dist.all_reduce(npts, op=dist.ReduceOp.SUM)
     total_points = int(npts.item())      # points of all sub-domains (shared points counted per rank,
     eng = ds.engine                      # as the reference's per-rank loops process them)
+    points = eng.get_points() if keep_points else None
     copies = shared_copies_check(ds, sub) if world > 1 else None      # parity_check (a): the state the timed steps left
     eng.reset_counters()
     eng.enable_timing(True)
@@ -740,7 +770,7 @@ def run_distributed(workload, K, W, rank, world, local_rank, backend, oracle=Tru
         par = {"shared_point_copies": copies, "small_case": small,
                "ok": bool((copies or {}).get("ok", rank != 0) and (small or {}).get("ok", False))}
     return dict(kind=kind, n_side=n_side, constraints=constraints, layers=layers, boundary=boundary, dt=dt, dt_ev=dt_ev, ctr=ctr, sizes=sizes,
-                total_points=total_points, res=res, frz=frz, pre=pre, cpu_baseline=base, parity_check=par, transport=info,
+                total_points=total_points, res=res, frz=frz, points=points, pre=pre, cpu_baseline=base, parity_check=par, transport=info,
                 parallelism=parallelism, n_global=n_global, halo_cost=halo_cost,
                 phases={"mesh_generation_s": t_mesh, "engine_setup_s": t_create, "oracle_leg_s": t_oracle})
 
@@ -954,7 +984,12 @@ def main():
                     "(100 on the hex block, 200 on the polyhedral mesh)")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle legs of the configs[] sub-runs (the 10 M-cell "
                     "oracle costs minutes of host time)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the headline's last timed "
+                    "step computed to DIR/<name>.npy (float64): points (rank 0's sub-domain when N > 1; a fixed sample past 64 MB), "
+                    "residual, nFrozenPoints")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -986,8 +1021,11 @@ def main():
         for k, v in (("RANK", "0"), ("WORLD_SIZE", "1"), ("MASTER_ADDR", "127.0.0.1"), ("MASTER_PORT", "29577")):
             os.environ.setdefault(k, v)
     if world == 1 and not force_dist:
-        r = run_single(args.workload, K, W, local_rank, oracle=not args.no_cpu_baseline, nominal100=True)
+        r = run_single(args.workload, K, W, local_rank, oracle=not args.no_cpu_baseline, nominal100=True,
+                       keep_points=args.dump_outputs is not None)
         dt, dt_ev, ctr, sizes, total_points, res, frz = r["dt"], r["dt_ev"], r["ctr"], r["sizes"], r["total_points"], r["res"], r["frz"]
+        if args.dump_outputs is not None and rank == 0:
+            dump_outputs(args.dump_outputs, r.pop("points"), res, frz)
         pre = r["pre"]
         single = r
         parallelism = "1 GPU"
@@ -998,8 +1036,11 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
         else:
             dist.init_process_group(backend)
-        r = run_distributed(args.workload, K, W, rank, world, local_rank, backend, oracle=not args.no_cpu_baseline, force_dist=force_dist)
+        r = run_distributed(args.workload, K, W, rank, world, local_rank, backend, oracle=not args.no_cpu_baseline, force_dist=force_dist,
+                            keep_points=args.dump_outputs is not None and rank == 0)
         dt, dt_ev, ctr, sizes, total_points, res, frz = r["dt"], r["dt_ev"], r["ctr"], r["sizes"], r["total_points"], r["res"], r["frz"]
+        if args.dump_outputs is not None and rank == 0:
+            dump_outputs(args.dump_outputs, r.pop("points"), res, frz)
         pre, parallelism, n_global = r["pre"], r["parallelism"], r["n_global"]
         multi = r
         # BASELINE configs[4] beside the weak-scaling headline: the polyhedral mesh, cavity215c per GPU (the 430^3-base, ~80 M-cell

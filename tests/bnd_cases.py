@@ -1,4 +1,8 @@
 """Shared builders for the boundary point smoothing tests (oracle and GPU sides get the same inputs)."""
+import gzip
+import os
+import shutil
+
 import numpy as np
 
 
@@ -53,3 +57,19 @@ def make_pair(mesh, oracle_lib, init, target, surf, constraints=False, layerPatc
         assert bool(info["enabled"]) == on_o
         e.boundary_info = info
     return o, e, prm, on_o
+
+
+def reference_geometry(dest):
+    """The feature edge and target surface files of the reference's own test cases (testcase3-8, constant/geometry/*.obj),
+    stored gzip'ed under tests/golden/reference_geometry/; unpacked to dest/testcaseN/constant/geometry/<name>.obj.
+    Returns the unpacked paths, sorted."""
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_geometry")
+    out = []
+    for case in sorted(os.listdir(src)):
+        os.makedirs(os.path.join(dest, case, "constant", "geometry"), exist_ok=True)
+        for name in sorted(os.listdir(os.path.join(src, case))):
+            path = os.path.join(dest, case, "constant", "geometry", name[:-len(".gz")])
+            with gzip.open(os.path.join(src, case, name), "rb") as f, open(path, "wb") as g:
+                shutil.copyfileobj(f, g)
+            out.append(path)
+    return sorted(out)

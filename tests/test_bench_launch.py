@@ -240,3 +240,56 @@ def test_bench_single_gpu_line_carries_the_other_configs(tmp_path):
         assert c["cpu_baseline"]["kind"] == "port" and c["cpu_baseline"]["value"] > 0
         # no impossible bandwidths in the per-kernel table (filter + exact kernels are accounted as one unit)
         assert all(k["algo_GBps"] is None or k["algo_GBps"] < 8000 for k in c["kernels"])
+
+
+def test_dump_outputs_stays_under_its_limit_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 arrays only; coordinates past the limit become a seeded sample of whole points with their row
+    numbers, the same rows on every call; files of an earlier dump do not linger"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    pts = np.random.default_rng(1).random((5000, 3))
+    res, frz = np.linspace(1.0, 0.5, 6), np.arange(6, dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "a"), pts, res, frz)
+    assert sorted(os.listdir(tmp_path / "a")) == ["nFrozenPoints.npy", "points.npy", "residual.npy"]
+    assert np.array_equal(np.load(tmp_path / "a" / "points.npy"), pts)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 * 1024)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), pts, res, frz)
+    assert sorted(os.listdir(tmp_path / "a")) == ["nFrozenPoints.npy", "points_sample.npy", "points_sample_index.npy", "residual.npy"]
+    got = {n: np.load(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in got) <= 64 * 1024
+    idx = got["points_sample_index.npy"].astype(np.int64)
+    assert len(idx) > 1000 and np.all(np.diff(idx) > 0) and np.array_equal(got["points_sample.npy"], pts[idx])
+    assert np.array_equal(got["residual.npy"], res) and np.array_equal(got["nFrozenPoints.npy"], frz)
+    for n in got:
+        assert np.array_equal(np.load(tmp_path / "b" / n), got[n])
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_the_timed_steps_computed(tmp_path, oracle_lib):
+    """--dump-outputs DIR: the coordinates, residuals and nFrozenPoints the headline's timed iterate() call left after its K
+    steps (--steps), identical from run to run and equal to the oracle's after the same W + K iterations of the same mesh"""
+    import numpy as np
+    from smoothmesh_amd import default_params
+    from smoothmesh_amd.meshgen import hex_block
+    runs = []
+    for k in range(2):
+        r = _run(["--steps", "7", "--warmup", "2", "--workload", "hex10", "--no-configs", "--no-cpu-baseline", "--dump-outputs",
+                  str(tmp_path / f"out{k}")], detail=tmp_path / "detail.json")
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        c_ = _compact(r)
+        assert c_["steps"] == 7 and c_["warmup"] == 2 and c_["ms_per_step"] > 0
+        runs.append({n: np.load(tmp_path / f"out{k}" / f"{n}.npy") for n in ("points", "residual", "nFrozenPoints")})
+    a, b = runs
+    assert a["points"].shape == (11 ** 3, 3) and a["residual"].shape == (7,) and a["nFrozenPoints"].shape == (7,)
+    for n in a:
+        assert a[n].dtype == np.float64 and np.array_equal(a[n], b[n]), n
+    orc = oracle_lib.Oracle(hex_block(10, jitter=0.2, seed=12345))
+    orc.set_params(default_params(orc.mesh_stats()[0], edgeAngleConstraint=False, faceAngleConstraint=False))
+    n, res, frz = orc.iterate(9, 0.0)
+    assert n == 9 and np.array_equal(a["nFrozenPoints"], np.asarray(frz[2:], np.float64))
+    assert np.allclose(a["residual"], res[2:], rtol=1e-10, atol=0)
+    o = orc.points()
+    assert np.max(np.abs(a["points"] - o)) / np.max(np.abs(o)) <= 1e-10

@@ -211,21 +211,21 @@ def test_edge_strings_of_closed_loops_and_branching_meshes(oracle_lib):
         assert n_p == n_o and np.array_equal(sp, so)
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference/testcase3/constant/geometry"), reason="reference tree not present")
-def test_edge_strings_on_the_reference_test_cases(oracle_lib):
+def test_edge_strings_on_the_reference_test_cases(oracle_lib, tmp_path):
     """The feature edge files of the reference's own test cases.  Where the reference builds strings (the target edge
     mesh, SM.C:2170) the restated recursion yields the maximal chains -- except on testcase3's edge mesh, where it splits
     two chains: the recursion decides whether to descend by pointEdges()[<edge id>] (BPS.C:534,542), a quirk kept as
     written.  The product's routine and the oracle's agree on every file."""
-    import glob
+    import os
+    from bnd_cases import reference_geometry
     from smoothmesh_amd.surfgen import read_obj_edges
     seen = {}
-    for f in sorted(glob.glob("/root/reference/testcase*/constant/geometry/*Edges.obj")):
+    for f in [f for f in reference_geometry(str(tmp_path)) if f.endswith("Edges.obj")]:
         pts, e = read_obj_edges(f)
         so, n_o = oracle_lib.edge_strings(len(pts), e)
         sp, n_p = _product_edge_strings(len(pts), e)
         assert n_p == n_o and np.array_equal(sp, so), f
-        seen[f.split("reference/")[1]] = (n_o, len(set(_ideal_chains(len(pts), e).tolist())), _same_partition(so, _ideal_chains(len(pts), e)))
+        seen[os.path.relpath(f, tmp_path)] = (n_o, len(set(_ideal_chains(len(pts), e).tolist())), _same_partition(so, _ideal_chains(len(pts), e)))
     for case in ("testcase4/constant/geometry/targetEdges.obj", "testcase5/constant/geometry/initEdges.obj",
                  "testcase6/constant/geometry/initEdges.obj", "testcase7/constant/geometry/targetEdges.obj",
                  "testcase8/constant/geometry/initEdges.obj"):

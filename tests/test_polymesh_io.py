@@ -137,13 +137,12 @@ def test_obj_readers_agree_and_follow_openfoam_conventions(tmp_path):
         read_obj(str(bad), "surface")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/testcase3/constant/geometry"), reason="reference tree not present")
-def test_obj_readers_on_the_reference_test_cases():
+def test_obj_readers_on_the_reference_test_cases(tmp_path):
     """the geometry files of the reference's own test cases (Blender / VTK exports with mtllib, o, vn, s records and quads)"""
-    import glob
+    from bnd_cases import reference_geometry
     from smoothmesh_amd.polymesh import read_obj
     from smoothmesh_amd.surfgen import read_obj_edges, read_obj_surface
-    files = sorted(glob.glob("/root/reference/testcase*/constant/geometry/*.obj"))
+    files = reference_geometry(str(tmp_path))
     assert len(files) >= 10
     for f in files:
         kind = "surface" if f.endswith("targetSurfaces.obj") else "edges"
