@@ -144,6 +144,29 @@ int smgpu_check_error(smgpu_handle* h);
 int smgpu_get_near_ties(smgpu_handle* h, int64_t out[4]);
 int smgpu_set_points(smgpu_handle* h, const double* points /* [3*nPoints] */);
 
+/* ---- mesh quality report of the current points (DESIGN.md "Mesh quality") ------------------------------------------------
+ * One pass on the device over the loop's own face centres / area vectors / cell centres: cell volumes, face areas,
+ * non-orthogonality (degrees), skewness, face pyramids, cell openness and aspect ratio, after OpenFOAM primitiveMeshCheck.
+ * Needs no smgpu_set_params; leaves points, freeze state, walk mode, statistics and the iteration count as they were.
+ * Refused on an engine with a halo (a sub-domain's processor faces are internal faces of the global mesh).
+ * Ties of the max / min ids go to the lowest id; every sum is reduced in a fixed order (bitwise repeatable).
+ * p == NULL: the defaults 70 degrees, 4, 1e-6, 1000. */
+typedef struct smgpu_quality_params { double nonOrthThreshold, skewThreshold, closedThreshold, aspectThreshold; } smgpu_quality_params;
+typedef struct smgpu_quality {
+    int64_t nCells, nFaces, nInternalFaces;
+    double minVolume, maxVolume, totalVolume;  int64_t nNonPositiveVolume;  int32_t minVolumeCell;
+    double minFaceArea, maxFaceArea;           int64_t nZeroAreaFaces;
+    double maxNonOrth, avgNonOrth;             int64_t nSevereNonOrth, nErrorNonOrth;  int32_t maxNonOrthFace;
+    double maxSkewness;                        int64_t nSkewFaces;  int32_t maxSkewFace;
+    int64_t nWrongOrientedFaces;
+    double maxOpenness;                        int64_t nOpenCells;
+    double maxAspectRatio;                     int64_t nHighAspectCells;
+} smgpu_quality;
+int smgpu_mesh_quality(smgpu_handle* h, const smgpu_quality_params* p, smgpu_quality* out);
+/* per-element field in polyMesh order: "cellVolume", "cellOpenness", "cellAspectRatio" [nCells], "faceNonOrthogonality"
+ * (degrees, 0 on boundary faces), "faceSkewness" [nFaces].  out == NULL: size only (*n). */
+int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t* n);
+
 /* Timing: when enabled every kernel launch is bracketed by hipEvents on the handle's stream. */
 int smgpu_enable_timing(smgpu_handle* h, int32_t on);
 int smgpu_get_counters(smgpu_handle* h, smgpu_counters* out);

@@ -90,6 +90,25 @@ class BoundaryInfo(C.Structure):
                 ("nSmoothingSurfacePoints", C.c_int32), ("nFrozenSurfacePoints", C.c_int32), ("nTargetEdgeStrings", C.c_int32)]
 
 
+class QualityParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("nonOrthThreshold", "skewThreshold", "closedThreshold", "aspectThreshold")]
+
+
+class Quality(C.Structure):
+    _fields_ = [
+        ("nCells", C.c_int64), ("nFaces", C.c_int64), ("nInternalFaces", C.c_int64),
+        ("minVolume", C.c_double), ("maxVolume", C.c_double), ("totalVolume", C.c_double), ("nNonPositiveVolume", C.c_int64),
+        ("minVolumeCell", C.c_int32),
+        ("minFaceArea", C.c_double), ("maxFaceArea", C.c_double), ("nZeroAreaFaces", C.c_int64),
+        ("maxNonOrth", C.c_double), ("avgNonOrth", C.c_double), ("nSevereNonOrth", C.c_int64), ("nErrorNonOrth", C.c_int64),
+        ("maxNonOrthFace", C.c_int32),
+        ("maxSkewness", C.c_double), ("nSkewFaces", C.c_int64), ("maxSkewFace", C.c_int32),
+        ("nWrongOrientedFaces", C.c_int64),
+        ("maxOpenness", C.c_double), ("nOpenCells", C.c_int64),
+        ("maxAspectRatio", C.c_double), ("nHighAspectCells", C.c_int64),
+    ]
+
+
 # every symbol include/smgpu.h declares: (restype, argtypes)
 SYMBOLS = {
     "smgpu_last_error": (C.c_char_p, []),
@@ -140,6 +159,8 @@ SYMBOLS = {
     "smgpu_halo_set_exchange_stream": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "smgpu_get_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "smgpu_iter_end": (C.c_int, [C.c_void_p]),
+    "smgpu_mesh_quality": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.POINTER(Quality)]),
+    "smgpu_quality_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_addressing": (C.c_int, [C.c_void_p, C.c_char_p, c_i32p, c_i32p, C.POINTER(C.c_int64)]),
     "smgpu_debug_propose": (C.c_int, [C.c_void_p]),

@@ -95,7 +95,7 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "faceAngleConstraint", "minEdgeLength", "totalMinFreeze", "minAngle", "maxAngle",
                                "layerMaxBlendingFraction", "layerEdgeLength", "layerExpansionRatio", "minLayers",
                                "maxLayers", "layerPatches", "smoothingPatches", "internalSmoothingBlendingFraction",
-                               "relTol", "writeInterval", "case", "writeFormat", "device"};
+                               "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -106,6 +106,7 @@ Options parseArgs(int argc, char** argv) {
             std::puts("Usage: smoothMesh [-case dir] [-parallel] [-time t] [-centroidalIters n] [-relTol x] [-minEdgeLength x]\n"
                       "       [-maxStepLength x] [-relStepFrac x] [-totalMinFreeze b] [-edgeAngleConstraint b] [-faceAngleConstraint b]\n"
                       "       [-minAngle deg] [-maxAngle deg] [-writeInterval n] [-writeFormat ascii|binary] [-device n]\n"
+                      "       [-checkQuality b]   (mesh quality report of the initial and the final mesh, serial runs only)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -497,6 +498,10 @@ int main(int argc, char** argv) {
     auto secondsSince = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
     const Options opt = parseArgs(argc, argv);
     const std::string& cd = opt.caseDir;
+    const bool checkQuality = opt.getB("checkQuality", false);
+    if (checkQuality && opt.parallel)
+        fatal("-checkQuality is not available with -parallel: the quality report does not exchange the neighbour cell centres across "
+              "processor patches (run it on the reconstructed case)");
     // SMOOTHMESH_TIMELINE=1: where this process's wall time goes, one stderr line per stage (seconds since main started)
     const bool timeline = std::getenv("SMOOTHMESH_TIMELINE") && std::atoi(std::getenv("SMOOTHMESH_TIMELINE")) > 0;
     auto mark = [&](const char* what) { if (timeline) std::fprintf(stderr, "[smoothMesh %8.3f s] %s\n", secondsSince(t0), what); };
@@ -788,6 +793,28 @@ int main(int argc, char** argv) {
     nInternalTot = g_comm.reduceSum(nInternalTot);
     OUT("Mesh includes a total of %ld points:\n  - %ld internal (non-boundary) points\n  - %ld boundary points\n", nPointsTot, nInternalTot, nPointsTot - nInternalTot);
     OUT("Mesh minimum edge length = %g\nMesh maximum edge length = %g\n\n", meshMinEdgeLength, meshMaxEdgeLength);
+
+    // -checkQuality: the quality report (include/smgpu.h, smgpu_mesh_quality) of the mesh the run starts from and of the one it writes
+    auto reportQuality = [&](const char* which) {
+        smgpu_quality q;
+        check(smgpu_mesh_quality(R[0].h, nullptr, &q), "smgpu_mesh_quality");
+        OUT("Mesh quality (%s):\n", which);
+        OUT("    cells %lld faces %lld internalFaces %lld\n", (long long)q.nCells, (long long)q.nFaces, (long long)q.nInternalFaces);
+        OUT("    cellVolume min %.9g max %.9g total %.9g nonPositive %lld minCell %d\n", q.minVolume, q.maxVolume, q.totalVolume,
+            (long long)q.nNonPositiveVolume, (int)q.minVolumeCell);
+        OUT("    faceArea min %.9g max %.9g zero %lld\n", q.minFaceArea, q.maxFaceArea, (long long)q.nZeroAreaFaces);
+        OUT("    nonOrthogonality max %.9g average %.9g severe %lld error %lld maxFace %d\n", q.maxNonOrth, q.avgNonOrth,
+            (long long)q.nSevereNonOrth, (long long)q.nErrorNonOrth, (int)q.maxNonOrthFace);
+        OUT("    skewness max %.9g severe %lld maxFace %d\n", q.maxSkewness, (long long)q.nSkewFaces, (int)q.maxSkewFace);
+        OUT("    facePyramids wrongOriented %lld\n", (long long)q.nWrongOrientedFaces);
+        OUT("    cellOpenness max %.9g open %lld\n", q.maxOpenness, (long long)q.nOpenCells);
+        OUT("    cellAspectRatio max %.9g high %lld\n", q.maxAspectRatio, (long long)q.nHighAspectCells);
+        if (q.nNonPositiveVolume > 0 || q.nWrongOrientedFaces > 0)
+            OUT("    ***Mesh has %lld non-positive volume cells and %lld wrongly oriented faces\n", (long long)q.nNonPositiveVolume,
+                (long long)q.nWrongOrientedFaces);
+        OUTS("");
+    };
+    if (checkQuality) reportQuality("initial mesh");
 
     for (Rank& K : R) check(smgpu_set_params(K.h, &prm), "smgpu_set_params");
     std::vector<std::vector<int64_t>> sharedGlobalOf;   // every rank's shared points (global ids, ascending): the set-up syncs
@@ -1222,6 +1249,8 @@ int main(int argc, char** argv) {
         if (stopIteration || ((i % writeInterval) == 0 && i > 1)) writeMesh(timeValue);
         if (done == 0) break;
     }
+
+    if (checkQuality) reportQuality("final mesh");
 
     // Near-tie census (include/smgpu.h): the engine's acos may differ from the reference's in the last bit, so only an angle
     // comparison with sides a few ulp apart could have been decided the other way by the reference -- say so when there was one

@@ -1,0 +1,275 @@
+// kernels_quality.hpp -- mesh quality report of the current points (smgpu_mesh_quality / smgpu_quality_field, include/smgpu.h).
+//
+// Inputs are the loop's own geometry: face centres / area vectors by face id and cell centres by cell id, as the geometry
+// kernel publishes them for ptsCur (runGeometry with writeFaces).  Definitions: DESIGN.md "Mesh quality" (after OpenFOAM
+// primitiveMeshCheck).  Three passes, no float atomics: a face pass (one lane per face, polyMesh order) and a cell pass (one lane
+// per cell) leave one partial record per workgroup; k_quality_final reduces the two slabs in a fixed order into one
+// smgpu_quality.  Every reduction is a fixed xor butterfly inside the wave, the waves of a workgroup in wave order, and the
+// workgroup records in a fixed stride order: the report is bitwise repeatable.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/smgpu.h"
+#include "kernels.hpp"
+#include "vec3.hpp"
+#include "smacos.hpp"
+
+namespace smgpu {
+
+constexpr int kQualityBlock = 256;
+constexpr int kQualityNoId = 0x7fffffff;   // the id of an empty max / min (lowest-id tie rule: never wins a tie)
+
+// partial record of the face pass (one per workgroup, then the final reduction's accumulator)
+struct QFace {
+    double maxNO, sumTh, maxSk, minA, maxA;
+    int maxNOId, maxSkId;
+    long long nSev, nErr, nSkew, nWrong, nZero;
+};
+// ... and of the cell pass
+struct QCell {
+    double minV, maxV, sumV, maxOpen, maxAR;
+    int minVId;
+    long long nNonPos, nOpen, nHigh;
+};
+
+__device__ __forceinline__ QFace qFaceEmpty() {
+    QFace a;
+    a.maxNO = -__builtin_inf(); a.sumTh = 0.0; a.maxSk = -__builtin_inf(); a.minA = __builtin_inf(); a.maxA = -__builtin_inf();
+    a.maxNOId = kQualityNoId; a.maxSkId = kQualityNoId;
+    a.nSev = a.nErr = a.nSkew = a.nWrong = a.nZero = 0;
+    return a;
+}
+__device__ __forceinline__ QCell qCellEmpty() {
+    QCell a;
+    a.minV = __builtin_inf(); a.maxV = -__builtin_inf(); a.sumV = 0.0; a.maxOpen = -__builtin_inf(); a.maxAR = -__builtin_inf();
+    a.minVId = kQualityNoId;
+    a.nNonPos = a.nOpen = a.nHigh = 0;
+    return a;
+}
+// larger value wins, a tie goes to the lower id (an order-independent rule: the result does not depend on the reduction tree)
+__device__ __forceinline__ void qMaxId(double& v, int& id, double ov, int oid) {
+    if (ov > v || (ov == v && oid < id)) { v = ov; id = oid; }
+}
+__device__ __forceinline__ void qMinId(double& v, int& id, double ov, int oid) {
+    if (ov < v || (ov == v && oid < id)) { v = ov; id = oid; }
+}
+__device__ __forceinline__ void qCombine(QFace& a, const QFace& b) {
+    qMaxId(a.maxNO, a.maxNOId, b.maxNO, b.maxNOId);
+    a.sumTh += b.sumTh;
+    qMaxId(a.maxSk, a.maxSkId, b.maxSk, b.maxSkId);
+    a.minA = fmin(a.minA, b.minA); a.maxA = fmax(a.maxA, b.maxA);
+    a.nSev += b.nSev; a.nErr += b.nErr; a.nSkew += b.nSkew; a.nWrong += b.nWrong; a.nZero += b.nZero;
+}
+__device__ __forceinline__ void qCombine(QCell& a, const QCell& b) {
+    qMinId(a.minV, a.minVId, b.minV, b.minVId);
+    a.maxV = fmax(a.maxV, b.maxV);
+    a.sumV += b.sumV;
+    a.maxOpen = fmax(a.maxOpen, b.maxOpen); a.maxAR = fmax(a.maxAR, b.maxAR);
+    a.nNonPos += b.nNonPos; a.nOpen += b.nOpen; a.nHigh += b.nHigh;
+}
+__device__ __forceinline__ QFace qShfl(const QFace& a, int o) {
+    QFace r;
+    r.maxNO = __shfl_xor(a.maxNO, o, 64); r.sumTh = __shfl_xor(a.sumTh, o, 64); r.maxSk = __shfl_xor(a.maxSk, o, 64);
+    r.minA = __shfl_xor(a.minA, o, 64); r.maxA = __shfl_xor(a.maxA, o, 64);
+    r.maxNOId = __shfl_xor(a.maxNOId, o, 64); r.maxSkId = __shfl_xor(a.maxSkId, o, 64);
+    r.nSev = __shfl_xor(a.nSev, o, 64); r.nErr = __shfl_xor(a.nErr, o, 64); r.nSkew = __shfl_xor(a.nSkew, o, 64);
+    r.nWrong = __shfl_xor(a.nWrong, o, 64); r.nZero = __shfl_xor(a.nZero, o, 64);
+    return r;
+}
+__device__ __forceinline__ QCell qShfl(const QCell& a, int o) {
+    QCell r;
+    r.minV = __shfl_xor(a.minV, o, 64); r.maxV = __shfl_xor(a.maxV, o, 64); r.sumV = __shfl_xor(a.sumV, o, 64);
+    r.maxOpen = __shfl_xor(a.maxOpen, o, 64); r.maxAR = __shfl_xor(a.maxAR, o, 64);
+    r.minVId = __shfl_xor(a.minVId, o, 64);
+    r.nNonPos = __shfl_xor(a.nNonPos, o, 64); r.nOpen = __shfl_xor(a.nOpen, o, 64); r.nHigh = __shfl_xor(a.nHigh, o, 64);
+    return r;
+}
+// workgroup reduction in a fixed order: xor butterfly in each wave (a + b and b + a are the same IEEE sum, so every lane ends
+// with the same bits), then the waves' records in wave order.  The result is valid in thread 0.
+template <class A>
+__device__ __forceinline__ A qBlockReduce(A v, A* sh /* [kQualityBlock / 64] in LDS */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const A w = qShfl(v, o);
+        qCombine(v, w);
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        v = sh[0];
+        for (int w = 1; w < kQualityBlock / 64; ++w) qCombine(v, sh[w]);
+    }
+    return v;
+}
+
+// owner / neighbour of every face from the cell -> face rows (bit 31 = the cell is the face's neighbour): the addressing the
+// engine holds on the device, so the first report uploads nothing.  Each face has one owner and at most one neighbour: plain
+// stores, no race.
+__global__ void __launch_bounds__(kQualityBlock) k_quality_owners(MeshView m, int* __restrict__ own, int* __restrict__ nei) {
+    const int c = blockIdx.x * kQualityBlock + threadIdx.x;
+    if (c >= m.nCells) return;
+    for (int j = m.cfOff[c]; j < m.cfOff[c + 1]; ++j) {
+        const int e = m.cfVal[j];
+        const int f = e & 0x7fffffff;
+        if (e < 0) { if (f < m.nInternalFaces) nei[f] = c; }
+        else if (f < m.nFaces) own[f] = c;
+    }
+}
+
+struct QualityThresholds { double cosNonOrth, skew, closed, aspect; };
+
+constexpr double kRadToDeg = 180.0 / SMGPU_PI;
+
+// face pass: non-orthogonality (internal faces), skewness, both face pyramids, face area of face f.  outNO / outSkew: optional
+// per-face fields (smgpu_quality_field), NULL for the report.
+// Each workgroup takes kQualityPer * kQualityBlock consecutive elements, lane t the elements t, t + 256, ... (coalesced), so that
+// the final reduction folds kQualityPer times fewer records (one workgroup folding one record per 256 elements took 0.7 ms on the
+// 10 M-cell mesh: profiles/quality/README.md)
+constexpr int kQualityPer = 8;
+__host__ __device__ constexpr int qualityGrid(int n) { return (int)(((long long)n + kQualityPer * kQualityBlock - 1) / (kQualityPer * kQualityBlock)); }
+
+__device__ __forceinline__ void qFaceOne(const MeshView& m, const double* __restrict__ pts, const double* __restrict__ fCtr, const double* __restrict__ fArea,
+                                         const double* __restrict__ cellCtr, const int* __restrict__ own, const int* __restrict__ nei,
+                                         const QualityThresholds& thr, int f, QFace& a, double* __restrict__ outNO, double* __restrict__ outSkew) {
+    {
+        const V3 Cf = ldv(fCtr, f), Sf = ldv(fArea, f);
+        const V3 CO = ldv(cellCtr, own[f]);
+        const bool internal = f < m.nInternalFaces;
+        const double magSf = mag(Sf);
+        a.minA = magSf; a.maxA = magSf;
+        a.nZero = (magSf <= SMGPU_VSMALL) ? 1 : 0;
+        const V3 Cpf = Cf - CO;
+        const double pO = dot(Sf, Cpf);
+        bool wrong = pO <= 0.0;
+        V3 d;
+        double theta = 0.0;
+        if (internal) {
+            const V3 CN = ldv(cellCtr, nei[f]);
+            d = CN - CO;
+            const double ortho = dot(d, Sf) / (mag(d) * magSf + SMGPU_VSMALL);
+            const double oc = fmin(fmax(ortho, -1.0), 1.0);
+            theta = smacos::acosX(oc) * kRadToDeg;
+            a.maxNO = theta; a.maxNOId = f;
+            a.sumTh = theta;
+            a.nSev = (ortho > 0.0 && ortho < thr.cosNonOrth) ? 1 : 0;
+            a.nErr = (ortho <= 0.0) ? 1 : 0;
+            const double pN = dot(Sf, CN - Cf);
+            wrong = wrong || pN <= 0.0;
+        } else {
+            const V3 n = Sf / (magSf + SMGPU_ROOTVSMALL);
+            d = dot(n, Cpf) * n;
+        }
+        a.nWrong = wrong ? 1 : 0;
+        // skewness
+        const V3 sv = Cpf - (dot(Sf, Cpf) / (dot(Sf, d) + SMGPU_ROOTVSMALL)) * d;
+        const double magSv = mag(sv);
+        const V3 sHat = sv / (magSv + SMGPU_ROOTVSMALL);
+        double fd = 0.2 * mag(d) + SMGPU_ROOTVSMALL;
+        for (int j = m.faceOff[f]; j < m.faceOff[f + 1]; ++j) fd = fmax(fd, fabs(dot(sHat, ldv(pts, m.facePts[j]) - Cf)));
+        const double skew = magSv / fd;
+        a.maxSk = skew; a.maxSkId = f;
+        a.nSkew = (skew > thr.skew) ? 1 : 0;
+        if (outNO) outNO[f] = theta;
+        if (outSkew) outSkew[f] = skew;
+    }
+}
+__global__ void __launch_bounds__(kQualityBlock) k_quality_faces(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                  const double* __restrict__ fArea, const double* __restrict__ cellCtr,
+                                                                  const int* __restrict__ own, const int* __restrict__ nei, QualityThresholds thr,
+                                                                  QFace* __restrict__ part, double* __restrict__ outNO, double* __restrict__ outSkew) {
+    __shared__ QFace sh[kQualityBlock / 64];
+    QFace a = qFaceEmpty();
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int f = base + k * kQualityBlock;
+        if (f >= m.nFaces) break;
+        QFace e = qFaceEmpty();
+        qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, thr, f, e, outNO, outSkew);
+        qCombine(a, e);
+    }
+    a = qBlockReduce(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// cell pass: signed volume, openness, aspect ratio of cell c.  Faces in the cell's geometry order (cfOff / cfVal), sign -1 on the
+// neighbour side.  outV / outOpen / outAR: optional per-cell fields, NULL for the report.
+__device__ __forceinline__ void qCellOne(const MeshView& m, const double* __restrict__ fCtr, const double* __restrict__ fArea, const QualityThresholds& thr,
+                                         int c, QCell& a, double* __restrict__ outV, double* __restrict__ outOpen, double* __restrict__ outAR) {
+    {
+        const int b = m.cfOff[c], e = m.cfOff[c + 1];
+        V3 cEst = v3(0, 0, 0);
+        for (int j = b; j < e; ++j) cEst = cEst + ldv(fCtr, m.cfVal[j] & 0x7fffffff);
+        cEst = cEst / (double)(e - b);
+        double pyr = 0.0;
+        V3 sumS = v3(0, 0, 0), M = v3(0, 0, 0);
+        for (int j = b; j < e; ++j) {
+            const int ev = m.cfVal[j];
+            const int f = ev & 0x7fffffff;
+            const V3 Sf = ldv(fArea, f);
+            double p = dot(Sf, ldv(fCtr, f) - cEst);
+            if (ev < 0) { p = -p; sumS = sumS - Sf; }
+            else sumS = sumS + Sf;
+            pyr += p;
+            M = M + v3(fabs(Sf.x), fabs(Sf.y), fabs(Sf.z));
+        }
+        const double V = (1.0 / 3.0) * pyr;
+        const double open = fmax(fmax(fabs(sumS.x) / (M.x + SMGPU_ROOTVSMALL), fabs(sumS.y) / (M.y + SMGPU_ROOTVSMALL)),
+                                 fabs(sumS.z) / (M.z + SMGPU_ROOTVSMALL));
+        const double maxM = fmax(fmax(M.x, M.y), M.z), minM = fmin(fmin(M.x, M.y), M.z);
+        const double ar = fmax(maxM / (minM + SMGPU_ROOTVSMALL),
+                               ((1.0 / 6.0) * ((M.x + M.y) + M.z)) / pow(fmax(V, SMGPU_ROOTVSMALL), 2.0 / 3.0));
+        a.minV = V; a.minVId = c; a.maxV = V; a.sumV = V;
+        a.nNonPos = (V <= SMGPU_VSMALL) ? 1 : 0;
+        a.maxOpen = open; a.nOpen = (open > thr.closed) ? 1 : 0;
+        a.maxAR = ar; a.nHigh = (ar > thr.aspect) ? 1 : 0;
+        if (outV) outV[c] = V;
+        if (outOpen) outOpen[c] = open;
+        if (outAR) outAR[c] = ar;
+    }
+}
+__global__ void __launch_bounds__(kQualityBlock) k_quality_cells(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea,
+                                                                  QualityThresholds thr, QCell* __restrict__ part, double* __restrict__ outV,
+                                                                  double* __restrict__ outOpen, double* __restrict__ outAR) {
+    __shared__ QCell sh[kQualityBlock / 64];
+    QCell a = qCellEmpty();
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int c = base + k * kQualityBlock;
+        if (c >= m.nCells) break;
+        QCell e = qCellEmpty();
+        qCellOne(m, fCtr, fArea, thr, c, e, outV, outOpen, outAR);
+        qCombine(a, e);
+    }
+    a = qBlockReduce(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// one workgroup: thread t folds the records t, t + 256, ... in that order, then the workgroup reduction -> the report
+__global__ void __launch_bounds__(kQualityBlock) k_quality_final(const QFace* __restrict__ fPart, int nFB, const QCell* __restrict__ cPart, int nCB,
+                                                                  int nCells, int nFaces, int nInternalFaces, smgpu_quality* __restrict__ out) {
+    __shared__ QFace shF[kQualityBlock / 64];
+    __shared__ QCell shC[kQualityBlock / 64];
+    QFace a = qFaceEmpty();
+    for (int i = threadIdx.x; i < nFB; i += kQualityBlock) qCombine(a, fPart[i]);
+    QCell b = qCellEmpty();
+    for (int i = threadIdx.x; i < nCB; i += kQualityBlock) qCombine(b, cPart[i]);
+    a = qBlockReduce(a, shF);
+    b = qBlockReduce(b, shC);
+    if (threadIdx.x != 0) return;
+    smgpu_quality q;
+    q.nCells = nCells; q.nFaces = nFaces; q.nInternalFaces = nInternalFaces;
+    const bool anyCell = nCells > 0, anyFace = nFaces > 0, anyInternal = nInternalFaces > 0;
+    q.minVolume = anyCell ? b.minV : 0.0; q.maxVolume = anyCell ? b.maxV : 0.0; q.totalVolume = b.sumV;
+    q.nNonPositiveVolume = b.nNonPos; q.minVolumeCell = anyCell ? b.minVId : -1;
+    q.minFaceArea = anyFace ? a.minA : 0.0; q.maxFaceArea = anyFace ? a.maxA : 0.0; q.nZeroAreaFaces = a.nZero;
+    q.maxNonOrth = anyInternal ? a.maxNO : 0.0; q.avgNonOrth = anyInternal ? a.sumTh / (double)nInternalFaces : 0.0;
+    q.nSevereNonOrth = a.nSev; q.nErrorNonOrth = a.nErr; q.maxNonOrthFace = anyInternal ? a.maxNOId : -1;
+    q.maxSkewness = anyFace ? a.maxSk : 0.0; q.nSkewFaces = a.nSkew; q.maxSkewFace = anyFace ? a.maxSkId : -1;
+    q.nWrongOrientedFaces = a.nWrong;
+    q.maxOpenness = anyCell ? b.maxOpen : 0.0; q.nOpenCells = b.nOpen;
+    q.maxAspectRatio = anyCell ? b.maxAR : 0.0; q.nHighAspectCells = b.nHigh;
+    *out = q;
+}
+
+}  // namespace smgpu

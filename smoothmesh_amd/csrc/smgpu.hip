@@ -19,6 +19,7 @@
 #include "kernels_walk.hpp"
 #include "kernels_filter.hpp"
 #include "kernels_boundary.hpp"
+#include "kernels_quality.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"
@@ -220,6 +221,12 @@ struct smgpu_handle {
     size_t edgeLds = 0;
     bool eaCoop = true;        // wave-cooperative edge-angle kernel (SMGPU_EDGE_ANGLE=faithful selects the per-angle acos form)
     int eaMaxEntries = 0;
+    // mesh quality report (smgpu_mesh_quality, kernels_quality.hpp): allocated by the first report, outside `allocs` (deviceBytes
+    // stays what the loop holds)
+    int *qOwn = nullptr, *qNei = nullptr;
+    QFace* qFacePart = nullptr;
+    QCell* qCellPart = nullptr;
+    smgpu_quality* qOut = nullptr;
 };
 
 static int envInt(const char* name, int def) {
@@ -1041,6 +1048,7 @@ int smgpu_destroy(smgpu_handle* h) {
     if (h->gtDev.valid)      // (a create that failed before the handle took the device-built tile tables over)
         for (const GeomTilesDev::Arr* a : {&h->gtDev.cellOrder, &h->gtDev.cellBeg, &h->gtDev.tpIds, &h->gtDev.tfIds, &h->gtDev.faceVerts, &h->gtDev.cellFaces, &h->gtDev.meta})
             if (a->p) (void)hipFree(a->p);
+    for (void* p : {(void*)h->qOwn, (void*)h->qNei, (void*)h->qFacePart, (void*)h->qCellPart, (void*)h->qOut}) if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
     for (hipEvent_t e : h->evWalkLag) if (e) (void)hipEventDestroy(e);
@@ -3165,6 +3173,104 @@ int smgpu_debug_find_line(smgpu_handle* h, int32_t n, const double* segments, do
     (void)hipFree(dSeg); (void)hipFree(dOut); (void)hipFree(dHit);
     if (e != hipSuccess) return fail(std::string("smgpu_debug_find_line: ") + hipGetErrorString(e));
     return 0;
+}
+
+// ---- mesh quality report (kernels_quality.hpp, DESIGN.md "Mesh quality") ---------------------------------------------------
+// the report's device memory, on the first call: owner / neighbour by face (derived on the device from the cell -> face rows),
+// the two partial slabs and the report
+static int qualityEnsure(smgpu_handle* h) {
+    if (h->qOut) return 0;
+    const MeshView& m = h->mv;
+    const size_t nFB = (size_t)std::max(1, qualityGrid(m.nFaces)), nCB = (size_t)std::max(1, qualityGrid(m.nCells));
+    hipError_t e = hipMalloc((void**)&h->qOwn, sizeof(int) * (size_t)std::max(1, m.nFaces));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qNei, sizeof(int) * (size_t)std::max(1, m.nInternalFaces));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qFacePart, sizeof(QFace) * nFB);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qCellPart, sizeof(QCell) * nCB);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qOut, sizeof(smgpu_quality));
+    if (e != hipSuccess) {
+        for (void** p : {(void**)&h->qOwn, (void**)&h->qNei, (void**)&h->qFacePart, (void**)&h->qCellPart, (void**)&h->qOut})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        return fail(std::string("mesh quality: device memory for the report: ") + hipGetErrorString(e));
+    }
+    HIP_OK(hipMemsetAsync(h->qOwn, 0, sizeof(int) * (size_t)std::max(1, m.nFaces), h->stream));   // (every face has an owner row; no
+    HIP_OK(hipMemsetAsync(h->qNei, 0, sizeof(int) * (size_t)std::max(1, m.nInternalFaces), h->stream));   //  id is left undefined)
+    if (m.nCells > 0) hipLaunchKernelGGL(k_quality_owners, dim3(gridFor(m.nCells)), dim3(kQualityBlock), 0, h->stream, m, h->qOwn, h->qNei);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// geometry of the current points (the loop's own kernel, publishing face values by id as for smgpu_debug_propose), then the face
+// pass, the cell pass and the final reduction into h->qOut.  The out* fields are optional per-element outputs.  The geometry
+// launch is not counted in the engine's statistics (launch counts, timing events).
+static const char* kQualityHaloRefusal = "mesh quality: not available on an engine with a halo (a sub-domain's processor faces are internal faces of "
+                                         "the global mesh, whose neighbour cell centres this report does not exchange); report on the undecomposed mesh";
+static int runQuality(smgpu_handle* h, const smgpu_quality_params* p, double* outNO, double* outSkew, double* outV, double* outOpen, double* outAR) {
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityEnsure(h)) return 1;
+    const MeshView& m = h->mv;
+    const bool timing = h->timing;
+    int64_t launches[K_COUNT];
+    std::memcpy(launches, h->launches, sizeof(launches));
+    h->timing = false;
+    h->writeFaces = true;
+    const int rcg = runGeometry(h);
+    h->writeFaces = false;
+    h->timing = timing;
+    std::memcpy(h->launches, launches, sizeof(launches));
+    if (rcg) return 1;
+    const smgpu_quality_params prm = p ? *p : smgpu_quality_params{70.0, 4.0, 1e-6, 1000.0};
+    const QualityThresholds thr{std::cos(prm.nonOrthThreshold * (SMGPU_PI / 180.0)), prm.skewThreshold, prm.closedThreshold, prm.aspectThreshold};
+    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+    const State& s = h->st;
+    if (nFB > 0)
+        hipLaunchKernelGGL(k_quality_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qOwn, h->qNei, thr,
+                           h->qFacePart, outNO, outSkew);
+    if (nCB > 0)
+        hipLaunchKernelGGL(k_quality_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qCellPart, outV, outOpen, outAR);
+    hipLaunchKernelGGL(k_quality_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qFacePart, nFB, h->qCellPart, nCB, m.nCells, m.nFaces,
+                       m.nInternalFaces, h->qOut);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_mesh_quality(smgpu_handle* h, const smgpu_quality_params* p, smgpu_quality* out) {
+    if (!h || !out) return fail("null argument");
+    if (runQuality(h, p, nullptr, nullptr, nullptr, nullptr, nullptr)) return 1;
+    HIP_OK(hipMemcpyAsync(out, h->qOut, sizeof(smgpu_quality), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
+    if (!h || !name || !n) return fail("null argument");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    const std::string s(name);
+    const int64_t C = h->mv.nCells, F = h->mv.nFaces;
+    int64_t cnt = 0;
+    int which = -1;
+    if (s == "faceNonOrthogonality") { which = 0; cnt = F; }
+    else if (s == "faceSkewness") { which = 1; cnt = F; }
+    else if (s == "cellVolume") { which = 2; cnt = C; }
+    else if (s == "cellOpenness") { which = 3; cnt = C; }
+    else if (s == "cellAspectRatio") { which = 4; cnt = C; }
+    else return fail("unknown quality field " + s + " (cellVolume, cellOpenness, cellAspectRatio, faceNonOrthogonality, faceSkewness)");
+    *n = cnt;
+    if (!out) return 0;
+    HIP_OK(hipSetDevice(h->device));
+    double* buf = nullptr;   // transient: one field's worth for this call only
+    HIP_OK(hipMalloc((void**)&buf, sizeof(double) * (size_t)std::max<int64_t>(1, cnt)));
+    double* o[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    o[which] = buf;
+    int rc = runQuality(h, nullptr, o[0], o[1], o[2], o[3], o[4]);
+    if (rc == 0 && cnt > 0) {
+        const hipError_t e = hipMemcpyAsync(out, buf, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream);
+        if (e != hipSuccess) rc = fail(std::string("smgpu_quality_field: ") + hipGetErrorString(e));
+    }
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (rc == 0 && es != hipSuccess) rc = fail(std::string("smgpu_quality_field: ") + hipGetErrorString(es));
+    (void)hipFree(buf);
+    return rc;
 }
 
 // ---- debug / parity access -------------------------------------------------------------------

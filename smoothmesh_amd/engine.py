@@ -51,6 +51,38 @@ class BoundaryParams:
     isFeatureEdgePointIO: object = None
 
 
+@dataclass
+class MeshQuality:
+    """smgpu_mesh_quality's report of the engine's current points (include/smgpu.h; definitions: DESIGN.md "Mesh quality")."""
+    nCells: int
+    nFaces: int
+    nInternalFaces: int
+    minVolume: float
+    maxVolume: float
+    totalVolume: float
+    nNonPositiveVolume: int
+    minVolumeCell: int
+    minFaceArea: float
+    maxFaceArea: float
+    nZeroAreaFaces: int
+    maxNonOrth: float
+    avgNonOrth: float
+    nSevereNonOrth: int
+    nErrorNonOrth: int
+    maxNonOrthFace: int
+    maxSkewness: float
+    nSkewFaces: int
+    maxSkewFace: int
+    nWrongOrientedFaces: int
+    maxOpenness: float
+    nOpenCells: int
+    maxAspectRatio: float
+    nHighAspectCells: int
+
+
+QUALITY_FIELDS = ("cellVolume", "cellOpenness", "cellAspectRatio", "faceNonOrthogonality", "faceSkewness")
+
+
 def patch_arrays(mesh: PolyMesh, layerPatches):
     """(start, size, kind, isLayer) of mesh.patches; kind 0 ordinary / 1 processor / 2 empty.  Selection as
     polyBoundaryMesh::patchSet (SM.C:1442-1471): a plain word matches a patch name, a quoted string is a regex."""
@@ -381,6 +413,23 @@ class SmoothEngine:
         pts = np.ascontiguousarray(pts, dtype=np.float64)
         assert pts.shape == (self.nPoints, 3)
         self._check(self._lib.smgpu_set_points(self._h, _p(pts, _ffi.c_f64p)))
+
+    # -- mesh quality --------------------------------------------------------------------------
+    def mesh_quality(self, nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0) -> MeshQuality:
+        """Quality report of the current points, computed on the device (include/smgpu.h, smgpu_mesh_quality).  Does not change
+        the points or the state of the loop; refused on an engine with a halo."""
+        p = _ffi.QualityParams(nonOrthThreshold, skewThreshold, closedThreshold, aspectThreshold)
+        q = _ffi.Quality()
+        self._check(self._lib.smgpu_mesh_quality(self._h, C.byref(p), C.byref(q)))
+        return MeshQuality(**{n: getattr(q, n) for n, _ in q._fields_})
+
+    def quality_field(self, name) -> np.ndarray:
+        """Per-element quality field in polyMesh order: one of QUALITY_FIELDS (non-orthogonality in degrees, 0 on boundary faces)."""
+        n = C.c_int64()
+        self._check(self._lib.smgpu_quality_field(self._h, name.encode(), None, C.byref(n)))
+        out = np.empty(n.value, np.float64)
+        self._check(self._lib.smgpu_quality_field(self._h, name.encode(), _p(out, _ffi.c_f64p), C.byref(n)))
+        return out
 
     # -- timing --------------------------------------------------------------------------------
     def enable_timing(self, on=True):
