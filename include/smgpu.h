@@ -167,6 +167,43 @@ int smgpu_mesh_quality(smgpu_handle* h, const smgpu_quality_params* p, smgpu_qua
  * (degrees, 0 on boundary faces), "faceSkewness" [nFaces].  out == NULL: size only (*n). */
 int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t* n);
 
+/* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
+ * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):
+ *   1. smgpu_quality_coupled_pack: the geometry of the current points (the loop's own launch, uncounted), then the owner cell
+ *      centre of every processor face, patch by patch in `c`'s order, 3 doubles per face, into the DEVICE buffer sendCc.
+ *      Returns once sendCc is written.  Face i of patch r->o pairs with face i of patch o->r (decomposePar's convention).
+ *   2. the host fills recvCc (device, same layout as sendCc): for each patch r->o, the neighbour o's sendCc of its patch o->r.
+ *   3. smgpu_quality_coupled_report / _field on the geometry of step 1 (refused when the points may have moved since: a pack
+ *      must follow smgpu_iterate, smgpu_iter_begin, smgpu_set_points, smgpu_set_foam_variant).
+ * A processor face takes the internal-face definitions with C_N from recvCc.  The record counts it only on the side with
+ * myRank < neighbRank, there as an internal face; fields carry its non-orthogonality and skewness on both sides.  Ids in the
+ * record are local; combine the records of all ranks as DESIGN.md 10.4 says (smoothmesh_amd/quality.py combine_quality).
+ * Refused: two patches to the same neighbour, a patch to myRank, patches outside the boundary faces or overlapping. */
+typedef struct smgpu_quality_coupling {
+    int32_t myRank, nPatches;          /* processor patches of this sub-domain, boundary-file order              */
+    const int32_t* patchStart;         /* [nPatches] first face                                                   */
+    const int32_t* patchSize;          /* [nPatches]                                                              */
+    const int32_t* neighbRank;         /* [nPatches]                                                              */
+} smgpu_quality_coupling;
+/* smgpu_quality with sumNonOrth (Σθ over the counted internal faces) in place of the average; nFaces / nInternalFaces after
+ * the counted-once rule; ids local (-1 where this rank has no such element). */
+typedef struct smgpu_quality_part {
+    int64_t nCells, nFaces, nInternalFaces;
+    double minVolume, maxVolume, totalVolume;  int64_t nNonPositiveVolume;  int32_t minVolumeCell;
+    double minFaceArea, maxFaceArea;           int64_t nZeroAreaFaces;
+    double maxNonOrth, sumNonOrth;             int64_t nSevereNonOrth, nErrorNonOrth;  int32_t maxNonOrthFace;
+    double maxSkewness;                        int64_t nSkewFaces;  int32_t maxSkewFace;
+    int64_t nWrongOrientedFaces;
+    double maxOpenness;                        int64_t nOpenCells;
+    double maxAspectRatio;                     int64_t nHighAspectCells;
+} smgpu_quality_part;
+/* *nProcFaces (may be NULL) = the number of processor faces, i.e. sendCc / recvCc hold 3 * *nProcFaces doubles.  sendCc may be
+ * NULL only when that number is 0. */
+int smgpu_quality_coupled_pack(smgpu_handle* h, const smgpu_quality_coupling* c, void* sendCc, int64_t* nProcFaces);
+int smgpu_quality_coupled_report(smgpu_handle* h, const smgpu_quality_params* p, const void* recvCc, smgpu_quality_part* out);
+/* names and sizes as smgpu_quality_field */
+int smgpu_quality_coupled_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n);
+
 /* Timing: when enabled every kernel launch is bracketed by hipEvents on the handle's stream. */
 int smgpu_enable_timing(smgpu_handle* h, int32_t on);
 int smgpu_get_counters(smgpu_handle* h, smgpu_counters* out);

@@ -109,6 +109,15 @@ class Quality(C.Structure):
     ]
 
 
+class QualityCoupling(C.Structure):
+    _fields_ = [("myRank", C.c_int32), ("nPatches", C.c_int32), ("patchStart", c_i32p), ("patchSize", c_i32p), ("neighbRank", c_i32p)]
+
+
+class QualityPart(C.Structure):
+    """smgpu_quality_part: Quality with sumNonOrth in place of avgNonOrth"""
+    _fields_ = [("sumNonOrth" if n == "avgNonOrth" else n, t) for n, t in Quality._fields_]
+
+
 # every symbol include/smgpu.h declares: (restype, argtypes)
 SYMBOLS = {
     "smgpu_last_error": (C.c_char_p, []),
@@ -161,6 +170,9 @@ SYMBOLS = {
     "smgpu_iter_end": (C.c_int, [C.c_void_p]),
     "smgpu_mesh_quality": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.POINTER(Quality)]),
     "smgpu_quality_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
+    "smgpu_quality_coupled_pack": (C.c_int, [C.c_void_p, C.POINTER(QualityCoupling), C.c_void_p, C.POINTER(C.c_int64)]),
+    "smgpu_quality_coupled_report": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(QualityPart)]),
+    "smgpu_quality_coupled_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_addressing": (C.c_int, [C.c_void_p, C.c_char_p, c_i32p, c_i32p, C.POINTER(C.c_int64)]),
     "smgpu_debug_propose": (C.c_int, [C.c_void_p]),

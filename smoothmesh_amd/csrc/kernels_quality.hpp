@@ -1,4 +1,5 @@
-// kernels_quality.hpp -- mesh quality report of the current points (smgpu_mesh_quality / smgpu_quality_field, include/smgpu.h).
+// kernels_quality.hpp -- mesh quality report of the current points (smgpu_mesh_quality / smgpu_quality_field and, for a sub-domain
+// of a decomposed mesh, smgpu_quality_coupled_*: include/smgpu.h).
 //
 // Inputs are the loop's own geometry: face centres / area vectors by face id and cell centres by cell id, as the geometry
 // kernel publishes them for ptsCur (runGeometry with writeFaces).  Definitions: DESIGN.md "Mesh quality" (after OpenFOAM
@@ -129,50 +130,53 @@ constexpr double kRadToDeg = 180.0 / SMGPU_PI;
 constexpr int kQualityPer = 8;
 __host__ __device__ constexpr int qualityGrid(int n) { return (int)(((long long)n + kQualityPer * kQualityBlock - 1) / (kQualityPer * kQualityBlock)); }
 
+// one face with owner centre CO and, where `internal`, neighbour centre CN (the internal-face definitions; a processor face of a
+// decomposed mesh takes them with CN from the neighbour rank: k_quality_faces_coupled)
+__device__ __forceinline__ void qFaceCore(const MeshView& m, const double* __restrict__ pts, const V3 Cf, const V3 Sf, const V3 CO, bool internal,
+                                          const V3 CN, const QualityThresholds& thr, int f, QFace& a, double* __restrict__ outNO,
+                                          double* __restrict__ outSkew) {
+    const double magSf = mag(Sf);
+    a.minA = magSf; a.maxA = magSf;
+    a.nZero = (magSf <= SMGPU_VSMALL) ? 1 : 0;
+    const V3 Cpf = Cf - CO;
+    const double pO = dot(Sf, Cpf);
+    bool wrong = pO <= 0.0;
+    V3 d;
+    double theta = 0.0;
+    if (internal) {
+        d = CN - CO;
+        const double ortho = dot(d, Sf) / (mag(d) * magSf + SMGPU_VSMALL);
+        const double oc = fmin(fmax(ortho, -1.0), 1.0);
+        theta = smacos::acosX(oc) * kRadToDeg;
+        a.maxNO = theta; a.maxNOId = f;
+        a.sumTh = theta;
+        a.nSev = (ortho > 0.0 && ortho < thr.cosNonOrth) ? 1 : 0;
+        a.nErr = (ortho <= 0.0) ? 1 : 0;
+        const double pN = dot(Sf, CN - Cf);
+        wrong = wrong || pN <= 0.0;
+    } else {
+        const V3 n = Sf / (magSf + SMGPU_ROOTVSMALL);
+        d = dot(n, Cpf) * n;
+    }
+    a.nWrong = wrong ? 1 : 0;
+    // skewness
+    const V3 sv = Cpf - (dot(Sf, Cpf) / (dot(Sf, d) + SMGPU_ROOTVSMALL)) * d;
+    const double magSv = mag(sv);
+    const V3 sHat = sv / (magSv + SMGPU_ROOTVSMALL);
+    double fd = 0.2 * mag(d) + SMGPU_ROOTVSMALL;
+    for (int j = m.faceOff[f]; j < m.faceOff[f + 1]; ++j) fd = fmax(fd, fabs(dot(sHat, ldv(pts, m.facePts[j]) - Cf)));
+    const double skew = magSv / fd;
+    a.maxSk = skew; a.maxSkId = f;
+    a.nSkew = (skew > thr.skew) ? 1 : 0;
+    if (outNO) outNO[f] = theta;
+    if (outSkew) outSkew[f] = skew;
+}
 __device__ __forceinline__ void qFaceOne(const MeshView& m, const double* __restrict__ pts, const double* __restrict__ fCtr, const double* __restrict__ fArea,
                                          const double* __restrict__ cellCtr, const int* __restrict__ own, const int* __restrict__ nei,
                                          const QualityThresholds& thr, int f, QFace& a, double* __restrict__ outNO, double* __restrict__ outSkew) {
-    {
-        const V3 Cf = ldv(fCtr, f), Sf = ldv(fArea, f);
-        const V3 CO = ldv(cellCtr, own[f]);
-        const bool internal = f < m.nInternalFaces;
-        const double magSf = mag(Sf);
-        a.minA = magSf; a.maxA = magSf;
-        a.nZero = (magSf <= SMGPU_VSMALL) ? 1 : 0;
-        const V3 Cpf = Cf - CO;
-        const double pO = dot(Sf, Cpf);
-        bool wrong = pO <= 0.0;
-        V3 d;
-        double theta = 0.0;
-        if (internal) {
-            const V3 CN = ldv(cellCtr, nei[f]);
-            d = CN - CO;
-            const double ortho = dot(d, Sf) / (mag(d) * magSf + SMGPU_VSMALL);
-            const double oc = fmin(fmax(ortho, -1.0), 1.0);
-            theta = smacos::acosX(oc) * kRadToDeg;
-            a.maxNO = theta; a.maxNOId = f;
-            a.sumTh = theta;
-            a.nSev = (ortho > 0.0 && ortho < thr.cosNonOrth) ? 1 : 0;
-            a.nErr = (ortho <= 0.0) ? 1 : 0;
-            const double pN = dot(Sf, CN - Cf);
-            wrong = wrong || pN <= 0.0;
-        } else {
-            const V3 n = Sf / (magSf + SMGPU_ROOTVSMALL);
-            d = dot(n, Cpf) * n;
-        }
-        a.nWrong = wrong ? 1 : 0;
-        // skewness
-        const V3 sv = Cpf - (dot(Sf, Cpf) / (dot(Sf, d) + SMGPU_ROOTVSMALL)) * d;
-        const double magSv = mag(sv);
-        const V3 sHat = sv / (magSv + SMGPU_ROOTVSMALL);
-        double fd = 0.2 * mag(d) + SMGPU_ROOTVSMALL;
-        for (int j = m.faceOff[f]; j < m.faceOff[f + 1]; ++j) fd = fmax(fd, fabs(dot(sHat, ldv(pts, m.facePts[j]) - Cf)));
-        const double skew = magSv / fd;
-        a.maxSk = skew; a.maxSkId = f;
-        a.nSkew = (skew > thr.skew) ? 1 : 0;
-        if (outNO) outNO[f] = theta;
-        if (outSkew) outSkew[f] = skew;
-    }
+    const bool internal = f < m.nInternalFaces;
+    const V3 CN = internal ? ldv(cellCtr, nei[f]) : v3(0, 0, 0);
+    qFaceCore(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, own[f]), internal, CN, thr, f, a, outNO, outSkew);
 }
 __global__ void __launch_bounds__(kQualityBlock) k_quality_faces(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
                                                                   const double* __restrict__ fArea, const double* __restrict__ cellCtr,
@@ -264,6 +268,76 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_final(const QFace* __
     q.nNonPositiveVolume = b.nNonPos; q.minVolumeCell = anyCell ? b.minVId : -1;
     q.minFaceArea = anyFace ? a.minA : 0.0; q.maxFaceArea = anyFace ? a.maxA : 0.0; q.nZeroAreaFaces = a.nZero;
     q.maxNonOrth = anyInternal ? a.maxNO : 0.0; q.avgNonOrth = anyInternal ? a.sumTh / (double)nInternalFaces : 0.0;
+    q.nSevereNonOrth = a.nSev; q.nErrorNonOrth = a.nErr; q.maxNonOrthFace = anyInternal ? a.maxNOId : -1;
+    q.maxSkewness = anyFace ? a.maxSk : 0.0; q.nSkewFaces = a.nSkew; q.maxSkewFace = anyFace ? a.maxSkId : -1;
+    q.nWrongOrientedFaces = a.nWrong;
+    q.maxOpenness = anyCell ? b.maxOpen : 0.0; q.nOpenCells = b.nOpen;
+    q.maxAspectRatio = anyCell ? b.maxAR : 0.0; q.nHighAspectCells = b.nHigh;
+    *out = q;
+}
+
+// ---- decomposed meshes (smgpu_quality_coupled_*, DESIGN.md "Mesh quality", 10.4) ----------------------------------------------
+// A processor face is an internal face of the global mesh: it takes the internal-face definitions with C_N = the neighbour rank's
+// cell centre, which the host has moved into recvCc (slot = the face's place in the processor patches, patch order).  It is
+// counted in the record only on the side with myRank < neighbRank; its per-face fields are written on both sides.
+constexpr int kQualitySlotMask = 0x3fffffff;
+constexpr int kQualityNotCounted = 0x40000000;   // slot flag: the neighbour rank counts this face
+
+// the owner cell centre of every processor face, in patch order: what the neighbour rank needs as its C_N
+__global__ void __launch_bounds__(kQualityBlock) k_quality_pack(const int* __restrict__ own, const double* __restrict__ cellCtr,
+                                                                 const int* __restrict__ procFace, int nProc, double* __restrict__ sendCc) {
+    const int i = blockIdx.x * kQualityBlock + threadIdx.x;
+    if (i >= nProc) return;
+    const V3 c = ldv(cellCtr, own[procFace[i]]);
+    sendCc[3 * (size_t)i] = c.x; sendCc[3 * (size_t)i + 1] = c.y; sendCc[3 * (size_t)i + 2] = c.z;
+}
+
+// k_quality_faces with processor faces: slot[f - nInternalFaces] is -1 on a physical boundary face, else the face's slot in recvCc
+// (| kQualityNotCounted on the side that does not count it)
+__global__ void __launch_bounds__(kQualityBlock) k_quality_faces_coupled(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                          const double* __restrict__ fArea, const double* __restrict__ cellCtr,
+                                                                          const int* __restrict__ own, const int* __restrict__ nei,
+                                                                          const int* __restrict__ slot, const double* __restrict__ recvCc,
+                                                                          QualityThresholds thr, QFace* __restrict__ part, double* __restrict__ outNO,
+                                                                          double* __restrict__ outSkew) {
+    __shared__ QFace sh[kQualityBlock / 64];
+    QFace a = qFaceEmpty();
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int f = base + k * kQualityBlock;
+        if (f >= m.nFaces) break;
+        QFace e = qFaceEmpty();
+        const int sl = f < m.nInternalFaces ? -1 : slot[f - m.nInternalFaces];
+        if (sl < 0) qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, thr, f, e, outNO, outSkew);
+        else {
+            qFaceCore(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, own[f]), true, ldv(recvCc, sl & kQualitySlotMask), thr, f, e, outNO, outSkew);
+            if (sl & kQualityNotCounted) e = qFaceEmpty();
+        }
+        qCombine(a, e);
+    }
+    a = qBlockReduce(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// k_quality_final for the per-rank record of a decomposed mesh: Σθ instead of the average; nFaces / nInternalFaces are the counted ones
+__global__ void __launch_bounds__(kQualityBlock) k_quality_part_final(const QFace* __restrict__ fPart, int nFB, const QCell* __restrict__ cPart, int nCB,
+                                                                       int nCells, int nFaces, int nInternalFaces, smgpu_quality_part* __restrict__ out) {
+    __shared__ QFace shF[kQualityBlock / 64];
+    __shared__ QCell shC[kQualityBlock / 64];
+    QFace a = qFaceEmpty();
+    for (int i = threadIdx.x; i < nFB; i += kQualityBlock) qCombine(a, fPart[i]);
+    QCell b = qCellEmpty();
+    for (int i = threadIdx.x; i < nCB; i += kQualityBlock) qCombine(b, cPart[i]);
+    a = qBlockReduce(a, shF);
+    b = qBlockReduce(b, shC);
+    if (threadIdx.x != 0) return;
+    smgpu_quality_part q;
+    q.nCells = nCells; q.nFaces = nFaces; q.nInternalFaces = nInternalFaces;
+    const bool anyCell = nCells > 0, anyFace = nFaces > 0, anyInternal = nInternalFaces > 0;
+    q.minVolume = anyCell ? b.minV : 0.0; q.maxVolume = anyCell ? b.maxV : 0.0; q.totalVolume = b.sumV;
+    q.nNonPositiveVolume = b.nNonPos; q.minVolumeCell = anyCell ? b.minVId : -1;
+    q.minFaceArea = anyFace ? a.minA : 0.0; q.maxFaceArea = anyFace ? a.maxA : 0.0; q.nZeroAreaFaces = a.nZero;
+    q.maxNonOrth = anyInternal ? a.maxNO : 0.0; q.sumNonOrth = a.sumTh;
     q.nSevereNonOrth = a.nSev; q.nErrorNonOrth = a.nErr; q.maxNonOrthFace = anyInternal ? a.maxNOId : -1;
     q.maxSkewness = anyFace ? a.maxSk : 0.0; q.nSkewFaces = a.nSkew; q.maxSkewFace = anyFace ? a.maxSkId : -1;
     q.nWrongOrientedFaces = a.nWrong;

@@ -227,6 +227,14 @@ struct smgpu_handle {
     QFace* qFacePart = nullptr;
     QCell* qCellPart = nullptr;
     smgpu_quality* qOut = nullptr;
+    // ... and of a sub-domain's coupled report (smgpu_quality_coupled_*): processor faces in patch order, the recvCc slot of every
+    // boundary face (-1: physical patch), the coupling they were built from, and the geometry epoch of the last pack
+    int *qProcFace = nullptr, *qSlot = nullptr;
+    int qNProc = 0, qNotCounted = 0, qCountedProc = 0;
+    std::vector<int32_t> qCoupling;
+    smgpu_quality_part* qPartOut = nullptr;
+    uint64_t qEpoch = 1, qPackEpoch = 0;   // qEpoch moves whenever the points (or the geometry variant) may have changed
+    bool iterOpen = false;                  // between smgpu_iter_begin and smgpu_iter_end
 };
 
 static int envInt(const char* name, int def) {
@@ -1048,7 +1056,9 @@ int smgpu_destroy(smgpu_handle* h) {
     if (h->gtDev.valid)      // (a create that failed before the handle took the device-built tile tables over)
         for (const GeomTilesDev::Arr* a : {&h->gtDev.cellOrder, &h->gtDev.cellBeg, &h->gtDev.tpIds, &h->gtDev.tfIds, &h->gtDev.faceVerts, &h->gtDev.cellFaces, &h->gtDev.meta})
             if (a->p) (void)hipFree(a->p);
-    for (void* p : {(void*)h->qOwn, (void*)h->qNei, (void*)h->qFacePart, (void*)h->qCellPart, (void*)h->qOut}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)h->qOwn, (void*)h->qNei, (void*)h->qFacePart, (void*)h->qCellPart, (void*)h->qOut, (void*)h->qProcFace, (void*)h->qSlot,
+                    (void*)h->qPartOut})
+        if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
     for (hipEvent_t e : h->evWalkLag) if (e) (void)hipEventDestroy(e);
@@ -1171,6 +1181,7 @@ int smgpu_set_foam_variant(smgpu_handle* h, int32_t variant) {
     if (!h) return fail("null handle");
     if (variant != SMGPU_FOAM_COM && variant != SMGPU_FOAM_ORG) return fail("smgpu_set_foam_variant: unknown variant");
     h->foamOrg = variant == SMGPU_FOAM_ORG;
+    h->qEpoch++;
     h->geomAheadDone = false;
     return 0;
 }
@@ -1828,6 +1839,7 @@ int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_sta
     if (!h) return fail("null handle");
     if (!h->prmSet) return fail("smgpu_set_params has not been called");
     if (h->haloOn) return fail("smgpu_iterate is the single-rank loop; use smgpu_iter_begin/mid/end with a halo");
+    h->qEpoch++;
     if (nIters < 0) return fail("nIters < 0");
     if (nDone) *nDone = 0;
     if (nIters == 0) return 0;
@@ -1972,6 +1984,7 @@ int smgpu_check_error(smgpu_handle* h) {
 
 int smgpu_set_points(smgpu_handle* h, const double* pts) {
     if (!h || !pts) return fail("null argument");
+    h->qEpoch++;
     HIP_OK(hipSetDevice(h->device));
     h->geomAheadDone = false;
     HIP_OK(hipMemcpyAsync(h->st.ptsCur, pts, sizeof(double) * 3 * (size_t)h->mv.nPoints, hipMemcpyHostToDevice, h->stream));
@@ -2528,6 +2541,8 @@ static int runMergedSmooth(smgpu_handle* h) {
 int smgpu_iter_begin(smgpu_handle* h) {
     if (!h || !h->haloOn) return fail("halo not configured");
     if (!h->prmSet) return fail("smgpu_set_params has not been called");
+    h->qEpoch++;
+    h->iterOpen = true;
     HIP_OK(hipSetDevice(h->device));
     if (h->pushOn && h->pushStride != (h->st.lStride > 0 ? h->st.lStride : SMGPU_HALO_L_LAYERS)) {   // the L records grew (boundary set-up)
         HIP_OK(hipStreamSynchronize(h->stream));
@@ -2681,6 +2696,7 @@ int smgpu_iter_ahead(smgpu_handle* h) {
 
 int smgpu_iter_end(smgpu_handle* h) {
     if (!h || !h->haloOn) return fail("halo not configured");
+    h->iterOpen = false;
     HIP_OK(hipSetDevice(h->device));
     const MeshView& m = h->mv;
     State s = h->st;
@@ -3203,12 +3219,10 @@ static int qualityEnsure(smgpu_handle* h) {
 // pass, the cell pass and the final reduction into h->qOut.  The out* fields are optional per-element outputs.  The geometry
 // launch is not counted in the engine's statistics (launch counts, timing events).
 static const char* kQualityHaloRefusal = "mesh quality: not available on an engine with a halo (a sub-domain's processor faces are internal faces of "
-                                         "the global mesh, whose neighbour cell centres this report does not exchange); report on the undecomposed mesh";
-static int runQuality(smgpu_handle* h, const smgpu_quality_params* p, double* outNO, double* outSkew, double* outV, double* outOpen, double* outAR) {
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityEnsure(h)) return 1;
-    const MeshView& m = h->mv;
+                                         "the global mesh, whose neighbour cell centres this report does not exchange); report on the undecomposed mesh, or use "
+                                         "smgpu_quality_coupled_pack / _report";
+// the loop's geometry launch with writeFaces, outside the engine's launch counters and timing events
+static int qualityGeometry(smgpu_handle* h) {
     const bool timing = h->timing;
     int64_t launches[K_COUNT];
     std::memcpy(launches, h->launches, sizeof(launches));
@@ -3218,9 +3232,19 @@ static int runQuality(smgpu_handle* h, const smgpu_quality_params* p, double* ou
     h->writeFaces = false;
     h->timing = timing;
     std::memcpy(h->launches, launches, sizeof(launches));
-    if (rcg) return 1;
+    return rcg;
+}
+static QualityThresholds qualityThresholds(const smgpu_quality_params* p) {
     const smgpu_quality_params prm = p ? *p : smgpu_quality_params{70.0, 4.0, 1e-6, 1000.0};
-    const QualityThresholds thr{std::cos(prm.nonOrthThreshold * (SMGPU_PI / 180.0)), prm.skewThreshold, prm.closedThreshold, prm.aspectThreshold};
+    return QualityThresholds{std::cos(prm.nonOrthThreshold * (SMGPU_PI / 180.0)), prm.skewThreshold, prm.closedThreshold, prm.aspectThreshold};
+}
+static int runQuality(smgpu_handle* h, const smgpu_quality_params* p, double* outNO, double* outSkew, double* outV, double* outOpen, double* outAR) {
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityEnsure(h)) return 1;
+    const MeshView& m = h->mv;
+    if (qualityGeometry(h)) return 1;
+    const QualityThresholds thr = qualityThresholds(p);
     const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
     const State& s = h->st;
     if (nFB > 0)
@@ -3242,9 +3266,11 @@ int smgpu_mesh_quality(smgpu_handle* h, const smgpu_quality_params* p, smgpu_qua
     return 0;
 }
 
-int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
-    if (!h || !name || !n) return fail("null argument");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
+// one per-element quality field: `run(o)` launches the passes with the outputs o[5] (faceNonOrthogonality, faceSkewness, cellVolume,
+// cellOpenness, cellAspectRatio), one of them set to a buffer allocated for this call
+extern "C++" {
+template <class Run>
+static int qualityField(smgpu_handle* h, const char* api, const char* name, double* out, int64_t* n, Run run) {
     const std::string s(name);
     const int64_t C = h->mv.nCells, F = h->mv.nFaces;
     int64_t cnt = 0;
@@ -3262,15 +3288,130 @@ int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t*
     HIP_OK(hipMalloc((void**)&buf, sizeof(double) * (size_t)std::max<int64_t>(1, cnt)));
     double* o[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     o[which] = buf;
-    int rc = runQuality(h, nullptr, o[0], o[1], o[2], o[3], o[4]);
+    int rc = run(o);
     if (rc == 0 && cnt > 0) {
         const hipError_t e = hipMemcpyAsync(out, buf, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) rc = fail(std::string("smgpu_quality_field: ") + hipGetErrorString(e));
+        if (e != hipSuccess) rc = fail(std::string(api) + ": " + hipGetErrorString(e));
     }
     const hipError_t es = hipStreamSynchronize(h->stream);
-    if (rc == 0 && es != hipSuccess) rc = fail(std::string("smgpu_quality_field: ") + hipGetErrorString(es));
+    if (rc == 0 && es != hipSuccess) rc = fail(std::string(api) + ": " + hipGetErrorString(es));
     (void)hipFree(buf);
     return rc;
+}
+}  // extern "C++"
+
+int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
+    if (!h || !name || !n) return fail("null argument");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    return qualityField(h, "smgpu_quality_field", name, out, n, [&](double** o) { return runQuality(h, nullptr, o[0], o[1], o[2], o[3], o[4]); });
+}
+
+// ---- the coupled report of a sub-domain (DESIGN.md "Mesh quality", 10.4) ----------------------------------------------------
+int smgpu_quality_coupled_pack(smgpu_handle* h, const smgpu_quality_coupling* c, void* sendCc, int64_t* nProcFaces) {
+    if (!h || !c) return fail("null argument");
+    if (h->iterOpen) return fail("smgpu_quality_coupled_pack: not between smgpu_iter_begin and smgpu_iter_end");
+    const MeshView& m = h->mv;
+    if (c->nPatches < 0 || (c->nPatches && (!c->patchStart || !c->patchSize || !c->neighbRank)))
+        return fail("smgpu_quality_coupled_pack: bad coupling description");
+    // the patches, checked: inside the boundary faces, disjoint, one per neighbour, none to this rank
+    std::vector<int32_t> key{c->myRank, c->nPatches};
+    std::vector<std::pair<int, int>> ranges;
+    std::vector<int> seen;
+    int64_t nProc = 0, notCounted = 0;
+    for (int i = 0; i < c->nPatches; ++i) {
+        const int32_t st = c->patchStart[i], sz = c->patchSize[i], o = c->neighbRank[i];
+        if (sz < 0 || st < m.nInternalFaces || (int64_t)st + sz > m.nFaces)
+            return fail("smgpu_quality_coupled_pack: processor patch " + std::to_string(i) + " is not a range of boundary faces");
+        if (o < 0 || o == c->myRank) return fail("smgpu_quality_coupled_pack: processor patch " + std::to_string(i) + " has a bad neighbour rank");
+        if (std::find(seen.begin(), seen.end(), o) != seen.end())
+            return fail("smgpu_quality_coupled_pack: two processor patches to rank " + std::to_string(o) +
+                        " (processorCyclic patches or several patches per neighbour are not supported)");
+        seen.push_back(o);
+        ranges.emplace_back(st, sz);
+        nProc += sz;
+        if (c->myRank > o) notCounted += sz;
+        key.insert(key.end(), {st, sz, o});
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); ++i)
+        if (ranges[i - 1].first + ranges[i - 1].second > ranges[i].first) return fail("smgpu_quality_coupled_pack: processor patches overlap");
+    if (nProc > 0 && !sendCc) return fail("smgpu_quality_coupled_pack: null sendCc");
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityEnsure(h)) return 1;
+    if (!h->qPartOut) HIP_OK(hipMalloc((void**)&h->qPartOut, sizeof(smgpu_quality_part)));
+    if (key != h->qCoupling) {
+        // face list and slots of this coupling (small: the boundary faces), uploaded once per coupling
+        const int nB = m.nFaces - m.nInternalFaces;
+        std::vector<int> procFace((size_t)nProc), slot((size_t)nB, -1);
+        int k = 0;
+        for (int i = 0; i < c->nPatches; ++i) {
+            const int flag = c->myRank > c->neighbRank[i] ? kQualityNotCounted : 0;
+            for (int j = 0; j < c->patchSize[i]; ++j, ++k) {
+                const int f = c->patchStart[i] + j;
+                procFace[(size_t)k] = f;
+                slot[(size_t)(f - m.nInternalFaces)] = k | flag;
+            }
+        }
+        for (void** p : {(void**)&h->qProcFace, (void**)&h->qSlot})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        h->qCoupling.clear();
+        HIP_OK(hipMalloc((void**)&h->qProcFace, sizeof(int) * (size_t)std::max<int64_t>(1, nProc)));
+        HIP_OK(hipMalloc((void**)&h->qSlot, sizeof(int) * (size_t)std::max(1, nB)));
+        if (nProc) HIP_OK(hipMemcpyAsync(h->qProcFace, procFace.data(), sizeof(int) * (size_t)nProc, hipMemcpyHostToDevice, h->stream));
+        if (nB) HIP_OK(hipMemcpyAsync(h->qSlot, slot.data(), sizeof(int) * (size_t)nB, hipMemcpyHostToDevice, h->stream));
+        HIP_OK(hipStreamSynchronize(h->stream));   // (the host vectors go out of scope)
+        h->qCoupling = key;
+        h->qNProc = (int)nProc;
+        h->qNotCounted = (int)notCounted;
+        h->qCountedProc = (int)(nProc - notCounted);
+    }
+    if (qualityGeometry(h)) return 1;
+    if (h->qNProc > 0)
+        hipLaunchKernelGGL(k_quality_pack, dim3(gridFor(h->qNProc)), dim3(kQualityBlock), 0, h->stream, h->qOwn, h->st.cellCtr, h->qProcFace, h->qNProc,
+                           (double*)sendCc);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(h->stream));       // sendCc is the host's to move
+    h->qPackEpoch = h->qEpoch;
+    if (nProcFaces) *nProcFaces = h->qNProc;
+    return 0;
+}
+
+// the face pass with processor faces, the cell pass and the per-rank record into h->qPartOut, on the geometry of the last pack
+static int runQualityCoupled(smgpu_handle* h, const char* api, const smgpu_quality_params* p, const void* recvCc, double* outNO, double* outSkew,
+                             double* outV, double* outOpen, double* outAR) {
+    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
+    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
+        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
+    if (h->qNProc > 0 && !recvCc) return fail(std::string(api) + ": null recvCc");
+    HIP_OK(hipSetDevice(h->device));
+    const MeshView& m = h->mv;
+    const QualityThresholds thr = qualityThresholds(p);
+    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+    const State& s = h->st;
+    if (nFB > 0)
+        hipLaunchKernelGGL(k_quality_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qOwn, h->qNei,
+                           h->qSlot, (const double*)recvCc, thr, h->qFacePart, outNO, outSkew);
+    if (nCB > 0)
+        hipLaunchKernelGGL(k_quality_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qCellPart, outV, outOpen, outAR);
+    hipLaunchKernelGGL(k_quality_part_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qFacePart, nFB, h->qCellPart, nCB, m.nCells,
+                       m.nFaces - h->qNotCounted, m.nInternalFaces + h->qCountedProc, h->qPartOut);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_quality_coupled_report(smgpu_handle* h, const smgpu_quality_params* p, const void* recvCc, smgpu_quality_part* out) {
+    if (!h || !out) return fail("null argument");
+    if (runQualityCoupled(h, "smgpu_quality_coupled_report", p, recvCc, nullptr, nullptr, nullptr, nullptr, nullptr)) return 1;
+    HIP_OK(hipMemcpyAsync(out, h->qPartOut, sizeof(smgpu_quality_part), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int smgpu_quality_coupled_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n) {
+    if (!h || !name || !n) return fail("null argument");
+    return qualityField(h, "smgpu_quality_coupled_field", name, out, n, [&](double** o) {
+        return runQualityCoupled(h, "smgpu_quality_coupled_field", nullptr, recvCc, o[0], o[1], o[2], o[3], o[4]);
+    });
 }
 
 // ---- debug / parity access -------------------------------------------------------------------

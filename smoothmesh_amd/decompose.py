@@ -26,6 +26,7 @@ class SubDomain:
     pointProcAddressing: np.ndarray   # local point -> global point id
     cellProcAddressing: np.ndarray = None
     faceProcAddressing: np.ndarray = None
+    faceFlip: np.ndarray = None       # local face reversed against the global one (decomposePar's sign in faceProcAddressing)
 
     def processor_patch_points(self) -> np.ndarray:
         """sorted unique GLOBAL ids of the points on this rank's processor patches"""
@@ -190,7 +191,7 @@ def decompose(mesh: PolyMesh, cellRank: np.ndarray, nRanks: int) -> List[SubDoma
         sub = PolyMesh(points=mesh.points[gpts], faceOffsets=off.astype(np.int32), facePoints=fpl.astype(np.int32),
                        owner=np.concatenate(own_l).astype(np.int32), neighbour=nei_l.astype(np.int32), patches=patches,
                        nCells=len(cells))
-        subs.append(SubDomain(sub, r, nRanks, gpts.astype(np.int64), cells.astype(np.int64), fids.astype(np.int64)))
+        subs.append(SubDomain(sub, r, nRanks, gpts.astype(np.int64), cells.astype(np.int64), fids.astype(np.int64), rev.astype(bool)))
     return subs
 
 

@@ -431,6 +431,50 @@ class SmoothEngine:
         self._check(self._lib.smgpu_quality_field(self._h, name.encode(), _p(out, _ffi.c_f64p), C.byref(n)))
         return out
 
+    # -- mesh quality of a sub-domain (DESIGN.md "Mesh quality", 10.4; smoothmesh_amd/quality.py drives these) -------------
+    def quality_coupling(self, rank=None):
+        """(myRank, [(patchStart, patchSize, neighbRank)]) of this engine's processor patches in boundary-file order.  Refuses
+        processorCyclic patches (their cell centres would need the patch transform)."""
+        pats = []
+        for p in self.mesh.patches:
+            if p.type == "processorCyclic":
+                raise SmgpuError(f"mesh quality: patch {p.name} is a processorCyclic patch: cyclic coupling between sub-domains is "
+                                 "not supported")
+            if p.type == "processor":
+                if rank is None:
+                    rank = int(p.myProcNo)
+                pats.append((int(p.startFace), int(p.nFaces), int(p.neighbProcNo)))
+        return (0 if rank is None else int(rank)), pats
+
+    def quality_coupled_pack(self, coupling, sendCc) -> int:
+        """smgpu_quality_coupled_pack: geometry of the current points, then the owner cell centre of every processor face (patch
+        order) into the device buffer at address sendCc (3 doubles per face; 0 when there are none).  Returns the number of
+        processor faces."""
+        rank, pats = coupling
+        st = np.array([p[0] for p in pats], np.int32)
+        sz = np.array([p[1] for p in pats], np.int32)
+        nb = np.array([p[2] for p in pats], np.int32)
+        c = _ffi.QualityCoupling(int(rank), len(pats), _p(st, _ffi.c_i32p), _p(sz, _ffi.c_i32p), _p(nb, _ffi.c_i32p))
+        n = C.c_int64()
+        self._check(self._lib.smgpu_quality_coupled_pack(self._h, C.byref(c), C.c_void_p(sendCc or None), C.byref(n)))
+        return n.value
+
+    def quality_coupled_report(self, recvCc, nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0) -> dict:
+        """smgpu_quality_coupled_report: this rank's record (smgpu_quality_part field names, local ids), the neighbours' cell
+        centres at device address recvCc"""
+        p = _ffi.QualityParams(nonOrthThreshold, skewThreshold, closedThreshold, aspectThreshold)
+        q = _ffi.QualityPart()
+        self._check(self._lib.smgpu_quality_coupled_report(self._h, C.byref(p), C.c_void_p(recvCc or None), C.byref(q)))
+        return {n: getattr(q, n) for n, _ in q._fields_}
+
+    def quality_coupled_field(self, name, recvCc) -> np.ndarray:
+        """smgpu_quality_coupled_field: as quality_field, processor faces with the internal-face definitions"""
+        n = C.c_int64()
+        self._check(self._lib.smgpu_quality_coupled_field(self._h, name.encode(), C.c_void_p(recvCc or None), None, C.byref(n)))
+        out = np.empty(n.value, np.float64)
+        self._check(self._lib.smgpu_quality_coupled_field(self._h, name.encode(), C.c_void_p(recvCc or None), _p(out, _ffi.c_f64p), C.byref(n)))
+        return out
+
     # -- timing --------------------------------------------------------------------------------
     def enable_timing(self, on=True):
         self._check(self._lib.smgpu_enable_timing(self._h, int(on)))

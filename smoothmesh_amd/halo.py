@@ -709,6 +709,65 @@ class DistributedSmoother:
     def get_points(self):
         return self.engine.get_points()
 
+    def _quality_exchange(self):
+        """pack, then every processor patch's owner cell centres to the neighbour and theirs back (one all_to_all_single, staged
+        through the host for gloo like _a2a) -> recvCc (device tensor, patch order)"""
+        torch = self.torch
+        coupling = self.engine.quality_coupling(self.rank)
+        pats = coupling[1]
+        n = sum(p[1] for p in pats)
+        send = torch.empty((max(n, 1), 3), dtype=torch.float64, device=self.device)
+        self.engine.quality_coupled_pack(coupling, send.data_ptr() if n else 0)
+        recv = torch.empty_like(send)
+        if self.world > 1:
+            offs = np.concatenate([[0], np.cumsum([p[1] for p in pats])]).astype(np.int64)
+            order = sorted(range(len(pats)), key=lambda i: pats[i][2])       # the collective's blocks go by ascending rank
+            counts = [0] * self.world
+            for i in order:
+                counts[pats[i][2]] = 3 * pats[i][1]
+            flat = lambda t: t.reshape(-1)  # noqa: E731
+            sbuf = torch.cat([flat(send[offs[i]:offs[i + 1]]) for i in order]) if pats else send.new_empty(0)
+            if self._staged():
+                rbuf = torch.empty(sum(counts), dtype=torch.float64)
+                self.dist.all_to_all_single(rbuf, sbuf.cpu(), counts, counts)
+                rbuf = rbuf.to(self.device)
+            else:
+                rbuf = torch.empty(sum(counts), dtype=torch.float64, device=self.device)
+                self.dist.all_to_all_single(rbuf, sbuf, counts, counts)
+            pos = 0
+            for i in order:
+                m = 3 * pats[i][1]
+                flat(recv)[3 * offs[i]:3 * offs[i] + m].copy_(rbuf[pos:pos + m])
+                pos += m
+        elif pats:
+            raise RuntimeError("mesh quality: a single rank with processor patches")
+        torch.cuda.synchronize(self.device)
+        return recv
+
+    def mesh_quality(self, **thresholds):
+        """Quality report of the whole decomposed mesh at the current points, identical on every rank (smoothmesh_amd/quality.py,
+        DESIGN.md 10.4): paired-patch exchange of the processor faces' cell centres, this rank's record, an all-gather of the
+        records and combine_quality.  Ids are global where every sub-domain carries cell and face addressing.  A collective:
+        every rank calls it, between iterations."""
+        from .quality import QUALITY_DEFAULTS, combine_quality
+        recv = self._quality_exchange()
+        part = self.engine.quality_coupled_report(recv.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds})
+        cp, fp = self.sub.cellProcAddressing, self.sub.faceProcAddressing
+        # only the three ids of this record travel, not the addressing
+        cmap = {part["minVolumeCell"]: int(cp[part["minVolumeCell"]])} if cp is not None and part["nCells"] else ({} if cp is not None else None)
+        fmap = None
+        if fp is not None:
+            fmap = {k: int(fp[k]) for k in (part["maxNonOrthFace"], part["maxSkewFace"]) if k >= 0}
+        allv = [None] * self.world
+        self.dist.all_gather_object(allv, (part, cmap, fmap))
+        return combine_quality([a[0] for a in allv], [a[1] for a in allv], [a[2] for a in allv])
+
+    def quality_field(self, name):
+        """this rank's per-element quality field (engine.QUALITY_FIELDS); processor faces carry their values on both sides.
+        A collective (the exchange of mesh_quality)."""
+        recv = self._quality_exchange()
+        return self.engine.quality_coupled_field(name, recv.data_ptr())
+
 
 class LocalMultiSmoother:
     """All sub-domains in ONE process on ONE device (engines side by side), the exchange done by
@@ -821,3 +880,15 @@ class LocalMultiSmoother:
 
     def get_points(self):
         return [st.eng.get_points() for st in self.states]
+
+    def mesh_quality(self, **thresholds):
+        """Quality report of the decomposed mesh at the current points (smoothmesh_amd/quality.py): the cell
+        centres of the processor faces move between the engines' buffers by device-side copies.  Ids are global where the
+        sub-domains carry cell and face addressing.  Between iterations only; the loop is left as it was."""
+        from .quality import local_quality
+        return local_quality([st.eng for st in self.states], self.subs, self.device, thresholds)
+
+    def quality_field(self, name):
+        """[per-rank array] of a quality field (engine.QUALITY_FIELDS); processor faces carry their values on both sides"""
+        from .quality import local_quality_field
+        return local_quality_field([st.eng for st in self.states], name, self.device)

@@ -224,3 +224,11 @@ def write_decomposed_case(caseDir, subs, binary=False, precision=17, **kw):
         write_polymesh(d, s.mesh, binary=binary, precision=precision)
         write_label_list(os.path.join(d, "pointProcAddressing"), s.pointProcAddressing, "constant/polyMesh", "pointProcAddressing",
                          "labelIOList", binary)
+        # decomposePar's cell and face addressing where the sub-domain carries it (faces: +-(global id + 1), minus where flipped)
+        if getattr(s, "cellProcAddressing", None) is not None:
+            write_label_list(os.path.join(d, "cellProcAddressing"), s.cellProcAddressing, "constant/polyMesh", "cellProcAddressing",
+                             "labelIOList", binary)
+        if getattr(s, "faceProcAddressing", None) is not None:
+            flip = s.faceFlip if getattr(s, "faceFlip", None) is not None else np.zeros(len(s.faceProcAddressing), bool)
+            signed = np.where(flip, -(s.faceProcAddressing + 1), s.faceProcAddressing + 1)
+            write_label_list(os.path.join(d, "faceProcAddressing"), signed, "constant/polyMesh", "faceProcAddressing", "labelIOList", binary)

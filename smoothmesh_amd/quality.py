@@ -1,0 +1,183 @@
+"""Mesh quality report of a decomposed mesh (DESIGN.md "Mesh quality", 10.4).
+
+Every sub-domain's engine reports a partial record (include/smgpu.h smgpu_quality_coupled_pack / _report): its processor faces
+take the internal-face definitions with the neighbour rank's cell centre, and count only on the side with the lower rank.
+combine_quality folds the records in a fixed order into the report the serial engine gives for the undecomposed mesh.
+Drivers: decomposed_mesh_quality (sub-domains without a point halo, one process), LocalMultiSmoother.mesh_quality and
+DistributedSmoother.mesh_quality (smoothmesh_amd/halo.py); the shell tool is smoothmesh_amd/check_quality.py.
+"""
+from dataclasses import dataclass, fields
+
+import numpy as np
+
+from .engine import MeshQuality, QUALITY_FIELDS  # noqa: F401
+
+QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
+_COUNTS = ("nNonPositiveVolume", "nZeroAreaFaces", "nSevereNonOrth", "nErrorNonOrth", "nSkewFaces", "nWrongOrientedFaces",
+           "nOpenCells", "nHighAspectCells")
+
+
+@dataclass
+class DecomposedMeshQuality(MeshQuality):
+    """MeshQuality of a decomposed mesh.  minVolumeCell, maxNonOrthFace, maxSkewFace are GLOBAL ids where every sub-domain
+    carries cell / face addressing, else -1; (rank, local id) of the same elements are always filled (-1 where there is none)."""
+    minVolumeRank: int = -1
+    minVolumeLocal: int = -1
+    maxNonOrthRank: int = -1
+    maxNonOrthLocal: int = -1
+    maxSkewRank: int = -1
+    maxSkewLocal: int = -1
+
+
+def _pick(parts, present, value, lid, ids, larger):
+    """(value, global id or -1, rank, local id) of the winner: the larger (or smaller) value; a tie goes to the lowest global id
+    when ids is given, else to the lowest (rank, local id)"""
+    best = None
+    for r, p in enumerate(parts):
+        if p[present] <= 0:
+            continue
+        v, loc = float(p[value]), int(p[lid])
+        gid = int(ids[r][loc]) if ids is not None else -1
+        key = (gid,) if ids is not None else (r, loc)
+        if best is None or (v > best[0] if larger else v < best[0]) or (v == best[0] and key < best[1]):
+            best = (v, key, gid, r, loc)
+    if best is None:
+        return 0.0, -1, -1, -1
+    return best[0], best[2], best[3], best[4]
+
+
+def combine_quality(parts, cellIds=None, faceIds=None) -> DecomposedMeshQuality:
+    """One report from the per-rank records `parts` (ascending rank; dicts with the smgpu_quality_part field names, local ids).
+    cellIds[r] / faceIds[r]: local -> global id of rank r (cellProcAddressing / faceProcAddressing); the ids of the report are
+    global only when every rank has both.  Rules: totals and Σθ are summed in ascending rank order, the average
+    is Σθ / the global nInternalFaces; min / max ties go to the lowest global id, or to the lowest (rank, local id)."""
+    parts = [dict(p) for p in parts]
+    glob = (cellIds is not None and faceIds is not None and len(cellIds) == len(parts) == len(faceIds)
+            and all(c is not None for c in cellIds) and all(f is not None for f in faceIds))
+    cids, fids = (cellIds, faceIds) if glob else (None, None)
+    out = {k: sum(int(p[k]) for p in parts) for k in ("nCells", "nFaces", "nInternalFaces") + _COUNTS}
+
+    def ordered_sum(k):
+        acc = None
+        for p in parts:
+            acc = float(p[k]) if acc is None else acc + float(p[k])
+        return 0.0 if acc is None else acc
+
+    def extreme(k, present, larger):
+        vals = [float(p[k]) for p in parts if p[present] > 0]
+        return (max(vals) if larger else min(vals)) if vals else 0.0
+
+    out["totalVolume"] = ordered_sum("totalVolume")
+    sumTh = ordered_sum("sumNonOrth")
+    out["avgNonOrth"] = sumTh / out["nInternalFaces"] if out["nInternalFaces"] else 0.0
+    out["maxVolume"] = extreme("maxVolume", "nCells", True)
+    out["minFaceArea"] = extreme("minFaceArea", "nFaces", False)
+    out["maxFaceArea"] = extreme("maxFaceArea", "nFaces", True)
+    out["maxOpenness"] = extreme("maxOpenness", "nCells", True)
+    out["maxAspectRatio"] = extreme("maxAspectRatio", "nCells", True)
+    (out["minVolume"], out["minVolumeCell"], out["minVolumeRank"], out["minVolumeLocal"]) = \
+        _pick(parts, "nCells", "minVolume", "minVolumeCell", cids, False)
+    (out["maxNonOrth"], out["maxNonOrthFace"], out["maxNonOrthRank"], out["maxNonOrthLocal"]) = \
+        _pick(parts, "nInternalFaces", "maxNonOrth", "maxNonOrthFace", fids, True)
+    (out["maxSkewness"], out["maxSkewFace"], out["maxSkewRank"], out["maxSkewLocal"]) = \
+        _pick(parts, "nFaces", "maxSkewness", "maxSkewFace", fids, True)
+    return DecomposedMeshQuality(**{f.name: out[f.name] for f in fields(DecomposedMeshQuality)})
+
+
+def paired_offsets(couplings):
+    """For couplings[i] = (rank, [(start, size, neighbour), ...]) of every rank: [(dst index, dst slot, src index, src slot, size)]
+    copies that fill every rank's recvCc from its neighbours' sendCc (slot = first face of the patch in patch order)."""
+    at = {}
+    for i, (rank, pats) in enumerate(couplings):
+        off = 0
+        for _, size, o in pats:
+            at[(int(rank), int(o))] = (i, off, size)
+            off += size
+    copies = []
+    for (r, o), (i, off, size) in at.items():
+        if (o, r) not in at:
+            raise ValueError(f"processor patch {r} -> {o} has no partner patch {o} -> {r}")
+        j, ooff, osize = at[(o, r)]
+        if osize != size:
+            raise ValueError(f"processor patches {r} -> {o} and {o} -> {r} differ in size ({size}, {osize})")
+        copies.append((i, off, j, ooff, size))
+    return copies
+
+
+def local_exchange(engines, couplings, torch_device):
+    """pack on every engine, then fill every recvCc from the partner patches by device-side copies (one process, one device)
+    -> list of recvCc tensors"""
+    import torch
+    send = []
+    for e, c in zip(engines, couplings):
+        n = sum(p[1] for p in c[1])
+        t = torch.empty((max(n, 1), 3), dtype=torch.float64, device=torch_device)
+        e.quality_coupled_pack(c, t.data_ptr() if n else 0)
+        send.append(t)
+    recv = [torch.empty_like(t) for t in send]
+    for i, off, j, ooff, size in paired_offsets(couplings):
+        recv[i][off:off + size].copy_(send[j][ooff:ooff + size])
+    torch.cuda.synchronize(torch_device)
+    return recv
+
+
+def _ids_of(sub):
+    return getattr(sub, "cellProcAddressing", None), getattr(sub, "faceProcAddressing", None)
+
+
+def local_quality(engines, subs, torch_device, thresholds):
+    couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
+    recv = local_exchange(engines, couplings, torch_device)
+    parts = [e.quality_coupled_report(t.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds}) for e, t in zip(engines, recv)]
+    ids = [_ids_of(s) for s in subs]
+    if len(subs) == 1 and any(x is None for x in ids[0]):            # one sub-domain is the whole mesh: its local ids are the global ones
+        m = getattr(subs[0], "mesh", subs[0])
+        ids = [(np.arange(m.nCells), np.arange(m.nFaces))]
+    return combine_quality(parts, [i[0] for i in ids], [i[1] for i in ids])
+
+
+def local_quality_field(engines, name, torch_device):
+    couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
+    recv = local_exchange(engines, couplings, torch_device)
+    return [e.quality_coupled_field(name, t.data_ptr()) for e, t in zip(engines, recv)]
+
+
+def decomposed_mesh_quality(subs, device=0, foam_variant=None, **thresholds) -> DecomposedMeshQuality:
+    """Quality report of a decomposed mesh whose sub-domains (decompose.SubDomain or PolyMesh, rank = position in the list) need
+    no point halo: one plain engine per sub-domain on one device.  Only the processor patches couple them.  Ids are global where
+    the sub-domains carry cell and face addressing (a single sub-domain is the whole mesh: its own ids)."""
+    import torch
+    from .engine import SmoothEngine
+    meshes = [getattr(s, "mesh", s) for s in subs]
+    engines = []
+    try:
+        for m in meshes:
+            e = SmoothEngine(m, device=device)
+            if len(meshes) > 1:
+                e.set_device_share(len(meshes))
+            if foam_variant is not None:
+                e.set_foam_variant(foam_variant)
+            engines.append(e)
+        return local_quality(engines, subs, torch.device("cuda", device), thresholds)
+    finally:
+        for e in engines:
+            e.close()
+
+
+def format_report(q, which="mesh"):
+    """the block smoothMesh -checkQuality prints (csrc/host/smoothMesh_main.cpp, reportQuality)"""
+    g = lambda x: "%.9g" % x  # noqa: E731
+    lines = [f"Mesh quality ({which}):",
+             f"    cells {q.nCells} faces {q.nFaces} internalFaces {q.nInternalFaces}",
+             f"    cellVolume min {g(q.minVolume)} max {g(q.maxVolume)} total {g(q.totalVolume)} nonPositive {q.nNonPositiveVolume} "
+             f"minCell {q.minVolumeCell}",
+             f"    faceArea min {g(q.minFaceArea)} max {g(q.maxFaceArea)} zero {q.nZeroAreaFaces}",
+             f"    nonOrthogonality max {g(q.maxNonOrth)} average {g(q.avgNonOrth)} severe {q.nSevereNonOrth} error {q.nErrorNonOrth} "
+             f"maxFace {q.maxNonOrthFace}",
+             f"    skewness max {g(q.maxSkewness)} severe {q.nSkewFaces} maxFace {q.maxSkewFace}",
+             f"    facePyramids wrongOriented {q.nWrongOrientedFaces}",
+             f"    cellOpenness max {g(q.maxOpenness)} open {q.nOpenCells}",
+             f"    cellAspectRatio max {g(q.maxAspectRatio)} high {q.nHighAspectCells}"]
+    if q.nNonPositiveVolume > 0 or q.nWrongOrientedFaces > 0:
+        lines.append(f"    ***Mesh has {q.nNonPositiveVolume} non-positive volume cells and {q.nWrongOrientedFaces} wrongly oriented faces")
+    return "\n".join(lines) + "\n\n"
