@@ -6,7 +6,12 @@ A "step" is one smoothing iteration over the whole (per-rank) mesh.  Default wor
 configs[1]: 1M-cell uniform hex block (100^3, interior jitter 0.2 h, seed 12345), constraints off,
 relTol 0 (exactly K iterations run).  Inputs are device-resident when the timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W [--workload hex100|hex100c|hexN[c]] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--workload hex100|hex100c|hexN[c]] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up, the W + K steps timed cold (ms_per_step_cold), the clock
+pre-run, the W warm-up and K timed steps (the reported value), --dump-outputs, and the result line.  Everything below
+that takes runs of its own -- the configs[] sub-runs, parity_check, cpu_baseline, the per-kernel hipEvent pass
+(roofline, kernels, chains), the 100-step at_100_iters leg, on N > 1 halo_cost -- is measured with --full only.
 
 N > 1, one rank per GPU (started by torch.distributed.run, or by this script itself when WORLD_SIZE is unset): weak
 scaling -- hexN: every rank owns an N^3 sub-block of a (Px*N, Py*N, Pz*N) block; cavityN: the castellated polyhedral
@@ -15,9 +20,9 @@ GPUs = the 430^3-base, ~80 M-cell mesh), every rank generating ITS box only (pol
 values are exchanged per iteration with RCCL all_to_all (smoothmesh_amd/halo.py); value = all ranks' points * K /
 max-over-ranks time.
 
-The default N = 1 run also measures BASELINE.json's other single-GPU configurations (configs[2] hex100c, configs[3]
+With --full the default N = 1 run also measures BASELINE.json's other single-GPU configurations (configs[2] hex100c, configs[3]
 cavity215c and its constraints-off twin) with BASELINE's iteration counts (100 / 200) and reports them under "configs" in the
-same JSON line (--no-configs skips that, --configs a,b,c selects).  The headline and every configs[] entry carry
+same JSON line (--no-configs skips that, --configs a,b,c selects).  With --full the headline and every configs[] entry carry
   ms_per_step_cold  the same W + K steps timed before the clock pre-run,
   parity_check      the engine against the CPU oracle on THIS workload's own mesh (same start, same n iterations),
   cpu_baseline      the serial oracle's rate on that mesh (bounded number of iterations),
@@ -389,11 +394,11 @@ def dump_outputs(path, points, res, frz):
         np.save(os.path.join(path, name + ".npy"), a)
 
 
-def run_single(workload, K, W, device, oracle=True, oracle_budget_s=12.0, nominal100=False, keep_points=False):
+def run_single(workload, K, W, device, oracle=True, oracle_budget_s=12.0, nominal100=False, keep_points=False, full=True):
     """one GPU, one workload: W warm-up + K timed steps on a cold GPU (ms_per_step_cold), the clock pre-run, W + K again (the
-    reported value; inputs resident), the same K steps with per-kernel hipEvents, and -- outside every timed region -- the
-    oracle leg (parity_check + cpu_baseline on this workload's own mesh).  keep_points: also return the coordinates the
-    timed steps left (read after the clock has stopped)"""
+    reported value; inputs resident), and with `full` -- outside every timed region -- the same K steps with per-kernel
+    hipEvents, the near-tie census and the oracle leg (parity_check + cpu_baseline on this workload's own mesh; only if
+    `oracle` too).  keep_points: also return the coordinates the timed steps left (read after the clock has stopped)"""
     import torch
     from smoothmesh_amd import SmoothEngine, default_params
     kind, n_side, constraints = parse_workload(workload)
@@ -427,11 +432,11 @@ def run_single(workload, K, W, device, oracle=True, oracle_budget_s=12.0, nomina
     pre = clock_warm(lambda k: eng.iterate(k, 0.0), eng, torch.cuda.synchronize)
     dt, res, frz = timed()
     points = eng.get_points() if keep_points else None
-    near_timed = eng.last_near_ties.sum() if hasattr(eng, "last_near_ties") else 0
+    near_timed = eng.last_near_ties.sum() if full and hasattr(eng, "last_near_ties") else 0
     # the metric says "(100 iters)": when the contract's K is shorter (the driver runs 20 steps = 1.7 ms on the hex block), the same
     # loop once more over 100 steps from the initial coordinates, reported beside the K-step value
     dt100 = None
-    if K < 100 and nominal100:
+    if K < 100 and nominal100 and full:
         eng.set_points(mesh.points)
         if W:
             eng.iterate(W, 0.0)
@@ -440,26 +445,28 @@ def run_single(workload, K, W, device, oracle=True, oracle_budget_s=12.0, nomina
         eng.iterate(100, 0.0)
         torch.cuda.synchronize()
         dt100 = time.perf_counter() - t0
-    # second pass over the same K steps with per-kernel hipEvent brackets (on the engine's stream)
-    eng.reset_counters()
-    eng.enable_timing(True)
-    t0 = time.perf_counter()
-    eng.iterate(K, 0.0)
-    dt_ev = time.perf_counter() - t0
-    eng.enable_timing(False)
-    ctr = [c for c in eng.counters() if c["launches"] > 0 and c["ms"] > 0]
+    dt_ev = ctr = None
+    if full:
+        # second pass over the same K steps with per-kernel hipEvent brackets (on the engine's stream)
+        eng.reset_counters()
+        eng.enable_timing(True)
+        t0 = time.perf_counter()
+        eng.iterate(K, 0.0)
+        dt_ev = time.perf_counter() - t0
+        eng.enable_timing(False)
+        ctr = [c for c in eng.counters() if c["launches"] > 0 and c["ms"] > 0]
     sizes = eng.sizes()
     nPoints = mesh.nPoints
     base = par = None
     t0 = time.perf_counter()
-    if oracle:
+    if oracle and full:
         base, par = oracle_leg(kind, n_side, constraints, eng, prm, budget_s=oracle_budget_s, layers=layers, boundary=boundary)
     t_oracle = time.perf_counter() - t0
     # near-tie census of everything this engine ran (include/smgpu.h): angle comparisons with sides within 4 ulp -- the decisions
     # the reference's acos could take the other way; zero = none
     # (since_create includes the clock pre-run: hundreds of iterations that drive a SMALL mesh to convergence, where steps of an ulp
     # make near ties of their own; the summary quotes the iterations that were compared with the oracle, else the timed ones)
-    near = {**eng.near_ties(), "timed_steps": int(near_timed)} if hasattr(eng, "near_ties") else None
+    near = {**eng.near_ties(), "timed_steps": int(near_timed)} if full and hasattr(eng, "near_ties") else None
     eng.close()
     del eng
     return dict(kind=kind, n_side=n_side, constraints=constraints, layers=layers, boundary=boundary, dt=dt, dt_cold=dt_cold, dt_ev=dt_ev,
@@ -594,12 +601,13 @@ def rank0_cpu_baseline(sub, prm, budget_s, rank, world):
 
 
 def run_distributed(workload, K, W, rank, world, local_rank, backend, oracle=True, force_dist=False, oracle_budget_s=12.0,
-                    keep_points=False):
-    """N ranks, one workload: per-rank sub-domain, exchange arrangement autotuned, clock pre-run, W warm-up + K timed steps between
-    barriers (max over ranks), the same K steps with per-kernel hipEvents; outside the timed region: parity_check (a) copies of
-    shared points identical across ranks, (b) a down-scaled case through the same transport against the oracle's MultiDomain;
-    cpu_baseline = rank 0's oracle on its own sub-domain; transport = how the records travelled (communicator size included);
-    keep_points: also return this rank's coordinates after the timed steps"""
+                    keep_points=False, full=True):
+    """N ranks, one workload: per-rank sub-domain, exchange arrangement autotuned (with `oracle`: the exchange-stream arrangement
+    only a candidate after its check), clock pre-run, W warm-up + K timed steps between barriers (max over ranks); transport = how
+    the records travelled (communicator size included); with `full`, outside the timed region: the same K steps with per-kernel
+    hipEvents, halo_cost, and (with `oracle` too) parity_check (a) copies of shared points identical across ranks, (b) a
+    down-scaled case through the same transport against the oracle's MultiDomain; cpu_baseline = rank 0's oracle on its own
+    sub-domain.  keep_points: also return this rank's coordinates after the timed steps"""
     import torch
     import torch.distributed as dist
     from smoothmesh_amd import default_params
@@ -609,7 +617,7 @@ def run_distributed(workload, K, W, rank, world, local_rank, backend, oracle=Tru
     grid = proc_grid(world)
     rdev = "cuda" if backend == "nccl" else "cpu"
     small = None
-    if oracle and world > 1:
+    if oracle and full and world > 1:
         try:
             small = small_case_parity(kind, constraints, grid, rank, world, local_rank)
         except Exception as ex:   # noqa: BLE001 -- reported in the line, the measurement goes on (on every rank alike)
@@ -717,15 +725,17 @@ def run_distributed(workload, K, W, rank, world, local_rank, backend, oracle=Tru
     total_points = int(npts.item())      # points of all sub-domains (shared points counted per rank,
     eng = ds.engine                      # as the reference's per-rank loops process them)
     points = eng.get_points() if keep_points else None
-    copies = shared_copies_check(ds, sub) if world > 1 else None      # parity_check (a): the state the timed steps left
-    eng.reset_counters()
-    eng.enable_timing(True)
-    t0 = time.perf_counter()
-    ds.iterate(K, 0.0)
-    torch.cuda.synchronize()
-    dt_ev = time.perf_counter() - t0
-    eng.enable_timing(False)
-    ctr = [c for c in eng.counters() if c["launches"] > 0 and c["ms"] > 0]
+    copies = shared_copies_check(ds, sub) if world > 1 and full else None      # parity_check (a): the state the timed steps left
+    dt_ev = ctr = None
+    if full:
+        eng.reset_counters()
+        eng.enable_timing(True)
+        t0 = time.perf_counter()
+        ds.iterate(K, 0.0)
+        torch.cuda.synchronize()
+        dt_ev = time.perf_counter() - t0
+        eng.enable_timing(False)
+        ctr = [c for c in eng.counters() if c["launches"] > 0 and c["ms"] > 0]
     sizes = dict(eng.sizes())
     info = ds.transport_info()
     hm = eng.debug_halo_mode() if hasattr(eng, "debug_halo_mode") else {}
@@ -743,7 +753,7 @@ def run_distributed(workload, K, W, rank, world, local_rank, backend, oracle=Tru
     # (its processor-patch points are plain internal points, nothing is packed, combined or exchanged) through the single-rank loop,
     # same W + K steps, max over the ranks
     halo_cost = None
-    if not (layers or boundary) and (world > 1 or force_dist):
+    if full and not (layers or boundary) and (world > 1 or force_dist):
         from smoothmesh_amd import SmoothEngine
         se = SmoothEngine(sub.mesh, device=local_rank)
         se.set_params(prm)
@@ -762,11 +772,11 @@ def run_distributed(workload, K, W, rank, world, local_rank, backend, oracle=Tru
                              "exchanged), same steps, max over ranks; the difference is the multi-rank code path (halo roles, exchanges, "
                              "k_shared_fix) plus link time; bound = serial / multi-rank"}
     t0 = time.perf_counter()
-    base = rank0_cpu_baseline(sub, prm, oracle_budget_s, rank, world) if oracle else None
+    base = rank0_cpu_baseline(sub, prm, oracle_budget_s, rank, world) if oracle and full else None
     t_oracle = time.perf_counter() - t0
     dist.barrier()           # (the other ranks wait for rank 0's oracle here)
     par = None
-    if world > 1 and oracle:
+    if world > 1 and oracle and full:
         par = {"shared_point_copies": copies, "small_case": small,
                "ok": bool((copies or {}).get("ok", rank != 0) and (small or {}).get("ok", False))}
     return dict(kind=kind, n_side=n_side, constraints=constraints, layers=layers, boundary=boundary, dt=dt, dt_ev=dt_ev, ctr=ctr, sizes=sizes,
@@ -976,9 +986,11 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="hex100")
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything that takes runs of its own: configs[], "
+                    "parity_check, cpu_baseline, the per-kernel hipEvent pass (roofline, kernels), at_100_iters, halo_cost")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--configs", default=None, help="comma-separated workloads reported under \"configs\" (N = 1); "
-                    "default with the default workload: hex100c,cavity215,cavity215c")
+    ap.add_argument("--configs", default=None, help="with --full: comma-separated workloads reported under \"configs\"; "
+                    "default with the default workload: hex100c,cavity215,cavity215c (N = 1), cavity215c (N > 1)")
     ap.add_argument("--no-configs", action="store_true")
     ap.add_argument("--config-steps", type=int, default=0, help="steps of the configs[] sub-runs; 0 = BASELINE.json's counts "
                     "(100 on the hex block, 200 on the polyhedral mesh)")
@@ -990,6 +1002,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.configs and not args.full:
+        ap.error("--configs measures sub-runs of their own: it needs --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1022,7 +1036,7 @@ def main():
             os.environ.setdefault(k, v)
     if world == 1 and not force_dist:
         r = run_single(args.workload, K, W, local_rank, oracle=not args.no_cpu_baseline, nominal100=True,
-                       keep_points=args.dump_outputs is not None)
+                       keep_points=args.dump_outputs is not None, full=args.full)
         dt, dt_ev, ctr, sizes, total_points, res, frz = r["dt"], r["dt_ev"], r["ctr"], r["sizes"], r["total_points"], r["res"], r["frz"]
         if args.dump_outputs is not None and rank == 0:
             dump_outputs(args.dump_outputs, r.pop("points"), res, frz)
@@ -1037,7 +1051,7 @@ def main():
         else:
             dist.init_process_group(backend)
         r = run_distributed(args.workload, K, W, rank, world, local_rank, backend, oracle=not args.no_cpu_baseline, force_dist=force_dist,
-                            keep_points=args.dump_outputs is not None and rank == 0)
+                            keep_points=args.dump_outputs is not None and rank == 0, full=args.full)
         dt, dt_ev, ctr, sizes, total_points, res, frz = r["dt"], r["dt_ev"], r["ctr"], r["sizes"], r["total_points"], r["res"], r["frz"]
         if args.dump_outputs is not None and rank == 0:
             dump_outputs(args.dump_outputs, r.pop("points"), res, frz)
@@ -1045,7 +1059,7 @@ def main():
         multi = r
         # BASELINE configs[4] beside the weak-scaling headline: the polyhedral mesh, cavity215c per GPU (the 430^3-base, ~80 M-cell
         # mesh on 8 GPUs), constraints on, BASELINE's 200 iterations -- in the same job, every rank taking part
-        names = [] if (args.no_configs or force_dist) else (args.configs.split(",") if args.configs is not None else
+        names = [] if (args.no_configs or force_dist or not args.full) else (args.configs.split(",") if args.configs is not None else
                                                             (["cavity215c"] if args.workload == "hex100" else []))
         multi_subs = []
         for wl in [w for w in names if w]:
@@ -1104,7 +1118,7 @@ def main():
             "device_bytes_per_gpu": int(sizes["deviceBytes"]),
             "parallelism": parallelism,
         },
-        **kernel_report(args.workload, ctr, K, dt, dt_ev, sizes),
+        **(kernel_report(args.workload, ctr, K, dt, dt_ev, sizes) if args.full else {}),
         "residual_last": float(res[-1]), "nFrozenPoints_last": int(frz[-1]),
         "parity": "HIP == CPU oracle (tests/); the oracle restates the reference and is unpinned against a real OpenFOAM build",
     }
@@ -1131,7 +1145,7 @@ def main():
             out["configs"] = multi_subs
     if world == 1 and not force_dist:
         # BASELINE.json's other single-GPU configurations, measured by this same run (bounded steps)
-        names = [] if args.no_configs else (args.configs.split(",") if args.configs is not None else
+        names = [] if (args.no_configs or not args.full) else (args.configs.split(",") if args.configs is not None else
                                             (["hex100c", "cavity215", "cavity215c"] if args.workload == "hex100" else []))
         subs = []
         for wl in [w for w in names if w]:
@@ -1172,7 +1186,8 @@ def main():
                                    "note": "the metric's nominal iteration count, timed like the K steps, from the initial coordinates"}
         if single:
             out["phases"] = single["phases"]
-            out["near_ties"] = single["near_ties"]
+            if single["near_ties"] is not None:
+                out["near_ties"] = single["near_ties"]
     import resource
     out["host_max_rss_gib"] = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2**20   # rank 0's process
     code = emit(out)

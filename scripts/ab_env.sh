@@ -9,7 +9,7 @@ i=0
 for e in "$@"; do
   i=$((i+1))
   out=$root/gpurun_out/ab/${wl}_env$i
-  env $e timeout 600 python $root/bench.py --workload $wl --no-cpu-baseline --no-configs --no-parity --steps $steps --warmup 5 > $out.json 2> $out.err
+  env $e timeout 600 python $root/bench.py --workload $wl --full --no-cpu-baseline --no-configs --no-parity --steps $steps --warmup 5 > $out.json 2> $out.err
   python - "$out.json" "$e" <<'PY'
 import json, sys
 try:

@@ -4,12 +4,13 @@
 export SMOOTHMESH_BENCH_FULL=1
 wl=$1; steps=$2; shift 2
 root=${GRAFT_REPO_ROOT:-$(pwd)}
-mkdir -p $root/gpurun_out/ab
+ab=$root/scripts/tmp/ab
+mkdir -p $ab
 i=0
 for e in "" "$@"; do
   i=$((i+1))
-  env $e timeout 900 python $root/bench.py --workload $wl --no-configs --steps $steps --warmup 5 > $root/gpurun_out/ab/${wl}_env$i.json 2> $root/gpurun_out/ab/${wl}_env$i.err
-  python - "$root/gpurun_out/ab/${wl}_env$i.json" "${e:-defaults}" <<'PY'
+  env $e timeout 900 python $root/bench.py --workload $wl --full --no-configs --steps $steps --warmup 5 > $ab/${wl}_env$i.json 2> $ab/${wl}_env$i.err
+  python - "$ab/${wl}_env$i.json" "${e:-defaults}" <<'PY'
 import json, sys
 try:
     d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][0])

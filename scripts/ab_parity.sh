@@ -4,12 +4,13 @@
 export SMOOTHMESH_BENCH_FULL=1
 wl=$1; steps=$2; shift 2
 root=${GRAFT_REPO_ROOT:-$(pwd)}
-mkdir -p $root/gpurun_out/ab
+ab=$root/scripts/tmp/ab
+mkdir -p $ab
 for v in default "$@"; do
   name=$(basename "$v" .so)
   if [ "$v" = default ]; then unset SMOOTHMESH_SMGPU_LIB; else export SMOOTHMESH_SMGPU_LIB=$root/$v; fi
-  timeout 900 python $root/bench.py --workload $wl --no-configs --steps $steps --warmup 5 > $root/gpurun_out/ab/${wl}_$name.json 2> $root/gpurun_out/ab/${wl}_$name.err
-  python - "$root/gpurun_out/ab/${wl}_$name.json" "$name" <<'PY'
+  timeout 900 python $root/bench.py --workload $wl --full --no-configs --steps $steps --warmup 5 > $ab/${wl}_$name.json 2> $ab/${wl}_$name.err
+  python - "$ab/${wl}_$name.json" "$name" <<'PY'
 import json, sys
 try:
     d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][0])

@@ -7,8 +7,8 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/profiles_$tag
 rm -rf $out; mkdir -p $out
 cd $root
-B="timeout 300 python bench.py"
-timeout 1500 python bench.py > $out/bench_default.json 2>$out/bench.err                                   # hex100 + configs[] (hex100c, cavity215, cavity215c) + cpu_baseline
+B="timeout 300 python bench.py --full"
+timeout 1500 python bench.py --full > $out/bench_default.json 2>$out/bench.err                                   # hex100 + configs[] (hex100c, cavity215, cavity215c) + cpu_baseline
 $B --workload hex100c --no-configs > $out/bench_hex100c.json 2>>$out/bench.err
 $B --workload hex215 --no-cpu-baseline --no-configs --steps 50 --warmup 5 > $out/bench_hex215.json 2>>$out/bench.err
 $B --workload hex300 --no-cpu-baseline --no-configs --steps 20 --warmup 2 > $out/bench_hex300.json 2>>$out/bench.err

@@ -55,6 +55,6 @@ done
 # 4. the bench lines the driver will ask for (each starts its own ranks; parity_check must be ok in every line)
 for g in 2 4 8; do
     [ "$g" -le "$N" ] || continue
-    run bench_$g sh -c "python3 bench.py --gpus $g > $OUT/bench_$g.json && python3 scripts/check_bench_line.py $OUT/bench_$g.json $g"
+    run bench_$g sh -c "python3 bench.py --gpus $g --full > $OUT/bench_$g.json && python3 scripts/check_bench_line.py $OUT/bench_$g.json $g"
 done
 echo "all $step steps passed"

@@ -6,5 +6,5 @@ steps=${1:-50}; shift
 for w in "$@"; do
     echo "== $w"
     timeout 1500 python bench.py --workload "$w" --steps "$steps" --warmup 5 \
-        --no-cpu-baseline --no-configs 2>&1 | python scripts/bench_summary.py
+        --full --no-cpu-baseline --no-configs 2>&1 | python scripts/bench_summary.py
 done

@@ -40,6 +40,13 @@ def test_self_launch_reaches_the_ranks_without_a_gpu():
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_configs_without_full_is_refused_before_the_gpu_is_touched():
+    """configs[] sub-runs are measured with --full only: asking for them in a plain run is a usage error, not a silent no-op"""
+    r = _run(["--steps", "1", "--warmup", "0", "--workload", "hex6", "--configs", "hex6c"], timeout=120)
+    assert r.returncode == 2 and "--configs" in r.stderr and "--full" in r.stderr
+    assert "no GPU visible" not in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("workload,configs", [("hex16", "cavity10c"), ("cavity12c", "")])
 def test_bench_two_ranks_self_launched(workload, configs, tmp_path):
@@ -49,7 +56,7 @@ def test_bench_two_ranks_self_launched(workload, configs, tmp_path):
     transport against the oracle's MultiDomain), cpu_baseline (rank 0's oracle on its own sub-domain), how the records travelled
     (transport, communicator size, self-check), and configs[] = the polyhedral constraints-on workload (BASELINE configs[4]) beside
     the hex headline"""
-    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--workload", workload, "--configs", configs, "--config-steps", "3"],
+    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--workload", workload, "--full", "--configs", configs, "--config-steps", "3"],
              env={"SMOOTHMESH_BACKEND": "gloo", "SMOOTHMESH_SHARE_GPU": "1"}, detail=tmp_path / "detail.json")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     c_ = _compact(r)
@@ -202,7 +209,7 @@ def test_compact_line_is_short_strict_and_complete():
 
 @pytest.mark.gpu
 def test_bench_exits_nonzero_when_a_comparison_fails(tmp_path):
-    r = _run(["--steps", "3", "--warmup", "1", "--workload", "hex10", "--configs", "hex10c", "--config-steps", "2"],
+    r = _run(["--steps", "3", "--warmup", "1", "--workload", "hex10", "--full", "--configs", "hex10c", "--config-steps", "2"],
              env={"SMOOTHMESH_BENCH_FALSIFY": "hex10c"}, detail=tmp_path / "detail.json")
     d = _compact(r)
     assert r.returncode == 1 and d["exit_code"] == 1 and d["failures"] == ["hex10c: parity_check not ok"]
@@ -212,7 +219,7 @@ def test_bench_exits_nonzero_when_a_comparison_fails(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line_carries_the_other_configs(tmp_path):
-    r = _run(["--steps", "5", "--warmup", "1", "--workload", "hex12", "--configs", "hex12c,cavity10c", "--config-steps", "3"],
+    r = _run(["--steps", "5", "--warmup", "1", "--workload", "hex12", "--full", "--configs", "hex12c,cavity10c", "--config-steps", "3"],
              detail=tmp_path / "detail.json")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     c_ = _compact(r)
@@ -293,3 +300,32 @@ def test_bench_dumps_what_the_timed_steps_computed(tmp_path, oracle_lib):
     assert np.allclose(a["residual"], res[2:], rtol=1e-10, atol=0)
     o = orc.points()
     assert np.max(np.abs(a["points"] - o)) / np.max(np.abs(o)) <= 1e-10
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_same_steps_as_full_and_nothing_else(tmp_path):
+    """a plain run (no --full) carries the headline and leaves out what takes runs of its own (configs[], the oracle leg, the
+    per-kernel pass, at_100_iters); what its timed steps computed is bit for bit what a --full run's timed steps computed"""
+    import numpy as np
+    docs, dumps = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--configs", "hex10c", "--config-steps", "2"])):
+        r = _run(["--steps", "7", "--warmup", "2", "--workload", "hex10", "--dump-outputs", str(tmp_path / mode)] + extra,
+                 detail=tmp_path / f"{mode}.json")
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        c_ = _compact(r)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert c_[k] is not None, k
+        assert c_["steps"] == 7 and c_["warmup"] == 2 and c_["value"] > 0 and c_["exit_code"] == 0
+        docs[mode] = json.load(open(tmp_path / f"{mode}.json"))
+        dumps[mode] = {n: np.load(tmp_path / mode / f"{n}.npy") for n in ("points", "residual", "nFrozenPoints")}
+    p, f = docs["plain"], docs["full"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup"):
+        assert p[k] == f[k], k
+    assert p["ms_per_step"] > 0 and p["ms_per_step_cold"] > 0
+    for k in ("configs", "cpu_baseline", "parity_check", "roofline", "kernels", "at_100_iters", "near_ties"):
+        assert k not in p, k
+        assert k in f, k
+    assert [c["workload"] for c in p["configs_summary"]] == ["hex10"]
+    assert f["parity_check"]["ok"] and [c["workload"] for c in f["configs"]] == ["hex10c"]
+    for n in dumps["plain"]:
+        assert np.array_equal(dumps["plain"][n], dumps["full"][n]), n
