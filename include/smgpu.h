@@ -204,6 +204,17 @@ int smgpu_quality_coupled_report(smgpu_handle* h, const smgpu_quality_params* p,
 /* names and sizes as smgpu_quality_field */
 int smgpu_quality_coupled_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n);
 
+/* ---- the failing elements of the report as sets (DESIGN.md "Mesh quality", 10.5) ---------------------------------------
+ * names and order: DESIGN.md 10.5 (nonOrthoFaces, skewFaces, wrongOrientedFaces, zeroAreaFaces, zeroVolumeCells,
+ * nonClosedCells, highAspectRatioCells).  counts[7] always filled; each equals the report's count under the same p.
+ * ids: the seven sets concatenated in that order, each ascending, written when ids != NULL and cap >= sum(counts); ids != NULL
+ * with a smaller cap is an error (counts still filled).  ids == NULL: counts only.  Refusals, side effects and state as
+ * smgpu_mesh_quality (serial, refused on a halo engine) and smgpu_quality_coupled_report (a sub-domain, on the geometry of the
+ * last pack; a processor face is a member only on the side that counts it).  Ids are local. */
+int smgpu_quality_sets(smgpu_handle* h, const smgpu_quality_params* p, int64_t counts[7], int32_t* ids, int64_t cap);
+int smgpu_quality_coupled_sets(smgpu_handle* h, const smgpu_quality_params* p, const void* recvCc,
+                               int64_t counts[7], int32_t* ids, int64_t cap);
+
 /* Timing: when enabled every kernel launch is bracketed by hipEvents on the handle's stream. */
 int smgpu_enable_timing(smgpu_handle* h, int32_t on);
 int smgpu_get_counters(smgpu_handle* h, smgpu_counters* out);

@@ -173,6 +173,8 @@ SYMBOLS = {
     "smgpu_quality_coupled_pack": (C.c_int, [C.c_void_p, C.POINTER(QualityCoupling), C.c_void_p, C.POINTER(C.c_int64)]),
     "smgpu_quality_coupled_report": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(QualityPart)]),
     "smgpu_quality_coupled_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),
+    "smgpu_quality_sets": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.POINTER(C.c_int64), c_i32p, C.c_int64]),
+    "smgpu_quality_coupled_sets": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(C.c_int64), c_i32p, C.c_int64]),
     "smgpu_debug_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_addressing": (C.c_int, [C.c_void_p, C.c_char_p, c_i32p, c_i32p, C.POINTER(C.c_int64)]),
     "smgpu_debug_propose": (C.c_int, [C.c_void_p]),

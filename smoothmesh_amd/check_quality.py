@@ -1,9 +1,12 @@
-"""python -m smoothmesh_amd.check_quality -case <dir> [-parallel] [-time <t|constant|latestTime>]
+"""python -m smoothmesh_amd.check_quality -case <dir> [-parallel] [-time <t|constant|latestTime>] [-writeSets]
 
 Prints the mesh quality report of a case in the format of `smoothMesh -checkQuality` (one block, label "mesh"): the serial
 case, or with -parallel every processorN/ sub-domain combined into the report of the whole mesh (smoothmesh_amd/quality.py).
 Ids are global where the sub-domains carry cellProcAddressing and faceProcAddressing, else -1.  Time selection as smoothMesh:
 the latest time directory by default, else constant; the faces from the newest instance at or before it, the points likewise.
+-writeSets: then the failing elements as OpenFOAM sets into <points instance>/sets, i.e. <time>/polyMesh/sets
+or constant/polyMesh/sets, in every processorN/ with local ids under -parallel; writeFormat and writeCompression from
+system/controlDict.  One "<<Writing" line per written set follows the report (with " in processorN" under -parallel).
 """
 import os
 import re
@@ -54,17 +57,48 @@ def _addressing(root, name):
     return read_label_list(os.path.join(d, name)).astype(np.int64)
 
 
-def case_quality(case, parallel=False, time=None, device=0):
-    """MeshQuality of the serial case, or DecomposedMeshQuality of its processorN/ sub-domains"""
+def _control(case):
+    """(binary, compressed) from system/controlDict's writeFormat and writeCompression"""
+    try:
+        with open(os.path.join(case, "system", "controlDict")) as f:
+            txt = f.read()
+    except OSError:
+        return False, False
+    fmt = re.search(r"^\s*writeFormat\s+(\w+)\s*;", txt, re.M)
+    cmp = re.search(r"^\s*writeCompression\s+(\w+)\s*;", txt, re.M)
+    return (fmt is not None and fmt.group(1) == "binary",
+            cmp is not None and cmp.group(1) in ("on", "true", "yes", "compressed"))
+
+
+def _write_sets(pts_dir, root, sets, control):
+    from .polymesh import set_write_compression
+    from .quality import write_quality_sets
+    binary, compressed = control
+    set_write_compression(compressed)
+    try:
+        return write_quality_sets(pts_dir, os.path.relpath(pts_dir, root), sets, binary)
+    finally:
+        set_write_compression(False)
+
+
+def case_quality(case, parallel=False, time=None, device=0, write_sets=False):
+    """MeshQuality of the serial case, or DecomposedMeshQuality of its processorN/ sub-domains.  write_sets: also write the
+    failing elements as sets into the points instance (every processorN/ under parallel) -> (quality, [(rank, name, size)])"""
+    control = _control(case)
     if not parallel:
         from .engine import SmoothEngine
-        e = SmoothEngine(_read(case, _select_time(case, time)), device=device)
+        t = _select_time(case, time)
+        e = SmoothEngine(_read(case, t), device=device)
         try:
-            return e.mesh_quality()
+            q = e.mesh_quality()
+            if not write_sets:
+                return q
+            written = _write_sets(_instance(case, t, "points"), case, e.quality_sets(), control)
+            return q, [(None, n, k) for n, k in written]
         finally:
             e.close()
     from .decompose import SubDomain
-    from .quality import decomposed_mesh_quality
+    from .quality import decomposed_mesh_quality, decomposed_quality_sets
     procs = sorted((int(d[9:]), d) for d in os.listdir(case) if re.fullmatch(r"processor\d+", d))
     if not procs or [p[0] for p in procs] != list(range(len(procs))):
         raise SystemExit(f"check_quality: no processor0 .. processorN-1 directories in {case}")
@@ -76,7 +110,21 @@ def case_quality(case, parallel=False, time=None, device=0):
         faces = _addressing(root, "faceProcAddressing")
         subs.append(SubDomain(m, r, len(procs), np.zeros(0, np.int64), _addressing(root, "cellProcAddressing"),
                               None if faces is None else np.abs(faces) - 1))          # decomposePar: +-(global face + 1)
-    return decomposed_mesh_quality(subs, device=device)
+    q = decomposed_mesh_quality(subs, device=device)
+    if not write_sets:
+        return q
+    written = []
+    for (r, d), sets in zip(procs, decomposed_quality_sets(subs, device=device)):
+        root = os.path.join(case, d)
+        written += [(r, n, k) for n, k in _write_sets(_instance(root, t, "points"), root, sets, control)]
+    return q, written
+
+
+def format_written(written):
+    """the "<<Writing" lines of -writeSets: (rank or None, name, size) in writing order"""
+    from .quality import format_sets_written
+    return "".join(format_sets_written([(n, k)]).rstrip("\n") + ("" if r is None else f" in processor{r}") + "\n"
+                   for r, n, k in written)
 
 
 def main(argv=None):
@@ -85,10 +133,14 @@ def main(argv=None):
     ap.add_argument("-case", default=".")
     ap.add_argument("-parallel", action="store_true")
     ap.add_argument("-time", default=None, help="a time, constant or latestTime (default: the latest time, else constant)")
+    ap.add_argument("-writeSets", action="store_true", help="write the failing faces and cells as sets into the points instance")
     a = ap.parse_args(argv)
     from .quality import format_report
-    q = case_quality(a.case, a.parallel, a.time)
-    sys.stdout.write(format_report(q, "mesh"))
+    if not a.writeSets:
+        sys.stdout.write(format_report(case_quality(a.case, a.parallel, a.time), "mesh"))
+        return 0
+    q, written = case_quality(a.case, a.parallel, a.time, write_sets=True)
+    sys.stdout.write(format_report(q, "mesh") + format_written(written))
     return 0
 
 

@@ -95,7 +95,7 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "faceAngleConstraint", "minEdgeLength", "totalMinFreeze", "minAngle", "maxAngle",
                                "layerMaxBlendingFraction", "layerEdgeLength", "layerExpansionRatio", "minLayers",
                                "maxLayers", "layerPatches", "smoothingPatches", "internalSmoothingBlendingFraction",
-                               "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality"};
+                               "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -107,6 +107,8 @@ Options parseArgs(int argc, char** argv) {
                       "       [-maxStepLength x] [-relStepFrac x] [-totalMinFreeze b] [-edgeAngleConstraint b] [-faceAngleConstraint b]\n"
                       "       [-minAngle deg] [-maxAngle deg] [-writeInterval n] [-writeFormat ascii|binary] [-device n]\n"
                       "       [-checkQuality b]   (mesh quality report of the initial and the final mesh, serial runs only)\n"
+                      "       [-writeSets b]      (with -checkQuality: the final mesh's failing faces and cells as sets in\n"
+                      "        <last written time>/polyMesh/sets)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -502,6 +504,10 @@ int main(int argc, char** argv) {
     if (checkQuality && opt.parallel)
         fatal("-checkQuality is not available with -parallel: the quality report does not exchange the neighbour cell centres across "
               "processor patches (run it on the reconstructed case)");
+    const bool writeSets = opt.getB("writeSets", false);
+    if (writeSets && opt.parallel)
+        fatal("-writeSets is not available with -parallel: it writes the sets of the -checkQuality report, which is serial only");
+    if (writeSets && !checkQuality) fatal("-writeSets needs -checkQuality true: the sets are the failing elements of the quality report");
     // SMOOTHMESH_TIMELINE=1: where this process's wall time goes, one stderr line per stage (seconds since main started)
     const bool timeline = std::getenv("SMOOTHMESH_TIMELINE") && std::atoi(std::getenv("SMOOTHMESH_TIMELINE")) > 0;
     auto mark = [&](const char* what) { if (timeline) std::fprintf(stderr, "[smoothMesh %8.3f s] %s\n", secondsSince(t0), what); };
@@ -1147,10 +1153,12 @@ int main(int argc, char** argv) {
     }
     enableExchangeStream();
 
+    std::string lastWritten;   // the time of the last mesh write ("" until there is one)
     auto writeMesh = [&](double timeValue) {
         const auto tw = std::chrono::steady_clock::now();
         struct Stop { double& acc; std::chrono::steady_clock::time_point a; ~Stop() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); } } stop{tWrite, tw};
         const std::string tn = timeName(timeValue);
+        lastWritten = tn;
         OUT("Writing new mesh to time %s\n\n", tn.c_str());
         for (Rank& K : R) {
             std::vector<double> pts((size_t)K.mesh.nPoints() * 3);
@@ -1251,6 +1259,41 @@ int main(int argc, char** argv) {
     }
 
     if (checkQuality) reportQuality("final mesh");
+    // -writeSets: the final mesh's failing elements (include/smgpu.h smgpu_quality_sets) as topoSet files next to
+    // the points just written; the input case is never touched.  Only non-empty sets, as checkMesh.
+    if (writeSets) {
+        static const char* const kSetName[7] = {"nonOrthoFaces", "skewFaces", "wrongOrientedFaces", "zeroAreaFaces", "zeroVolumeCells",
+                                                "nonClosedCells", "highAspectRatioCells"};
+        static const char* const kSetWords[7] = {"non-orthogonal faces", "skew faces", "wrongly oriented faces", "zero area faces",
+                                                 "zero or negative volume cells", "non-closed cells", "high aspect ratio cells"};
+        if (lastWritten.empty()) OUTS("    no mesh was written: no sets written\n");
+        else {
+            const auto tw = std::chrono::steady_clock::now();
+            // one device call when the sets hold at most nFaces + nCells ids; else again with the size the refused call reported
+            int64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
+            std::vector<int32_t> ids((size_t)K0.mesh.nFaces() + (size_t)K0.mesh.nCells + 1);
+            if (smgpu_quality_sets(K0.h, nullptr, counts, ids.data(), (int64_t)ids.size()) != 0) {
+                int64_t total = 0;
+                for (int64_t c : counts) total += c;
+                if (total <= (int64_t)ids.size()) check(1, "smgpu_quality_sets");
+                ids.resize((size_t)total);
+                check(smgpu_quality_sets(K0.h, nullptr, counts, ids.data(), total), "smgpu_quality_sets");
+            }
+            const std::string loc = lastWritten + "/polyMesh/sets", dir = K0.root + "/" + loc;
+            int64_t at = 0;
+            for (int s = 0; s < 7; ++s) {
+                if (counts[s] > 0) {
+                    try {
+                        makeDirs(dir);
+                        writeLabelList(dir + "/" + kSetName[s], loc, kSetName[s], s < 4 ? "faceSet" : "cellSet", counts[s], ids.data() + at, binary, "");
+                    } catch (const std::exception& e) { fatal(e.what()); }
+                    OUT("    <<Writing %lld %s to set %s\n", (long long)counts[s], kSetWords[s], kSetName[s]);
+                }
+                at += counts[s];
+            }
+            tWrite += secondsSince(tw);
+        }
+    }
 
     // Near-tie census (include/smgpu.h): the engine's acos may differ from the reference's in the last bit, so only an angle
     // comparison with sides a few ulp apart could have been decided the other way by the reference -- say so when there was one

@@ -346,4 +346,193 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_part_final(const QFac
     *out = q;
 }
 
+// ---- the failing elements as sets (smgpu_quality_sets / _coupled_sets, DESIGN.md "Mesh quality", 10.5) ------------------------
+// Three steps, no atomics:
+//   1. flag passes (the report's face / cell passes with the same qFaceOne / qFaceCore / qCellOne records): one mask byte per
+//      element (bit s = member of set s of its kind), and per workgroup the member count of every set: cnt[row(s) + block];
+//   2. k_quality_set_scan: one exclusive scan of cnt in its flat order.  Rows go set by set (the 4 face sets over the face
+//      workgroups, then the 3 cell sets over the cell workgroups), so the scan is at once each workgroup's offset inside its
+//      set and the set's offset inside the concatenated output;
+//   3. k_quality_set_scatter: each workgroup walks its 2048 elements in 256-element rounds; a wave ranks its members with a
+//      64-bit ballot, the waves' totals go through LDS in wave order.  Ids come out ascending.
+constexpr int kQualityFaceSets = 4;   // nonOrthoFaces, skewFaces, wrongOrientedFaces, zeroAreaFaces
+constexpr int kQualityCellSets = 3;   // zeroVolumeCells, nonClosedCells, highAspectRatioCells
+constexpr int kQualitySets = kQualityFaceSets + kQualityCellSets;
+
+__device__ __forceinline__ unsigned qFaceBits(const QFace& e) {
+    return ((e.nSev | e.nErr) ? 1u : 0u) | (e.nSkew ? 2u : 0u) | (e.nWrong ? 4u : 0u) | (e.nZero ? 8u : 0u);
+}
+__device__ __forceinline__ unsigned qCellBits(const QCell& e) {
+    return (e.nNonPos ? 1u : 0u) | (e.nOpen ? 2u : 0u) | (e.nHigh ? 4u : 0u);
+}
+// the member counts of the workgroup's rounds (bits of each round's elements), set by set, into cnt[s * nB + blockIdx.x]
+template <int NS>
+__device__ __forceinline__ void qSetCountStore(const int (&waveCnt)[NS], int* __restrict__ sh /* [NS][4] */, int* __restrict__ cnt, int nB) {
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+        for (int s = 0; s < NS; ++s) sh[s * (kQualityBlock / 64) + w] = waveCnt[s];
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        int t = 0;
+        for (int v = 0; v < kQualityBlock / 64; ++v) t += sh[threadIdx.x * (kQualityBlock / 64) + v];
+        cnt[(size_t)threadIdx.x * nB + blockIdx.x] = t;
+    }
+}
+
+__global__ void __launch_bounds__(kQualityBlock) k_quality_face_flags(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                       const double* __restrict__ fArea, const double* __restrict__ cellCtr,
+                                                                       const int* __restrict__ own, const int* __restrict__ nei, QualityThresholds thr,
+                                                                       uint8_t* __restrict__ mask, int* __restrict__ cnt) {
+    __shared__ int sh[kQualityFaceSets * (kQualityBlock / 64)];
+    int wc[kQualityFaceSets] = {0, 0, 0, 0};
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int f = base + k * kQualityBlock;
+        unsigned bits = 0;
+        if (f < m.nFaces) {
+            QFace e = qFaceEmpty();
+            qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, thr, f, e, nullptr, nullptr);
+            bits = qFaceBits(e);
+            mask[f] = (uint8_t)bits;
+        }
+#pragma unroll
+        for (int s = 0; s < kQualityFaceSets; ++s) wc[s] += __popcll(__ballot((bits >> s) & 1u));
+    }
+    qSetCountStore(wc, sh, cnt, gridDim.x);
+}
+
+// k_quality_face_flags with processor faces, as k_quality_faces_coupled: a face the neighbour rank counts is in no set here
+__global__ void __launch_bounds__(kQualityBlock) k_quality_face_flags_coupled(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                               const double* __restrict__ fArea, const double* __restrict__ cellCtr,
+                                                                               const int* __restrict__ own, const int* __restrict__ nei,
+                                                                               const int* __restrict__ slot, const double* __restrict__ recvCc,
+                                                                               QualityThresholds thr, uint8_t* __restrict__ mask, int* __restrict__ cnt) {
+    __shared__ int sh[kQualityFaceSets * (kQualityBlock / 64)];
+    int wc[kQualityFaceSets] = {0, 0, 0, 0};
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int f = base + k * kQualityBlock;
+        unsigned bits = 0;
+        if (f < m.nFaces) {
+            QFace e = qFaceEmpty();
+            const int sl = f < m.nInternalFaces ? -1 : slot[f - m.nInternalFaces];
+            if (sl < 0) qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, thr, f, e, nullptr, nullptr);
+            else {
+                qFaceCore(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, own[f]), true, ldv(recvCc, sl & kQualitySlotMask), thr, f, e, nullptr, nullptr);
+                if (sl & kQualityNotCounted) e = qFaceEmpty();
+            }
+            bits = qFaceBits(e);
+            mask[f] = (uint8_t)bits;
+        }
+#pragma unroll
+        for (int s = 0; s < kQualityFaceSets; ++s) wc[s] += __popcll(__ballot((bits >> s) & 1u));
+    }
+    qSetCountStore(wc, sh, cnt, gridDim.x);
+}
+
+__global__ void __launch_bounds__(kQualityBlock) k_quality_cell_flags(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea,
+                                                                       QualityThresholds thr, uint8_t* __restrict__ mask, int* __restrict__ cnt) {
+    __shared__ int sh[kQualityCellSets * (kQualityBlock / 64)];
+    int wc[kQualityCellSets] = {0, 0, 0};
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int c = base + k * kQualityBlock;
+        unsigned bits = 0;
+        if (c < m.nCells) {
+            QCell e = qCellEmpty();
+            qCellOne(m, fCtr, fArea, thr, c, e, nullptr, nullptr, nullptr);
+            bits = qCellBits(e);
+            mask[c] = (uint8_t)bits;
+        }
+#pragma unroll
+        for (int s = 0; s < kQualityCellSets; ++s) wc[s] += __popcll(__ballot((bits >> s) & 1u));
+    }
+    qSetCountStore(wc, sh, cnt, gridDim.x);
+}
+
+// one workgroup of 1024: exclusive scan of cnt[0, n) into off[0, n] (off[n] = the total), tile by tile in index order; then the
+// seven set sizes: counts[s] = off[rowEnd(s)] - off[rowStart(s)]
+constexpr int kQualityScanBlock = 1024;
+__global__ void __launch_bounds__(kQualityScanBlock) k_quality_set_scan(const int* __restrict__ cnt, int n, int nFB, int nCB,
+                                                                         long long* __restrict__ off, long long* __restrict__ counts) {
+    __shared__ long long shW[kQualityScanBlock / 64];
+    __shared__ long long shCarry;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (threadIdx.x == 0) shCarry = 0;
+    __syncthreads();
+    for (int t0 = 0; t0 < n; t0 += kQualityScanBlock) {
+        const int i = t0 + threadIdx.x;
+        const long long v = i < n ? (long long)cnt[i] : 0;
+        long long x = v;                               // inclusive scan inside the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) shW[w] = x;
+        __syncthreads();
+        long long before = shCarry;
+        for (int u = 0; u < w; ++u) before += shW[u];
+        if (i < n) off[i] = before + x - v;
+        __syncthreads();                               // every thread has read shCarry and shW
+        if (threadIdx.x == kQualityScanBlock - 1) shCarry = before + x;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) off[n] = shCarry;
+    __syncthreads();
+    if (threadIdx.x < kQualitySets) {
+        const int s = threadIdx.x;
+        const int b = s < kQualityFaceSets ? s * nFB : kQualityFaceSets * nFB + (s - kQualityFaceSets) * nCB;
+        const int e = b + (s < kQualityFaceSets ? nFB : nCB);
+        counts[s] = off[e] - off[b];
+    }
+}
+
+// workgroups [0, nFB) take the face sets of face workgroup b, the rest the cell sets of cell workgroup b - nFB (mask[nFaces + c]).
+// A member's place: the scan's offset of (set, workgroup), plus the members of the earlier rounds, of the earlier waves of this
+// round, and of the lower lanes of its wave.  pos < total always holds (the masks are the ones counted); it is checked anyway.
+__global__ void __launch_bounds__(kQualityBlock) k_quality_set_scatter(const uint8_t* __restrict__ mask, int nFaces, int nCells, int nFB, int nCB,
+                                                                        const long long* __restrict__ off, int* __restrict__ ids, long long total) {
+    __shared__ int sh[2][kQualityFaceSets][kQualityBlock / 64];
+    const bool faces = (int)blockIdx.x < nFB;
+    const int b = faces ? (int)blockIdx.x : (int)blockIdx.x - nFB;
+    const int n = faces ? nFaces : nCells;
+    const int ns = faces ? kQualityFaceSets : kQualityCellSets;
+    const uint8_t* mk = faces ? mask : mask + nFaces;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    long long run[kQualityFaceSets];
+    for (int s = 0; s < kQualityFaceSets; ++s)
+        run[s] = s < ns ? off[faces ? s * nFB + b : kQualityFaceSets * nFB + s * nCB + b] : 0;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int i0 = b * (kQualityPer * kQualityBlock) + k * kQualityBlock;
+        if (i0 >= n) break;                            // uniform in the workgroup
+        const int i = i0 + threadIdx.x;
+        const unsigned bits = i < n ? mk[i] : 0u;
+        const int buf = k & 1;                         // two LDS buffers: round k + 1 writes while no wave still reads round k's
+        unsigned long long bal[kQualityFaceSets];
+#pragma unroll
+        for (int s = 0; s < kQualityFaceSets; ++s) {
+            bal[s] = __ballot((bits >> s) & 1u);
+            if (lane == 0) sh[buf][s][w] = __popcll(bal[s]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < kQualityFaceSets; ++s) {
+            if (s >= ns) break;
+            int before = 0, all = 0;
+            for (int v = 0; v < kQualityBlock / 64; ++v) {
+                const int c = sh[buf][s][v];
+                if (v < w) before += c;
+                all += c;
+            }
+            if ((bits >> s) & 1u) {
+                const long long pos = run[s] + before + __popcll(bal[s] & below);
+                if (pos < total) ids[pos] = i;
+            }
+            run[s] += all;
+        }
+    }
+}
+
 }  // namespace smgpu

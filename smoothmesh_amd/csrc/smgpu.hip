@@ -3414,6 +3414,104 @@ int smgpu_quality_coupled_field(smgpu_handle* h, const char* name, const void* r
     });
 }
 
+// ---- the failing elements as sets (DESIGN.md "Mesh quality", 10.5) --------------------------------------------------------
+// `flags(mask, cnt)` launches the face flag pass (mask[0, F), cnt rows of the face sets) and the cell flag pass (mask[F, F + C),
+// cnt + 4 * nFB); then the scan, one copy of the counts, and when ids fit the scatter and one copy of the ids.  Every buffer is
+// this call's own (outside deviceBytes, as the field buffers).
+extern "C++" {
+template <class Flags>
+static int qualitySets(smgpu_handle* h, const char* api, int64_t counts[7], int32_t* ids, int64_t cap, Flags flags) {
+    const MeshView& m = h->mv;
+    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+    const int nCnt = kQualityFaceSets * nFB + kQualityCellSets * nCB;
+    uint8_t* mask = nullptr;
+    int* cnt = nullptr;
+    long long *off = nullptr, *dCounts = nullptr;
+    int* dIds = nullptr;
+    int rc = 0;
+    auto hipFail = [&](hipError_t e) { rc = fail(std::string(api) + ": " + hipGetErrorString(e)); };
+    hipError_t e = hipMalloc((void**)&mask, (size_t)std::max<int64_t>(1, (int64_t)m.nFaces + m.nCells));
+    if (e == hipSuccess) e = hipMalloc((void**)&cnt, sizeof(int) * (size_t)std::max(1, nCnt));
+    if (e == hipSuccess) e = hipMalloc((void**)&off, sizeof(long long) * ((size_t)nCnt + 1));
+    if (e == hipSuccess) e = hipMalloc((void**)&dCounts, sizeof(long long) * kQualitySets);
+    if (e != hipSuccess) hipFail(e);
+    if (rc == 0) rc = flags(mask, cnt);
+    if (rc == 0) {
+        hipLaunchKernelGGL(k_quality_set_scan, dim3(1), dim3(kQualityScanBlock), 0, h->stream, cnt, nCnt, nFB, nCB, off, dCounts);
+        long long hc[kQualitySets];
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(hc, dCounts, sizeof(hc), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) hipFail(e);
+        int64_t total = 0;
+        for (int s = 0; s < kQualitySets && rc == 0; ++s) { counts[s] = hc[s]; total += hc[s]; }
+        if (rc == 0 && ids && cap < total)
+            rc = fail(std::string(api) + ": ids holds " + std::to_string(cap) + " labels, the sets need " + std::to_string(total));
+        if (rc == 0 && ids && total > 0) {
+            e = hipMalloc((void**)&dIds, sizeof(int) * (size_t)total);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(k_quality_set_scatter, dim3(nFB + nCB), dim3(kQualityBlock), 0, h->stream, mask, m.nFaces, m.nCells, nFB, nCB, off, dIds,
+                                   (long long)total);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(ids, dIds, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess) hipFail(e);
+        }
+    }
+    (void)hipStreamSynchronize(h->stream);
+    for (void* p : {(void*)mask, (void*)cnt, (void*)off, (void*)dCounts, (void*)dIds})
+        if (p) (void)hipFree(p);
+    return rc;
+}
+}  // extern "C++"
+
+int smgpu_quality_sets(smgpu_handle* h, const smgpu_quality_params* p, int64_t counts[7], int32_t* ids, int64_t cap) {
+    if (!h || !counts) return fail("null argument");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityEnsure(h)) return 1;
+    if (qualityGeometry(h)) return 1;
+    const MeshView& m = h->mv;
+    const QualityThresholds thr = qualityThresholds(p);
+    return qualitySets(h, "smgpu_quality_sets", counts, ids, cap, [&](uint8_t* mask, int* cnt) {
+        const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+        const State& s = h->st;
+        if (nFB > 0)
+            hipLaunchKernelGGL(k_quality_face_flags, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qOwn,
+                               h->qNei, thr, mask, cnt);
+        if (nCB > 0)
+            hipLaunchKernelGGL(k_quality_cell_flags, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, mask + m.nFaces,
+                               cnt + (size_t)kQualityFaceSets * nFB);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? 0 : fail(std::string("smgpu_quality_sets: ") + hipGetErrorString(e));
+    });
+}
+
+int smgpu_quality_coupled_sets(smgpu_handle* h, const smgpu_quality_params* p, const void* recvCc, int64_t counts[7], int32_t* ids, int64_t cap) {
+    if (!h || !counts) return fail("null argument");
+    const char* api = "smgpu_quality_coupled_sets";
+    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
+    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
+        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
+    if (h->qNProc > 0 && !recvCc) return fail(std::string(api) + ": null recvCc");
+    HIP_OK(hipSetDevice(h->device));
+    const MeshView& m = h->mv;
+    const QualityThresholds thr = qualityThresholds(p);
+    return qualitySets(h, api, counts, ids, cap, [&](uint8_t* mask, int* cnt) {
+        const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+        const State& s = h->st;
+        if (nFB > 0)
+            hipLaunchKernelGGL(k_quality_face_flags_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr,
+                               h->qOwn, h->qNei, h->qSlot, (const double*)recvCc, thr, mask, cnt);
+        if (nCB > 0)
+            hipLaunchKernelGGL(k_quality_cell_flags, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, mask + m.nFaces,
+                               cnt + (size_t)kQualityFaceSets * nFB);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? 0 : fail(std::string(api) + ": " + hipGetErrorString(e));
+    });
+}
+
 // ---- debug / parity access -------------------------------------------------------------------
 int smgpu_debug_propose(smgpu_handle* h) {
     if (!h) return fail("null handle");

@@ -81,6 +81,17 @@ class MeshQuality:
 
 
 QUALITY_FIELDS = ("cellVolume", "cellOpenness", "cellAspectRatio", "faceNonOrthogonality", "faceSkewness")
+# the failing elements of the report as sets (DESIGN.md "Mesh quality", 10.5), in smgpu_quality_sets' order: name, topoSet class,
+# the report counts whose sum is the set's size, and the words of the "<<Writing" line
+QUALITY_SETS = (
+    ("nonOrthoFaces", "faceSet", ("nSevereNonOrth", "nErrorNonOrth"), "non-orthogonal faces"),
+    ("skewFaces", "faceSet", ("nSkewFaces",), "skew faces"),
+    ("wrongOrientedFaces", "faceSet", ("nWrongOrientedFaces",), "wrongly oriented faces"),
+    ("zeroAreaFaces", "faceSet", ("nZeroAreaFaces",), "zero area faces"),
+    ("zeroVolumeCells", "cellSet", ("nNonPositiveVolume",), "zero or negative volume cells"),
+    ("nonClosedCells", "cellSet", ("nOpenCells",), "non-closed cells"),
+    ("highAspectRatioCells", "cellSet", ("nHighAspectCells",), "high aspect ratio cells"),
+)
 
 
 def patch_arrays(mesh: PolyMesh, layerPatches):
@@ -431,6 +442,29 @@ class SmoothEngine:
         self._check(self._lib.smgpu_quality_field(self._h, name.encode(), _p(out, _ffi.c_f64p), C.byref(n)))
         return out
 
+    def _sets(self, call, *args):
+        # one call when the sets hold at most nFaces + nCells ids (an element in several sets may exceed that: then again with
+        # the exact size, which the refused call has reported)
+        counts = (C.c_int64 * 7)()
+        ids = np.empty(max(1, self.mesh.nFaces + self.mesh.nCells), np.int32)
+        if call(self._h, *args, counts, _p(ids, _ffi.c_i32p), len(ids)):
+            if sum(counts) <= len(ids):
+                self._check(1)
+            ids = np.empty(sum(counts), np.int32)
+            self._check(call(self._h, *args, counts, _p(ids, _ffi.c_i32p), len(ids)))
+        out, at = {}, 0
+        for (name, *_), n in zip(QUALITY_SETS, counts):
+            out[name] = ids[at:at + n].copy()
+            at += n
+        return out
+
+    def quality_sets(self, nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0) -> dict:
+        """The failing elements of mesh_quality's report as sets (include/smgpu.h, smgpu_quality_sets): {name: ascending int32
+        ids} for every name of QUALITY_SETS, empty ones included; each size equals the report's count.  Refused on an engine
+        with a halo; leaves the points and the loop as they were."""
+        p = _ffi.QualityParams(nonOrthThreshold, skewThreshold, closedThreshold, aspectThreshold)
+        return self._sets(self._lib.smgpu_quality_sets, C.byref(p))
+
     # -- mesh quality of a sub-domain (DESIGN.md "Mesh quality", 10.4; smoothmesh_amd/quality.py drives these) -------------
     def quality_coupling(self, rank=None):
         """(myRank, [(patchStart, patchSize, neighbRank)]) of this engine's processor patches in boundary-file order.  Refuses
@@ -466,6 +500,12 @@ class SmoothEngine:
         q = _ffi.QualityPart()
         self._check(self._lib.smgpu_quality_coupled_report(self._h, C.byref(p), C.c_void_p(recvCc or None), C.byref(q)))
         return {n: getattr(q, n) for n, _ in q._fields_}
+
+    def quality_coupled_sets(self, recvCc, nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0) -> dict:
+        """smgpu_quality_coupled_sets: as quality_sets for this rank, local ids; a processor face is a member only on the side
+        that counts it"""
+        p = _ffi.QualityParams(nonOrthThreshold, skewThreshold, closedThreshold, aspectThreshold)
+        return self._sets(self._lib.smgpu_quality_coupled_sets, C.byref(p), C.c_void_p(recvCc or None))
 
     def quality_coupled_field(self, name, recvCc) -> np.ndarray:
         """smgpu_quality_coupled_field: as quality_field, processor faces with the internal-face definitions"""

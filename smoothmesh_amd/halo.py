@@ -768,6 +768,13 @@ class DistributedSmoother:
         recv = self._quality_exchange()
         return self.engine.quality_coupled_field(name, recv.data_ptr())
 
+    def quality_sets(self, **thresholds):
+        """this rank's failing elements as sets: {name: local ids}; a processor face is a member only on the
+        lower rank.  A collective (the exchange of mesh_quality); the sets themselves stay on their rank."""
+        from .quality import QUALITY_DEFAULTS
+        recv = self._quality_exchange()
+        return self.engine.quality_coupled_sets(recv.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds})
+
 
 class LocalMultiSmoother:
     """All sub-domains in ONE process on ONE device (engines side by side), the exchange done by
@@ -892,3 +899,9 @@ class LocalMultiSmoother:
         """[per-rank array] of a quality field (engine.QUALITY_FIELDS); processor faces carry their values on both sides"""
         from .quality import local_quality_field
         return local_quality_field([st.eng for st in self.states], name, self.device)
+
+    def quality_sets(self, **thresholds):
+        """[per-rank {name: local ids}] of the failing elements; a processor face is a member only on the lower
+        rank.  Between iterations only; the loop is left as it was."""
+        from .quality import local_quality_sets
+        return local_quality_sets([st.eng for st in self.states], self.device, thresholds)

@@ -5,12 +5,13 @@ take the internal-face definitions with the neighbour rank's cell centre, and co
 combine_quality folds the records in a fixed order into the report the serial engine gives for the undecomposed mesh.
 Drivers: decomposed_mesh_quality (sub-domains without a point halo, one process), LocalMultiSmoother.mesh_quality and
 DistributedSmoother.mesh_quality (smoothmesh_amd/halo.py); the shell tool is smoothmesh_amd/check_quality.py.
+The failing elements as sets: decomposed_quality_sets, the drivers' quality_sets, write_quality_sets.
 """
 from dataclasses import dataclass, fields
 
 import numpy as np
 
-from .engine import MeshQuality, QUALITY_FIELDS  # noqa: F401
+from .engine import MeshQuality, QUALITY_FIELDS, QUALITY_SETS  # noqa: F401
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
 _COUNTS = ("nNonPositiveVolume", "nZeroAreaFaces", "nSevereNonOrth", "nErrorNonOrth", "nSkewFaces", "nWrongOrientedFaces",
@@ -142,6 +143,13 @@ def local_quality_field(engines, name, torch_device):
     return [e.quality_coupled_field(name, t.data_ptr()) for e, t in zip(engines, recv)]
 
 
+def local_quality_sets(engines, torch_device, thresholds):
+    """[per-rank {name: local ids}]: a processor face is a member only on the rank that counts it"""
+    couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
+    recv = local_exchange(engines, couplings, torch_device)
+    return [e.quality_coupled_sets(t.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds}) for e, t in zip(engines, recv)]
+
+
 def decomposed_mesh_quality(subs, device=0, foam_variant=None, **thresholds) -> DecomposedMeshQuality:
     """Quality report of a decomposed mesh whose sub-domains (decompose.SubDomain or PolyMesh, rank = position in the list) need
     no point halo: one plain engine per sub-domain on one device.  Only the processor patches couple them.  Ids are global where
@@ -162,6 +170,51 @@ def decomposed_mesh_quality(subs, device=0, foam_variant=None, **thresholds) -> 
     finally:
         for e in engines:
             e.close()
+
+
+def decomposed_quality_sets(subs, device=0, foam_variant=None, **thresholds) -> list:
+    """The failing elements of decomposed_mesh_quality's report as sets: one {name: local ids} per rank.
+    Mapped through cell / face addressing, the ranks' sets are disjoint and their union is the undecomposed mesh's set."""
+    import torch
+    from .engine import SmoothEngine
+    meshes = [getattr(s, "mesh", s) for s in subs]
+    engines = []
+    try:
+        for m in meshes:
+            e = SmoothEngine(m, device=device)
+            if len(meshes) > 1:
+                e.set_device_share(len(meshes))
+            if foam_variant is not None:
+                e.set_foam_variant(foam_variant)
+            engines.append(e)
+        return local_quality_sets(engines, torch.device("cuda", device), thresholds)
+    finally:
+        for e in engines:
+            e.close()
+
+
+def write_quality_sets(polyMeshDir, location, sets, binary=False):
+    """the non-empty sets as OpenFOAM topoSet files <polyMeshDir>/sets/<name> (class faceSet / cellSet, location
+    "<location>/sets"), as checkMesh writes them; compressed when polymesh.set_write_compression is on.  Nothing else in the
+    directory is touched.  Returns [(name, size)] of the files written, in QUALITY_SETS order."""
+    import os
+    from .polymesh import write_label_list
+    d = os.path.join(polyMeshDir, "sets")
+    written = []
+    for name, cls, _, _ in QUALITY_SETS:
+        ids = np.asarray(sets.get(name, ()), dtype=np.int32)
+        if ids.size == 0:
+            continue
+        os.makedirs(d, exist_ok=True)
+        write_label_list(os.path.join(d, name), ids, location.rstrip("/") + "/sets", name, cls, binary)
+        written.append((name, int(ids.size)))
+    return written
+
+
+def format_sets_written(written):
+    """the lines smoothMesh -writeSets prints after the report block, one per written set"""
+    desc = {name: words for name, _, _, words in QUALITY_SETS}
+    return "".join(f"    <<Writing {n} {desc[name]} to set {name}\n" for name, n in written)
 
 
 def format_report(q, which="mesh"):
