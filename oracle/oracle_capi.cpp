@@ -1,5 +1,5 @@
 // oracle_capi.cpp -- plain C entry points over the oracle for ctypes (tests, smoke, bench's
-// cpu_baseline leg only).  TEST INFRASTRUCTURE ONLY; PARITY UNPINNED (see smooth_oracle.hpp).
+// cpu_baseline leg only).  TEST INFRASTRUCTURE ONLY; What pins it and what does not: smooth_oracle.hpp.
 #include <cstring>
 #include <string>
 
@@ -78,6 +78,10 @@ void orc_set_points(void* h, const double* pts) {
 
 int orc_num_edges(void* h) { return int(static_cast<Domain*>(h)->edges.size()); }
 
+// face centres / areas and cell centres of the current points and nothing else: the geometry that the reference pin hands to
+// the stand-in mesh (oracle/ref_ffi.py)
+void orc_update_geometry(void* h) { static_cast<Domain*>(h)->updateGeometry(); }
+
 // run one iteration's phases without committing (operator-level parity checks)
 void orc_phaseA(void* h) { static_cast<Domain*>(h)->phaseA(); }
 void orc_phaseB(void* h) { static_cast<Domain*>(h)->phaseB(); }
@@ -132,7 +136,7 @@ long long orc_get_field(void* h, const char* name, double* out) {
 }
 
 // Addressing as CSR (offsets has n+1 entries).  kind: pointCells, pointFaces, pointEdges, pointPoints,
-// edgeFaces, edgeCells, cellFaces, edges (returned as 2 per row).  Returns nnz; call with NULLs to size.
+// edgeFaces, edgeCells, cellFaces, cellPoints, edges (returned as 2 per row).  Returns nnz; call with NULLs to size.
 long long orc_get_addressing(void* h, const char* kind, int* offsets, int* values) {
     Domain* d = static_cast<Domain*>(h);
     const std::string n(kind);
@@ -144,6 +148,7 @@ long long orc_get_addressing(void* h, const char* kind, int* offsets, int* value
     else if (n == "edgeFaces") ll = &d->edgeFaces;
     else if (n == "edgeCells") ll = &d->edgeCells;
     else if (n == "cellFaces") ll = &d->cellFaces;
+    else if (n == "cellPoints") ll = &d->cellPoints;
     else if (n == "edges") {
         if (values) for (size_t e = 0; e < d->edges.size(); ++e) { values[2 * e] = d->edges[e][0]; values[2 * e + 1] = d->edges[e][1]; }
         return (long long)d->edges.size() * 2;

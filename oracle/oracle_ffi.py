@@ -1,6 +1,6 @@
 """ctypes wrapper over oracle/liboracle.so.  TEST INFRASTRUCTURE ONLY: imported by tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg; never by smoothmesh_amd/.
-PARITY UNPINNED (see oracle/smooth_oracle.hpp)."""
+What pins it and what does not: oracle/smooth_oracle.hpp."""
 import ctypes as C
 import os
 import subprocess
@@ -51,7 +51,7 @@ def lib():
         l.orc_set_points.argtypes = [C.c_void_p, f64p]
         l.orc_num_edges.restype = C.c_int
         l.orc_num_edges.argtypes = [C.c_void_p]
-        for n in ("orc_phaseA", "orc_phaseB", "orc_phaseC", "orc_commit"):
+        for n in ("orc_phaseA", "orc_phaseB", "orc_phaseC", "orc_commit", "orc_update_geometry"):
             getattr(l, n).argtypes = [C.c_void_p]
         l.orc_get_field.restype = C.c_longlong
         l.orc_get_field.argtypes = [C.c_void_p, C.c_char_p, f64p]
@@ -230,6 +230,7 @@ class Oracle:
         a, p = _v(pts)
         self._lib.orc_set_points(self._h, p)
 
+    def update_geometry(self): self._lib.orc_update_geometry(self._h)
     def phaseA(self): self._lib.orc_phaseA(self._h)
     def phaseB(self): self._lib.orc_phaseB(self._h)
     def phaseC(self): self._lib.orc_phaseC(self._h)
@@ -262,7 +263,7 @@ class Oracle:
             return None, vals.reshape(-1, 2)
         rows = {"pointCells": self.nPoints, "pointFaces": self.nPoints, "pointEdges": self.nPoints,
                 "pointPoints": self.nPoints, "edgeFaces": self.num_edges(), "edgeCells": self.num_edges(),
-                "cellFaces": self.nCells}[kind]
+                "cellFaces": self.nCells, "cellPoints": self.nCells}[kind]
         off = np.empty(rows + 1, np.int32)
         self._lib.orc_get_addressing(self._h, kind.encode(), _p(off, i32p), _p(vals, i32p))
         return off, vals

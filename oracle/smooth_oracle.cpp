@@ -1,5 +1,5 @@
 // smooth_oracle.cpp -- CPU restatement of the reference's smoothing iteration loop.
-// TEST INFRASTRUCTURE ONLY (see smooth_oracle.hpp).  PARITY UNPINNED (see header).
+// TEST INFRASTRUCTURE ONLY (see smooth_oracle.hpp).  Pinned to the reference for serial runs; what is not: see the header.
 //
 // Build: g++ -O2 -std=c++17 -ffp-contract=off  (no FMA contraction, no fast-math: the
 // x86-64 reference build evaluates every expression in plain IEEE f64, left to right).

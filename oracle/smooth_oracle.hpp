@@ -4,11 +4,12 @@
 // call anything in this directory; only tests/, __graft_entry__.smoke() and
 // bench.py's cpu_baseline leg do.
 //
-// PARITY UNPINNED: the reference (OpenFOAM application, src/smoothMesh.C) cannot be
-// compiled or run in this environment (no OpenFOAM, no MPI) and ships no golden
-// vectors (run_tests.sh only checks for crashes).  This restatement follows the
-// reference function by function (citations below and in the .cpp) and is pinned
-// only by analytic known answers and invariances (tests/test_oracle_*.py).
+// PINNED TO THE REFERENCE'S PROGRAM TEXT for serial runs: the reference's own source, compiled against the stand-in
+// OpenFOAM of oracle/foam_shim/ and executed (oracle/ref_driver.cpp, tests/test_reference_pin.py), gives bit-equal
+// points, nFrozenPoints and printed residuals.  NOT pinned, because OpenFOAM decides them and OpenFOAM is absent: the
+// addressing orders and the primitiveMesh geometry restated below, the constants, parallel syncTools, the octree of the
+// boundary point smoothing.  This restatement follows the reference function by function
+// (citations below and in the .cpp); analytic known answers and invariances: tests/test_oracle_*.py.
 //
 // Reference citations are relative to /root/reference/ (SM.C = src/smoothMesh.C,
 // BPS.C = src/boundaryPointSmoothing.C, COM.H = src/smoothMeshCommon.H).
