@@ -549,8 +549,13 @@ int smgpu_create(const smgpu_mesh_desc* d, smgpu_handle** out) {
     // rest of the addressing; the smoothing and edge tile tables follow the addressing, side by side.
     const bool wantTiles = envInt("SMGPU_TILES", 1) != 0;
     const bool mortonTiles = envInt("SMGPU_TILE_MORTON", 1) != 0;
+    // Lattice Z-curve keys by default on meshes of hexahedra alone, bounding-box keys on the others; SMGPU_TILE_LATTICE = 1 / 0 forces
+    // either on any mesh (tiles.hpp, tileLatticeKnob: the measurements behind the default)
+    const bool allHex = tileLatticeDefault(d->nCells, d->nFaces, d->nInternalFaces, d->nFaces > 0 ? (int64_t)d->faceOffsets[d->nFaces] - d->faceOffsets[0] : 0);
+    const bool latticeKeys = tileLatticeKnob(allHex);
+    h->gt.latticeKeys = h->stl.latticeKeys = h->etl.latticeKeys = latticeKeys;
     std::future<std::vector<int32_t>> fPointOrder;
-    if (wantTiles && mortonTiles) fPointOrder = std::async(std::launch::async, [&] { return mortonOrderOf(d->nPoints, d->points); });
+    if (wantTiles && mortonTiles) fPointOrder = std::async(std::launch::async, [&] { return mortonOrderOf(d->nPoints, d->points, latticeKeys); });
     std::future<std::string> fGeom, fSmooth, fEdge;
     std::function<void()> startEdge;
     CornerChains chains;       // (tiles_dev.hip; released by the smoothing task's device build, or below)
@@ -579,7 +584,7 @@ int smgpu_create(const smgpu_mesh_desc* d, smgpu_handle** out) {
                       std::vector<int32_t> cellOrder;      // (a device build: the Z-curve of the cells there too -- the order the host would find)
                       if (mortonTiles && devTiles && devTopo.valid && envInt("SMGPU_DEVICE_TILES", 1) == 1) {
                           std::string why;
-                          if (cellMortonOrderOnDevice(devTopo, d->nCells, d->nPoints, d->points, h->device, cellOrder, why) != 0) cellOrder.clear();
+                          if (cellMortonOrderOnDevice(devTopo, d->nCells, d->nPoints, d->points, h->device, cellOrder, why, latticeKeys) != 0) cellOrder.clear();
                       }
                       const std::string e = h->gt.buildBoundaries(h->topo, d->points, mortonTiles, geomT0, geomCells0, capGP0, capGF0,
                                                                   envInt("SMGPU_GEOM_CAPWEIGHTED", defaultGeomCapWeighted(geomT0)), SMGPU_GEOM_AOS ? kGF : 6,
@@ -831,17 +836,48 @@ int smgpu_create(const smgpu_mesh_desc* d, smgpu_handle** out) {
             rc |= devUpload(h, &g.cfBase, h->gt.cfBase);
             rc |= devUpload(h, &g.cfWidth, h->gt.cfWidth);
             rc |= devUpload(h, &g.tileFlags, h->gt.tileFlags);
-            if (!g.meta) {   // the per-tile scalars once more, one record per tile (GeomTileMeta: scalar loads in the kernel)
+            // Shared topology blocks (tiles.hpp): tiles whose rows are byte-identical read the first copy.  The pass runs on the tables
+            // of whichever side built them (a device build's rows are hashed and compared where they are, tiles_dev.hip) and only changes
+            // the bases in the meta records.
+            const bool shareTiles = tileShareKnob();
+            // (one array of a device build: the pass runs where the rows are)
+            auto shareDev = [&](TileShare& out, int nT, const uint16_t* a, const uint16_t* b, const std::vector<int32_t>& base, auto lenOf, const std::vector<uint8_t>& width) {
+                std::vector<int32_t> len((size_t)nT), key(width.begin(), width.end());
+                for (int t = 0; t < nT; ++t) len[(size_t)t] = (int32_t)lenOf(t);
+                std::string why;
+                if (shareBlocksOnDevice(nT, a, b, base, len, key, h->device, out, why)) rc |= fail("smgpu_create: shared tile blocks: " + why);
+            };
+            auto putMeta = [&](const int*& dst, const std::vector<int>& meta) {      // a device build's records are overwritten in place
+                if (!dst) { rc |= devUpload(h, &dst, meta); return; }
+                if (!meta.empty() && hipMemcpy((void*)dst, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc |= fail("smgpu_create: upload of the tile records failed");
+            };
+            // SMGPU_VERBOSE=1, per tile set: tiles, distinct blocks per array (= tiles where every tile reads its own), staged elements per
+            // element of the mesh
+            const bool sayTiles = envInt("SMGPU_VERBOSE", 0) != 0;
+            int dFv = h->gt.nTiles, dCf = h->gt.nTiles, dPc = h->stl.nTiles, dPp = h->stl.nTiles, dPf = h->stl.nTiles;
+            if (!g.meta || shareTiles) {   // the per-tile scalars once more, one record per tile (GeomTileMeta: scalar loads in the kernel)
                 const auto& gt = h->gt;
+                const int nT = gt.nTiles;
+                TileShare fv, cf;
+                if (gt.faceVerts.empty() && g.faceVerts) {
+                    shareDev(fv, nT, g.faceVerts, nullptr, gt.fvBase, [&](int t) { return (size_t)(gt.tfOff[(size_t)t + 1] - gt.tfOff[(size_t)t]) * gt.fvWidth[(size_t)t]; }, gt.fvWidth);
+                    shareDev(cf, nT, g.cellFaces, nullptr, gt.cfBase, [&](int t) { return (size_t)gt.cfWidth[(size_t)t] * (size_t)gt.threads; }, gt.cfWidth);
+                } else shareGeomBlocks(gt, gt.faceVerts.data(), gt.cellFaces.data(), fv, cf);
+                if (rc) return cleanup(1);
                 std::vector<int> meta((size_t)kGeomMetaInts * (size_t)gt.nTiles, 0);
                 for (int t = 0; t < gt.nTiles; ++t) {
                     int* r = meta.data() + (size_t)kGeomMetaInts * t;
                     r[0] = gt.tpOff[t]; r[1] = gt.tpOff[t + 1] - gt.tpOff[t]; r[2] = gt.tfOff[t]; r[3] = gt.tfOff[t + 1] - gt.tfOff[t];
-                    r[4] = gt.fvBase[t]; r[5] = gt.fvWidth[t]; r[6] = gt.cellBeg[t]; r[7] = gt.cellBeg[t + 1] - gt.cellBeg[t];
-                    r[8] = gt.cfBase[t]; r[9] = gt.cfWidth[t]; r[10] = gt.tileFlags[t];
+                    r[4] = fv.remap(gt.fvBase, t); r[5] = gt.fvWidth[t]; r[6] = gt.cellBeg[t]; r[7] = gt.cellBeg[t + 1] - gt.cellBeg[t];
+                    r[8] = cf.remap(gt.cfBase, t); r[9] = gt.cfWidth[t]; r[10] = gt.tileFlags[t];
                 }
-                rc |= devUpload(h, &g.meta, meta);
+                putMeta(g.meta, meta);
+                dFv = fv.distinct; dCf = cf.distinct;
             }
+            if (sayTiles)
+                std::fprintf(stderr, "[smgpu] geometry tiles: %d tiles, distinct blocks: faceVerts %d, cellFaces %d (SMGPU_TILE_LATTICE=%d SMGPU_TILE_SHARE=%d), staged faces x%.4f, "
+                             "staged points x%.4f\n", h->gt.nTiles, dFv, dCf, (int)h->gt.latticeKeys, (int)shareTiles, (double)h->gt.tfOff.back() / std::max(1, t.nFaces),
+                             (double)h->gt.tpOff.back() / std::max(1, t.nPoints));
             g.maxPoints = h->gt.maxPoints; g.maxFaces = h->gt.maxFaces;
             if (h->stDev.valid) {
                 auto adoptS = [&](auto*& dst, const SmoothTilesDev::Arr& a) { dst = (std::remove_reference_t<decltype(dst)>)a.p; h->allocs.push_back(a.p); h->deviceBytes += (int64_t)a.bytes; };
@@ -867,17 +903,30 @@ int smgpu_create(const smgpu_mesh_desc* d, smgpu_handle** out) {
             rc |= devUpload(h, &v.ppWidth, h->stl.ppWidth);
             rc |= devUpload(h, &v.pfBase, h->stl.pfBase);
             rc |= devUpload(h, &v.pfWidth, h->stl.pfWidth);
-            if (!v.meta) {   // SmoothTileMeta records
+            if (!v.meta || shareTiles) {   // SmoothTileMeta records
                 const auto& st = h->stl;
+                const int nS = st.nTiles;
+                TileShare pc, pp, pf;
+                if (st.pcEll.empty() && v.pcEll) {
+                    const size_t T = (size_t)st.threads;
+                    shareDev(pc, nS, v.pcEll, nullptr, st.pcBase, [&](int t) { return st.pcWidth[(size_t)t] * T; }, st.pcWidth);
+                    shareDev(pp, nS, v.ppEll, v.pairEll, st.ppBase, [&](int t) { return st.ppWidth[(size_t)t] * T; }, st.ppWidth);
+                    shareDev(pf, nS, v.pfEll, nullptr, st.pfBase, [&](int t) { return st.pfWidth[(size_t)t] * T; }, st.pfWidth);
+                } else shareSmoothBlocks(st, st.pcEll.data(), st.ppEll.data(), st.pairEll.data(), st.pfEll.data(), pc, pp, pf);
+                if (rc) return cleanup(1);
                 std::vector<int> meta((size_t)kSmoothMetaInts * (size_t)st.nTiles, 0);
                 for (int t = 0; t < st.nTiles; ++t) {
                     int* r = meta.data() + (size_t)kSmoothMetaInts * t;
                     r[0] = st.ptBeg[t]; r[1] = st.ptBeg[t + 1] - st.ptBeg[t]; r[2] = st.tcOff[t]; r[3] = st.tcOff[t + 1] - st.tcOff[t];
-                    r[4] = st.tnOff[t]; r[5] = st.tnOff[t + 1] - st.tnOff[t]; r[6] = st.pcBase[t]; r[7] = st.pcWidth[t];
-                    r[8] = st.ppBase[t]; r[9] = st.ppWidth[t]; r[10] = st.pfBase[t]; r[11] = st.pfWidth[t];
+                    r[4] = st.tnOff[t]; r[5] = st.tnOff[t + 1] - st.tnOff[t]; r[6] = pc.remap(st.pcBase, t); r[7] = st.pcWidth[t];
+                    r[8] = pp.remap(st.ppBase, t); r[9] = st.ppWidth[t]; r[10] = pf.remap(st.pfBase, t); r[11] = st.pfWidth[t];
                 }
-                rc |= devUpload(h, &v.meta, meta);
+                putMeta(v.meta, meta);
+                dPc = pc.distinct; dPp = pp.distinct; dPf = pf.distinct;
             }
+            if (sayTiles)
+                std::fprintf(stderr, "[smgpu] smoothing tiles: %d tiles, distinct blocks: pcEll %d, ppEll+pairEll %d, pfEll %d, staged cell centres x%.4f, staged points x%.4f (per point)\n",
+                             h->stl.nTiles, dPc, dPp, dPf, (double)h->stl.tcOff.back() / std::max(1, t.nPoints), (double)h->stl.tnOff.back() / std::max(1, t.nPoints));
             v.maxCells = h->stl.maxCells; v.maxPoints = h->stl.maxPoints;
             v.usePairShare = t.maxPointPoints <= 16 ? 1 : 0;
             if (h->useFilter) {
@@ -921,17 +970,30 @@ int smgpu_create(const smgpu_mesh_desc* d, smgpu_handle** out) {
                     rc |= devUpload(h, &ev.ecBase, h->etl.ecBase);
                     rc |= devUpload(h, &ev.efWidth, h->etl.efWidth);
                     rc |= devUpload(h, &ev.ecWidth, h->etl.ecWidth);
-                    if (!ev.meta) {   // EdgeTileMeta records
+                    int dEf = h->etl.nTiles, dEc = h->etl.nTiles;
+                    if (!ev.meta || shareTiles) {   // EdgeTileMeta records
                         const auto& et = h->etl;
+                        const int nE = et.nTiles;
+                        TileShare ef, ec;
+                        if (et.efEll.empty() && ev.efEll) {
+                            const size_t T = (size_t)et.threads;
+                            shareDev(ef, nE, ev.efEll, nullptr, et.efBase, [&](int ti) { return et.efWidth[(size_t)ti] * T; }, et.efWidth);
+                            shareDev(ec, nE, ev.ecEll, nullptr, et.ecBase, [&](int ti) { return et.ecWidth[(size_t)ti] * T; }, et.ecWidth);
+                        } else shareEdgeBlocks(et, et.efEll.data(), et.ecEll.data(), ef, ec);
+                        if (rc) return cleanup(1);
+                        dEf = ef.distinct; dEc = ec.distinct;
                         std::vector<int> meta((size_t)kEdgeMetaInts * (size_t)et.nTiles, 0);
                         for (int ti = 0; ti < et.nTiles; ++ti) {
                             int* r = meta.data() + (size_t)kEdgeMetaInts * ti;
                             r[0] = et.edgeBeg[ti]; r[1] = et.edgeBeg[ti + 1] - et.edgeBeg[ti]; r[2] = et.tpOff[ti]; r[3] = et.tpOff[ti + 1] - et.tpOff[ti];
                             r[4] = et.tfOff[ti]; r[5] = et.tfOff[ti + 1] - et.tfOff[ti]; r[6] = et.tcOff[ti]; r[7] = et.tcOff[ti + 1] - et.tcOff[ti];
-                            r[8] = et.efBase[ti]; r[9] = et.efWidth[ti]; r[10] = et.ecBase[ti]; r[11] = et.ecWidth[ti];
+                            r[8] = ef.remap(et.efBase, ti); r[9] = et.efWidth[ti]; r[10] = ec.remap(et.ecBase, ti); r[11] = et.ecWidth[ti];
                         }
-                        rc |= devUpload(h, &ev.meta, meta);
+                        putMeta(ev.meta, meta);
                     }
+                    if (sayTiles)
+                        std::fprintf(stderr, "[smgpu] edge tiles: %d tiles, distinct blocks: efEll %d, ecEll %d, staged points x%.4f, faces x%.4f, cells x%.4f (per edge)\n", h->etl.nTiles, dEf, dEc,
+                                     (double)h->etl.tpOff.back() / std::max(1, t.nEdges), (double)h->etl.tfOff.back() / std::max(1, t.nEdges), (double)h->etl.tcOff.back() / std::max(1, t.nEdges));
                     ev.maxPoints = h->etl.maxPoints; ev.maxFaces = h->etl.maxFaces; ev.maxCells = h->etl.maxCells;
                     h->edgeLds = sizeof(double) * 3 * maxTileTotal(h->etl.nTiles, {&h->etl.tpOff, &h->etl.tfOff, &h->etl.tcOff});
                     h->edgeTilesOk = h->edgeLds <= 64 * 1024;

@@ -38,7 +38,7 @@ static inline uint64_t spread21(uint64_t v) {   // 21 bits -> every third bit
 }
 
 // positions sorted along the Z-curve of the given coordinates (3 per element); ties keep id order
-static std::vector<int32_t> mortonOrder(int32_t n, const double* xyz) {
+static std::vector<int32_t> mortonOrder(int32_t n, const double* xyz, bool lattice) {
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     {
         const int parts = rangeParts(n);
@@ -52,9 +52,9 @@ static std::vector<int32_t> mortonOrder(int32_t n, const double* xyz) {
         for (int part = 0; part < parts; ++part)
             for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], plo[3 * (size_t)part + a]); hi[a] = std::max(hi[a], phi[3 * (size_t)part + a]); }
     }
-    double ext = 0.0;
-    for (int a = 0; a < 3; ++a) ext = std::max(ext, hi[a] - lo[a]);
-    const double scale = ext > 0.0 ? 2097151.0 / ext : 0.0;   // one isotropic scale: bricks stay cubic in space
+    const MortonFrame fr = mortonFrame(n, lo, hi, lattice);   // one isotropic scale: bricks stay cubic in space
+    const double scale = fr.scale;
+    for (int a = 0; a < 3; ++a) lo[a] = fr.origin[a];
     std::vector<std::pair<uint64_t, int32_t>> key((size_t)n);
     parallelRanges(n, rangeParts(n), [&](int, int64_t b, int64_t e) {
         for (int64_t i = b; i < e; ++i) {
@@ -66,7 +66,7 @@ static std::vector<int32_t> mortonOrder(int32_t n, const double* xyz) {
     // sort by (key, id): the keys' top byte cuts the sequence into 256 buckets (an octant subdivision of the curve) that are
     // sorted side by side -- the same order as one std::sort over all pairs
     if (rangeParts(n) > 1) {
-        const int shift = 55;   // keys have 63 bits
+        const int shift = std::max(3 * fr.bits - 8, 0);   // keys have 3 * bits bits (63 for the bounding-box keys)
         std::vector<size_t> cnt(257, 0);
         for (int32_t i = 0; i < n; ++i) ++cnt[(size_t)(key[(size_t)i].first >> shift) + 1];
         for (int bkt = 0; bkt < 256; ++bkt) cnt[(size_t)bkt + 1] += cnt[(size_t)bkt];
@@ -86,7 +86,7 @@ static std::vector<int32_t> mortonOrder(int32_t n, const double* xyz) {
     return order;
 }
 
-std::vector<int32_t> mortonOrderOf(int32_t n, const double* xyz) { return mortonOrder(n, xyz); }
+std::vector<int32_t> mortonOrderOf(int32_t n, const double* xyz, bool lattice) { return mortonOrder(n, xyz, lattice); }
 
 static std::vector<int32_t> naturalOrder(int32_t n) {
     std::vector<int32_t> o((size_t)n);
@@ -147,7 +147,7 @@ std::string GeomTiles::buildBoundaries(const Topology& t, const double* pts, boo
                 for (int a = 0; a < 3; ++a) cc[3 * (size_t)c + a] = n ? s[a] / n : 0.0;
             }
         });
-        order = mortonOrder(t.nCells, cc.data());
+        order = mortonOrder(t.nCells, cc.data(), latticeKeys);
     } else order = naturalOrder(t.nCells);
     tm.lap("order");
     // pass 1: greedy tile boundaries under the three capacities (mesh-sized stamp arrays: an L1-resident hash set per open tile
@@ -303,6 +303,107 @@ std::string GeomTiles::buildTables(const Topology& t) {
     return "";
 }
 
+// ---- shared topology blocks (tiles.hpp) -----------------------------------------------------------------------------------------
+namespace {
+struct BlockSpan { const uint16_t* p; size_t n; };
+// rep / distinct over nTiles blocks; block(t, spans, key) lists the tile's rows and the scalars that belong to its identity
+template <class F> void shareBlocks(int32_t nTiles, TileShare& out, F block) {
+    out.rep.resize((size_t)nTiles);
+    for (int32_t t = 0; t < nTiles; ++t) out.rep[(size_t)t] = t;
+    out.distinct = nTiles;
+    if (!tileShareKnob() || nTiles < 2) return;
+    std::vector<uint64_t> hash((size_t)nTiles);
+    parallelRanges(nTiles, rangeParts(nTiles, 64), [&](int, int64_t tb, int64_t te) {
+        BlockSpan sp[4];
+        for (int32_t t = (int32_t)tb; t < (int32_t)te; ++t) {
+            uint64_t key = 0;
+            const int ns = block(t, sp, key);
+            uint64_t hh = 1469598103934665603ull ^ key;
+            for (int s = 0; s < ns; ++s) {
+                hh = (hh ^ sp[s].n) * 1099511628211ull;
+                for (size_t i = 0; i < sp[s].n; ++i) { hh ^= sp[s].p[i]; hh *= 1099511628211ull; }
+            }
+            hash[(size_t)t] = hh;
+        }
+    });
+    // tiles in (hash, id) order: the first of every run of one hash is a candidate, the others are compared with the run's distinct blocks
+    std::vector<int32_t> idx((size_t)nTiles);
+    for (int32_t t = 0; t < nTiles; ++t) idx[(size_t)t] = t;
+    std::sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) { return hash[(size_t)a] != hash[(size_t)b] ? hash[(size_t)a] < hash[(size_t)b] : a < b; });
+    auto same = [&](int32_t a, int32_t b) {
+        BlockSpan x[4], y[4];
+        uint64_t kx = 0, ky = 0;
+        const int nx = block(a, x, kx), ny = block(b, y, ky);
+        if (nx != ny || kx != ky) return false;
+        for (int s = 0; s < nx; ++s)
+            if (x[s].n != y[s].n || !std::equal(x[s].p, x[s].p + x[s].n, y[s].p)) return false;
+        return true;
+    };
+    std::vector<int32_t> firsts;
+    for (size_t i = 0; i < idx.size();) {
+        size_t j = i;
+        firsts.clear();
+        for (; j < idx.size() && hash[(size_t)idx[j]] == hash[(size_t)idx[i]]; ++j) {
+            const int32_t t = idx[j];
+            bool found = false;
+            for (int32_t f : firsts)
+                if (same(f, t)) { out.rep[(size_t)t] = f; --out.distinct; found = true; break; }
+            if (!found) firsts.push_back(t);
+        }
+        i = j;
+    }
+}
+}  // namespace
+
+void shareGeomBlocks(const GeomTiles& gt, const uint16_t* faceVerts, const uint16_t* cellFaces, TileShare& fv, TileShare& cf) {
+    shareBlocks(gt.nTiles, fv, [&](int32_t t, BlockSpan* sp, uint64_t& key) {
+        const int32_t nf = gt.tfOff[(size_t)t + 1] - gt.tfOff[(size_t)t];
+        key = gt.fvWidth[(size_t)t];
+        sp[0] = {faceVerts + gt.fvBase[(size_t)t], (size_t)nf * gt.fvWidth[(size_t)t]};
+        return 1;
+    });
+    shareBlocks(gt.nTiles, cf, [&](int32_t t, BlockSpan* sp, uint64_t& key) {
+        key = gt.cfWidth[(size_t)t];
+        sp[0] = {cellFaces + gt.cfBase[(size_t)t], (size_t)gt.cfWidth[(size_t)t] * (size_t)gt.threads};
+        return 1;
+    });
+}
+
+void shareSmoothBlocks(const SmoothTiles& st, const uint16_t* pcEll, const uint16_t* ppEll, const uint16_t* pairEll, const uint16_t* pfEll,
+                       TileShare& pc, TileShare& pp, TileShare& pf) {
+    const size_t T = (size_t)st.threads;
+    shareBlocks(st.nTiles, pc, [&](int32_t t, BlockSpan* sp, uint64_t& key) {
+        key = st.pcWidth[(size_t)t];
+        sp[0] = {pcEll + st.pcBase[(size_t)t], st.pcWidth[(size_t)t] * T};
+        return 1;
+    });
+    shareBlocks(st.nTiles, pp, [&](int32_t t, BlockSpan* sp, uint64_t& key) {      // (one base for the neighbour rows and their pair masks)
+        key = st.ppWidth[(size_t)t];
+        sp[0] = {ppEll + st.ppBase[(size_t)t], st.ppWidth[(size_t)t] * T};
+        sp[1] = {pairEll + st.ppBase[(size_t)t], st.ppWidth[(size_t)t] * T};
+        return 2;
+    });
+    shareBlocks(st.nTiles, pf, [&](int32_t t, BlockSpan* sp, uint64_t& key) {
+        key = st.pfWidth[(size_t)t];
+        sp[0] = {pfEll + st.pfBase[(size_t)t], st.pfWidth[(size_t)t] * T};
+        return 1;
+    });
+}
+
+void shareEdgeBlocks(const EdgeTiles& et, const uint16_t* efEll, const uint16_t* ecEll, TileShare& ef, TileShare& ec) {
+    const size_t T = (size_t)et.threads;
+    shareBlocks(et.nTiles, ef, [&](int32_t t, BlockSpan* sp, uint64_t& key) {
+        key = et.efWidth[(size_t)t];
+        sp[0] = {efEll + et.efBase[(size_t)t], et.efWidth[(size_t)t] * T};
+        return 1;
+    });
+    shareBlocks(et.nTiles, ec, [&](int32_t t, BlockSpan* sp, uint64_t& key) {
+        key = et.ecWidth[(size_t)t];
+        sp[0] = {ecEll + et.ecBase[(size_t)t], et.ecWidth[(size_t)t] * T};
+        return 1;
+    });
+}
+
 // The face corners of a point, (previous vertex, next vertex) per incident face, are the edges of a small graph on the
 // point's neighbours (an octahedron for an interior hex point).  The edge-angle filter evaluates a pair of unit vectors
 // per neighbour and corner; ordered as Euler trails (each corner starts where the previous one ended, corners flipped as
@@ -392,7 +493,7 @@ std::string SmoothTiles::buildBoundaries(const Topology& t, const double* xyz, b
     threads = nThreads;
     PhaseTimer tm(subset ? "shared-point" : "smoothing");
     if (subset) order = *subset;
-    else if (morton) order = pointOrder ? *pointOrder : mortonOrder(t.nPoints, xyz);
+    else if (morton) order = pointOrder ? *pointOrder : mortonOrder(t.nPoints, xyz, latticeKeys);
     else order = naturalOrder(t.nPoints);
     const int32_t nPos = (int32_t)order.size();      // positions = points to tile (all of them, or the subset)
     maxCells = maxPoints = 0;
@@ -613,7 +714,7 @@ std::string EdgeTiles::buildBoundaries(const Topology& t, const double* xyz, boo
             for (int64_t e = b; e < e1; ++e)
                 for (int a = 0; a < 3; ++a) mid[3 * (size_t)e + a] = 0.5 * (xyz[3 * (size_t)t.edges[2 * e] + a] + xyz[3 * (size_t)t.edges[2 * e + 1] + a]);
         });
-        order = mortonOrder(nE, mid.data());
+        order = mortonOrder(nE, mid.data(), latticeKeys);
     } else order = naturalOrder(nE);
     tm.lap("order");
     const auto& ef = t.edgeFaces;

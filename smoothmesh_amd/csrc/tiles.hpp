@@ -12,7 +12,10 @@
 // access then happens inside LDS and global memory is only streamed.  Arithmetic and summation
 // order are unchanged (entries keep the list order, 0xFFFF pads the tail).
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -22,12 +25,90 @@ namespace smgpu {
 
 constexpr uint16_t kEllPad = 0xFFFF;
 
+// The frame of the Z-curve keys of n elements whose coordinates fill the box lo..hi: key = interleave((u64)((x - origin) * scale)).
+//  - bounding-box keys: 21 bits per axis of the box's longest side (one isotropic scale).  The octree splits of a 100-cell axis
+//    then fall at 50, 25, 12.5, ...: runs of consecutive elements are ragged, not the bricks of the mesh's own lattice.
+//  - lattice keys (SMGPU_TILE_LATTICE, default on): the index of the element on a lattice of the mean spacing h, n elements at
+//    the nodes of a lattice that fills the box: prod_a (ext_a / h + 1) = n, i.e. h = cbrt(box volume / n) corrected for the
+//    half spacing the outermost elements keep from the box (cell centres) -- solved by a fixed-point iteration that starts there.
+//    The origin lies h/2 below the box, so that an element on its node sits in the middle of its interval: jitter of up to
+//    h/2 leaves the index alone.  Wherever the mesh is locally structured, 2^k consecutive keys are an aligned brick of it.
+//    Falls back to the bounding-box keys when h is degenerate or an axis would need more than 21 bits.
+// The host (tiles.cpp) and the device (tiles_dev.hip) builds of an order both take their frame from here.
+struct MortonFrame { double origin[3]; double scale; int bits; bool lattice; };     // bits: per axis, of the largest index
+// SMGPU_TILE_LATTICE where it is set (1 forces lattice keys on any mesh, 0 the bounding-box keys); else the caller's default.  The
+// engine's default follows the mesh (tileLatticeDefault): on for meshes of hexahedra alone, off for the others -- on the castellated
+// polyhedral mesh lattice keys were measured 0.9 % (constraints off) and 1.4 % (on) SLOWER than bounding-box keys, beyond the 0.4 %
+// / 0.2 % run-to-run spread (profiles/tile_lattice_sharing.md, "The polyhedral configurations").  The builders used on their own
+// (GeomTiles::latticeKeys etc., mortonOrderOf) default to ON whatever the mesh: that is how the CPU tests hold lattice keys to the
+// polyhedral, baffle and fan meshes too.
+inline bool tileLatticeKnob(bool dflt = true) { const char* e = std::getenv("SMGPU_TILE_LATTICE"); return e ? std::atoi(e) != 0 : dflt; }
+// hexahedra alone, read off the counts: every face a quadrilateral, and six faces per cell (each internal face counts for two cells)
+inline bool tileLatticeDefault(int64_t nCells, int64_t nFaces, int64_t nInternalFaces, int64_t nFacePoints) {
+    return nFaces > 0 && nFacePoints == 4 * nFaces && nFaces + nInternalFaces == 6 * nCells;
+}
+inline MortonFrame mortonFrame(int64_t n, const double lo[3], const double hi[3], bool lattice) {
+    MortonFrame f{{lo[0], lo[1], lo[2]}, 0.0, 21, false};
+    double ext = 0.0, e[3];
+    for (int a = 0; a < 3; ++a) { e[a] = hi[a] - lo[a]; ext = std::max(ext, e[a]); }
+    f.scale = ext > 0.0 ? 2097151.0 / ext : 0.0;
+    if (!lattice || n < 2 || !(ext > 0.0) || !std::isfinite(ext)) return f;
+    int k = 0;
+    double h = 1.0;
+    for (int a = 0; a < 3; ++a) if (e[a] > 0.0) { h *= e[a]; ++k; }
+    h = std::pow(h / (double)n, 1.0 / k);
+    // (a fixed count, so that every build of an order takes the same h: the map contracts by (h / k) * sum_a 1 / (ext_a + h), about
+    // 1 / (elements per axis + 1) -- at most 1/2, for two elements on an axis -- so 16 rounds leave less than 2^-16 of the first
+    // guess's error, itself below one spacing: far inside the h/2 an index tolerates)
+    for (int it = 0; it < 16; ++it) {
+        double v = 1.0;
+        for (int a = 0; a < 3; ++a) if (e[a] > 0.0) v *= e[a] + h;
+        h = std::pow(v / (double)n, 1.0 / k);
+    }
+    if (!(h > 0.0) || !std::isfinite(h) || !std::isfinite(1.0 / h) || !(ext / h + 1.0 < 2097151.0)) return f;
+    f.lattice = true;
+    f.scale = 1.0 / h;
+    for (int a = 0; a < 3; ++a) f.origin[a] = lo[a] - 0.5 * h;
+    const uint64_t top = (uint64_t)((ext + 0.5 * h) * f.scale) + 1;      // (an index may round one up from the box's own)
+    f.bits = 1;
+    while (f.bits < 21 && (top >> f.bits)) ++f.bits;
+    return f;
+}
+
 // Z-curve (Morton) order of n elements given by 3 coordinates each: position -> element id, ties in id order
-std::vector<int32_t> mortonOrderOf(int32_t n, const double* xyz);
+// (lattice: tileLatticeKnob() of the caller's default)
+std::vector<int32_t> mortonOrderOf(int32_t n, const double* xyz, bool lattice = tileLatticeKnob());
+
+// ---- shared topology blocks ----------------------------------------------------------------------------------------------------
+// The ELL tables of a tile are written in tile-local indices over ascending-id lists: two tiles that are the same brick of a
+// structured region hold the same bytes.  rep[t] = the first tile whose block (the rows at the given bases, `len(t)` entries of
+// every array, the widths / counts in `key(t)` part of the identity) equals tile t's entry for entry -- found by hash, verified by
+// full comparison.  The kernels address the tables through the bases of their per-tile meta records only, so pointing a
+// duplicate's base at rep[t]'s rows leaves what they read unchanged and lets the workgroups of a Morton range re-read one block
+// from their L2.  The builders' own arrays (bases ascending, tiles packed in order) stay as they are: the remap goes into the
+// meta records.  Lists of global ids (tpIds, tfIds, cellOrder, ...) are never shared.  SMGPU_TILE_SHARE=0: rep[t] = t.
+struct TileShare {
+    std::vector<int32_t> rep;
+    int32_t distinct = 0;
+    int32_t remap(const std::vector<int32_t>& base, int32_t t) const { return base[(size_t)rep[(size_t)t]]; }
+};
+inline bool tileShareKnob() { const char* e = std::getenv("SMGPU_TILE_SHARE"); return !e || std::atoi(e) != 0; }
+struct GeomTiles; struct SmoothTiles; struct EdgeTiles;
+// (the table arrays of a host build; a device build's rows: shareBlocksOnDevice below)
+void shareGeomBlocks(const GeomTiles& gt, const uint16_t* faceVerts, const uint16_t* cellFaces, TileShare& fv, TileShare& cf);
+void shareSmoothBlocks(const SmoothTiles& st, const uint16_t* pcEll, const uint16_t* ppEll, const uint16_t* pairEll, const uint16_t* pfEll,
+                       TileShare& pc, TileShare& pp, TileShare& pf);
+void shareEdgeBlocks(const EdgeTiles& et, const uint16_t* efEll, const uint16_t* ecEll, TileShare& ef, TileShare& ec);
+// the pass for one array of a device build, run where the rows are (tiles_dev.hip): a = the rows, b = a second array under the same
+// bases or NULL; base / len / key per tile.  The same representatives as the host pass.  0 done; 2 a HIP error (why)
+int shareBlocksOnDevice(int32_t nTiles, const uint16_t* a, const uint16_t* b, const std::vector<int32_t>& base, const std::vector<int32_t>& len, const std::vector<int32_t>& key,
+                        int device, TileShare& out, std::string& why);
 
 // ---- geometry: tile = consecutive cells; LDS holds the tile's points and faces --------------------
 struct GeomTiles {
     int32_t nTiles = 0, threads = 0;
+    bool latticeKeys = tileLatticeKnob();   // the keys of an order built here (mortonFrame): on unless the knob says otherwise; the engine
+                                            // sets its per-mesh default (tileLatticeDefault)
     std::vector<int32_t> cellBeg;   // nTiles+1
     std::vector<int32_t> tpOff;     // nTiles+1 -> tpIds
     std::vector<int32_t> tpIds;     // unique point ids per tile, ascending
@@ -69,12 +150,14 @@ struct GeomTilesDev {
 struct DeviceTopologyArrays;
 // 0: built (gt holds the offsets / widths / flags / tfIds / maxima the host reads, `out` the device arrays); 1: not handled there
 // (the caller runs gt.buildTables); 2: a HIP error (why)
-int cellMortonOrderOnDevice(const DeviceTopologyArrays& td, int32_t nCells, int32_t nPoints, const double* points, int device, std::vector<int32_t>& order, std::string& why);
+int cellMortonOrderOnDevice(const DeviceTopologyArrays& td, int32_t nCells, int32_t nPoints, const double* points, int device, std::vector<int32_t>& order, std::string& why,
+                            bool lattice = tileLatticeKnob());
 int buildGeomTablesOnDevice(GeomTiles& gt, const DeviceTopologyArrays& td, int32_t nCells, int device, GeomTilesDev& out, std::string& why);
 
 // ---- smoothing: tile = consecutive points; LDS holds the cell centres and neighbour points -------
 struct SmoothTiles {
     int32_t nTiles = 0, threads = 0;
+    bool latticeKeys = tileLatticeKnob();   // (as GeomTiles')
     std::vector<int32_t> ptBeg;     // nTiles+1
     std::vector<int32_t> tcOff;     // nTiles+1 -> tcIds
     std::vector<int32_t> tcIds;     // unique cell ids per tile, ascending
@@ -128,6 +211,7 @@ int buildSmoothTablesOnDevice(SmoothTiles& st, const DeviceTopologyArrays& td, i
 // face vertex averages and the cell centres the tile's edges need ------------------------------------------
 struct EdgeTiles {
     int32_t nTiles = 0, threads = 0;
+    bool latticeKeys = tileLatticeKnob();   // (as GeomTiles')
     std::vector<int32_t> order;     // position -> edge id
     std::vector<int32_t> edgeBeg;   // nTiles+1
     std::vector<int32_t> tpOff, tpIds, tfOff, tfIds, tcOff, tcIds;   // unique points / faces / cells per tile

@@ -817,7 +817,8 @@ int buildSmoothTablesOnDevice(SmoothTiles& st, const DeviceTopologyArrays& td, i
 
 // order = the cells sorted along the Z-curve of their vertex averages, as tiles.cpp's mortonOrder gives it.  0 done; 1 not handled;
 // 2 a HIP error
-int cellMortonOrderOnDevice(const DeviceTopologyArrays& td, int32_t nCells, int32_t nPoints, const double* points, int device, std::vector<int32_t>& order, std::string& why) {
+int cellMortonOrderOnDevice(const DeviceTopologyArrays& td, int32_t nCells, int32_t nPoints, const double* points, int device, std::vector<int32_t>& order, std::string& why,
+                            bool lattice) {
     if (!td.valid || nCells <= 0 || nPoints <= 0) return 1;
     TL_OK(hipSetDevice(device));
     hipStream_t st = nullptr;
@@ -837,10 +838,8 @@ int cellMortonOrderOnDevice(const DeviceTopologyArrays& td, int32_t nCells, int3
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     for (int b = 0; b < nB; ++b)
         for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], hp[6 * (size_t)b + a]); hi[a] = std::max(hi[a], hp[6 * (size_t)b + 3 + a]); }
-    double ext = 0.0;
-    for (int a = 0; a < 3; ++a) ext = std::max(ext, hi[a] - lo[a]);
-    const double scale = ext > 0.0 ? 2097151.0 / ext : 0.0;
-    hipLaunchKernelGGL(k_tl_mortonKeys, dim3(nB), dim3(kT), 0, st, nCells, cc, lo[0], lo[1], lo[2], scale, kA, iA);
+    const MortonFrame fr = mortonFrame(nCells, lo, hi, lattice);      // (bounding-box or lattice keys: the frame tiles.cpp's mortonOrder takes)
+    hipLaunchKernelGGL(k_tl_mortonKeys, dim3(nB), dim3(kT), 0, st, nCells, cc, fr.origin[0], fr.origin[1], fr.origin[2], fr.scale, kA, iA);
     size_t tempBytes = 0;
     (void)rocprim::radix_sort_pairs(nullptr, tempBytes, kA, kB, iA, iB, (size_t)nCells, 0, 63, st);
     void* temp = D.get<char>(tempBytes + 256);
@@ -850,6 +849,115 @@ int cellMortonOrderOnDevice(const DeviceTopologyArrays& td, int32_t nCells, int3
     TL_OK(hipMemcpyAsync(order.data(), iB, (size_t)nCells * 4, hipMemcpyDeviceToHost, st));
     TL_OK(hipStreamSynchronize(st));
     TL_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- shared topology blocks of a device build (tiles.hpp): the share pass where the rows are -----------------------------------
+// A block's hash is a sum of mixed (position, entries) words, so that the lanes of a workgroup add their shares in any order.  The
+// host groups the tiles by (hash, length, key); every member of a group is compared in full with the group's first tile and takes it
+// as its representative where nothing differs; the members that differ are grouped again among themselves -- rep[t] = the first tile
+// with identical rows, as tiles.cpp's pass finds it, hash collisions or not.
+namespace {
+__global__ void __launch_bounds__(kT) k_tl_blockHash(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b, const long long* __restrict__ base, const int* __restrict__ len,
+                                                     u64* __restrict__ hash) {
+    const int t = blockIdx.x;
+    const long long o = base[t];
+    const int n = len[t];
+    u64 h = 0;
+    for (int i = threadIdx.x; i < n; i += kT) {
+        u64 x = ((u64)(unsigned)i << 32) | ((u64)a[o + i] << 16) | (b ? (u64)b[o + i] : 0ull);
+        x *= 0x9E3779B97F4A7C15ull; x ^= x >> 29; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 32;
+        h += x;
+    }
+    for (int d = 32; d > 0; d >>= 1) h += __shfl_xor(h, d, 64);
+    __shared__ u64 sh[kT / 64];
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = h;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 s = 0;
+        for (int i = 0; i < kT / 64; ++i) s += sh[i];
+        hash[t] = s;
+    }
+}
+// differs[k] = 1 where the rows of tiles pairT[k] and pairR[k] (of one length) differ in any entry
+__global__ void __launch_bounds__(kT) k_tl_blockDiffers(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b, const long long* __restrict__ base, const int* __restrict__ len,
+                                                        const int* __restrict__ pairT, const int* __restrict__ pairR, int* __restrict__ differs) {
+    const int t = pairT[blockIdx.x], r = pairR[blockIdx.x];
+    const long long ot = base[t], orr = base[r];
+    const int n = len[t];
+    bool d = false;
+    for (int i = threadIdx.x; i < n; i += kT) {
+        d |= a[ot + i] != a[orr + i];
+        if (b) d |= b[ot + i] != b[orr + i];
+    }
+    if (d) differs[blockIdx.x] = 1;
+}
+}  // namespace
+
+// rows: one array (b = nullptr) or two arrays under one base (ppEll + pairEll); base / len / key per tile.  0 done; 2 a HIP error
+int shareBlocksOnDevice(int32_t nTiles, const uint16_t* a, const uint16_t* b, const std::vector<int32_t>& base, const std::vector<int32_t>& len, const std::vector<int32_t>& key, int device,
+                        TileShare& out, std::string& why) {
+    out.rep.resize((size_t)nTiles);
+    for (int32_t t = 0; t < nTiles; ++t) out.rep[(size_t)t] = t;
+    out.distinct = nTiles;
+    if (!tileShareKnob() || nTiles < 2) return 0;
+    TL_OK(hipSetDevice(device));
+    DevBuf D;
+    long long* dBase = D.get<long long>((size_t)nTiles);
+    int* dLen = D.get<int>((size_t)nTiles);
+    u64* dHash = D.get<u64>((size_t)nTiles);
+    if (!dBase || !dLen || !dHash) { why = "device allocation failed"; return 2; }
+    std::vector<long long> hBase(base.begin(), base.end());
+    TL_OK(hipMemcpy(dBase, hBase.data(), (size_t)nTiles * 8, hipMemcpyHostToDevice));
+    TL_OK(hipMemcpy(dLen, len.data(), (size_t)nTiles * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_tl_blockHash, dim3(nTiles), dim3(kT), 0, nullptr, a, b, dBase, dLen, dHash);
+    TL_OK(hipGetLastError());
+    std::vector<u64> hash((size_t)nTiles);
+    TL_OK(hipMemcpy(hash.data(), dHash, (size_t)nTiles * 8, hipMemcpyDeviceToHost));
+    std::vector<int32_t> idx((size_t)nTiles);
+    for (int32_t t = 0; t < nTiles; ++t) idx[(size_t)t] = t;
+    auto groupLess = [&](int32_t x, int32_t y) {
+        if (hash[(size_t)x] != hash[(size_t)y]) return hash[(size_t)x] < hash[(size_t)y];
+        if (len[(size_t)x] != len[(size_t)y]) return len[(size_t)x] < len[(size_t)y];
+        return key[(size_t)x] < key[(size_t)y];
+    };
+    std::sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) { return groupLess(x, y) || (!groupLess(y, x) && x < y); });
+    // Every group of one (hash, length, key), in id order: its first tile stands for itself; the others are compared with it, those that
+    // differ (a hash collision) form the next round's group -- so a tile ends on the first tile with identical rows whatever the hash says
+    std::vector<std::vector<int32_t>> groups;
+    for (size_t i = 0; i < idx.size();) {
+        size_t j = i + 1;
+        while (j < idx.size() && !groupLess(idx[i], idx[j])) ++j;
+        if (j - i > 1) groups.emplace_back(idx.begin() + (std::ptrdiff_t)i, idx.begin() + (std::ptrdiff_t)j);
+        i = j;
+    }
+    std::vector<int> pairT, pairR, differs;
+    while (!groups.empty()) {
+        pairT.clear(); pairR.clear();
+        for (const auto& g : groups)
+            for (size_t k = 1; k < g.size(); ++k) { pairT.push_back(g[k]); pairR.push_back(g[0]); }
+        const size_t nP = pairT.size();
+        int *dT = D.get<int>(nP), *dR = D.get<int>(nP), *dDiff = D.get<int>(nP);
+        if (!dT || !dR || !dDiff) { why = "device allocation failed"; return 2; }
+        TL_OK(hipMemcpy(dT, pairT.data(), nP * 4, hipMemcpyHostToDevice));
+        TL_OK(hipMemcpy(dR, pairR.data(), nP * 4, hipMemcpyHostToDevice));
+        TL_OK(hipMemset(dDiff, 0, nP * 4));
+        hipLaunchKernelGGL(k_tl_blockDiffers, dim3((unsigned)nP), dim3(kT), 0, nullptr, a, b, dBase, dLen, dT, dR, dDiff);
+        TL_OK(hipGetLastError());
+        differs.resize(nP);
+        TL_OK(hipMemcpy(differs.data(), dDiff, nP * 4, hipMemcpyDeviceToHost));
+        std::vector<std::vector<int32_t>> next;
+        size_t k = 0;
+        for (const auto& g : groups) {
+            std::vector<int32_t> rest;
+            for (size_t m = 1; m < g.size(); ++m, ++k) {
+                if (differs[k]) rest.push_back(g[m]);
+                else { out.rep[(size_t)g[m]] = g[0]; --out.distinct; }
+            }
+            if (rest.size() > 1) next.push_back(std::move(rest));
+        }
+        groups.swap(next);
+    }
     return 0;
 }
 
