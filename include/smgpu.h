@@ -215,6 +215,30 @@ int smgpu_quality_sets(smgpu_handle* h, const smgpu_quality_params* p, int64_t c
 int smgpu_quality_coupled_sets(smgpu_handle* h, const smgpu_quality_params* p, const void* recvCc,
                                int64_t counts[7], int32_t* ids, int64_t cap);
 
+/* ---- the checks `checkMesh -allGeometry` adds (DESIGN.md "Mesh quality", 10.6) ------------------------------------------
+ * Face concavity (the sine of the worst concave corner and its angle in degrees), face flatness, face interpolation weight,
+ * owner / neighbour volume ratio (internal faces) and cell determinant, of the current points, on the same inputs as
+ * smgpu_mesh_quality.  Refusals, side effects and state as smgpu_mesh_quality (refused on an engine with a halo; needs no
+ * smgpu_set_params).  Ties go to the lowest id, sums are reduced in a fixed order.  An id is -1 where no element qualifies (no
+ * concave face, no face with more than 3 vertices, no internal face, no cell); the minima and averages are then 1 (determinant:
+ * 0) and the concavity figures 0.
+ * p == NULL: the defaults 10 degrees, 0.8, 0.05, 0.01, 0.001. */
+typedef struct smgpu_quality_geometry_params {
+    double concaveThreshold, flatnessThreshold, weightThreshold, volRatioThreshold, determinantThreshold;
+} smgpu_quality_geometry_params;
+typedef struct smgpu_quality_geometry {
+    int64_t nConcaveFaces;  double maxConcaveSin, maxConcaveAngle;  int32_t maxConcaveFace;
+    double minFlatness, avgFlatness;        int64_t nFlatnessFaces, nWarpedFaces;  int32_t minFlatnessFace;
+    double minFaceWeight, avgFaceWeight;    int64_t nLowWeightFaces;               int32_t minFaceWeightFace;
+    double minVolRatio, avgVolRatio;        int64_t nLowVolRatioFaces;             int32_t minVolRatioFace;
+    double minDeterminant, avgDeterminant;  int64_t nUnderdeterminedCells;         int32_t minDeterminantCell;
+} smgpu_quality_geometry;
+int smgpu_mesh_quality_geometry(smgpu_handle* h, const smgpu_quality_geometry_params* p, smgpu_quality_geometry* out);
+/* per-element field in polyMesh order: "faceConcavity" (the sine, under the default concaveThreshold; 0 where no corner is
+ * concave), "faceFlatness" (1 on triangles), "faceWeight", "faceVolumeRatio" (1 on boundary faces) [nFaces], "cellDeterminant"
+ * [nCells].  out == NULL: size only (*n). */
+int smgpu_quality_geometry_field(smgpu_handle* h, const char* name, double* out, int64_t* n);
+
 /* Timing: when enabled every kernel launch is bracketed by hipEvents on the handle's stream. */
 int smgpu_enable_timing(smgpu_handle* h, int32_t on);
 int smgpu_get_counters(smgpu_handle* h, smgpu_counters* out);

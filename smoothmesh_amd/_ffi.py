@@ -109,6 +109,23 @@ class Quality(C.Structure):
     ]
 
 
+class QualityGeometryParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("concaveThreshold", "flatnessThreshold", "weightThreshold", "volRatioThreshold",
+                                          "determinantThreshold")]
+
+
+class QualityGeometry(C.Structure):
+    _fields_ = [
+        ("nConcaveFaces", C.c_int64), ("maxConcaveSin", C.c_double), ("maxConcaveAngle", C.c_double), ("maxConcaveFace", C.c_int32),
+        ("minFlatness", C.c_double), ("avgFlatness", C.c_double), ("nFlatnessFaces", C.c_int64), ("nWarpedFaces", C.c_int64),
+        ("minFlatnessFace", C.c_int32),
+        ("minFaceWeight", C.c_double), ("avgFaceWeight", C.c_double), ("nLowWeightFaces", C.c_int64), ("minFaceWeightFace", C.c_int32),
+        ("minVolRatio", C.c_double), ("avgVolRatio", C.c_double), ("nLowVolRatioFaces", C.c_int64), ("minVolRatioFace", C.c_int32),
+        ("minDeterminant", C.c_double), ("avgDeterminant", C.c_double), ("nUnderdeterminedCells", C.c_int64),
+        ("minDeterminantCell", C.c_int32),
+    ]
+
+
 class QualityCoupling(C.Structure):
     _fields_ = [("myRank", C.c_int32), ("nPatches", C.c_int32), ("patchStart", c_i32p), ("patchSize", c_i32p), ("neighbRank", c_i32p)]
 
@@ -175,6 +192,8 @@ SYMBOLS = {
     "smgpu_quality_coupled_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_quality_sets": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.POINTER(C.c_int64), c_i32p, C.c_int64]),
     "smgpu_quality_coupled_sets": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(C.c_int64), c_i32p, C.c_int64]),
+    "smgpu_mesh_quality_geometry": (C.c_int, [C.c_void_p, C.POINTER(QualityGeometryParams), C.POINTER(QualityGeometry)]),
+    "smgpu_quality_geometry_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_addressing": (C.c_int, [C.c_void_p, C.c_char_p, c_i32p, c_i32p, C.POINTER(C.c_int64)]),
     "smgpu_debug_propose": (C.c_int, [C.c_void_p]),

@@ -1,4 +1,4 @@
-"""python -m smoothmesh_amd.check_quality -case <dir> [-parallel] [-time <t|constant|latestTime>] [-writeSets]
+"""python -m smoothmesh_amd.check_quality -case <dir> [-parallel] [-time <t|constant|latestTime>] [-writeSets] [-allGeometry]
 
 Prints the mesh quality report of a case in the format of `smoothMesh -checkQuality` (one block, label "mesh"): the serial
 case, or with -parallel every processorN/ sub-domain combined into the report of the whole mesh (smoothmesh_amd/quality.py).
@@ -7,6 +7,7 @@ the latest time directory by default, else constant; the faces from the newest i
 -writeSets: then the failing elements as OpenFOAM sets into <points instance>/sets, i.e. <time>/polyMesh/sets
 or constant/polyMesh/sets, in every processorN/ with local ids under -parallel; writeFormat and writeCompression from
 system/controlDict.  One "<<Writing" line per written set follows the report (with " in processorN" under -parallel).
+-allGeometry: the block also carries the five lines of the checks `checkMesh -allGeometry` adds; serial cases only.
 """
 import os
 import re
@@ -81,9 +82,17 @@ def _write_sets(pts_dir, root, sets, control):
         set_write_compression(False)
 
 
-def case_quality(case, parallel=False, time=None, device=0, write_sets=False):
+ALL_GEOMETRY_PARALLEL_REFUSAL = ("check_quality: -allGeometry is not available with -parallel: face weight and volume ratio across processor "
+                                 "faces need the neighbour rank's cell volume, which the decomposed report does not exchange (run it on the "
+                                 "reconstructed case)")
+
+
+def case_quality(case, parallel=False, time=None, device=0, write_sets=False, all_geometry=False):
     """MeshQuality of the serial case, or DecomposedMeshQuality of its processorN/ sub-domains.  write_sets: also write the
-    failing elements as sets into the points instance (every processorN/ under parallel) -> (quality, [(rank, name, size)])"""
+    failing elements as sets into the points instance (every processorN/ under parallel) -> (quality, [(rank, name, size)]).
+    all_geometry (serial only): the quality is the pair (MeshQuality, MeshQualityGeometry)"""
+    if all_geometry and parallel:
+        raise SystemExit(ALL_GEOMETRY_PARALLEL_REFUSAL)
     control = _control(case)
     if not parallel:
         from .engine import SmoothEngine
@@ -91,6 +100,8 @@ def case_quality(case, parallel=False, time=None, device=0, write_sets=False):
         e = SmoothEngine(_read(case, t), device=device)
         try:
             q = e.mesh_quality()
+            if all_geometry:
+                q = (q, e.mesh_quality_geometry())
             if not write_sets:
                 return q
             written = _write_sets(_instance(case, t, "points"), case, e.quality_sets(), control)
@@ -134,13 +145,18 @@ def main(argv=None):
     ap.add_argument("-parallel", action="store_true")
     ap.add_argument("-time", default=None, help="a time, constant or latestTime (default: the latest time, else constant)")
     ap.add_argument("-writeSets", action="store_true", help="write the failing faces and cells as sets into the points instance")
+    ap.add_argument("-allGeometry", action="store_true", help="also concavity, flatness, weight, volume ratio, determinant (serial only)")
     a = ap.parse_args(argv)
     from .quality import format_report
+    if a.allGeometry and a.parallel:
+        raise SystemExit(ALL_GEOMETRY_PARALLEL_REFUSAL)
+    geo = dict(all_geometry=True) if a.allGeometry else {}
+    fmt = (lambda q: format_report(q[0], "mesh", q[1])) if a.allGeometry else (lambda q: format_report(q, "mesh"))
     if not a.writeSets:
-        sys.stdout.write(format_report(case_quality(a.case, a.parallel, a.time), "mesh"))
+        sys.stdout.write(fmt(case_quality(a.case, a.parallel, a.time, **geo)))
         return 0
-    q, written = case_quality(a.case, a.parallel, a.time, write_sets=True)
-    sys.stdout.write(format_report(q, "mesh") + format_written(written))
+    q, written = case_quality(a.case, a.parallel, a.time, write_sets=True, **geo)
+    sys.stdout.write(fmt(q) + format_written(written))
     return 0
 
 

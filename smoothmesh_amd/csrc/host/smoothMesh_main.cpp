@@ -95,7 +95,7 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "faceAngleConstraint", "minEdgeLength", "totalMinFreeze", "minAngle", "maxAngle",
                                "layerMaxBlendingFraction", "layerEdgeLength", "layerExpansionRatio", "minLayers",
                                "maxLayers", "layerPatches", "smoothingPatches", "internalSmoothingBlendingFraction",
-                               "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets"};
+                               "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets", "allGeometry"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -109,6 +109,8 @@ Options parseArgs(int argc, char** argv) {
                       "       [-checkQuality b]   (mesh quality report of the initial and the final mesh, serial runs only)\n"
                       "       [-writeSets b]      (with -checkQuality: the final mesh's failing faces and cells as sets in\n"
                       "        <last written time>/polyMesh/sets)\n"
+                      "       [-allGeometry b]    (with -checkQuality: also face concavity, flatness, interpolation weight, volume\n"
+                      "        ratio and cell determinant, the checks of checkMesh -allGeometry)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -508,6 +510,11 @@ int main(int argc, char** argv) {
     if (writeSets && opt.parallel)
         fatal("-writeSets is not available with -parallel: it writes the sets of the -checkQuality report, which is serial only");
     if (writeSets && !checkQuality) fatal("-writeSets needs -checkQuality true: the sets are the failing elements of the quality report");
+    const bool allGeometry = opt.getB("allGeometry", false);
+    if (allGeometry && opt.parallel)
+        fatal("-allGeometry is not available with -parallel: face weight and volume ratio across processor faces need the neighbour "
+              "rank's cell volume, which the quality report does not exchange (run it on the reconstructed case)");
+    if (allGeometry && !checkQuality) fatal("-allGeometry needs -checkQuality true: its lines are part of the quality report");
     // SMOOTHMESH_TIMELINE=1: where this process's wall time goes, one stderr line per stage (seconds since main started)
     const bool timeline = std::getenv("SMOOTHMESH_TIMELINE") && std::atoi(std::getenv("SMOOTHMESH_TIMELINE")) > 0;
     auto mark = [&](const char* what) { if (timeline) std::fprintf(stderr, "[smoothMesh %8.3f s] %s\n", secondsSince(t0), what); };
@@ -818,6 +825,19 @@ int main(int argc, char** argv) {
         if (q.nNonPositiveVolume > 0 || q.nWrongOrientedFaces > 0)
             OUT("    ***Mesh has %lld non-positive volume cells and %lld wrongly oriented faces\n", (long long)q.nNonPositiveVolume,
                 (long long)q.nWrongOrientedFaces);
+        if (allGeometry) {   // the checks of checkMesh -allGeometry (include/smgpu.h, smgpu_mesh_quality_geometry)
+            smgpu_quality_geometry g;
+            check(smgpu_mesh_quality_geometry(R[0].h, nullptr, &g), "smgpu_mesh_quality_geometry");
+            OUT("    faceConcavity maxAngle %.9g concave %lld maxFace %d\n", g.maxConcaveAngle, (long long)g.nConcaveFaces, (int)g.maxConcaveFace);
+            OUT("    faceFlatness min %.9g average %.9g warped %lld minFace %d\n", g.minFlatness, g.avgFlatness, (long long)g.nWarpedFaces,
+                (int)g.minFlatnessFace);
+            OUT("    faceWeight min %.9g average %.9g low %lld minFace %d\n", g.minFaceWeight, g.avgFaceWeight, (long long)g.nLowWeightFaces,
+                (int)g.minFaceWeightFace);
+            OUT("    volumeRatio min %.9g average %.9g low %lld minFace %d\n", g.minVolRatio, g.avgVolRatio, (long long)g.nLowVolRatioFaces,
+                (int)g.minVolRatioFace);
+            OUT("    cellDeterminant min %.9g average %.9g underdetermined %lld minCell %d\n", g.minDeterminant, g.avgDeterminant,
+                (long long)g.nUnderdeterminedCells, (int)g.minDeterminantCell);
+        }
         OUTS("");
     };
     if (checkQuality) reportQuality("initial mesh");

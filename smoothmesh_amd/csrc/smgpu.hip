@@ -20,6 +20,7 @@
 #include "kernels_filter.hpp"
 #include "kernels_boundary.hpp"
 #include "kernels_quality.hpp"
+#include "kernels_quality_geom.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"
@@ -233,6 +234,12 @@ struct smgpu_handle {
     int qNProc = 0, qNotCounted = 0, qCountedProc = 0;
     std::vector<int32_t> qCoupling;
     smgpu_quality_part* qPartOut = nullptr;
+    // ... and of the -allGeometry checks (smgpu_mesh_quality_geometry, kernels_quality_geom.hpp): the cell volumes the face pass
+    // reads, the two partial slabs and the report, allocated by the first such call, outside `allocs` as well
+    double* qgVol = nullptr;
+    QGFace* qgFacePart = nullptr;
+    QGCell* qgCellPart = nullptr;
+    smgpu_quality_geometry* qgOut = nullptr;
     uint64_t qEpoch = 1, qPackEpoch = 0;   // qEpoch moves whenever the points (or the geometry variant) may have changed
     bool iterOpen = false;                  // between smgpu_iter_begin and smgpu_iter_end
 };
@@ -1119,7 +1126,7 @@ int smgpu_destroy(smgpu_handle* h) {
         for (const GeomTilesDev::Arr* a : {&h->gtDev.cellOrder, &h->gtDev.cellBeg, &h->gtDev.tpIds, &h->gtDev.tfIds, &h->gtDev.faceVerts, &h->gtDev.cellFaces, &h->gtDev.meta})
             if (a->p) (void)hipFree(a->p);
     for (void* p : {(void*)h->qOwn, (void*)h->qNei, (void*)h->qFacePart, (void*)h->qCellPart, (void*)h->qOut, (void*)h->qProcFace, (void*)h->qSlot,
-                    (void*)h->qPartOut})
+                    (void*)h->qPartOut, (void*)h->qgVol, (void*)h->qgFacePart, (void*)h->qgCellPart, (void*)h->qgOut})
         if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
@@ -3366,6 +3373,84 @@ int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t*
     if (!h || !name || !n) return fail("null argument");
     if (h->haloOn) return fail(kQualityHaloRefusal);
     return qualityField(h, "smgpu_quality_field", name, out, n, [&](double** o) { return runQuality(h, nullptr, o[0], o[1], o[2], o[3], o[4]); });
+}
+
+// ---- the checks `checkMesh -allGeometry` adds (kernels_quality_geom.hpp, DESIGN.md "Mesh quality", 10.6) -------------------
+static int qualityGeomEnsure(smgpu_handle* h) {
+    if (qualityEnsure(h)) return 1;
+    if (h->qgOut) return 0;
+    const MeshView& m = h->mv;
+    const size_t nFB = (size_t)std::max(1, qualityGrid(m.nFaces)), nCB = (size_t)std::max(1, qualityGrid(m.nCells));
+    hipError_t e = hipMalloc((void**)&h->qgVol, sizeof(double) * (size_t)std::max(1, m.nCells));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qgFacePart, sizeof(QGFace) * nFB);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qgCellPart, sizeof(QGCell) * nCB);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qgOut, sizeof(smgpu_quality_geometry));
+    if (e != hipSuccess) {
+        for (void** p : {(void**)&h->qgVol, (void**)&h->qgFacePart, (void**)&h->qgCellPart, (void**)&h->qgOut})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        return fail(std::string("mesh quality: device memory for the geometry report: ") + hipGetErrorString(e));
+    }
+    return 0;
+}
+// geometry of the current points (uncounted, as runQuality), the cell pass (volumes into h->qgVol), the face pass and the final
+// reduction into h->qgOut.  o[5]: optional per-element outputs faceConcavity, faceFlatness, faceWeight, faceVolumeRatio, cellDeterminant.
+static int runQualityGeom(smgpu_handle* h, const smgpu_quality_geometry_params* p, double* const* o) {
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityGeomEnsure(h)) return 1;
+    const MeshView& m = h->mv;
+    if (qualityGeometry(h)) return 1;
+    const smgpu_quality_geometry_params prm = p ? *p : smgpu_quality_geometry_params{10.0, 0.8, 0.05, 0.01, 0.001};
+    const QualityGeomThresholds thr{std::sin(prm.concaveThreshold * (SMGPU_PI / 180.0)), prm.flatnessThreshold, prm.weightThreshold,
+                                    prm.volRatioThreshold, prm.determinantThreshold};
+    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+    const State& s = h->st;
+    if (nCB > 0)
+        hipLaunchKernelGGL(k_quality_geom_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qgCellPart, h->qgVol, o[4]);
+    if (nFB > 0)
+        hipLaunchKernelGGL(k_quality_geom_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qgVol,
+                           h->qOwn, h->qNei, thr, h->qgFacePart, o[0], o[1], o[2], o[3]);
+    hipLaunchKernelGGL(k_quality_geom_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qgFacePart, nFB, h->qgCellPart, nCB, m.nCells,
+                       m.nInternalFaces, h->qgOut);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_mesh_quality_geometry(smgpu_handle* h, const smgpu_quality_geometry_params* p, smgpu_quality_geometry* out) {
+    if (!h || !out) return fail("null argument");
+    double* const none[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (runQualityGeom(h, p, none)) return 1;
+    HIP_OK(hipMemcpyAsync(out, h->qgOut, sizeof(smgpu_quality_geometry), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int smgpu_quality_geometry_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
+    if (!h || !name || !n) return fail("null argument");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    static const char* const names[5] = {"faceConcavity", "faceFlatness", "faceWeight", "faceVolumeRatio", "cellDeterminant"};
+    int which = -1;
+    for (int i = 0; i < 5; ++i)
+        if (std::strcmp(name, names[i]) == 0) which = i;
+    if (which < 0)
+        return fail(std::string("unknown quality geometry field ") + name + " (faceConcavity, faceFlatness, faceWeight, faceVolumeRatio, cellDeterminant)");
+    const int64_t cnt = which == 4 ? h->mv.nCells : h->mv.nFaces;
+    *n = cnt;
+    if (!out) return 0;
+    HIP_OK(hipSetDevice(h->device));
+    double* buf = nullptr;   // transient: one field's worth for this call only
+    HIP_OK(hipMalloc((void**)&buf, sizeof(double) * (size_t)std::max<int64_t>(1, cnt)));
+    double* o[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    o[which] = buf;
+    int rc = runQualityGeom(h, nullptr, o);
+    if (rc == 0 && cnt > 0) {
+        const hipError_t e = hipMemcpyAsync(out, buf, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream);
+        if (e != hipSuccess) rc = fail(std::string("smgpu_quality_geometry_field: ") + hipGetErrorString(e));
+    }
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (rc == 0 && es != hipSuccess) rc = fail(std::string("smgpu_quality_geometry_field: ") + hipGetErrorString(es));
+    (void)hipFree(buf);
+    return rc;
 }
 
 // ---- the coupled report of a sub-domain (DESIGN.md "Mesh quality", 10.4) ----------------------------------------------------

@@ -94,6 +94,36 @@ QUALITY_SETS = (
 )
 
 
+@dataclass
+class MeshQualityGeometry:
+    """smgpu_mesh_quality_geometry's report of the engine's current points: the checks `checkMesh -allGeometry` adds
+    (include/smgpu.h; definitions: DESIGN.md "Mesh quality", 10.6)."""
+    nConcaveFaces: int
+    maxConcaveSin: float
+    maxConcaveAngle: float
+    maxConcaveFace: int
+    minFlatness: float
+    avgFlatness: float
+    nFlatnessFaces: int
+    nWarpedFaces: int
+    minFlatnessFace: int
+    minFaceWeight: float
+    avgFaceWeight: float
+    nLowWeightFaces: int
+    minFaceWeightFace: int
+    minVolRatio: float
+    avgVolRatio: float
+    nLowVolRatioFaces: int
+    minVolRatioFace: int
+    minDeterminant: float
+    avgDeterminant: float
+    nUnderdeterminedCells: int
+    minDeterminantCell: int
+
+
+QUALITY_GEOMETRY_FIELDS = ("faceConcavity", "faceFlatness", "faceWeight", "faceVolumeRatio", "cellDeterminant")
+
+
 def patch_arrays(mesh: PolyMesh, layerPatches):
     """(start, size, kind, isLayer) of mesh.patches; kind 0 ordinary / 1 processor / 2 empty.  Selection as
     polyBoundaryMesh::patchSet (SM.C:1442-1471): a plain word matches a patch name, a quoted string is a regex."""
@@ -464,6 +494,24 @@ class SmoothEngine:
         with a halo; leaves the points and the loop as they were."""
         p = _ffi.QualityParams(nonOrthThreshold, skewThreshold, closedThreshold, aspectThreshold)
         return self._sets(self._lib.smgpu_quality_sets, C.byref(p))
+
+    def mesh_quality_geometry(self, concaveThreshold=10.0, flatnessThreshold=0.8, weightThreshold=0.05, volRatioThreshold=0.01,
+                              determinantThreshold=0.001) -> MeshQualityGeometry:
+        """The checks `checkMesh -allGeometry` adds, of the current points (include/smgpu.h, smgpu_mesh_quality_geometry): face
+        concavity, flatness, interpolation weight, volume ratio, cell determinant.  Side effects and refusals as mesh_quality."""
+        p = _ffi.QualityGeometryParams(concaveThreshold, flatnessThreshold, weightThreshold, volRatioThreshold, determinantThreshold)
+        q = _ffi.QualityGeometry()
+        self._check(self._lib.smgpu_mesh_quality_geometry(self._h, C.byref(p), C.byref(q)))
+        return MeshQualityGeometry(**{n: getattr(q, n) for n, _ in q._fields_})
+
+    def quality_geometry_field(self, name) -> np.ndarray:
+        """Per-element field of the geometry checks in polyMesh order: one of QUALITY_GEOMETRY_FIELDS (faceConcavity is the sine of
+        the worst concave corner under the default threshold; weight and volume ratio are 1 on boundary faces)."""
+        n = C.c_int64(0)
+        self._check(self._lib.smgpu_quality_geometry_field(self._h, name.encode(), None, C.byref(n)))
+        out = np.empty(n.value, dtype=np.float64)
+        self._check(self._lib.smgpu_quality_geometry_field(self._h, name.encode(), _p(out, _ffi.c_f64p), C.byref(n)))
+        return out
 
     # -- mesh quality of a sub-domain (DESIGN.md "Mesh quality", 10.4; smoothmesh_amd/quality.py drives these) -------------
     def quality_coupling(self, rank=None):

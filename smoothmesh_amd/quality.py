@@ -11,7 +11,7 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from .engine import MeshQuality, QUALITY_FIELDS, QUALITY_SETS  # noqa: F401
+from .engine import MeshQuality, MeshQualityGeometry, QUALITY_FIELDS, QUALITY_GEOMETRY_FIELDS, QUALITY_SETS  # noqa: F401
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
 _COUNTS = ("nNonPositiveVolume", "nZeroAreaFaces", "nSevereNonOrth", "nErrorNonOrth", "nSkewFaces", "nWrongOrientedFaces",
@@ -217,8 +217,20 @@ def format_sets_written(written):
     return "".join(f"    <<Writing {n} {desc[name]} to set {name}\n" for name, n in written)
 
 
-def format_report(q, which="mesh"):
-    """the block smoothMesh -checkQuality prints (csrc/host/smoothMesh_main.cpp, reportQuality)"""
+def format_geometry_lines(g):
+    """the five lines -allGeometry adds to the block (csrc/host/smoothMesh_main.cpp, reportQuality), of a MeshQualityGeometry"""
+    f = lambda x: "%.9g" % x  # noqa: E731
+    return (f"    faceConcavity maxAngle {f(g.maxConcaveAngle)} concave {g.nConcaveFaces} maxFace {g.maxConcaveFace}\n"
+            f"    faceFlatness min {f(g.minFlatness)} average {f(g.avgFlatness)} warped {g.nWarpedFaces} minFace {g.minFlatnessFace}\n"
+            f"    faceWeight min {f(g.minFaceWeight)} average {f(g.avgFaceWeight)} low {g.nLowWeightFaces} minFace {g.minFaceWeightFace}\n"
+            f"    volumeRatio min {f(g.minVolRatio)} average {f(g.avgVolRatio)} low {g.nLowVolRatioFaces} minFace {g.minVolRatioFace}\n"
+            f"    cellDeterminant min {f(g.minDeterminant)} average {f(g.avgDeterminant)} underdetermined {g.nUnderdeterminedCells} "
+            f"minCell {g.minDeterminantCell}\n")
+
+
+def format_report(q, which="mesh", geometry=None):
+    """the block smoothMesh -checkQuality prints (csrc/host/smoothMesh_main.cpp, reportQuality); geometry: the MeshQualityGeometry
+    whose lines -allGeometry adds before the block's blank line"""
     g = lambda x: "%.9g" % x  # noqa: E731
     lines = [f"Mesh quality ({which}):",
              f"    cells {q.nCells} faces {q.nFaces} internalFaces {q.nInternalFaces}",
@@ -233,4 +245,4 @@ def format_report(q, which="mesh"):
              f"    cellAspectRatio max {g(q.maxAspectRatio)} high {q.nHighAspectCells}"]
     if q.nNonPositiveVolume > 0 or q.nWrongOrientedFaces > 0:
         lines.append(f"    ***Mesh has {q.nNonPositiveVolume} non-positive volume cells and {q.nWrongOrientedFaces} wrongly oriented faces")
-    return "\n".join(lines) + "\n\n"
+    return "\n".join(lines) + "\n" + (format_geometry_lines(geometry) if geometry is not None else "") + "\n"
