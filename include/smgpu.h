@@ -239,6 +239,30 @@ int smgpu_mesh_quality_geometry(smgpu_handle* h, const smgpu_quality_geometry_pa
  * [nCells].  out == NULL: size only (*n). */
 int smgpu_quality_geometry_field(smgpu_handle* h, const char* name, double* out, int64_t* n);
 
+/* ---- the motion criteria: what checkMesh -meshQuality / snappyHexMesh test beyond the two reports above (DESIGN.md "Mesh
+ * quality", 10.7) --------------------------------------------------------------------------------------------------------
+ * Per face, of the current points, on the same inputs as smgpu_mesh_quality: the worst tet of the face-centre decomposition
+ * (minTetQuality), the best base point's worst tet of the base-point decomposition particle tracking uses (a face with none
+ * at or above tetThreshold has no valid base point), face twist and triangle twist (faces with more than 3 vertices).  A tet
+ * quality is the signed volume over that of the regular tetrahedron with the same circumradius: 1 at best, negative when
+ * inverted.  Refusals, side effects and state as smgpu_mesh_quality (refused on an engine with a halo; needs no
+ * smgpu_set_params).  Ties go to the lowest id, sums are reduced in a fixed order.  Where no face qualifies (no face; no face
+ * with more than 3 vertices) the minima and averages are 1 and the id is -1.
+ * p == NULL: the defaults 1e-15, 0.02, -1 (triangle twist off), as in the default meshQualityDict. */
+typedef struct smgpu_quality_motion_params {
+    double tetThreshold, twistThreshold, triangleTwistThreshold;
+} smgpu_quality_motion_params;
+typedef struct smgpu_quality_motion {
+    double minTetQuality, avgTetQuality;        int64_t nLowTetFaces;                 int32_t minTetFace;
+    double minBaseTetQuality;                   int64_t nNoBasePointFaces;            int32_t minBaseTetFace;
+    double minTwist, avgTwist;                  int64_t nTwistFaces, nLowTwistFaces;  int32_t minTwistFace;
+    double minTriangleTwist, avgTriangleTwist;  int64_t nLowTriangleTwistFaces;       int32_t minTriangleTwistFace;
+} smgpu_quality_motion;
+int smgpu_mesh_quality_motion(smgpu_handle* h, const smgpu_quality_motion_params* p, smgpu_quality_motion* out);
+/* per-face field in polyMesh order [nFaces]: "faceTetQuality", "faceBaseTetQuality", "faceTwist", "faceTriangleTwist" (1 on
+ * triangles).  out == NULL: size only (*n). */
+int smgpu_quality_motion_field(smgpu_handle* h, const char* name, double* out, int64_t* n);
+
 /* Timing: when enabled every kernel launch is bracketed by hipEvents on the handle's stream. */
 int smgpu_enable_timing(smgpu_handle* h, int32_t on);
 int smgpu_get_counters(smgpu_handle* h, smgpu_counters* out);

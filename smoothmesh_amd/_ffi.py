@@ -126,6 +126,21 @@ class QualityGeometry(C.Structure):
     ]
 
 
+class QualityMotionParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("tetThreshold", "twistThreshold", "triangleTwistThreshold")]
+
+
+class QualityMotion(C.Structure):
+    _fields_ = [
+        ("minTetQuality", C.c_double), ("avgTetQuality", C.c_double), ("nLowTetFaces", C.c_int64), ("minTetFace", C.c_int32),
+        ("minBaseTetQuality", C.c_double), ("nNoBasePointFaces", C.c_int64), ("minBaseTetFace", C.c_int32),
+        ("minTwist", C.c_double), ("avgTwist", C.c_double), ("nTwistFaces", C.c_int64), ("nLowTwistFaces", C.c_int64),
+        ("minTwistFace", C.c_int32),
+        ("minTriangleTwist", C.c_double), ("avgTriangleTwist", C.c_double), ("nLowTriangleTwistFaces", C.c_int64),
+        ("minTriangleTwistFace", C.c_int32),
+    ]
+
+
 class QualityCoupling(C.Structure):
     _fields_ = [("myRank", C.c_int32), ("nPatches", C.c_int32), ("patchStart", c_i32p), ("patchSize", c_i32p), ("neighbRank", c_i32p)]
 
@@ -194,6 +209,8 @@ SYMBOLS = {
     "smgpu_quality_coupled_sets": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(C.c_int64), c_i32p, C.c_int64]),
     "smgpu_mesh_quality_geometry": (C.c_int, [C.c_void_p, C.POINTER(QualityGeometryParams), C.POINTER(QualityGeometry)]),
     "smgpu_quality_geometry_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
+    "smgpu_mesh_quality_motion": (C.c_int, [C.c_void_p, C.POINTER(QualityMotionParams), C.POINTER(QualityMotion)]),
+    "smgpu_quality_motion_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_addressing": (C.c_int, [C.c_void_p, C.c_char_p, c_i32p, c_i32p, C.POINTER(C.c_int64)]),
     "smgpu_debug_propose": (C.c_int, [C.c_void_p]),

@@ -1,4 +1,4 @@
-"""python -m smoothmesh_amd.check_quality -case <dir> [-parallel] [-time <t|constant|latestTime>] [-writeSets] [-allGeometry]
+"""python -m smoothmesh_amd.check_quality -case <dir> [-parallel] [-time <t|constant|latestTime>] [-writeSets] [-allGeometry] [-meshQuality]
 
 Prints the mesh quality report of a case in the format of `smoothMesh -checkQuality` (one block, label "mesh"): the serial
 case, or with -parallel every processorN/ sub-domain combined into the report of the whole mesh (smoothmesh_amd/quality.py).
@@ -8,6 +8,8 @@ the latest time directory by default, else constant; the faces from the newest i
 or constant/polyMesh/sets, in every processorN/ with local ids under -parallel; writeFormat and writeCompression from
 system/controlDict.  One "<<Writing" line per written set follows the report (with " in processorN" under -parallel).
 -allGeometry: the block also carries the five lines of the checks `checkMesh -allGeometry` adds; serial cases only.
+-meshQuality: the block also carries the four lines of the motion criteria, face and base-point tet quality, face twist and triangle
+twist, after those of -allGeometry; serial cases only.
 """
 import os
 import re
@@ -87,12 +89,20 @@ ALL_GEOMETRY_PARALLEL_REFUSAL = ("check_quality: -allGeometry is not available w
                                  "reconstructed case)")
 
 
-def case_quality(case, parallel=False, time=None, device=0, write_sets=False, all_geometry=False):
+MESH_QUALITY_PARALLEL_REFUSAL = ("check_quality: -meshQuality is not available with -parallel: the tets and the twist of a processor face "
+                                 "need the neighbour rank's cell centre, which the decomposed report does not exchange for them (run it on "
+                                 "the reconstructed case)")
+
+
+def case_quality(case, parallel=False, time=None, device=0, write_sets=False, all_geometry=False, mesh_quality=False):
     """MeshQuality of the serial case, or DecomposedMeshQuality of its processorN/ sub-domains.  write_sets: also write the
     failing elements as sets into the points instance (every processorN/ under parallel) -> (quality, [(rank, name, size)]).
-    all_geometry (serial only): the quality is the pair (MeshQuality, MeshQualityGeometry)"""
+    all_geometry (serial only): the quality is the pair (MeshQuality, MeshQualityGeometry); mesh_quality (serial only): the triple
+    (MeshQuality, MeshQualityGeometry or None, MeshQualityMotion)"""
     if all_geometry and parallel:
         raise SystemExit(ALL_GEOMETRY_PARALLEL_REFUSAL)
+    if mesh_quality and parallel:
+        raise SystemExit(MESH_QUALITY_PARALLEL_REFUSAL)
     control = _control(case)
     if not parallel:
         from .engine import SmoothEngine
@@ -100,7 +110,9 @@ def case_quality(case, parallel=False, time=None, device=0, write_sets=False, al
         e = SmoothEngine(_read(case, t), device=device)
         try:
             q = e.mesh_quality()
-            if all_geometry:
+            if mesh_quality:
+                q = (q, e.mesh_quality_geometry() if all_geometry else None, e.mesh_quality_motion())
+            elif all_geometry:
                 q = (q, e.mesh_quality_geometry())
             if not write_sets:
                 return q
@@ -146,12 +158,17 @@ def main(argv=None):
     ap.add_argument("-time", default=None, help="a time, constant or latestTime (default: the latest time, else constant)")
     ap.add_argument("-writeSets", action="store_true", help="write the failing faces and cells as sets into the points instance")
     ap.add_argument("-allGeometry", action="store_true", help="also concavity, flatness, weight, volume ratio, determinant (serial only)")
+    ap.add_argument("-meshQuality", action="store_true", help="also face and base-point tet quality, twist, triangle twist (serial only)")
     a = ap.parse_args(argv)
     from .quality import format_report
     if a.allGeometry and a.parallel:
         raise SystemExit(ALL_GEOMETRY_PARALLEL_REFUSAL)
+    if a.meshQuality and a.parallel:
+        raise SystemExit(MESH_QUALITY_PARALLEL_REFUSAL)
     geo = dict(all_geometry=True) if a.allGeometry else {}
-    fmt = (lambda q: format_report(q[0], "mesh", q[1])) if a.allGeometry else (lambda q: format_report(q, "mesh"))
+    if a.meshQuality:
+        geo["mesh_quality"] = True
+    fmt = (lambda q: format_report(q[0], "mesh", *q[1:])) if geo else (lambda q: format_report(q, "mesh"))
     if not a.writeSets:
         sys.stdout.write(fmt(case_quality(a.case, a.parallel, a.time, **geo)))
         return 0

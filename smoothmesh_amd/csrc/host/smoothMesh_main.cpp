@@ -95,7 +95,8 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "faceAngleConstraint", "minEdgeLength", "totalMinFreeze", "minAngle", "maxAngle",
                                "layerMaxBlendingFraction", "layerEdgeLength", "layerExpansionRatio", "minLayers",
                                "maxLayers", "layerPatches", "smoothingPatches", "internalSmoothingBlendingFraction",
-                               "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets", "allGeometry"};
+                               "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets", "allGeometry",
+                               "meshQuality"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -111,6 +112,8 @@ Options parseArgs(int argc, char** argv) {
                       "        <last written time>/polyMesh/sets)\n"
                       "       [-allGeometry b]    (with -checkQuality: also face concavity, flatness, interpolation weight, volume\n"
                       "        ratio and cell determinant, the checks of checkMesh -allGeometry)\n"
+                      "       [-meshQuality b]    (with -checkQuality: also face tet quality, base-point tet quality, face twist and\n"
+                      "        triangle twist, the meshQualityDict criteria of checkMesh -meshQuality)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -515,6 +518,11 @@ int main(int argc, char** argv) {
         fatal("-allGeometry is not available with -parallel: face weight and volume ratio across processor faces need the neighbour "
               "rank's cell volume, which the quality report does not exchange (run it on the reconstructed case)");
     if (allGeometry && !checkQuality) fatal("-allGeometry needs -checkQuality true: its lines are part of the quality report");
+    const bool meshQuality = opt.getB("meshQuality", false);
+    if (meshQuality && opt.parallel)
+        fatal("-meshQuality is not available with -parallel: the tets and the twist of a processor face need the neighbour rank's cell "
+              "centre, which the quality report does not exchange (run it on the reconstructed case)");
+    if (meshQuality && !checkQuality) fatal("-meshQuality needs -checkQuality true: its lines are part of the quality report");
     // SMOOTHMESH_TIMELINE=1: where this process's wall time goes, one stderr line per stage (seconds since main started)
     const bool timeline = std::getenv("SMOOTHMESH_TIMELINE") && std::atoi(std::getenv("SMOOTHMESH_TIMELINE")) > 0;
     auto mark = [&](const char* what) { if (timeline) std::fprintf(stderr, "[smoothMesh %8.3f s] %s\n", secondsSince(t0), what); };
@@ -837,6 +845,18 @@ int main(int argc, char** argv) {
                 (int)g.minVolRatioFace);
             OUT("    cellDeterminant min %.9g average %.9g underdetermined %lld minCell %d\n", g.minDeterminant, g.avgDeterminant,
                 (long long)g.nUnderdeterminedCells, (int)g.minDeterminantCell);
+        }
+        if (meshQuality) {   // the motion criteria (include/smgpu.h, smgpu_mesh_quality_motion)
+            smgpu_quality_motion t;
+            check(smgpu_mesh_quality_motion(R[0].h, nullptr, &t), "smgpu_mesh_quality_motion");
+            OUT("    faceTets min %.9g average %.9g low %lld minFace %d\n", t.minTetQuality, t.avgTetQuality, (long long)t.nLowTetFaces,
+                (int)t.minTetFace);
+            OUT("    faceBaseTets min %.9g noBasePoint %lld minFace %d\n", t.minBaseTetQuality, (long long)t.nNoBasePointFaces,
+                (int)t.minBaseTetFace);
+            OUT("    faceTwist min %.9g average %.9g low %lld minFace %d\n", t.minTwist, t.avgTwist, (long long)t.nLowTwistFaces,
+                (int)t.minTwistFace);
+            OUT("    triangleTwist min %.9g average %.9g low %lld minFace %d\n", t.minTriangleTwist, t.avgTriangleTwist,
+                (long long)t.nLowTriangleTwistFaces, (int)t.minTriangleTwistFace);
         }
         OUTS("");
     };

@@ -1,0 +1,183 @@
+// kernels_quality_motion.hpp -- the motion criteria of the quality report (smgpu_mesh_quality_motion / smgpu_quality_motion_field:
+// include/smgpu.h): the meshQualityDict checks that the reports of kernels_quality.hpp and kernels_quality_geom.hpp do not cover --
+// face-centre tet quality, base-point tet quality (the decomposition particle tracking uses), face twist, triangle twist.
+// Definitions: DESIGN.md "Mesh quality", 10.7.
+//
+// Same inputs and the same layout as kernels_quality.hpp: face centres by face id and cell centres by cell id as the loop's
+// geometry launch publishes them, kQualityBlock threads, kQualityPer faces per lane (lane t the faces t, t + 256, ...), one partial
+// record per workgroup, one folding workgroup at the end, no float atomics.  A face pass only: every criterion is per face.
+// Nothing of kernels_quality.hpp is changed; its reduction helpers (qMinId, qBlockReduce) are used as they are.
+#pragma once
+#include "kernels_quality.hpp"
+
+namespace smgpu {
+
+// partial record of the face pass
+struct QMFace {
+    double minTet, sumTet, minBase, minTw, sumTw, minTri, sumTri;
+    int minTetId, minBaseId, minTwId, minTriId;
+    long long nLowTet, nNoBase, nTw, nLowTw, nLowTri;
+};
+
+__device__ __forceinline__ QMFace qmFaceEmpty() {
+    QMFace a;
+    a.minTet = a.minBase = a.minTw = a.minTri = __builtin_inf();
+    a.sumTet = a.sumTw = a.sumTri = 0.0;
+    a.minTetId = a.minBaseId = a.minTwId = a.minTriId = kQualityNoId;
+    a.nLowTet = a.nNoBase = a.nTw = a.nLowTw = a.nLowTri = 0;
+    return a;
+}
+__device__ __forceinline__ void qCombine(QMFace& a, const QMFace& b) {
+    qMinId(a.minTet, a.minTetId, b.minTet, b.minTetId);
+    qMinId(a.minBase, a.minBaseId, b.minBase, b.minBaseId);
+    qMinId(a.minTw, a.minTwId, b.minTw, b.minTwId);
+    qMinId(a.minTri, a.minTriId, b.minTri, b.minTriId);
+    a.sumTet += b.sumTet; a.sumTw += b.sumTw; a.sumTri += b.sumTri;
+    a.nLowTet += b.nLowTet; a.nNoBase += b.nNoBase; a.nTw += b.nTw; a.nLowTw += b.nLowTw; a.nLowTri += b.nLowTri;
+}
+__device__ __forceinline__ QMFace qShfl(const QMFace& a, int o) {
+    QMFace r;
+    r.minTet = __shfl_xor(a.minTet, o, 64); r.sumTet = __shfl_xor(a.sumTet, o, 64); r.minBase = __shfl_xor(a.minBase, o, 64);
+    r.minTw = __shfl_xor(a.minTw, o, 64); r.sumTw = __shfl_xor(a.sumTw, o, 64);
+    r.minTri = __shfl_xor(a.minTri, o, 64); r.sumTri = __shfl_xor(a.sumTri, o, 64);
+    r.minTetId = __shfl_xor(a.minTetId, o, 64); r.minBaseId = __shfl_xor(a.minBaseId, o, 64);
+    r.minTwId = __shfl_xor(a.minTwId, o, 64); r.minTriId = __shfl_xor(a.minTriId, o, 64);
+    r.nLowTet = __shfl_xor(a.nLowTet, o, 64); r.nNoBase = __shfl_xor(a.nNoBase, o, 64); r.nTw = __shfl_xor(a.nTw, o, 64);
+    r.nLowTw = __shfl_xor(a.nLowTw, o, 64); r.nLowTri = __shfl_xor(a.nLowTri, o, 64);
+    return r;
+}
+
+// k: the host's 8.0 / (9.0 * sqrt(3.0)), the normalisation that gives a regular tetrahedron |q| = 1
+struct QualityMotionThresholds { double tet, twist, triTwist, k; };
+
+// tet quality q(a, b, c, d) with u = b - a, v = c - a and n = u x v given (the two sides of a face share them), d the apex:
+// signed volume over the volume of the regular tetrahedron with the same circumradius
+__device__ __forceinline__ double qmTetQ(const V3& a, const V3& u, const V3& v, const V3& n, const V3& d, double k) {
+    const V3 w = d - a;
+    const double D = dot(n, w);
+    double R = SMGPU_GREAT;
+    if (fabs(D) >= SMGPU_ROOTVSMALL) {
+        const V3 num = (magSqr(w) * n + magSqr(v) * cross(w, u)) + magSqr(u) * cross(v, w);
+        R = fmin(mag(num) / (2.0 * fabs(D)), SMGPU_GREAT);
+    }
+    return (D / 6.0) / (k * ((R * R) * R) + SMGPU_ROOTVSMALL);
+}
+// the smaller of the owner's and (internal faces) the neighbour's tet on the triangle (a, a + u, a + v): the signs make a valid
+// tet positive on both sides
+__device__ __forceinline__ double qmTetPair(const V3& a, const V3& u, const V3& v, const V3& CO, bool internal, const V3& CN, double k) {
+    const V3 n = cross(u, v);
+    double q = -qmTetQ(a, u, v, n, CO, k);
+    if (internal) q = fmin(q, qmTetQ(a, u, v, n, CN, k));
+    return q;
+}
+
+// Two walks over the face's points, read by id as the skewness loop does (no per-lane array of points).  The first reads each
+// vertex once and gives the face-centre tets of both sides, the twist and the triangle twist: the first point and the first
+// valid unit triangle normal are carried to close the cycle.  The second gives the base-point tets: for every base the fan
+// (p_b, p_{b+k}, p_{b+k+1}), the edge p_{b+k+1} - p_b carried from one tet to the next.  out*: optional per-face fields.
+__device__ __forceinline__ void qmFaceOne(const MeshView& m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                          const double* __restrict__ cellCtr, const int* __restrict__ own, const int* __restrict__ nei,
+                                          const QualityMotionThresholds& thr, int f, QMFace& a, double* __restrict__ outTet,
+                                          double* __restrict__ outBase, double* __restrict__ outTw, double* __restrict__ outTri) {
+    const V3 Cf = ldv(fCtr, f);
+    const bool internal = f < m.nInternalFaces;
+    const V3 CO = ldv(cellCtr, own[f]);
+    const V3 CN = internal ? ldv(cellCtr, nei[f]) : v3(0, 0, 0);
+    const int jb = m.faceOff[f], nv = m.faceOff[f + 1] - jb;
+    const bool summed = nv > 3;
+    double tet = __builtin_inf(), tw = __builtin_inf(), tri = __builtin_inf();
+    int nValid = 0;
+    if (nv > 0) {
+        const V3 dv = sel3(internal, CN, Cf) - CO;
+        const V3 nHat = dv / (mag(dv) + SMGPU_VSMALL);
+        const V3 p0 = ldv(pts, m.facePts[jb]);
+        V3 cur = p0, hFirst = v3(0, 0, 0), hPrev = v3(0, 0, 0);
+        for (int i = 0; i < nv; ++i) {
+            const V3 nxt = (i + 1 < nv) ? ldv(pts, m.facePts[jb + i + 1]) : p0;
+            const V3 u = nxt - cur, v = Cf - cur;
+            tet = fmin(tet, qmTetPair(cur, u, v, CO, internal, CN, thr.k));
+            if (summed) {
+                const V3 t = 0.5 * cross(u, v);
+                const double mt = mag(t);
+                if (mt > SMGPU_VSMALL) {
+                    const V3 h = t / mt;
+                    tw = fmin(tw, dot(nHat, h));
+                    if (nValid > 0) tri = fmin(tri, dot(hPrev, h));
+                    else hFirst = h;
+                    hPrev = h;
+                    ++nValid;
+                }
+            }
+            cur = nxt;
+        }
+        if (nValid >= 2) tri = fmin(tri, dot(hPrev, hFirst));
+    }
+    double base = __builtin_inf();
+    for (int b = 0; b < nv; ++b) {
+        const V3 pb = ldv(pts, m.facePts[jb + b]);
+        int i = b + 1 < nv ? b + 1 : b + 1 - nv;
+        V3 u = ldv(pts, m.facePts[jb + i]) - pb;
+        double mb = __builtin_inf();
+        for (int k = 1; k + 2 <= nv; ++k) {
+            i = i + 1 < nv ? i + 1 : 0;
+            const V3 v = ldv(pts, m.facePts[jb + i]) - pb;
+            mb = fmin(mb, qmTetPair(pb, u, v, CO, internal, CN, thr.k));
+            u = v;
+        }
+        if (b == 0 || mb > base) base = mb;
+    }
+    a.minTet = tet; a.minTetId = f; a.sumTet = tet; a.nLowTet = (tet < thr.tet) ? 1 : 0;
+    a.minBase = base; a.minBaseId = f; a.nNoBase = (base < thr.tet) ? 1 : 0;
+    if (nValid < 1) tw = 1.0;
+    if (nValid < 2) tri = 1.0;
+    if (summed) {
+        a.minTw = tw; a.minTwId = f; a.sumTw = tw; a.nTw = 1; a.nLowTw = (tw < thr.twist) ? 1 : 0;
+        a.minTri = tri; a.minTriId = f; a.sumTri = tri; a.nLowTri = (tri < thr.triTwist) ? 1 : 0;
+    }
+    if (outTet) outTet[f] = tet;
+    if (outBase) outBase[f] = base;
+    if (outTw) outTw[f] = tw;
+    if (outTri) outTri[f] = tri;
+}
+__global__ void __launch_bounds__(kQualityBlock) k_quality_motion_faces(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                         const double* __restrict__ cellCtr, const int* __restrict__ own,
+                                                                         const int* __restrict__ nei, QualityMotionThresholds thr,
+                                                                         QMFace* __restrict__ part, double* __restrict__ outTet,
+                                                                         double* __restrict__ outBase, double* __restrict__ outTw,
+                                                                         double* __restrict__ outTri) {
+    __shared__ QMFace sh[kQualityBlock / 64];
+    QMFace a = qmFaceEmpty();
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int f = base + k * kQualityBlock;
+        if (f >= m.nFaces) break;
+        QMFace e = qmFaceEmpty();
+        qmFaceOne(m, pts, fCtr, cellCtr, own, nei, thr, f, e, outTet, outBase, outTw, outTri);
+        qCombine(a, e);
+    }
+    a = qBlockReduce(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// one workgroup, the fold of k_quality_geom_final: thread t folds the records t, t + 256, ... in that order, then the workgroup
+// reduction -> the report
+__global__ void __launch_bounds__(kQualityBlock) k_quality_motion_final(const QMFace* __restrict__ fPart, int nFB, int nFaces,
+                                                                         smgpu_quality_motion* __restrict__ out) {
+    __shared__ QMFace sh[kQualityBlock / 64];
+    QMFace a = qmFaceEmpty();
+    for (int i = threadIdx.x; i < nFB; i += kQualityBlock) qCombine(a, fPart[i]);
+    a = qBlockReduce(a, sh);
+    if (threadIdx.x != 0) return;
+    smgpu_quality_motion q;
+    const bool anyFace = nFaces > 0, anyTw = a.nTw > 0;
+    q.minTetQuality = anyFace ? a.minTet : 1.0; q.avgTetQuality = anyFace ? a.sumTet / (double)nFaces : 1.0;
+    q.nLowTetFaces = a.nLowTet; q.minTetFace = anyFace ? a.minTetId : -1;
+    q.minBaseTetQuality = anyFace ? a.minBase : 1.0; q.nNoBasePointFaces = a.nNoBase; q.minBaseTetFace = anyFace ? a.minBaseId : -1;
+    q.minTwist = anyTw ? a.minTw : 1.0; q.avgTwist = anyTw ? a.sumTw / (double)a.nTw : 1.0;
+    q.nTwistFaces = a.nTw; q.nLowTwistFaces = a.nLowTw; q.minTwistFace = anyTw ? a.minTwId : -1;
+    q.minTriangleTwist = anyTw ? a.minTri : 1.0; q.avgTriangleTwist = anyTw ? a.sumTri / (double)a.nTw : 1.0;
+    q.nLowTriangleTwistFaces = a.nLowTri; q.minTriangleTwistFace = anyTw ? a.minTriId : -1;
+    *out = q;
+}
+
+}  // namespace smgpu

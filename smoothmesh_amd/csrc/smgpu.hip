@@ -21,6 +21,7 @@
 #include "kernels_boundary.hpp"
 #include "kernels_quality.hpp"
 #include "kernels_quality_geom.hpp"
+#include "kernels_quality_motion.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"
@@ -240,6 +241,9 @@ struct smgpu_handle {
     QGFace* qgFacePart = nullptr;
     QGCell* qgCellPart = nullptr;
     smgpu_quality_geometry* qgOut = nullptr;
+    // ... and of the motion criteria (smgpu_mesh_quality_motion, kernels_quality_motion.hpp): the partial slab and the report, likewise
+    QMFace* qmFacePart = nullptr;
+    smgpu_quality_motion* qmOut = nullptr;
     uint64_t qEpoch = 1, qPackEpoch = 0;   // qEpoch moves whenever the points (or the geometry variant) may have changed
     bool iterOpen = false;                  // between smgpu_iter_begin and smgpu_iter_end
 };
@@ -1126,7 +1130,8 @@ int smgpu_destroy(smgpu_handle* h) {
         for (const GeomTilesDev::Arr* a : {&h->gtDev.cellOrder, &h->gtDev.cellBeg, &h->gtDev.tpIds, &h->gtDev.tfIds, &h->gtDev.faceVerts, &h->gtDev.cellFaces, &h->gtDev.meta})
             if (a->p) (void)hipFree(a->p);
     for (void* p : {(void*)h->qOwn, (void*)h->qNei, (void*)h->qFacePart, (void*)h->qCellPart, (void*)h->qOut, (void*)h->qProcFace, (void*)h->qSlot,
-                    (void*)h->qPartOut, (void*)h->qgVol, (void*)h->qgFacePart, (void*)h->qgCellPart, (void*)h->qgOut})
+                    (void*)h->qPartOut, (void*)h->qgVol, (void*)h->qgFacePart, (void*)h->qgCellPart, (void*)h->qgOut,
+                    (void*)h->qmFacePart, (void*)h->qmOut})
         if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
@@ -3449,6 +3454,78 @@ int smgpu_quality_geometry_field(smgpu_handle* h, const char* name, double* out,
     }
     const hipError_t es = hipStreamSynchronize(h->stream);
     if (rc == 0 && es != hipSuccess) rc = fail(std::string("smgpu_quality_geometry_field: ") + hipGetErrorString(es));
+    (void)hipFree(buf);
+    return rc;
+}
+
+// ---- the motion criteria (kernels_quality_motion.hpp, DESIGN.md "Mesh quality", 10.7) ---------------------------------------
+static int qualityMotionEnsure(smgpu_handle* h) {
+    if (qualityEnsure(h)) return 1;
+    if (h->qmOut) return 0;
+    const size_t nFB = (size_t)std::max(1, qualityGrid(h->mv.nFaces));
+    hipError_t e = hipMalloc((void**)&h->qmFacePart, sizeof(QMFace) * nFB);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qmOut, sizeof(smgpu_quality_motion));
+    if (e != hipSuccess) {
+        for (void** p : {(void**)&h->qmFacePart, (void**)&h->qmOut})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        return fail(std::string("mesh quality: device memory for the motion criteria: ") + hipGetErrorString(e));
+    }
+    return 0;
+}
+// geometry of the current points (uncounted, as runQuality), the face pass and the final reduction into h->qmOut.
+// o[4]: optional per-face outputs faceTetQuality, faceBaseTetQuality, faceTwist, faceTriangleTwist.
+static int runQualityMotion(smgpu_handle* h, const smgpu_quality_motion_params* p, double* const* o) {
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityMotionEnsure(h)) return 1;
+    const MeshView& m = h->mv;
+    if (qualityGeometry(h)) return 1;
+    const smgpu_quality_motion_params prm = p ? *p : smgpu_quality_motion_params{1e-15, 0.02, -1.0};
+    // k = 8 / (9 sqrt 3) is the host's double, as the contract says: the kernel takes it as an argument
+    const QualityMotionThresholds thr{prm.tetThreshold, prm.twistThreshold, prm.triangleTwistThreshold, 8.0 / (9.0 * std::sqrt(3.0))};
+    const int nFB = qualityGrid(m.nFaces);
+    const State& s = h->st;
+    if (nFB > 0)
+        hipLaunchKernelGGL(k_quality_motion_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.cellCtr, h->qOwn, h->qNei,
+                           thr, h->qmFacePart, o[0], o[1], o[2], o[3]);
+    hipLaunchKernelGGL(k_quality_motion_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qmFacePart, nFB, m.nFaces, h->qmOut);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_mesh_quality_motion(smgpu_handle* h, const smgpu_quality_motion_params* p, smgpu_quality_motion* out) {
+    if (!h || !out) return fail("null argument");
+    double* const none[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (runQualityMotion(h, p, none)) return 1;
+    HIP_OK(hipMemcpyAsync(out, h->qmOut, sizeof(smgpu_quality_motion), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int smgpu_quality_motion_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
+    if (!h || !name || !n) return fail("null argument");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    static const char* const names[4] = {"faceTetQuality", "faceBaseTetQuality", "faceTwist", "faceTriangleTwist"};
+    int which = -1;
+    for (int i = 0; i < 4; ++i)
+        if (std::strcmp(name, names[i]) == 0) which = i;
+    if (which < 0)
+        return fail(std::string("unknown quality motion field ") + name + " (faceTetQuality, faceBaseTetQuality, faceTwist, faceTriangleTwist)");
+    const int64_t cnt = h->mv.nFaces;
+    *n = cnt;
+    if (!out) return 0;
+    HIP_OK(hipSetDevice(h->device));
+    double* buf = nullptr;   // transient: one field's worth for this call only
+    HIP_OK(hipMalloc((void**)&buf, sizeof(double) * (size_t)std::max<int64_t>(1, cnt)));
+    double* o[4] = {nullptr, nullptr, nullptr, nullptr};
+    o[which] = buf;
+    int rc = runQualityMotion(h, nullptr, o);
+    if (rc == 0 && cnt > 0) {
+        const hipError_t e = hipMemcpyAsync(out, buf, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream);
+        if (e != hipSuccess) rc = fail(std::string("smgpu_quality_motion_field: ") + hipGetErrorString(e));
+    }
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (rc == 0 && es != hipSuccess) rc = fail(std::string("smgpu_quality_motion_field: ") + hipGetErrorString(es));
     (void)hipFree(buf);
     return rc;
 }

@@ -124,6 +124,31 @@ class MeshQualityGeometry:
 QUALITY_GEOMETRY_FIELDS = ("faceConcavity", "faceFlatness", "faceWeight", "faceVolumeRatio", "cellDeterminant")
 
 
+@dataclass
+class MeshQualityMotion:
+    """smgpu_mesh_quality_motion's report of the engine's current points: the motion criteria, i.e. the meshQualityDict checks the
+    other two reports do not cover (include/smgpu.h; definitions: DESIGN.md "Mesh quality", 10.7)."""
+    minTetQuality: float
+    avgTetQuality: float
+    nLowTetFaces: int
+    minTetFace: int
+    minBaseTetQuality: float
+    nNoBasePointFaces: int
+    minBaseTetFace: int
+    minTwist: float
+    avgTwist: float
+    nTwistFaces: int
+    nLowTwistFaces: int
+    minTwistFace: int
+    minTriangleTwist: float
+    avgTriangleTwist: float
+    nLowTriangleTwistFaces: int
+    minTriangleTwistFace: int
+
+
+QUALITY_MOTION_FIELDS = ("faceTetQuality", "faceBaseTetQuality", "faceTwist", "faceTriangleTwist")
+
+
 def patch_arrays(mesh: PolyMesh, layerPatches):
     """(start, size, kind, isLayer) of mesh.patches; kind 0 ordinary / 1 processor / 2 empty.  Selection as
     polyBoundaryMesh::patchSet (SM.C:1442-1471): a plain word matches a patch name, a quoted string is a regex."""
@@ -511,6 +536,23 @@ class SmoothEngine:
         self._check(self._lib.smgpu_quality_geometry_field(self._h, name.encode(), None, C.byref(n)))
         out = np.empty(n.value, dtype=np.float64)
         self._check(self._lib.smgpu_quality_geometry_field(self._h, name.encode(), _p(out, _ffi.c_f64p), C.byref(n)))
+        return out
+
+    def mesh_quality_motion(self, tetThreshold=1e-15, twistThreshold=0.02, triangleTwistThreshold=-1.0) -> MeshQualityMotion:
+        """The motion criteria of the current points (include/smgpu.h, smgpu_mesh_quality_motion): face-centre and base-point tet
+        quality, face twist, triangle twist, under the default meshQualityDict thresholds.  Side effects and refusals as mesh_quality."""
+        p = _ffi.QualityMotionParams(tetThreshold, twistThreshold, triangleTwistThreshold)
+        q = _ffi.QualityMotion()
+        self._check(self._lib.smgpu_mesh_quality_motion(self._h, C.byref(p), C.byref(q)))
+        return MeshQualityMotion(**{n: getattr(q, n) for n, _ in q._fields_})
+
+    def quality_motion_field(self, name) -> np.ndarray:
+        """Per-face field of the motion criteria in polyMesh order: one of QUALITY_MOTION_FIELDS (twist and triangle twist are 1 on
+        triangles)."""
+        n = C.c_int64(0)
+        self._check(self._lib.smgpu_quality_motion_field(self._h, name.encode(), None, C.byref(n)))
+        out = np.empty(n.value, dtype=np.float64)
+        self._check(self._lib.smgpu_quality_motion_field(self._h, name.encode(), _p(out, _ffi.c_f64p), C.byref(n)))
         return out
 
     # -- mesh quality of a sub-domain (DESIGN.md "Mesh quality", 10.4; smoothmesh_amd/quality.py drives these) -------------

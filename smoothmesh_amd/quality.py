@@ -11,7 +11,8 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from .engine import MeshQuality, MeshQualityGeometry, QUALITY_FIELDS, QUALITY_GEOMETRY_FIELDS, QUALITY_SETS  # noqa: F401
+from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QUALITY_FIELDS, QUALITY_GEOMETRY_FIELDS,  # noqa: F401
+                     QUALITY_MOTION_FIELDS, QUALITY_SETS)
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
 _COUNTS = ("nNonPositiveVolume", "nZeroAreaFaces", "nSevereNonOrth", "nErrorNonOrth", "nSkewFaces", "nWrongOrientedFaces",
@@ -228,9 +229,19 @@ def format_geometry_lines(g):
             f"minCell {g.minDeterminantCell}\n")
 
 
-def format_report(q, which="mesh", geometry=None):
+def format_motion_lines(t):
+    """the four lines -meshQuality adds to the block (csrc/host/smoothMesh_main.cpp, reportQuality), of a MeshQualityMotion"""
+    f = lambda x: "%.9g" % x  # noqa: E731
+    return (f"    faceTets min {f(t.minTetQuality)} average {f(t.avgTetQuality)} low {t.nLowTetFaces} minFace {t.minTetFace}\n"
+            f"    faceBaseTets min {f(t.minBaseTetQuality)} noBasePoint {t.nNoBasePointFaces} minFace {t.minBaseTetFace}\n"
+            f"    faceTwist min {f(t.minTwist)} average {f(t.avgTwist)} low {t.nLowTwistFaces} minFace {t.minTwistFace}\n"
+            f"    triangleTwist min {f(t.minTriangleTwist)} average {f(t.avgTriangleTwist)} low {t.nLowTriangleTwistFaces} "
+            f"minFace {t.minTriangleTwistFace}\n")
+
+
+def format_report(q, which="mesh", geometry=None, motion=None):
     """the block smoothMesh -checkQuality prints (csrc/host/smoothMesh_main.cpp, reportQuality); geometry: the MeshQualityGeometry
-    whose lines -allGeometry adds before the block's blank line"""
+    whose lines -allGeometry adds before the block's blank line; motion: the MeshQualityMotion whose lines -meshQuality adds after them"""
     g = lambda x: "%.9g" % x  # noqa: E731
     lines = [f"Mesh quality ({which}):",
              f"    cells {q.nCells} faces {q.nFaces} internalFaces {q.nInternalFaces}",
@@ -245,4 +256,5 @@ def format_report(q, which="mesh", geometry=None):
              f"    cellAspectRatio max {g(q.maxAspectRatio)} high {q.nHighAspectCells}"]
     if q.nNonPositiveVolume > 0 or q.nWrongOrientedFaces > 0:
         lines.append(f"    ***Mesh has {q.nNonPositiveVolume} non-positive volume cells and {q.nWrongOrientedFaces} wrongly oriented faces")
-    return "\n".join(lines) + "\n" + (format_geometry_lines(geometry) if geometry is not None else "") + "\n"
+    return ("\n".join(lines) + "\n" + (format_geometry_lines(geometry) if geometry is not None else "")
+            + (format_motion_lines(motion) if motion is not None else "") + "\n")
