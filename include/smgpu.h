@@ -263,6 +263,46 @@ int smgpu_mesh_quality_motion(smgpu_handle* h, const smgpu_quality_motion_params
  * triangles).  out == NULL: size only (*n). */
 int smgpu_quality_motion_field(smgpu_handle* h, const char* name, double* out, int64_t* n);
 
+/* ---- the two reports above for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.8) -------------------------
+ * The steps of smgpu_quality_coupled_pack / _report, with one more buffer for the geometry report:
+ *   1. smgpu_quality_coupled_pack, then smgpu_quality_coupled_pack_volumes on the same points: the signed volume of every cell
+ *      (formula and summation order of smgpu_mesh_quality_geometry) into the engine's scratch, and the owner cell's volume of
+ *      every processor face into the DEVICE buffer sendVc: 1 double per face, the slot order of sendCc.
+ *   2. the host fills recvCc as before and recvVc (device, same layout as sendVc) the same way.
+ *   3. smgpu_quality_coupled_geometry_report / _field (recvCc and recvVc) and smgpu_quality_coupled_motion_report / _field (recvCc
+ *      only; needs no pack_volumes), on the geometry of step 1.
+ * A processor face takes the internal-face branch of every criterion (weight, volume ratio, both tet decompositions, twist) with
+ * C_N and V_N of the neighbour rank, and a cell's determinant runs over its internal and its processor faces.  The records count a
+ * processor face only on the side with myRank < neighbRank; fields carry its values on both sides.  Refusals, state and side
+ * effects as smgpu_quality_coupled_report; the geometry calls are also refused when no pack_volumes followed the pack.  Field
+ * names as smgpu_quality_geometry_field / smgpu_quality_motion_field.
+ * The records are the serial structs with every average replaced by its sum, behind the denominators the combine needs (after the
+ * counted-once rule); ids local, -1 where this rank has no such element; maxConcaveAngle is this rank's own (the combine takes the
+ * winner's pair).  Combine them as DESIGN.md 10.8 says (smoothmesh_amd/quality.py combine_quality_geometry / _motion). */
+typedef struct smgpu_quality_geometry_part {
+    int64_t nCells, nFaces, nInternalFaces;
+    int64_t nConcaveFaces;  double maxConcaveSin, maxConcaveAngle;  int32_t maxConcaveFace;
+    double minFlatness, sumFlatness;        int64_t nFlatnessFaces, nWarpedFaces;  int32_t minFlatnessFace;
+    double minFaceWeight, sumFaceWeight;    int64_t nLowWeightFaces;               int32_t minFaceWeightFace;
+    double minVolRatio, sumVolRatio;        int64_t nLowVolRatioFaces;             int32_t minVolRatioFace;
+    double minDeterminant, sumDeterminant;  int64_t nUnderdeterminedCells;         int32_t minDeterminantCell;
+} smgpu_quality_geometry_part;
+typedef struct smgpu_quality_motion_part {
+    int64_t nFaces;
+    double minTetQuality, sumTetQuality;        int64_t nLowTetFaces;                 int32_t minTetFace;
+    double minBaseTetQuality;                   int64_t nNoBasePointFaces;            int32_t minBaseTetFace;
+    double minTwist, sumTwist;                  int64_t nTwistFaces, nLowTwistFaces;  int32_t minTwistFace;
+    double minTriangleTwist, sumTriangleTwist;  int64_t nLowTriangleTwistFaces;       int32_t minTriangleTwistFace;
+} smgpu_quality_motion_part;
+/* *nProcFaces (may be NULL) = the number of processor faces = the doubles of sendVc, which may be NULL only when that is 0 */
+int smgpu_quality_coupled_pack_volumes(smgpu_handle* h, void* sendVc, int64_t* nProcFaces);
+int smgpu_quality_coupled_geometry_report(smgpu_handle* h, const smgpu_quality_geometry_params* p, const void* recvCc, const void* recvVc,
+                                          smgpu_quality_geometry_part* out);
+int smgpu_quality_coupled_geometry_field(smgpu_handle* h, const char* name, const void* recvCc, const void* recvVc, double* out, int64_t* n);
+int smgpu_quality_coupled_motion_report(smgpu_handle* h, const smgpu_quality_motion_params* p, const void* recvCc,
+                                        smgpu_quality_motion_part* out);
+int smgpu_quality_coupled_motion_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n);
+
 /* Timing: when enabled every kernel launch is bracketed by hipEvents on the handle's stream. */
 int smgpu_enable_timing(smgpu_handle* h, int32_t on);
 int smgpu_get_counters(smgpu_handle* h, smgpu_counters* out);

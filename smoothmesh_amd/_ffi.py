@@ -150,6 +150,20 @@ class QualityPart(C.Structure):
     _fields_ = [("sumNonOrth" if n == "avgNonOrth" else n, t) for n, t in Quality._fields_]
 
 
+def _sums(fields):
+    return [("sum" + n[3:] if n.startswith("avg") else n, t) for n, t in fields]
+
+
+class QualityGeometryPart(C.Structure):
+    """smgpu_quality_geometry_part: the counted denominators, then QualityGeometry with every average replaced by its sum"""
+    _fields_ = [("nCells", C.c_int64), ("nFaces", C.c_int64), ("nInternalFaces", C.c_int64)] + _sums(QualityGeometry._fields_)
+
+
+class QualityMotionPart(C.Structure):
+    """smgpu_quality_motion_part: the counted faces, then QualityMotion with every average replaced by its sum"""
+    _fields_ = [("nFaces", C.c_int64)] + _sums(QualityMotion._fields_)
+
+
 # every symbol include/smgpu.h declares: (restype, argtypes)
 SYMBOLS = {
     "smgpu_last_error": (C.c_char_p, []),
@@ -211,6 +225,12 @@ SYMBOLS = {
     "smgpu_quality_geometry_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_mesh_quality_motion": (C.c_int, [C.c_void_p, C.POINTER(QualityMotionParams), C.POINTER(QualityMotion)]),
     "smgpu_quality_motion_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
+    "smgpu_quality_coupled_pack_volumes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "smgpu_quality_coupled_geometry_report": (C.c_int, [C.c_void_p, C.POINTER(QualityGeometryParams), C.c_void_p, C.c_void_p,
+                                                        C.POINTER(QualityGeometryPart)]),
+    "smgpu_quality_coupled_geometry_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),
+    "smgpu_quality_coupled_motion_report": (C.c_int, [C.c_void_p, C.POINTER(QualityMotionParams), C.c_void_p, C.POINTER(QualityMotionPart)]),
+    "smgpu_quality_coupled_motion_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_addressing": (C.c_int, [C.c_void_p, C.c_char_p, c_i32p, c_i32p, C.POINTER(C.c_int64)]),
     "smgpu_debug_propose": (C.c_int, [C.c_void_p]),

@@ -94,6 +94,34 @@ MESH_QUALITY_PARALLEL_REFUSAL = ("check_quality: -meshQuality is not available w
                                  "the reconstructed case)")
 
 
+def _read_subs(case, time):
+    """(processor directories [(rank, name)], the selected time, the SubDomain of every processorN/)"""
+    from .decompose import SubDomain
+    procs = sorted((int(d[9:]), d) for d in os.listdir(case) if re.fullmatch(r"processor\d+", d))
+    if not procs or [p[0] for p in procs] != list(range(len(procs))):
+        raise SystemExit(f"check_quality: no processor0 .. processorN-1 directories in {case}")
+    t = _select_time(os.path.join(case, procs[0][1]), time)
+    subs = []
+    for r, d in procs:
+        root = os.path.join(case, d)
+        m = _read(root, t)
+        faces = _addressing(root, "faceProcAddressing")
+        subs.append(SubDomain(m, r, len(procs), np.zeros(0, np.int64), _addressing(root, "cellProcAddressing"),
+                              None if faces is None else np.abs(faces) - 1))          # decomposePar: +-(global face + 1)
+    return procs, t, subs
+
+
+def decomposed_case_quality(case, time=None, device=0, all_geometry=False, mesh_quality=False):
+    """The reports of a decomposed case, every processorN/ combined: (DecomposedMeshQuality,
+    DecomposedMeshQualityGeometry or None, DecomposedMeshQualityMotion or None), which format_report(*q) prints as one block.  The
+    shell spellings -parallel -allGeometry / -meshQuality keep their refusals; this function is the way in."""
+    from .quality import decomposed_mesh_quality, decomposed_mesh_quality_geometry, decomposed_mesh_quality_motion
+    _, _, subs = _read_subs(case, time)
+    return (decomposed_mesh_quality(subs, device=device),
+            decomposed_mesh_quality_geometry(subs, device=device) if all_geometry else None,
+            decomposed_mesh_quality_motion(subs, device=device) if mesh_quality else None)
+
+
 def case_quality(case, parallel=False, time=None, device=0, write_sets=False, all_geometry=False, mesh_quality=False):
     """MeshQuality of the serial case, or DecomposedMeshQuality of its processorN/ sub-domains.  write_sets: also write the
     failing elements as sets into the points instance (every processorN/ under parallel) -> (quality, [(rank, name, size)]).
@@ -120,19 +148,8 @@ def case_quality(case, parallel=False, time=None, device=0, write_sets=False, al
             return q, [(None, n, k) for n, k in written]
         finally:
             e.close()
-    from .decompose import SubDomain
     from .quality import decomposed_mesh_quality, decomposed_quality_sets
-    procs = sorted((int(d[9:]), d) for d in os.listdir(case) if re.fullmatch(r"processor\d+", d))
-    if not procs or [p[0] for p in procs] != list(range(len(procs))):
-        raise SystemExit(f"check_quality: no processor0 .. processorN-1 directories in {case}")
-    t = _select_time(os.path.join(case, procs[0][1]), time)
-    subs = []
-    for r, d in procs:
-        root = os.path.join(case, d)
-        m = _read(root, t)
-        faces = _addressing(root, "faceProcAddressing")
-        subs.append(SubDomain(m, r, len(procs), np.zeros(0, np.int64), _addressing(root, "cellProcAddressing"),
-                              None if faces is None else np.abs(faces) - 1))          # decomposePar: +-(global face + 1)
+    procs, t, subs = _read_subs(case, time)
     q = decomposed_mesh_quality(subs, device=device)
     if not write_sets:
         return q

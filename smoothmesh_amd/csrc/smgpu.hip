@@ -22,6 +22,7 @@
 #include "kernels_quality.hpp"
 #include "kernels_quality_geom.hpp"
 #include "kernels_quality_motion.hpp"
+#include "kernels_quality_coupled.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"
@@ -244,6 +245,13 @@ struct smgpu_handle {
     // ... and of the motion criteria (smgpu_mesh_quality_motion, kernels_quality_motion.hpp): the partial slab and the report, likewise
     QMFace* qmFacePart = nullptr;
     smgpu_quality_motion* qmOut = nullptr;
+    // ... and of the two reports above for a sub-domain (smgpu_quality_coupled_geometry_* / _motion_*, kernels_quality_coupled.hpp):
+    // the records; the scratch is the serial reports' (qgVol, the partial slabs).  qVolEpoch, qVolCoupling: the geometry epoch and the coupling of the
+    // last pack_volumes (a later pack with another coupling lays the slots out anew: sendVc / recvVc of the old one no longer fit)
+    smgpu_quality_geometry_part* qgPartOut = nullptr;
+    smgpu_quality_motion_part* qmPartOut = nullptr;
+    uint64_t qVolEpoch = 0;
+    std::vector<int32_t> qVolCoupling;
     uint64_t qEpoch = 1, qPackEpoch = 0;   // qEpoch moves whenever the points (or the geometry variant) may have changed
     bool iterOpen = false;                  // between smgpu_iter_begin and smgpu_iter_end
 };
@@ -1131,7 +1139,7 @@ int smgpu_destroy(smgpu_handle* h) {
             if (a->p) (void)hipFree(a->p);
     for (void* p : {(void*)h->qOwn, (void*)h->qNei, (void*)h->qFacePart, (void*)h->qCellPart, (void*)h->qOut, (void*)h->qProcFace, (void*)h->qSlot,
                     (void*)h->qPartOut, (void*)h->qgVol, (void*)h->qgFacePart, (void*)h->qgCellPart, (void*)h->qgOut,
-                    (void*)h->qmFacePart, (void*)h->qmOut})
+                    (void*)h->qmFacePart, (void*)h->qmOut, (void*)h->qgPartOut, (void*)h->qmPartOut})
         if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
@@ -3636,6 +3644,158 @@ int smgpu_quality_coupled_field(smgpu_handle* h, const char* name, const void* r
     return qualityField(h, "smgpu_quality_coupled_field", name, out, n, [&](double** o) {
         return runQualityCoupled(h, "smgpu_quality_coupled_field", nullptr, recvCc, o[0], o[1], o[2], o[3], o[4]);
     });
+}
+
+// ---- the -allGeometry checks and the motion criteria of a sub-domain (kernels_quality_coupled.hpp, DESIGN.md "Mesh quality", 10.8)
+static int qualityCoupledReady(smgpu_handle* h, const char* api, const void* recvCc) {
+    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
+    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
+        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
+    if (h->qNProc > 0 && !recvCc) return fail(std::string(api) + ": null recvCc");
+    return 0;
+}
+
+int smgpu_quality_coupled_pack_volumes(smgpu_handle* h, void* sendVc, int64_t* nProcFaces) {
+    if (!h) return fail("null argument");
+    const char* api = "smgpu_quality_coupled_pack_volumes";
+    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
+    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
+        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
+    if (h->qNProc > 0 && !sendVc) return fail(std::string(api) + ": null sendVc");
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityGeomEnsure(h)) return 1;
+    if (!h->qgPartOut) HIP_OK(hipMalloc((void**)&h->qgPartOut, sizeof(smgpu_quality_geometry_part)));
+    const MeshView& m = h->mv;
+    const int nCB = qualityGrid(m.nCells);
+    if (nCB > 0)
+        hipLaunchKernelGGL(k_quality_cell_volumes, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, h->st.fCtr, h->st.fArea, h->qgVol);
+    if (h->qNProc > 0)
+        hipLaunchKernelGGL(k_quality_pack_volumes, dim3(gridFor(h->qNProc)), dim3(kQualityBlock), 0, h->stream, h->qOwn, h->qgVol, h->qProcFace,
+                           h->qNProc, (double*)sendVc);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(h->stream));       // sendVc is the host's to move
+    h->qVolEpoch = h->qEpoch;
+    h->qVolCoupling = h->qCoupling;
+    if (nProcFaces) *nProcFaces = h->qNProc;
+    return 0;
+}
+
+// the determinant pass, the face pass with processor faces and the per-rank record into h->qgPartOut, on the geometry of the last
+// pack and the volumes of the last pack_volumes.  o[5] as runQualityGeom.
+static int runQualityGeomCoupled(smgpu_handle* h, const char* api, const smgpu_quality_geometry_params* p, const void* recvCc, const void* recvVc,
+                                 double* const* o) {
+    if (qualityCoupledReady(h, api, recvCc)) return 1;
+    if (!h->qgPartOut || h->qVolEpoch != h->qEpoch || h->qVolCoupling != h->qCoupling)
+        return fail(std::string(api) + ": call smgpu_quality_coupled_pack_volumes after smgpu_quality_coupled_pack first");
+    if (h->qNProc > 0 && !recvVc) return fail(std::string(api) + ": null recvVc");
+    HIP_OK(hipSetDevice(h->device));
+    const MeshView& m = h->mv;
+    const smgpu_quality_geometry_params prm = p ? *p : smgpu_quality_geometry_params{10.0, 0.8, 0.05, 0.01, 0.001};
+    const QualityGeomThresholds thr{std::sin(prm.concaveThreshold * (SMGPU_PI / 180.0)), prm.flatnessThreshold, prm.weightThreshold,
+                                    prm.volRatioThreshold, prm.determinantThreshold};
+    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+    const State& s = h->st;
+    if (nCB > 0)
+        hipLaunchKernelGGL(k_quality_geom_cells_coupled, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fArea, h->qSlot, thr, h->qgCellPart, o[4]);
+    if (nFB > 0)
+        hipLaunchKernelGGL(k_quality_geom_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qgVol,
+                           h->qOwn, h->qNei, h->qSlot, (const double*)recvCc, (const double*)recvVc, thr, h->qgFacePart, o[0], o[1], o[2], o[3]);
+    hipLaunchKernelGGL(k_quality_geom_part_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qgFacePart, nFB, h->qgCellPart, nCB, m.nCells,
+                       m.nFaces - h->qNotCounted, m.nInternalFaces + h->qCountedProc, h->qgPartOut);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_quality_coupled_geometry_report(smgpu_handle* h, const smgpu_quality_geometry_params* p, const void* recvCc, const void* recvVc,
+                                          smgpu_quality_geometry_part* out) {
+    if (!h || !out) return fail("null argument");
+    double* const none[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (runQualityGeomCoupled(h, "smgpu_quality_coupled_geometry_report", p, recvCc, recvVc, none)) return 1;
+    HIP_OK(hipMemcpyAsync(out, h->qgPartOut, sizeof(smgpu_quality_geometry_part), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// one per-element field of the two coupled reports: `run(o)` launches the passes with the outputs o[NF], o[which] a buffer
+// allocated for this call (outside deviceBytes, as qualityField's)
+extern "C++" {
+template <int NF, class Run>
+static int qualityCoupledField(smgpu_handle* h, const char* api, int which, int64_t cnt, double* out, Run run) {
+    HIP_OK(hipSetDevice(h->device));
+    double* buf = nullptr;   // transient: one field's worth for this call only
+    HIP_OK(hipMalloc((void**)&buf, sizeof(double) * (size_t)std::max<int64_t>(1, cnt)));
+    double* o[NF];
+    for (int i = 0; i < NF; ++i) o[i] = nullptr;
+    o[which] = buf;
+    int rc = run(o);
+    if (rc == 0 && cnt > 0) {
+        const hipError_t e = hipMemcpyAsync(out, buf, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream);
+        if (e != hipSuccess) rc = fail(std::string(api) + ": " + hipGetErrorString(e));
+    }
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (rc == 0 && es != hipSuccess) rc = fail(std::string(api) + ": " + hipGetErrorString(es));
+    (void)hipFree(buf);
+    return rc;
+}
+}  // extern "C++"
+
+int smgpu_quality_coupled_geometry_field(smgpu_handle* h, const char* name, const void* recvCc, const void* recvVc, double* out, int64_t* n) {
+    if (!h || !name || !n) return fail("null argument");
+    static const char* const names[5] = {"faceConcavity", "faceFlatness", "faceWeight", "faceVolumeRatio", "cellDeterminant"};
+    int which = -1;
+    for (int i = 0; i < 5; ++i)
+        if (std::strcmp(name, names[i]) == 0) which = i;
+    if (which < 0)
+        return fail(std::string("unknown quality geometry field ") + name + " (faceConcavity, faceFlatness, faceWeight, faceVolumeRatio, cellDeterminant)");
+    const int64_t cnt = which == 4 ? h->mv.nCells : h->mv.nFaces;
+    *n = cnt;
+    if (!out) return 0;
+    const char* api = "smgpu_quality_coupled_geometry_field";
+    return qualityCoupledField<5>(h, api, which, cnt, out, [&](double** o) { return runQualityGeomCoupled(h, api, nullptr, recvCc, recvVc, o); });
+}
+
+// the face pass with processor faces and the per-rank record into h->qmPartOut, on the geometry of the last pack.  o[4] as runQualityMotion.
+static int runQualityMotionCoupled(smgpu_handle* h, const char* api, const smgpu_quality_motion_params* p, const void* recvCc, double* const* o) {
+    if (qualityCoupledReady(h, api, recvCc)) return 1;
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityMotionEnsure(h)) return 1;
+    if (!h->qmPartOut) HIP_OK(hipMalloc((void**)&h->qmPartOut, sizeof(smgpu_quality_motion_part)));
+    const MeshView& m = h->mv;
+    const smgpu_quality_motion_params prm = p ? *p : smgpu_quality_motion_params{1e-15, 0.02, -1.0};
+    const QualityMotionThresholds thr{prm.tetThreshold, prm.twistThreshold, prm.triangleTwistThreshold, 8.0 / (9.0 * std::sqrt(3.0))};
+    const int nFB = qualityGrid(m.nFaces);
+    const State& s = h->st;
+    if (nFB > 0)
+        hipLaunchKernelGGL(k_quality_motion_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.cellCtr, h->qOwn,
+                           h->qNei, h->qSlot, (const double*)recvCc, thr, h->qmFacePart, o[0], o[1], o[2], o[3]);
+    hipLaunchKernelGGL(k_quality_motion_part_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qmFacePart, nFB, m.nFaces - h->qNotCounted,
+                       h->qmPartOut);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_quality_coupled_motion_report(smgpu_handle* h, const smgpu_quality_motion_params* p, const void* recvCc, smgpu_quality_motion_part* out) {
+    if (!h || !out) return fail("null argument");
+    double* const none[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (runQualityMotionCoupled(h, "smgpu_quality_coupled_motion_report", p, recvCc, none)) return 1;
+    HIP_OK(hipMemcpyAsync(out, h->qmPartOut, sizeof(smgpu_quality_motion_part), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int smgpu_quality_coupled_motion_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n) {
+    if (!h || !name || !n) return fail("null argument");
+    static const char* const names[4] = {"faceTetQuality", "faceBaseTetQuality", "faceTwist", "faceTriangleTwist"};
+    int which = -1;
+    for (int i = 0; i < 4; ++i)
+        if (std::strcmp(name, names[i]) == 0) which = i;
+    if (which < 0)
+        return fail(std::string("unknown quality motion field ") + name + " (faceTetQuality, faceBaseTetQuality, faceTwist, faceTriangleTwist)");
+    const int64_t cnt = h->mv.nFaces;
+    *n = cnt;
+    if (!out) return 0;
+    const char* api = "smgpu_quality_coupled_motion_field";
+    return qualityCoupledField<4>(h, api, which, cnt, out, [&](double** o) { return runQualityMotionCoupled(h, api, nullptr, recvCc, o); });
 }
 
 // ---- the failing elements as sets (DESIGN.md "Mesh quality", 10.5) --------------------------------------------------------

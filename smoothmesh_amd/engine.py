@@ -605,6 +605,50 @@ class SmoothEngine:
         self._check(self._lib.smgpu_quality_coupled_field(self._h, name.encode(), C.c_void_p(recvCc or None), _p(out, _ffi.c_f64p), C.byref(n)))
         return out
 
+    # -- the -allGeometry checks and the motion criteria of a sub-domain (DESIGN.md "Mesh quality", 10.8) --------------------
+    def quality_coupled_pack_volumes(self, sendVc) -> int:
+        """smgpu_quality_coupled_pack_volumes, after quality_coupled_pack on the same points: every cell's signed volume into the
+        engine's scratch and the owner cell's volume of every processor face (the slot order of sendCc) into the device buffer at
+        address sendVc (1 double per face; 0 when there are none).  Returns the number of processor faces."""
+        n = C.c_int64()
+        self._check(self._lib.smgpu_quality_coupled_pack_volumes(self._h, C.c_void_p(sendVc or None), C.byref(n)))
+        return n.value
+
+    def quality_coupled_geometry_report(self, recvCc, recvVc, concaveThreshold=10.0, flatnessThreshold=0.8, weightThreshold=0.05,
+                                        volRatioThreshold=0.01, determinantThreshold=0.001) -> dict:
+        """smgpu_quality_coupled_geometry_report: this rank's record (smgpu_quality_geometry_part field names, local ids), the
+        neighbours' cell centres and volumes at the device addresses recvCc and recvVc"""
+        p = _ffi.QualityGeometryParams(concaveThreshold, flatnessThreshold, weightThreshold, volRatioThreshold, determinantThreshold)
+        q = _ffi.QualityGeometryPart()
+        self._check(self._lib.smgpu_quality_coupled_geometry_report(self._h, C.byref(p), C.c_void_p(recvCc or None),
+                                                                    C.c_void_p(recvVc or None), C.byref(q)))
+        return {n: getattr(q, n) for n, _ in q._fields_}
+
+    def quality_coupled_geometry_field(self, name, recvCc, recvVc) -> np.ndarray:
+        """smgpu_quality_coupled_geometry_field: as quality_geometry_field, processor faces with the internal-face definitions"""
+        n = C.c_int64()
+        a = (self._h, name.encode(), C.c_void_p(recvCc or None), C.c_void_p(recvVc or None))
+        self._check(self._lib.smgpu_quality_coupled_geometry_field(*a, None, C.byref(n)))
+        out = np.empty(n.value, np.float64)
+        self._check(self._lib.smgpu_quality_coupled_geometry_field(*a, _p(out, _ffi.c_f64p), C.byref(n)))
+        return out
+
+    def quality_coupled_motion_report(self, recvCc, tetThreshold=1e-15, twistThreshold=0.02, triangleTwistThreshold=-1.0) -> dict:
+        """smgpu_quality_coupled_motion_report: this rank's record (smgpu_quality_motion_part field names, local ids)"""
+        p = _ffi.QualityMotionParams(tetThreshold, twistThreshold, triangleTwistThreshold)
+        q = _ffi.QualityMotionPart()
+        self._check(self._lib.smgpu_quality_coupled_motion_report(self._h, C.byref(p), C.c_void_p(recvCc or None), C.byref(q)))
+        return {n: getattr(q, n) for n, _ in q._fields_}
+
+    def quality_coupled_motion_field(self, name, recvCc) -> np.ndarray:
+        """smgpu_quality_coupled_motion_field: as quality_motion_field, processor faces with the internal-face definitions"""
+        n = C.c_int64()
+        a = (self._h, name.encode(), C.c_void_p(recvCc or None))
+        self._check(self._lib.smgpu_quality_coupled_motion_field(*a, None, C.byref(n)))
+        out = np.empty(n.value, np.float64)
+        self._check(self._lib.smgpu_quality_coupled_motion_field(*a, _p(out, _ffi.c_f64p), C.byref(n)))
+        return out
+
     # -- timing --------------------------------------------------------------------------------
     def enable_timing(self, on=True):
         self._check(self._lib.smgpu_enable_timing(self._h, int(on)))

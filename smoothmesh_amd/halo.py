@@ -709,22 +709,38 @@ class DistributedSmoother:
     def get_points(self):
         return self.engine.get_points()
 
-    def _quality_exchange(self):
+    def _quality_exchange(self, volumes=False):
         """pack, then every processor patch's owner cell centres to the neighbour and theirs back (one all_to_all_single, staged
-        through the host for gloo like _a2a) -> recvCc (device tensor, patch order)"""
+        through the host for gloo like _a2a) -> recvCc (device tensor, patch order).  volumes: also pack_volumes, the owner cells'
+        volumes riding a second all_to_all_single of one double per face -> (recvCc, recvVc)"""
         torch = self.torch
         coupling = self.engine.quality_coupling(self.rank)
         pats = coupling[1]
         n = sum(p[1] for p in pats)
         send = torch.empty((max(n, 1), 3), dtype=torch.float64, device=self.device)
         self.engine.quality_coupled_pack(coupling, send.data_ptr() if n else 0)
+        if self.world <= 1 and pats:
+            raise RuntimeError("mesh quality: a single rank with processor patches")
+        recv = self._quality_swap(pats, send, 3)
+        if not volumes:
+            torch.cuda.synchronize(self.device)
+            return recv
+        sendV = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)
+        self.engine.quality_coupled_pack_volumes(sendV.data_ptr() if n else 0)
+        recvV = self._quality_swap(pats, sendV, 1)
+        torch.cuda.synchronize(self.device)
+        return recv, recvV
+
+    def _quality_swap(self, pats, send, width):
+        """the paired-patch exchange of one packed buffer, `width` doubles per processor face"""
+        torch = self.torch
         recv = torch.empty_like(send)
         if self.world > 1:
             offs = np.concatenate([[0], np.cumsum([p[1] for p in pats])]).astype(np.int64)
             order = sorted(range(len(pats)), key=lambda i: pats[i][2])       # the collective's blocks go by ascending rank
             counts = [0] * self.world
             for i in order:
-                counts[pats[i][2]] = 3 * pats[i][1]
+                counts[pats[i][2]] = width * pats[i][1]
             flat = lambda t: t.reshape(-1)  # noqa: E731
             sbuf = torch.cat([flat(send[offs[i]:offs[i + 1]]) for i in order]) if pats else send.new_empty(0)
             if self._staged():
@@ -736,12 +752,9 @@ class DistributedSmoother:
                 self.dist.all_to_all_single(rbuf, sbuf, counts, counts)
             pos = 0
             for i in order:
-                m = 3 * pats[i][1]
-                flat(recv)[3 * offs[i]:3 * offs[i] + m].copy_(rbuf[pos:pos + m])
+                m = width * pats[i][1]
+                flat(recv)[width * offs[i]:width * offs[i] + m].copy_(rbuf[pos:pos + m])
                 pos += m
-        elif pats:
-            raise RuntimeError("mesh quality: a single rank with processor patches")
-        torch.cuda.synchronize(self.device)
         return recv
 
     def mesh_quality(self, **thresholds):
@@ -774,6 +787,45 @@ class DistributedSmoother:
         from .quality import QUALITY_DEFAULTS
         recv = self._quality_exchange()
         return self.engine.quality_coupled_sets(recv.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds})
+
+    def _gather_parts(self, part, cellKeys, faceKeys):
+        """all-gather of this rank's record with only its winning ids mapped to global ones -> (parts, cellIds, faceIds) for a combine"""
+        cp, fp = self.sub.cellProcAddressing, self.sub.faceProcAddressing
+        cmap = None if cp is None else {part[k]: int(cp[part[k]]) for k in cellKeys if part[k] >= 0}
+        fmap = None if fp is None else {part[k]: int(fp[part[k]]) for k in faceKeys if part[k] >= 0}
+        allv = [None] * self.world
+        self.dist.all_gather_object(allv, (part, cmap, fmap))
+        return [a[0] for a in allv], [a[1] for a in allv], [a[2] for a in allv]
+
+    def mesh_quality_geometry(self, **thresholds):
+        """The -allGeometry report of the whole decomposed mesh at the current points, identical on every rank: the
+        exchange of mesh_quality plus the owner cells' volumes, this rank's record, an all-gather and combine_quality_geometry.
+        A collective: every rank calls it, between iterations."""
+        from .quality import GEOMETRY_DEFAULTS, combine_quality_geometry
+        recv, recvV = self._quality_exchange(volumes=True)
+        part = self.engine.quality_coupled_geometry_report(recv.data_ptr(), recvV.data_ptr(), **{**GEOMETRY_DEFAULTS, **thresholds})
+        return combine_quality_geometry(*self._gather_parts(part, ("minDeterminantCell",), (
+            "maxConcaveFace", "minFlatnessFace", "minFaceWeightFace", "minVolRatioFace")))
+
+    def quality_geometry_field(self, name):
+        """this rank's per-element field (engine.QUALITY_GEOMETRY_FIELDS); processor faces carry their values on both sides.
+        A collective (the exchange of mesh_quality_geometry)."""
+        recv, recvV = self._quality_exchange(volumes=True)
+        return self.engine.quality_coupled_geometry_field(name, recv.data_ptr(), recvV.data_ptr())
+
+    def mesh_quality_motion(self, **thresholds):
+        """The motion criteria of the whole decomposed mesh at the current points, identical on every rank.
+        A collective: every rank calls it, between iterations."""
+        from .quality import MOTION_DEFAULTS, combine_quality_motion
+        recv = self._quality_exchange()
+        part = self.engine.quality_coupled_motion_report(recv.data_ptr(), **{**MOTION_DEFAULTS, **thresholds})
+        return combine_quality_motion(*self._gather_parts(part, (), ("minTetFace", "minBaseTetFace", "minTwistFace", "minTriangleTwistFace")))
+
+    def quality_motion_field(self, name):
+        """this rank's per-face field (engine.QUALITY_MOTION_FIELDS); processor faces carry their values on both sides.
+        A collective (the exchange of mesh_quality)."""
+        recv = self._quality_exchange()
+        return self.engine.quality_coupled_motion_field(name, recv.data_ptr())
 
 
 class LocalMultiSmoother:
@@ -905,3 +957,23 @@ class LocalMultiSmoother:
         rank.  Between iterations only; the loop is left as it was."""
         from .quality import local_quality_sets
         return local_quality_sets([st.eng for st in self.states], self.device, thresholds)
+
+    def mesh_quality_geometry(self, **thresholds):
+        """The -allGeometry report of the decomposed mesh at the current points (smoothmesh_amd/quality.py)"""
+        from .quality import local_quality_geometry
+        return local_quality_geometry([st.eng for st in self.states], self.subs, self.device, thresholds)
+
+    def quality_geometry_field(self, name):
+        """[per-rank array] of a field of engine.QUALITY_GEOMETRY_FIELDS; processor faces carry their values on both sides"""
+        from .quality import local_quality_geometry_field
+        return local_quality_geometry_field([st.eng for st in self.states], name, self.device)
+
+    def mesh_quality_motion(self, **thresholds):
+        """The motion criteria of the decomposed mesh at the current points (smoothmesh_amd/quality.py)"""
+        from .quality import local_quality_motion
+        return local_quality_motion([st.eng for st in self.states], self.subs, self.device, thresholds)
+
+    def quality_motion_field(self, name):
+        """[per-rank array] of a field of engine.QUALITY_MOTION_FIELDS; processor faces carry their values on both sides"""
+        from .quality import local_quality_motion_field
+        return local_quality_motion_field([st.eng for st in self.states], name, self.device)
