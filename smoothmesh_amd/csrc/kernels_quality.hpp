@@ -5,8 +5,10 @@
 // kernel publishes them for ptsCur (runGeometry with writeFaces).  Definitions: DESIGN.md "Mesh quality" (after OpenFOAM
 // primitiveMeshCheck).  Three passes, no float atomics: a face pass (one lane per face, polyMesh order) and a cell pass (one lane
 // per cell) leave one partial record per workgroup; k_quality_final reduces the two slabs in a fixed order into one
-// smgpu_quality.  Every reduction is a fixed xor butterfly inside the wave, the waves of a workgroup in wave order, and the
-// workgroup records in a fixed stride order: the report is bitwise repeatable.
+// smgpu_quality (or, for a sub-domain, one smgpu_quality_part).  The face pass and the face flag pass are one kernel template
+// each: the serial and the coupled report are its Coupled = false / true instantiations, and differ in what qNeighbour returns.
+// Every reduction is a fixed xor butterfly inside the wave, the waves of a workgroup in wave order, and the workgroup records in
+// a fixed stride order: the report is bitwise repeatable.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,14 +36,15 @@ struct QCell {
     long long nNonPos, nOpen, nHigh;
 };
 
-__device__ __forceinline__ QFace qFaceEmpty() {
+template <class A> __device__ __forceinline__ A qEmpty();
+template <> __device__ __forceinline__ QFace qEmpty<QFace>() {
     QFace a;
     a.maxNO = -__builtin_inf(); a.sumTh = 0.0; a.maxSk = -__builtin_inf(); a.minA = __builtin_inf(); a.maxA = -__builtin_inf();
     a.maxNOId = kQualityNoId; a.maxSkId = kQualityNoId;
     a.nSev = a.nErr = a.nSkew = a.nWrong = a.nZero = 0;
     return a;
 }
-__device__ __forceinline__ QCell qCellEmpty() {
+template <> __device__ __forceinline__ QCell qEmpty<QCell>() {
     QCell a;
     a.minV = __builtin_inf(); a.maxV = -__builtin_inf(); a.sumV = 0.0; a.maxOpen = -__builtin_inf(); a.maxAR = -__builtin_inf();
     a.minVId = kQualityNoId;
@@ -104,6 +107,46 @@ __device__ __forceinline__ A qBlockReduce(A v, A* sh /* [kQualityBlock / 64] in 
     return v;
 }
 
+// Each workgroup takes kQualityPer * kQualityBlock consecutive elements, lane t the elements t, t + 256, ... (coalesced), so that
+// the final reduction folds kQualityPer times fewer records (one workgroup folding one record per 256 elements took 0.7 ms on the
+// 10 M-cell mesh: profiles/quality/README.md)
+constexpr int kQualityPer = 8;
+__host__ __device__ constexpr int qualityGrid(int n) { return (int)(((long long)n + kQualityPer * kQualityBlock - 1) / (kQualityPer * kQualityBlock)); }
+
+// the workgroup's elements of [0, n) in lane order: each(i)
+template <class Each>
+__device__ __forceinline__ void qEach(int n, Each each) {
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int i = base + k * kQualityBlock;
+        if (i >= n) break;
+        each(i);
+    }
+}
+// a reducing pass: one(i, e) fills the record e of element i; the lane folds its elements in order, the workgroup reduces, and
+// part[blockIdx.x] takes the workgroup's record
+template <class A, class One>
+__device__ __forceinline__ void qPass(int n, A* __restrict__ part, One one) {
+    __shared__ A sh[kQualityBlock / 64];
+    A a = qEmpty<A>();
+    qEach(n, [&](int i) {
+        A e = qEmpty<A>();
+        one(i, e);
+        qCombine(a, e);
+    });
+    a = qBlockReduce(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+// the final reduction's fold of one slab: thread t folds the records t, t + 256, ... in that order, then the workgroup reduction
+// (valid in thread 0)
+template <class A>
+__device__ __forceinline__ A qFold(const A* __restrict__ part, int nB) {
+    __shared__ A sh[kQualityBlock / 64];
+    A a = qEmpty<A>();
+    for (int i = threadIdx.x; i < nB; i += kQualityBlock) qCombine(a, part[i]);
+    return qBlockReduce(a, sh);
+}
+
 // owner / neighbour of every face from the cell -> face rows (bit 31 = the cell is the face's neighbour): the addressing the
 // engine holds on the device, so the first report uploads nothing.  Each face has one owner and at most one neighbour: plain
 // stores, no race.
@@ -122,16 +165,40 @@ struct QualityThresholds { double cosNonOrth, skew, closed, aspect; };
 
 constexpr double kRadToDeg = 180.0 / SMGPU_PI;
 
+// ---- the neighbour side of a face ------------------------------------------------------------------------------------------
+// A processor face of a decomposed mesh (smgpu_quality_coupled_*, DESIGN.md "Mesh quality", 10.4 and 10.8) is an internal face
+// of the global mesh: it takes the internal-face branch of every criterion with the neighbour rank's cell centre and volume,
+// which the host has moved into recvCc / recvVc.  slot[f - nInternalFaces] is the array smgpu_quality_coupled_pack builds: -1 on
+// a physical boundary face, else the face's place in recvCc / recvVc (patch order), | kQualityNotCounted on the side with
+// myRank > neighbRank: the record counts the face on the other side only, the per-face fields carry it on both.  The kernels of
+// this file read it here only; the coupled geometry and motion kernels decode it themselves.
+constexpr int kQualitySlotMask = 0x3fffffff;
+constexpr int kQualityNotCounted = 0x40000000;
+template <bool Coupled> struct QCoupling {};                   // the serial kernels carry no coupling
+template <> struct QCoupling<true> { const int* __restrict__ slot; const double* __restrict__ recvCc; const double* __restrict__ recvVc; };
+
+// cc: where the neighbour's cell centre is, valid where `internal`
+struct QNeighbour { bool internal, counted; const double* cc; };
+template <bool Coupled>
+__device__ __forceinline__ QNeighbour qNeighbour(const MeshView& m, const double* __restrict__ cellCtr, const int* __restrict__ nei, const QCoupling<Coupled>& cp, int f) {
+    if (f < m.nInternalFaces) {
+        const int n = nei[f];
+        return QNeighbour{true, true, cellCtr + 3 * (size_t)n};
+    }
+    if constexpr (Coupled) {
+        const int sl = cp.slot[f - m.nInternalFaces];
+        if (sl >= 0) {
+            const int k = sl & kQualitySlotMask;
+            return QNeighbour{true, !(sl & kQualityNotCounted), cp.recvCc + 3 * (size_t)k};
+        }
+    }
+    return QNeighbour{false, true, nullptr};
+}
+__device__ __forceinline__ V3 qNeighbourCentre(const QNeighbour& nb) { return nb.internal ? v3(nb.cc[0], nb.cc[1], nb.cc[2]) : v3(0, 0, 0); }
+
 // face pass: non-orthogonality (internal faces), skewness, both face pyramids, face area of face f.  outNO / outSkew: optional
 // per-face fields (smgpu_quality_field), NULL for the report.
-// Each workgroup takes kQualityPer * kQualityBlock consecutive elements, lane t the elements t, t + 256, ... (coalesced), so that
-// the final reduction folds kQualityPer times fewer records (one workgroup folding one record per 256 elements took 0.7 ms on the
-// 10 M-cell mesh: profiles/quality/README.md)
-constexpr int kQualityPer = 8;
-__host__ __device__ constexpr int qualityGrid(int n) { return (int)(((long long)n + kQualityPer * kQualityBlock - 1) / (kQualityPer * kQualityBlock)); }
-
-// one face with owner centre CO and, where `internal`, neighbour centre CN (the internal-face definitions; a processor face of a
-// decomposed mesh takes them with CN from the neighbour rank: k_quality_faces_coupled)
+// one face with owner centre CO and, where `internal`, neighbour centre CN
 __device__ __forceinline__ void qFaceCore(const MeshView& m, const double* __restrict__ pts, const V3 Cf, const V3 Sf, const V3 CO, bool internal,
                                           const V3 CN, const QualityThresholds& thr, int f, QFace& a, double* __restrict__ outNO,
                                           double* __restrict__ outSkew) {
@@ -171,53 +238,56 @@ __device__ __forceinline__ void qFaceCore(const MeshView& m, const double* __res
     if (outNO) outNO[f] = theta;
     if (outSkew) outSkew[f] = skew;
 }
+template <bool Coupled>
 __device__ __forceinline__ void qFaceOne(const MeshView& m, const double* __restrict__ pts, const double* __restrict__ fCtr, const double* __restrict__ fArea,
                                          const double* __restrict__ cellCtr, const int* __restrict__ own, const int* __restrict__ nei,
-                                         const QualityThresholds& thr, int f, QFace& a, double* __restrict__ outNO, double* __restrict__ outSkew) {
-    const bool internal = f < m.nInternalFaces;
-    const V3 CN = internal ? ldv(cellCtr, nei[f]) : v3(0, 0, 0);
-    qFaceCore(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, own[f]), internal, CN, thr, f, a, outNO, outSkew);
+                                         const QCoupling<Coupled>& cp, const QualityThresholds& thr, int f, QFace& a, double* __restrict__ outNO,
+                                         double* __restrict__ outSkew) {
+    const QNeighbour nb = qNeighbour(m, cellCtr, nei, cp, f);
+    qFaceCore(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, own[f]), nb.internal, qNeighbourCentre(nb), thr, f, a, outNO, outSkew);
+    if (!nb.counted) a = qEmpty<QFace>();
 }
+template <bool Coupled>
 __global__ void __launch_bounds__(kQualityBlock) k_quality_faces(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
                                                                   const double* __restrict__ fArea, const double* __restrict__ cellCtr,
-                                                                  const int* __restrict__ own, const int* __restrict__ nei, QualityThresholds thr,
-                                                                  QFace* __restrict__ part, double* __restrict__ outNO, double* __restrict__ outSkew) {
-    __shared__ QFace sh[kQualityBlock / 64];
-    QFace a = qFaceEmpty();
-    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
-    for (int k = 0; k < kQualityPer; ++k) {
-        const int f = base + k * kQualityBlock;
-        if (f >= m.nFaces) break;
-        QFace e = qFaceEmpty();
-        qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, thr, f, e, outNO, outSkew);
-        qCombine(a, e);
-    }
-    a = qBlockReduce(a, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = a;
+                                                                  const int* __restrict__ own, const int* __restrict__ nei, QCoupling<Coupled> cp,
+                                                                  QualityThresholds thr, QFace* __restrict__ part, double* __restrict__ outNO,
+                                                                  double* __restrict__ outSkew) {
+    qPass(m.nFaces, part, [&](int f, QFace& e) { qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, cp, thr, f, e, outNO, outSkew); });
 }
 
-// cell pass: signed volume, openness, aspect ratio of cell c.  Faces in the cell's geometry order (cfOff / cfVal), sign -1 on the
-// neighbour side.  outV / outOpen / outAR: optional per-cell fields, NULL for the report.
+// the signed volume of cell c: the estimated centre (mean of the face centres), then a third of the signed face pyramids, faces in
+// the cell's geometry order (cfOff / cfVal), sign -1 on the neighbour side.  extra(flipped, f, Sf): the caller's own sums over
+// the same faces, each its own chain
+template <class Extra>
+__device__ __forceinline__ double qCellVolume(const MeshView& m, const double* __restrict__ fCtr, const double* __restrict__ fArea, int c, Extra extra) {
+    const int b = m.cfOff[c], e = m.cfOff[c + 1];
+    V3 cEst = v3(0, 0, 0);
+    for (int j = b; j < e; ++j) cEst = cEst + ldv(fCtr, m.cfVal[j] & 0x7fffffff);
+    cEst = cEst / (double)(e - b);
+    double pyr = 0.0;
+    for (int j = b; j < e; ++j) {
+        const int ev = m.cfVal[j];
+        const int f = ev & 0x7fffffff;
+        const V3 Sf = ldv(fArea, f);
+        double p = dot(Sf, ldv(fCtr, f) - cEst);
+        if (ev < 0) p = -p;
+        extra(ev < 0, f, Sf);
+        pyr += p;
+    }
+    return (1.0 / 3.0) * pyr;
+}
+
+// cell pass: signed volume, openness, aspect ratio of cell c.  outV / outOpen / outAR: optional per-cell fields, NULL for the report.
 __device__ __forceinline__ void qCellOne(const MeshView& m, const double* __restrict__ fCtr, const double* __restrict__ fArea, const QualityThresholds& thr,
                                          int c, QCell& a, double* __restrict__ outV, double* __restrict__ outOpen, double* __restrict__ outAR) {
     {
-        const int b = m.cfOff[c], e = m.cfOff[c + 1];
-        V3 cEst = v3(0, 0, 0);
-        for (int j = b; j < e; ++j) cEst = cEst + ldv(fCtr, m.cfVal[j] & 0x7fffffff);
-        cEst = cEst / (double)(e - b);
-        double pyr = 0.0;
         V3 sumS = v3(0, 0, 0), M = v3(0, 0, 0);
-        for (int j = b; j < e; ++j) {
-            const int ev = m.cfVal[j];
-            const int f = ev & 0x7fffffff;
-            const V3 Sf = ldv(fArea, f);
-            double p = dot(Sf, ldv(fCtr, f) - cEst);
-            if (ev < 0) { p = -p; sumS = sumS - Sf; }
+        const double V = qCellVolume(m, fCtr, fArea, c, [&](bool flipped, int, const V3& Sf) {
+            if (flipped) sumS = sumS - Sf;
             else sumS = sumS + Sf;
-            pyr += p;
             M = M + v3(fabs(Sf.x), fabs(Sf.y), fabs(Sf.z));
-        }
-        const double V = (1.0 / 3.0) * pyr;
+        });
         const double open = fmax(fmax(fabs(sumS.x) / (M.x + SMGPU_ROOTVSMALL), fabs(sumS.y) / (M.y + SMGPU_ROOTVSMALL)),
                                  fabs(sumS.z) / (M.z + SMGPU_ROOTVSMALL));
         const double maxM = fmax(fmax(M.x, M.y), M.z), minM = fmin(fmin(M.x, M.y), M.z);
@@ -235,101 +305,32 @@ __device__ __forceinline__ void qCellOne(const MeshView& m, const double* __rest
 __global__ void __launch_bounds__(kQualityBlock) k_quality_cells(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea,
                                                                   QualityThresholds thr, QCell* __restrict__ part, double* __restrict__ outV,
                                                                   double* __restrict__ outOpen, double* __restrict__ outAR) {
-    __shared__ QCell sh[kQualityBlock / 64];
-    QCell a = qCellEmpty();
-    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
-    for (int k = 0; k < kQualityPer; ++k) {
-        const int c = base + k * kQualityBlock;
-        if (c >= m.nCells) break;
-        QCell e = qCellEmpty();
-        qCellOne(m, fCtr, fArea, thr, c, e, outV, outOpen, outAR);
-        qCombine(a, e);
-    }
-    a = qBlockReduce(a, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = a;
+    qPass(m.nCells, part, [&](int c, QCell& e) { qCellOne(m, fCtr, fArea, thr, c, e, outV, outOpen, outAR); });
 }
 
-// one workgroup: thread t folds the records t, t + 256, ... in that order, then the workgroup reduction -> the report
+// the serial report of the folded record: the average in place of the sum
+__device__ __forceinline__ void qFinish(const smgpu_quality_part& q, smgpu_quality_part* __restrict__ out) { *out = q; }
+__device__ __forceinline__ void qFinish(const smgpu_quality_part& q, smgpu_quality* __restrict__ out) {
+    smgpu_quality r;
+    r.nCells = q.nCells; r.nFaces = q.nFaces; r.nInternalFaces = q.nInternalFaces;
+    r.minVolume = q.minVolume; r.maxVolume = q.maxVolume; r.totalVolume = q.totalVolume;
+    r.nNonPositiveVolume = q.nNonPositiveVolume; r.minVolumeCell = q.minVolumeCell;
+    r.minFaceArea = q.minFaceArea; r.maxFaceArea = q.maxFaceArea; r.nZeroAreaFaces = q.nZeroAreaFaces;
+    r.maxNonOrth = q.maxNonOrth; r.avgNonOrth = q.nInternalFaces > 0 ? q.sumNonOrth / (double)q.nInternalFaces : 0.0;
+    r.nSevereNonOrth = q.nSevereNonOrth; r.nErrorNonOrth = q.nErrorNonOrth; r.maxNonOrthFace = q.maxNonOrthFace;
+    r.maxSkewness = q.maxSkewness; r.nSkewFaces = q.nSkewFaces; r.maxSkewFace = q.maxSkewFace;
+    r.nWrongOrientedFaces = q.nWrongOrientedFaces;
+    r.maxOpenness = q.maxOpenness; r.nOpenCells = q.nOpenCells;
+    r.maxAspectRatio = q.maxAspectRatio; r.nHighAspectCells = q.nHighAspectCells;
+    *out = r;
+}
+// one workgroup folds the two slabs into the record of sums and denominators.  Out = smgpu_quality_part: the per-rank record of a
+// decomposed mesh (nFaces / nInternalFaces are the counted ones); Out = smgpu_quality: the serial report
+template <class Out>
 __global__ void __launch_bounds__(kQualityBlock) k_quality_final(const QFace* __restrict__ fPart, int nFB, const QCell* __restrict__ cPart, int nCB,
-                                                                  int nCells, int nFaces, int nInternalFaces, smgpu_quality* __restrict__ out) {
-    __shared__ QFace shF[kQualityBlock / 64];
-    __shared__ QCell shC[kQualityBlock / 64];
-    QFace a = qFaceEmpty();
-    for (int i = threadIdx.x; i < nFB; i += kQualityBlock) qCombine(a, fPart[i]);
-    QCell b = qCellEmpty();
-    for (int i = threadIdx.x; i < nCB; i += kQualityBlock) qCombine(b, cPart[i]);
-    a = qBlockReduce(a, shF);
-    b = qBlockReduce(b, shC);
-    if (threadIdx.x != 0) return;
-    smgpu_quality q;
-    q.nCells = nCells; q.nFaces = nFaces; q.nInternalFaces = nInternalFaces;
-    const bool anyCell = nCells > 0, anyFace = nFaces > 0, anyInternal = nInternalFaces > 0;
-    q.minVolume = anyCell ? b.minV : 0.0; q.maxVolume = anyCell ? b.maxV : 0.0; q.totalVolume = b.sumV;
-    q.nNonPositiveVolume = b.nNonPos; q.minVolumeCell = anyCell ? b.minVId : -1;
-    q.minFaceArea = anyFace ? a.minA : 0.0; q.maxFaceArea = anyFace ? a.maxA : 0.0; q.nZeroAreaFaces = a.nZero;
-    q.maxNonOrth = anyInternal ? a.maxNO : 0.0; q.avgNonOrth = anyInternal ? a.sumTh / (double)nInternalFaces : 0.0;
-    q.nSevereNonOrth = a.nSev; q.nErrorNonOrth = a.nErr; q.maxNonOrthFace = anyInternal ? a.maxNOId : -1;
-    q.maxSkewness = anyFace ? a.maxSk : 0.0; q.nSkewFaces = a.nSkew; q.maxSkewFace = anyFace ? a.maxSkId : -1;
-    q.nWrongOrientedFaces = a.nWrong;
-    q.maxOpenness = anyCell ? b.maxOpen : 0.0; q.nOpenCells = b.nOpen;
-    q.maxAspectRatio = anyCell ? b.maxAR : 0.0; q.nHighAspectCells = b.nHigh;
-    *out = q;
-}
-
-// ---- decomposed meshes (smgpu_quality_coupled_*, DESIGN.md "Mesh quality", 10.4) ----------------------------------------------
-// A processor face is an internal face of the global mesh: it takes the internal-face definitions with C_N = the neighbour rank's
-// cell centre, which the host has moved into recvCc (slot = the face's place in the processor patches, patch order).  It is
-// counted in the record only on the side with myRank < neighbRank; its per-face fields are written on both sides.
-constexpr int kQualitySlotMask = 0x3fffffff;
-constexpr int kQualityNotCounted = 0x40000000;   // slot flag: the neighbour rank counts this face
-
-// the owner cell centre of every processor face, in patch order: what the neighbour rank needs as its C_N
-__global__ void __launch_bounds__(kQualityBlock) k_quality_pack(const int* __restrict__ own, const double* __restrict__ cellCtr,
-                                                                 const int* __restrict__ procFace, int nProc, double* __restrict__ sendCc) {
-    const int i = blockIdx.x * kQualityBlock + threadIdx.x;
-    if (i >= nProc) return;
-    const V3 c = ldv(cellCtr, own[procFace[i]]);
-    sendCc[3 * (size_t)i] = c.x; sendCc[3 * (size_t)i + 1] = c.y; sendCc[3 * (size_t)i + 2] = c.z;
-}
-
-// k_quality_faces with processor faces: slot[f - nInternalFaces] is -1 on a physical boundary face, else the face's slot in recvCc
-// (| kQualityNotCounted on the side that does not count it)
-__global__ void __launch_bounds__(kQualityBlock) k_quality_faces_coupled(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
-                                                                          const double* __restrict__ fArea, const double* __restrict__ cellCtr,
-                                                                          const int* __restrict__ own, const int* __restrict__ nei,
-                                                                          const int* __restrict__ slot, const double* __restrict__ recvCc,
-                                                                          QualityThresholds thr, QFace* __restrict__ part, double* __restrict__ outNO,
-                                                                          double* __restrict__ outSkew) {
-    __shared__ QFace sh[kQualityBlock / 64];
-    QFace a = qFaceEmpty();
-    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
-    for (int k = 0; k < kQualityPer; ++k) {
-        const int f = base + k * kQualityBlock;
-        if (f >= m.nFaces) break;
-        QFace e = qFaceEmpty();
-        const int sl = f < m.nInternalFaces ? -1 : slot[f - m.nInternalFaces];
-        if (sl < 0) qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, thr, f, e, outNO, outSkew);
-        else {
-            qFaceCore(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, own[f]), true, ldv(recvCc, sl & kQualitySlotMask), thr, f, e, outNO, outSkew);
-            if (sl & kQualityNotCounted) e = qFaceEmpty();
-        }
-        qCombine(a, e);
-    }
-    a = qBlockReduce(a, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = a;
-}
-
-// k_quality_final for the per-rank record of a decomposed mesh: Σθ instead of the average; nFaces / nInternalFaces are the counted ones
-__global__ void __launch_bounds__(kQualityBlock) k_quality_part_final(const QFace* __restrict__ fPart, int nFB, const QCell* __restrict__ cPart, int nCB,
-                                                                       int nCells, int nFaces, int nInternalFaces, smgpu_quality_part* __restrict__ out) {
-    __shared__ QFace shF[kQualityBlock / 64];
-    __shared__ QCell shC[kQualityBlock / 64];
-    QFace a = qFaceEmpty();
-    for (int i = threadIdx.x; i < nFB; i += kQualityBlock) qCombine(a, fPart[i]);
-    QCell b = qCellEmpty();
-    for (int i = threadIdx.x; i < nCB; i += kQualityBlock) qCombine(b, cPart[i]);
-    a = qBlockReduce(a, shF);
-    b = qBlockReduce(b, shC);
+                                                                  int nCells, int nFaces, int nInternalFaces, Out* __restrict__ out) {
+    const QFace a = qFold(fPart, nFB);
+    const QCell b = qFold(cPart, nCB);
     if (threadIdx.x != 0) return;
     smgpu_quality_part q;
     q.nCells = nCells; q.nFaces = nFaces; q.nInternalFaces = nInternalFaces;
@@ -343,12 +344,21 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_part_final(const QFac
     q.nWrongOrientedFaces = a.nWrong;
     q.maxOpenness = anyCell ? b.maxOpen : 0.0; q.nOpenCells = b.nOpen;
     q.maxAspectRatio = anyCell ? b.maxAR : 0.0; q.nHighAspectCells = b.nHigh;
-    *out = q;
+    qFinish(q, out);
+}
+
+// the owner cell centre of every processor face, in patch order: what the neighbour rank needs as its C_N
+__global__ void __launch_bounds__(kQualityBlock) k_quality_pack(const int* __restrict__ own, const double* __restrict__ cellCtr,
+                                                                 const int* __restrict__ procFace, int nProc, double* __restrict__ sendCc) {
+    const int i = blockIdx.x * kQualityBlock + threadIdx.x;
+    if (i >= nProc) return;
+    const V3 c = ldv(cellCtr, own[procFace[i]]);
+    sendCc[3 * (size_t)i] = c.x; sendCc[3 * (size_t)i + 1] = c.y; sendCc[3 * (size_t)i + 2] = c.z;
 }
 
 // ---- the failing elements as sets (smgpu_quality_sets / _coupled_sets, DESIGN.md "Mesh quality", 10.5) ------------------------
 // Three steps, no atomics:
-//   1. flag passes (the report's face / cell passes with the same qFaceOne / qFaceCore / qCellOne records): one mask byte per
+//   1. flag passes (the report's face / cell passes with the same qFaceOne / qCellOne records): one mask byte per
 //      element (bit s = member of set s of its kind), and per workgroup the member count of every set: cnt[row(s) + block];
 //   2. k_quality_set_scan: one exclusive scan of cnt in its flat order.  Rows go set by set (the 4 face sets over the face
 //      workgroups, then the 3 cell sets over the cell workgroups), so the scan is at once each workgroup's offset inside its
@@ -379,75 +389,43 @@ __device__ __forceinline__ void qSetCountStore(const int (&waveCnt)[NS], int* __
     }
 }
 
+// a flag pass: bitsOf(i) gives the mask byte of element i (a face the neighbour rank counts is in no set here).  Not qEach: a
+// lane past the end must not leave the loop, every lane of the wave has to reach the ballots of every round
+template <int NS, class Bits>
+__device__ __forceinline__ void qFlagPass(int n, uint8_t* __restrict__ mask, int* __restrict__ cnt, Bits bitsOf) {
+    __shared__ int sh[NS * (kQualityBlock / 64)];
+    int wc[NS] = {};
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int i = base + k * kQualityBlock;
+        unsigned bits = 0;
+        if (i < n) {
+            bits = bitsOf(i);
+            mask[i] = (uint8_t)bits;
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) wc[s] += __popcll(__ballot((bits >> s) & 1u));
+    }
+    qSetCountStore(wc, sh, cnt, gridDim.x);
+}
+template <bool Coupled>
 __global__ void __launch_bounds__(kQualityBlock) k_quality_face_flags(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
                                                                        const double* __restrict__ fArea, const double* __restrict__ cellCtr,
-                                                                       const int* __restrict__ own, const int* __restrict__ nei, QualityThresholds thr,
-                                                                       uint8_t* __restrict__ mask, int* __restrict__ cnt) {
-    __shared__ int sh[kQualityFaceSets * (kQualityBlock / 64)];
-    int wc[kQualityFaceSets] = {0, 0, 0, 0};
-    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
-    for (int k = 0; k < kQualityPer; ++k) {
-        const int f = base + k * kQualityBlock;
-        unsigned bits = 0;
-        if (f < m.nFaces) {
-            QFace e = qFaceEmpty();
-            qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, thr, f, e, nullptr, nullptr);
-            bits = qFaceBits(e);
-            mask[f] = (uint8_t)bits;
-        }
-#pragma unroll
-        for (int s = 0; s < kQualityFaceSets; ++s) wc[s] += __popcll(__ballot((bits >> s) & 1u));
-    }
-    qSetCountStore(wc, sh, cnt, gridDim.x);
+                                                                       const int* __restrict__ own, const int* __restrict__ nei, QCoupling<Coupled> cp,
+                                                                       QualityThresholds thr, uint8_t* __restrict__ mask, int* __restrict__ cnt) {
+    qFlagPass<kQualityFaceSets>(m.nFaces, mask, cnt, [&](int f) {
+        QFace e = qEmpty<QFace>();
+        qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, cp, thr, f, e, nullptr, nullptr);
+        return qFaceBits(e);
+    });
 }
-
-// k_quality_face_flags with processor faces, as k_quality_faces_coupled: a face the neighbour rank counts is in no set here
-__global__ void __launch_bounds__(kQualityBlock) k_quality_face_flags_coupled(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
-                                                                               const double* __restrict__ fArea, const double* __restrict__ cellCtr,
-                                                                               const int* __restrict__ own, const int* __restrict__ nei,
-                                                                               const int* __restrict__ slot, const double* __restrict__ recvCc,
-                                                                               QualityThresholds thr, uint8_t* __restrict__ mask, int* __restrict__ cnt) {
-    __shared__ int sh[kQualityFaceSets * (kQualityBlock / 64)];
-    int wc[kQualityFaceSets] = {0, 0, 0, 0};
-    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
-    for (int k = 0; k < kQualityPer; ++k) {
-        const int f = base + k * kQualityBlock;
-        unsigned bits = 0;
-        if (f < m.nFaces) {
-            QFace e = qFaceEmpty();
-            const int sl = f < m.nInternalFaces ? -1 : slot[f - m.nInternalFaces];
-            if (sl < 0) qFaceOne(m, pts, fCtr, fArea, cellCtr, own, nei, thr, f, e, nullptr, nullptr);
-            else {
-                qFaceCore(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, own[f]), true, ldv(recvCc, sl & kQualitySlotMask), thr, f, e, nullptr, nullptr);
-                if (sl & kQualityNotCounted) e = qFaceEmpty();
-            }
-            bits = qFaceBits(e);
-            mask[f] = (uint8_t)bits;
-        }
-#pragma unroll
-        for (int s = 0; s < kQualityFaceSets; ++s) wc[s] += __popcll(__ballot((bits >> s) & 1u));
-    }
-    qSetCountStore(wc, sh, cnt, gridDim.x);
-}
-
 __global__ void __launch_bounds__(kQualityBlock) k_quality_cell_flags(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea,
                                                                        QualityThresholds thr, uint8_t* __restrict__ mask, int* __restrict__ cnt) {
-    __shared__ int sh[kQualityCellSets * (kQualityBlock / 64)];
-    int wc[kQualityCellSets] = {0, 0, 0};
-    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
-    for (int k = 0; k < kQualityPer; ++k) {
-        const int c = base + k * kQualityBlock;
-        unsigned bits = 0;
-        if (c < m.nCells) {
-            QCell e = qCellEmpty();
-            qCellOne(m, fCtr, fArea, thr, c, e, nullptr, nullptr, nullptr);
-            bits = qCellBits(e);
-            mask[c] = (uint8_t)bits;
-        }
-#pragma unroll
-        for (int s = 0; s < kQualityCellSets; ++s) wc[s] += __popcll(__ballot((bits >> s) & 1u));
-    }
-    qSetCountStore(wc, sh, cnt, gridDim.x);
+    qFlagPass<kQualityCellSets>(m.nCells, mask, cnt, [&](int c) {
+        QCell e = qEmpty<QCell>();
+        qCellOne(m, fCtr, fArea, thr, c, e, nullptr, nullptr, nullptr);
+        return qCellBits(e);
+    });
 }
 
 // one workgroup of 1024: exclusive scan of cnt[0, n) into off[0, n] (off[n] = the total), tile by tile in index order; then the

@@ -5,8 +5,13 @@
 // Same inputs and the same layout as kernels_quality.hpp: face centres / area vectors by face id and cell centres by cell id as
 // the loop's geometry launch publishes them, kQualityBlock threads, kQualityPer elements per lane (lane t the elements t, t + 256,
 // ...), one partial record per workgroup, one folding workgroup at the end, no float atomics.  The cell pass runs first: it leaves
-// the signed cell volumes in a scratch array that the face pass reads by owner / neighbour.  Nothing of kernels_quality.hpp is
-// changed; its reduction helpers (qMaxId, qMinId, qBlockReduce) are used as they are.
+// the signed cell volumes in a scratch array that the face pass reads by owner / neighbour.  For a sub-domain of a decomposed
+// mesh (smgpu_quality_coupled_pack_volumes, smgpu_quality_coupled_geometry_*) the *_coupled kernels run: a
+// processor face takes the internal-face branch of weight and volume ratio with C_N (recvCc) and V_N (recvVc) of the neighbour
+// rank, a cell's determinant runs over its internal and its processor faces, and the volumes are computed before the exchange, by
+// k_quality_cell_volumes.  The cell and the face pass stay a serial / coupled pair each, with their own pass loops: sharing their
+// bodies (qPass, qNeighbour, qCellVolume) changed the register allocation and cost 0.6 - 1.5 % of kernel time
+// (profiles/quality/README.md), so they are the functions that were measured.  Keep each pair alike.
 #pragma once
 #include "kernels_quality.hpp"
 
@@ -27,7 +32,7 @@ struct QGCell {
     long long nUnder;
 };
 
-__device__ __forceinline__ QGFace qgFaceEmpty() {
+template <> __device__ __forceinline__ QGFace qEmpty<QGFace>() {
     QGFace a;
     a.maxSin = -__builtin_inf(); a.minFlat = __builtin_inf(); a.minW = __builtin_inf(); a.minR = __builtin_inf();
     a.sumFlat = a.sumW = a.sumR = 0.0;
@@ -35,7 +40,7 @@ __device__ __forceinline__ QGFace qgFaceEmpty() {
     a.nConcave = a.nFlat = a.nWarped = a.nLowW = a.nLowR = 0;
     return a;
 }
-__device__ __forceinline__ QGCell qgCellEmpty() {
+template <> __device__ __forceinline__ QGCell qEmpty<QGCell>() {
     QGCell a;
     a.minDet = __builtin_inf(); a.sumDet = 0.0; a.minDetId = kQualityNoId; a.nUnder = 0;
     return a;
@@ -73,12 +78,26 @@ __device__ __forceinline__ QGCell qShfl(const QGCell& a, int o) {
 
 struct QualityGeomThresholds { double sinConcave, flatness, weight, volRatio, determinant; };
 
+// the signed volume of every cell into vol, before the exchange of a decomposed mesh: for the volume pack and the face pass
+__global__ void __launch_bounds__(kQualityBlock) k_quality_cell_volumes(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea,
+                                                                         double* __restrict__ vol) {
+    qEach(m.nCells, [&](int c) { vol[c] = qCellVolume(m, fCtr, fArea, c, [](bool, int, const V3&) {}); });
+}
+// the owner cell's volume of every processor face, in patch order (the slot order of k_quality_pack): what the neighbour rank
+// needs as its V_N.  Lane i stores sendVc[i]: contiguous stores, gathered loads.
+__global__ void __launch_bounds__(kQualityBlock) k_quality_pack_volumes(const int* __restrict__ own, const double* __restrict__ vol,
+                                                                         const int* __restrict__ procFace, int nProc, double* __restrict__ sendVc) {
+    const int i = blockIdx.x * kQualityBlock + threadIdx.x;
+    if (i >= nProc) return;
+    sendVc[i] = vol[own[procFace[i]]];
+}
+
 // cell pass: signed volume (into vol, for the face pass) and determinant of cell c.  outDet: optional per-cell field.
 __device__ __forceinline__ void qgCellOne(const MeshView& m, const double* __restrict__ fCtr, const double* __restrict__ fArea,
                                           const QualityGeomThresholds& thr, int c, QGCell& a, double* __restrict__ vol, double* __restrict__ outDet) {
     const int b = m.cfOff[c], e = m.cfOff[c + 1];
-    // V_c: the volume arithmetic of qCellOne (kernels_quality.hpp), written a second time on purpose -- the same formula in the
-    // same order, so the same bits; qCellOne stays untouched and its instantiations compile to what they were.  Keep the two alike.
+    // V_c: the arithmetic of qCellVolume (kernels_quality.hpp) in the same order, so the same bits, written out here because the
+    // injected form compiled to a slower kernel (see the head of this file).  Keep the two alike.
     V3 cEst = v3(0, 0, 0);
     for (int j = b; j < e; ++j) cEst = cEst + ldv(fCtr, m.cfVal[j] & 0x7fffffff);
     cEst = cEst / (double)(e - b);
@@ -116,13 +135,62 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_geom_cells(MeshView m
                                                                        QualityGeomThresholds thr, QGCell* __restrict__ part, double* __restrict__ vol,
                                                                        double* __restrict__ outDet) {
     __shared__ QGCell sh[kQualityBlock / 64];
-    QGCell a = qgCellEmpty();
+    QGCell a = qEmpty<QGCell>();
     const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
     for (int k = 0; k < kQualityPer; ++k) {
         const int c = base + k * kQualityBlock;
         if (c >= m.nCells) break;
-        QGCell e = qgCellEmpty();
+        QGCell e = qEmpty<QGCell>();
         qgCellOne(m, fCtr, fArea, thr, c, e, vol, outDet);
+        qCombine(a, e);
+    }
+    a = qBlockReduce(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// the determinant of cell c over its internal and its processor faces.  Twin of the determinant part of qgCellOne
+// above: the face test "f < nInternalFaces" widened by "or has a slot >= 0", the sums in the same order
+// (without processor faces the same bits).  The volumes are k_quality_cell_volumes'.
+__device__ __forceinline__ bool qgcCounts(const MeshView& m, const int* __restrict__ slot, int f) {
+    return f < m.nInternalFaces || slot[f - m.nInternalFaces] >= 0;
+}
+__device__ __forceinline__ void qgCellOneCoupled(const MeshView& m, const double* __restrict__ fArea, const int* __restrict__ slot,
+                                                 const QualityGeomThresholds& thr, int c, QGCell& a, double* __restrict__ outDet) {
+    const int b = m.cfOff[c], e = m.cfOff[c + 1];
+    double sumA = 0.0;
+    int nInt = 0;
+    for (int j = b; j < e; ++j) {
+        const int f = m.cfVal[j] & 0x7fffffff;
+        if (qgcCounts(m, slot, f)) { sumA += mag(ldv(fArea, f)); ++nInt; }
+    }
+    double det = 0.0;
+    const double avgA = nInt > 0 ? sumA / (double)nInt : 0.0;
+    if (nInt > 0 && avgA >= SMGPU_ROOTVSMALL) {
+        double xx = 0.0, xy = 0.0, xz = 0.0, yy = 0.0, yz = 0.0, zz = 0.0;
+        for (int j = b; j < e; ++j) {
+            const int f = m.cfVal[j] & 0x7fffffff;
+            if (!qgcCounts(m, slot, f)) continue;
+            const V3 s = ldv(fArea, f) / avgA;
+            xx += s.x * s.x; xy += s.x * s.y; xz += s.x * s.z;
+            yy += s.y * s.y; yz += s.y * s.z; zz += s.z * s.z;
+        }
+        det = fabs((xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz)) + xz * (xy * yz - yy * xz)) / 8.0;
+    }
+    a.minDet = det; a.minDetId = c; a.sumDet = det;
+    a.nUnder = (det < thr.determinant) ? 1 : 0;
+    if (outDet) outDet[c] = det;
+}
+__global__ void __launch_bounds__(kQualityBlock) k_quality_geom_cells_coupled(MeshView m, const double* __restrict__ fArea, const int* __restrict__ slot,
+                                                                               QualityGeomThresholds thr, QGCell* __restrict__ part,
+                                                                               double* __restrict__ outDet) {
+    __shared__ QGCell sh[kQualityBlock / 64];
+    QGCell a = qEmpty<QGCell>();
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int c = base + k * kQualityBlock;
+        if (c >= m.nCells) break;
+        QGCell e = qEmpty<QGCell>();
+        qgCellOneCoupled(m, fArea, slot, thr, c, e, outDet);
         qCombine(a, e);
     }
     a = qBlockReduce(a, sh);
@@ -202,12 +270,12 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_geom_faces(MeshView m
                                                                        double* __restrict__ outConc, double* __restrict__ outFlat,
                                                                        double* __restrict__ outW, double* __restrict__ outR) {
     __shared__ QGFace sh[kQualityBlock / 64];
-    QGFace a = qgFaceEmpty();
+    QGFace a = qEmpty<QGFace>();
     const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
     for (int k = 0; k < kQualityPer; ++k) {
         const int f = base + k * kQualityBlock;
         if (f >= m.nFaces) break;
-        QGFace e = qgFaceEmpty();
+        QGFace e = qEmpty<QGFace>();
         qgFaceOne(m, pts, fCtr, fArea, cellCtr, vol, own, nei, thr, f, e, outConc, outFlat, outW, outR);
         qCombine(a, e);
     }
@@ -215,34 +283,86 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_geom_faces(MeshView m
     if (threadIdx.x == 0) part[blockIdx.x] = a;
 }
 
-// one workgroup, the fold of k_quality_final: thread t folds the records t, t + 256, ... in that order, then the workgroup
-// reduction -> the report
-__global__ void __launch_bounds__(kQualityBlock) k_quality_geom_final(const QGFace* __restrict__ fPart, int nFB, const QGCell* __restrict__ cPart, int nCB,
-                                                                       int nCells, int nInternalFaces, smgpu_quality_geometry* __restrict__ out) {
-    __shared__ QGFace shF[kQualityBlock / 64];
-    __shared__ QGCell shC[kQualityBlock / 64];
-    QGFace a = qgFaceEmpty();
-    for (int i = threadIdx.x; i < nFB; i += kQualityBlock) qCombine(a, fPart[i]);
-    QGCell b = qgCellEmpty();
-    for (int i = threadIdx.x; i < nCB; i += kQualityBlock) qCombine(b, cPart[i]);
-    a = qBlockReduce(a, shF);
-    b = qBlockReduce(b, shC);
+// k_quality_geom_faces with processor faces.  qgFaceOne gives every face its concavity and flatness (they read the face's own
+// points and C_f only) and the internal faces their weight and volume ratio; a processor face then takes the weight / ratio lines
+// of qgFaceOne (their twin, keep alike) with C_N = recvCc[slot], V_N = recvVc[slot], and leaves the record where the other side
+// counts it.  Its outW / outR entries, which qgFaceOne set to 1, are written again by the same lane.
+__global__ void __launch_bounds__(kQualityBlock) k_quality_geom_faces_coupled(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                               const double* __restrict__ fArea, const double* __restrict__ cellCtr,
+                                                                               const double* __restrict__ vol, const int* __restrict__ own,
+                                                                               const int* __restrict__ nei, const int* __restrict__ slot,
+                                                                               const double* __restrict__ recvCc, const double* __restrict__ recvVc,
+                                                                               QualityGeomThresholds thr, QGFace* __restrict__ part,
+                                                                               double* __restrict__ outConc, double* __restrict__ outFlat,
+                                                                               double* outW, double* outR) {
+    __shared__ QGFace sh[kQualityBlock / 64];
+    QGFace a = qEmpty<QGFace>();
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int f = base + k * kQualityBlock;
+        if (f >= m.nFaces) break;
+        QGFace e = qEmpty<QGFace>();
+        qgFaceOne(m, pts, fCtr, fArea, cellCtr, vol, own, nei, thr, f, e, outConc, outFlat, outW, outR);
+        const int sl = f < m.nInternalFaces ? -1 : slot[f - m.nInternalFaces];
+        if (sl >= 0) {
+            const V3 Cf = ldv(fCtr, f), Sf = ldv(fArea, f);
+            const int o = own[f];
+            const double dO = fabs(dot(Sf, Cf - ldv(cellCtr, o))), dN = fabs(dot(Sf, ldv(recvCc, sl & kQualitySlotMask) - Cf));
+            const double w = fmin(dO, dN) / ((dO + dN) + SMGPU_VSMALL);
+            const double vO = vol[o], vN = recvVc[sl & kQualitySlotMask];
+            const double r = fmin(vO, vN) / (fmax(vO, vN) + SMGPU_VSMALL);
+            e.minW = w; e.minWId = f; e.sumW = w; e.nLowW = (w < thr.weight) ? 1 : 0;
+            e.minR = r; e.minRId = f; e.sumR = r; e.nLowR = (r < thr.volRatio) ? 1 : 0;
+            if (outW) outW[f] = w;
+            if (outR) outR[f] = r;
+            if (sl & kQualityNotCounted) e = qEmpty<QGFace>();
+        }
+        qCombine(a, e);
+    }
+    a = qBlockReduce(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// the serial report of the folded record: the averages in place of the sums
+__device__ __forceinline__ void qFinish(const smgpu_quality_geometry_part& q, smgpu_quality_geometry_part* __restrict__ out) { *out = q; }
+__device__ __forceinline__ void qFinish(const smgpu_quality_geometry_part& q, smgpu_quality_geometry* __restrict__ out) {
+    smgpu_quality_geometry r;
+    r.nConcaveFaces = q.nConcaveFaces; r.maxConcaveSin = q.maxConcaveSin; r.maxConcaveAngle = q.maxConcaveAngle; r.maxConcaveFace = q.maxConcaveFace;
+    r.minFlatness = q.minFlatness; r.avgFlatness = q.nFlatnessFaces > 0 ? q.sumFlatness / (double)q.nFlatnessFaces : 1.0;
+    r.nFlatnessFaces = q.nFlatnessFaces; r.nWarpedFaces = q.nWarpedFaces; r.minFlatnessFace = q.minFlatnessFace;
+    r.minFaceWeight = q.minFaceWeight; r.avgFaceWeight = q.nInternalFaces > 0 ? q.sumFaceWeight / (double)q.nInternalFaces : 1.0;
+    r.nLowWeightFaces = q.nLowWeightFaces; r.minFaceWeightFace = q.minFaceWeightFace;
+    r.minVolRatio = q.minVolRatio; r.avgVolRatio = q.nInternalFaces > 0 ? q.sumVolRatio / (double)q.nInternalFaces : 1.0;
+    r.nLowVolRatioFaces = q.nLowVolRatioFaces; r.minVolRatioFace = q.minVolRatioFace;
+    r.minDeterminant = q.minDeterminant; r.avgDeterminant = q.nCells > 0 ? q.sumDeterminant / (double)q.nCells : 0.0;
+    r.nUnderdeterminedCells = q.nUnderdeterminedCells; r.minDeterminantCell = q.minDeterminantCell;
+    *out = r;
+}
+// one workgroup folds the two slabs (qFold) into the record of sums and denominators.  Out = smgpu_quality_geometry_part: the
+// per-rank record (nFaces / nInternalFaces are the counted ones); Out = smgpu_quality_geometry: the serial report.  A rank's own
+// maxConcaveAngle is derived here from its maxConcaveSin, so the combine evaluates no acos on the host.
+template <class Out>
+__global__ void __launch_bounds__(kQualityBlock) k_quality_geom_final(const QGFace* __restrict__ fPart, int nFB, const QGCell* __restrict__ cPart,
+                                                                       int nCB, int nCells, int nFaces, int nInternalFaces, Out* __restrict__ out) {
+    const QGFace a = qFold(fPart, nFB);
+    const QGCell b = qFold(cPart, nCB);
     if (threadIdx.x != 0) return;
-    smgpu_quality_geometry q;
+    smgpu_quality_geometry_part q;
+    q.nCells = nCells; q.nFaces = nFaces; q.nInternalFaces = nInternalFaces;
     const bool anyConcave = a.nConcave > 0, anyFlat = a.nFlat > 0, anyInternal = nInternalFaces > 0, anyCell = nCells > 0;
     q.nConcaveFaces = a.nConcave;
     q.maxConcaveSin = anyConcave ? a.maxSin : 0.0;
     q.maxConcaveAngle = anyConcave ? 90.0 - kRadToDeg * smacos::acosX(fmin(1.0, a.maxSin)) : 0.0;
     q.maxConcaveFace = anyConcave ? a.maxSinId : -1;
-    q.minFlatness = anyFlat ? a.minFlat : 1.0; q.avgFlatness = anyFlat ? a.sumFlat / (double)a.nFlat : 1.0;
+    q.minFlatness = anyFlat ? a.minFlat : 1.0; q.sumFlatness = a.sumFlat;
     q.nFlatnessFaces = a.nFlat; q.nWarpedFaces = a.nWarped; q.minFlatnessFace = anyFlat ? a.minFlatId : -1;
-    q.minFaceWeight = anyInternal ? a.minW : 1.0; q.avgFaceWeight = anyInternal ? a.sumW / (double)nInternalFaces : 1.0;
+    q.minFaceWeight = anyInternal ? a.minW : 1.0; q.sumFaceWeight = a.sumW;
     q.nLowWeightFaces = a.nLowW; q.minFaceWeightFace = anyInternal ? a.minWId : -1;
-    q.minVolRatio = anyInternal ? a.minR : 1.0; q.avgVolRatio = anyInternal ? a.sumR / (double)nInternalFaces : 1.0;
+    q.minVolRatio = anyInternal ? a.minR : 1.0; q.sumVolRatio = a.sumR;
     q.nLowVolRatioFaces = a.nLowR; q.minVolRatioFace = anyInternal ? a.minRId : -1;
-    q.minDeterminant = anyCell ? b.minDet : 0.0; q.avgDeterminant = anyCell ? b.sumDet / (double)nCells : 0.0;
+    q.minDeterminant = anyCell ? b.minDet : 0.0; q.sumDeterminant = b.sumDet;
     q.nUnderdeterminedCells = b.nUnder; q.minDeterminantCell = anyCell ? b.minDetId : -1;
-    *out = q;
+    qFinish(q, out);
 }
 
 }  // namespace smgpu

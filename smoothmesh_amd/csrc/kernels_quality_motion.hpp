@@ -6,7 +6,10 @@
 // Same inputs and the same layout as kernels_quality.hpp: face centres by face id and cell centres by cell id as the loop's
 // geometry launch publishes them, kQualityBlock threads, kQualityPer faces per lane (lane t the faces t, t + 256, ...), one partial
 // record per workgroup, one folding workgroup at the end, no float atomics.  A face pass only: every criterion is per face.
-// Nothing of kernels_quality.hpp is changed; its reduction helpers (qMinId, qBlockReduce) are used as they are.
+// For a sub-domain of a decomposed mesh (smgpu_quality_coupled_motion_*) k_quality_motion_faces_coupled runs: a
+// processor face takes the internal-face branch of the tets and the twist with the neighbour rank's cell centre.  The serial and
+// the coupled face pass stay a pair, with their own pass loops: one shared body changed the register allocation and cost 2 % of
+// kernel time (profiles/quality/README.md), so they are the functions that were measured.
 #pragma once
 #include "kernels_quality.hpp"
 
@@ -19,7 +22,7 @@ struct QMFace {
     long long nLowTet, nNoBase, nTw, nLowTw, nLowTri;
 };
 
-__device__ __forceinline__ QMFace qmFaceEmpty() {
+template <> __device__ __forceinline__ QMFace qEmpty<QMFace>() {
     QMFace a;
     a.minTet = a.minBase = a.minTw = a.minTri = __builtin_inf();
     a.sumTet = a.sumTw = a.sumTri = 0.0;
@@ -146,12 +149,12 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_motion_faces(MeshView
                                                                          double* __restrict__ outBase, double* __restrict__ outTw,
                                                                          double* __restrict__ outTri) {
     __shared__ QMFace sh[kQualityBlock / 64];
-    QMFace a = qmFaceEmpty();
+    QMFace a = qEmpty<QMFace>();
     const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
     for (int k = 0; k < kQualityPer; ++k) {
         const int f = base + k * kQualityBlock;
         if (f >= m.nFaces) break;
-        QMFace e = qmFaceEmpty();
+        QMFace e = qEmpty<QMFace>();
         qmFaceOne(m, pts, fCtr, cellCtr, own, nei, thr, f, e, outTet, outBase, outTw, outTri);
         qCombine(a, e);
     }
@@ -159,25 +162,131 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_motion_faces(MeshView
     if (threadIdx.x == 0) part[blockIdx.x] = a;
 }
 
-// one workgroup, the fold of k_quality_geom_final: thread t folds the records t, t + 256, ... in that order, then the workgroup
-// reduction -> the report
-__global__ void __launch_bounds__(kQualityBlock) k_quality_motion_final(const QMFace* __restrict__ fPart, int nFB, int nFaces,
-                                                                         smgpu_quality_motion* __restrict__ out) {
+// qmFaceOne with `internal` and C_N given by the caller, so that a processor face takes the internal-face branch of the tets
+// and the twist with the neighbour rank's cell centre.  Its twin: the two walks, statement by statement; with
+// internal = f < nInternalFaces and C_N = cellCtr[nei[f]] the same bits.  Keep the two alike.
+__device__ __forceinline__ void qmFaceOneCoupled(const MeshView& m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                 const V3 CO, const bool internal, const V3 CN, const QualityMotionThresholds& thr, int f,
+                                                 QMFace& a, double* __restrict__ outTet, double* __restrict__ outBase,
+                                                 double* __restrict__ outTw, double* __restrict__ outTri) {
+    const V3 Cf = ldv(fCtr, f);
+    const int jb = m.faceOff[f], nv = m.faceOff[f + 1] - jb;
+    const bool summed = nv > 3;
+    double tet = __builtin_inf(), tw = __builtin_inf(), tri = __builtin_inf();
+    int nValid = 0;
+    if (nv > 0) {
+        const V3 dv = sel3(internal, CN, Cf) - CO;
+        const V3 nHat = dv / (mag(dv) + SMGPU_VSMALL);
+        const V3 p0 = ldv(pts, m.facePts[jb]);
+        V3 cur = p0, hFirst = v3(0, 0, 0), hPrev = v3(0, 0, 0);
+        for (int i = 0; i < nv; ++i) {
+            const V3 nxt = (i + 1 < nv) ? ldv(pts, m.facePts[jb + i + 1]) : p0;
+            const V3 u = nxt - cur, v = Cf - cur;
+            tet = fmin(tet, qmTetPair(cur, u, v, CO, internal, CN, thr.k));
+            if (summed) {
+                const V3 t = 0.5 * cross(u, v);
+                const double mt = mag(t);
+                if (mt > SMGPU_VSMALL) {
+                    const V3 h = t / mt;
+                    tw = fmin(tw, dot(nHat, h));
+                    if (nValid > 0) tri = fmin(tri, dot(hPrev, h));
+                    else hFirst = h;
+                    hPrev = h;
+                    ++nValid;
+                }
+            }
+            cur = nxt;
+        }
+        if (nValid >= 2) tri = fmin(tri, dot(hPrev, hFirst));
+    }
+    double base = __builtin_inf();
+    for (int b = 0; b < nv; ++b) {
+        const V3 pb = ldv(pts, m.facePts[jb + b]);
+        int i = b + 1 < nv ? b + 1 : b + 1 - nv;
+        V3 u = ldv(pts, m.facePts[jb + i]) - pb;
+        double mb = __builtin_inf();
+        for (int k = 1; k + 2 <= nv; ++k) {
+            i = i + 1 < nv ? i + 1 : 0;
+            const V3 v = ldv(pts, m.facePts[jb + i]) - pb;
+            mb = fmin(mb, qmTetPair(pb, u, v, CO, internal, CN, thr.k));
+            u = v;
+        }
+        if (b == 0 || mb > base) base = mb;
+    }
+    a.minTet = tet; a.minTetId = f; a.sumTet = tet; a.nLowTet = (tet < thr.tet) ? 1 : 0;
+    a.minBase = base; a.minBaseId = f; a.nNoBase = (base < thr.tet) ? 1 : 0;
+    if (nValid < 1) tw = 1.0;
+    if (nValid < 2) tri = 1.0;
+    if (summed) {
+        a.minTw = tw; a.minTwId = f; a.sumTw = tw; a.nTw = 1; a.nLowTw = (tw < thr.twist) ? 1 : 0;
+        a.minTri = tri; a.minTriId = f; a.sumTri = tri; a.nLowTri = (tri < thr.triTwist) ? 1 : 0;
+    }
+    if (outTet) outTet[f] = tet;
+    if (outBase) outBase[f] = base;
+    if (outTw) outTw[f] = tw;
+    if (outTri) outTri[f] = tri;
+}
+// k_quality_motion_faces with processor faces: one body for the three kinds of face, the slot only selects where C_N comes
+// from (148 VGPR where k_quality_motion_faces holds 146, both three waves per SIMD)
+__global__ void __launch_bounds__(kQualityBlock) k_quality_motion_faces_coupled(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                                 const double* __restrict__ cellCtr, const int* __restrict__ own,
+                                                                                 const int* __restrict__ nei, const int* __restrict__ slot,
+                                                                                 const double* __restrict__ recvCc, QualityMotionThresholds thr,
+                                                                                 QMFace* __restrict__ part, double* __restrict__ outTet,
+                                                                                 double* __restrict__ outBase, double* __restrict__ outTw,
+                                                                                 double* __restrict__ outTri) {
     __shared__ QMFace sh[kQualityBlock / 64];
-    QMFace a = qmFaceEmpty();
-    for (int i = threadIdx.x; i < nFB; i += kQualityBlock) qCombine(a, fPart[i]);
+    QMFace a = qEmpty<QMFace>();
+    const int base = blockIdx.x * (kQualityPer * kQualityBlock) + threadIdx.x;
+    for (int k = 0; k < kQualityPer; ++k) {
+        const int f = base + k * kQualityBlock;
+        if (f >= m.nFaces) break;
+        QMFace e = qEmpty<QMFace>();
+        const int sl = f < m.nInternalFaces ? -1 : slot[f - m.nInternalFaces];
+        // C_N by address: the neighbour cell's row of cellCtr, the slot's row of recvCc, or (physical patch, unused) the owner's row
+        const double* cnAt = f < m.nInternalFaces ? cellCtr + 3 * (size_t)nei[f]
+                                                  : (sl >= 0 ? recvCc + 3 * (size_t)(sl & kQualitySlotMask) : cellCtr + 3 * (size_t)own[f]);
+        const bool internal = f < m.nInternalFaces || sl >= 0;
+        const V3 CN = internal ? v3(cnAt[0], cnAt[1], cnAt[2]) : v3(0, 0, 0);
+        qmFaceOneCoupled(m, pts, fCtr, ldv(cellCtr, own[f]), internal, CN, thr, f, e, outTet, outBase, outTw, outTri);
+        if (sl >= 0 && (sl & kQualityNotCounted)) e = qEmpty<QMFace>();
+        qCombine(a, e);
+    }
     a = qBlockReduce(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// the serial report of the folded record: the averages in place of the sums
+__device__ __forceinline__ void qFinish(const smgpu_quality_motion_part& q, smgpu_quality_motion_part* __restrict__ out) { *out = q; }
+__device__ __forceinline__ void qFinish(const smgpu_quality_motion_part& q, smgpu_quality_motion* __restrict__ out) {
+    smgpu_quality_motion r;
+    const bool anyFace = q.nFaces > 0, anyTw = q.nTwistFaces > 0;
+    r.minTetQuality = q.minTetQuality; r.avgTetQuality = anyFace ? q.sumTetQuality / (double)q.nFaces : 1.0;
+    r.nLowTetFaces = q.nLowTetFaces; r.minTetFace = q.minTetFace;
+    r.minBaseTetQuality = q.minBaseTetQuality; r.nNoBasePointFaces = q.nNoBasePointFaces; r.minBaseTetFace = q.minBaseTetFace;
+    r.minTwist = q.minTwist; r.avgTwist = anyTw ? q.sumTwist / (double)q.nTwistFaces : 1.0;
+    r.nTwistFaces = q.nTwistFaces; r.nLowTwistFaces = q.nLowTwistFaces; r.minTwistFace = q.minTwistFace;
+    r.minTriangleTwist = q.minTriangleTwist; r.avgTriangleTwist = anyTw ? q.sumTriangleTwist / (double)q.nTwistFaces : 1.0;
+    r.nLowTriangleTwistFaces = q.nLowTriangleTwistFaces; r.minTriangleTwistFace = q.minTriangleTwistFace;
+    *out = r;
+}
+// one workgroup folds the slab (qFold) into the record of sums and denominators.  Out = smgpu_quality_motion_part: the per-rank
+// record (nFaces is the counted one); Out = smgpu_quality_motion: the serial report
+template <class Out>
+__global__ void __launch_bounds__(kQualityBlock) k_quality_motion_final(const QMFace* __restrict__ fPart, int nFB, int nFaces, Out* __restrict__ out) {
+    const QMFace a = qFold(fPart, nFB);
     if (threadIdx.x != 0) return;
-    smgpu_quality_motion q;
+    smgpu_quality_motion_part q;
+    q.nFaces = nFaces;
     const bool anyFace = nFaces > 0, anyTw = a.nTw > 0;
-    q.minTetQuality = anyFace ? a.minTet : 1.0; q.avgTetQuality = anyFace ? a.sumTet / (double)nFaces : 1.0;
+    q.minTetQuality = anyFace ? a.minTet : 1.0; q.sumTetQuality = a.sumTet;
     q.nLowTetFaces = a.nLowTet; q.minTetFace = anyFace ? a.minTetId : -1;
     q.minBaseTetQuality = anyFace ? a.minBase : 1.0; q.nNoBasePointFaces = a.nNoBase; q.minBaseTetFace = anyFace ? a.minBaseId : -1;
-    q.minTwist = anyTw ? a.minTw : 1.0; q.avgTwist = anyTw ? a.sumTw / (double)a.nTw : 1.0;
+    q.minTwist = anyTw ? a.minTw : 1.0; q.sumTwist = a.sumTw;
     q.nTwistFaces = a.nTw; q.nLowTwistFaces = a.nLowTw; q.minTwistFace = anyTw ? a.minTwId : -1;
-    q.minTriangleTwist = anyTw ? a.minTri : 1.0; q.avgTriangleTwist = anyTw ? a.sumTri / (double)a.nTw : 1.0;
+    q.minTriangleTwist = anyTw ? a.minTri : 1.0; q.sumTriangleTwist = a.sumTri;
     q.nLowTriangleTwistFaces = a.nLowTri; q.minTriangleTwistFace = anyTw ? a.minTriId : -1;
-    *out = q;
+    qFinish(q, out);
 }
 
 }  // namespace smgpu

@@ -22,7 +22,6 @@
 #include "kernels_quality.hpp"
 #include "kernels_quality_geom.hpp"
 #include "kernels_quality_motion.hpp"
-#include "kernels_quality_coupled.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"
@@ -245,7 +244,7 @@ struct smgpu_handle {
     // ... and of the motion criteria (smgpu_mesh_quality_motion, kernels_quality_motion.hpp): the partial slab and the report, likewise
     QMFace* qmFacePart = nullptr;
     smgpu_quality_motion* qmOut = nullptr;
-    // ... and of the two reports above for a sub-domain (smgpu_quality_coupled_geometry_* / _motion_*, kernels_quality_coupled.hpp):
+    // ... and of the two reports above for a sub-domain (smgpu_quality_coupled_geometry_* / _motion_*):
     // the records; the scratch is the serial reports' (qgVol, the partial slabs).  qVolEpoch, qVolCoupling: the geometry epoch and the coupling of the
     // last pack_volumes (a later pack with another coupling lays the slots out anew: sendVc / recvVc of the old one no longer fit)
     smgpu_quality_geometry_part* qgPartOut = nullptr;
@@ -3297,9 +3296,6 @@ static int qualityEnsure(smgpu_handle* h) {
     return 0;
 }
 
-// geometry of the current points (the loop's own kernel, publishing face values by id as for smgpu_debug_propose), then the face
-// pass, the cell pass and the final reduction into h->qOut.  The out* fields are optional per-element outputs.  The geometry
-// launch is not counted in the engine's statistics (launch counts, timing events).
 static const char* kQualityHaloRefusal = "mesh quality: not available on an engine with a halo (a sub-domain's processor faces are internal faces of "
                                          "the global mesh, whose neighbour cell centres this report does not exchange); report on the undecomposed mesh, or use "
                                          "smgpu_quality_coupled_pack / _report";
@@ -3320,49 +3316,203 @@ static QualityThresholds qualityThresholds(const smgpu_quality_params* p) {
     const smgpu_quality_params prm = p ? *p : smgpu_quality_params{70.0, 4.0, 1e-6, 1000.0};
     return QualityThresholds{std::cos(prm.nonOrthThreshold * (SMGPU_PI / 180.0)), prm.skewThreshold, prm.closedThreshold, prm.aspectThreshold};
 }
-static int runQuality(smgpu_handle* h, const smgpu_quality_params* p, double* outNO, double* outSkew, double* outV, double* outOpen, double* outAR) {
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    HIP_OK(hipSetDevice(h->device));
+static QualityGeomThresholds geomThresholds(const smgpu_quality_geometry_params* p) {
+    const smgpu_quality_geometry_params prm = p ? *p : smgpu_quality_geometry_params{10.0, 0.8, 0.05, 0.01, 0.001};
+    return QualityGeomThresholds{std::sin(prm.concaveThreshold * (SMGPU_PI / 180.0)), prm.flatnessThreshold, prm.weightThreshold,
+                                 prm.volRatioThreshold, prm.determinantThreshold};
+}
+static QualityMotionThresholds motionThresholds(const smgpu_quality_motion_params* p) {
+    const smgpu_quality_motion_params prm = p ? *p : smgpu_quality_motion_params{1e-15, 0.02, -1.0};
+    // k = 8 / (9 sqrt 3) is the host's double, as the contract says: the kernel takes it as an argument
+    return QualityMotionThresholds{prm.tetThreshold, prm.twistThreshold, prm.triangleTwistThreshold, 8.0 / (9.0 * std::sqrt(3.0))};
+}
+// a coupled call's refusals: the geometry and the coupling are those of the last pack (DESIGN.md "Mesh quality", 10.4); `buf` is the
+// device buffer the call may not go without (`what`) when there are processor faces
+static int qualityCoupledReady(smgpu_handle* h, const char* api, const void* buf, const char* what = "recvCc") {
+    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
+    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
+        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
+    if (h->qNProc > 0 && !buf) return fail(std::string(api) + ": null " + what);
+    return 0;
+}
+static QCoupling<true> qualityCoupling(const smgpu_handle* h, const void* recvCc, const void* recvVc) {
+    return QCoupling<true>{h->qSlot, (const double*)recvCc, (const double*)recvVc};
+}
+static double* const kQualityNoFields[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+
+static int qualityGeomEnsure(smgpu_handle* h) {
     if (qualityEnsure(h)) return 1;
+    if (h->qgOut) return 0;
     const MeshView& m = h->mv;
-    if (qualityGeometry(h)) return 1;
-    const QualityThresholds thr = qualityThresholds(p);
-    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-    const State& s = h->st;
-    if (nFB > 0)
-        hipLaunchKernelGGL(k_quality_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qOwn, h->qNei, thr,
-                           h->qFacePart, outNO, outSkew);
-    if (nCB > 0)
-        hipLaunchKernelGGL(k_quality_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qCellPart, outV, outOpen, outAR);
-    hipLaunchKernelGGL(k_quality_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qFacePart, nFB, h->qCellPart, nCB, m.nCells, m.nFaces,
-                       m.nInternalFaces, h->qOut);
-    HIP_OK(hipGetLastError());
+    const size_t nFB = (size_t)std::max(1, qualityGrid(m.nFaces)), nCB = (size_t)std::max(1, qualityGrid(m.nCells));
+    hipError_t e = hipMalloc((void**)&h->qgVol, sizeof(double) * (size_t)std::max(1, m.nCells));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qgFacePart, sizeof(QGFace) * nFB);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qgCellPart, sizeof(QGCell) * nCB);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qgOut, sizeof(smgpu_quality_geometry));
+    if (e != hipSuccess) {
+        for (void** p : {(void**)&h->qgVol, (void**)&h->qgFacePart, (void**)&h->qgCellPart, (void**)&h->qgOut})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        return fail(std::string("mesh quality: device memory for the geometry report: ") + hipGetErrorString(e));
+    }
+    return 0;
+}
+static int qualityMotionEnsure(smgpu_handle* h) {
+    if (qualityEnsure(h)) return 1;
+    if (h->qmOut) return 0;
+    const size_t nFB = (size_t)std::max(1, qualityGrid(h->mv.nFaces));
+    hipError_t e = hipMalloc((void**)&h->qmFacePart, sizeof(QMFace) * nFB);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qmOut, sizeof(smgpu_quality_motion));
+    if (e != hipSuccess) {
+        for (void** p : {(void**)&h->qmFacePart, (void**)&h->qmOut})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        return fail(std::string("mesh quality: device memory for the motion criteria: ") + hipGetErrorString(e));
+    }
     return 0;
 }
 
-int smgpu_mesh_quality(smgpu_handle* h, const smgpu_quality_params* p, smgpu_quality* out) {
-    if (!h || !out) return fail("null argument");
-    if (runQuality(h, p, nullptr, nullptr, nullptr, nullptr, nullptr)) return 1;
-    HIP_OK(hipMemcpyAsync(out, h->qOut, sizeof(smgpu_quality), hipMemcpyDeviceToHost, h->stream));
+// Every report is one function for the serial mesh (Coupled = false: cp is empty, api unused) and for a sub-domain (Coupled = true,
+// on the geometry of the last pack): the same launches of the same kernels, with or without the coupling.  o: the optional
+// per-element outputs, in the order of the report's field table below.
+extern "C++" {
+// the record a report's final reduction left on the device, to the host
+template <class T>
+static int qualityCopyOut(smgpu_handle* h, T* out, const T* dev) {
+    HIP_OK(hipMemcpyAsync(out, dev, sizeof(T), hipMemcpyDeviceToHost, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     return 0;
 }
 
-// one per-element quality field: `run(o)` launches the passes with the outputs o[5] (faceNonOrthogonality, faceSkewness, cellVolume,
-// cellOpenness, cellAspectRatio), one of them set to a buffer allocated for this call
-extern "C++" {
+// serial: geometry of the current points (the loop's own kernel, publishing face values by id as for smgpu_debug_propose; not counted
+// in the engine's statistics), then the face pass, the cell pass and the final reduction into h->qOut; coupled: into h->qPartOut
+template <bool Coupled>
+static int runQuality(smgpu_handle* h, const char* api, const smgpu_quality_params* p, const QCoupling<Coupled>& cp, double* const* o) {
+    if constexpr (Coupled) {
+        if (qualityCoupledReady(h, api, cp.recvCc)) return 1;
+        HIP_OK(hipSetDevice(h->device));
+    } else {
+        if (h->haloOn) return fail(kQualityHaloRefusal);
+        HIP_OK(hipSetDevice(h->device));
+        if (qualityEnsure(h)) return 1;
+        if (qualityGeometry(h)) return 1;
+    }
+    const MeshView& m = h->mv;
+    const QualityThresholds thr = qualityThresholds(p);
+    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+    const State& s = h->st;
+    if (nFB > 0)
+        hipLaunchKernelGGL(k_quality_faces<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qOwn,
+                           h->qNei, cp, thr, h->qFacePart, o[0], o[1]);
+    if (nCB > 0)
+        hipLaunchKernelGGL(k_quality_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qCellPart, o[2], o[3], o[4]);
+    if constexpr (Coupled)
+        hipLaunchKernelGGL(k_quality_final<smgpu_quality_part>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qFacePart, nFB, h->qCellPart, nCB,
+                           m.nCells, m.nFaces - h->qNotCounted, m.nInternalFaces + h->qCountedProc, h->qPartOut);
+    else
+        hipLaunchKernelGGL(k_quality_final<smgpu_quality>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qFacePart, nFB, h->qCellPart, nCB,
+                           m.nCells, m.nFaces, m.nInternalFaces, h->qOut);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// the -allGeometry checks (DESIGN.md "Mesh quality", 10.6 and 10.8).  serial: geometry, the cell pass (volumes into h->qgVol), the face
+// pass, the final reduction into h->qgOut; coupled: the volumes are those of the last pack_volumes, the record goes to h->qgPartOut
+template <bool Coupled>
+static int runQualityGeom(smgpu_handle* h, const char* api, const smgpu_quality_geometry_params* p, const QCoupling<Coupled>& cp, double* const* o) {
+    if constexpr (Coupled) {
+        if (qualityCoupledReady(h, api, cp.recvCc)) return 1;
+        if (!h->qgPartOut || h->qVolEpoch != h->qEpoch || h->qVolCoupling != h->qCoupling)
+            return fail(std::string(api) + ": call smgpu_quality_coupled_pack_volumes after smgpu_quality_coupled_pack first");
+        if (h->qNProc > 0 && !cp.recvVc) return fail(std::string(api) + ": null recvVc");
+        HIP_OK(hipSetDevice(h->device));
+    } else {
+        if (h->haloOn) return fail(kQualityHaloRefusal);
+        HIP_OK(hipSetDevice(h->device));
+        if (qualityGeomEnsure(h)) return 1;
+        if (qualityGeometry(h)) return 1;
+    }
+    const MeshView& m = h->mv;
+    const QualityGeomThresholds thr = geomThresholds(p);
+    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+    const State& s = h->st;
+    if (nCB > 0) {
+        if constexpr (Coupled)
+            hipLaunchKernelGGL(k_quality_geom_cells_coupled, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fArea, cp.slot, thr, h->qgCellPart, o[4]);
+        else
+            hipLaunchKernelGGL(k_quality_geom_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qgCellPart, h->qgVol, o[4]);
+    }
+    if (nFB > 0) {
+        if constexpr (Coupled)
+            hipLaunchKernelGGL(k_quality_geom_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr,
+                               h->qgVol, h->qOwn, h->qNei, cp.slot, cp.recvCc, cp.recvVc, thr, h->qgFacePart, o[0], o[1], o[2], o[3]);
+        else
+            hipLaunchKernelGGL(k_quality_geom_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qgVol,
+                               h->qOwn, h->qNei, thr, h->qgFacePart, o[0], o[1], o[2], o[3]);
+    }
+    if constexpr (Coupled)
+        hipLaunchKernelGGL(k_quality_geom_final<smgpu_quality_geometry_part>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qgFacePart, nFB,
+                           h->qgCellPart, nCB, m.nCells, m.nFaces - h->qNotCounted, m.nInternalFaces + h->qCountedProc, h->qgPartOut);
+    else
+        hipLaunchKernelGGL(k_quality_geom_final<smgpu_quality_geometry>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qgFacePart, nFB,
+                           h->qgCellPart, nCB, m.nCells, m.nFaces, m.nInternalFaces, h->qgOut);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// the motion criteria (DESIGN.md "Mesh quality", 10.7 and 10.8).  serial: geometry, the face pass, the final reduction into h->qmOut;
+// coupled: the record goes to h->qmPartOut
+template <bool Coupled>
+static int runQualityMotion(smgpu_handle* h, const char* api, const smgpu_quality_motion_params* p, const QCoupling<Coupled>& cp, double* const* o) {
+    if constexpr (Coupled) {
+        if (qualityCoupledReady(h, api, cp.recvCc)) return 1;
+        HIP_OK(hipSetDevice(h->device));
+        if (qualityMotionEnsure(h)) return 1;
+        if (!h->qmPartOut) HIP_OK(hipMalloc((void**)&h->qmPartOut, sizeof(smgpu_quality_motion_part)));
+    } else {
+        if (h->haloOn) return fail(kQualityHaloRefusal);
+        HIP_OK(hipSetDevice(h->device));
+        if (qualityMotionEnsure(h)) return 1;
+        if (qualityGeometry(h)) return 1;
+    }
+    const MeshView& m = h->mv;
+    const QualityMotionThresholds thr = motionThresholds(p);
+    const int nFB = qualityGrid(m.nFaces);
+    const State& s = h->st;
+    if (nFB > 0) {
+        if constexpr (Coupled)
+            hipLaunchKernelGGL(k_quality_motion_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.cellCtr, h->qOwn,
+                               h->qNei, cp.slot, cp.recvCc, thr, h->qmFacePart, o[0], o[1], o[2], o[3]);
+        else
+            hipLaunchKernelGGL(k_quality_motion_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.cellCtr, h->qOwn, h->qNei,
+                               thr, h->qmFacePart, o[0], o[1], o[2], o[3]);
+    }
+    if constexpr (Coupled)
+        hipLaunchKernelGGL(k_quality_motion_final<smgpu_quality_motion_part>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qmFacePart, nFB,
+                           m.nFaces - h->qNotCounted, h->qmPartOut);
+    else
+        hipLaunchKernelGGL(k_quality_motion_final<smgpu_quality_motion>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qmFacePart, nFB, m.nFaces,
+                           h->qmOut);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// the per-element fields of a report kind: names[0, n), those from firstCell on per cell, and the refusal of any other name
+struct QualityFields { int n, firstCell; const char* names[5]; const char* unknown; const char* known; };
+static const QualityFields kQualityFields{5, 2, {"faceNonOrthogonality", "faceSkewness", "cellVolume", "cellOpenness", "cellAspectRatio"},
+                                          "unknown quality field ", " (cellVolume, cellOpenness, cellAspectRatio, faceNonOrthogonality, faceSkewness)"};
+static const QualityFields kQualityGeomFields{5, 4, {"faceConcavity", "faceFlatness", "faceWeight", "faceVolumeRatio", "cellDeterminant"},
+                                              "unknown quality geometry field ",
+                                              " (faceConcavity, faceFlatness, faceWeight, faceVolumeRatio, cellDeterminant)"};
+static const QualityFields kQualityMotionFields{4, 4, {"faceTetQuality", "faceBaseTetQuality", "faceTwist", "faceTriangleTwist"},
+                                                "unknown quality motion field ", " (faceTetQuality, faceBaseTetQuality, faceTwist, faceTriangleTwist)"};
+// one per-element field: `run(o)` launches the report's passes with the outputs o, the named one set to a buffer allocated for
+// this call (outside deviceBytes)
 template <class Run>
-static int qualityField(smgpu_handle* h, const char* api, const char* name, double* out, int64_t* n, Run run) {
-    const std::string s(name);
-    const int64_t C = h->mv.nCells, F = h->mv.nFaces;
-    int64_t cnt = 0;
+static int qualityField(smgpu_handle* h, const QualityFields& t, const char* api, const char* name, double* out, int64_t* n, Run run) {
     int which = -1;
-    if (s == "faceNonOrthogonality") { which = 0; cnt = F; }
-    else if (s == "faceSkewness") { which = 1; cnt = F; }
-    else if (s == "cellVolume") { which = 2; cnt = C; }
-    else if (s == "cellOpenness") { which = 3; cnt = C; }
-    else if (s == "cellAspectRatio") { which = 4; cnt = C; }
-    else return fail("unknown quality field " + s + " (cellVolume, cellOpenness, cellAspectRatio, faceNonOrthogonality, faceSkewness)");
+    for (int i = 0; i < t.n; ++i)
+        if (std::strcmp(name, t.names[i]) == 0) which = i;
+    if (which < 0) return fail(std::string(t.unknown) + name + t.known);
+    const int64_t cnt = which >= t.firstCell ? h->mv.nCells : h->mv.nFaces;
     *n = cnt;
     if (!out) return 0;
     HIP_OK(hipSetDevice(h->device));
@@ -3382,163 +3532,43 @@ static int qualityField(smgpu_handle* h, const char* api, const char* name, doub
 }
 }  // extern "C++"
 
+int smgpu_mesh_quality(smgpu_handle* h, const smgpu_quality_params* p, smgpu_quality* out) {
+    if (!h || !out) return fail("null argument");
+    if (runQuality(h, nullptr, p, QCoupling<false>{}, kQualityNoFields)) return 1;
+    return qualityCopyOut(h, out, h->qOut);
+}
 int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
     if (!h || !name || !n) return fail("null argument");
     if (h->haloOn) return fail(kQualityHaloRefusal);
-    return qualityField(h, "smgpu_quality_field", name, out, n, [&](double** o) { return runQuality(h, nullptr, o[0], o[1], o[2], o[3], o[4]); });
-}
-
-// ---- the checks `checkMesh -allGeometry` adds (kernels_quality_geom.hpp, DESIGN.md "Mesh quality", 10.6) -------------------
-static int qualityGeomEnsure(smgpu_handle* h) {
-    if (qualityEnsure(h)) return 1;
-    if (h->qgOut) return 0;
-    const MeshView& m = h->mv;
-    const size_t nFB = (size_t)std::max(1, qualityGrid(m.nFaces)), nCB = (size_t)std::max(1, qualityGrid(m.nCells));
-    hipError_t e = hipMalloc((void**)&h->qgVol, sizeof(double) * (size_t)std::max(1, m.nCells));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qgFacePart, sizeof(QGFace) * nFB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qgCellPart, sizeof(QGCell) * nCB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qgOut, sizeof(smgpu_quality_geometry));
-    if (e != hipSuccess) {
-        for (void** p : {(void**)&h->qgVol, (void**)&h->qgFacePart, (void**)&h->qgCellPart, (void**)&h->qgOut})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        return fail(std::string("mesh quality: device memory for the geometry report: ") + hipGetErrorString(e));
-    }
-    return 0;
-}
-// geometry of the current points (uncounted, as runQuality), the cell pass (volumes into h->qgVol), the face pass and the final
-// reduction into h->qgOut.  o[5]: optional per-element outputs faceConcavity, faceFlatness, faceWeight, faceVolumeRatio, cellDeterminant.
-static int runQualityGeom(smgpu_handle* h, const smgpu_quality_geometry_params* p, double* const* o) {
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityGeomEnsure(h)) return 1;
-    const MeshView& m = h->mv;
-    if (qualityGeometry(h)) return 1;
-    const smgpu_quality_geometry_params prm = p ? *p : smgpu_quality_geometry_params{10.0, 0.8, 0.05, 0.01, 0.001};
-    const QualityGeomThresholds thr{std::sin(prm.concaveThreshold * (SMGPU_PI / 180.0)), prm.flatnessThreshold, prm.weightThreshold,
-                                    prm.volRatioThreshold, prm.determinantThreshold};
-    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-    const State& s = h->st;
-    if (nCB > 0)
-        hipLaunchKernelGGL(k_quality_geom_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qgCellPart, h->qgVol, o[4]);
-    if (nFB > 0)
-        hipLaunchKernelGGL(k_quality_geom_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qgVol,
-                           h->qOwn, h->qNei, thr, h->qgFacePart, o[0], o[1], o[2], o[3]);
-    hipLaunchKernelGGL(k_quality_geom_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qgFacePart, nFB, h->qgCellPart, nCB, m.nCells,
-                       m.nInternalFaces, h->qgOut);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return qualityField(h, kQualityFields, "smgpu_quality_field", name, out, n,
+                        [&](double** o) { return runQuality(h, nullptr, nullptr, QCoupling<false>{}, o); });
 }
 
 int smgpu_mesh_quality_geometry(smgpu_handle* h, const smgpu_quality_geometry_params* p, smgpu_quality_geometry* out) {
     if (!h || !out) return fail("null argument");
-    double* const none[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (runQualityGeom(h, p, none)) return 1;
-    HIP_OK(hipMemcpyAsync(out, h->qgOut, sizeof(smgpu_quality_geometry), hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
-    return 0;
+    if (runQualityGeom(h, nullptr, p, QCoupling<false>{}, kQualityNoFields)) return 1;
+    return qualityCopyOut(h, out, h->qgOut);
 }
-
 int smgpu_quality_geometry_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
     if (!h || !name || !n) return fail("null argument");
     if (h->haloOn) return fail(kQualityHaloRefusal);
-    static const char* const names[5] = {"faceConcavity", "faceFlatness", "faceWeight", "faceVolumeRatio", "cellDeterminant"};
-    int which = -1;
-    for (int i = 0; i < 5; ++i)
-        if (std::strcmp(name, names[i]) == 0) which = i;
-    if (which < 0)
-        return fail(std::string("unknown quality geometry field ") + name + " (faceConcavity, faceFlatness, faceWeight, faceVolumeRatio, cellDeterminant)");
-    const int64_t cnt = which == 4 ? h->mv.nCells : h->mv.nFaces;
-    *n = cnt;
-    if (!out) return 0;
-    HIP_OK(hipSetDevice(h->device));
-    double* buf = nullptr;   // transient: one field's worth for this call only
-    HIP_OK(hipMalloc((void**)&buf, sizeof(double) * (size_t)std::max<int64_t>(1, cnt)));
-    double* o[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    o[which] = buf;
-    int rc = runQualityGeom(h, nullptr, o);
-    if (rc == 0 && cnt > 0) {
-        const hipError_t e = hipMemcpyAsync(out, buf, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) rc = fail(std::string("smgpu_quality_geometry_field: ") + hipGetErrorString(e));
-    }
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    if (rc == 0 && es != hipSuccess) rc = fail(std::string("smgpu_quality_geometry_field: ") + hipGetErrorString(es));
-    (void)hipFree(buf);
-    return rc;
-}
-
-// ---- the motion criteria (kernels_quality_motion.hpp, DESIGN.md "Mesh quality", 10.7) ---------------------------------------
-static int qualityMotionEnsure(smgpu_handle* h) {
-    if (qualityEnsure(h)) return 1;
-    if (h->qmOut) return 0;
-    const size_t nFB = (size_t)std::max(1, qualityGrid(h->mv.nFaces));
-    hipError_t e = hipMalloc((void**)&h->qmFacePart, sizeof(QMFace) * nFB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qmOut, sizeof(smgpu_quality_motion));
-    if (e != hipSuccess) {
-        for (void** p : {(void**)&h->qmFacePart, (void**)&h->qmOut})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        return fail(std::string("mesh quality: device memory for the motion criteria: ") + hipGetErrorString(e));
-    }
-    return 0;
-}
-// geometry of the current points (uncounted, as runQuality), the face pass and the final reduction into h->qmOut.
-// o[4]: optional per-face outputs faceTetQuality, faceBaseTetQuality, faceTwist, faceTriangleTwist.
-static int runQualityMotion(smgpu_handle* h, const smgpu_quality_motion_params* p, double* const* o) {
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityMotionEnsure(h)) return 1;
-    const MeshView& m = h->mv;
-    if (qualityGeometry(h)) return 1;
-    const smgpu_quality_motion_params prm = p ? *p : smgpu_quality_motion_params{1e-15, 0.02, -1.0};
-    // k = 8 / (9 sqrt 3) is the host's double, as the contract says: the kernel takes it as an argument
-    const QualityMotionThresholds thr{prm.tetThreshold, prm.twistThreshold, prm.triangleTwistThreshold, 8.0 / (9.0 * std::sqrt(3.0))};
-    const int nFB = qualityGrid(m.nFaces);
-    const State& s = h->st;
-    if (nFB > 0)
-        hipLaunchKernelGGL(k_quality_motion_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.cellCtr, h->qOwn, h->qNei,
-                           thr, h->qmFacePart, o[0], o[1], o[2], o[3]);
-    hipLaunchKernelGGL(k_quality_motion_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qmFacePart, nFB, m.nFaces, h->qmOut);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return qualityField(h, kQualityGeomFields, "smgpu_quality_geometry_field", name, out, n,
+                        [&](double** o) { return runQualityGeom(h, nullptr, nullptr, QCoupling<false>{}, o); });
 }
 
 int smgpu_mesh_quality_motion(smgpu_handle* h, const smgpu_quality_motion_params* p, smgpu_quality_motion* out) {
     if (!h || !out) return fail("null argument");
-    double* const none[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (runQualityMotion(h, p, none)) return 1;
-    HIP_OK(hipMemcpyAsync(out, h->qmOut, sizeof(smgpu_quality_motion), hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
-    return 0;
+    if (runQualityMotion(h, nullptr, p, QCoupling<false>{}, kQualityNoFields)) return 1;
+    return qualityCopyOut(h, out, h->qmOut);
 }
-
 int smgpu_quality_motion_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
     if (!h || !name || !n) return fail("null argument");
     if (h->haloOn) return fail(kQualityHaloRefusal);
-    static const char* const names[4] = {"faceTetQuality", "faceBaseTetQuality", "faceTwist", "faceTriangleTwist"};
-    int which = -1;
-    for (int i = 0; i < 4; ++i)
-        if (std::strcmp(name, names[i]) == 0) which = i;
-    if (which < 0)
-        return fail(std::string("unknown quality motion field ") + name + " (faceTetQuality, faceBaseTetQuality, faceTwist, faceTriangleTwist)");
-    const int64_t cnt = h->mv.nFaces;
-    *n = cnt;
-    if (!out) return 0;
-    HIP_OK(hipSetDevice(h->device));
-    double* buf = nullptr;   // transient: one field's worth for this call only
-    HIP_OK(hipMalloc((void**)&buf, sizeof(double) * (size_t)std::max<int64_t>(1, cnt)));
-    double* o[4] = {nullptr, nullptr, nullptr, nullptr};
-    o[which] = buf;
-    int rc = runQualityMotion(h, nullptr, o);
-    if (rc == 0 && cnt > 0) {
-        const hipError_t e = hipMemcpyAsync(out, buf, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) rc = fail(std::string("smgpu_quality_motion_field: ") + hipGetErrorString(e));
-    }
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    if (rc == 0 && es != hipSuccess) rc = fail(std::string("smgpu_quality_motion_field: ") + hipGetErrorString(es));
-    (void)hipFree(buf);
-    return rc;
+    return qualityField(h, kQualityMotionFields, "smgpu_quality_motion_field", name, out, n,
+                        [&](double** o) { return runQualityMotion(h, nullptr, nullptr, QCoupling<false>{}, o); });
 }
 
-// ---- the coupled report of a sub-domain (DESIGN.md "Mesh quality", 10.4) ----------------------------------------------------
+// ---- the coupled reports of a sub-domain (DESIGN.md "Mesh quality", 10.4 and 10.8) -----------------------------------------
 int smgpu_quality_coupled_pack(smgpu_handle* h, const smgpu_quality_coupling* c, void* sendCc, int64_t* nProcFaces) {
     if (!h || !c) return fail("null argument");
     if (h->iterOpen) return fail("smgpu_quality_coupled_pack: not between smgpu_iter_begin and smgpu_iter_end");
@@ -3608,60 +3638,21 @@ int smgpu_quality_coupled_pack(smgpu_handle* h, const smgpu_quality_coupling* c,
     return 0;
 }
 
-// the face pass with processor faces, the cell pass and the per-rank record into h->qPartOut, on the geometry of the last pack
-static int runQualityCoupled(smgpu_handle* h, const char* api, const smgpu_quality_params* p, const void* recvCc, double* outNO, double* outSkew,
-                             double* outV, double* outOpen, double* outAR) {
-    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
-    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
-        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
-    if (h->qNProc > 0 && !recvCc) return fail(std::string(api) + ": null recvCc");
-    HIP_OK(hipSetDevice(h->device));
-    const MeshView& m = h->mv;
-    const QualityThresholds thr = qualityThresholds(p);
-    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-    const State& s = h->st;
-    if (nFB > 0)
-        hipLaunchKernelGGL(k_quality_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qOwn, h->qNei,
-                           h->qSlot, (const double*)recvCc, thr, h->qFacePart, outNO, outSkew);
-    if (nCB > 0)
-        hipLaunchKernelGGL(k_quality_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qCellPart, outV, outOpen, outAR);
-    hipLaunchKernelGGL(k_quality_part_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qFacePart, nFB, h->qCellPart, nCB, m.nCells,
-                       m.nFaces - h->qNotCounted, m.nInternalFaces + h->qCountedProc, h->qPartOut);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
 int smgpu_quality_coupled_report(smgpu_handle* h, const smgpu_quality_params* p, const void* recvCc, smgpu_quality_part* out) {
     if (!h || !out) return fail("null argument");
-    if (runQualityCoupled(h, "smgpu_quality_coupled_report", p, recvCc, nullptr, nullptr, nullptr, nullptr, nullptr)) return 1;
-    HIP_OK(hipMemcpyAsync(out, h->qPartOut, sizeof(smgpu_quality_part), hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
-    return 0;
+    if (runQuality(h, "smgpu_quality_coupled_report", p, qualityCoupling(h, recvCc, nullptr), kQualityNoFields)) return 1;
+    return qualityCopyOut(h, out, h->qPartOut);
 }
-
 int smgpu_quality_coupled_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n) {
     if (!h || !name || !n) return fail("null argument");
-    return qualityField(h, "smgpu_quality_coupled_field", name, out, n, [&](double** o) {
-        return runQualityCoupled(h, "smgpu_quality_coupled_field", nullptr, recvCc, o[0], o[1], o[2], o[3], o[4]);
-    });
-}
-
-// ---- the -allGeometry checks and the motion criteria of a sub-domain (kernels_quality_coupled.hpp, DESIGN.md "Mesh quality", 10.8)
-static int qualityCoupledReady(smgpu_handle* h, const char* api, const void* recvCc) {
-    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
-    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
-        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
-    if (h->qNProc > 0 && !recvCc) return fail(std::string(api) + ": null recvCc");
-    return 0;
+    const char* api = "smgpu_quality_coupled_field";
+    return qualityField(h, kQualityFields, api, name, out, n,
+                        [&](double** o) { return runQuality(h, api, nullptr, qualityCoupling(h, recvCc, nullptr), o); });
 }
 
 int smgpu_quality_coupled_pack_volumes(smgpu_handle* h, void* sendVc, int64_t* nProcFaces) {
     if (!h) return fail("null argument");
-    const char* api = "smgpu_quality_coupled_pack_volumes";
-    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
-    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
-        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
-    if (h->qNProc > 0 && !sendVc) return fail(std::string(api) + ": null sendVc");
+    if (qualityCoupledReady(h, "smgpu_quality_coupled_pack_volumes", sendVc, "sendVc")) return 1;
     HIP_OK(hipSetDevice(h->device));
     if (qualityGeomEnsure(h)) return 1;
     if (!h->qgPartOut) HIP_OK(hipMalloc((void**)&h->qgPartOut, sizeof(smgpu_quality_geometry_part)));
@@ -3680,131 +3671,53 @@ int smgpu_quality_coupled_pack_volumes(smgpu_handle* h, void* sendVc, int64_t* n
     return 0;
 }
 
-// the determinant pass, the face pass with processor faces and the per-rank record into h->qgPartOut, on the geometry of the last
-// pack and the volumes of the last pack_volumes.  o[5] as runQualityGeom.
-static int runQualityGeomCoupled(smgpu_handle* h, const char* api, const smgpu_quality_geometry_params* p, const void* recvCc, const void* recvVc,
-                                 double* const* o) {
-    if (qualityCoupledReady(h, api, recvCc)) return 1;
-    if (!h->qgPartOut || h->qVolEpoch != h->qEpoch || h->qVolCoupling != h->qCoupling)
-        return fail(std::string(api) + ": call smgpu_quality_coupled_pack_volumes after smgpu_quality_coupled_pack first");
-    if (h->qNProc > 0 && !recvVc) return fail(std::string(api) + ": null recvVc");
-    HIP_OK(hipSetDevice(h->device));
-    const MeshView& m = h->mv;
-    const smgpu_quality_geometry_params prm = p ? *p : smgpu_quality_geometry_params{10.0, 0.8, 0.05, 0.01, 0.001};
-    const QualityGeomThresholds thr{std::sin(prm.concaveThreshold * (SMGPU_PI / 180.0)), prm.flatnessThreshold, prm.weightThreshold,
-                                    prm.volRatioThreshold, prm.determinantThreshold};
-    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-    const State& s = h->st;
-    if (nCB > 0)
-        hipLaunchKernelGGL(k_quality_geom_cells_coupled, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fArea, h->qSlot, thr, h->qgCellPart, o[4]);
-    if (nFB > 0)
-        hipLaunchKernelGGL(k_quality_geom_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qgVol,
-                           h->qOwn, h->qNei, h->qSlot, (const double*)recvCc, (const double*)recvVc, thr, h->qgFacePart, o[0], o[1], o[2], o[3]);
-    hipLaunchKernelGGL(k_quality_geom_part_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qgFacePart, nFB, h->qgCellPart, nCB, m.nCells,
-                       m.nFaces - h->qNotCounted, m.nInternalFaces + h->qCountedProc, h->qgPartOut);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
 int smgpu_quality_coupled_geometry_report(smgpu_handle* h, const smgpu_quality_geometry_params* p, const void* recvCc, const void* recvVc,
                                           smgpu_quality_geometry_part* out) {
     if (!h || !out) return fail("null argument");
-    double* const none[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (runQualityGeomCoupled(h, "smgpu_quality_coupled_geometry_report", p, recvCc, recvVc, none)) return 1;
-    HIP_OK(hipMemcpyAsync(out, h->qgPartOut, sizeof(smgpu_quality_geometry_part), hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
-    return 0;
+    if (runQualityGeom(h, "smgpu_quality_coupled_geometry_report", p, qualityCoupling(h, recvCc, recvVc), kQualityNoFields)) return 1;
+    return qualityCopyOut(h, out, h->qgPartOut);
 }
-
-// one per-element field of the two coupled reports: `run(o)` launches the passes with the outputs o[NF], o[which] a buffer
-// allocated for this call (outside deviceBytes, as qualityField's)
-extern "C++" {
-template <int NF, class Run>
-static int qualityCoupledField(smgpu_handle* h, const char* api, int which, int64_t cnt, double* out, Run run) {
-    HIP_OK(hipSetDevice(h->device));
-    double* buf = nullptr;   // transient: one field's worth for this call only
-    HIP_OK(hipMalloc((void**)&buf, sizeof(double) * (size_t)std::max<int64_t>(1, cnt)));
-    double* o[NF];
-    for (int i = 0; i < NF; ++i) o[i] = nullptr;
-    o[which] = buf;
-    int rc = run(o);
-    if (rc == 0 && cnt > 0) {
-        const hipError_t e = hipMemcpyAsync(out, buf, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) rc = fail(std::string(api) + ": " + hipGetErrorString(e));
-    }
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    if (rc == 0 && es != hipSuccess) rc = fail(std::string(api) + ": " + hipGetErrorString(es));
-    (void)hipFree(buf);
-    return rc;
-}
-}  // extern "C++"
-
 int smgpu_quality_coupled_geometry_field(smgpu_handle* h, const char* name, const void* recvCc, const void* recvVc, double* out, int64_t* n) {
     if (!h || !name || !n) return fail("null argument");
-    static const char* const names[5] = {"faceConcavity", "faceFlatness", "faceWeight", "faceVolumeRatio", "cellDeterminant"};
-    int which = -1;
-    for (int i = 0; i < 5; ++i)
-        if (std::strcmp(name, names[i]) == 0) which = i;
-    if (which < 0)
-        return fail(std::string("unknown quality geometry field ") + name + " (faceConcavity, faceFlatness, faceWeight, faceVolumeRatio, cellDeterminant)");
-    const int64_t cnt = which == 4 ? h->mv.nCells : h->mv.nFaces;
-    *n = cnt;
-    if (!out) return 0;
     const char* api = "smgpu_quality_coupled_geometry_field";
-    return qualityCoupledField<5>(h, api, which, cnt, out, [&](double** o) { return runQualityGeomCoupled(h, api, nullptr, recvCc, recvVc, o); });
-}
-
-// the face pass with processor faces and the per-rank record into h->qmPartOut, on the geometry of the last pack.  o[4] as runQualityMotion.
-static int runQualityMotionCoupled(smgpu_handle* h, const char* api, const smgpu_quality_motion_params* p, const void* recvCc, double* const* o) {
-    if (qualityCoupledReady(h, api, recvCc)) return 1;
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityMotionEnsure(h)) return 1;
-    if (!h->qmPartOut) HIP_OK(hipMalloc((void**)&h->qmPartOut, sizeof(smgpu_quality_motion_part)));
-    const MeshView& m = h->mv;
-    const smgpu_quality_motion_params prm = p ? *p : smgpu_quality_motion_params{1e-15, 0.02, -1.0};
-    const QualityMotionThresholds thr{prm.tetThreshold, prm.twistThreshold, prm.triangleTwistThreshold, 8.0 / (9.0 * std::sqrt(3.0))};
-    const int nFB = qualityGrid(m.nFaces);
-    const State& s = h->st;
-    if (nFB > 0)
-        hipLaunchKernelGGL(k_quality_motion_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.cellCtr, h->qOwn,
-                           h->qNei, h->qSlot, (const double*)recvCc, thr, h->qmFacePart, o[0], o[1], o[2], o[3]);
-    hipLaunchKernelGGL(k_quality_motion_part_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qmFacePart, nFB, m.nFaces - h->qNotCounted,
-                       h->qmPartOut);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return qualityField(h, kQualityGeomFields, api, name, out, n,
+                        [&](double** o) { return runQualityGeom(h, api, nullptr, qualityCoupling(h, recvCc, recvVc), o); });
 }
 
 int smgpu_quality_coupled_motion_report(smgpu_handle* h, const smgpu_quality_motion_params* p, const void* recvCc, smgpu_quality_motion_part* out) {
     if (!h || !out) return fail("null argument");
-    double* const none[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (runQualityMotionCoupled(h, "smgpu_quality_coupled_motion_report", p, recvCc, none)) return 1;
-    HIP_OK(hipMemcpyAsync(out, h->qmPartOut, sizeof(smgpu_quality_motion_part), hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
-    return 0;
+    if (runQualityMotion(h, "smgpu_quality_coupled_motion_report", p, qualityCoupling(h, recvCc, nullptr), kQualityNoFields)) return 1;
+    return qualityCopyOut(h, out, h->qmPartOut);
 }
-
 int smgpu_quality_coupled_motion_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n) {
     if (!h || !name || !n) return fail("null argument");
-    static const char* const names[4] = {"faceTetQuality", "faceBaseTetQuality", "faceTwist", "faceTriangleTwist"};
-    int which = -1;
-    for (int i = 0; i < 4; ++i)
-        if (std::strcmp(name, names[i]) == 0) which = i;
-    if (which < 0)
-        return fail(std::string("unknown quality motion field ") + name + " (faceTetQuality, faceBaseTetQuality, faceTwist, faceTriangleTwist)");
-    const int64_t cnt = h->mv.nFaces;
-    *n = cnt;
-    if (!out) return 0;
     const char* api = "smgpu_quality_coupled_motion_field";
-    return qualityCoupledField<4>(h, api, which, cnt, out, [&](double** o) { return runQualityMotionCoupled(h, api, nullptr, recvCc, o); });
+    return qualityField(h, kQualityMotionFields, api, name, out, n,
+                        [&](double** o) { return runQualityMotion(h, api, nullptr, qualityCoupling(h, recvCc, nullptr), o); });
 }
 
 // ---- the failing elements as sets (DESIGN.md "Mesh quality", 10.5) --------------------------------------------------------
-// `flags(mask, cnt)` launches the face flag pass (mask[0, F), cnt rows of the face sets) and the cell flag pass (mask[F, F + C),
-// cnt + 4 * nFB); then the scan, one copy of the counts, and when ids fit the scatter and one copy of the ids.  Every buffer is
-// this call's own (outside deviceBytes, as the field buffers).
+// The face flag pass (mask[0, F), cnt rows of the face sets) and the cell flag pass (mask[F, F + C), cnt + 4 * nFB); then the scan,
+// one copy of the counts, and when ids fit the scatter and one copy of the ids.  Every buffer is this call's own (outside
+// deviceBytes, as the field buffers).
 extern "C++" {
-template <class Flags>
-static int qualitySets(smgpu_handle* h, const char* api, int64_t counts[7], int32_t* ids, int64_t cap, Flags flags) {
+template <bool Coupled>
+static int qualitySets(smgpu_handle* h, const char* api, const smgpu_quality_params* p, const QCoupling<Coupled>& cp, int64_t counts[7], int32_t* ids,
+                       int64_t cap) {
+    const QualityThresholds thr = qualityThresholds(p);
+    auto flags = [&](uint8_t* mask, int* cnt) {
+        const MeshView& m = h->mv;
+        const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
+        const State& s = h->st;
+        if (nFB > 0)
+            hipLaunchKernelGGL(k_quality_face_flags<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr,
+                               h->qOwn, h->qNei, cp, thr, mask, cnt);
+        if (nCB > 0)
+            hipLaunchKernelGGL(k_quality_cell_flags, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, mask + m.nFaces,
+                               cnt + (size_t)kQualityFaceSets * nFB);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? 0 : fail(std::string(api) + ": " + hipGetErrorString(e));
+    };
     const MeshView& m = h->mv;
     const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
     const int nCnt = kQualityFaceSets * nFB + kQualityCellSets * nCB;
@@ -3856,44 +3769,15 @@ int smgpu_quality_sets(smgpu_handle* h, const smgpu_quality_params* p, int64_t c
     HIP_OK(hipSetDevice(h->device));
     if (qualityEnsure(h)) return 1;
     if (qualityGeometry(h)) return 1;
-    const MeshView& m = h->mv;
-    const QualityThresholds thr = qualityThresholds(p);
-    return qualitySets(h, "smgpu_quality_sets", counts, ids, cap, [&](uint8_t* mask, int* cnt) {
-        const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-        const State& s = h->st;
-        if (nFB > 0)
-            hipLaunchKernelGGL(k_quality_face_flags, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qOwn,
-                               h->qNei, thr, mask, cnt);
-        if (nCB > 0)
-            hipLaunchKernelGGL(k_quality_cell_flags, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, mask + m.nFaces,
-                               cnt + (size_t)kQualityFaceSets * nFB);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail(std::string("smgpu_quality_sets: ") + hipGetErrorString(e));
-    });
+    return qualitySets(h, "smgpu_quality_sets", p, QCoupling<false>{}, counts, ids, cap);
 }
 
 int smgpu_quality_coupled_sets(smgpu_handle* h, const smgpu_quality_params* p, const void* recvCc, int64_t counts[7], int32_t* ids, int64_t cap) {
     if (!h || !counts) return fail("null argument");
     const char* api = "smgpu_quality_coupled_sets";
-    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
-    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
-        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
-    if (h->qNProc > 0 && !recvCc) return fail(std::string(api) + ": null recvCc");
+    if (qualityCoupledReady(h, api, recvCc)) return 1;
     HIP_OK(hipSetDevice(h->device));
-    const MeshView& m = h->mv;
-    const QualityThresholds thr = qualityThresholds(p);
-    return qualitySets(h, api, counts, ids, cap, [&](uint8_t* mask, int* cnt) {
-        const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-        const State& s = h->st;
-        if (nFB > 0)
-            hipLaunchKernelGGL(k_quality_face_flags_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr,
-                               h->qOwn, h->qNei, h->qSlot, (const double*)recvCc, thr, mask, cnt);
-        if (nCB > 0)
-            hipLaunchKernelGGL(k_quality_cell_flags, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, mask + m.nFaces,
-                               cnt + (size_t)kQualityFaceSets * nFB);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail(std::string(api) + ": " + hipGetErrorString(e));
-    });
+    return qualitySets(h, api, p, qualityCoupling(h, recvCc, nullptr), counts, ids, cap);
 }
 
 // ---- debug / parity access -------------------------------------------------------------------

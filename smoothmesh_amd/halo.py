@@ -712,7 +712,7 @@ class DistributedSmoother:
     def _quality_exchange(self, volumes=False):
         """pack, then every processor patch's owner cell centres to the neighbour and theirs back (one all_to_all_single, staged
         through the host for gloo like _a2a) -> recvCc (device tensor, patch order).  volumes: also pack_volumes, the owner cells'
-        volumes riding a second all_to_all_single of one double per face -> (recvCc, recvVc)"""
+        volumes riding a second all_to_all_single of one double per face -> the tuple (recvCc,) or (recvCc, recvVc)"""
         torch = self.torch
         coupling = self.engine.quality_coupling(self.rank)
         pats = coupling[1]
@@ -724,7 +724,7 @@ class DistributedSmoother:
         recv = self._quality_swap(pats, send, 3)
         if not volumes:
             torch.cuda.synchronize(self.device)
-            return recv
+            return (recv,)
         sendV = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)
         self.engine.quality_coupled_pack_volumes(sendV.data_ptr() if n else 0)
         recvV = self._quality_swap(pats, sendV, 1)
@@ -757,75 +757,61 @@ class DistributedSmoother:
                 pos += m
         return recv
 
-    def mesh_quality(self, **thresholds):
-        """Quality report of the whole decomposed mesh at the current points, identical on every rank (smoothmesh_amd/quality.py,
-        DESIGN.md 10.4): paired-patch exchange of the processor faces' cell centres, this rank's record, an all-gather of the
-        records and combine_quality.  Ids are global where every sub-domain carries cell and face addressing.  A collective:
-        every rank calls it, between iterations."""
-        from .quality import QUALITY_DEFAULTS, combine_quality
-        recv = self._quality_exchange()
-        part = self.engine.quality_coupled_report(recv.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds})
+    def _quality_report(self, kind, thresholds):
+        """the report of one kind (quality.QUALITY_KINDS) of the whole decomposed mesh at the current points, identical on every
+        rank: the paired-patch exchange, this rank's record, an all-gather of the records with only their winning ids mapped to
+        global ones (not the addressing), and the kind's combine.  A collective: every rank calls it, between iterations."""
+        from .quality import QUALITY_KINDS
+        k = QUALITY_KINDS[kind]
+        recv = self._quality_exchange(volumes=k.volumes)
+        part = getattr(self.engine, k.report)(*(t.data_ptr() for t in recv), **{**k.defaults, **thresholds})
         cp, fp = self.sub.cellProcAddressing, self.sub.faceProcAddressing
-        # only the three ids of this record travel, not the addressing
-        cmap = {part["minVolumeCell"]: int(cp[part["minVolumeCell"]])} if cp is not None and part["nCells"] else ({} if cp is not None else None)
-        fmap = None
-        if fp is not None:
-            fmap = {k: int(fp[k]) for k in (part["maxNonOrthFace"], part["maxSkewFace"]) if k >= 0}
+        cmap = None if cp is None else {part[i]: int(cp[part[i]]) for i in k.cellIds if part[i] >= 0}
+        fmap = None if fp is None else {part[i]: int(fp[part[i]]) for i in k.faceIds if part[i] >= 0}
         allv = [None] * self.world
         self.dist.all_gather_object(allv, (part, cmap, fmap))
-        return combine_quality([a[0] for a in allv], [a[1] for a in allv], [a[2] for a in allv])
+        return k.combine([a[0] for a in allv], [a[1] for a in allv], [a[2] for a in allv])
+
+    def _quality_field(self, kind, name):
+        """this rank's per-element field of one kind; processor faces carry their values on both sides.  A collective (the exchange
+        of _quality_report)."""
+        from .quality import QUALITY_KINDS
+        k = QUALITY_KINDS[kind]
+        return getattr(self.engine, k.field)(name, *(t.data_ptr() for t in self._quality_exchange(volumes=k.volumes)))
+
+    def mesh_quality(self, **thresholds):
+        """Quality report of the whole decomposed mesh, identical on every rank; ids are global where every
+        sub-domain carries addressing.  A collective: every rank calls it, between iterations."""
+        return self._quality_report("quality", thresholds)
 
     def quality_field(self, name):
-        """this rank's per-element quality field (engine.QUALITY_FIELDS); processor faces carry their values on both sides.
-        A collective (the exchange of mesh_quality)."""
-        recv = self._quality_exchange()
-        return self.engine.quality_coupled_field(name, recv.data_ptr())
+        """this rank's field of engine.QUALITY_FIELDS.  A collective: every rank calls it."""
+        return self._quality_field("quality", name)
 
     def quality_sets(self, **thresholds):
         """this rank's failing elements as sets: {name: local ids}; a processor face is a member only on the
         lower rank.  A collective (the exchange of mesh_quality); the sets themselves stay on their rank."""
         from .quality import QUALITY_DEFAULTS
-        recv = self._quality_exchange()
+        recv, = self._quality_exchange()
         return self.engine.quality_coupled_sets(recv.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds})
 
-    def _gather_parts(self, part, cellKeys, faceKeys):
-        """all-gather of this rank's record with only its winning ids mapped to global ones -> (parts, cellIds, faceIds) for a combine"""
-        cp, fp = self.sub.cellProcAddressing, self.sub.faceProcAddressing
-        cmap = None if cp is None else {part[k]: int(cp[part[k]]) for k in cellKeys if part[k] >= 0}
-        fmap = None if fp is None else {part[k]: int(fp[part[k]]) for k in faceKeys if part[k] >= 0}
-        allv = [None] * self.world
-        self.dist.all_gather_object(allv, (part, cmap, fmap))
-        return [a[0] for a in allv], [a[1] for a in allv], [a[2] for a in allv]
-
     def mesh_quality_geometry(self, **thresholds):
-        """The -allGeometry report of the whole decomposed mesh at the current points, identical on every rank: the
-        exchange of mesh_quality plus the owner cells' volumes, this rank's record, an all-gather and combine_quality_geometry.
-        A collective: every rank calls it, between iterations."""
-        from .quality import GEOMETRY_DEFAULTS, combine_quality_geometry
-        recv, recvV = self._quality_exchange(volumes=True)
-        part = self.engine.quality_coupled_geometry_report(recv.data_ptr(), recvV.data_ptr(), **{**GEOMETRY_DEFAULTS, **thresholds})
-        return combine_quality_geometry(*self._gather_parts(part, ("minDeterminantCell",), (
-            "maxConcaveFace", "minFlatnessFace", "minFaceWeightFace", "minVolRatioFace")))
+        """The -allGeometry report of the whole decomposed mesh, identical on every rank.  A collective: every rank
+        calls it, between iterations."""
+        return self._quality_report("geometry", thresholds)
 
     def quality_geometry_field(self, name):
-        """this rank's per-element field (engine.QUALITY_GEOMETRY_FIELDS); processor faces carry their values on both sides.
-        A collective (the exchange of mesh_quality_geometry)."""
-        recv, recvV = self._quality_exchange(volumes=True)
-        return self.engine.quality_coupled_geometry_field(name, recv.data_ptr(), recvV.data_ptr())
+        """this rank's field of engine.QUALITY_GEOMETRY_FIELDS.  A collective: every rank calls it."""
+        return self._quality_field("geometry", name)
 
     def mesh_quality_motion(self, **thresholds):
-        """The motion criteria of the whole decomposed mesh at the current points, identical on every rank.
-        A collective: every rank calls it, between iterations."""
-        from .quality import MOTION_DEFAULTS, combine_quality_motion
-        recv = self._quality_exchange()
-        part = self.engine.quality_coupled_motion_report(recv.data_ptr(), **{**MOTION_DEFAULTS, **thresholds})
-        return combine_quality_motion(*self._gather_parts(part, (), ("minTetFace", "minBaseTetFace", "minTwistFace", "minTriangleTwistFace")))
+        """The motion criteria of the whole decomposed mesh, identical on every rank.  A collective: every rank
+        calls it, between iterations."""
+        return self._quality_report("motion", thresholds)
 
     def quality_motion_field(self, name):
-        """this rank's per-face field (engine.QUALITY_MOTION_FIELDS); processor faces carry their values on both sides.
-        A collective (the exchange of mesh_quality)."""
-        recv = self._quality_exchange()
-        return self.engine.quality_coupled_motion_field(name, recv.data_ptr())
+        """this rank's field of engine.QUALITY_MOTION_FIELDS.  A collective: every rank calls it."""
+        return self._quality_field("motion", name)
 
 
 class LocalMultiSmoother:
@@ -940,40 +926,44 @@ class LocalMultiSmoother:
     def get_points(self):
         return [st.eng.get_points() for st in self.states]
 
+    # The reports of the decomposed mesh at the current points (smoothmesh_amd/quality.py): the cell
+    # centres (and volumes) of the processor faces move between the engines' buffers by device-side copies.  Ids are global where
+    # the sub-domains carry cell and face addressing; fields and sets come as one entry per rank, processor faces carrying their
+    # field values on both sides and set membership on the lower rank.  Between iterations only; the loop is left as it was.
+    def _engines(self):
+        return [st.eng for st in self.states]
+
     def mesh_quality(self, **thresholds):
-        """Quality report of the decomposed mesh at the current points (smoothmesh_amd/quality.py): the cell
-        centres of the processor faces move between the engines' buffers by device-side copies.  Ids are global where the
-        sub-domains carry cell and face addressing.  Between iterations only; the loop is left as it was."""
+        """Quality report of the decomposed mesh at the current points"""
         from .quality import local_quality
-        return local_quality([st.eng for st in self.states], self.subs, self.device, thresholds)
+        return local_quality(self._engines(), self.subs, self.device, thresholds)
 
     def quality_field(self, name):
-        """[per-rank array] of a quality field (engine.QUALITY_FIELDS); processor faces carry their values on both sides"""
+        """[per-rank array] of a field of engine.QUALITY_FIELDS"""
         from .quality import local_quality_field
-        return local_quality_field([st.eng for st in self.states], name, self.device)
+        return local_quality_field(self._engines(), name, self.device)
 
     def quality_sets(self, **thresholds):
-        """[per-rank {name: local ids}] of the failing elements; a processor face is a member only on the lower
-        rank.  Between iterations only; the loop is left as it was."""
+        """[per-rank {name: local ids}] of the failing elements"""
         from .quality import local_quality_sets
-        return local_quality_sets([st.eng for st in self.states], self.device, thresholds)
+        return local_quality_sets(self._engines(), self.device, thresholds)
 
     def mesh_quality_geometry(self, **thresholds):
-        """The -allGeometry report of the decomposed mesh at the current points (smoothmesh_amd/quality.py)"""
+        """The -allGeometry report of the decomposed mesh at the current points"""
         from .quality import local_quality_geometry
-        return local_quality_geometry([st.eng for st in self.states], self.subs, self.device, thresholds)
+        return local_quality_geometry(self._engines(), self.subs, self.device, thresholds)
 
     def quality_geometry_field(self, name):
-        """[per-rank array] of a field of engine.QUALITY_GEOMETRY_FIELDS; processor faces carry their values on both sides"""
+        """[per-rank array] of a field of engine.QUALITY_GEOMETRY_FIELDS"""
         from .quality import local_quality_geometry_field
-        return local_quality_geometry_field([st.eng for st in self.states], name, self.device)
+        return local_quality_geometry_field(self._engines(), name, self.device)
 
     def mesh_quality_motion(self, **thresholds):
-        """The motion criteria of the decomposed mesh at the current points (smoothmesh_amd/quality.py)"""
+        """The motion criteria of the decomposed mesh at the current points"""
         from .quality import local_quality_motion
-        return local_quality_motion([st.eng for st in self.states], self.subs, self.device, thresholds)
+        return local_quality_motion(self._engines(), self.subs, self.device, thresholds)
 
     def quality_motion_field(self, name):
-        """[per-rank array] of a field of engine.QUALITY_MOTION_FIELDS; processor faces carry their values on both sides"""
+        """[per-rank array] of a field of engine.QUALITY_MOTION_FIELDS"""
         from .quality import local_quality_motion_field
-        return local_quality_motion_field([st.eng for st in self.states], name, self.device)
+        return local_quality_motion_field(self._engines(), name, self.device)

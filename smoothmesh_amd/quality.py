@@ -234,77 +234,79 @@ def _all_ids(subs):
     return [i[0] for i in ids], [i[1] for i in ids]
 
 
-def local_quality(engines, subs, torch_device, thresholds):
+@dataclass(frozen=True)
+class QualityKind:
+    """one report kind: its default thresholds, whether the owner cells' volumes are exchanged too, the engine's coupled report
+    and field methods, the combine of the per-rank records and the record's winning cell / face ids"""
+    defaults: dict
+    volumes: bool
+    report: str
+    field: str
+    combine: object
+    cellIds: tuple
+    faceIds: tuple
+
+
+QUALITY_KINDS = dict(
+    quality=QualityKind(QUALITY_DEFAULTS, False, "quality_coupled_report", "quality_coupled_field", combine_quality,
+                        ("minVolumeCell",), ("maxNonOrthFace", "maxSkewFace")),
+    geometry=QualityKind(GEOMETRY_DEFAULTS, True, "quality_coupled_geometry_report", "quality_coupled_geometry_field", combine_quality_geometry,
+                         ("minDeterminantCell",), ("maxConcaveFace", "minFlatnessFace", "minFaceWeightFace", "minVolRatioFace")),
+    motion=QualityKind(MOTION_DEFAULTS, False, "quality_coupled_motion_report", "quality_coupled_motion_field", combine_quality_motion,
+                       (), ("minTetFace", "minBaseTetFace", "minTwistFace", "minTriangleTwistFace")))
+
+
+def _local(engines, torch_device, volumes, call):
+    """the exchange between the engines of one process, then [call(engine, recvCc pointer[, recvVc pointer])] in rank order"""
     couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
-    recv = local_exchange(engines, couplings, torch_device)
-    parts = [e.quality_coupled_report(t.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds}) for e, t in zip(engines, recv)]
-    return combine_quality(parts, *_all_ids(subs))
+    recv = local_exchange(engines, couplings, torch_device, volumes=volumes)
+    bufs = zip(*recv) if volumes else ((t,) for t in recv)
+    return [call(e, *(t.data_ptr() for t in b)) for e, b in zip(engines, bufs)]
+
+
+def _local_report(kind, engines, subs, torch_device, thresholds):
+    k = QUALITY_KINDS[kind]
+    parts = _local(engines, torch_device, k.volumes, lambda e, *recv: getattr(e, k.report)(*recv, **{**k.defaults, **thresholds}))
+    return k.combine(parts, *_all_ids(subs))
+
+
+def _local_field(kind, engines, name, torch_device):
+    k = QUALITY_KINDS[kind]
+    return _local(engines, torch_device, k.volumes, lambda e, *recv: getattr(e, k.field)(name, *recv))
+
+
+def local_quality(engines, subs, torch_device, thresholds):
+    return _local_report("quality", engines, subs, torch_device, thresholds)
 
 
 def local_quality_geometry(engines, subs, torch_device, thresholds):
-    couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
-    recv, recvV = local_exchange(engines, couplings, torch_device, volumes=True)
-    parts = [e.quality_coupled_geometry_report(t.data_ptr(), v.data_ptr(), **{**GEOMETRY_DEFAULTS, **thresholds})
-             for e, t, v in zip(engines, recv, recvV)]
-    return combine_quality_geometry(parts, *_all_ids(subs))
-
-
-def local_quality_geometry_field(engines, name, torch_device):
-    couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
-    recv, recvV = local_exchange(engines, couplings, torch_device, volumes=True)
-    return [e.quality_coupled_geometry_field(name, t.data_ptr(), v.data_ptr()) for e, t, v in zip(engines, recv, recvV)]
+    return _local_report("geometry", engines, subs, torch_device, thresholds)
 
 
 def local_quality_motion(engines, subs, torch_device, thresholds):
-    couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
-    recv = local_exchange(engines, couplings, torch_device)
-    parts = [e.quality_coupled_motion_report(t.data_ptr(), **{**MOTION_DEFAULTS, **thresholds}) for e, t in zip(engines, recv)]
-    return combine_quality_motion(parts, *_all_ids(subs))
-
-
-def local_quality_motion_field(engines, name, torch_device):
-    couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
-    recv = local_exchange(engines, couplings, torch_device)
-    return [e.quality_coupled_motion_field(name, t.data_ptr()) for e, t in zip(engines, recv)]
+    return _local_report("motion", engines, subs, torch_device, thresholds)
 
 
 def local_quality_field(engines, name, torch_device):
-    couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
-    recv = local_exchange(engines, couplings, torch_device)
-    return [e.quality_coupled_field(name, t.data_ptr()) for e, t in zip(engines, recv)]
+    return _local_field("quality", engines, name, torch_device)
+
+
+def local_quality_geometry_field(engines, name, torch_device):
+    return _local_field("geometry", engines, name, torch_device)
+
+
+def local_quality_motion_field(engines, name, torch_device):
+    return _local_field("motion", engines, name, torch_device)
 
 
 def local_quality_sets(engines, torch_device, thresholds):
     """[per-rank {name: local ids}]: a processor face is a member only on the rank that counts it"""
-    couplings = [e.quality_coupling(r) for r, e in enumerate(engines)]
-    recv = local_exchange(engines, couplings, torch_device)
-    return [e.quality_coupled_sets(t.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds}) for e, t in zip(engines, recv)]
-
-
-def decomposed_mesh_quality(subs, device=0, foam_variant=None, **thresholds) -> DecomposedMeshQuality:
-    """Quality report of a decomposed mesh whose sub-domains (decompose.SubDomain or PolyMesh, rank = position in the list) need
-    no point halo: one plain engine per sub-domain on one device.  Only the processor patches couple them.  Ids are global where
-    the sub-domains carry cell and face addressing (a single sub-domain is the whole mesh: its own ids)."""
-    import torch
-    from .engine import SmoothEngine
-    meshes = [getattr(s, "mesh", s) for s in subs]
-    engines = []
-    try:
-        for m in meshes:
-            e = SmoothEngine(m, device=device)
-            if len(meshes) > 1:
-                e.set_device_share(len(meshes))
-            if foam_variant is not None:
-                e.set_foam_variant(foam_variant)
-            engines.append(e)
-        return local_quality(engines, subs, torch.device("cuda", device), thresholds)
-    finally:
-        for e in engines:
-            e.close()
+    return _local(engines, torch_device, False, lambda e, recv: e.quality_coupled_sets(recv, **{**QUALITY_DEFAULTS, **thresholds}))
 
 
 def _with_engines(subs, device, foam_variant, run):
-    """run(engines, torch device) on one plain engine per sub-domain, as decomposed_mesh_quality builds them"""
+    """run(engines, torch device) on one plain engine per sub-domain (decompose.SubDomain or PolyMesh, rank = position in the
+    list) on one device: sub-domains that need no point halo, coupled by their processor patches only"""
     import torch
     from .engine import SmoothEngine
     meshes = [getattr(s, "mesh", s) for s in subs]
@@ -323,6 +325,12 @@ def _with_engines(subs, device, foam_variant, run):
             e.close()
 
 
+def decomposed_mesh_quality(subs, device=0, foam_variant=None, **thresholds) -> DecomposedMeshQuality:
+    """Quality report of a decomposed mesh whose sub-domains need no point halo (_with_engines).  Ids are global where the
+    sub-domains carry cell and face addressing (a single sub-domain is the whole mesh: its own ids)."""
+    return _with_engines(subs, device, foam_variant, lambda engines, dev: local_quality(engines, subs, dev, thresholds))
+
+
 def decomposed_mesh_quality_geometry(subs, device=0, foam_variant=None, **thresholds) -> DecomposedMeshQualityGeometry:
     """The -allGeometry report of a decomposed mesh: the serial mesh_quality_geometry of the undecomposed mesh.
     Sub-domains, engines and ids as decomposed_mesh_quality."""
@@ -338,22 +346,7 @@ def decomposed_mesh_quality_motion(subs, device=0, foam_variant=None, **threshol
 def decomposed_quality_sets(subs, device=0, foam_variant=None, **thresholds) -> list:
     """The failing elements of decomposed_mesh_quality's report as sets: one {name: local ids} per rank.
     Mapped through cell / face addressing, the ranks' sets are disjoint and their union is the undecomposed mesh's set."""
-    import torch
-    from .engine import SmoothEngine
-    meshes = [getattr(s, "mesh", s) for s in subs]
-    engines = []
-    try:
-        for m in meshes:
-            e = SmoothEngine(m, device=device)
-            if len(meshes) > 1:
-                e.set_device_share(len(meshes))
-            if foam_variant is not None:
-                e.set_foam_variant(foam_variant)
-            engines.append(e)
-        return local_quality_sets(engines, torch.device("cuda", device), thresholds)
-    finally:
-        for e in engines:
-            e.close()
+    return _with_engines(subs, device, foam_variant, lambda engines, dev: local_quality_sets(engines, dev, thresholds))
 
 
 def write_quality_sets(polyMeshDir, location, sets, binary=False):
