@@ -303,6 +303,25 @@ int smgpu_quality_coupled_motion_report(smgpu_handle* h, const smgpu_quality_mot
                                         smgpu_quality_motion_part* out);
 int smgpu_quality_coupled_motion_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n);
 
+/* ---- the findings of the two reports above as sets (DESIGN.md "Mesh quality", 10.9) --------------------------------------
+ * Geometry, counts[5]: concaveFaces, warpedFaces, lowWeightFaces, lowVolRatioFaces (face sets), underdeterminedCells (cell
+ * set); sizes nConcaveFaces, nWarpedFaces, nLowWeightFaces, nLowVolRatioFaces, nUnderdeterminedCells of the report under the same
+ * p.  Motion, counts[4]: lowQualityTetFaces, noBasePointFaces, twistedFaces, lowTriangleTwistFaces (face sets); sizes nLowTetFaces,
+ * nNoBasePointFaces, nLowTwistFaces, nLowTriangleTwistFaces.  Membership is read off the record the report's per-element body
+ * fills, so the sizes are identities.  counts, ids and cap exactly as smgpu_quality_sets: counts always filled; the sets
+ * concatenated in that order, each ascending, into ids when ids != NULL and cap >= sum(counts); a smaller cap is an error (counts
+ * still filled, ids untouched); ids == NULL: counts only.  Ids are local and bitwise repeatable.
+ * Refusals, side effects and state as the matching report: smgpu_mesh_quality_geometry / _motion (serial, refused on a halo
+ * engine) and smgpu_quality_coupled_geometry_report / _motion_report (a sub-domain, on the geometry of the last pack, the geometry
+ * call after pack_volumes; a processor face is a member only on the side with myRank < neighbRank).  The seven-set calls above
+ * are unchanged. */
+int smgpu_quality_geometry_sets(smgpu_handle* h, const smgpu_quality_geometry_params* p, int64_t counts[5], int32_t* ids, int64_t cap);
+int smgpu_quality_motion_sets(smgpu_handle* h, const smgpu_quality_motion_params* p, int64_t counts[4], int32_t* ids, int64_t cap);
+int smgpu_quality_coupled_geometry_sets(smgpu_handle* h, const smgpu_quality_geometry_params* p, const void* recvCc, const void* recvVc,
+                                        int64_t counts[5], int32_t* ids, int64_t cap);
+int smgpu_quality_coupled_motion_sets(smgpu_handle* h, const smgpu_quality_motion_params* p, const void* recvCc,
+                                      int64_t counts[4], int32_t* ids, int64_t cap);
+
 /* Timing: when enabled every kernel launch is bracketed by hipEvents on the handle's stream. */
 int smgpu_enable_timing(smgpu_handle* h, int32_t on);
 int smgpu_get_counters(smgpu_handle* h, smgpu_counters* out);

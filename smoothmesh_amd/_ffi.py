@@ -231,6 +231,12 @@ SYMBOLS = {
     "smgpu_quality_coupled_geometry_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_quality_coupled_motion_report": (C.c_int, [C.c_void_p, C.POINTER(QualityMotionParams), C.c_void_p, C.POINTER(QualityMotionPart)]),
     "smgpu_quality_coupled_motion_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),
+    "smgpu_quality_geometry_sets": (C.c_int, [C.c_void_p, C.POINTER(QualityGeometryParams), C.POINTER(C.c_int64), c_i32p, C.c_int64]),
+    "smgpu_quality_motion_sets": (C.c_int, [C.c_void_p, C.POINTER(QualityMotionParams), C.POINTER(C.c_int64), c_i32p, C.c_int64]),
+    "smgpu_quality_coupled_geometry_sets": (C.c_int, [C.c_void_p, C.POINTER(QualityGeometryParams), C.c_void_p, C.c_void_p,
+                                                      C.POINTER(C.c_int64), c_i32p, C.c_int64]),
+    "smgpu_quality_coupled_motion_sets": (C.c_int, [C.c_void_p, C.POINTER(QualityMotionParams), C.c_void_p, C.POINTER(C.c_int64), c_i32p,
+                                                    C.c_int64]),
     "smgpu_debug_get_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_debug_get_addressing": (C.c_int, [C.c_void_p, C.c_char_p, c_i32p, c_i32p, C.POINTER(C.c_int64)]),
     "smgpu_debug_propose": (C.c_int, [C.c_void_p]),

@@ -7,6 +7,9 @@ the latest time directory by default, else constant; the faces from the newest i
 -writeSets: then the failing elements as OpenFOAM sets into <points instance>/sets, i.e. <time>/polyMesh/sets
 or constant/polyMesh/sets, in every processorN/ with local ids under -parallel; writeFormat and writeCompression from
 system/controlDict.  One "<<Writing" line per written set follows the report (with " in processorN" under -parallel).
+With -allGeometry and / or -meshQuality on a serial case, -writeSets also writes the non-empty sets of those reports (DESIGN.md
+10.9) into the same sets/ directory, their "<<Writing" lines after the seven's: geometry first, then motion.  A decomposed case
+gets them through decomposed_case_quality(..., write_sets=True).
 -allGeometry: the block also carries the five lines of the checks `checkMesh -allGeometry` adds; serial cases only.
 -meshQuality: the block also carries the four lines of the motion criteria, face and base-point tet quality, face twist and triangle
 twist, after those of -allGeometry; serial cases only.
@@ -73,13 +76,13 @@ def _control(case):
             cmp is not None and cmp.group(1) in ("on", "true", "yes", "compressed"))
 
 
-def _write_sets(pts_dir, root, sets, control):
+def _write_sets(pts_dir, root, sets, control, table=None):
     from .polymesh import set_write_compression
-    from .quality import write_quality_sets
+    from .quality import QUALITY_SETS, write_quality_sets
     binary, compressed = control
     set_write_compression(compressed)
     try:
-        return write_quality_sets(pts_dir, os.path.relpath(pts_dir, root), sets, binary)
+        return write_quality_sets(pts_dir, os.path.relpath(pts_dir, root), sets, binary, table or QUALITY_SETS)
     finally:
         set_write_compression(False)
 
@@ -111,20 +114,38 @@ def _read_subs(case, time):
     return procs, t, subs
 
 
-def decomposed_case_quality(case, time=None, device=0, all_geometry=False, mesh_quality=False):
+def decomposed_case_quality(case, time=None, device=0, all_geometry=False, mesh_quality=False, write_sets=False):
     """The reports of a decomposed case, every processorN/ combined: (DecomposedMeshQuality,
     DecomposedMeshQualityGeometry or None, DecomposedMeshQualityMotion or None), which format_report(*q) prints as one block.  The
-    shell spellings -parallel -allGeometry / -meshQuality keep their refusals; this function is the way in."""
-    from .quality import decomposed_mesh_quality, decomposed_mesh_quality_geometry, decomposed_mesh_quality_motion
-    _, _, subs = _read_subs(case, time)
-    return (decomposed_mesh_quality(subs, device=device),
-            decomposed_mesh_quality_geometry(subs, device=device) if all_geometry else None,
-            decomposed_mesh_quality_motion(subs, device=device) if mesh_quality else None)
+    shell spellings -parallel -allGeometry / -meshQuality keep their refusals; this function is the way in.
+    write_sets: also write every processorN/'s sets, local ids, of the reports asked for (the seven, then geometry, then motion:
+    DESIGN.md 10.5, 10.9) into its points instance -> (the triple, [(rank, name, size)] in writing order)."""
+    from . import quality as Q
+    procs, t, subs = _read_subs(case, time)
+    q = (Q.decomposed_mesh_quality(subs, device=device),
+         Q.decomposed_mesh_quality_geometry(subs, device=device) if all_geometry else None,
+         Q.decomposed_mesh_quality_motion(subs, device=device) if mesh_quality else None)
+    if not write_sets:
+        return q
+    control = _control(case)
+    kinds = [(Q.decomposed_quality_sets, Q.QUALITY_SETS)]
+    if all_geometry:
+        kinds.append((Q.decomposed_quality_geometry_sets, Q.QUALITY_GEOMETRY_SETS))
+    if mesh_quality:
+        kinds.append((Q.decomposed_quality_motion_sets, Q.QUALITY_MOTION_SETS))
+    per_kind = [(fn(subs, device=device), table) for fn, table in kinds]
+    written = []
+    for i, (r, d) in enumerate(procs):
+        root = os.path.join(case, d)
+        for ranks, table in per_kind:
+            written += [(r, n, k) for n, k in _write_sets(_instance(root, t, "points"), root, ranks[i], control, table)]
+    return q, written
 
 
 def case_quality(case, parallel=False, time=None, device=0, write_sets=False, all_geometry=False, mesh_quality=False):
     """MeshQuality of the serial case, or DecomposedMeshQuality of its processorN/ sub-domains.  write_sets: also write the
-    failing elements as sets into the points instance (every processorN/ under parallel) -> (quality, [(rank, name, size)]).
+    failing elements as sets into the points instance (every processorN/ under parallel) -> (quality, [(rank, name, size)]);
+    with all_geometry / mesh_quality also the sets of those reports, after the seven.
     all_geometry (serial only): the quality is the pair (MeshQuality, MeshQualityGeometry); mesh_quality (serial only): the triple
     (MeshQuality, MeshQualityGeometry or None, MeshQualityMotion)"""
     if all_geometry and parallel:
@@ -144,7 +165,13 @@ def case_quality(case, parallel=False, time=None, device=0, write_sets=False, al
                 q = (q, e.mesh_quality_geometry())
             if not write_sets:
                 return q
-            written = _write_sets(_instance(case, t, "points"), case, e.quality_sets(), control)
+            from .quality import QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS
+            pts_dir = _instance(case, t, "points")
+            written = _write_sets(pts_dir, case, e.quality_sets(), control)
+            if all_geometry:
+                written += _write_sets(pts_dir, case, e.quality_geometry_sets(), control, QUALITY_GEOMETRY_SETS)
+            if mesh_quality:
+                written += _write_sets(pts_dir, case, e.quality_motion_sets(), control, QUALITY_MOTION_SETS)
             return q, [(None, n, k) for n, k in written]
         finally:
             e.close()
@@ -162,8 +189,9 @@ def case_quality(case, parallel=False, time=None, device=0, write_sets=False, al
 
 def format_written(written):
     """the "<<Writing" lines of -writeSets: (rank or None, name, size) in writing order"""
-    from .quality import format_sets_written
-    return "".join(format_sets_written([(n, k)]).rstrip("\n") + ("" if r is None else f" in processor{r}") + "\n"
+    from .quality import QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS, QUALITY_SETS, format_sets_written
+    table = QUALITY_SETS + QUALITY_GEOMETRY_SETS + QUALITY_MOTION_SETS
+    return "".join(format_sets_written([(n, k)], table).rstrip("\n") + ("" if r is None else f" in processor{r}") + "\n"
                    for r, n, k in written)
 
 
@@ -173,7 +201,8 @@ def main(argv=None):
     ap.add_argument("-case", default=".")
     ap.add_argument("-parallel", action="store_true")
     ap.add_argument("-time", default=None, help="a time, constant or latestTime (default: the latest time, else constant)")
-    ap.add_argument("-writeSets", action="store_true", help="write the failing faces and cells as sets into the points instance")
+    ap.add_argument("-writeSets", action="store_true", help="write the failing faces and cells as sets into the points instance; with -allGeometry / -meshQuality also "
+                    "those reports' sets")
     ap.add_argument("-allGeometry", action="store_true", help="also concavity, flatness, weight, volume ratio, determinant (serial only)")
     ap.add_argument("-meshQuality", action="store_true", help="also face and base-point tet quality, twist, triangle twist (serial only)")
     a = ap.parse_args(argv)

@@ -109,7 +109,7 @@ Options parseArgs(int argc, char** argv) {
                       "       [-minAngle deg] [-maxAngle deg] [-writeInterval n] [-writeFormat ascii|binary] [-device n]\n"
                       "       [-checkQuality b]   (mesh quality report of the initial and the final mesh, serial runs only)\n"
                       "       [-writeSets b]      (with -checkQuality: the final mesh's failing faces and cells as sets in\n"
-                      "        <last written time>/polyMesh/sets)\n"
+                      "        <last written time>/polyMesh/sets; with -allGeometry / -meshQuality also the sets of those reports)\n"
                       "       [-allGeometry b]    (with -checkQuality: also face concavity, flatness, interpolation weight, volume\n"
                       "        ratio and cell determinant, the checks of checkMesh -allGeometry)\n"
                       "       [-meshQuality b]    (with -checkQuality: also face tet quality, base-point tet quality, face twist and\n"
@@ -1300,37 +1300,56 @@ int main(int argc, char** argv) {
 
     if (checkQuality) reportQuality("final mesh");
     // -writeSets: the final mesh's failing elements (include/smgpu.h smgpu_quality_sets) as topoSet files next to
-    // the points just written; the input case is never touched.  Only non-empty sets, as checkMesh.
+    // the points just written; the input case is never touched.  Only non-empty sets, as checkMesh.  With -allGeometry and / or
+    // -meshQuality also the sets of those reports (smgpu_quality_geometry_sets / _motion_sets), after the seven.
     if (writeSets) {
+        struct SetKind { int n, nFace; const char* api; const char* const* name; const char* const* words; };
         static const char* const kSetName[7] = {"nonOrthoFaces", "skewFaces", "wrongOrientedFaces", "zeroAreaFaces", "zeroVolumeCells",
                                                 "nonClosedCells", "highAspectRatioCells"};
         static const char* const kSetWords[7] = {"non-orthogonal faces", "skew faces", "wrongly oriented faces", "zero area faces",
                                                  "zero or negative volume cells", "non-closed cells", "high aspect ratio cells"};
+        static const char* const kGeomSetName[5] = {"concaveFaces", "warpedFaces", "lowWeightFaces", "lowVolRatioFaces", "underdeterminedCells"};
+        static const char* const kGeomSetWords[5] = {"concave faces", "warped faces", "faces with low interpolation weight",
+                                                     "faces with low volume ratio", "under-determined cells"};
+        static const char* const kMotionSetName[4] = {"lowQualityTetFaces", "noBasePointFaces", "twistedFaces", "lowTriangleTwistFaces"};
+        static const char* const kMotionSetWords[4] = {"faces with low quality or negative volume decomposition tets",
+                                                       "faces without a valid tet base point", "twisted faces", "faces with low triangle twist"};
         if (lastWritten.empty()) OUTS("    no mesh was written: no sets written\n");
         else {
             const auto tw = std::chrono::steady_clock::now();
-            // one device call when the sets hold at most nFaces + nCells ids; else again with the size the refused call reported
-            int64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
-            std::vector<int32_t> ids((size_t)K0.mesh.nFaces() + (size_t)K0.mesh.nCells + 1);
-            if (smgpu_quality_sets(K0.h, nullptr, counts, ids.data(), (int64_t)ids.size()) != 0) {
-                int64_t total = 0;
-                for (int64_t c : counts) total += c;
-                if (total <= (int64_t)ids.size()) check(1, "smgpu_quality_sets");
-                ids.resize((size_t)total);
-                check(smgpu_quality_sets(K0.h, nullptr, counts, ids.data(), total), "smgpu_quality_sets");
-            }
             const std::string loc = lastWritten + "/polyMesh/sets", dir = K0.root + "/" + loc;
-            int64_t at = 0;
-            for (int s = 0; s < 7; ++s) {
-                if (counts[s] > 0) {
-                    try {
-                        makeDirs(dir);
-                        writeLabelList(dir + "/" + kSetName[s], loc, kSetName[s], s < 4 ? "faceSet" : "cellSet", counts[s], ids.data() + at, binary, "");
-                    } catch (const std::exception& e) { fatal(e.what()); }
-                    OUT("    <<Writing %lld %s to set %s\n", (long long)counts[s], kSetWords[s], kSetName[s]);
+            std::vector<int32_t> ids((size_t)K0.mesh.nFaces() + (size_t)K0.mesh.nCells + 1);
+            // one device call when the sets hold at most nFaces + nCells ids; else again with the size the refused call reported
+            auto writeKind = [&](const SetKind& k, auto call) {
+                int64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
+                if (call(counts, ids.data(), (int64_t)ids.size()) != 0) {
+                    int64_t total = 0;
+                    for (int64_t c : counts) total += c;
+                    if (total <= (int64_t)ids.size()) check(1, k.api);
+                    ids.resize((size_t)total);
+                    check(call(counts, ids.data(), total), k.api);
                 }
-                at += counts[s];
-            }
+                int64_t at = 0;
+                for (int s = 0; s < k.n; ++s) {
+                    if (counts[s] > 0) {
+                        try {
+                            makeDirs(dir);
+                            writeLabelList(dir + "/" + k.name[s], loc, k.name[s], s < k.nFace ? "faceSet" : "cellSet", counts[s], ids.data() + at, binary,
+                                           "");
+                        } catch (const std::exception& e) { fatal(e.what()); }
+                        OUT("    <<Writing %lld %s to set %s\n", (long long)counts[s], k.words[s], k.name[s]);
+                    }
+                    at += counts[s];
+                }
+            };
+            writeKind(SetKind{7, 4, "smgpu_quality_sets", kSetName, kSetWords},
+                      [&](int64_t* c, int32_t* d, int64_t cap) { return smgpu_quality_sets(K0.h, nullptr, c, d, cap); });
+            if (allGeometry)
+                writeKind(SetKind{5, 4, "smgpu_quality_geometry_sets", kGeomSetName, kGeomSetWords},
+                          [&](int64_t* c, int32_t* d, int64_t cap) { return smgpu_quality_geometry_sets(K0.h, nullptr, c, d, cap); });
+            if (meshQuality)
+                writeKind(SetKind{4, 4, "smgpu_quality_motion_sets", kMotionSetName, kMotionSetWords},
+                          [&](int64_t* c, int32_t* d, int64_t cap) { return smgpu_quality_motion_sets(K0.h, nullptr, c, d, cap); });
             tWrite += secondsSince(tw);
         }
     }

@@ -365,9 +365,10 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_pack(const int* __res
 //      set and the set's offset inside the concatenated output;
 //   3. k_quality_set_scatter: each workgroup walks its 2048 elements in 256-element rounds; a wave ranks its members with a
 //      64-bit ballot, the waves' totals go through LDS in wave order.  Ids come out ascending.
+// qFlagPass, the scan and the scatter also serve the sets of the -allGeometry checks and of the motion criteria (10.9), whose flag
+// passes are in kernels_quality_geom.hpp and kernels_quality_motion.hpp: scan and scatter are templates over the set layout.
 constexpr int kQualityFaceSets = 4;   // nonOrthoFaces, skewFaces, wrongOrientedFaces, zeroAreaFaces
 constexpr int kQualityCellSets = 3;   // zeroVolumeCells, nonClosedCells, highAspectRatioCells
-constexpr int kQualitySets = kQualityFaceSets + kQualityCellSets;
 
 __device__ __forceinline__ unsigned qFaceBits(const QFace& e) {
     return ((e.nSev | e.nErr) ? 1u : 0u) | (e.nSkew ? 2u : 0u) | (e.nWrong ? 4u : 0u) | (e.nZero ? 8u : 0u);
@@ -429,8 +430,11 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_cell_flags(MeshView m
 }
 
 // one workgroup of 1024: exclusive scan of cnt[0, n) into off[0, n] (off[n] = the total), tile by tile in index order; then the
-// seven set sizes: counts[s] = off[rowEnd(s)] - off[rowStart(s)]
+// set sizes: counts[s] = off[rowEnd(s)] - off[rowStart(s)].  <NF, NC>: the set layout, NF face sets over the face workgroups
+// then NC cell sets over the cell workgroups -- <4, 3> for the report of this file, <4, 1> for the -allGeometry checks and
+// <4, 0> for the motion criteria (with NC = 0 there are no cell rows and nCB is 0)
 constexpr int kQualityScanBlock = 1024;
+template <int NF, int NC>
 __global__ void __launch_bounds__(kQualityScanBlock) k_quality_set_scan(const int* __restrict__ cnt, int n, int nFB, int nCB,
                                                                          long long* __restrict__ off, long long* __restrict__ counts) {
     __shared__ long long shW[kQualityScanBlock / 64];
@@ -458,10 +462,10 @@ __global__ void __launch_bounds__(kQualityScanBlock) k_quality_set_scan(const in
     }
     if (threadIdx.x == 0) off[n] = shCarry;
     __syncthreads();
-    if (threadIdx.x < kQualitySets) {
+    if (threadIdx.x < NF + NC) {
         const int s = threadIdx.x;
-        const int b = s < kQualityFaceSets ? s * nFB : kQualityFaceSets * nFB + (s - kQualityFaceSets) * nCB;
-        const int e = b + (s < kQualityFaceSets ? nFB : nCB);
+        const int b = s < NF ? s * nFB : NF * nFB + (s - NF) * nCB;
+        const int e = b + (s < NF ? nFB : nCB);
         counts[s] = off[e] - off[b];
     }
 }
@@ -469,34 +473,37 @@ __global__ void __launch_bounds__(kQualityScanBlock) k_quality_set_scan(const in
 // workgroups [0, nFB) take the face sets of face workgroup b, the rest the cell sets of cell workgroup b - nFB (mask[nFaces + c]).
 // A member's place: the scan's offset of (set, workgroup), plus the members of the earlier rounds, of the earlier waves of this
 // round, and of the lower lanes of its wave.  pos < total always holds (the masks are the ones counted); it is checked anyway.
+// <NF, NC> as k_quality_set_scan; with NC = 0 the grid is the nFB face workgroups and the mask holds nFaces bytes only.
+template <int NF, int NC>
 __global__ void __launch_bounds__(kQualityBlock) k_quality_set_scatter(const uint8_t* __restrict__ mask, int nFaces, int nCells, int nFB, int nCB,
                                                                         const long long* __restrict__ off, int* __restrict__ ids, long long total) {
-    __shared__ int sh[2][kQualityFaceSets][kQualityBlock / 64];
+    static_assert(NC <= NF && NF <= 8, "a cell workgroup uses the face sets' slots; one mask byte per element");
+    __shared__ int sh[2][NF][kQualityBlock / 64];
     const bool faces = (int)blockIdx.x < nFB;
     const int b = faces ? (int)blockIdx.x : (int)blockIdx.x - nFB;
     const int n = faces ? nFaces : nCells;
-    const int ns = faces ? kQualityFaceSets : kQualityCellSets;
+    const int ns = faces ? NF : NC;
     const uint8_t* mk = faces ? mask : mask + nFaces;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    long long run[kQualityFaceSets];
-    for (int s = 0; s < kQualityFaceSets; ++s)
-        run[s] = s < ns ? off[faces ? s * nFB + b : kQualityFaceSets * nFB + s * nCB + b] : 0;
+    long long run[NF];
+    for (int s = 0; s < NF; ++s)
+        run[s] = s < ns ? off[faces ? s * nFB + b : NF * nFB + s * nCB + b] : 0;
     for (int k = 0; k < kQualityPer; ++k) {
         const int i0 = b * (kQualityPer * kQualityBlock) + k * kQualityBlock;
         if (i0 >= n) break;                            // uniform in the workgroup
         const int i = i0 + threadIdx.x;
         const unsigned bits = i < n ? mk[i] : 0u;
         const int buf = k & 1;                         // two LDS buffers: round k + 1 writes while no wave still reads round k's
-        unsigned long long bal[kQualityFaceSets];
+        unsigned long long bal[NF];
 #pragma unroll
-        for (int s = 0; s < kQualityFaceSets; ++s) {
+        for (int s = 0; s < NF; ++s) {
             bal[s] = __ballot((bits >> s) & 1u);
             if (lane == 0) sh[buf][s][w] = __popcll(bal[s]);
         }
         __syncthreads();
 #pragma unroll
-        for (int s = 0; s < kQualityFaceSets; ++s) {
+        for (int s = 0; s < NF; ++s) {
             if (s >= ns) break;
             int before = 0, all = 0;
             for (int v = 0; v < kQualityBlock / 64; ++v) {

@@ -12,6 +12,7 @@
 // k_quality_cell_volumes.  The cell and the face pass stay a serial / coupled pair each, with their own pass loops: sharing their
 // bodies (qPass, qNeighbour, qCellVolume) changed the register allocation and cost 0.6 - 1.5 % of kernel time
 // (profiles/quality/README.md), so they are the functions that were measured.  Keep each pair alike.
+// The findings as sets (smgpu_quality_geometry_sets / _coupled_geometry_sets): the flag passes at the end of this file.
 #pragma once
 #include "kernels_quality.hpp"
 
@@ -363,6 +364,57 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_geom_final(const QGFa
     q.minDeterminant = anyCell ? b.minDet : 0.0; q.sumDeterminant = b.sumDet;
     q.nUnderdeterminedCells = b.nUnder; q.minDeterminantCell = anyCell ? b.minDetId : -1;
     qFinish(q, out);
+}
+
+// ---- the findings as sets (smgpu_quality_geometry_sets / _coupled_geometry_sets, DESIGN.md "Mesh quality", 10.9) ----------------
+// The flag passes of kernels_quality.hpp (qFlagPass: one mask byte per element, member counts per workgroup) over the bodies
+// above, with null field outputs: a record's count members become the mask bits, so a set's size is the report's count by
+// construction.  The sets then go through k_quality_set_scan / _scatter<4, 1>.  nFlat, the flatness denominator, is no set.
+constexpr int kQualityGeomFaceSets = 4;   // concaveFaces, warpedFaces, lowWeightFaces, lowVolRatioFaces
+constexpr int kQualityGeomCellSets = 1;   // underdeterminedCells
+__device__ __forceinline__ unsigned qgFaceBits(const QGFace& e) {
+    return (e.nConcave ? 1u : 0u) | (e.nWarped ? 2u : 0u) | (e.nLowW ? 4u : 0u) | (e.nLowR ? 8u : 0u);
+}
+// Coupled: what k_quality_geom_faces_coupled does to the record of a processor face (its twin, keep alike): weight and ratio
+// again with C_N = recvCc[slot], V_N = recvVc[slot]; no bits where the neighbour rank counts the face
+template <bool Coupled>
+__global__ void __launch_bounds__(kQualityBlock) k_quality_geom_face_flags(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                            const double* __restrict__ fArea, const double* __restrict__ cellCtr,
+                                                                            const double* __restrict__ vol, const int* __restrict__ own,
+                                                                            const int* __restrict__ nei, QCoupling<Coupled> cp,
+                                                                            QualityGeomThresholds thr, uint8_t* __restrict__ mask, int* __restrict__ cnt) {
+    qFlagPass<kQualityGeomFaceSets>(m.nFaces, mask, cnt, [&](int f) {
+        QGFace e = qEmpty<QGFace>();
+        qgFaceOne(m, pts, fCtr, fArea, cellCtr, vol, own, nei, thr, f, e, nullptr, nullptr, nullptr, nullptr);
+        if constexpr (Coupled) {
+            const int sl = f < m.nInternalFaces ? -1 : cp.slot[f - m.nInternalFaces];
+            if (sl >= 0) {
+                const V3 Cf = ldv(fCtr, f), Sf = ldv(fArea, f);
+                const int o = own[f];
+                const double dO = fabs(dot(Sf, Cf - ldv(cellCtr, o))), dN = fabs(dot(Sf, ldv(cp.recvCc, sl & kQualitySlotMask) - Cf));
+                const double w = fmin(dO, dN) / ((dO + dN) + SMGPU_VSMALL);
+                const double vO = vol[o], vN = cp.recvVc[sl & kQualitySlotMask];
+                const double r = fmin(vO, vN) / (fmax(vO, vN) + SMGPU_VSMALL);
+                e.nLowW = (w < thr.weight) ? 1 : 0;
+                e.nLowR = (r < thr.volRatio) ? 1 : 0;
+                if (sl & kQualityNotCounted) e = qEmpty<QGFace>();
+            }
+        }
+        return qgFaceBits(e);
+    });
+}
+// serial: qgCellOne, which also leaves the cell's volume in vol for the face flag pass (launched after this one), as
+// k_quality_geom_cells does; coupled: qgCellOneCoupled over internal and processor faces, the volumes are k_quality_cell_volumes'
+template <bool Coupled>
+__global__ void __launch_bounds__(kQualityBlock) k_quality_geom_cell_flags(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea,
+                                                                            QCoupling<Coupled> cp, QualityGeomThresholds thr, double* __restrict__ vol,
+                                                                            uint8_t* __restrict__ mask, int* __restrict__ cnt) {
+    qFlagPass<kQualityGeomCellSets>(m.nCells, mask, cnt, [&](int c) {
+        QGCell e = qEmpty<QGCell>();
+        if constexpr (Coupled) qgCellOneCoupled(m, fArea, cp.slot, thr, c, e, nullptr);
+        else qgCellOne(m, fCtr, fArea, thr, c, e, vol, nullptr);
+        return e.nUnder ? 1u : 0u;
+    });
 }
 
 }  // namespace smgpu

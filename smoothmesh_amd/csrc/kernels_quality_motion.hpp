@@ -10,6 +10,7 @@
 // processor face takes the internal-face branch of the tets and the twist with the neighbour rank's cell centre.  The serial and
 // the coupled face pass stay a pair, with their own pass loops: one shared body changed the register allocation and cost 2 % of
 // kernel time (profiles/quality/README.md), so they are the functions that were measured.
+// The findings as sets (smgpu_quality_motion_sets / _coupled_motion_sets): the flag pass at the end of this file.
 #pragma once
 #include "kernels_quality.hpp"
 
@@ -287,6 +288,38 @@ __global__ void __launch_bounds__(kQualityBlock) k_quality_motion_final(const QM
     q.minTriangleTwist = anyTw ? a.minTri : 1.0; q.sumTriangleTwist = a.sumTri;
     q.nLowTriangleTwistFaces = a.nLowTri; q.minTriangleTwistFace = anyTw ? a.minTriId : -1;
     qFinish(q, out);
+}
+
+// ---- the findings as sets (smgpu_quality_motion_sets / _coupled_motion_sets, DESIGN.md "Mesh quality", 10.9) --------------------
+// The flag pass of kernels_quality.hpp (qFlagPass) over the bodies above, with null field outputs: a record's count members become
+// the mask bits.  Face sets only: k_quality_set_scan / _scatter<4, 0>.  nTw, the twist denominator, is no set.
+constexpr int kQualityMotionFaceSets = 4;   // lowQualityTetFaces, noBasePointFaces, twistedFaces, lowTriangleTwistFaces
+__device__ __forceinline__ unsigned qmFaceBits(const QMFace& e) {
+    return (e.nLowTet ? 1u : 0u) | (e.nNoBase ? 2u : 0u) | (e.nLowTw ? 4u : 0u) | (e.nLowTri ? 8u : 0u);
+}
+// Coupled: C_N and `internal` of a face as k_quality_motion_faces_coupled selects them (its twin, keep alike); no bits where the
+// neighbour rank counts the face
+template <bool Coupled>
+__global__ void __launch_bounds__(kQualityBlock) k_quality_motion_face_flags(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                              const double* __restrict__ cellCtr, const int* __restrict__ own,
+                                                                              const int* __restrict__ nei, QCoupling<Coupled> cp,
+                                                                              QualityMotionThresholds thr, uint8_t* __restrict__ mask,
+                                                                              int* __restrict__ cnt) {
+    qFlagPass<kQualityMotionFaceSets>(m.nFaces, mask, cnt, [&](int f) {
+        QMFace e = qEmpty<QMFace>();
+        if constexpr (Coupled) {
+            const int sl = f < m.nInternalFaces ? -1 : cp.slot[f - m.nInternalFaces];
+            const double* cnAt = f < m.nInternalFaces ? cellCtr + 3 * (size_t)nei[f]
+                                                      : (sl >= 0 ? cp.recvCc + 3 * (size_t)(sl & kQualitySlotMask) : cellCtr + 3 * (size_t)own[f]);
+            const bool internal = f < m.nInternalFaces || sl >= 0;
+            const V3 CN = internal ? v3(cnAt[0], cnAt[1], cnAt[2]) : v3(0, 0, 0);
+            qmFaceOneCoupled(m, pts, fCtr, ldv(cellCtr, own[f]), internal, CN, thr, f, e, nullptr, nullptr, nullptr, nullptr);
+            if (sl >= 0 && (sl & kQualityNotCounted)) e = qEmpty<QMFace>();
+        } else {
+            qmFaceOne(m, pts, fCtr, cellCtr, own, nei, thr, f, e, nullptr, nullptr, nullptr, nullptr);
+        }
+        return qmFaceBits(e);
+    });
 }
 
 }  // namespace smgpu

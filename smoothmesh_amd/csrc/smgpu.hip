@@ -3335,6 +3335,14 @@ static int qualityCoupledReady(smgpu_handle* h, const char* api, const void* buf
     if (h->qNProc > 0 && !buf) return fail(std::string(api) + ": null " + what);
     return 0;
 }
+// ... and of a coupled geometry call: the volumes are those of a pack_volumes on the same pack
+static int qualityCoupledGeomReady(smgpu_handle* h, const char* api, const void* recvCc, const void* recvVc) {
+    if (qualityCoupledReady(h, api, recvCc)) return 1;
+    if (!h->qgPartOut || h->qVolEpoch != h->qEpoch || h->qVolCoupling != h->qCoupling)
+        return fail(std::string(api) + ": call smgpu_quality_coupled_pack_volumes after smgpu_quality_coupled_pack first");
+    if (h->qNProc > 0 && !recvVc) return fail(std::string(api) + ": null recvVc");
+    return 0;
+}
 static QCoupling<true> qualityCoupling(const smgpu_handle* h, const void* recvCc, const void* recvVc) {
     return QCoupling<true>{h->qSlot, (const double*)recvCc, (const double*)recvVc};
 }
@@ -3419,10 +3427,7 @@ static int runQuality(smgpu_handle* h, const char* api, const smgpu_quality_para
 template <bool Coupled>
 static int runQualityGeom(smgpu_handle* h, const char* api, const smgpu_quality_geometry_params* p, const QCoupling<Coupled>& cp, double* const* o) {
     if constexpr (Coupled) {
-        if (qualityCoupledReady(h, api, cp.recvCc)) return 1;
-        if (!h->qgPartOut || h->qVolEpoch != h->qEpoch || h->qVolCoupling != h->qCoupling)
-            return fail(std::string(api) + ": call smgpu_quality_coupled_pack_volumes after smgpu_quality_coupled_pack first");
-        if (h->qNProc > 0 && !cp.recvVc) return fail(std::string(api) + ": null recvVc");
+        if (qualityCoupledGeomReady(h, api, cp.recvCc, cp.recvVc)) return 1;
         HIP_OK(hipSetDevice(h->device));
     } else {
         if (h->haloOn) return fail(kQualityHaloRefusal);
@@ -3696,59 +3701,49 @@ int smgpu_quality_coupled_motion_field(smgpu_handle* h, const char* name, const 
                         [&](double** o) { return runQualityMotion(h, api, nullptr, qualityCoupling(h, recvCc, nullptr), o); });
 }
 
-// ---- the failing elements as sets (DESIGN.md "Mesh quality", 10.5) --------------------------------------------------------
-// The face flag pass (mask[0, F), cnt rows of the face sets) and the cell flag pass (mask[F, F + C), cnt + 4 * nFB); then the scan,
-// one copy of the counts, and when ids fit the scatter and one copy of the ids.  Every buffer is this call's own (outside
-// deviceBytes, as the field buffers).
+// ---- the failing elements as sets (DESIGN.md "Mesh quality", 10.5 and 10.9) ------------------------------------------------
+// One sequence for the three reports' sets, <NF, NC> being the report's set layout (NF face sets, then NC cell sets):
+// flags(mask, cnt) launches the report's flag passes (faces: mask[0, F), the cnt rows of the face sets; cells: mask[F, F + C),
+// cnt + NF * nFB); then the scan, one copy of the counts, and when ids fit the scatter and one copy of the ids.  Every buffer is
+// this call's own (outside deviceBytes, as the field buffers).
 extern "C++" {
-template <bool Coupled>
-static int qualitySets(smgpu_handle* h, const char* api, const smgpu_quality_params* p, const QCoupling<Coupled>& cp, int64_t counts[7], int32_t* ids,
-                       int64_t cap) {
-    const QualityThresholds thr = qualityThresholds(p);
-    auto flags = [&](uint8_t* mask, int* cnt) {
-        const MeshView& m = h->mv;
-        const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-        const State& s = h->st;
-        if (nFB > 0)
-            hipLaunchKernelGGL(k_quality_face_flags<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr,
-                               h->qOwn, h->qNei, cp, thr, mask, cnt);
-        if (nCB > 0)
-            hipLaunchKernelGGL(k_quality_cell_flags, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, mask + m.nFaces,
-                               cnt + (size_t)kQualityFaceSets * nFB);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail(std::string(api) + ": " + hipGetErrorString(e));
-    };
+template <int NF, int NC, class Flags>
+static int qualitySetsOf(smgpu_handle* h, const char* api, Flags flags, int64_t* counts, int32_t* ids, int64_t cap) {
     const MeshView& m = h->mv;
-    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-    const int nCnt = kQualityFaceSets * nFB + kQualityCellSets * nCB;
+    const int nFB = qualityGrid(m.nFaces), nCB = NC > 0 ? qualityGrid(m.nCells) : 0;
+    const int nCnt = NF * nFB + NC * nCB;
     uint8_t* mask = nullptr;
     int* cnt = nullptr;
     long long *off = nullptr, *dCounts = nullptr;
     int* dIds = nullptr;
     int rc = 0;
     auto hipFail = [&](hipError_t e) { rc = fail(std::string(api) + ": " + hipGetErrorString(e)); };
-    hipError_t e = hipMalloc((void**)&mask, (size_t)std::max<int64_t>(1, (int64_t)m.nFaces + m.nCells));
+    hipError_t e = hipMalloc((void**)&mask, (size_t)std::max<int64_t>(1, (int64_t)m.nFaces + (NC > 0 ? m.nCells : 0)));
     if (e == hipSuccess) e = hipMalloc((void**)&cnt, sizeof(int) * (size_t)std::max(1, nCnt));
     if (e == hipSuccess) e = hipMalloc((void**)&off, sizeof(long long) * ((size_t)nCnt + 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&dCounts, sizeof(long long) * kQualitySets);
+    if (e == hipSuccess) e = hipMalloc((void**)&dCounts, sizeof(long long) * (NF + NC));
     if (e != hipSuccess) hipFail(e);
-    if (rc == 0) rc = flags(mask, cnt);
     if (rc == 0) {
-        hipLaunchKernelGGL(k_quality_set_scan, dim3(1), dim3(kQualityScanBlock), 0, h->stream, cnt, nCnt, nFB, nCB, off, dCounts);
-        long long hc[kQualitySets];
+        flags(mask, cnt, nFB, nCB);
+        e = hipGetLastError();
+        if (e != hipSuccess) hipFail(e);
+    }
+    if (rc == 0) {
+        hipLaunchKernelGGL((k_quality_set_scan<NF, NC>), dim3(1), dim3(kQualityScanBlock), 0, h->stream, cnt, nCnt, nFB, nCB, off, dCounts);
+        long long hc[NF + NC];
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(hc, dCounts, sizeof(hc), hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) hipFail(e);
         int64_t total = 0;
-        for (int s = 0; s < kQualitySets && rc == 0; ++s) { counts[s] = hc[s]; total += hc[s]; }
+        for (int s = 0; s < NF + NC && rc == 0; ++s) { counts[s] = hc[s]; total += hc[s]; }
         if (rc == 0 && ids && cap < total)
             rc = fail(std::string(api) + ": ids holds " + std::to_string(cap) + " labels, the sets need " + std::to_string(total));
         if (rc == 0 && ids && total > 0) {
             e = hipMalloc((void**)&dIds, sizeof(int) * (size_t)total);
             if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_quality_set_scatter, dim3(nFB + nCB), dim3(kQualityBlock), 0, h->stream, mask, m.nFaces, m.nCells, nFB, nCB, off, dIds,
-                                   (long long)total);
+                hipLaunchKernelGGL((k_quality_set_scatter<NF, NC>), dim3(nFB + nCB), dim3(kQualityBlock), 0, h->stream, mask, m.nFaces, m.nCells, nFB,
+                                   nCB, off, dIds, (long long)total);
                 e = hipGetLastError();
             }
             if (e == hipSuccess) e = hipMemcpyAsync(ids, dIds, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, h->stream);
@@ -3760,6 +3755,51 @@ static int qualitySets(smgpu_handle* h, const char* api, const smgpu_quality_par
     for (void* p : {(void*)mask, (void*)cnt, (void*)off, (void*)dCounts, (void*)dIds})
         if (p) (void)hipFree(p);
     return rc;
+}
+
+template <bool Coupled>
+static int qualitySets(smgpu_handle* h, const char* api, const smgpu_quality_params* p, const QCoupling<Coupled>& cp, int64_t counts[7], int32_t* ids,
+                       int64_t cap) {
+    const QualityThresholds thr = qualityThresholds(p);
+    return qualitySetsOf<kQualityFaceSets, kQualityCellSets>(h, api, [&](uint8_t* mask, int* cnt, int nFB, int nCB) {
+        const MeshView& m = h->mv;
+        const State& s = h->st;
+        if (nFB > 0)
+            hipLaunchKernelGGL(k_quality_face_flags<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr,
+                               h->qOwn, h->qNei, cp, thr, mask, cnt);
+        if (nCB > 0)
+            hipLaunchKernelGGL(k_quality_cell_flags, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, mask + m.nFaces,
+                               cnt + (size_t)kQualityFaceSets * nFB);
+    }, counts, ids, cap);
+}
+// the sets of the -allGeometry checks (10.9): the cell flag pass first (serial: it leaves the volumes in h->qgVol), then the
+// face flag pass.  The caller has made the refusals and the geometry of the matching report (runQualityGeom).
+template <bool Coupled>
+static int qualityGeomSets(smgpu_handle* h, const char* api, const smgpu_quality_geometry_params* p, const QCoupling<Coupled>& cp, int64_t counts[5],
+                           int32_t* ids, int64_t cap) {
+    const QualityGeomThresholds thr = geomThresholds(p);
+    return qualitySetsOf<kQualityGeomFaceSets, kQualityGeomCellSets>(h, api, [&](uint8_t* mask, int* cnt, int nFB, int nCB) {
+        const MeshView& m = h->mv;
+        const State& s = h->st;
+        if (nCB > 0)
+            hipLaunchKernelGGL(k_quality_geom_cell_flags<Coupled>, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, cp, thr, h->qgVol,
+                               mask + m.nFaces, cnt + (size_t)kQualityGeomFaceSets * nFB);
+        if (nFB > 0)
+            hipLaunchKernelGGL(k_quality_geom_face_flags<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea,
+                               s.cellCtr, h->qgVol, h->qOwn, h->qNei, cp, thr, mask, cnt);
+    }, counts, ids, cap);
+}
+// ... and of the motion criteria: face sets only
+template <bool Coupled>
+static int qualityMotionSets(smgpu_handle* h, const char* api, const smgpu_quality_motion_params* p, const QCoupling<Coupled>& cp, int64_t counts[4],
+                             int32_t* ids, int64_t cap) {
+    const QualityMotionThresholds thr = motionThresholds(p);
+    return qualitySetsOf<kQualityMotionFaceSets, 0>(h, api, [&](uint8_t* mask, int* cnt, int nFB, int) {
+        const State& s = h->st;
+        if (nFB > 0)
+            hipLaunchKernelGGL(k_quality_motion_face_flags<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, h->mv, s.ptsCur, s.fCtr, s.cellCtr,
+                               h->qOwn, h->qNei, cp, thr, mask, cnt);
+    }, counts, ids, cap);
 }
 }  // extern "C++"
 
@@ -3778,6 +3818,42 @@ int smgpu_quality_coupled_sets(smgpu_handle* h, const smgpu_quality_params* p, c
     if (qualityCoupledReady(h, api, recvCc)) return 1;
     HIP_OK(hipSetDevice(h->device));
     return qualitySets(h, api, p, qualityCoupling(h, recvCc, nullptr), counts, ids, cap);
+}
+
+int smgpu_quality_geometry_sets(smgpu_handle* h, const smgpu_quality_geometry_params* p, int64_t counts[5], int32_t* ids, int64_t cap) {
+    if (!h || !counts) return fail("null argument");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityGeomEnsure(h)) return 1;
+    if (qualityGeometry(h)) return 1;
+    return qualityGeomSets(h, "smgpu_quality_geometry_sets", p, QCoupling<false>{}, counts, ids, cap);
+}
+
+int smgpu_quality_motion_sets(smgpu_handle* h, const smgpu_quality_motion_params* p, int64_t counts[4], int32_t* ids, int64_t cap) {
+    if (!h || !counts) return fail("null argument");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityEnsure(h)) return 1;
+    if (qualityGeometry(h)) return 1;
+    return qualityMotionSets(h, "smgpu_quality_motion_sets", p, QCoupling<false>{}, counts, ids, cap);
+}
+
+int smgpu_quality_coupled_geometry_sets(smgpu_handle* h, const smgpu_quality_geometry_params* p, const void* recvCc, const void* recvVc,
+                                        int64_t counts[5], int32_t* ids, int64_t cap) {
+    if (!h || !counts) return fail("null argument");
+    const char* api = "smgpu_quality_coupled_geometry_sets";
+    if (qualityCoupledGeomReady(h, api, recvCc, recvVc)) return 1;
+    HIP_OK(hipSetDevice(h->device));
+    return qualityGeomSets(h, api, p, qualityCoupling(h, recvCc, recvVc), counts, ids, cap);
+}
+
+int smgpu_quality_coupled_motion_sets(smgpu_handle* h, const smgpu_quality_motion_params* p, const void* recvCc, int64_t counts[4], int32_t* ids,
+                                      int64_t cap) {
+    if (!h || !counts) return fail("null argument");
+    const char* api = "smgpu_quality_coupled_motion_sets";
+    if (qualityCoupledReady(h, api, recvCc)) return 1;
+    HIP_OK(hipSetDevice(h->device));
+    return qualityMotionSets(h, api, p, qualityCoupling(h, recvCc, nullptr), counts, ids, cap);
 }
 
 // ---- debug / parity access -------------------------------------------------------------------

@@ -147,6 +147,21 @@ class MeshQualityMotion:
 
 
 QUALITY_MOTION_FIELDS = ("faceTetQuality", "faceBaseTetQuality", "faceTwist", "faceTriangleTwist")
+# the findings of the two reports above as sets (DESIGN.md "Mesh quality", 10.9), in smgpu_quality_geometry_sets' and
+# smgpu_quality_motion_sets' order; the 4-tuples of QUALITY_SETS, the counts being fields of MeshQualityGeometry / MeshQualityMotion
+QUALITY_GEOMETRY_SETS = (
+    ("concaveFaces", "faceSet", ("nConcaveFaces",), "concave faces"),
+    ("warpedFaces", "faceSet", ("nWarpedFaces",), "warped faces"),
+    ("lowWeightFaces", "faceSet", ("nLowWeightFaces",), "faces with low interpolation weight"),
+    ("lowVolRatioFaces", "faceSet", ("nLowVolRatioFaces",), "faces with low volume ratio"),
+    ("underdeterminedCells", "cellSet", ("nUnderdeterminedCells",), "under-determined cells"),
+)
+QUALITY_MOTION_SETS = (
+    ("lowQualityTetFaces", "faceSet", ("nLowTetFaces",), "faces with low quality or negative volume decomposition tets"),
+    ("noBasePointFaces", "faceSet", ("nNoBasePointFaces",), "faces without a valid tet base point"),
+    ("twistedFaces", "faceSet", ("nLowTwistFaces",), "twisted faces"),
+    ("lowTriangleTwistFaces", "faceSet", ("nLowTriangleTwistFaces",), "faces with low triangle twist"),
+)
 
 
 def patch_arrays(mesh: PolyMesh, layerPatches):
@@ -497,10 +512,10 @@ class SmoothEngine:
         self._check(self._lib.smgpu_quality_field(self._h, name.encode(), _p(out, _ffi.c_f64p), C.byref(n)))
         return out
 
-    def _sets(self, call, *args):
+    def _sets(self, call, *args, table=QUALITY_SETS):
         # one call when the sets hold at most nFaces + nCells ids (an element in several sets may exceed that: then again with
         # the exact size, which the refused call has reported)
-        counts = (C.c_int64 * 7)()
+        counts = (C.c_int64 * len(table))()
         ids = np.empty(max(1, self.mesh.nFaces + self.mesh.nCells), np.int32)
         if call(self._h, *args, counts, _p(ids, _ffi.c_i32p), len(ids)):
             if sum(counts) <= len(ids):
@@ -508,7 +523,7 @@ class SmoothEngine:
             ids = np.empty(sum(counts), np.int32)
             self._check(call(self._h, *args, counts, _p(ids, _ffi.c_i32p), len(ids)))
         out, at = {}, 0
-        for (name, *_), n in zip(QUALITY_SETS, counts):
+        for (name, *_), n in zip(table, counts):
             out[name] = ids[at:at + n].copy()
             at += n
         return out
@@ -554,6 +569,20 @@ class SmoothEngine:
         out = np.empty(n.value, dtype=np.float64)
         self._check(self._lib.smgpu_quality_motion_field(self._h, name.encode(), _p(out, _ffi.c_f64p), C.byref(n)))
         return out
+
+    def quality_geometry_sets(self, concaveThreshold=10.0, flatnessThreshold=0.8, weightThreshold=0.05, volRatioThreshold=0.01,
+                              determinantThreshold=0.001) -> dict:
+        """The findings of mesh_quality_geometry's report as sets (include/smgpu.h, smgpu_quality_geometry_sets): {name: ascending
+        int32 ids} for every name of QUALITY_GEOMETRY_SETS, empty ones included; each size equals the report's count under the same
+        thresholds.  Refusals and side effects as mesh_quality_geometry."""
+        p = _ffi.QualityGeometryParams(concaveThreshold, flatnessThreshold, weightThreshold, volRatioThreshold, determinantThreshold)
+        return self._sets(self._lib.smgpu_quality_geometry_sets, C.byref(p), table=QUALITY_GEOMETRY_SETS)
+
+    def quality_motion_sets(self, tetThreshold=1e-15, twistThreshold=0.02, triangleTwistThreshold=-1.0) -> dict:
+        """The findings of mesh_quality_motion's report as sets (smgpu_quality_motion_sets): as quality_geometry_sets, the names of
+        QUALITY_MOTION_SETS."""
+        p = _ffi.QualityMotionParams(tetThreshold, twistThreshold, triangleTwistThreshold)
+        return self._sets(self._lib.smgpu_quality_motion_sets, C.byref(p), table=QUALITY_MOTION_SETS)
 
     # -- mesh quality of a sub-domain (DESIGN.md "Mesh quality", 10.4; smoothmesh_amd/quality.py drives these) -------------
     def quality_coupling(self, rank=None):
@@ -639,6 +668,19 @@ class SmoothEngine:
         q = _ffi.QualityMotionPart()
         self._check(self._lib.smgpu_quality_coupled_motion_report(self._h, C.byref(p), C.c_void_p(recvCc or None), C.byref(q)))
         return {n: getattr(q, n) for n, _ in q._fields_}
+
+    def quality_coupled_geometry_sets(self, recvCc, recvVc, concaveThreshold=10.0, flatnessThreshold=0.8, weightThreshold=0.05,
+                                      volRatioThreshold=0.01, determinantThreshold=0.001) -> dict:
+        """smgpu_quality_coupled_geometry_sets: as quality_geometry_sets for this rank, local ids; a processor face is a member only
+        on the side that counts it"""
+        p = _ffi.QualityGeometryParams(concaveThreshold, flatnessThreshold, weightThreshold, volRatioThreshold, determinantThreshold)
+        return self._sets(self._lib.smgpu_quality_coupled_geometry_sets, C.byref(p), C.c_void_p(recvCc or None), C.c_void_p(recvVc or None),
+                          table=QUALITY_GEOMETRY_SETS)
+
+    def quality_coupled_motion_sets(self, recvCc, tetThreshold=1e-15, twistThreshold=0.02, triangleTwistThreshold=-1.0) -> dict:
+        """smgpu_quality_coupled_motion_sets: as quality_motion_sets for this rank, local ids, members counted once"""
+        p = _ffi.QualityMotionParams(tetThreshold, twistThreshold, triangleTwistThreshold)
+        return self._sets(self._lib.smgpu_quality_coupled_motion_sets, C.byref(p), C.c_void_p(recvCc or None), table=QUALITY_MOTION_SETS)
 
     def quality_coupled_motion_field(self, name, recvCc) -> np.ndarray:
         """smgpu_quality_coupled_motion_field: as quality_motion_field, processor faces with the internal-face definitions"""

@@ -788,12 +788,26 @@ class DistributedSmoother:
         """this rank's field of engine.QUALITY_FIELDS.  A collective: every rank calls it."""
         return self._quality_field("quality", name)
 
+    def _quality_sets(self, kind, thresholds):
+        """this rank's sets of one kind: the exchange of _quality_report and no all-gather, the sets stay on their rank"""
+        from .quality import QUALITY_KINDS
+        k = QUALITY_KINDS[kind]
+        recv = self._quality_exchange(volumes=k.volumes)
+        return getattr(self.engine, k.sets)(*(t.data_ptr() for t in recv), **{**k.defaults, **thresholds})
+
     def quality_sets(self, **thresholds):
         """this rank's failing elements as sets: {name: local ids}; a processor face is a member only on the
         lower rank.  A collective (the exchange of mesh_quality); the sets themselves stay on their rank."""
-        from .quality import QUALITY_DEFAULTS
-        recv, = self._quality_exchange()
-        return self.engine.quality_coupled_sets(recv.data_ptr(), **{**QUALITY_DEFAULTS, **thresholds})
+        return self._quality_sets("quality", thresholds)
+
+    def quality_geometry_sets(self, **thresholds):
+        """this rank's findings of the -allGeometry checks as sets, as quality_sets.  A collective (the two
+        exchanges of mesh_quality_geometry)."""
+        return self._quality_sets("geometry", thresholds)
+
+    def quality_motion_sets(self, **thresholds):
+        """this rank's findings of the motion criteria as sets, as quality_sets.  A collective."""
+        return self._quality_sets("motion", thresholds)
 
     def mesh_quality_geometry(self, **thresholds):
         """The -allGeometry report of the whole decomposed mesh, identical on every rank.  A collective: every rank
@@ -926,7 +940,7 @@ class LocalMultiSmoother:
     def get_points(self):
         return [st.eng.get_points() for st in self.states]
 
-    # The reports of the decomposed mesh at the current points (smoothmesh_amd/quality.py, DESIGN.md 10.4, 10.5, 10.8): the cell
+    # The reports of the decomposed mesh at the current points (smoothmesh_amd/quality.py, DESIGN.md 10.4, 10.5, 10.8, 10.9): the cell
     # centres (and volumes) of the processor faces move between the engines' buffers by device-side copies.  Ids are global where
     # the sub-domains carry cell and face addressing; fields and sets come as one entry per rank, processor faces carrying their
     # field values on both sides and set membership on the lower rank.  Between iterations only; the loop is left as it was.
@@ -947,6 +961,16 @@ class LocalMultiSmoother:
         """[per-rank {name: local ids}] of the failing elements"""
         from .quality import local_quality_sets
         return local_quality_sets(self._engines(), self.device, thresholds)
+
+    def quality_geometry_sets(self, **thresholds):
+        """[per-rank {name: local ids}] of the findings of the -allGeometry checks"""
+        from .quality import local_quality_geometry_sets
+        return local_quality_geometry_sets(self._engines(), self.device, thresholds)
+
+    def quality_motion_sets(self, **thresholds):
+        """[per-rank {name: local ids}] of the findings of the motion criteria"""
+        from .quality import local_quality_motion_sets
+        return local_quality_motion_sets(self._engines(), self.device, thresholds)
 
     def mesh_quality_geometry(self, **thresholds):
         """The -allGeometry report of the decomposed mesh at the current points"""

@@ -8,13 +8,15 @@ DistributedSmoother.mesh_quality (smoothmesh_amd/halo.py); the shell tool is smo
 The failing elements as sets: decomposed_quality_sets, the drivers' quality_sets, write_quality_sets.
 The -allGeometry checks and the motion criteria of a decomposed mesh: combine_quality_geometry,
 combine_quality_motion, decomposed_mesh_quality_geometry, decomposed_mesh_quality_motion and the drivers' methods of those names.
+Their findings as sets: decomposed_quality_geometry_sets, decomposed_quality_motion_sets, the drivers'
+quality_geometry_sets / quality_motion_sets; write_quality_sets and format_sets_written take the table of the report.
 """
 from dataclasses import dataclass, fields
 
 import numpy as np
 
 from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QUALITY_FIELDS, QUALITY_GEOMETRY_FIELDS,  # noqa: F401
-                     QUALITY_MOTION_FIELDS, QUALITY_SETS)
+                     QUALITY_MOTION_FIELDS, QUALITY_SETS, QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS)
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
 _COUNTS = ("nNonPositiveVolume", "nZeroAreaFaces", "nSevereNonOrth", "nErrorNonOrth", "nSkewFaces", "nWrongOrientedFaces",
@@ -237,7 +239,8 @@ def _all_ids(subs):
 @dataclass(frozen=True)
 class QualityKind:
     """one report kind: its default thresholds, whether the owner cells' volumes are exchanged too, the engine's coupled report
-    and field methods, the combine of the per-rank records and the record's winning cell / face ids"""
+    and field methods, the combine of the per-rank records, the record's winning cell / face ids, the engine's coupled sets
+    method and the table of its sets"""
     defaults: dict
     volumes: bool
     report: str
@@ -245,15 +248,19 @@ class QualityKind:
     combine: object
     cellIds: tuple
     faceIds: tuple
+    sets: str
+    table: tuple
 
 
 QUALITY_KINDS = dict(
     quality=QualityKind(QUALITY_DEFAULTS, False, "quality_coupled_report", "quality_coupled_field", combine_quality,
-                        ("minVolumeCell",), ("maxNonOrthFace", "maxSkewFace")),
+                        ("minVolumeCell",), ("maxNonOrthFace", "maxSkewFace"), "quality_coupled_sets", QUALITY_SETS),
     geometry=QualityKind(GEOMETRY_DEFAULTS, True, "quality_coupled_geometry_report", "quality_coupled_geometry_field", combine_quality_geometry,
-                         ("minDeterminantCell",), ("maxConcaveFace", "minFlatnessFace", "minFaceWeightFace", "minVolRatioFace")),
+                         ("minDeterminantCell",), ("maxConcaveFace", "minFlatnessFace", "minFaceWeightFace", "minVolRatioFace"),
+                         "quality_coupled_geometry_sets", QUALITY_GEOMETRY_SETS),
     motion=QualityKind(MOTION_DEFAULTS, False, "quality_coupled_motion_report", "quality_coupled_motion_field", combine_quality_motion,
-                       (), ("minTetFace", "minBaseTetFace", "minTwistFace", "minTriangleTwistFace")))
+                       (), ("minTetFace", "minBaseTetFace", "minTwistFace", "minTriangleTwistFace"), "quality_coupled_motion_sets",
+                       QUALITY_MOTION_SETS))
 
 
 def _local(engines, torch_device, volumes, call):
@@ -299,9 +306,24 @@ def local_quality_motion_field(engines, name, torch_device):
     return _local_field("motion", engines, name, torch_device)
 
 
+def _local_sets(kind, engines, torch_device, thresholds):
+    k = QUALITY_KINDS[kind]
+    return _local(engines, torch_device, k.volumes, lambda e, *recv: getattr(e, k.sets)(*recv, **{**k.defaults, **thresholds}))
+
+
 def local_quality_sets(engines, torch_device, thresholds):
     """[per-rank {name: local ids}]: a processor face is a member only on the rank that counts it"""
-    return _local(engines, torch_device, False, lambda e, recv: e.quality_coupled_sets(recv, **{**QUALITY_DEFAULTS, **thresholds}))
+    return _local_sets("quality", engines, torch_device, thresholds)
+
+
+def local_quality_geometry_sets(engines, torch_device, thresholds):
+    """local_quality_sets for the sets of the -allGeometry checks; the exchange also moves the volumes"""
+    return _local_sets("geometry", engines, torch_device, thresholds)
+
+
+def local_quality_motion_sets(engines, torch_device, thresholds):
+    """local_quality_sets for the sets of the motion criteria"""
+    return _local_sets("motion", engines, torch_device, thresholds)
 
 
 def _with_engines(subs, device, foam_variant, run):
@@ -349,15 +371,28 @@ def decomposed_quality_sets(subs, device=0, foam_variant=None, **thresholds) -> 
     return _with_engines(subs, device, foam_variant, lambda engines, dev: local_quality_sets(engines, dev, thresholds))
 
 
-def write_quality_sets(polyMeshDir, location, sets, binary=False):
+def decomposed_quality_geometry_sets(subs, device=0, foam_variant=None, **thresholds) -> list:
+    """The findings of decomposed_mesh_quality_geometry's report as sets: one {name: local ids} per rank, the names of
+    QUALITY_GEOMETRY_SETS; disjoint between the ranks and complete as decomposed_quality_sets'."""
+    return _with_engines(subs, device, foam_variant, lambda engines, dev: local_quality_geometry_sets(engines, dev, thresholds))
+
+
+def decomposed_quality_motion_sets(subs, device=0, foam_variant=None, **thresholds) -> list:
+    """The findings of decomposed_mesh_quality_motion's report as sets: as decomposed_quality_geometry_sets, the names of
+    QUALITY_MOTION_SETS."""
+    return _with_engines(subs, device, foam_variant, lambda engines, dev: local_quality_motion_sets(engines, dev, thresholds))
+
+
+def write_quality_sets(polyMeshDir, location, sets, binary=False, table=QUALITY_SETS):
     """the non-empty sets as OpenFOAM topoSet files <polyMeshDir>/sets/<name> (class faceSet / cellSet, location
     "<location>/sets"), as checkMesh writes them; compressed when polymesh.set_write_compression is on.  Nothing else in the
-    directory is touched.  Returns [(name, size)] of the files written, in QUALITY_SETS order."""
+    directory is touched.  table: the sets' table (QUALITY_SETS, QUALITY_GEOMETRY_SETS or QUALITY_MOTION_SETS).  Returns
+    [(name, size)] of the files written, in the table's order."""
     import os
     from .polymesh import write_label_list
     d = os.path.join(polyMeshDir, "sets")
     written = []
-    for name, cls, _, _ in QUALITY_SETS:
+    for name, cls, _, _ in table:
         ids = np.asarray(sets.get(name, ()), dtype=np.int32)
         if ids.size == 0:
             continue
@@ -367,9 +402,9 @@ def write_quality_sets(polyMeshDir, location, sets, binary=False):
     return written
 
 
-def format_sets_written(written):
-    """the lines smoothMesh -writeSets prints after the report block, one per written set"""
-    desc = {name: words for name, _, _, words in QUALITY_SETS}
+def format_sets_written(written, table=QUALITY_SETS):
+    """the lines smoothMesh -writeSets prints after the report block, one per written set of `table`"""
+    desc = {name: words for name, _, _, words in table}
     return "".join(f"    <<Writing {n} {desc[name]} to set {name}\n" for name, n in written)
 
 
