@@ -167,6 +167,42 @@ int smgpu_mesh_quality(smgpu_handle* h, const smgpu_quality_params* p, smgpu_qua
  * (degrees, 0 on boundary faces), "faceSkewness" [nFaces].  out == NULL: size only (*n). */
 int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t* n);
 
+/* ---- a quality history of the run (DESIGN.md "Mesh quality", 10.10) -----------------------------------------------------
+ * smgpu_set_quality_trace(interval > 0) switches the trace on: smgpu_iterate then numbers the iterations that run 1, 2, ...
+ * across its calls, and after every iteration whose number is a multiple of `interval` it queues the trace's launches on the
+ * engine's stream, behind that iteration's movePoints.  They leave one record on the device; the records of a call come to the
+ * host together with its smgpu_iter_stats -- no synchronisation is added to the loop -- and wait in the engine until
+ * smgpu_get_quality_trace takes them.  An iteration that did not run (queued behind the stop by relTol) leaves no record and
+ * does not advance the number; the iteration that met relTol did run.
+ *
+ * A record holds every field of smgpu_quality that does not depend on the order of a floating-point sum (totalVolume and
+ * avgNonOrth are left out), and EVERY FIELD EQUALS, BIT FOR BIT, the field of that name smgpu_mesh_quality returns for the
+ * same points; definitions, thresholds and lowest-id tie rules are the report's.
+ *
+ * smgpu_set_quality_trace: interval > 0 also sets the running number to 0 and discards unread records; interval == 0 switches
+ * the trace off and frees its device memory (allocated by the first traced smgpu_iterate, outside deviceBytes like the
+ * report's); interval < 0 is an error.  Refused on an engine with a halo; smgpu_halo_configure is refused while the trace is
+ * on.  p == NULL: the defaults of smgpu_mesh_quality.  With the trace off nothing the engine launches changes; with it on,
+ * the loop's kernels, results, smgpu_counters and timing events are what they are without it.
+ * SMGPU_QUALITY_TRACE_FUSED=0 (read at smgpu_create), or an engine without tiles (SMGPU_TILES=0), queues the report's own
+ * launches in place of the fused tile kernel: the records are identical.
+ *
+ * smgpu_get_quality_trace: out == NULL returns the number of pending records in *n; otherwise cap below that number is an
+ * error that clears nothing; otherwise the records are copied in ascending `iteration`, *n is their number, and they are
+ * cleared. */
+typedef struct smgpu_quality_trace_record {
+    int64_t iteration;                      /* 1-based running number since smgpu_set_quality_trace */
+    double minVolume, maxVolume;   int64_t nNonPositiveVolume;  int32_t minVolumeCell;
+    double minFaceArea, maxFaceArea;  int64_t nZeroAreaFaces;
+    double maxNonOrth;             int64_t nSevereNonOrth, nErrorNonOrth;  int32_t maxNonOrthFace;
+    double maxSkewness;            int64_t nSkewFaces;  int32_t maxSkewFace;
+    int64_t nWrongOrientedFaces;
+    double maxOpenness;            int64_t nOpenCells;
+    double maxAspectRatio;         int64_t nHighAspectCells;
+} smgpu_quality_trace_record;
+int smgpu_set_quality_trace(smgpu_handle* h, int32_t interval, const smgpu_quality_params* p);   /* 0 = off; p NULL = defaults */
+int smgpu_get_quality_trace(smgpu_handle* h, smgpu_quality_trace_record* out, int64_t cap, int64_t* n);
+
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):
  *   1. smgpu_quality_coupled_pack: the geometry of the current points (the loop's own launch, uncounted), then the owner cell

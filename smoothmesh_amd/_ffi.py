@@ -109,6 +109,13 @@ class Quality(C.Structure):
     ]
 
 
+class QualityTraceRecord(C.Structure):
+    """smgpu_quality_trace_record: the running iteration number, then Quality without the sizes and the two fields that depend on
+    the order of a floating-point sum"""
+    _fields_ = [("iteration", C.c_int64)] + [(n, t) for n, t in Quality._fields_
+                                             if n not in ("nCells", "nFaces", "nInternalFaces", "totalVolume", "avgNonOrth")]
+
+
 class QualityGeometryParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("concaveThreshold", "flatnessThreshold", "weightThreshold", "volRatioThreshold",
                                           "determinantThreshold")]
@@ -216,6 +223,8 @@ SYMBOLS = {
     "smgpu_iter_end": (C.c_int, [C.c_void_p]),
     "smgpu_mesh_quality": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.POINTER(Quality)]),
     "smgpu_quality_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
+    "smgpu_set_quality_trace": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(QualityParams)]),
+    "smgpu_get_quality_trace": (C.c_int, [C.c_void_p, C.POINTER(QualityTraceRecord), C.c_int64, C.POINTER(C.c_int64)]),
     "smgpu_quality_coupled_pack": (C.c_int, [C.c_void_p, C.POINTER(QualityCoupling), C.c_void_p, C.POINTER(C.c_int64)]),
     "smgpu_quality_coupled_report": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(QualityPart)]),
     "smgpu_quality_coupled_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),

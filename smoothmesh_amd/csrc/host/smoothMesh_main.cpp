@@ -96,7 +96,7 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "layerMaxBlendingFraction", "layerEdgeLength", "layerExpansionRatio", "minLayers",
                                "maxLayers", "layerPatches", "smoothingPatches", "internalSmoothingBlendingFraction",
                                "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets", "allGeometry",
-                               "meshQuality"};
+                               "meshQuality", "qualityInterval"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -114,6 +114,8 @@ Options parseArgs(int argc, char** argv) {
                       "        ratio and cell determinant, the checks of checkMesh -allGeometry)\n"
                       "       [-meshQuality b]    (with -checkQuality: also face tet quality, base-point tet quality, face twist and\n"
                       "        triangle twist, the meshQualityDict criteria of checkMesh -meshQuality)\n"
+                      "       [-qualityInterval n] (with -checkQuality: a quality line under every n-th iteration line, traced on the GPU\n"
+                      "        without stopping the loop, and a warning at the first traced iteration that tangles the mesh)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -523,6 +525,12 @@ int main(int argc, char** argv) {
         fatal("-meshQuality is not available with -parallel: the tets and the twist of a processor face need the neighbour rank's cell "
               "centre, which the quality report does not exchange (run it on the reconstructed case)");
     if (meshQuality && !checkQuality) fatal("-meshQuality needs -checkQuality true: its lines are part of the quality report");
+    const bool qualityTrace = opt.found("qualityInterval");
+    const long qualityInterval = opt.getL("qualityInterval", 0);
+    if (qualityTrace && opt.parallel)
+        fatal("-qualityInterval is not available with -parallel: it traces the measures of the -checkQuality report, which is serial only");
+    if (qualityTrace && !checkQuality) fatal("-qualityInterval needs -checkQuality true: its lines are measures of the quality report");
+    if (qualityTrace && (qualityInterval < 1 || qualityInterval > 0x7fffffffL)) fatal("qualityInterval must be positive");
     // SMOOTHMESH_TIMELINE=1: where this process's wall time goes, one stderr line per stage (seconds since main started)
     const bool timeline = std::getenv("SMOOTHMESH_TIMELINE") && std::atoi(std::getenv("SMOOTHMESH_TIMELINE")) > 0;
     auto mark = [&](const char* what) { if (timeline) std::fprintf(stderr, "[smoothMesh %8.3f s] %s\n", secondsSince(t0), what); };
@@ -816,8 +824,9 @@ int main(int argc, char** argv) {
     OUT("Mesh minimum edge length = %g\nMesh maximum edge length = %g\n\n", meshMinEdgeLength, meshMaxEdgeLength);
 
     // -checkQuality: the quality report (include/smgpu.h, smgpu_mesh_quality) of the mesh the run starts from and of the one it writes
+    smgpu_quality lastQuality{};
     auto reportQuality = [&](const char* which) {
-        smgpu_quality q;
+        smgpu_quality& q = lastQuality;
         check(smgpu_mesh_quality(R[0].h, nullptr, &q), "smgpu_mesh_quality");
         OUT("Mesh quality (%s):\n", which);
         OUT("    cells %lld faces %lld internalFaces %lld\n", (long long)q.nCells, (long long)q.nFaces, (long long)q.nInternalFaces);
@@ -861,6 +870,12 @@ int main(int argc, char** argv) {
         OUTS("");
     };
     if (checkQuality) reportQuality("initial mesh");
+    // -qualityInterval: the quality history of the run (include/smgpu.h, smgpu_set_quality_trace): the engine leaves
+    // one record per traced iteration on the device and hands a chunk's records over with its statistics
+    const long long initNonPositive = (long long)lastQuality.nNonPositiveVolume, initWrongOriented = (long long)lastQuality.nWrongOrientedFaces;
+    bool tangleReported = false;
+    std::vector<smgpu_quality_trace_record> trace;
+    if (qualityTrace) check(smgpu_set_quality_trace(R[0].h, (int32_t)qualityInterval, nullptr), "smgpu_set_quality_trace");
 
     for (Rank& K : R) check(smgpu_set_params(K.h, &prm), "smgpu_set_params");
     std::vector<std::vector<int64_t>> sharedGlobalOf;   // every rank's shared points (global ids, ascending): the set-up syncs
@@ -1286,8 +1301,26 @@ int main(int argc, char** argv) {
         }
         tLoop += secondsSince(tl);
         mark("a stretch of the loop done");
-        for (int32_t k = 0; k < done; ++k)
+        size_t nextRecord = 0;
+        if (qualityTrace) {
+            int64_t nRecords = 0;
+            check(smgpu_get_quality_trace(R[0].h, nullptr, 0, &nRecords), "smgpu_get_quality_trace");
+            trace.resize((size_t)nRecords);
+            if (nRecords > 0) check(smgpu_get_quality_trace(R[0].h, trace.data(), nRecords, &nRecords), "smgpu_get_quality_trace");
+        }
+        for (int32_t k = 0; k < done; ++k) {
             OUT("Smoothing iteration=%ld nFrozenPoints=%d residual=%g\n", i + k + 1, stats[(size_t)k].nFrozenPoints, stats[(size_t)k].residual);
+            if (!qualityTrace || nextRecord >= trace.size() || trace[nextRecord].iteration != (int64_t)(i + k + 1)) continue;
+            const smgpu_quality_trace_record& t = trace[nextRecord++];
+            OUT("    quality iteration=%lld minVolume %.9g nonPositive %lld maxNonOrth %.9g error %lld maxSkewness %.9g wrongOriented %lld "
+                "maxOpenness %.9g maxAspectRatio %.9g\n", (long long)t.iteration, t.minVolume, (long long)t.nNonPositiveVolume, t.maxNonOrth,
+                (long long)t.nErrorNonOrth, t.maxSkewness, (long long)t.nWrongOrientedFaces, t.maxOpenness, t.maxAspectRatio);
+            if (!tangleReported && ((long long)t.nNonPositiveVolume > initNonPositive || (long long)t.nWrongOrientedFaces > initWrongOriented)) {
+                tangleReported = true;
+                OUT("    ***Iteration %lld: %lld non-positive volume cells and %lld wrongly oriented faces (initial mesh: %lld, %lld)\n",
+                    (long long)t.iteration, (long long)t.nNonPositiveVolume, (long long)t.nWrongOrientedFaces, initNonPositive, initWrongOriented);
+            }
+        }
         i += done;
         timeValue += done * deltaT;   // runTime++ per iteration, SM.C:2414
         const bool hitTol = done > 0 && stats[(size_t)done - 1].residual < relTol;

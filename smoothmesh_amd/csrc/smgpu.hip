@@ -22,6 +22,7 @@
 #include "kernels_quality.hpp"
 #include "kernels_quality_geom.hpp"
 #include "kernels_quality_motion.hpp"
+#include "kernels_quality_trace.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"
@@ -251,6 +252,20 @@ struct smgpu_handle {
     smgpu_quality_motion_part* qmPartOut = nullptr;
     uint64_t qVolEpoch = 0;
     std::vector<int32_t> qVolCoupling;
+    // ... and of the quality history (smgpu_set_quality_trace, kernels_quality_trace.hpp): allocated by the first traced smgpu_iterate,
+    // outside `allocs` as well.  The trace's geometry launch writes cell centres of its own and reads a stop word of its own
+    // (always 0), so that nothing the loop reads is written between two iterations; qtSlab: the records of one smgpu_iterate call
+    int qtInterval = 0;                     // 0: off
+    int64_t qtIter = 0;                     // iterations that ran since smgpu_set_quality_trace
+    bool qtFusedWanted = true;              // SMGPU_QUALITY_TRACE_FUSED=0: the report's launches instead of k_quality_geom_tile
+    QualityThresholds qtThr{};
+    double* qtCellCtr = nullptr;
+    Accum* qtAcc = nullptr;
+    QFace* qtFacePart = nullptr;
+    QCell *qtCellPart = nullptr, *qtCellFold = nullptr;
+    smgpu_quality_trace_record* qtSlab = nullptr;
+    int qtSlabCap = 0;
+    std::vector<smgpu_quality_trace_record> qtPending;
     uint64_t qEpoch = 1, qPackEpoch = 0;   // qEpoch moves whenever the points (or the geometry variant) may have changed
     bool iterOpen = false;                  // between smgpu_iter_begin and smgpu_iter_end
 };
@@ -802,6 +817,7 @@ int smgpu_create(const smgpu_mesh_desc* d, smgpu_handle** out) {
     h->faLists = envInt("SMGPU_FA_LISTS", 1) != 0;
     h->faSideExact = envInt("SMGPU_FA_SIDE_EXACT", 1) != 0;
     h->bndInGeom = envInt("SMGPU_BND_IN_GEOM", 1) != 0;
+    h->qtFusedWanted = envInt("SMGPU_QUALITY_TRACE_FUSED", 1) != 0;
     { const char* fv = std::getenv("SMGPU_FOAM_VARIANT"); h->foamOrg = fv && std::string(fv) == "org"; }
     { const char* sv = std::getenv("SMGPU_SYNC_VARIANT"); h->st.ownFold = (sv && std::string(sv) == "own") ? 1 : 0; }
     if (h->useTiles) {
@@ -1138,7 +1154,8 @@ int smgpu_destroy(smgpu_handle* h) {
             if (a->p) (void)hipFree(a->p);
     for (void* p : {(void*)h->qOwn, (void*)h->qNei, (void*)h->qFacePart, (void*)h->qCellPart, (void*)h->qOut, (void*)h->qProcFace, (void*)h->qSlot,
                     (void*)h->qPartOut, (void*)h->qgVol, (void*)h->qgFacePart, (void*)h->qgCellPart, (void*)h->qgOut,
-                    (void*)h->qmFacePart, (void*)h->qmOut, (void*)h->qgPartOut, (void*)h->qmPartOut})
+                    (void*)h->qmFacePart, (void*)h->qmOut, (void*)h->qgPartOut, (void*)h->qmPartOut, (void*)h->qtCellCtr, (void*)h->qtAcc,
+                    (void*)h->qtFacePart, (void*)h->qtCellPart, (void*)h->qtCellFold, (void*)h->qtSlab})
         if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
@@ -1916,6 +1933,10 @@ static int flushDeferred(smgpu_handle* h) {
     return 0;
 }
 
+// the quality history (smgpu_set_quality_trace; defined with the mesh quality report below)
+static int qualityTraceBegin(smgpu_handle* h, int nIters);
+static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate);
+
 int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_stats* stats, int32_t* nDone) {
     if (!h) return fail("null handle");
     if (!h->prmSet) return fail("smgpu_set_params has not been called");
@@ -1958,6 +1979,10 @@ int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_sta
     // iteration's geometry launch instead of a launch of its own; the last iteration is closed by k_finish
     const bool deferFinish = relTol <= 0.0 && h->useTiles && h->geomT >= 64 && envInt("SMGPU_DEFER_FINISH", 1);
     if (flushDeferred(h)) return 1;
+    // quality history: the iterations of this call whose running number is due get a slot of the call's record slab, in order
+    const bool traced = h->qtInterval > 0;
+    std::vector<int> qtSlotIter;
+    if (traced && qualityTraceBegin(h, nIters)) return 1;
     for (int i = 0; i < nIters; ++i) {
         if (runBndPre(h)) return 1;
         if (runGeometry(h, nullptr, 0, false, true)) return 1;
@@ -1974,6 +1999,11 @@ int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_sta
         else if (launchK(h, K_FINISH, [&] { hipLaunchKernelGGL(k_finish, dim3(1), dim3(kFinishBlock), 0, h->stream, s, nPart, i, relTol, (double*)nullptr, (double*)nullptr); })) return 1;
         std::swap(h->st.ptsCur, other);  // mesh.movePoints, SM.C:2399
         ++launched;
+        // (with relTol > 0 this iteration may turn out not to have run: k_finish has written stats[i] by then, or has not)
+        if (traced && (h->qtIter + i + 1) % h->qtInterval == 0) {
+            if (qualityTraceQueue(h, (int)qtSlotIter.size(), h->qtIter + i + 1, relTol > 0.0 ? h->dStats + i : nullptr)) return 1;
+            qtSlotIter.push_back(i);
+        }
         // a positive relTol can stop the loop: poll the device flag now and then so a converged run
         // does not queue thousands of no-op launches (relTol <= 0 can never stop: residual >= 0)
         if (relTol > 0.0 && (i % 8) == 7 && i + 1 < nIters) {
@@ -1985,9 +2015,16 @@ int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_sta
     }
     std::vector<smgpu_iter_stats> hs((size_t)launched);
     HIP_OK(hipMemcpyAsync(hs.data(), h->dStats, sizeof(smgpu_iter_stats) * (size_t)launched, hipMemcpyDeviceToHost, h->stream));
+    std::vector<smgpu_quality_trace_record> qtRecs(qtSlotIter.size());
+    if (!qtRecs.empty()) HIP_OK(hipMemcpyAsync(qtRecs.data(), h->qtSlab, sizeof(smgpu_quality_trace_record) * qtRecs.size(), hipMemcpyDeviceToHost, h->stream));
     if (checkDeviceError(h)) return 1;
     int done = 0;
     while (done < launched && (hs[done].nNearTies & kStatsWritten)) ++done;
+    if (traced) {
+        for (size_t r = 0; r < qtRecs.size(); ++r)
+            if (qtSlotIter[r] < done && qtRecs[r].iteration != 0) h->qtPending.push_back(qtRecs[r]);
+        h->qtIter += done;
+    }
     for (int i = 0; i < done; ++i) hs[i].nNearTies &= kStatsWritten - 1;
     if (stats) std::memcpy(stats, hs.data(), sizeof(smgpu_iter_stats) * (size_t)done);
     if (nDone) *nDone = done;
@@ -2156,6 +2193,7 @@ int smgpu_halo_set_exchange_stream(smgpu_handle* h, int32_t useExchangeStream, v
 
 int smgpu_halo_configure(smgpu_handle* h, const smgpu_halo_desc* d) {
     if (!h || !d) return fail("null argument");
+    if (h->qtInterval > 0) return fail("smgpu_halo_configure: the quality trace is on (smgpu_set_quality_trace), and a trace is not available on an engine with a halo; switch it off first");
     HIP_OK(hipSetDevice(h->device));
     // the host's buffers may still be being initialised on the host's streams
     HIP_OK(hipDeviceSynchronize());
@@ -3306,6 +3344,9 @@ static int qualityGeometry(smgpu_handle* h) {
     std::memcpy(launches, h->launches, sizeof(launches));
     h->timing = false;
     h->writeFaces = true;
+    // a loop that relTol stopped leaves its stop word set until the next smgpu_iterate clears it, and the geometry kernels return at
+    // once on that word: the report would be one of the face values and cell centres of the last iteration's start
+    HIP_OK(hipMemsetAsync(&h->st.acc->stop, 0, sizeof(int), h->stream));
     const int rcg = runGeometry(h);
     h->writeFaces = false;
     h->timing = timing;
@@ -3422,6 +3463,25 @@ static int runQuality(smgpu_handle* h, const char* api, const smgpu_quality_para
     return 0;
 }
 
+// ---- the quality history (kernels_quality_trace.hpp, DESIGN.md "Mesh quality", 10.10) ----
+template <int T, bool ORG>
+static void launchQualityGeomTileAs(smgpu_handle* h, const State& ts, bool fused, int nT, const smgpu_iter_stats* gate) {
+    if (fused) {
+        ensureDynLds(k_quality_geom_tile<T, ORG>, h->device, h->geomLds);
+        hipLaunchKernelGGL((k_quality_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, nT, h->xcdMap,
+                           h->qtThr, h->qtCellPart, gate);
+    } else {   // the report's geometry launch: writeFaces, no face averages, and the engine's deferred finish is not this launch's to close
+        ensureDynLds(k_geom_tile<T, ORG>, h->device, h->geomLds);
+        hipLaunchKernelGGL((k_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, 0, 1,
+                           (const int*)nullptr, nT, h->xcdMap, 0, 0, (double*)nullptr, (double*)nullptr);
+    }
+}
+template <int T>
+static void launchQualityGeomTile(smgpu_handle* h, const State& ts, bool fused, int nT, const smgpu_iter_stats* gate) {
+    if (h->foamOrg) launchQualityGeomTileAs<T, true>(h, ts, fused, nT, gate);
+    else launchQualityGeomTileAs<T, false>(h, ts, fused, nT, gate);
+}
+
 // the -allGeometry checks (DESIGN.md "Mesh quality", 10.6 and 10.8).  serial: geometry, the cell pass (volumes into h->qgVol), the face
 // pass, the final reduction into h->qgOut; coupled: the volumes are those of the last pack_volumes, the record goes to h->qgPartOut
 template <bool Coupled>
@@ -3536,6 +3596,115 @@ static int qualityField(smgpu_handle* h, const QualityFields& t, const char* api
     return rc;
 }
 }  // extern "C++"
+
+static void qualityTraceFree(smgpu_handle* h) {
+    for (void** p : {(void**)&h->qtCellCtr, (void**)&h->qtAcc, (void**)&h->qtFacePart, (void**)&h->qtCellPart, (void**)&h->qtCellFold, (void**)&h->qtSlab})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    h->qtSlabCap = 0;
+}
+static bool qualityTraceFused(const smgpu_handle* h) { return h->qtFusedWanted && h->useTiles && h->gt.nTiles > 0; }
+// start of a traced smgpu_iterate call: the trace's device memory (on the first one), and a zeroed slab with one record per due
+// iteration of the call (iteration == 0: not written)
+static int qualityTraceBegin(smgpu_handle* h, int nIters) {
+    if (qualityEnsure(h)) return 1;
+    const MeshView& m = h->mv;
+    if (!h->qtAcc) {
+        const size_t nFB = (size_t)std::max(1, qualityGrid(m.nFaces)), nCB = (size_t)std::max(1, qualityGrid(m.nCells));
+        const size_t nT = h->useTiles ? (size_t)std::max(1, h->gt.nTiles) : 1;
+        hipError_t e = hipMalloc((void**)&h->qtCellCtr, sizeof(double) * 3 * (size_t)std::max(1, m.nCells));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->qtFacePart, sizeof(QFace) * nFB);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->qtCellPart, sizeof(QCell) * std::max(nCB, nT));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->qtCellFold, sizeof(QCell) * (size_t)std::max(1, qualityGrid((int)nT)));
+        if (e == hipSuccess) e = hipMalloc((void**)&h->qtAcc, sizeof(Accum));
+        if (e != hipSuccess) {
+            qualityTraceFree(h);
+            return fail(std::string("mesh quality: device memory for the quality trace: ") + hipGetErrorString(e));
+        }
+        HIP_OK(hipMemsetAsync(h->qtAcc, 0, sizeof(Accum), h->stream));
+    }
+    const int64_t first = h->qtIter + 1, last = h->qtIter + nIters;
+    const int nDue = (int)(last / h->qtInterval - (first - 1) / h->qtInterval);
+    if (nDue > h->qtSlabCap) {
+        if (h->qtSlab) {   // outgrown (nothing of the trace is in flight between two smgpu_iterate calls)
+            HIP_OK(hipStreamSynchronize(h->stream));
+            (void)hipFree(h->qtSlab);
+            h->qtSlab = nullptr;
+            h->qtSlabCap = 0;
+        }
+        const hipError_t e = hipMalloc((void**)&h->qtSlab, sizeof(smgpu_quality_trace_record) * (size_t)nDue);
+        if (e != hipSuccess) return fail(std::string("mesh quality: device memory for the quality trace: ") + hipGetErrorString(e));
+        h->qtSlabCap = nDue;
+    }
+    if (nDue > 0) HIP_OK(hipMemsetAsync(h->qtSlab, 0, sizeof(smgpu_quality_trace_record) * (size_t)nDue, h->stream));
+    return 0;
+}
+// the trace of the points ptsCur now names, behind everything queued on the engine's stream; outside the engine's launch counters
+// and timing events, like the report's geometry launch.  The geometry writes the trace's own cell centres and tests the trace's
+// own stop word, wantAvg is 0 and no deferred finish rides in it: the loop finds everything it reads as it left it.
+static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate) {
+    if (slot >= h->qtSlabCap) return fail("mesh quality: quality trace slab overrun");
+    const MeshView& m = h->mv;
+    State ts = h->st;
+    ts.cellCtr = h->qtCellCtr;
+    ts.acc = h->qtAcc;
+    ts.stats = nullptr;
+    const bool fused = qualityTraceFused(h);
+    const int nFB = qualityGrid(m.nFaces);
+    int nCB = qualityGrid(m.nCells);
+    const QCell* cPart = h->qtCellPart;
+    if (h->useTiles) {
+        const int nT = h->gt.nTiles;
+        if (nT > 0) {
+            if (h->geomT == 64) launchQualityGeomTile<64>(h, ts, fused, nT, gate);
+            else if (h->geomT == 128) launchQualityGeomTile<128>(h, ts, fused, nT, gate);
+            else launchQualityGeomTile<256>(h, ts, fused, nT, gate);
+        }
+    } else {
+        if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
+        if (m.nCells > 0) hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
+    }
+    if (nFB > 0)
+        hipLaunchKernelGGL(k_quality_faces<false>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, ts.ptsCur, ts.fCtr, ts.fArea, ts.cellCtr, h->qOwn, h->qNei,
+                           QCoupling<false>{}, h->qtThr, h->qtFacePart, (double*)nullptr, (double*)nullptr);
+    if (fused) {
+        nCB = qualityGrid(h->gt.nTiles);
+        hipLaunchKernelGGL(k_quality_trace_fold, dim3(nCB), dim3(kQualityBlock), 0, h->stream, h->qtCellPart, h->gt.nTiles, h->qtCellFold, gate);
+        cPart = h->qtCellFold;
+    } else if (nCB > 0) {
+        hipLaunchKernelGGL(k_quality_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, ts.fCtr, ts.fArea, h->qtThr, h->qtCellPart, (double*)nullptr,
+                           (double*)nullptr, (double*)nullptr);
+    }
+    hipLaunchKernelGGL(k_quality_trace_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qtFacePart, nFB, cPart, nCB, m.nCells, m.nFaces, m.nInternalFaces,
+                       (long long)number, h->qtSlab + slot, gate);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_set_quality_trace(smgpu_handle* h, int32_t interval, const smgpu_quality_params* p) {
+    if (!h) return fail("null handle");
+    if (interval < 0) return fail("smgpu_set_quality_trace: interval < 0");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    HIP_OK(hipSetDevice(h->device));
+    h->qtInterval = interval;
+    h->qtIter = 0;
+    h->qtPending.clear();
+    h->qtThr = qualityThresholds(p);
+    if (interval == 0) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        qualityTraceFree(h);
+    }
+    return 0;
+}
+int smgpu_get_quality_trace(smgpu_handle* h, smgpu_quality_trace_record* out, int64_t cap, int64_t* n) {
+    if (!h || !n) return fail("null argument");
+    const int64_t have = (int64_t)h->qtPending.size();
+    if (!out) { *n = have; return 0; }
+    if (cap < have) return fail("smgpu_get_quality_trace: cap " + std::to_string(cap) + " is below the " + std::to_string(have) + " pending records");
+    if (have > 0) std::memcpy(out, h->qtPending.data(), sizeof(smgpu_quality_trace_record) * (size_t)have);
+    h->qtPending.clear();
+    *n = have;
+    return 0;
+}
 
 int smgpu_mesh_quality(smgpu_handle* h, const smgpu_quality_params* p, smgpu_quality* out) {
     if (!h || !out) return fail("null argument");

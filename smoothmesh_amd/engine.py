@@ -80,6 +80,33 @@ class MeshQuality:
     nHighAspectCells: int
 
 
+@dataclass
+class QualityTraceRecord:
+    """One record of the run's quality history (include/smgpu.h, smgpu_quality_trace_record; DESIGN.md "Mesh quality", 10.10): the
+    fields of MeshQuality that do not depend on the order of a floating-point sum, of the points after iteration `iteration`
+    (1-based, counted since set_quality_trace).  Every field has the bits mesh_quality() gives for the same points."""
+    iteration: int
+    minVolume: float
+    maxVolume: float
+    nNonPositiveVolume: int
+    minVolumeCell: int
+    minFaceArea: float
+    maxFaceArea: float
+    nZeroAreaFaces: int
+    maxNonOrth: float
+    nSevereNonOrth: int
+    nErrorNonOrth: int
+    maxNonOrthFace: int
+    maxSkewness: float
+    nSkewFaces: int
+    maxSkewFace: int
+    nWrongOrientedFaces: int
+    maxOpenness: float
+    nOpenCells: int
+    maxAspectRatio: float
+    nHighAspectCells: int
+
+
 QUALITY_FIELDS = ("cellVolume", "cellOpenness", "cellAspectRatio", "faceNonOrthogonality", "faceSkewness")
 # the failing elements of the report as sets (DESIGN.md "Mesh quality", 10.5), in smgpu_quality_sets' order: name, topoSet class,
 # the report counts whose sum is the set's size, and the words of the "<<Writing" line
@@ -503,6 +530,23 @@ class SmoothEngine:
         q = _ffi.Quality()
         self._check(self._lib.smgpu_mesh_quality(self._h, C.byref(p), C.byref(q)))
         return MeshQuality(**{n: getattr(q, n) for n, _ in q._fields_})
+
+    def set_quality_trace(self, interval, nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0):
+        """Quality history of the run (include/smgpu.h, smgpu_set_quality_trace): interval > 0 makes iterate() leave one
+        QualityTraceRecord after every interval-th iteration that runs, counted across calls from this call on, with no
+        synchronisation added to the loop; 0 switches the trace off.  Discards unread records.  Refused on an engine with a halo."""
+        p = _ffi.QualityParams(nonOrthThreshold, skewThreshold, closedThreshold, aspectThreshold)
+        self._check(self._lib.smgpu_set_quality_trace(self._h, int(interval), C.byref(p)))
+
+    def quality_trace(self) -> list:
+        """The pending records of the quality history, in ascending iteration; clears them."""
+        n = C.c_int64(0)
+        self._check(self._lib.smgpu_get_quality_trace(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        buf = (_ffi.QualityTraceRecord * n.value)()
+        self._check(self._lib.smgpu_get_quality_trace(self._h, buf, n.value, C.byref(n)))
+        return [QualityTraceRecord(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
 
     def quality_field(self, name) -> np.ndarray:
         """Per-element quality field in polyMesh order: one of QUALITY_FIELDS (non-orthogonality in degrees, 0 on boundary faces)."""

@@ -10,13 +10,15 @@ The -allGeometry checks and the motion criteria of a decomposed mesh (DESIGN.md 
 combine_quality_motion, decomposed_mesh_quality_geometry, decomposed_mesh_quality_motion and the drivers' methods of those names.
 Their findings as sets: decomposed_quality_geometry_sets, decomposed_quality_motion_sets, the drivers'
 quality_geometry_sets / quality_motion_sets; write_quality_sets and format_sets_written take the table of the report.
+The quality history of a run is the engine's (SmoothEngine.set_quality_trace / quality_trace); format_trace_line
+and format_trace_warning give the front-end's lines of a record.
 """
 from dataclasses import dataclass, fields
 
 import numpy as np
 
-from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QUALITY_FIELDS, QUALITY_GEOMETRY_FIELDS,  # noqa: F401
-                     QUALITY_MOTION_FIELDS, QUALITY_SETS, QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS)
+from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityTraceRecord, QUALITY_FIELDS,  # noqa: F401
+                     QUALITY_GEOMETRY_FIELDS, QUALITY_MOTION_FIELDS, QUALITY_SETS, QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS)
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
 _COUNTS = ("nNonPositiveVolume", "nZeroAreaFaces", "nSevereNonOrth", "nErrorNonOrth", "nSkewFaces", "nWrongOrientedFaces",
@@ -427,6 +429,22 @@ def format_motion_lines(t):
             f"    faceTwist min {f(t.minTwist)} average {f(t.avgTwist)} low {t.nLowTwistFaces} minFace {t.minTwistFace}\n"
             f"    triangleTwist min {f(t.minTriangleTwist)} average {f(t.avgTriangleTwist)} low {t.nLowTriangleTwistFaces} "
             f"minFace {t.minTriangleTwistFace}\n")
+
+
+def format_trace_line(rec):
+    """the line smoothMesh -qualityInterval prints under the iteration line of a traced iteration (csrc/host/smoothMesh_main.cpp,
+    printQualityTrace), of a QualityTraceRecord"""
+    g = lambda x: "%.9g" % x  # noqa: E731
+    return (f"    quality iteration={rec.iteration} minVolume {g(rec.minVolume)} nonPositive {rec.nNonPositiveVolume} "
+            f"maxNonOrth {g(rec.maxNonOrth)} error {rec.nErrorNonOrth} maxSkewness {g(rec.maxSkewness)} "
+            f"wrongOriented {rec.nWrongOrientedFaces} maxOpenness {g(rec.maxOpenness)} maxAspectRatio {g(rec.maxAspectRatio)}\n")
+
+
+def format_trace_warning(rec, initial):
+    """the line printed once per run, under the first traced iteration whose nNonPositiveVolume or nWrongOrientedFaces exceeds the
+    initial mesh's (`initial`: its MeshQuality)"""
+    return (f"    ***Iteration {rec.iteration}: {rec.nNonPositiveVolume} non-positive volume cells and {rec.nWrongOrientedFaces} "
+            f"wrongly oriented faces (initial mesh: {initial.nNonPositiveVolume}, {initial.nWrongOrientedFaces})\n")
 
 
 def format_report(q, which="mesh", geometry=None, motion=None):
