@@ -203,6 +203,50 @@ typedef struct smgpu_quality_trace_record {
 int smgpu_set_quality_trace(smgpu_handle* h, int32_t interval, const smgpu_quality_params* p);   /* 0 = off; p NULL = defaults */
 int smgpu_get_quality_trace(smgpu_handle* h, smgpu_quality_trace_record* out, int64_t cap, int64_t* n);
 
+/* ---- a guard on the quality history (DESIGN.md "Mesh quality", 10.11) ----------------------------------------------------
+ * smgpu_set_quality_guard(p, on != 0) arms the guard; it needs the trace on.  Arming runs the trace's own launches once on the
+ * current points: the result is `baseline` (iteration 0), kept on the device; and it takes the first snapshot of those points,
+ * numbered with the trace's running number (0 when the guard is armed directly after smgpu_set_quality_trace).  From then
+ * on smgpu_iterate queues, behind the trace of every traced iteration, a verdict and a snapshot on the engine's stream:
+ *   verdict   for each criterion in `criteria`: record.count > baseline.count, with the counts nNonPositiveVolume,
+ *             nWrongOrientedFaces and nErrorNonOrth of the trace record -- integers only, so the host can repeat every verdict
+ *             from the records.  A record that fails TRIPS the guard: the device sets the loop's stop word, and everything queued
+ *             behind is the no-op the stop by relTol makes it.
+ *   snapshot  after a record that passed: a copy of the per-point state an iteration carries to the next -- the points and,
+ *             with smgpu_set_layers, the layer normals -- in buffers of the guard (allocated at arming, outside deviceBytes).
+ * While armed smgpu_iterate closes every iteration with k_finish (the deferred finish of relTol <= 0 is off: one more K_FINISH
+ * launch per iteration in smgpu_counters) and polls the stop word every eighth iteration, as with relTol > 0.  The results of an
+ * armed run that does not trip -- points, statistics, trace records, near-tie census -- are those of the run without a guard, bit
+ * for bit.
+ *
+ * A call of smgpu_iterate that trips returns the statistics and trace records of every iteration that ran, the tripping one
+ * included (*nDone counts it).  Before it returns it restores the snapshot and, with `refine`, looks for the exact last
+ * iteration that passes: from the snapshot it steps one iteration at a time, each followed by a trace and a verdict, at most
+ * interval - 1 times; the first step that fails ends the search and the last state that passed is restored.  These steps leave
+ * no statistics, no trace records, and nothing in smgpu_counters or the near-tie census.  restoredIteration is the largest r for
+ * which every traced or refined iteration from the snapshot through r passed; the trace's running number becomes r, so that the
+ * number names the points.  The guard then disarms itself; smgpu_get_quality_guard keeps answering.
+ *
+ * smgpu_quality_guard_restore is the same rollback on request, for callers who judge the trace by criteria of their own: to
+ * snapshotIteration, without refining; the guard stays armed and the running number becomes snapshotIteration.  Pending trace
+ * records stay.  Refused when the guard is not armed.
+ *
+ * Not covered: an engine with a halo (refused with the trace's wording; so smoothMesh -parallel and the smoothers of halo.py
+ * have no guard) and an engine with boundary point smoothing (refused: its point normals are a running blend across
+ * iterations and its corner lists are host state, neither of which the snapshot holds).  smgpu_set_boundary_smoothing and
+ * smgpu_halo_configure are refused while the guard is armed; smgpu_set_quality_trace disarms it, because it restarts the
+ * numbering.  on == 0 disarms and frees the guard's device memory. */
+enum { SMGPU_GUARD_NONPOSITIVE_VOLUME = 1, SMGPU_GUARD_WRONG_ORIENTED = 2, SMGPU_GUARD_ERROR_NONORTH = 4 };
+typedef struct smgpu_quality_guard_params { uint32_t criteria; int32_t refine; } smgpu_quality_guard_params;   /* NULL params = {1|2, 1} */
+typedef struct smgpu_quality_guard_state {
+    int32_t armed, tripped;  uint32_t reasons;
+    int64_t snapshotIteration, trippedIteration, restoredIteration;      /* trace numbers; 0 = the points at arming */
+    smgpu_quality_trace_record baseline, tripRecord;
+} smgpu_quality_guard_state;
+int smgpu_set_quality_guard(smgpu_handle* h, const smgpu_quality_guard_params* p, int32_t on);
+int smgpu_get_quality_guard(smgpu_handle* h, smgpu_quality_guard_state* out);
+int smgpu_quality_guard_restore(smgpu_handle* h);
+
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):
  *   1. smgpu_quality_coupled_pack: the geometry of the current points (the loop's own launch, uncounted), then the owner cell

@@ -116,6 +116,17 @@ class QualityTraceRecord(C.Structure):
                                              if n not in ("nCells", "nFaces", "nInternalFaces", "totalVolume", "avgNonOrth")]
 
 
+class QualityGuardParams(C.Structure):
+    _fields_ = [("criteria", C.c_uint32), ("refine", C.c_int32)]
+
+
+class QualityGuardState(C.Structure):
+    """smgpu_quality_guard_state"""
+    _fields_ = [("armed", C.c_int32), ("tripped", C.c_int32), ("reasons", C.c_uint32),
+                ("snapshotIteration", C.c_int64), ("trippedIteration", C.c_int64), ("restoredIteration", C.c_int64),
+                ("baseline", QualityTraceRecord), ("tripRecord", QualityTraceRecord)]
+
+
 class QualityGeometryParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("concaveThreshold", "flatnessThreshold", "weightThreshold", "volRatioThreshold",
                                           "determinantThreshold")]
@@ -225,6 +236,9 @@ SYMBOLS = {
     "smgpu_quality_field": (C.c_int, [C.c_void_p, C.c_char_p, c_f64p, C.POINTER(C.c_int64)]),
     "smgpu_set_quality_trace": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(QualityParams)]),
     "smgpu_get_quality_trace": (C.c_int, [C.c_void_p, C.POINTER(QualityTraceRecord), C.c_int64, C.POINTER(C.c_int64)]),
+    "smgpu_set_quality_guard": (C.c_int, [C.c_void_p, C.POINTER(QualityGuardParams), C.c_int32]),
+    "smgpu_get_quality_guard": (C.c_int, [C.c_void_p, C.POINTER(QualityGuardState)]),
+    "smgpu_quality_guard_restore": (C.c_int, [C.c_void_p]),
     "smgpu_quality_coupled_pack": (C.c_int, [C.c_void_p, C.POINTER(QualityCoupling), C.c_void_p, C.POINTER(C.c_int64)]),
     "smgpu_quality_coupled_report": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(QualityPart)]),
     "smgpu_quality_coupled_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),

@@ -96,7 +96,7 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "layerMaxBlendingFraction", "layerEdgeLength", "layerExpansionRatio", "minLayers",
                                "maxLayers", "layerPatches", "smoothingPatches", "internalSmoothingBlendingFraction",
                                "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets", "allGeometry",
-                               "meshQuality", "qualityInterval"};
+                               "meshQuality", "qualityInterval", "qualityGuard", "qualityGuardRefine"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -116,6 +116,9 @@ Options parseArgs(int argc, char** argv) {
                       "        triangle twist, the meshQualityDict criteria of checkMesh -meshQuality)\n"
                       "       [-qualityInterval n] (with -checkQuality: a quality line under every n-th iteration line, traced on the GPU\n"
                       "        without stopping the loop, and a warning at the first traced iteration that tangles the mesh)\n"
+                      "       [-qualityGuard b]   (with -qualityInterval: stop at the first traced iteration with more non-positive volume cells\n"
+                      "        or wrongly oriented faces than the initial mesh, and write the last mesh before it instead)\n"
+                      "       [-qualityGuardRefine b]  (default true: find the exact last good iteration, not only the last traced one)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -531,6 +534,13 @@ int main(int argc, char** argv) {
         fatal("-qualityInterval is not available with -parallel: it traces the measures of the -checkQuality report, which is serial only");
     if (qualityTrace && !checkQuality) fatal("-qualityInterval needs -checkQuality true: its lines are measures of the quality report");
     if (qualityTrace && (qualityInterval < 1 || qualityInterval > 0x7fffffffL)) fatal("qualityInterval must be positive");
+    const bool qualityGuard = opt.getB("qualityGuard", false);
+    const bool qualityGuardRefine = opt.getB("qualityGuardRefine", true);
+    if (qualityGuard && opt.parallel)
+        fatal("-qualityGuard is not available with -parallel: it judges the records of -qualityInterval, which is serial only");
+    if (qualityGuard && !checkQuality) fatal("-qualityGuard needs -checkQuality true: it judges measures of the quality report");
+    if (qualityGuard && !qualityTrace) fatal("-qualityGuard needs -qualityInterval N: it judges the traced iterations");
+    if (opt.found("qualityGuardRefine") && !qualityGuard) fatal("-qualityGuardRefine needs -qualityGuard true");
     // SMOOTHMESH_TIMELINE=1: where this process's wall time goes, one stderr line per stage (seconds since main started)
     const bool timeline = std::getenv("SMOOTHMESH_TIMELINE") && std::atoi(std::getenv("SMOOTHMESH_TIMELINE")) > 0;
     auto mark = [&](const char* what) { if (timeline) std::fprintf(stderr, "[smoothMesh %8.3f s] %s\n", secondsSince(t0), what); };
@@ -711,6 +721,9 @@ int main(int argc, char** argv) {
                                      anySmoothingPatch;
     if (doBoundarySmoothing) OUTS("Enabled boundary point smoothing\n");
     else OUT("Boundary point smoothing is disabled. Missing smoothingPatches, or one or both of files:\n%s\n%s\n\n", targetSurfacesFile.c_str(), initEdgesFile.c_str());
+    if (qualityGuard && doBoundarySmoothing)
+        fatal("-qualityGuard is not available with boundary point smoothing: the point normals it blends from iteration to iteration and "
+              "its corner lists are not part of the guard's snapshot (run without -smoothingPatches, or without the guard)");
     if (doLayerTreatment && !doBoundarySmoothing)   // SM.C:2095-2098
         OUTS("WARNING: Boundary layer treatment will be done without boundary point smoothing. This can result in distorted boundary cells.\n");
 
@@ -1236,6 +1249,13 @@ int main(int argc, char** argv) {
     bool stopIteration = false;
     long i = 0;
     double timeValue = startIsConstant ? 0.0 : startValue;
+    // -qualityGuard: the guard on that history (include/smgpu.h, smgpu_set_quality_guard), armed on the initial
+    // points with everything set up: the engine stops the loop on the device and rolls the points back itself
+    if (qualityGuard) {
+        const smgpu_quality_guard_params gp{SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED, qualityGuardRefine ? 1 : 0};
+        check(smgpu_set_quality_guard(R[0].h, &gp, 1), "smgpu_set_quality_guard");
+    }
+    const double timeStart = timeValue;
     std::vector<smgpu_iter_stats> stats;
     double* dHist = nullptr;       // -parallel, relTol <= 0: the chunk's {residual, nFrozenPoints} records on the device
     size_t histCap = 0;
@@ -1323,9 +1343,20 @@ int main(int argc, char** argv) {
         }
         i += done;
         timeValue += done * deltaT;   // runTime++ per iteration, SM.C:2414
-        const bool hitTol = done > 0 && stats[(size_t)done - 1].residual < relTol;
+        smgpu_quality_guard_state guard{};
+        if (qualityGuard) check(smgpu_get_quality_guard(R[0].h, &guard), "smgpu_get_quality_guard");
+        if (guard.tripped) {   // the engine holds the mesh of iteration restoredIteration again: the run's counter and time go back to it
+            OUT("    ***Quality guard: iteration %lld: %lld non-positive volume cells and %lld wrongly oriented faces (initial mesh: %lld, %lld)\n",
+                (long long)guard.trippedIteration, (long long)guard.tripRecord.nNonPositiveVolume, (long long)guard.tripRecord.nWrongOrientedFaces,
+                (long long)guard.baseline.nNonPositiveVolume, (long long)guard.baseline.nWrongOrientedFaces);
+            OUT("    ***Quality guard: restored the mesh of iteration %lld, stopping.\n", (long long)guard.restoredIteration);
+            i = (long)guard.restoredIteration;
+            timeValue = timeStart + (double)i * deltaT;
+            stopIteration = true;
+        }
+        const bool hitTol = !guard.tripped && done > 0 && stats[(size_t)done - 1].residual < relTol;
         if (hitTol) { OUTS("Residual reached relTol, stopping."); stopIteration = true; }
-        if (i == centroidalIters) { OUTS("Maximum centroidalIters reached, stopping."); stopIteration = true; }
+        if (!guard.tripped && i == centroidalIters) { OUTS("Maximum centroidalIters reached, stopping."); stopIteration = true; }
         // SM.C:2416: write at stop or every writeInterval iterations (not after the very first one)
         if (stopIteration || ((i % writeInterval) == 0 && i > 1)) writeMesh(timeValue);
         if (done == 0) break;

@@ -23,6 +23,7 @@
 #include "kernels_quality_geom.hpp"
 #include "kernels_quality_motion.hpp"
 #include "kernels_quality_trace.hpp"
+#include "kernels_quality_guard.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"
@@ -266,6 +267,17 @@ struct smgpu_handle {
     smgpu_quality_trace_record* qtSlab = nullptr;
     int qtSlabCap = 0;
     std::vector<smgpu_quality_trace_record> qtPending;
+    // ... and of the guard on it (smgpu_set_quality_guard, kernels_quality_guard.hpp): allocated at arming, outside `allocs` too.
+    // qgPts / qgNormal: the snapshot; qgRec: the record slot of the baseline; qgState: what smgpu_get_quality_guard answers
+    bool qgArmed = false;
+    bool qgRefining = false;                // inside the search for the last good iteration: smgpu_iterate's body leaves no trace
+    bool qgTripPending = false;             // the call that just read back tripped: roll back before it returns
+    int qgLastVerdict = 0;                  // the verdict word after the last read-back
+    smgpu_quality_guard_params qgPrm{SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED, 1};
+    smgpu_quality_guard_state qgState{};
+    GuardDev* qgDev = nullptr;
+    smgpu_quality_trace_record* qgRec = nullptr;
+    double *qgPts = nullptr, *qgNormal = nullptr;
     uint64_t qEpoch = 1, qPackEpoch = 0;   // qEpoch moves whenever the points (or the geometry variant) may have changed
     bool iterOpen = false;                  // between smgpu_iter_begin and smgpu_iter_end
 };
@@ -1155,7 +1167,8 @@ int smgpu_destroy(smgpu_handle* h) {
     for (void* p : {(void*)h->qOwn, (void*)h->qNei, (void*)h->qFacePart, (void*)h->qCellPart, (void*)h->qOut, (void*)h->qProcFace, (void*)h->qSlot,
                     (void*)h->qPartOut, (void*)h->qgVol, (void*)h->qgFacePart, (void*)h->qgCellPart, (void*)h->qgOut,
                     (void*)h->qmFacePart, (void*)h->qmOut, (void*)h->qgPartOut, (void*)h->qmPartOut, (void*)h->qtCellCtr, (void*)h->qtAcc,
-                    (void*)h->qtFacePart, (void*)h->qtCellPart, (void*)h->qtCellFold, (void*)h->qtSlab})
+                    (void*)h->qtFacePart, (void*)h->qtCellPart, (void*)h->qtCellFold, (void*)h->qtSlab, (void*)h->qgDev, (void*)h->qgRec,
+                    (void*)h->qgPts, (void*)h->qgNormal})
         if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
@@ -1935,9 +1948,19 @@ static int flushDeferred(smgpu_handle* h) {
 
 // the quality history (smgpu_set_quality_trace; defined with the mesh quality report below)
 static int qualityTraceBegin(smgpu_handle* h, int nIters);
-static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate);
+static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, smgpu_quality_trace_record* out = nullptr);
+// the guard on it (smgpu_set_quality_guard; defined there as well)
+static int qualityGuardQueue(smgpu_handle* h, const smgpu_quality_trace_record* rec, int64_t number, const smgpu_iter_stats* gate);
+static int qualityGuardAfterTrip(smgpu_handle* h);
 
+static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_stats* stats, int32_t* nDone);
 int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_stats* stats, int32_t* nDone) {
+    if (iterateBody(h, nIters, relTol, stats, nDone)) return 1;
+    // a call that tripped the quality guard: its statistics and trace records stand; the points go back to the last good state
+    if (h->qgTripPending && qualityGuardAfterTrip(h)) return 1;
+    return 0;
+}
+static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_stats* stats, int32_t* nDone) {
     if (!h) return fail("null handle");
     if (!h->prmSet) return fail("smgpu_set_params has not been called");
     if (h->haloOn) return fail("smgpu_iterate is the single-rank loop; use smgpu_iter_begin/mid/end with a halo");
@@ -1977,7 +2000,9 @@ int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_sta
     int launched = 0;
     // relTol <= 0 cannot stop the loop (residual >= 0): the end-of-iteration reduction then rides in the next
     // iteration's geometry launch instead of a launch of its own; the last iteration is closed by k_finish
-    const bool deferFinish = relTol <= 0.0 && h->useTiles && h->geomT >= 64 && envInt("SMGPU_DEFER_FINISH", 1);
+    // (not under the quality guard: its verdict on iteration i may stop the loop, and stats[i] has to be written before it)
+    const bool guarded = h->qgArmed;
+    const bool deferFinish = relTol <= 0.0 && !guarded && h->useTiles && h->geomT >= 64 && envInt("SMGPU_DEFER_FINISH", 1);
     if (flushDeferred(h)) return 1;
     // quality history: the iterations of this call whose running number is due get a slot of the call's record slab, in order
     const bool traced = h->qtInterval > 0;
@@ -2001,12 +2026,14 @@ int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_sta
         ++launched;
         // (with relTol > 0 this iteration may turn out not to have run: k_finish has written stats[i] by then, or has not)
         if (traced && (h->qtIter + i + 1) % h->qtInterval == 0) {
-            if (qualityTraceQueue(h, (int)qtSlotIter.size(), h->qtIter + i + 1, relTol > 0.0 ? h->dStats + i : nullptr)) return 1;
+            const smgpu_iter_stats* gate = (relTol > 0.0 || guarded) ? h->dStats + i : nullptr;
+            if (qualityTraceQueue(h, (int)qtSlotIter.size(), h->qtIter + i + 1, gate)) return 1;
+            if (guarded && qualityGuardQueue(h, h->qtSlab + qtSlotIter.size(), h->qtIter + i + 1, gate)) return 1;
             qtSlotIter.push_back(i);
         }
         // a positive relTol can stop the loop: poll the device flag now and then so a converged run
-        // does not queue thousands of no-op launches (relTol <= 0 can never stop: residual >= 0)
-        if (relTol > 0.0 && (i % 8) == 7 && i + 1 < nIters) {
+        // does not queue thousands of no-op launches (relTol <= 0 can never stop: residual >= 0); so can the quality guard
+        if ((relTol > 0.0 || guarded) && (i % 8) == 7 && i + 1 < nIters) {
             int stop = 0;
             HIP_OK(hipMemcpyAsync(&stop, &h->st.acc->stop, sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIP_OK(hipStreamSynchronize(h->stream));
@@ -2017,13 +2044,26 @@ int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_sta
     HIP_OK(hipMemcpyAsync(hs.data(), h->dStats, sizeof(smgpu_iter_stats) * (size_t)launched, hipMemcpyDeviceToHost, h->stream));
     std::vector<smgpu_quality_trace_record> qtRecs(qtSlotIter.size());
     if (!qtRecs.empty()) HIP_OK(hipMemcpyAsync(qtRecs.data(), h->qtSlab, sizeof(smgpu_quality_trace_record) * qtRecs.size(), hipMemcpyDeviceToHost, h->stream));
+    GuardDev gd{};
+    if (guarded) HIP_OK(hipMemcpyAsync(&gd, h->qgDev, sizeof(GuardDev), hipMemcpyDeviceToHost, h->stream));
     if (checkDeviceError(h)) return 1;
     int done = 0;
     while (done < launched && (hs[done].nNearTies & kStatsWritten)) ++done;
     if (traced) {
-        for (size_t r = 0; r < qtRecs.size(); ++r)
+        for (size_t r = 0; r < qtRecs.size() && !h->qgRefining; ++r)
             if (qtSlotIter[r] < done && qtRecs[r].iteration != 0) h->qtPending.push_back(qtRecs[r]);
         h->qtIter += done;
+    }
+    if (guarded) {
+        h->qgLastVerdict = gd.verdict;
+        h->qgState.snapshotIteration = gd.snapshotIteration;
+        if (gd.tripped && !h->qgRefining) {
+            h->qgState.tripped = 1;
+            h->qgState.reasons = gd.reasons;
+            h->qgState.trippedIteration = gd.trippedIteration;
+            h->qgState.tripRecord = gd.tripRecord;
+            h->qgTripPending = true;
+        }
     }
     for (int i = 0; i < done; ++i) hs[i].nNearTies &= kStatsWritten - 1;
     if (stats) std::memcpy(stats, hs.data(), sizeof(smgpu_iter_stats) * (size_t)done);
@@ -2193,6 +2233,7 @@ int smgpu_halo_set_exchange_stream(smgpu_handle* h, int32_t useExchangeStream, v
 
 int smgpu_halo_configure(smgpu_handle* h, const smgpu_halo_desc* d) {
     if (!h || !d) return fail("null argument");
+    if (h->qgArmed) return fail("smgpu_halo_configure: the quality guard is armed (smgpu_set_quality_guard), and a guard is not available on an engine with a halo; disarm it first");
     if (h->qtInterval > 0) return fail("smgpu_halo_configure: the quality trace is on (smgpu_set_quality_trace), and a trace is not available on an engine with a halo; switch it off first");
     HIP_OK(hipSetDevice(h->device));
     // the host's buffers may still be being initialised on the host's streams
@@ -2963,6 +3004,7 @@ int smgpu_layers_shared(smgpu_handle* h, int32_t field, int32_t set, double* v) 
 int smgpu_set_layers(smgpu_handle* h, const smgpu_layer_desc* d, int32_t* enabled) {
     if (!h || !d) return fail("null argument");
     if (h->haloOn) return fail("smgpu_set_layers is the serial set-up; with a halo use smgpu_layers_begin / step / shared");
+    if (h->qgArmed) return fail("smgpu_set_layers: the quality guard is armed (smgpu_set_quality_guard), and its snapshot was sized without the layer normals; disarm it, set the layers, arm it again");
     int32_t on = 0, maxIter = 0;
     if (smgpu_layers_begin(h, d, &on, &maxIter)) return 1;
     if (enabled) *enabled = on;
@@ -3256,6 +3298,7 @@ int smgpu_boundary_shared(smgpu_handle* h, int32_t field, int32_t set, double* v
 int smgpu_set_boundary_smoothing(smgpu_handle* h, const smgpu_boundary_desc* d, smgpu_boundary_info* info) {
     if (!h || !d) return fail("null argument");
     if (h->haloOn) return fail("smgpu_set_boundary_smoothing is the serial set-up; with a halo use smgpu_boundary_stats / begin / step / shared");
+    if (h->qgArmed) return fail("smgpu_set_boundary_smoothing: the quality guard is armed (smgpu_set_quality_guard), and its snapshot does not hold the state boundary point smoothing carries from one iteration to the next; disarm it first");
     double minEdge = 0.0, bb[6];
     if (smgpu_boundary_stats(h, &minEdge, bb)) return 1;
     smgpu_boundary_info bi{};
@@ -3641,8 +3684,9 @@ static int qualityTraceBegin(smgpu_handle* h, int nIters) {
 // the trace of the points ptsCur now names, behind everything queued on the engine's stream; outside the engine's launch counters
 // and timing events, like the report's geometry launch.  The geometry writes the trace's own cell centres and tests the trace's
 // own stop word, wantAvg is 0 and no deferred finish rides in it: the loop finds everything it reads as it left it.
-static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate) {
-    if (slot >= h->qtSlabCap) return fail("mesh quality: quality trace slab overrun");
+static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, smgpu_quality_trace_record* out) {
+    if (!out && slot >= h->qtSlabCap) return fail("mesh quality: quality trace slab overrun");
+    if (!out) out = h->qtSlab + slot;
     const MeshView& m = h->mv;
     State ts = h->st;
     ts.cellCtr = h->qtCellCtr;
@@ -3675,16 +3719,18 @@ static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const sm
                            (double*)nullptr, (double*)nullptr);
     }
     hipLaunchKernelGGL(k_quality_trace_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qtFacePart, nFB, cPart, nCB, m.nCells, m.nFaces, m.nInternalFaces,
-                       (long long)number, h->qtSlab + slot, gate);
+                       (long long)number, out, gate);
     HIP_OK(hipGetLastError());
     return 0;
 }
 
+static int qualityGuardDisarm(smgpu_handle* h, bool release);
 int smgpu_set_quality_trace(smgpu_handle* h, int32_t interval, const smgpu_quality_params* p) {
     if (!h) return fail("null handle");
     if (interval < 0) return fail("smgpu_set_quality_trace: interval < 0");
     if (h->haloOn) return fail(kQualityHaloRefusal);
     HIP_OK(hipSetDevice(h->device));
+    if (qualityGuardDisarm(h, true)) return 1;   // the numbering restarts: the guard's iteration numbers would name other points
     h->qtInterval = interval;
     h->qtIter = 0;
     h->qtPending.clear();
@@ -3703,6 +3749,144 @@ int smgpu_get_quality_trace(smgpu_handle* h, smgpu_quality_trace_record* out, in
     if (have > 0) std::memcpy(out, h->qtPending.data(), sizeof(smgpu_quality_trace_record) * (size_t)have);
     h->qtPending.clear();
     *n = have;
+    return 0;
+}
+
+// ---- the guard on the quality history (kernels_quality_guard.hpp, DESIGN.md "Mesh quality", 10.11) ----
+static void qualityGuardFree(smgpu_handle* h) {
+    for (void** p : {(void**)&h->qgDev, (void**)&h->qgRec, (void**)&h->qgPts, (void**)&h->qgNormal})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+}
+static int qualityGuardDisarm(smgpu_handle* h, bool release) {
+    h->qgArmed = false;
+    h->qgTripPending = false;
+    h->qgState.armed = 0;
+    if (release && h->qgDev) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        qualityGuardFree(h);
+    }
+    return 0;
+}
+// the per-point state an iteration carries to the next (State's non-const pointers that an iteration reads before it writes them:
+// ptsCur, and layerNormal with layers) between the engine and the snapshot, on the engine's stream
+static int qualityGuardCopy(smgpu_handle* h, bool restore, int64_t number, bool needGood) {
+    const long long n = 3 * (long long)h->mv.nPoints;
+    const bool normals = h->layersOn && h->qgNormal && h->st.layerNormal;
+    const double *s0 = restore ? h->qgPts : h->st.ptsCur, *s1 = normals ? (restore ? h->qgNormal : h->st.layerNormal) : nullptr;
+    double *d0 = restore ? h->st.ptsCur : h->qgPts, *d1 = normals ? (restore ? h->st.layerNormal : h->qgNormal) : nullptr;
+    const int grid = (int)std::max<long long>(1, ((n >> 1) + (long long)kGuardBlock * kGuardPer - 1) / ((long long)kGuardBlock * kGuardPer));
+    if (normals) hipLaunchKernelGGL(k_quality_guard_snapshot<true>, dim3(grid), dim3(kGuardBlock), 0, h->stream, s0, d0, s1, d1, n, (long long)number, h->qgDev, needGood ? 1 : 0);
+    else hipLaunchKernelGGL(k_quality_guard_snapshot<false>, dim3(grid), dim3(kGuardBlock), 0, h->stream, s0, d0, s1, d1, n, (long long)number, h->qgDev, needGood ? 1 : 0);
+    HIP_OK(hipGetLastError());
+    if (restore) { h->qEpoch++; h->geomAheadDone = false; }
+    return 0;
+}
+// behind k_quality_trace_final of a traced iteration: the verdict on its record, then the snapshot if it passed
+static int qualityGuardQueue(smgpu_handle* h, const smgpu_quality_trace_record* rec, int64_t number, const smgpu_iter_stats* gate) {
+    hipLaunchKernelGGL(k_quality_guard_verdict, dim3(1), dim3(64), 0, h->stream, rec, h->qgDev, (unsigned)h->qgPrm.criteria, &h->st.acc->stop, gate);
+    HIP_OK(hipGetLastError());
+    return qualityGuardCopy(h, false, number, true);
+}
+// After the read-back of a call that tripped: back to the snapshot; with `refine`, on from it one iteration at a time, a trace and
+// a verdict behind each, until one fails or interval - 1 have passed (the loop is deterministic from the snapshot's state, so
+// these are the iterations of the call over again).  The steps go through smgpu_iterate's body with the trace at interval 1;
+// what they would leave behind -- launch counts, timing events, the near-tie census, trace records -- is put back or not kept.
+static int qualityGuardAfterTrip(smgpu_handle* h) {
+    h->qgTripPending = false;
+    if (qualityGuardCopy(h, true, -1, false)) return 1;
+    int64_t good = h->qgState.snapshotIteration;
+    const int interval = h->qtInterval;
+    int rc = 0;
+    if (h->qgPrm.refine && interval > 1) {
+        const bool timing = h->timing;
+        int64_t launches[K_COUNT];
+        std::memcpy(launches, h->launches, sizeof(launches));
+        unsigned long long nearSaved[3] = {0, 0, 0};
+        if (h->st.nearTotal) HIP_OK(hipMemcpyAsync(nearSaved, h->st.nearTotal, sizeof(nearSaved), hipMemcpyDeviceToHost, h->stream));
+        HIP_OK(hipMemsetAsync(&h->qgDev->tripped, 0, sizeof(int), h->stream));
+        HIP_OK(hipStreamSynchronize(h->stream));
+        h->timing = false;
+        h->qgRefining = true;
+        h->qtInterval = 1;
+        for (int step = 1; step < interval && !rc; ++step) {
+            h->qtIter = good;
+            int32_t done = 0;
+            rc = iterateBody(h, 1, 0.0, nullptr, &done);
+            if (rc) break;
+            if (done != 1 || h->qgLastVerdict != kGuardGood) {   // the first bad step: the snapshot is the state before it
+                rc = qualityGuardCopy(h, true, -1, false);
+                break;
+            }
+            ++good;
+        }
+        h->qtInterval = interval;
+        h->qgRefining = false;
+        h->timing = timing;
+        std::memcpy(h->launches, launches, sizeof(launches));
+        if (!rc && h->st.nearTotal) HIP_OK(hipMemcpyAsync(h->st.nearTotal, nearSaved, sizeof(nearSaved), hipMemcpyHostToDevice, h->stream));
+        HIP_OK(hipStreamSynchronize(h->stream));
+        if (rc) return 1;
+    }
+    h->qgState.snapshotIteration = good;
+    h->qgState.restoredIteration = good;
+    h->qtIter = good;
+    return qualityGuardDisarm(h, false);
+}
+
+int smgpu_set_quality_guard(smgpu_handle* h, const smgpu_quality_guard_params* p, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityGuardDisarm(h, true);
+    const smgpu_quality_guard_params prm = p ? *p : smgpu_quality_guard_params{SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED, 1};
+    const uint32_t all = SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED | SMGPU_GUARD_ERROR_NONORTH;
+    if (prm.criteria == 0 || (prm.criteria & ~all)) return fail("smgpu_set_quality_guard: criteria must be a non-empty combination of SMGPU_GUARD_NONPOSITIVE_VOLUME, _WRONG_ORIENTED and _ERROR_NONORTH");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    if (h->bndOn)
+        return fail("smgpu_set_quality_guard: not available on an engine with boundary point smoothing (its point normals are a running blend across the "
+                    "iterations and its corner lists are host state, neither of which the guard's snapshot holds)");
+    if (h->qtInterval <= 0) return fail("smgpu_set_quality_guard: the guard judges the records of the quality trace; switch it on first (smgpu_set_quality_trace)");
+    if (h->iterOpen) return fail("smgpu_set_quality_guard: between smgpu_iter_begin and smgpu_iter_end");
+    if (qualityGuardDisarm(h, true)) return 1;
+    if (flushDeferred(h)) return 1;
+    if (qualityTraceBegin(h, 0)) return 1;
+    const size_t n = sizeof(double) * 3 * (size_t)std::max(1, h->mv.nPoints);
+    hipError_t e = hipMalloc((void**)&h->qgDev, sizeof(GuardDev));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qgRec, sizeof(smgpu_quality_trace_record));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->qgPts, n);
+    if (e == hipSuccess && h->layersOn && h->st.layerNormal) e = hipMalloc((void**)&h->qgNormal, n);
+    if (e != hipSuccess) {
+        qualityGuardFree(h);
+        return fail(std::string("mesh quality: device memory for the quality guard: ") + hipGetErrorString(e));
+    }
+    HIP_OK(hipMemsetAsync(h->qgDev, 0, sizeof(GuardDev), h->stream));
+    HIP_OK(hipMemsetAsync(h->qgRec, 0, sizeof(smgpu_quality_trace_record), h->stream));
+    // the baseline: the trace's launches on the current points, number 0
+    if (qualityTraceQueue(h, 0, 0, nullptr, h->qgRec)) { qualityGuardFree(h); return 1; }
+    HIP_OK(hipMemcpyAsync(&h->qgDev->baseline, h->qgRec, sizeof(smgpu_quality_trace_record), hipMemcpyDeviceToDevice, h->stream));
+    h->qgPrm = prm;
+    h->qgState = smgpu_quality_guard_state{};
+    if (qualityGuardCopy(h, false, h->qtIter, false)) { qualityGuardFree(h); return 1; }
+    HIP_OK(hipMemcpyAsync(&h->qgState.baseline, h->qgRec, sizeof(smgpu_quality_trace_record), hipMemcpyDeviceToHost, h->stream));
+    if (checkDeviceError(h)) { qualityGuardFree(h); return 1; }
+    h->qgState.armed = 1;
+    h->qgState.snapshotIteration = h->qtIter;
+    h->qgArmed = true;
+    return 0;
+}
+int smgpu_get_quality_guard(smgpu_handle* h, smgpu_quality_guard_state* out) {
+    if (!h || !out) return fail("null argument");
+    *out = h->qgState;
+    return 0;
+}
+int smgpu_quality_guard_restore(smgpu_handle* h) {
+    if (!h) return fail("null handle");
+    if (!h->qgArmed) return fail("smgpu_quality_guard_restore: the quality guard is not armed (smgpu_set_quality_guard)");
+    HIP_OK(hipSetDevice(h->device));
+    if (flushDeferred(h)) return 1;
+    if (qualityGuardCopy(h, true, -1, false)) return 1;
+    if (checkDeviceError(h)) return 1;
+    h->qgState.restoredIteration = h->qgState.snapshotIteration;
+    h->qtIter = h->qgState.snapshotIteration;
     return 0;
 }
 

@@ -107,6 +107,25 @@ class QualityTraceRecord:
     nHighAspectCells: int
 
 
+# the criteria of the quality guard (include/smgpu.h, SMGPU_GUARD_*): name -> bit, in the order the reasons are listed
+QUALITY_GUARD_CRITERIA = {"nonPositiveVolume": 1, "wrongOriented": 2, "errorNonOrth": 4}
+
+
+@dataclass
+class QualityGuardState:
+    """The state of the guard on the quality history (include/smgpu.h, smgpu_quality_guard_state; DESIGN.md "Mesh quality", 10.11).
+    The iterations are trace numbers; `reasons`: the names of the criteria that tripped, in QUALITY_GUARD_CRITERIA's order;
+    `baseline`: the trace's record of the points at arming (iteration 0); `tripRecord`: the record that tripped, or None."""
+    armed: bool
+    tripped: bool
+    reasons: tuple
+    snapshotIteration: int
+    trippedIteration: int
+    restoredIteration: int
+    baseline: QualityTraceRecord
+    tripRecord: Optional[QualityTraceRecord]
+
+
 QUALITY_FIELDS = ("cellVolume", "cellOpenness", "cellAspectRatio", "faceNonOrthogonality", "faceSkewness")
 # the failing elements of the report as sets (DESIGN.md "Mesh quality", 10.5), in smgpu_quality_sets' order: name, topoSet class,
 # the report counts whose sum is the set's size, and the words of the "<<Writing" line
@@ -547,6 +566,42 @@ class SmoothEngine:
         buf = (_ffi.QualityTraceRecord * n.value)()
         self._check(self._lib.smgpu_get_quality_trace(self._h, buf, n.value, C.byref(n)))
         return [QualityTraceRecord(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+
+    def set_quality_guard(self, criteria=("nonPositiveVolume", "wrongOriented"), refine=True):
+        """Guard on the quality history (include/smgpu.h, smgpu_set_quality_guard); needs set_quality_trace first.  The points now
+        become the baseline and snapshot 0.  A traced iteration whose count of a criterion (names of QUALITY_GUARD_CRITERIA)
+        exceeds the baseline's stops the loop on the device; the iterate() call that meets it returns the iterations that ran,
+        the tripping one included, and leaves the engine at the last good state: the last traced iteration that passed, or with
+        `refine` the exact last iteration that passes.  The guard then disarms itself.  criteria=None disarms.  Refused on an
+        engine with a halo or with boundary point smoothing."""
+        if criteria is None:
+            self._check(self._lib.smgpu_set_quality_guard(self._h, None, 0))
+            return
+        if isinstance(criteria, str):
+            criteria = (criteria,)
+        bits = 0
+        for c in criteria:
+            if c not in QUALITY_GUARD_CRITERIA:
+                raise ValueError(f"unknown quality guard criterion {c!r}: one of {', '.join(QUALITY_GUARD_CRITERIA)}")
+            bits |= QUALITY_GUARD_CRITERIA[c]
+        p = _ffi.QualityGuardParams(bits, 1 if refine else 0)
+        self._check(self._lib.smgpu_set_quality_guard(self._h, C.byref(p), 1))
+
+    def quality_guard(self) -> QualityGuardState:
+        """The guard's state; it keeps answering after the guard has tripped and disarmed itself."""
+        s = _ffi.QualityGuardState()
+        self._check(self._lib.smgpu_get_quality_guard(self._h, C.byref(s)))
+        rec = lambda r: QualityTraceRecord(**{f: getattr(r, f) for f, _ in r._fields_})  # noqa: E731
+        return QualityGuardState(armed=bool(s.armed), tripped=bool(s.tripped),
+                                 reasons=tuple(n for n, b in QUALITY_GUARD_CRITERIA.items() if s.reasons & b),
+                                 snapshotIteration=s.snapshotIteration, trippedIteration=s.trippedIteration,
+                                 restoredIteration=s.restoredIteration, baseline=rec(s.baseline),
+                                 tripRecord=rec(s.tripRecord) if s.tripped else None)
+
+    def quality_guard_restore(self):
+        """Roll the engine back to the guard's snapshot (snapshotIteration) on request, for callers who judge the trace by criteria
+        of their own: no refining, the guard stays armed, the trace's running number becomes snapshotIteration."""
+        self._check(self._lib.smgpu_quality_guard_restore(self._h))
 
     def quality_field(self, name) -> np.ndarray:
         """Per-element quality field in polyMesh order: one of QUALITY_FIELDS (non-orthogonality in degrees, 0 on boundary faces)."""

@@ -11,13 +11,14 @@ combine_quality_motion, decomposed_mesh_quality_geometry, decomposed_mesh_qualit
 Their findings as sets: decomposed_quality_geometry_sets, decomposed_quality_motion_sets, the drivers'
 quality_geometry_sets / quality_motion_sets; write_quality_sets and format_sets_written take the table of the report.
 The quality history of a run is the engine's (SmoothEngine.set_quality_trace / quality_trace); format_trace_line
-and format_trace_warning give the front-end's lines of a record.
+and format_trace_warning give the front-end's lines of a record.  The guard on it is the engine's as well
+(SmoothEngine.set_quality_guard / quality_guard / quality_guard_restore); format_guard_lines gives the front-end's two lines.
 """
 from dataclasses import dataclass, fields
 
 import numpy as np
 
-from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityTraceRecord, QUALITY_FIELDS,  # noqa: F401
+from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityGuardState, QualityTraceRecord, QUALITY_FIELDS,  # noqa: F401
                      QUALITY_GEOMETRY_FIELDS, QUALITY_MOTION_FIELDS, QUALITY_SETS, QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS)
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
@@ -445,6 +446,15 @@ def format_trace_warning(rec, initial):
     initial mesh's (`initial`: its MeshQuality)"""
     return (f"    ***Iteration {rec.iteration}: {rec.nNonPositiveVolume} non-positive volume cells and {rec.nWrongOrientedFaces} "
             f"wrongly oriented faces (initial mesh: {initial.nNonPositiveVolume}, {initial.nWrongOrientedFaces})\n")
+
+
+def format_guard_lines(state):
+    """the two lines smoothMesh -qualityGuard prints under the lines of the chunk in which the guard tripped (csrc/host/
+    smoothMesh_main.cpp), of a QualityGuardState that has tripped"""
+    t, b = state.tripRecord, state.baseline
+    return (f"    ***Quality guard: iteration {state.trippedIteration}: {t.nNonPositiveVolume} non-positive volume cells and "
+            f"{t.nWrongOrientedFaces} wrongly oriented faces (initial mesh: {b.nNonPositiveVolume}, {b.nWrongOrientedFaces})\n"
+            f"    ***Quality guard: restored the mesh of iteration {state.restoredIteration}, stopping.\n")
 
 
 def format_report(q, which="mesh", geometry=None, motion=None):
