@@ -247,6 +247,64 @@ int smgpu_set_quality_guard(smgpu_handle* h, const smgpu_quality_guard_params* p
 int smgpu_get_quality_guard(smgpu_handle* h, smgpu_quality_guard_state* out);
 int smgpu_quality_guard_restore(smgpu_handle* h);
 
+/* ---- the tangle constraint (DESIGN.md "Mesh quality", 10.12) --------------------------------------------------------------
+ * A constraint of the engine's own, in the style of the reference's three: a point stays at its current coordinates when its
+ * move would turn a cell bad.  Opt-in; with it off nothing the engine launches or returns changes.
+ *
+ * x: the points an iteration of smgpu_iterate starts from.  x': the points it has produced after everything the loop does
+ * without the constraint (proposal, layers, the reference's constraints, the freeze walk, movePoints).  C_f, S_f, C_c: the
+ * engine's geometry of a set of points under the current foam variant.
+ *
+ * A cell c is BAD at a set of points if V_c <= VSMALL -- the report's V_c: the mean of the face centres by a plain division,
+ * signed pyramids, no clamp under either variant, the cellFacesGeom order -- or if one of its own-side pyramids is <= 0:
+ * S_f.(C_f - C_c) for a face it owns, S_f.(C_c - C_f) for a face it neighbours, the operands and operation order of the
+ * report's pO and pN.  So a face is in wrongOrientedFaces exactly when its owner or its neighbour is bad through it.
+ *
+ * smgpu_set_tangle_constraint(p, on != 0) evaluates the current points once: the cells bad there are EXEMPT for as long as the
+ * constraint stays on, even if they heal (one byte per cell); they never count and never mark.  (The reference requires an
+ * untangled initial mesh; without the exemption one bad initial cell would freeze the whole run.)  p == NULL: passes = 2.
+ *
+ * Then, per iteration that ran, behind its movePoints:
+ *   for k = 0 .. passes:  evaluate the geometry of x'; B = the cells that are bad and not exempt;
+ *                         B empty: stop;
+ *                         k == passes: x' = x for every point (the FULL REVERT), stop;
+ *                         otherwise x'_p = x_p for every point p of every face of every cell in B.
+ * INVARIANT: if no non-exempt cell is bad at x, none is bad at the accepted x' -- by induction, from the moment of enabling.
+ * The accepted x' is what the next iteration, smgpu_get_points, the quality trace and the guard see; the trace's launches of an
+ * iteration are queued behind the constraint's.  The iteration's residual and nFrozenPoints keep their meaning -- the loop's own
+ * values, computed before the passes -- so a run whose remaining moves are all reverted never meets relTol.
+ *
+ * One smgpu_tangle_record per iteration that ran: `iteration` a running number since enabling, across smgpu_iterate calls, as
+ * the trace numbers them; `passes` the evaluations that found B non-empty and reverted marked points; `fullRevert` whether the
+ * full revert ran; `nBadCells` the size of B at k = 0; `nPointsReverted` the points with accepted x'_p == x_p whose loop result
+ * differed from x_p.  The records stay on the device until the call's read-back; smgpu_get_tangle_records has the semantics of
+ * smgpu_get_quality_trace (out == NULL: the number; a short cap is an error that clears nothing; ascending; a read clears).
+ *
+ * While on, smgpu_iterate adds no host synchronisation; it closes every iteration with k_finish, like an armed guard (one more
+ * K_FINISH launch per iteration in smgpu_counters with relTol <= 0), because every launch of the constraint is gated on the
+ * written bit of the iteration's statistics.  The evaluations after the first stay queued and return at once on a device word
+ * once one has found B empty.  The constraint's launches stay outside smgpu_counters and the timing events; its memory is
+ * allocated at enabling, outside deviceBytes: nCells + nPoints bytes, and 32 bytes per iteration of the longest call.
+ * An engine without tiles (SMGPU_TILES=0) evaluates with the direct geometry kernels: identical points and records.
+ *
+ * Refused (with the trace's wording where one exists): an engine with a halo -- so no smoothMesh -parallel and none of the
+ * smoothers of halo.py; an engine with boundary point smoothing; smgpu_halo_configure and smgpu_set_boundary_smoothing while
+ * the constraint is on; passes < 0.  Layers, both foam variants, the trace and the guard go together with it: the guard's
+ * snapshot gains nothing (the exempt mask is static), and its refining steps replay the constraint deterministically; their
+ * records are dropped like their statistics.  When the guard rolls the points back (a trip, or smgpu_quality_guard_restore)
+ * the constraint's running number goes back by as many iterations as the trace's, so the two keep naming the same points; the
+ * records of the iterations that ran stand, like the trace's.  on == 0 switches it off, discards unread records and frees its memory. */
+typedef struct smgpu_tangle_params { int32_t passes; } smgpu_tangle_params;   /* NULL params = {2} */
+typedef struct smgpu_tangle_record {
+    int64_t iteration;                      /* 1-based running number since smgpu_set_tangle_constraint */
+    int32_t passes, fullRevert;
+    int64_t nBadCells, nPointsReverted;
+} smgpu_tangle_record;
+typedef struct smgpu_tangle_state { int32_t on, passes;  int64_t nExemptCells, iteration; } smgpu_tangle_state;
+int smgpu_set_tangle_constraint(smgpu_handle* h, const smgpu_tangle_params* p, int32_t on);
+int smgpu_get_tangle_records(smgpu_handle* h, smgpu_tangle_record* out, int64_t cap, int64_t* n);
+int smgpu_get_tangle_state(smgpu_handle* h, smgpu_tangle_state* out);
+
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):
  *   1. smgpu_quality_coupled_pack: the geometry of the current points (the loop's own launch, uncounted), then the owner cell

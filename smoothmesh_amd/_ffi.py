@@ -127,6 +127,22 @@ class QualityGuardState(C.Structure):
                 ("baseline", QualityTraceRecord), ("tripRecord", QualityTraceRecord)]
 
 
+class TangleParams(C.Structure):
+    """smgpu_tangle_params"""
+    _fields_ = [("passes", C.c_int32)]
+
+
+class TangleRecord(C.Structure):
+    """smgpu_tangle_record"""
+    _fields_ = [("iteration", C.c_int64), ("passes", C.c_int32), ("fullRevert", C.c_int32), ("nBadCells", C.c_int64),
+                ("nPointsReverted", C.c_int64)]
+
+
+class TangleState(C.Structure):
+    """smgpu_tangle_state"""
+    _fields_ = [("on", C.c_int32), ("passes", C.c_int32), ("nExemptCells", C.c_int64), ("iteration", C.c_int64)]
+
+
 class QualityGeometryParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("concaveThreshold", "flatnessThreshold", "weightThreshold", "volRatioThreshold",
                                           "determinantThreshold")]
@@ -239,6 +255,9 @@ SYMBOLS = {
     "smgpu_set_quality_guard": (C.c_int, [C.c_void_p, C.POINTER(QualityGuardParams), C.c_int32]),
     "smgpu_get_quality_guard": (C.c_int, [C.c_void_p, C.POINTER(QualityGuardState)]),
     "smgpu_quality_guard_restore": (C.c_int, [C.c_void_p]),
+    "smgpu_set_tangle_constraint": (C.c_int, [C.c_void_p, C.POINTER(TangleParams), C.c_int32]),
+    "smgpu_get_tangle_records": (C.c_int, [C.c_void_p, C.POINTER(TangleRecord), C.c_int64, C.POINTER(C.c_int64)]),
+    "smgpu_get_tangle_state": (C.c_int, [C.c_void_p, C.POINTER(TangleState)]),
     "smgpu_quality_coupled_pack": (C.c_int, [C.c_void_p, C.POINTER(QualityCoupling), C.c_void_p, C.POINTER(C.c_int64)]),
     "smgpu_quality_coupled_report": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(QualityPart)]),
     "smgpu_quality_coupled_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),

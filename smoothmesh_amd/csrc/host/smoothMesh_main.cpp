@@ -96,7 +96,7 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "layerMaxBlendingFraction", "layerEdgeLength", "layerExpansionRatio", "minLayers",
                                "maxLayers", "layerPatches", "smoothingPatches", "internalSmoothingBlendingFraction",
                                "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets", "allGeometry",
-                               "meshQuality", "qualityInterval", "qualityGuard", "qualityGuardRefine"};
+                               "meshQuality", "qualityInterval", "qualityGuard", "qualityGuardRefine", "tangleConstraint", "tanglePasses"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -119,6 +119,9 @@ Options parseArgs(int argc, char** argv) {
                       "       [-qualityGuard b]   (with -qualityInterval: stop at the first traced iteration with more non-positive volume cells\n"
                       "        or wrongly oriented faces than the initial mesh, and write the last mesh before it instead)\n"
                       "       [-qualityGuardRefine b]  (default true: find the exact last good iteration, not only the last traced one)\n"
+                      "       [-tangleConstraint b] (freeze, iteration by iteration, the points whose move would turn a cell's volume non-positive\n"
+                      "        or a face wrongly oriented; cells that are bad in the initial mesh are exempt; serial runs only)\n"
+                      "       [-tanglePasses n]   (with -tangleConstraint: marked passes per iteration before the whole iteration is reverted, default 2)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -541,6 +544,12 @@ int main(int argc, char** argv) {
     if (qualityGuard && !checkQuality) fatal("-qualityGuard needs -checkQuality true: it judges measures of the quality report");
     if (qualityGuard && !qualityTrace) fatal("-qualityGuard needs -qualityInterval N: it judges the traced iterations");
     if (opt.found("qualityGuardRefine") && !qualityGuard) fatal("-qualityGuardRefine needs -qualityGuard true");
+    const bool tangleConstraint = opt.getB("tangleConstraint", false);
+    const long tanglePasses = opt.getL("tanglePasses", 2);
+    if (tangleConstraint && opt.parallel)
+        fatal("-tangleConstraint is not available with -parallel: it judges the cells by the measure of the quality report, which is serial only");
+    if (opt.found("tanglePasses") && !tangleConstraint) fatal("-tanglePasses needs -tangleConstraint true");
+    if (tangleConstraint && (tanglePasses < 0 || tanglePasses > 0x7fffffffL)) fatal("tanglePasses must be between 0 and 2147483647");
     // SMOOTHMESH_TIMELINE=1: where this process's wall time goes, one stderr line per stage (seconds since main started)
     const bool timeline = std::getenv("SMOOTHMESH_TIMELINE") && std::atoi(std::getenv("SMOOTHMESH_TIMELINE")) > 0;
     auto mark = [&](const char* what) { if (timeline) std::fprintf(stderr, "[smoothMesh %8.3f s] %s\n", secondsSince(t0), what); };
@@ -724,6 +733,9 @@ int main(int argc, char** argv) {
     if (qualityGuard && doBoundarySmoothing)
         fatal("-qualityGuard is not available with boundary point smoothing: the point normals it blends from iteration to iteration and "
               "its corner lists are not part of the guard's snapshot (run without -smoothingPatches, or without the guard)");
+    if (tangleConstraint && doBoundarySmoothing)
+        fatal("-tangleConstraint is not available with boundary point smoothing: it rewrites the boundary points from state that a reverted "
+              "iteration would leave ahead of the points (run without -smoothingPatches, or without the constraint)");
     if (doLayerTreatment && !doBoundarySmoothing)   // SM.C:2095-2098
         OUTS("WARNING: Boundary layer treatment will be done without boundary point smoothing. This can result in distorted boundary cells.\n");
 
@@ -1249,6 +1261,16 @@ int main(int argc, char** argv) {
     bool stopIteration = false;
     long i = 0;
     double timeValue = startIsConstant ? 0.0 : startValue;
+    // -tangleConstraint: the engine's own constraint (include/smgpu.h, smgpu_set_tangle_constraint), enabled on the
+    // initial points with everything set up, in front of the guard: the guard judges what the constraint accepts
+    std::vector<smgpu_tangle_record> tangle;
+    if (tangleConstraint) {
+        const smgpu_tangle_params tp{(int32_t)tanglePasses};
+        check(smgpu_set_tangle_constraint(R[0].h, &tp, 1), "smgpu_set_tangle_constraint");
+        smgpu_tangle_state ts{};
+        check(smgpu_get_tangle_state(R[0].h, &ts), "smgpu_get_tangle_state");
+        OUT("Tangle constraint: %lld exempt cells, %d passes\n", (long long)ts.nExemptCells, (int)ts.passes);
+    }
     // -qualityGuard: the guard on that history (include/smgpu.h, smgpu_set_quality_guard), armed on the initial
     // points with everything set up: the engine stops the loop on the device and rolls the points back itself
     if (qualityGuard) {
@@ -1328,8 +1350,21 @@ int main(int argc, char** argv) {
             trace.resize((size_t)nRecords);
             if (nRecords > 0) check(smgpu_get_quality_trace(R[0].h, trace.data(), nRecords, &nRecords), "smgpu_get_quality_trace");
         }
+        size_t nextTangle = 0;
+        if (tangleConstraint) {
+            int64_t nRecords = 0;
+            check(smgpu_get_tangle_records(R[0].h, nullptr, 0, &nRecords), "smgpu_get_tangle_records");
+            tangle.resize((size_t)nRecords);
+            if (nRecords > 0) check(smgpu_get_tangle_records(R[0].h, tangle.data(), nRecords, &nRecords), "smgpu_get_tangle_records");
+        }
         for (int32_t k = 0; k < done; ++k) {
             OUT("Smoothing iteration=%ld nFrozenPoints=%d residual=%g\n", i + k + 1, stats[(size_t)k].nFrozenPoints, stats[(size_t)k].residual);
+            if (nextTangle < tangle.size() && tangle[nextTangle].iteration == (int64_t)(i + k + 1)) {
+                const smgpu_tangle_record& t = tangle[nextTangle++];
+                if (t.nBadCells > 0)
+                    OUT("    tangle iteration=%lld badCells %lld passes %d pointsReverted %lld%s\n", (long long)t.iteration, (long long)t.nBadCells,
+                        (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
+            }
             if (!qualityTrace || nextRecord >= trace.size() || trace[nextRecord].iteration != (int64_t)(i + k + 1)) continue;
             const smgpu_quality_trace_record& t = trace[nextRecord++];
             OUT("    quality iteration=%lld minVolume %.9g nonPositive %lld maxNonOrth %.9g error %lld maxSkewness %.9g wrongOriented %lld "

@@ -24,6 +24,7 @@
 #include "kernels_quality_motion.hpp"
 #include "kernels_quality_trace.hpp"
 #include "kernels_quality_guard.hpp"
+#include "kernels_quality_tangle.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"
@@ -278,6 +279,19 @@ struct smgpu_handle {
     GuardDev* qgDev = nullptr;
     smgpu_quality_trace_record* qgRec = nullptr;
     double *qgPts = nullptr, *qgNormal = nullptr;
+    // ... and of the tangle constraint (smgpu_set_tangle_constraint, kernels_quality_tangle.hpp): allocated at enabling, outside
+    // `allocs` too.  tgExempt: one byte per cell; tgMarks: one per point (rounded up to whole words); tgSlab: the records of one
+    // smgpu_iterate call; tgCellCtr / tgAcc: cell centres and a stop word (always 0) of its own for the evaluation without tiles
+    bool tgOn = false;
+    int tgPasses = 2;
+    int64_t tgIter = 0, tgNExempt = 0;      // iterations that ran since enabling; exempt cells
+    uint8_t *tgExempt = nullptr, *tgMarks = nullptr;
+    TangleDev* tgDev = nullptr;
+    smgpu_tangle_record* tgSlab = nullptr;
+    int tgSlabCap = 0;
+    double* tgCellCtr = nullptr;
+    Accum* tgAcc = nullptr;
+    std::vector<smgpu_tangle_record> tgPending;
     uint64_t qEpoch = 1, qPackEpoch = 0;   // qEpoch moves whenever the points (or the geometry variant) may have changed
     bool iterOpen = false;                  // between smgpu_iter_begin and smgpu_iter_end
 };
@@ -1168,7 +1182,8 @@ int smgpu_destroy(smgpu_handle* h) {
                     (void*)h->qPartOut, (void*)h->qgVol, (void*)h->qgFacePart, (void*)h->qgCellPart, (void*)h->qgOut,
                     (void*)h->qmFacePart, (void*)h->qmOut, (void*)h->qgPartOut, (void*)h->qmPartOut, (void*)h->qtCellCtr, (void*)h->qtAcc,
                     (void*)h->qtFacePart, (void*)h->qtCellPart, (void*)h->qtCellFold, (void*)h->qtSlab, (void*)h->qgDev, (void*)h->qgRec,
-                    (void*)h->qgPts, (void*)h->qgNormal})
+                    (void*)h->qgPts, (void*)h->qgNormal, (void*)h->tgExempt, (void*)h->tgMarks, (void*)h->tgDev, (void*)h->tgSlab,
+                    (void*)h->tgCellCtr, (void*)h->tgAcc})
         if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
@@ -1952,6 +1967,9 @@ static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const sm
 // the guard on it (smgpu_set_quality_guard; defined there as well)
 static int qualityGuardQueue(smgpu_handle* h, const smgpu_quality_trace_record* rec, int64_t number, const smgpu_iter_stats* gate);
 static int qualityGuardAfterTrip(smgpu_handle* h);
+// the tangle constraint (smgpu_set_tangle_constraint; defined there as well)
+static int tangleBegin(smgpu_handle* h, int nIters);
+static int tangleQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x);
 
 static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_stats* stats, int32_t* nDone);
 int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_stats* stats, int32_t* nDone) {
@@ -2000,14 +2018,17 @@ static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_ite
     int launched = 0;
     // relTol <= 0 cannot stop the loop (residual >= 0): the end-of-iteration reduction then rides in the next
     // iteration's geometry launch instead of a launch of its own; the last iteration is closed by k_finish
-    // (not under the quality guard: its verdict on iteration i may stop the loop, and stats[i] has to be written before it)
+    // (not under the quality guard: its verdict on iteration i may stop the loop, and stats[i] has to be written before it; nor
+    // under the tangle constraint: its launches of iteration i are gated on the written bit of stats[i])
     const bool guarded = h->qgArmed;
-    const bool deferFinish = relTol <= 0.0 && !guarded && h->useTiles && h->geomT >= 64 && envInt("SMGPU_DEFER_FINISH", 1);
+    const bool tangled = h->tgOn;
+    const bool deferFinish = relTol <= 0.0 && !guarded && !tangled && h->useTiles && h->geomT >= 64 && envInt("SMGPU_DEFER_FINISH", 1);
     if (flushDeferred(h)) return 1;
     // quality history: the iterations of this call whose running number is due get a slot of the call's record slab, in order
     const bool traced = h->qtInterval > 0;
     std::vector<int> qtSlotIter;
     if (traced && qualityTraceBegin(h, nIters)) return 1;
+    if (tangled && tangleBegin(h, nIters)) return 1;
     for (int i = 0; i < nIters; ++i) {
         if (runBndPre(h)) return 1;
         if (runGeometry(h, nullptr, 0, false, true)) return 1;
@@ -2024,9 +2045,12 @@ static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_ite
         else if (launchK(h, K_FINISH, [&] { hipLaunchKernelGGL(k_finish, dim3(1), dim3(kFinishBlock), 0, h->stream, s, nPart, i, relTol, (double*)nullptr, (double*)nullptr); })) return 1;
         std::swap(h->st.ptsCur, other);  // mesh.movePoints, SM.C:2399
         ++launched;
+        // the tangle constraint: `other` now names x, the points the iteration started from; nothing queued writes them before
+        // the next iteration's proposal (fused: ptsNext; k_apply: ptsNext; k_apply_swap: prop), which is queued behind the passes
+        if (tangled && tangleQueue(h, i, h->tgIter + i + 1, h->dStats + i, other)) return 1;
         // (with relTol > 0 this iteration may turn out not to have run: k_finish has written stats[i] by then, or has not)
         if (traced && (h->qtIter + i + 1) % h->qtInterval == 0) {
-            const smgpu_iter_stats* gate = (relTol > 0.0 || guarded) ? h->dStats + i : nullptr;
+            const smgpu_iter_stats* gate = (relTol > 0.0 || guarded || tangled) ? h->dStats + i : nullptr;
             if (qualityTraceQueue(h, (int)qtSlotIter.size(), h->qtIter + i + 1, gate)) return 1;
             if (guarded && qualityGuardQueue(h, h->qtSlab + qtSlotIter.size(), h->qtIter + i + 1, gate)) return 1;
             qtSlotIter.push_back(i);
@@ -2046,9 +2070,21 @@ static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_ite
     if (!qtRecs.empty()) HIP_OK(hipMemcpyAsync(qtRecs.data(), h->qtSlab, sizeof(smgpu_quality_trace_record) * qtRecs.size(), hipMemcpyDeviceToHost, h->stream));
     GuardDev gd{};
     if (guarded) HIP_OK(hipMemcpyAsync(&gd, h->qgDev, sizeof(GuardDev), hipMemcpyDeviceToHost, h->stream));
+    std::vector<smgpu_tangle_record> tgRecs(tangled ? (size_t)launched : 0);
+    TangleDev td{};
+    if (tangled) {
+        HIP_OK(hipMemcpyAsync(tgRecs.data(), h->tgSlab, sizeof(smgpu_tangle_record) * tgRecs.size(), hipMemcpyDeviceToHost, h->stream));
+        HIP_OK(hipMemcpyAsync(&td, h->tgDev, sizeof(TangleDev), hipMemcpyDeviceToHost, h->stream));
+    }
     if (checkDeviceError(h)) return 1;
+    if (td.err) return fail("smgpu_iterate: tangle constraint: the marks of a geometry tile do not fit the LDS of its points");
     int done = 0;
     while (done < launched && (hs[done].nNearTies & kStatsWritten)) ++done;
+    if (tangled && !h->qgRefining) {   // (the guard's refining steps replay iterations of the call: no records, no numbers)
+        for (int i = 0; i < done; ++i)
+            if (tgRecs[i].iteration != 0) h->tgPending.push_back(tgRecs[i]);
+        h->tgIter += done;
+    }
     if (traced) {
         for (size_t r = 0; r < qtRecs.size() && !h->qgRefining; ++r)
             if (qtSlotIter[r] < done && qtRecs[r].iteration != 0) h->qtPending.push_back(qtRecs[r]);
@@ -2233,6 +2269,7 @@ int smgpu_halo_set_exchange_stream(smgpu_handle* h, int32_t useExchangeStream, v
 
 int smgpu_halo_configure(smgpu_handle* h, const smgpu_halo_desc* d) {
     if (!h || !d) return fail("null argument");
+    if (h->tgOn) return fail("smgpu_halo_configure: the tangle constraint is on (smgpu_set_tangle_constraint), and it is not available on an engine with a halo; switch it off first");
     if (h->qgArmed) return fail("smgpu_halo_configure: the quality guard is armed (smgpu_set_quality_guard), and a guard is not available on an engine with a halo; disarm it first");
     if (h->qtInterval > 0) return fail("smgpu_halo_configure: the quality trace is on (smgpu_set_quality_trace), and a trace is not available on an engine with a halo; switch it off first");
     HIP_OK(hipSetDevice(h->device));
@@ -3298,6 +3335,7 @@ int smgpu_boundary_shared(smgpu_handle* h, int32_t field, int32_t set, double* v
 int smgpu_set_boundary_smoothing(smgpu_handle* h, const smgpu_boundary_desc* d, smgpu_boundary_info* info) {
     if (!h || !d) return fail("null argument");
     if (h->haloOn) return fail("smgpu_set_boundary_smoothing is the serial set-up; with a halo use smgpu_boundary_stats / begin / step / shared");
+    if (h->tgOn) return fail("smgpu_set_boundary_smoothing: the tangle constraint is on (smgpu_set_tangle_constraint), and it is not available on an engine with boundary point smoothing; switch it off first");
     if (h->qgArmed) return fail("smgpu_set_boundary_smoothing: the quality guard is armed (smgpu_set_quality_guard), and its snapshot does not hold the state boundary point smoothing carries from one iteration to the next; disarm it first");
     double minEdge = 0.0, bb[6];
     if (smgpu_boundary_stats(h, &minEdge, bb)) return 1;
@@ -3793,6 +3831,7 @@ static int qualityGuardQueue(smgpu_handle* h, const smgpu_quality_trace_record* 
 // what they would leave behind -- launch counts, timing events, the near-tie census, trace records -- is put back or not kept.
 static int qualityGuardAfterTrip(smgpu_handle* h) {
     h->qgTripPending = false;
+    const int64_t ranTo = h->qtIter;   // (the tangle constraint's running number goes back with the trace's: see the end)
     if (qualityGuardCopy(h, true, -1, false)) return 1;
     int64_t good = h->qgState.snapshotIteration;
     const int interval = h->qtInterval;
@@ -3830,6 +3869,7 @@ static int qualityGuardAfterTrip(smgpu_handle* h) {
     h->qgState.snapshotIteration = good;
     h->qgState.restoredIteration = good;
     h->qtIter = good;
+    if (h->tgOn) h->tgIter -= ranTo - good;
     return qualityGuardDisarm(h, false);
 }
 
@@ -3886,7 +3926,151 @@ int smgpu_quality_guard_restore(smgpu_handle* h) {
     if (qualityGuardCopy(h, true, -1, false)) return 1;
     if (checkDeviceError(h)) return 1;
     h->qgState.restoredIteration = h->qgState.snapshotIteration;
+    if (h->tgOn) h->tgIter -= h->qtIter - h->qgState.snapshotIteration;   // the two numbers name the same points
     h->qtIter = h->qgState.snapshotIteration;
+    return 0;
+}
+
+// ---- the tangle constraint (kernels_quality_tangle.hpp, DESIGN.md "Mesh quality", 10.12) ----
+static void tangleFree(smgpu_handle* h) {
+    for (void** p : {(void**)&h->tgExempt, (void**)&h->tgMarks, (void**)&h->tgDev, (void**)&h->tgSlab, (void**)&h->tgCellCtr, (void**)&h->tgAcc})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    h->tgSlabCap = 0;
+}
+static int tangleOff(smgpu_handle* h) {
+    h->tgOn = false;
+    h->tgPending.clear();
+    if (h->tgDev) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        tangleFree(h);
+    }
+    return 0;
+}
+extern "C++" {
+template <int T, bool ORG>
+static void launchTangleTileAs(smgpu_handle* h, const State& ts, int nT, uint8_t* exemptOut, int pass, const smgpu_iter_stats* gate) {
+    ensureDynLds(k_tangle_tile<T, ORG>, h->device, h->geomLds);
+    hipLaunchKernelGGL((k_tangle_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, nT, h->xcdMap,
+                       exemptOut ? (const uint8_t*)nullptr : (const uint8_t*)h->tgExempt, exemptOut, h->tgMarks, h->tgDev, pass, gate);
+}
+template <int T>
+static void launchTangleTile(smgpu_handle* h, const State& ts, int nT, uint8_t* exemptOut, int pass, const smgpu_iter_stats* gate) {
+    if (h->foamOrg) launchTangleTileAs<T, true>(h, ts, nT, exemptOut, pass, gate);
+    else launchTangleTileAs<T, false>(h, ts, nT, exemptOut, pass, gate);
+}
+}  // extern "C++"
+// one evaluation of the points ptsCur names, behind everything queued on the engine's stream; outside the launch counters and
+// the timing events.  Tiles: nothing the loop reads is written.  Without tiles the direct geometry kernels write the loop's face
+// values (the next geometry launch writes them again before anything reads them), cell centres of the constraint's own, and
+// test a stop word of its own.
+static int tangleEvaluate(smgpu_handle* h, uint8_t* exemptOut, int pass, const smgpu_iter_stats* gate) {
+    const MeshView& m = h->mv;
+    State ts = h->st;
+    ts.stats = nullptr;
+    if (h->useTiles) {
+        const int nT = h->gt.nTiles;
+        if (nT > 0) {
+            if (h->geomT == 64) launchTangleTile<64>(h, ts, nT, exemptOut, pass, gate);
+            else if (h->geomT == 128) launchTangleTile<128>(h, ts, nT, exemptOut, pass, gate);
+            else launchTangleTile<256>(h, ts, nT, exemptOut, pass, gate);
+        }
+    } else {
+        ts.cellCtr = h->tgCellCtr;
+        ts.acc = h->tgAcc;
+        if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
+        if (m.nCells > 0) {
+            hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
+            hipLaunchKernelGGL(k_tangle_cells, dim3((m.nCells + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, m, ts.fCtr, ts.fArea,
+                               ts.cellCtr, exemptOut ? (const uint8_t*)nullptr : (const uint8_t*)h->tgExempt, exemptOut, h->tgMarks, h->tgDev, pass, gate);
+        }
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+// start of a smgpu_iterate call with the constraint on: a zeroed slab with one record per iteration (iteration == 0: not written)
+static int tangleBegin(smgpu_handle* h, int nIters) {
+    if (nIters > h->tgSlabCap) {
+        if (h->tgSlab) {   // outgrown (nothing of the constraint is in flight between two smgpu_iterate calls)
+            HIP_OK(hipStreamSynchronize(h->stream));
+            (void)hipFree(h->tgSlab);
+            h->tgSlab = nullptr;
+            h->tgSlabCap = 0;
+        }
+        const hipError_t e = hipMalloc((void**)&h->tgSlab, sizeof(smgpu_tangle_record) * (size_t)nIters);
+        if (e != hipSuccess) return fail(std::string("mesh quality: device memory for the tangle constraint: ") + hipGetErrorString(e));
+        h->tgSlabCap = nIters;
+    }
+    HIP_OK(hipMemsetAsync(h->tgSlab, 0, sizeof(smgpu_tangle_record) * (size_t)nIters, h->stream));
+    return 0;
+}
+// behind the movePoints of an iteration: the passes on the points ptsCur now names; x: the points the iteration started from
+static int tangleQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x) {
+    if (slot >= h->tgSlabCap) return fail("mesh quality: tangle constraint slab overrun");
+    const int nP = h->mv.nPoints;
+    const int gApply = std::max(1, (int)(((int64_t)nP + kTanglePts - 1) / kTanglePts));
+    smgpu_tangle_record* rec = h->tgSlab + slot;
+    for (int k = 0; k <= h->tgPasses; ++k) {
+        if (tangleEvaluate(h, nullptr, k, gate)) return 1;
+        hipLaunchKernelGGL(k_tangle_verdict, dim3(1), dim3(64), 0, h->stream, h->tgDev, rec, (long long)number, k, h->tgPasses, gate);
+        hipLaunchKernelGGL(k_tangle_apply, dim3(gApply), dim3(kTangleBlock), 0, h->stream, x, h->st.ptsCur, h->tgMarks, nP, (const TangleDev*)h->tgDev, rec, gate);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_set_tangle_constraint(smgpu_handle* h, const smgpu_tangle_params* p, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return tangleOff(h);
+    const smgpu_tangle_params prm = p ? *p : smgpu_tangle_params{2};
+    if (prm.passes < 0) return fail("smgpu_set_tangle_constraint: passes < 0");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    if (h->bndOn)
+        return fail("smgpu_set_tangle_constraint: not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
+                    "points from state that a reverted iteration would leave ahead of the points)");
+    if (h->iterOpen) return fail("smgpu_set_tangle_constraint: between smgpu_iter_begin and smgpu_iter_end");
+    if (tangleOff(h)) return 1;
+    if (flushDeferred(h)) return 1;
+    const MeshView& m = h->mv;
+    const size_t nMark = ((size_t)std::max(1, m.nPoints) + 3) & ~(size_t)3, nCell = (size_t)std::max(1, m.nCells);
+    hipError_t e = hipMalloc((void**)&h->tgDev, sizeof(TangleDev));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->tgExempt, nCell);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->tgMarks, nMark);
+    if (e == hipSuccess && !h->useTiles) e = hipMalloc((void**)&h->tgCellCtr, sizeof(double) * 3 * nCell);
+    if (e == hipSuccess && !h->useTiles) e = hipMalloc((void**)&h->tgAcc, sizeof(Accum));
+    if (e != hipSuccess) {
+        tangleFree(h);
+        return fail(std::string("mesh quality: device memory for the tangle constraint: ") + hipGetErrorString(e));
+    }
+    HIP_OK(hipMemsetAsync(h->tgDev, 0, sizeof(TangleDev), h->stream));
+    HIP_OK(hipMemsetAsync(h->tgExempt, 0, nCell, h->stream));
+    HIP_OK(hipMemsetAsync(h->tgMarks, 0, nMark, h->stream));
+    if (h->tgAcc) HIP_OK(hipMemsetAsync(h->tgAcc, 0, sizeof(Accum), h->stream));
+    // the exempt cells: one evaluation of the current points
+    h->tgPasses = prm.passes;
+    if (tangleEvaluate(h, h->tgExempt, 0, nullptr)) { tangleFree(h); return 1; }
+    TangleDev td{};
+    HIP_OK(hipMemcpyAsync(&td, h->tgDev, sizeof(TangleDev), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemsetAsync(h->tgDev, 0, sizeof(TangleDev), h->stream));
+    if (checkDeviceError(h)) { tangleFree(h); return 1; }
+    h->tgNExempt = td.badNow;
+    h->tgIter = 0;
+    h->tgOn = true;
+    return 0;
+}
+int smgpu_get_tangle_records(smgpu_handle* h, smgpu_tangle_record* out, int64_t cap, int64_t* n) {
+    if (!h || !n) return fail("null argument");
+    const int64_t have = (int64_t)h->tgPending.size();
+    if (!out) { *n = have; return 0; }
+    if (cap < have) return fail("smgpu_get_tangle_records: cap " + std::to_string(cap) + " is below the " + std::to_string(have) + " pending records");
+    if (have > 0) std::memcpy(out, h->tgPending.data(), sizeof(smgpu_tangle_record) * (size_t)have);
+    h->tgPending.clear();
+    *n = have;
+    return 0;
+}
+int smgpu_get_tangle_state(smgpu_handle* h, smgpu_tangle_state* out) {
+    if (!h || !out) return fail("null argument");
+    *out = smgpu_tangle_state{h->tgOn ? 1 : 0, h->tgPasses, h->tgOn ? h->tgNExempt : 0, h->tgOn ? h->tgIter : 0};
     return 0;
 }
 

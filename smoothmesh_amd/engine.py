@@ -126,6 +126,28 @@ class QualityGuardState:
     tripRecord: Optional[QualityTraceRecord]
 
 
+@dataclass
+class TangleRecord:
+    """One record of the tangle constraint (include/smgpu.h, smgpu_tangle_record; DESIGN.md "Mesh quality", 10.12), of iteration
+    `iteration` (1-based, counted since set_tangle_constraint): `nBadCells` cells that are not exempt were bad after the loop's
+    move, `passes` evaluations reverted the points of such cells, `fullRevert` says whether every point went back in the end, and
+    `nPointsReverted` points ended where the iteration found them although the loop had moved them."""
+    iteration: int
+    passes: int
+    fullRevert: int
+    nBadCells: int
+    nPointsReverted: int
+
+
+@dataclass
+class TangleState:
+    """smgpu_tangle_state: whether the constraint is on, its passes, the cells exempt since enabling, the running number"""
+    on: bool
+    passes: int
+    nExemptCells: int
+    iteration: int
+
+
 QUALITY_FIELDS = ("cellVolume", "cellOpenness", "cellAspectRatio", "faceNonOrthogonality", "faceSkewness")
 # the failing elements of the report as sets (DESIGN.md "Mesh quality", 10.5), in smgpu_quality_sets' order: name, topoSet class,
 # the report counts whose sum is the set's size, and the words of the "<<Writing" line
@@ -602,6 +624,33 @@ class SmoothEngine:
         """Roll the engine back to the guard's snapshot (snapshotIteration) on request, for callers who judge the trace by criteria
         of their own: no refining, the guard stays armed, the trace's running number becomes snapshotIteration."""
         self._check(self._lib.smgpu_quality_guard_restore(self._h))
+
+    def set_tangle_constraint(self, passes=2):
+        """Tangle constraint (include/smgpu.h, smgpu_set_tangle_constraint): from now on iterate() puts the points of every cell
+        that an iteration turned bad -- non-positive volume or a wrongly oriented face, by the report's measure -- back where the
+        iteration found them, in up to `passes` marked passes and then a full revert of the iteration.  Cells bad at the current
+        points are exempt.  Adds no synchronisation to the loop.  Refused on an engine with a halo or with boundary point smoothing."""
+        p = _ffi.TangleParams(int(passes))
+        self._check(self._lib.smgpu_set_tangle_constraint(self._h, C.byref(p), 1))
+
+    def clear_tangle_constraint(self):
+        """Switch the tangle constraint off; discards unread records."""
+        self._check(self._lib.smgpu_set_tangle_constraint(self._h, None, 0))
+
+    def tangle_records(self) -> list:
+        """The pending records of the tangle constraint, one per iteration that ran, in ascending iteration; clears them."""
+        n = C.c_int64(0)
+        self._check(self._lib.smgpu_get_tangle_records(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        buf = (_ffi.TangleRecord * n.value)()
+        self._check(self._lib.smgpu_get_tangle_records(self._h, buf, n.value, C.byref(n)))
+        return [TangleRecord(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+
+    def tangle_state(self) -> TangleState:
+        s = _ffi.TangleState()
+        self._check(self._lib.smgpu_get_tangle_state(self._h, C.byref(s)))
+        return TangleState(on=bool(s.on), passes=s.passes, nExemptCells=s.nExemptCells, iteration=s.iteration)
 
     def quality_field(self, name) -> np.ndarray:
         """Per-element quality field in polyMesh order: one of QUALITY_FIELDS (non-orthogonality in degrees, 0 on boundary faces)."""

@@ -18,7 +18,7 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityGuardState, QualityTraceRecord, QUALITY_FIELDS,  # noqa: F401
+from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityGuardState, QualityTraceRecord, TangleRecord, TangleState, QUALITY_FIELDS,  # noqa: F401
                      QUALITY_GEOMETRY_FIELDS, QUALITY_MOTION_FIELDS, QUALITY_SETS, QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS)
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
@@ -446,6 +446,13 @@ def format_trace_warning(rec, initial):
     initial mesh's (`initial`: its MeshQuality)"""
     return (f"    ***Iteration {rec.iteration}: {rec.nNonPositiveVolume} non-positive volume cells and {rec.nWrongOrientedFaces} "
             f"wrongly oriented faces (initial mesh: {initial.nNonPositiveVolume}, {initial.nWrongOrientedFaces})\n")
+
+
+def format_tangle_line(rec):
+    """the line smoothMesh -tangleConstraint prints under the iteration line of an iteration whose nBadCells > 0 (csrc/host/
+    smoothMesh_main.cpp), of a TangleRecord"""
+    return (f"    tangle iteration={rec.iteration} badCells {rec.nBadCells} passes {rec.passes} pointsReverted {rec.nPointsReverted}"
+            + (" fullRevert" if rec.fullRevert else "") + "\n")
 
 
 def format_guard_lines(state):
