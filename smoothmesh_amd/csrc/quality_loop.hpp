@@ -1,0 +1,327 @@
+// quality_loop.hpp -- the mesh quality features that follow smgpu_iterate (DESIGN.md "Mesh quality", 10.10 - 10.12): the quality
+// history, the guard on it, the tangle constraint.  Host code; included by smgpu.hip once, inside its extern "C", in front of
+// iterateBody, which calls into it.  State: smgpu_handle::qt, qg, tg (quality_state.hpp), numbered by smgpu_handle::iterCount.
+// ---- the quality history (kernels_quality_trace.hpp, 10.10) ----
+// the running number of the points the engine holds, and how many of the next n iterations are due a record
+static int64_t qualityTraceNumber(const smgpu_handle* h) { return h->iterCount - h->qt.since; }
+static int qualityTraceDue(const smgpu_handle* h, int n) {
+    const int64_t at = qualityTraceNumber(h);
+    return (int)((at + n) / h->qt.interval - at / h->qt.interval);
+}
+// start of a traced smgpu_iterate call: the trace's device memory (on the first one), and a zeroed slab with one record per due
+// iteration of the call
+static int qualityTraceBegin(smgpu_handle* h, int nIters) {
+    if (qualityEnsure(h)) return 1;
+    const MeshView& m = h->mv;
+    QualityTraceHost& t = h->qt;
+    if (!t.block.live()) {
+        const size_t nFB = (size_t)std::max(1, qualityGrid(m.nFaces)), nCB = (size_t)std::max(1, qualityGrid(m.nCells));
+        const size_t nT = h->useTiles ? (size_t)std::max(1, h->gt.nTiles) : 1;
+        if (t.block.alloc(&t.cellCtr, 3 * (size_t)std::max(1, m.nCells)) || t.block.alloc(&t.facePart, nFB) ||
+            t.block.alloc(&t.cellPart, std::max(nCB, nT)) || t.block.alloc(&t.cellFold, (size_t)std::max(1, qualityGrid((int)nT))) ||
+            t.block.alloc(&t.acc, 1))
+            return t.block.failed("the quality trace");
+        HIP_OK(hipMemsetAsync(t.acc, 0, sizeof(Accum), h->stream));
+    }
+    return t.slab.begin(h->stream, qualityTraceDue(h, nIters));
+}
+// the trace of the points ptsCur now names into the record `out` on the device, behind everything queued on the engine's stream;
+// outside the engine's launch counters and timing events, like the report's geometry launch.  The geometry writes the trace's own
+// cell centres and tests the trace's own stop word, wantAvg is 0 and no deferred finish rides in it: the loop finds everything it
+// reads as it left it.
+static int qualityTraceQueue(smgpu_handle* h, int64_t number, const smgpu_iter_stats* gate, smgpu_quality_trace_record* out) {
+    const MeshView& m = h->mv;
+    State ts = h->st;
+    ts.cellCtr = h->qt.cellCtr;
+    ts.acc = h->qt.acc;
+    ts.stats = nullptr;
+    const bool fused = h->qt.fusedWanted && h->useTiles && h->gt.nTiles > 0;
+    const int nFB = qualityGrid(m.nFaces);
+    int nCB = qualityGrid(m.nCells);
+    const QCell* cPart = h->qt.cellPart;
+    if (h->useTiles) {
+        const int nT = h->gt.nTiles;
+        if (nT > 0)
+            withGeomTile(h, [&](auto tile, auto org) {
+                constexpr int T = decltype(tile)::value;
+                constexpr bool ORG = decltype(org)::value;
+                if (fused) {
+                    ensureDynLds(k_quality_geom_tile<T, ORG>, h->device, h->geomLds);
+                    hipLaunchKernelGGL((k_quality_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, nT,
+                                       h->xcdMap, h->qt.thr, h->qt.cellPart, gate);
+                } else {   // the report's geometry launch: writeFaces, no face averages, and the engine's deferred finish is not this launch's to close
+                    ensureDynLds(k_geom_tile<T, ORG>, h->device, h->geomLds);
+                    hipLaunchKernelGGL((k_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, 0, 1,
+                                       (const int*)nullptr, nT, h->xcdMap, 0, 0, (double*)nullptr, (double*)nullptr);
+                }
+            });
+    } else {
+        if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
+        if (m.nCells > 0) hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
+    }
+    if (nFB > 0)
+        hipLaunchKernelGGL(k_quality_faces<false>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, ts.ptsCur, ts.fCtr, ts.fArea, ts.cellCtr, h->q.own, h->q.nei,
+                           QCoupling<false>{}, h->qt.thr, h->qt.facePart, (double*)nullptr, (double*)nullptr);
+    if (fused) {
+        nCB = qualityGrid(h->gt.nTiles);
+        hipLaunchKernelGGL(k_quality_trace_fold, dim3(nCB), dim3(kQualityBlock), 0, h->stream, h->qt.cellPart, h->gt.nTiles, h->qt.cellFold, gate);
+        cPart = h->qt.cellFold;
+    } else if (nCB > 0) {
+        hipLaunchKernelGGL(k_quality_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, ts.fCtr, ts.fArea, h->qt.thr, h->qt.cellPart, (double*)nullptr,
+                           (double*)nullptr, (double*)nullptr);
+    }
+    hipLaunchKernelGGL(k_quality_trace_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qt.facePart, nFB, cPart, nCB, m.nCells, m.nFaces, m.nInternalFaces,
+                       (long long)number, out, gate);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+static int qualityGuardDisarm(smgpu_handle* h, bool release);
+int smgpu_set_quality_trace(smgpu_handle* h, int32_t interval, const smgpu_quality_params* p) {
+    if (!h) return fail("null handle");
+    if (interval < 0) return fail("smgpu_set_quality_trace: interval < 0");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    HIP_OK(hipSetDevice(h->device));
+    if (qualityGuardDisarm(h, true)) return 1;   // the numbering restarts: the guard's iteration numbers would name other points
+    h->qt.interval = interval;
+    h->qt.since = h->iterCount;
+    h->qt.slab.discard();
+    h->qt.thr = qualityThresholds(p);
+    if (interval == 0) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        h->qt.release();
+    }
+    return 0;
+}
+int smgpu_get_quality_trace(smgpu_handle* h, smgpu_quality_trace_record* out, int64_t cap, int64_t* n) {
+    if (!h || !n) return fail("null argument");
+    return h->qt.slab.drain(out, cap, n, "smgpu_get_quality_trace");
+}
+
+// ---- the guard on the quality history (kernels_quality_guard.hpp, DESIGN.md "Mesh quality", 10.11) ----
+static int qualityGuardDisarm(smgpu_handle* h, bool release) {
+    h->qg.armed = false;
+    h->qg.tripPending = false;
+    h->qg.state.armed = 0;
+    if (release && h->qg.block.live()) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        h->qg.release();
+    }
+    return 0;
+}
+// the per-point state an iteration carries to the next (State's non-const pointers that an iteration reads before it writes them:
+// ptsCur, and layerNormal with layers) between the engine and the snapshot, on the engine's stream
+static int qualityGuardCopy(smgpu_handle* h, bool restore, int64_t number, bool needGood) {
+    const long long n = 3 * (long long)h->mv.nPoints;
+    const bool normals = h->layersOn && h->qg.normal && h->st.layerNormal;
+    const double *s0 = restore ? h->qg.pts : h->st.ptsCur, *s1 = normals ? (restore ? h->qg.normal : h->st.layerNormal) : nullptr;
+    double *d0 = restore ? h->st.ptsCur : h->qg.pts, *d1 = normals ? (restore ? h->st.layerNormal : h->qg.normal) : nullptr;
+    const int grid = (int)std::max<long long>(1, ((n >> 1) + (long long)kGuardBlock * kGuardPer - 1) / ((long long)kGuardBlock * kGuardPer));
+    if (normals) hipLaunchKernelGGL(k_quality_guard_snapshot<true>, dim3(grid), dim3(kGuardBlock), 0, h->stream, s0, d0, s1, d1, n, (long long)number, h->qg.dev, needGood ? 1 : 0);
+    else hipLaunchKernelGGL(k_quality_guard_snapshot<false>, dim3(grid), dim3(kGuardBlock), 0, h->stream, s0, d0, s1, d1, n, (long long)number, h->qg.dev, needGood ? 1 : 0);
+    HIP_OK(hipGetLastError());
+    if (restore) { h->q.epoch++; h->geomAheadDone = false; }
+    return 0;
+}
+// behind k_quality_trace_final of a traced iteration: the verdict on its record, then the snapshot if it passed
+static int qualityGuardQueue(smgpu_handle* h, const smgpu_quality_trace_record* rec, int64_t number, const smgpu_iter_stats* gate) {
+    hipLaunchKernelGGL(k_quality_guard_verdict, dim3(1), dim3(64), 0, h->stream, rec, h->qg.dev, (unsigned)h->qg.prm.criteria, &h->st.acc->stop, gate);
+    HIP_OK(hipGetLastError());
+    return qualityGuardCopy(h, false, number, true);
+}
+// After the read-back of a call that tripped: back to the snapshot; with `refine`, on from it one iteration at a time, a trace and
+// a verdict behind each, until one fails or interval - 1 have passed (the loop is deterministic from the snapshot's state, so
+// these are the iterations of the call over again).  The steps go through smgpu_iterate's body with the trace at interval 1;
+// what they would leave behind -- launch counts, timing events, the near-tie census, trace records -- is put back or not kept.
+// The engine's iteration count goes back to the restored iteration, and every running number with it.
+static int qualityGuardAfterTrip(smgpu_handle* h) {
+    h->qg.tripPending = false;
+    if (qualityGuardCopy(h, true, -1, false)) return 1;
+    int64_t good = h->qg.state.snapshotIteration;
+    const int interval = h->qt.interval;
+    int rc = 0;
+    if (h->qg.prm.refine && interval > 1) {
+        Uncounted scope(h);
+        unsigned long long nearSaved[3] = {0, 0, 0};
+        if (h->st.nearTotal) HIP_OK(hipMemcpyAsync(nearSaved, h->st.nearTotal, sizeof(nearSaved), hipMemcpyDeviceToHost, h->stream));
+        HIP_OK(hipMemsetAsync(&h->qg.dev->tripped, 0, sizeof(int), h->stream));
+        HIP_OK(hipStreamSynchronize(h->stream));
+        h->qg.refining = true;
+        h->qt.interval = 1;
+        for (int step = 1; step < interval && !rc; ++step) {
+            h->iterCount = h->qt.since + good;
+            int32_t done = 0;
+            rc = iterateBody(h, 1, 0.0, nullptr, &done);
+            if (rc) break;
+            if (done != 1 || h->qg.lastVerdict != kGuardGood) {   // the first bad step: the snapshot is the state before it
+                rc = qualityGuardCopy(h, true, -1, false);
+                break;
+            }
+            ++good;
+        }
+        h->qt.interval = interval;
+        h->qg.refining = false;
+        if (!rc && h->st.nearTotal) HIP_OK(hipMemcpyAsync(h->st.nearTotal, nearSaved, sizeof(nearSaved), hipMemcpyHostToDevice, h->stream));
+        HIP_OK(hipStreamSynchronize(h->stream));
+        if (rc) return 1;
+    }
+    h->qg.state.snapshotIteration = good;
+    h->qg.state.restoredIteration = good;
+    h->iterCount = h->qt.since + good;
+    return qualityGuardDisarm(h, false);
+}
+
+int smgpu_set_quality_guard(smgpu_handle* h, const smgpu_quality_guard_params* p, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityGuardDisarm(h, true);
+    const smgpu_quality_guard_params prm = p ? *p : smgpu_quality_guard_params{SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED, 1};
+    const uint32_t all = SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED | SMGPU_GUARD_ERROR_NONORTH;
+    if (prm.criteria == 0 || (prm.criteria & ~all)) return fail("smgpu_set_quality_guard: criteria must be a non-empty combination of SMGPU_GUARD_NONPOSITIVE_VOLUME, _WRONG_ORIENTED and _ERROR_NONORTH");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    if (h->bndOn)
+        return fail("smgpu_set_quality_guard: not available on an engine with boundary point smoothing (its point normals are a running blend across the "
+                    "iterations and its corner lists are host state, neither of which the guard's snapshot holds)");
+    if (h->qt.interval <= 0) return fail("smgpu_set_quality_guard: the guard judges the records of the quality trace; switch it on first (smgpu_set_quality_trace)");
+    if (h->iterOpen) return fail("smgpu_set_quality_guard: between smgpu_iter_begin and smgpu_iter_end");
+    if (qualityGuardDisarm(h, true)) return 1;
+    if (flushDeferred(h)) return 1;
+    if (qualityTraceBegin(h, 0)) return 1;
+    QualityGuardHost& g = h->qg;
+    const size_t n = 3 * (size_t)std::max(1, h->mv.nPoints);
+    if (g.block.alloc(&g.dev, 1) || g.block.alloc(&g.rec, 1) || g.block.alloc(&g.pts, n) ||
+        (h->layersOn && h->st.layerNormal && g.block.alloc(&g.normal, n)))
+        return g.block.failed("the quality guard");
+    HIP_OK(hipMemsetAsync(h->qg.dev, 0, sizeof(GuardDev), h->stream));
+    HIP_OK(hipMemsetAsync(h->qg.rec, 0, sizeof(smgpu_quality_trace_record), h->stream));
+    // the baseline: the trace's launches on the current points, number 0
+    if (qualityTraceQueue(h, 0, nullptr, h->qg.rec)) { h->qg.release(); return 1; }
+    HIP_OK(hipMemcpyAsync(&h->qg.dev->baseline, h->qg.rec, sizeof(smgpu_quality_trace_record), hipMemcpyDeviceToDevice, h->stream));
+    h->qg.prm = prm;
+    h->qg.state = smgpu_quality_guard_state{};
+    if (qualityGuardCopy(h, false, qualityTraceNumber(h), false)) { h->qg.release(); return 1; }
+    HIP_OK(hipMemcpyAsync(&h->qg.state.baseline, h->qg.rec, sizeof(smgpu_quality_trace_record), hipMemcpyDeviceToHost, h->stream));
+    if (checkDeviceError(h)) { h->qg.release(); return 1; }
+    h->qg.state.armed = 1;
+    h->qg.state.snapshotIteration = qualityTraceNumber(h);
+    h->qg.armed = true;
+    return 0;
+}
+int smgpu_get_quality_guard(smgpu_handle* h, smgpu_quality_guard_state* out) {
+    if (!h || !out) return fail("null argument");
+    *out = h->qg.state;
+    return 0;
+}
+int smgpu_quality_guard_restore(smgpu_handle* h) {
+    if (!h) return fail("null handle");
+    if (!h->qg.armed) return fail("smgpu_quality_guard_restore: the quality guard is not armed (smgpu_set_quality_guard)");
+    HIP_OK(hipSetDevice(h->device));
+    if (flushDeferred(h)) return 1;
+    if (qualityGuardCopy(h, true, -1, false)) return 1;
+    if (checkDeviceError(h)) return 1;
+    h->qg.state.restoredIteration = h->qg.state.snapshotIteration;
+    h->iterCount = h->qt.since + h->qg.state.snapshotIteration;   // every running number names the same points
+    return 0;
+}
+
+// ---- the tangle constraint (kernels_quality_tangle.hpp, DESIGN.md "Mesh quality", 10.12) ----
+static int tangleOff(smgpu_handle* h) {
+    h->tg.on = false;
+    h->tg.slab.discard();
+    if (h->tg.block.live()) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        h->tg.release();
+    }
+    return 0;
+}
+// one evaluation of the points ptsCur names, behind everything queued on the engine's stream; outside the launch counters and
+// the timing events.  Tiles: nothing the loop reads is written.  Without tiles the direct geometry kernels write the loop's face
+// values (the next geometry launch writes them again before anything reads them), cell centres of the constraint's own, and
+// test a stop word of its own.
+static int tangleEvaluate(smgpu_handle* h, uint8_t* exemptOut, int pass, const smgpu_iter_stats* gate) {
+    const MeshView& m = h->mv;
+    State ts = h->st;
+    ts.stats = nullptr;
+    if (h->useTiles) {
+        const int nT = h->gt.nTiles;
+        if (nT > 0)
+            withGeomTile(h, [&](auto tile, auto org) {
+                constexpr int T = decltype(tile)::value;
+                constexpr bool ORG = decltype(org)::value;
+                ensureDynLds(k_tangle_tile<T, ORG>, h->device, h->geomLds);
+                hipLaunchKernelGGL((k_tangle_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, nT, h->xcdMap,
+                                   exemptOut ? (const uint8_t*)nullptr : (const uint8_t*)h->tg.exempt, exemptOut, h->tg.marks, h->tg.dev, pass, gate);
+            });
+    } else {
+        ts.cellCtr = h->tg.cellCtr;
+        ts.acc = h->tg.acc;
+        if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
+        if (m.nCells > 0) {
+            hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
+            hipLaunchKernelGGL(k_tangle_cells, dim3((m.nCells + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, m, ts.fCtr, ts.fArea,
+                               ts.cellCtr, exemptOut ? (const uint8_t*)nullptr : (const uint8_t*)h->tg.exempt, exemptOut, h->tg.marks, h->tg.dev, pass, gate);
+        }
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+// behind the movePoints of an iteration: the passes on the points ptsCur now names; x: the points the iteration started from
+static int tangleQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x) {
+    smgpu_tangle_record* rec = nullptr;
+    if (h->tg.slab.slot(slot, &rec)) return 1;
+    const int nP = h->mv.nPoints;
+    const int gApply = std::max(1, (int)(((int64_t)nP + kTanglePts - 1) / kTanglePts));
+    for (int k = 0; k <= h->tg.passes; ++k) {
+        if (tangleEvaluate(h, nullptr, k, gate)) return 1;
+        hipLaunchKernelGGL(k_tangle_verdict, dim3(1), dim3(64), 0, h->stream, h->tg.dev, rec, (long long)number, k, h->tg.passes, gate);
+        hipLaunchKernelGGL(k_tangle_apply, dim3(gApply), dim3(kTangleBlock), 0, h->stream, x, h->st.ptsCur, h->tg.marks, nP, (const TangleDev*)h->tg.dev, rec, gate);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_set_tangle_constraint(smgpu_handle* h, const smgpu_tangle_params* p, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return tangleOff(h);
+    const smgpu_tangle_params prm = p ? *p : smgpu_tangle_params{2};
+    if (prm.passes < 0) return fail("smgpu_set_tangle_constraint: passes < 0");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    if (h->bndOn)
+        return fail("smgpu_set_tangle_constraint: not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
+                    "points from state that a reverted iteration would leave ahead of the points)");
+    if (h->iterOpen) return fail("smgpu_set_tangle_constraint: between smgpu_iter_begin and smgpu_iter_end");
+    if (tangleOff(h)) return 1;
+    if (flushDeferred(h)) return 1;
+    const MeshView& m = h->mv;
+    const size_t nMark = ((size_t)std::max(1, m.nPoints) + 3) & ~(size_t)3, nCell = (size_t)std::max(1, m.nCells);
+    TangleHost& t = h->tg;
+    if (t.block.alloc(&t.dev, 1) || t.block.alloc(&t.exempt, nCell) || t.block.alloc(&t.marks, nMark) ||
+        (!h->useTiles && (t.block.alloc(&t.cellCtr, 3 * nCell) || t.block.alloc(&t.acc, 1))))
+        return t.block.failed("the tangle constraint");
+    HIP_OK(hipMemsetAsync(h->tg.dev, 0, sizeof(TangleDev), h->stream));
+    HIP_OK(hipMemsetAsync(h->tg.exempt, 0, nCell, h->stream));
+    HIP_OK(hipMemsetAsync(h->tg.marks, 0, nMark, h->stream));
+    if (h->tg.acc) HIP_OK(hipMemsetAsync(h->tg.acc, 0, sizeof(Accum), h->stream));
+    // the exempt cells: one evaluation of the current points
+    h->tg.passes = prm.passes;
+    if (tangleEvaluate(h, h->tg.exempt, 0, nullptr)) { h->tg.release(); return 1; }
+    TangleDev td{};
+    HIP_OK(hipMemcpyAsync(&td, h->tg.dev, sizeof(TangleDev), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemsetAsync(h->tg.dev, 0, sizeof(TangleDev), h->stream));
+    if (checkDeviceError(h)) { h->tg.release(); return 1; }
+    h->tg.nExempt = td.badNow;
+    h->tg.since = h->iterCount;
+    h->tg.on = true;
+    return 0;
+}
+int smgpu_get_tangle_records(smgpu_handle* h, smgpu_tangle_record* out, int64_t cap, int64_t* n) {
+    if (!h || !n) return fail("null argument");
+    return h->tg.slab.drain(out, cap, n, "smgpu_get_tangle_records");
+}
+int smgpu_get_tangle_state(smgpu_handle* h, smgpu_tangle_state* out) {
+    if (!h || !out) return fail("null argument");
+    *out = smgpu_tangle_state{h->tg.on ? 1 : 0, h->tg.passes, h->tg.on ? h->tg.nExempt : 0, h->tg.on ? h->iterCount - h->tg.since : 0};
+    return 0;
+}
+

@@ -1,0 +1,176 @@
+// quality_state.hpp -- host state of the mesh quality features (DESIGN.md "Mesh quality"): the owners of their device memory and
+// the four groups of members smgpu_handle carries.  Included by smgpu.hip once, before the handle (after fail() and HIP_OK).
+// All of this memory lives outside the handle's `allocs`: deviceBytes stays what the loop holds.
+#pragma once
+
+// Owner of one feature's device memory: alloc() fills a pointer member and remembers where that member is, release() frees and
+// nulls every member it filled: a feature names its pointers once, where it allocates them.
+class DevBlock {
+    std::vector<void**> slots;
+    hipError_t err = hipSuccess;
+  public:
+    DevBlock() = default;
+    DevBlock(const DevBlock&) = delete;
+    DevBlock& operator=(const DevBlock&) = delete;
+    // n elements of T into the null member *slot; an error (non-zero) leaves the block as it was: see failed()
+    template <class T>
+    hipError_t alloc(T** slot, size_t n) {
+        void* p = nullptr;
+        err = hipMalloc(&p, sizeof(T) * n);
+        if (err != hipSuccess) return err;
+        *slot = (T*)p;
+        slots.push_back((void**)slot);
+        return hipSuccess;
+    }
+    bool live() const { return !slots.empty(); }
+    void release() {
+        for (void** s : slots) { (void)hipFree(*s); *s = nullptr; }
+        slots.clear();
+    }
+    // after an alloc() that returned an error: everything released, and the refusal "mesh quality: device memory for <what>: ..."
+    int failed(const char* what) {
+        release();
+        return fail(std::string("mesh quality: device memory for ") + what + ": " + hipGetErrorString(err));
+    }
+};
+
+// The records one smgpu_iterate call leaves on the device, one slot per record in queueing order, and those of earlier calls
+// that nobody has fetched yet.  A record whose `iteration` is 0 was not written (its iteration did not run).
+template <class Rec>
+class RecordSlab {
+    const char* what;            // the feature, in the refusals
+    Rec* dev = nullptr;
+    int cap = 0;
+    std::vector<Rec> back;       // the read-back of the call
+    std::vector<Rec> pending;
+  public:
+    explicit RecordSlab(const char* feature) : what(feature) {}
+    RecordSlab(const RecordSlab&) = delete;
+    RecordSlab& operator=(const RecordSlab&) = delete;
+    // start of a call that queues up to n records: n zeroed slots (outgrown: replaced; nothing is in flight between two calls)
+    int begin(hipStream_t stream, int n) {
+        if (n > cap) {
+            if (dev) {
+                HIP_OK(hipStreamSynchronize(stream));
+                release();
+            }
+            const hipError_t e = hipMalloc((void**)&dev, sizeof(Rec) * (size_t)n);
+            if (e != hipSuccess) return fail(std::string("mesh quality: device memory for the ") + what + ": " + hipGetErrorString(e));
+            cap = n;
+        }
+        if (n > 0) HIP_OK(hipMemsetAsync(dev, 0, sizeof(Rec) * (size_t)n, stream));
+        return 0;
+    }
+    // *rec: the device address of slot i, one of those begin() made
+    int slot(int i, Rec** rec) const {
+        if (i >= cap) return fail(std::string("mesh quality: ") + what + " slab overrun");
+        *rec = dev + i;
+        return 0;
+    }
+    // queues the copy of the first n slots to the host; complete once the stream has been waited for
+    int readBack(hipStream_t stream, int n) {
+        back.resize((size_t)n);
+        if (n > 0) HIP_OK(hipMemcpyAsync(back.data(), dev, sizeof(Rec) * (size_t)n, hipMemcpyDeviceToHost, stream));
+        return 0;
+    }
+    // the written ones of the first n records read back become pending
+    void keep(int n) {
+        for (int i = 0; i < n; ++i)
+            if (back[(size_t)i].iteration != 0) pending.push_back(back[(size_t)i]);
+    }
+    void discard() { pending.clear(); }
+    // the getter of the pending records (out == NULL: their number only); a read clears them
+    int drain(Rec* out, int64_t capOut, int64_t* n, const char* api) {
+        const int64_t have = (int64_t)pending.size();
+        if (!out) { *n = have; return 0; }
+        if (capOut < have) return fail(std::string(api) + ": cap " + std::to_string(capOut) + " is below the " + std::to_string(have) + " pending records");
+        if (have > 0) std::memcpy(out, pending.data(), sizeof(Rec) * (size_t)have);
+        pending.clear();
+        *n = have;
+        return 0;
+    }
+    // the device slab (the pending records stay)
+    void release() { if (dev) (void)hipFree(dev); dev = nullptr; cap = 0; }
+};
+
+// The three reports (smgpu_mesh_quality, _geometry, _motion; kernels_quality*.hpp) and their coupled forms.  Each block is
+// allocated by the first call that needs it.
+struct QualityReportHost {
+    // the base report: owner / neighbour by face, the two partial slabs and the report
+    DevBlock base;
+    int *own = nullptr, *nei = nullptr;
+    QFace* facePart = nullptr;
+    QCell* cellPart = nullptr;
+    smgpu_quality* out = nullptr;
+    // the -allGeometry checks: the cell volumes the face pass reads, the two partial slabs and the report
+    DevBlock geom;
+    double* vol = nullptr;
+    QGFace* gFacePart = nullptr;
+    QGCell* gCellPart = nullptr;
+    smgpu_quality_geometry* gOut = nullptr;
+    // the motion criteria: the partial slab and the report
+    DevBlock motion;
+    QMFace* mFacePart = nullptr;
+    smgpu_quality_motion* mOut = nullptr;
+    // a sub-domain's coupled reports (smgpu_quality_coupled_*): processor faces in patch order, the recvCc slot of every boundary
+    // face (-1: physical patch), the coupling they were built from, the three records.  A pack with another coupling releases it
+    DevBlock coupled;
+    int *procFace = nullptr, *slot = nullptr;
+    int nProc = 0, notCounted = 0, countedProc = 0;
+    std::vector<int32_t> coupling;
+    smgpu_quality_part* partOut = nullptr;
+    smgpu_quality_geometry_part* gPartOut = nullptr;
+    smgpu_quality_motion_part* mPartOut = nullptr;
+    // epoch moves whenever the points (or the geometry variant) may have changed; packEpoch: that of the last pack; volEpoch,
+    // volCoupling: epoch and coupling of the last pack_volumes (another coupling's slots differ: its sendVc / recvVc no longer fit)
+    uint64_t epoch = 1, packEpoch = 0, volEpoch = 0;
+    std::vector<int32_t> volCoupling;
+    void release() { base.release(); geom.release(); motion.release(); coupled.release(); }
+};
+
+// The quality history (smgpu_set_quality_trace, kernels_quality_trace.hpp): allocated by the first traced smgpu_iterate.  Its
+// geometry launch writes cell centres of its own and reads a stop word of its own (always 0): nothing the loop reads is written
+struct QualityTraceHost {
+    int interval = 0;                       // 0: off
+    int64_t since = 0;                      // smgpu_handle::iterCount at switching on: a record's number is the count less this
+    bool fusedWanted = true;                // SMGPU_QUALITY_TRACE_FUSED=0: the report's launches instead of k_quality_geom_tile
+    QualityThresholds thr{};
+    DevBlock block;
+    double* cellCtr = nullptr;
+    Accum* acc = nullptr;
+    QFace* facePart = nullptr;
+    QCell *cellPart = nullptr, *cellFold = nullptr;
+    RecordSlab<smgpu_quality_trace_record> slab{"quality trace"};   // one record per due iteration of the call
+    void release() { block.release(); slab.release(); }
+};
+
+// The guard on the trace (smgpu_set_quality_guard, kernels_quality_guard.hpp): allocated at arming.  pts / normal: the snapshot;
+// rec: the record slot of the baseline; state: what smgpu_get_quality_guard answers
+struct QualityGuardHost {
+    bool armed = false;
+    bool refining = false;                  // inside the search for the last good iteration: smgpu_iterate's body leaves no trace
+    bool tripPending = false;               // the call that just read back tripped: roll back before it returns
+    int lastVerdict = 0;                    // the verdict word after the last read-back
+    smgpu_quality_guard_params prm{SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED, 1};
+    smgpu_quality_guard_state state{};
+    DevBlock block;
+    GuardDev* dev = nullptr;
+    smgpu_quality_trace_record* rec = nullptr;
+    double *pts = nullptr, *normal = nullptr;
+    void release() { block.release(); }
+};
+
+// The tangle constraint (smgpu_set_tangle_constraint, kernels_quality_tangle.hpp): allocated at enabling.  exempt: one byte per
+// cell; marks: one per point (rounded up to whole words); cellCtr / acc: as the trace's, for the evaluation without tiles
+struct TangleHost {
+    bool on = false;
+    int passes = 2;
+    int64_t since = 0, nExempt = 0;         // smgpu_handle::iterCount at enabling (numbers as the trace's); exempt cells
+    DevBlock block;
+    uint8_t *exempt = nullptr, *marks = nullptr;
+    TangleDev* dev = nullptr;
+    double* cellCtr = nullptr;
+    Accum* acc = nullptr;
+    RecordSlab<smgpu_tangle_record> slab{"tangle constraint"};       // one record per iteration of the call
+    void release() { block.release(); slab.release(); }
+};

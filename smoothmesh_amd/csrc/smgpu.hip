@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.hpp"
@@ -48,6 +49,8 @@ enum KernelId { K_FACE_GEOM = 0, K_CELL_CENTRES, K_SMOOTH_FINAL, K_SMOOTH_PROP, 
 static const char* kKernelNames[K_COUNT] = {"k_face_geom", "k_cell_centres", "k_smooth<final>", "k_smooth<proposal>",
                                             "k_edge_angle", "k_fa_edges", "k_fa_points", "k_fa_pred", "k_fa_walk",
                                             "k_apply", "k_finish", "k_halo_*", "k_geom_tile", "k_edge_angle_filter", "k_fa_edges_filter", "k_bnd_*"};
+
+#include "quality_state.hpp"
 
 struct smgpu_handle {
     Topology topo;
@@ -226,73 +229,13 @@ struct smgpu_handle {
     size_t edgeLds = 0;
     bool eaCoop = true;        // wave-cooperative edge-angle kernel (SMGPU_EDGE_ANGLE=faithful selects the per-angle acos form)
     int eaMaxEntries = 0;
-    // mesh quality report (smgpu_mesh_quality, kernels_quality.hpp): allocated by the first report, outside `allocs` (deviceBytes
-    // stays what the loop holds)
-    int *qOwn = nullptr, *qNei = nullptr;
-    QFace* qFacePart = nullptr;
-    QCell* qCellPart = nullptr;
-    smgpu_quality* qOut = nullptr;
-    // ... and of a sub-domain's coupled report (smgpu_quality_coupled_*): processor faces in patch order, the recvCc slot of every
-    // boundary face (-1: physical patch), the coupling they were built from, and the geometry epoch of the last pack
-    int *qProcFace = nullptr, *qSlot = nullptr;
-    int qNProc = 0, qNotCounted = 0, qCountedProc = 0;
-    std::vector<int32_t> qCoupling;
-    smgpu_quality_part* qPartOut = nullptr;
-    // ... and of the -allGeometry checks (smgpu_mesh_quality_geometry, kernels_quality_geom.hpp): the cell volumes the face pass
-    // reads, the two partial slabs and the report, allocated by the first such call, outside `allocs` as well
-    double* qgVol = nullptr;
-    QGFace* qgFacePart = nullptr;
-    QGCell* qgCellPart = nullptr;
-    smgpu_quality_geometry* qgOut = nullptr;
-    // ... and of the motion criteria (smgpu_mesh_quality_motion, kernels_quality_motion.hpp): the partial slab and the report, likewise
-    QMFace* qmFacePart = nullptr;
-    smgpu_quality_motion* qmOut = nullptr;
-    // ... and of the two reports above for a sub-domain (smgpu_quality_coupled_geometry_* / _motion_*):
-    // the records; the scratch is the serial reports' (qgVol, the partial slabs).  qVolEpoch, qVolCoupling: the geometry epoch and the coupling of the
-    // last pack_volumes (a later pack with another coupling lays the slots out anew: sendVc / recvVc of the old one no longer fit)
-    smgpu_quality_geometry_part* qgPartOut = nullptr;
-    smgpu_quality_motion_part* qmPartOut = nullptr;
-    uint64_t qVolEpoch = 0;
-    std::vector<int32_t> qVolCoupling;
-    // ... and of the quality history (smgpu_set_quality_trace, kernels_quality_trace.hpp): allocated by the first traced smgpu_iterate,
-    // outside `allocs` as well.  The trace's geometry launch writes cell centres of its own and reads a stop word of its own
-    // (always 0), so that nothing the loop reads is written between two iterations; qtSlab: the records of one smgpu_iterate call
-    int qtInterval = 0;                     // 0: off
-    int64_t qtIter = 0;                     // iterations that ran since smgpu_set_quality_trace
-    bool qtFusedWanted = true;              // SMGPU_QUALITY_TRACE_FUSED=0: the report's launches instead of k_quality_geom_tile
-    QualityThresholds qtThr{};
-    double* qtCellCtr = nullptr;
-    Accum* qtAcc = nullptr;
-    QFace* qtFacePart = nullptr;
-    QCell *qtCellPart = nullptr, *qtCellFold = nullptr;
-    smgpu_quality_trace_record* qtSlab = nullptr;
-    int qtSlabCap = 0;
-    std::vector<smgpu_quality_trace_record> qtPending;
-    // ... and of the guard on it (smgpu_set_quality_guard, kernels_quality_guard.hpp): allocated at arming, outside `allocs` too.
-    // qgPts / qgNormal: the snapshot; qgRec: the record slot of the baseline; qgState: what smgpu_get_quality_guard answers
-    bool qgArmed = false;
-    bool qgRefining = false;                // inside the search for the last good iteration: smgpu_iterate's body leaves no trace
-    bool qgTripPending = false;             // the call that just read back tripped: roll back before it returns
-    int qgLastVerdict = 0;                  // the verdict word after the last read-back
-    smgpu_quality_guard_params qgPrm{SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED, 1};
-    smgpu_quality_guard_state qgState{};
-    GuardDev* qgDev = nullptr;
-    smgpu_quality_trace_record* qgRec = nullptr;
-    double *qgPts = nullptr, *qgNormal = nullptr;
-    // ... and of the tangle constraint (smgpu_set_tangle_constraint, kernels_quality_tangle.hpp): allocated at enabling, outside
-    // `allocs` too.  tgExempt: one byte per cell; tgMarks: one per point (rounded up to whole words); tgSlab: the records of one
-    // smgpu_iterate call; tgCellCtr / tgAcc: cell centres and a stop word (always 0) of its own for the evaluation without tiles
-    bool tgOn = false;
-    int tgPasses = 2;
-    int64_t tgIter = 0, tgNExempt = 0;      // iterations that ran since enabling; exempt cells
-    uint8_t *tgExempt = nullptr, *tgMarks = nullptr;
-    TangleDev* tgDev = nullptr;
-    smgpu_tangle_record* tgSlab = nullptr;
-    int tgSlabCap = 0;
-    double* tgCellCtr = nullptr;
-    Accum* tgAcc = nullptr;
-    std::vector<smgpu_tangle_record> tgPending;
-    uint64_t qEpoch = 1, qPackEpoch = 0;   // qEpoch moves whenever the points (or the geometry variant) may have changed
+    // mesh quality (quality_state.hpp): the reports, the quality history, the guard on it, the tangle constraint.  iterCount: the
+    // iterations smgpu_iterate has completed (the guard's rollbacks set it back); trace and constraint number their records by it
+    QualityReportHost q;
+    QualityTraceHost qt;
+    QualityGuardHost qg;
+    TangleHost tg;
+    int64_t iterCount = 0;
     bool iterOpen = false;                  // between smgpu_iter_begin and smgpu_iter_end
 };
 
@@ -843,7 +786,7 @@ int smgpu_create(const smgpu_mesh_desc* d, smgpu_handle** out) {
     h->faLists = envInt("SMGPU_FA_LISTS", 1) != 0;
     h->faSideExact = envInt("SMGPU_FA_SIDE_EXACT", 1) != 0;
     h->bndInGeom = envInt("SMGPU_BND_IN_GEOM", 1) != 0;
-    h->qtFusedWanted = envInt("SMGPU_QUALITY_TRACE_FUSED", 1) != 0;
+    h->qt.fusedWanted = envInt("SMGPU_QUALITY_TRACE_FUSED", 1) != 0;
     { const char* fv = std::getenv("SMGPU_FOAM_VARIANT"); h->foamOrg = fv && std::string(fv) == "org"; }
     { const char* sv = std::getenv("SMGPU_SYNC_VARIANT"); h->st.ownFold = (sv && std::string(sv) == "own") ? 1 : 0; }
     if (h->useTiles) {
@@ -1178,13 +1121,7 @@ int smgpu_destroy(smgpu_handle* h) {
     if (h->gtDev.valid)      // (a create that failed before the handle took the device-built tile tables over)
         for (const GeomTilesDev::Arr* a : {&h->gtDev.cellOrder, &h->gtDev.cellBeg, &h->gtDev.tpIds, &h->gtDev.tfIds, &h->gtDev.faceVerts, &h->gtDev.cellFaces, &h->gtDev.meta})
             if (a->p) (void)hipFree(a->p);
-    for (void* p : {(void*)h->qOwn, (void*)h->qNei, (void*)h->qFacePart, (void*)h->qCellPart, (void*)h->qOut, (void*)h->qProcFace, (void*)h->qSlot,
-                    (void*)h->qPartOut, (void*)h->qgVol, (void*)h->qgFacePart, (void*)h->qgCellPart, (void*)h->qgOut,
-                    (void*)h->qmFacePart, (void*)h->qmOut, (void*)h->qgPartOut, (void*)h->qmPartOut, (void*)h->qtCellCtr, (void*)h->qtAcc,
-                    (void*)h->qtFacePart, (void*)h->qtCellPart, (void*)h->qtCellFold, (void*)h->qtSlab, (void*)h->qgDev, (void*)h->qgRec,
-                    (void*)h->qgPts, (void*)h->qgNormal, (void*)h->tgExempt, (void*)h->tgMarks, (void*)h->tgDev, (void*)h->tgSlab,
-                    (void*)h->tgCellCtr, (void*)h->tgAcc})
-        if (p) (void)hipFree(p);
+    h->q.release(); h->qt.release(); h->qg.release(); h->tg.release();
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
     for (hipEvent_t e : h->evWalkLag) if (e) (void)hipEventDestroy(e);
@@ -1307,7 +1244,7 @@ int smgpu_set_foam_variant(smgpu_handle* h, int32_t variant) {
     if (!h) return fail("null handle");
     if (variant != SMGPU_FOAM_COM && variant != SMGPU_FOAM_ORG) return fail("smgpu_set_foam_variant: unknown variant");
     h->foamOrg = variant == SMGPU_FOAM_ORG;
-    h->qEpoch++;
+    h->q.epoch++;
     h->geomAheadDone = false;
     return 0;
 }
@@ -1346,28 +1283,16 @@ static void ensureDynLds(K kernel, int device, size_t bytes) {
     if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) have[device] = bytes;
     else (void)hipGetLastError();
 }
-template <int T, bool ORG>
-static void launchGeomTileAs(smgpu_handle* h, const MeshView& m, const State& s, int wantAvg, const int* tileList, int nTiles, hipEvent_t evA, hipEvent_t evB,
-                             bool withBndPre) {
-    if (withBndPre) {   // the boundary pre-kernels in the first workgroups of this launch (k_geom_tile_bnd)
-        const int nNormal = (h->bv.nB + T - 1) / T, nFeat = (h->bv.nFeat + (T / 64) - 1) / (T / 64);
-        const int nBnd = ((nNormal + nFeat + 7) / 8) * 8;
-        ensureDynLds(k_geom_tile_bnd<T, ORG>, h->device, h->geomLds);
-        hipExtLaunchKernelGGL((k_geom_tile_bnd<T, ORG>), dim3(nBnd + tileGrid(nTiles, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, evA, evB, 0, m, s, h->gv,
-                              wantAvg, h->writeFaces ? 1 : 0, tileList, nTiles, h->xcdMap, h->deferN, h->deferIter, h->deferLocal, h->deferHist, h->bv, nBnd, nNormal);
-    } else {
-        ensureDynLds(k_geom_tile<T, ORG>, h->device, h->geomLds);
-        hipExtLaunchKernelGGL((k_geom_tile<T, ORG>), dim3(tileGrid(nTiles, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, evA, evB, 0, m, s, h->gv, wantAvg,
-                              h->writeFaces ? 1 : 0, tileList, nTiles, h->xcdMap, h->deferN, h->deferIter, h->deferLocal, h->deferHist);
-    }
-    h->deferN = 0;
-    h->deferLocal = h->deferHist = nullptr;
-}
-template <int T>
-static void launchGeomTile(smgpu_handle* h, const MeshView& m, const State& s, int wantAvg, const int* tileList, int nTiles, hipEvent_t evA, hipEvent_t evB,
-                           bool withBndPre) {
-    if (h->foamOrg) launchGeomTileAs<T, true>(h, m, s, wantAvg, tileList, nTiles, evA, evB, withBndPre);
-    else launchGeomTileAs<T, false>(h, m, s, wantAvg, tileList, nTiles, evA, evB, withBndPre);
+// h->geomT and h->foamOrg as compile-time values: f(std::integral_constant<int, T>, std::bool_constant<ORG>), once
+template <class F>
+static void withGeomTile(const smgpu_handle* h, F&& f) {
+    auto variant = [&](auto t) {
+        if (h->foamOrg) f(t, std::true_type{});
+        else f(t, std::false_type{});
+    };
+    if (h->geomT == 64) variant(std::integral_constant<int, 64>{});
+    else if (h->geomT == 128) variant(std::integral_constant<int, 128>{});
+    else variant(std::integral_constant<int, 256>{});
 }
 template <bool FINAL, int T>
 static void launchSmoothTile(smgpu_handle* h, const MeshView& m, const State& s, const Prm& prm, const int* tileList, int nTiles, hipEvent_t evA, hipEvent_t evB) {
@@ -1449,9 +1374,24 @@ static int runGeometry(smgpu_handle* h, const int* tileList = nullptr, int nList
         const bool bnd = withBndPre && h->bndOn && h->bndInGeom && !fromNext && h->bv.nB > 0 && !h->bndPreInFlight && !h->bndPreDone;
         if (bnd) h->bndPreDone = true;
         return launchKDispatch(h, K_GEOM_TILE, [&](hipEvent_t evA, hipEvent_t evB) {
-            if (h->geomT == 64) launchGeomTile<64>(h, m, s, wantAvg, tileList, nT, evA, evB, bnd);
-            else if (h->geomT == 128) launchGeomTile<128>(h, m, s, wantAvg, tileList, nT, evA, evB, bnd);
-            else launchGeomTile<256>(h, m, s, wantAvg, tileList, nT, evA, evB, bnd);
+            withGeomTile(h, [&](auto tile, auto org) {
+                constexpr int T = decltype(tile)::value;
+                constexpr bool ORG = decltype(org)::value;
+                if (bnd) {   // the boundary pre-kernels in the first workgroups of this launch (k_geom_tile_bnd)
+                    const int nNormal = (h->bv.nB + T - 1) / T, nFeat = (h->bv.nFeat + (T / 64) - 1) / (T / 64);
+                    const int nBnd = ((nNormal + nFeat + 7) / 8) * 8;
+                    ensureDynLds(k_geom_tile_bnd<T, ORG>, h->device, h->geomLds);
+                    hipExtLaunchKernelGGL((k_geom_tile_bnd<T, ORG>), dim3(nBnd + tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, evA, evB, 0, m, s,
+                                          h->gv, wantAvg, h->writeFaces ? 1 : 0, tileList, nT, h->xcdMap, h->deferN, h->deferIter, h->deferLocal, h->deferHist, h->bv,
+                                          nBnd, nNormal);
+                } else {
+                    ensureDynLds(k_geom_tile<T, ORG>, h->device, h->geomLds);
+                    hipExtLaunchKernelGGL((k_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, evA, evB, 0, m, s, h->gv,
+                                          wantAvg, h->writeFaces ? 1 : 0, tileList, nT, h->xcdMap, h->deferN, h->deferIter, h->deferLocal, h->deferHist);
+                }
+            });
+            h->deferN = 0;
+            h->deferLocal = h->deferHist = nullptr;
         });
     }
     if (launchK(h, K_FACE_GEOM, [&] { hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, s, wantAvg, h->foamOrg ? 1 : 0); })) return 1;
@@ -1961,28 +1901,22 @@ static int flushDeferred(smgpu_handle* h) {
     return 0;
 }
 
-// the quality history (smgpu_set_quality_trace; defined with the mesh quality report below)
-static int qualityTraceBegin(smgpu_handle* h, int nIters);
-static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, smgpu_quality_trace_record* out = nullptr);
-// the guard on it (smgpu_set_quality_guard; defined there as well)
-static int qualityGuardQueue(smgpu_handle* h, const smgpu_quality_trace_record* rec, int64_t number, const smgpu_iter_stats* gate);
-static int qualityGuardAfterTrip(smgpu_handle* h);
-// the tangle constraint (smgpu_set_tangle_constraint; defined there as well)
-static int tangleBegin(smgpu_handle* h, int nIters);
-static int tangleQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x);
-
+// mesh quality: the reports, then the features that follow the loop (the guard's refinement steps through iterateBody)
 static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_stats* stats, int32_t* nDone);
+#include "quality_reports.hpp"
+#include "quality_loop.hpp"
+
 int smgpu_iterate(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_stats* stats, int32_t* nDone) {
     if (iterateBody(h, nIters, relTol, stats, nDone)) return 1;
     // a call that tripped the quality guard: its statistics and trace records stand; the points go back to the last good state
-    if (h->qgTripPending && qualityGuardAfterTrip(h)) return 1;
+    if (h->qg.tripPending && qualityGuardAfterTrip(h)) return 1;
     return 0;
 }
 static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_iter_stats* stats, int32_t* nDone) {
     if (!h) return fail("null handle");
     if (!h->prmSet) return fail("smgpu_set_params has not been called");
     if (h->haloOn) return fail("smgpu_iterate is the single-rank loop; use smgpu_iter_begin/mid/end with a halo");
-    h->qEpoch++;
+    h->q.epoch++;
     if (nIters < 0) return fail("nIters < 0");
     if (nDone) *nDone = 0;
     if (nIters == 0) return 0;
@@ -2020,15 +1954,17 @@ static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_ite
     // iteration's geometry launch instead of a launch of its own; the last iteration is closed by k_finish
     // (not under the quality guard: its verdict on iteration i may stop the loop, and stats[i] has to be written before it; nor
     // under the tangle constraint: its launches of iteration i are gated on the written bit of stats[i])
-    const bool guarded = h->qgArmed;
-    const bool tangled = h->tgOn;
+    const bool guarded = h->qg.armed;
+    const bool tangled = h->tg.on;
     const bool deferFinish = relTol <= 0.0 && !guarded && !tangled && h->useTiles && h->geomT >= 64 && envInt("SMGPU_DEFER_FINISH", 1);
     if (flushDeferred(h)) return 1;
     // quality history: the iterations of this call whose running number is due get a slot of the call's record slab, in order
-    const bool traced = h->qtInterval > 0;
-    std::vector<int> qtSlotIter;
+    const bool traced = h->qt.interval > 0;
+    int qtSlots = 0;
     if (traced && qualityTraceBegin(h, nIters)) return 1;
-    if (tangled && tangleBegin(h, nIters)) return 1;
+    if (tangled && h->tg.slab.begin(h->stream, nIters)) return 1;
+    // iteration i of this call is number qtNumber + i + 1 of the trace and tgNumber + i + 1 of the tangle constraint
+    const int64_t qtNumber = h->iterCount - h->qt.since, tgNumber = h->iterCount - h->tg.since;
     for (int i = 0; i < nIters; ++i) {
         if (runBndPre(h)) return 1;
         if (runGeometry(h, nullptr, 0, false, true)) return 1;
@@ -2047,13 +1983,14 @@ static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_ite
         ++launched;
         // the tangle constraint: `other` now names x, the points the iteration started from; nothing queued writes them before
         // the next iteration's proposal (fused: ptsNext; k_apply: ptsNext; k_apply_swap: prop), which is queued behind the passes
-        if (tangled && tangleQueue(h, i, h->tgIter + i + 1, h->dStats + i, other)) return 1;
+        if (tangled && tangleQueue(h, i, tgNumber + i + 1, h->dStats + i, other)) return 1;
         // (with relTol > 0 this iteration may turn out not to have run: k_finish has written stats[i] by then, or has not)
-        if (traced && (h->qtIter + i + 1) % h->qtInterval == 0) {
+        if (traced && (qtNumber + i + 1) % h->qt.interval == 0) {
             const smgpu_iter_stats* gate = (relTol > 0.0 || guarded || tangled) ? h->dStats + i : nullptr;
-            if (qualityTraceQueue(h, (int)qtSlotIter.size(), h->qtIter + i + 1, gate)) return 1;
-            if (guarded && qualityGuardQueue(h, h->qtSlab + qtSlotIter.size(), h->qtIter + i + 1, gate)) return 1;
-            qtSlotIter.push_back(i);
+            smgpu_quality_trace_record* rec = nullptr;
+            if (h->qt.slab.slot(qtSlots++, &rec)) return 1;
+            if (qualityTraceQueue(h, qtNumber + i + 1, gate, rec)) return 1;
+            if (guarded && qualityGuardQueue(h, rec, qtNumber + i + 1, gate)) return 1;
         }
         // a positive relTol can stop the loop: poll the device flag now and then so a converged run
         // does not queue thousands of no-op launches (relTol <= 0 can never stop: residual >= 0); so can the quality guard
@@ -2066,39 +2003,32 @@ static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_ite
     }
     std::vector<smgpu_iter_stats> hs((size_t)launched);
     HIP_OK(hipMemcpyAsync(hs.data(), h->dStats, sizeof(smgpu_iter_stats) * (size_t)launched, hipMemcpyDeviceToHost, h->stream));
-    std::vector<smgpu_quality_trace_record> qtRecs(qtSlotIter.size());
-    if (!qtRecs.empty()) HIP_OK(hipMemcpyAsync(qtRecs.data(), h->qtSlab, sizeof(smgpu_quality_trace_record) * qtRecs.size(), hipMemcpyDeviceToHost, h->stream));
+    if (traced && h->qt.slab.readBack(h->stream, qtSlots)) return 1;
     GuardDev gd{};
-    if (guarded) HIP_OK(hipMemcpyAsync(&gd, h->qgDev, sizeof(GuardDev), hipMemcpyDeviceToHost, h->stream));
-    std::vector<smgpu_tangle_record> tgRecs(tangled ? (size_t)launched : 0);
+    if (guarded) HIP_OK(hipMemcpyAsync(&gd, h->qg.dev, sizeof(GuardDev), hipMemcpyDeviceToHost, h->stream));
     TangleDev td{};
     if (tangled) {
-        HIP_OK(hipMemcpyAsync(tgRecs.data(), h->tgSlab, sizeof(smgpu_tangle_record) * tgRecs.size(), hipMemcpyDeviceToHost, h->stream));
-        HIP_OK(hipMemcpyAsync(&td, h->tgDev, sizeof(TangleDev), hipMemcpyDeviceToHost, h->stream));
+        if (h->tg.slab.readBack(h->stream, launched)) return 1;
+        HIP_OK(hipMemcpyAsync(&td, h->tg.dev, sizeof(TangleDev), hipMemcpyDeviceToHost, h->stream));
     }
     if (checkDeviceError(h)) return 1;
     if (td.err) return fail("smgpu_iterate: tangle constraint: the marks of a geometry tile do not fit the LDS of its points");
     int done = 0;
     while (done < launched && (hs[done].nNearTies & kStatsWritten)) ++done;
-    if (tangled && !h->qgRefining) {   // (the guard's refining steps replay iterations of the call: no records, no numbers)
-        for (int i = 0; i < done; ++i)
-            if (tgRecs[i].iteration != 0) h->tgPending.push_back(tgRecs[i]);
-        h->tgIter += done;
-    }
-    if (traced) {
-        for (size_t r = 0; r < qtRecs.size() && !h->qgRefining; ++r)
-            if (qtSlotIter[r] < done && qtRecs[r].iteration != 0) h->qtPending.push_back(qtRecs[r]);
-        h->qtIter += done;
+    if (!h->qg.refining) {   // (the guard's refining steps replay iterations of the call: no records, no numbers)
+        if (tangled) h->tg.slab.keep(done);
+        if (traced) h->qt.slab.keep(qualityTraceDue(h, done));   // the slots of the iterations that ran
+        h->iterCount += done;
     }
     if (guarded) {
-        h->qgLastVerdict = gd.verdict;
-        h->qgState.snapshotIteration = gd.snapshotIteration;
-        if (gd.tripped && !h->qgRefining) {
-            h->qgState.tripped = 1;
-            h->qgState.reasons = gd.reasons;
-            h->qgState.trippedIteration = gd.trippedIteration;
-            h->qgState.tripRecord = gd.tripRecord;
-            h->qgTripPending = true;
+        h->qg.lastVerdict = gd.verdict;
+        h->qg.state.snapshotIteration = gd.snapshotIteration;
+        if (gd.tripped && !h->qg.refining) {
+            h->qg.state.tripped = 1;
+            h->qg.state.reasons = gd.reasons;
+            h->qg.state.trippedIteration = gd.trippedIteration;
+            h->qg.state.tripRecord = gd.tripRecord;
+            h->qg.tripPending = true;
         }
     }
     for (int i = 0; i < done; ++i) hs[i].nNearTies &= kStatsWritten - 1;
@@ -2178,7 +2108,7 @@ int smgpu_check_error(smgpu_handle* h) {
 
 int smgpu_set_points(smgpu_handle* h, const double* pts) {
     if (!h || !pts) return fail("null argument");
-    h->qEpoch++;
+    h->q.epoch++;
     HIP_OK(hipSetDevice(h->device));
     h->geomAheadDone = false;
     HIP_OK(hipMemcpyAsync(h->st.ptsCur, pts, sizeof(double) * 3 * (size_t)h->mv.nPoints, hipMemcpyHostToDevice, h->stream));
@@ -2269,9 +2199,9 @@ int smgpu_halo_set_exchange_stream(smgpu_handle* h, int32_t useExchangeStream, v
 
 int smgpu_halo_configure(smgpu_handle* h, const smgpu_halo_desc* d) {
     if (!h || !d) return fail("null argument");
-    if (h->tgOn) return fail("smgpu_halo_configure: the tangle constraint is on (smgpu_set_tangle_constraint), and it is not available on an engine with a halo; switch it off first");
-    if (h->qgArmed) return fail("smgpu_halo_configure: the quality guard is armed (smgpu_set_quality_guard), and a guard is not available on an engine with a halo; disarm it first");
-    if (h->qtInterval > 0) return fail("smgpu_halo_configure: the quality trace is on (smgpu_set_quality_trace), and a trace is not available on an engine with a halo; switch it off first");
+    if (h->tg.on) return fail("smgpu_halo_configure: the tangle constraint is on (smgpu_set_tangle_constraint), and it is not available on an engine with a halo; switch it off first");
+    if (h->qg.armed) return fail("smgpu_halo_configure: the quality guard is armed (smgpu_set_quality_guard), and a guard is not available on an engine with a halo; disarm it first");
+    if (h->qt.interval > 0) return fail("smgpu_halo_configure: the quality trace is on (smgpu_set_quality_trace), and a trace is not available on an engine with a halo; switch it off first");
     HIP_OK(hipSetDevice(h->device));
     // the host's buffers may still be being initialised on the host's streams
     HIP_OK(hipDeviceSynchronize());
@@ -2738,7 +2668,7 @@ static int runMergedSmooth(smgpu_handle* h) {
 int smgpu_iter_begin(smgpu_handle* h) {
     if (!h || !h->haloOn) return fail("halo not configured");
     if (!h->prmSet) return fail("smgpu_set_params has not been called");
-    h->qEpoch++;
+    h->q.epoch++;
     h->iterOpen = true;
     HIP_OK(hipSetDevice(h->device));
     if (h->pushOn && h->pushStride != (h->st.lStride > 0 ? h->st.lStride : SMGPU_HALO_L_LAYERS)) {   // the L records grew (boundary set-up)
@@ -3041,7 +2971,7 @@ int smgpu_layers_shared(smgpu_handle* h, int32_t field, int32_t set, double* v) 
 int smgpu_set_layers(smgpu_handle* h, const smgpu_layer_desc* d, int32_t* enabled) {
     if (!h || !d) return fail("null argument");
     if (h->haloOn) return fail("smgpu_set_layers is the serial set-up; with a halo use smgpu_layers_begin / step / shared");
-    if (h->qgArmed) return fail("smgpu_set_layers: the quality guard is armed (smgpu_set_quality_guard), and its snapshot was sized without the layer normals; disarm it, set the layers, arm it again");
+    if (h->qg.armed) return fail("smgpu_set_layers: the quality guard is armed (smgpu_set_quality_guard), and its snapshot was sized without the layer normals; disarm it, set the layers, arm it again");
     int32_t on = 0, maxIter = 0;
     if (smgpu_layers_begin(h, d, &on, &maxIter)) return 1;
     if (enabled) *enabled = on;
@@ -3335,8 +3265,8 @@ int smgpu_boundary_shared(smgpu_handle* h, int32_t field, int32_t set, double* v
 int smgpu_set_boundary_smoothing(smgpu_handle* h, const smgpu_boundary_desc* d, smgpu_boundary_info* info) {
     if (!h || !d) return fail("null argument");
     if (h->haloOn) return fail("smgpu_set_boundary_smoothing is the serial set-up; with a halo use smgpu_boundary_stats / begin / step / shared");
-    if (h->tgOn) return fail("smgpu_set_boundary_smoothing: the tangle constraint is on (smgpu_set_tangle_constraint), and it is not available on an engine with boundary point smoothing; switch it off first");
-    if (h->qgArmed) return fail("smgpu_set_boundary_smoothing: the quality guard is armed (smgpu_set_quality_guard), and its snapshot does not hold the state boundary point smoothing carries from one iteration to the next; disarm it first");
+    if (h->tg.on) return fail("smgpu_set_boundary_smoothing: the tangle constraint is on (smgpu_set_tangle_constraint), and it is not available on an engine with boundary point smoothing; switch it off first");
+    if (h->qg.armed) return fail("smgpu_set_boundary_smoothing: the quality guard is armed (smgpu_set_quality_guard), and its snapshot does not hold the state boundary point smoothing carries from one iteration to the next; disarm it first");
     double minEdge = 0.0, bb[6];
     if (smgpu_boundary_stats(h, &minEdge, bb)) return 1;
     smgpu_boundary_info bi{};
@@ -3389,1008 +3319,6 @@ int smgpu_debug_find_line(smgpu_handle* h, int32_t n, const double* segments, do
     (void)hipFree(dSeg); (void)hipFree(dOut); (void)hipFree(dHit);
     if (e != hipSuccess) return fail(std::string("smgpu_debug_find_line: ") + hipGetErrorString(e));
     return 0;
-}
-
-// ---- mesh quality report (kernels_quality.hpp, DESIGN.md "Mesh quality") ---------------------------------------------------
-// the report's device memory, on the first call: owner / neighbour by face (derived on the device from the cell -> face rows),
-// the two partial slabs and the report
-static int qualityEnsure(smgpu_handle* h) {
-    if (h->qOut) return 0;
-    const MeshView& m = h->mv;
-    const size_t nFB = (size_t)std::max(1, qualityGrid(m.nFaces)), nCB = (size_t)std::max(1, qualityGrid(m.nCells));
-    hipError_t e = hipMalloc((void**)&h->qOwn, sizeof(int) * (size_t)std::max(1, m.nFaces));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qNei, sizeof(int) * (size_t)std::max(1, m.nInternalFaces));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qFacePart, sizeof(QFace) * nFB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qCellPart, sizeof(QCell) * nCB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qOut, sizeof(smgpu_quality));
-    if (e != hipSuccess) {
-        for (void** p : {(void**)&h->qOwn, (void**)&h->qNei, (void**)&h->qFacePart, (void**)&h->qCellPart, (void**)&h->qOut})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        return fail(std::string("mesh quality: device memory for the report: ") + hipGetErrorString(e));
-    }
-    HIP_OK(hipMemsetAsync(h->qOwn, 0, sizeof(int) * (size_t)std::max(1, m.nFaces), h->stream));   // (every face has an owner row; no
-    HIP_OK(hipMemsetAsync(h->qNei, 0, sizeof(int) * (size_t)std::max(1, m.nInternalFaces), h->stream));   //  id is left undefined)
-    if (m.nCells > 0) hipLaunchKernelGGL(k_quality_owners, dim3(gridFor(m.nCells)), dim3(kQualityBlock), 0, h->stream, m, h->qOwn, h->qNei);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-static const char* kQualityHaloRefusal = "mesh quality: not available on an engine with a halo (a sub-domain's processor faces are internal faces of "
-                                         "the global mesh, whose neighbour cell centres this report does not exchange); report on the undecomposed mesh, or use "
-                                         "smgpu_quality_coupled_pack / _report";
-// the loop's geometry launch with writeFaces, outside the engine's launch counters and timing events
-static int qualityGeometry(smgpu_handle* h) {
-    const bool timing = h->timing;
-    int64_t launches[K_COUNT];
-    std::memcpy(launches, h->launches, sizeof(launches));
-    h->timing = false;
-    h->writeFaces = true;
-    // a loop that relTol stopped leaves its stop word set until the next smgpu_iterate clears it, and the geometry kernels return at
-    // once on that word: the report would be one of the face values and cell centres of the last iteration's start
-    HIP_OK(hipMemsetAsync(&h->st.acc->stop, 0, sizeof(int), h->stream));
-    const int rcg = runGeometry(h);
-    h->writeFaces = false;
-    h->timing = timing;
-    std::memcpy(h->launches, launches, sizeof(launches));
-    return rcg;
-}
-static QualityThresholds qualityThresholds(const smgpu_quality_params* p) {
-    const smgpu_quality_params prm = p ? *p : smgpu_quality_params{70.0, 4.0, 1e-6, 1000.0};
-    return QualityThresholds{std::cos(prm.nonOrthThreshold * (SMGPU_PI / 180.0)), prm.skewThreshold, prm.closedThreshold, prm.aspectThreshold};
-}
-static QualityGeomThresholds geomThresholds(const smgpu_quality_geometry_params* p) {
-    const smgpu_quality_geometry_params prm = p ? *p : smgpu_quality_geometry_params{10.0, 0.8, 0.05, 0.01, 0.001};
-    return QualityGeomThresholds{std::sin(prm.concaveThreshold * (SMGPU_PI / 180.0)), prm.flatnessThreshold, prm.weightThreshold,
-                                 prm.volRatioThreshold, prm.determinantThreshold};
-}
-static QualityMotionThresholds motionThresholds(const smgpu_quality_motion_params* p) {
-    const smgpu_quality_motion_params prm = p ? *p : smgpu_quality_motion_params{1e-15, 0.02, -1.0};
-    // k = 8 / (9 sqrt 3) is the host's double, as the contract says: the kernel takes it as an argument
-    return QualityMotionThresholds{prm.tetThreshold, prm.twistThreshold, prm.triangleTwistThreshold, 8.0 / (9.0 * std::sqrt(3.0))};
-}
-// a coupled call's refusals: the geometry and the coupling are those of the last pack (DESIGN.md "Mesh quality", 10.4); `buf` is the
-// device buffer the call may not go without (`what`) when there are processor faces
-static int qualityCoupledReady(smgpu_handle* h, const char* api, const void* buf, const char* what = "recvCc") {
-    if (h->iterOpen) return fail(std::string(api) + ": not between smgpu_iter_begin and smgpu_iter_end");
-    if (!h->qPartOut || h->qPackEpoch != h->qEpoch)
-        return fail(std::string(api) + ": call smgpu_quality_coupled_pack first (the points may have moved since the last pack)");
-    if (h->qNProc > 0 && !buf) return fail(std::string(api) + ": null " + what);
-    return 0;
-}
-// ... and of a coupled geometry call: the volumes are those of a pack_volumes on the same pack
-static int qualityCoupledGeomReady(smgpu_handle* h, const char* api, const void* recvCc, const void* recvVc) {
-    if (qualityCoupledReady(h, api, recvCc)) return 1;
-    if (!h->qgPartOut || h->qVolEpoch != h->qEpoch || h->qVolCoupling != h->qCoupling)
-        return fail(std::string(api) + ": call smgpu_quality_coupled_pack_volumes after smgpu_quality_coupled_pack first");
-    if (h->qNProc > 0 && !recvVc) return fail(std::string(api) + ": null recvVc");
-    return 0;
-}
-static QCoupling<true> qualityCoupling(const smgpu_handle* h, const void* recvCc, const void* recvVc) {
-    return QCoupling<true>{h->qSlot, (const double*)recvCc, (const double*)recvVc};
-}
-static double* const kQualityNoFields[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-
-static int qualityGeomEnsure(smgpu_handle* h) {
-    if (qualityEnsure(h)) return 1;
-    if (h->qgOut) return 0;
-    const MeshView& m = h->mv;
-    const size_t nFB = (size_t)std::max(1, qualityGrid(m.nFaces)), nCB = (size_t)std::max(1, qualityGrid(m.nCells));
-    hipError_t e = hipMalloc((void**)&h->qgVol, sizeof(double) * (size_t)std::max(1, m.nCells));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qgFacePart, sizeof(QGFace) * nFB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qgCellPart, sizeof(QGCell) * nCB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qgOut, sizeof(smgpu_quality_geometry));
-    if (e != hipSuccess) {
-        for (void** p : {(void**)&h->qgVol, (void**)&h->qgFacePart, (void**)&h->qgCellPart, (void**)&h->qgOut})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        return fail(std::string("mesh quality: device memory for the geometry report: ") + hipGetErrorString(e));
-    }
-    return 0;
-}
-static int qualityMotionEnsure(smgpu_handle* h) {
-    if (qualityEnsure(h)) return 1;
-    if (h->qmOut) return 0;
-    const size_t nFB = (size_t)std::max(1, qualityGrid(h->mv.nFaces));
-    hipError_t e = hipMalloc((void**)&h->qmFacePart, sizeof(QMFace) * nFB);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qmOut, sizeof(smgpu_quality_motion));
-    if (e != hipSuccess) {
-        for (void** p : {(void**)&h->qmFacePart, (void**)&h->qmOut})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        return fail(std::string("mesh quality: device memory for the motion criteria: ") + hipGetErrorString(e));
-    }
-    return 0;
-}
-
-// Every report is one function for the serial mesh (Coupled = false: cp is empty, api unused) and for a sub-domain (Coupled = true,
-// on the geometry of the last pack): the same launches of the same kernels, with or without the coupling.  o: the optional
-// per-element outputs, in the order of the report's field table below.
-extern "C++" {
-// the record a report's final reduction left on the device, to the host
-template <class T>
-static int qualityCopyOut(smgpu_handle* h, T* out, const T* dev) {
-    HIP_OK(hipMemcpyAsync(out, dev, sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// serial: geometry of the current points (the loop's own kernel, publishing face values by id as for smgpu_debug_propose; not counted
-// in the engine's statistics), then the face pass, the cell pass and the final reduction into h->qOut; coupled: into h->qPartOut
-template <bool Coupled>
-static int runQuality(smgpu_handle* h, const char* api, const smgpu_quality_params* p, const QCoupling<Coupled>& cp, double* const* o) {
-    if constexpr (Coupled) {
-        if (qualityCoupledReady(h, api, cp.recvCc)) return 1;
-        HIP_OK(hipSetDevice(h->device));
-    } else {
-        if (h->haloOn) return fail(kQualityHaloRefusal);
-        HIP_OK(hipSetDevice(h->device));
-        if (qualityEnsure(h)) return 1;
-        if (qualityGeometry(h)) return 1;
-    }
-    const MeshView& m = h->mv;
-    const QualityThresholds thr = qualityThresholds(p);
-    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-    const State& s = h->st;
-    if (nFB > 0)
-        hipLaunchKernelGGL(k_quality_faces<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qOwn,
-                           h->qNei, cp, thr, h->qFacePart, o[0], o[1]);
-    if (nCB > 0)
-        hipLaunchKernelGGL(k_quality_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qCellPart, o[2], o[3], o[4]);
-    if constexpr (Coupled)
-        hipLaunchKernelGGL(k_quality_final<smgpu_quality_part>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qFacePart, nFB, h->qCellPart, nCB,
-                           m.nCells, m.nFaces - h->qNotCounted, m.nInternalFaces + h->qCountedProc, h->qPartOut);
-    else
-        hipLaunchKernelGGL(k_quality_final<smgpu_quality>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qFacePart, nFB, h->qCellPart, nCB,
-                           m.nCells, m.nFaces, m.nInternalFaces, h->qOut);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// ---- the quality history (kernels_quality_trace.hpp, DESIGN.md "Mesh quality", 10.10) ----
-template <int T, bool ORG>
-static void launchQualityGeomTileAs(smgpu_handle* h, const State& ts, bool fused, int nT, const smgpu_iter_stats* gate) {
-    if (fused) {
-        ensureDynLds(k_quality_geom_tile<T, ORG>, h->device, h->geomLds);
-        hipLaunchKernelGGL((k_quality_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, nT, h->xcdMap,
-                           h->qtThr, h->qtCellPart, gate);
-    } else {   // the report's geometry launch: writeFaces, no face averages, and the engine's deferred finish is not this launch's to close
-        ensureDynLds(k_geom_tile<T, ORG>, h->device, h->geomLds);
-        hipLaunchKernelGGL((k_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, 0, 1,
-                           (const int*)nullptr, nT, h->xcdMap, 0, 0, (double*)nullptr, (double*)nullptr);
-    }
-}
-template <int T>
-static void launchQualityGeomTile(smgpu_handle* h, const State& ts, bool fused, int nT, const smgpu_iter_stats* gate) {
-    if (h->foamOrg) launchQualityGeomTileAs<T, true>(h, ts, fused, nT, gate);
-    else launchQualityGeomTileAs<T, false>(h, ts, fused, nT, gate);
-}
-
-// the -allGeometry checks (DESIGN.md "Mesh quality", 10.6 and 10.8).  serial: geometry, the cell pass (volumes into h->qgVol), the face
-// pass, the final reduction into h->qgOut; coupled: the volumes are those of the last pack_volumes, the record goes to h->qgPartOut
-template <bool Coupled>
-static int runQualityGeom(smgpu_handle* h, const char* api, const smgpu_quality_geometry_params* p, const QCoupling<Coupled>& cp, double* const* o) {
-    if constexpr (Coupled) {
-        if (qualityCoupledGeomReady(h, api, cp.recvCc, cp.recvVc)) return 1;
-        HIP_OK(hipSetDevice(h->device));
-    } else {
-        if (h->haloOn) return fail(kQualityHaloRefusal);
-        HIP_OK(hipSetDevice(h->device));
-        if (qualityGeomEnsure(h)) return 1;
-        if (qualityGeometry(h)) return 1;
-    }
-    const MeshView& m = h->mv;
-    const QualityGeomThresholds thr = geomThresholds(p);
-    const int nFB = qualityGrid(m.nFaces), nCB = qualityGrid(m.nCells);
-    const State& s = h->st;
-    if (nCB > 0) {
-        if constexpr (Coupled)
-            hipLaunchKernelGGL(k_quality_geom_cells_coupled, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fArea, cp.slot, thr, h->qgCellPart, o[4]);
-        else
-            hipLaunchKernelGGL(k_quality_geom_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, h->qgCellPart, h->qgVol, o[4]);
-    }
-    if (nFB > 0) {
-        if constexpr (Coupled)
-            hipLaunchKernelGGL(k_quality_geom_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr,
-                               h->qgVol, h->qOwn, h->qNei, cp.slot, cp.recvCc, cp.recvVc, thr, h->qgFacePart, o[0], o[1], o[2], o[3]);
-        else
-            hipLaunchKernelGGL(k_quality_geom_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr, h->qgVol,
-                               h->qOwn, h->qNei, thr, h->qgFacePart, o[0], o[1], o[2], o[3]);
-    }
-    if constexpr (Coupled)
-        hipLaunchKernelGGL(k_quality_geom_final<smgpu_quality_geometry_part>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qgFacePart, nFB,
-                           h->qgCellPart, nCB, m.nCells, m.nFaces - h->qNotCounted, m.nInternalFaces + h->qCountedProc, h->qgPartOut);
-    else
-        hipLaunchKernelGGL(k_quality_geom_final<smgpu_quality_geometry>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qgFacePart, nFB,
-                           h->qgCellPart, nCB, m.nCells, m.nFaces, m.nInternalFaces, h->qgOut);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// the motion criteria (DESIGN.md "Mesh quality", 10.7 and 10.8).  serial: geometry, the face pass, the final reduction into h->qmOut;
-// coupled: the record goes to h->qmPartOut
-template <bool Coupled>
-static int runQualityMotion(smgpu_handle* h, const char* api, const smgpu_quality_motion_params* p, const QCoupling<Coupled>& cp, double* const* o) {
-    if constexpr (Coupled) {
-        if (qualityCoupledReady(h, api, cp.recvCc)) return 1;
-        HIP_OK(hipSetDevice(h->device));
-        if (qualityMotionEnsure(h)) return 1;
-        if (!h->qmPartOut) HIP_OK(hipMalloc((void**)&h->qmPartOut, sizeof(smgpu_quality_motion_part)));
-    } else {
-        if (h->haloOn) return fail(kQualityHaloRefusal);
-        HIP_OK(hipSetDevice(h->device));
-        if (qualityMotionEnsure(h)) return 1;
-        if (qualityGeometry(h)) return 1;
-    }
-    const MeshView& m = h->mv;
-    const QualityMotionThresholds thr = motionThresholds(p);
-    const int nFB = qualityGrid(m.nFaces);
-    const State& s = h->st;
-    if (nFB > 0) {
-        if constexpr (Coupled)
-            hipLaunchKernelGGL(k_quality_motion_faces_coupled, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.cellCtr, h->qOwn,
-                               h->qNei, cp.slot, cp.recvCc, thr, h->qmFacePart, o[0], o[1], o[2], o[3]);
-        else
-            hipLaunchKernelGGL(k_quality_motion_faces, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.cellCtr, h->qOwn, h->qNei,
-                               thr, h->qmFacePart, o[0], o[1], o[2], o[3]);
-    }
-    if constexpr (Coupled)
-        hipLaunchKernelGGL(k_quality_motion_final<smgpu_quality_motion_part>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qmFacePart, nFB,
-                           m.nFaces - h->qNotCounted, h->qmPartOut);
-    else
-        hipLaunchKernelGGL(k_quality_motion_final<smgpu_quality_motion>, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qmFacePart, nFB, m.nFaces,
-                           h->qmOut);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// the per-element fields of a report kind: names[0, n), those from firstCell on per cell, and the refusal of any other name
-struct QualityFields { int n, firstCell; const char* names[5]; const char* unknown; const char* known; };
-static const QualityFields kQualityFields{5, 2, {"faceNonOrthogonality", "faceSkewness", "cellVolume", "cellOpenness", "cellAspectRatio"},
-                                          "unknown quality field ", " (cellVolume, cellOpenness, cellAspectRatio, faceNonOrthogonality, faceSkewness)"};
-static const QualityFields kQualityGeomFields{5, 4, {"faceConcavity", "faceFlatness", "faceWeight", "faceVolumeRatio", "cellDeterminant"},
-                                              "unknown quality geometry field ",
-                                              " (faceConcavity, faceFlatness, faceWeight, faceVolumeRatio, cellDeterminant)"};
-static const QualityFields kQualityMotionFields{4, 4, {"faceTetQuality", "faceBaseTetQuality", "faceTwist", "faceTriangleTwist"},
-                                                "unknown quality motion field ", " (faceTetQuality, faceBaseTetQuality, faceTwist, faceTriangleTwist)"};
-// one per-element field: `run(o)` launches the report's passes with the outputs o, the named one set to a buffer allocated for
-// this call (outside deviceBytes)
-template <class Run>
-static int qualityField(smgpu_handle* h, const QualityFields& t, const char* api, const char* name, double* out, int64_t* n, Run run) {
-    int which = -1;
-    for (int i = 0; i < t.n; ++i)
-        if (std::strcmp(name, t.names[i]) == 0) which = i;
-    if (which < 0) return fail(std::string(t.unknown) + name + t.known);
-    const int64_t cnt = which >= t.firstCell ? h->mv.nCells : h->mv.nFaces;
-    *n = cnt;
-    if (!out) return 0;
-    HIP_OK(hipSetDevice(h->device));
-    double* buf = nullptr;   // transient: one field's worth for this call only
-    HIP_OK(hipMalloc((void**)&buf, sizeof(double) * (size_t)std::max<int64_t>(1, cnt)));
-    double* o[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    o[which] = buf;
-    int rc = run(o);
-    if (rc == 0 && cnt > 0) {
-        const hipError_t e = hipMemcpyAsync(out, buf, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) rc = fail(std::string(api) + ": " + hipGetErrorString(e));
-    }
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    if (rc == 0 && es != hipSuccess) rc = fail(std::string(api) + ": " + hipGetErrorString(es));
-    (void)hipFree(buf);
-    return rc;
-}
-}  // extern "C++"
-
-static void qualityTraceFree(smgpu_handle* h) {
-    for (void** p : {(void**)&h->qtCellCtr, (void**)&h->qtAcc, (void**)&h->qtFacePart, (void**)&h->qtCellPart, (void**)&h->qtCellFold, (void**)&h->qtSlab})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    h->qtSlabCap = 0;
-}
-static bool qualityTraceFused(const smgpu_handle* h) { return h->qtFusedWanted && h->useTiles && h->gt.nTiles > 0; }
-// start of a traced smgpu_iterate call: the trace's device memory (on the first one), and a zeroed slab with one record per due
-// iteration of the call (iteration == 0: not written)
-static int qualityTraceBegin(smgpu_handle* h, int nIters) {
-    if (qualityEnsure(h)) return 1;
-    const MeshView& m = h->mv;
-    if (!h->qtAcc) {
-        const size_t nFB = (size_t)std::max(1, qualityGrid(m.nFaces)), nCB = (size_t)std::max(1, qualityGrid(m.nCells));
-        const size_t nT = h->useTiles ? (size_t)std::max(1, h->gt.nTiles) : 1;
-        hipError_t e = hipMalloc((void**)&h->qtCellCtr, sizeof(double) * 3 * (size_t)std::max(1, m.nCells));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->qtFacePart, sizeof(QFace) * nFB);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->qtCellPart, sizeof(QCell) * std::max(nCB, nT));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->qtCellFold, sizeof(QCell) * (size_t)std::max(1, qualityGrid((int)nT)));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->qtAcc, sizeof(Accum));
-        if (e != hipSuccess) {
-            qualityTraceFree(h);
-            return fail(std::string("mesh quality: device memory for the quality trace: ") + hipGetErrorString(e));
-        }
-        HIP_OK(hipMemsetAsync(h->qtAcc, 0, sizeof(Accum), h->stream));
-    }
-    const int64_t first = h->qtIter + 1, last = h->qtIter + nIters;
-    const int nDue = (int)(last / h->qtInterval - (first - 1) / h->qtInterval);
-    if (nDue > h->qtSlabCap) {
-        if (h->qtSlab) {   // outgrown (nothing of the trace is in flight between two smgpu_iterate calls)
-            HIP_OK(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->qtSlab);
-            h->qtSlab = nullptr;
-            h->qtSlabCap = 0;
-        }
-        const hipError_t e = hipMalloc((void**)&h->qtSlab, sizeof(smgpu_quality_trace_record) * (size_t)nDue);
-        if (e != hipSuccess) return fail(std::string("mesh quality: device memory for the quality trace: ") + hipGetErrorString(e));
-        h->qtSlabCap = nDue;
-    }
-    if (nDue > 0) HIP_OK(hipMemsetAsync(h->qtSlab, 0, sizeof(smgpu_quality_trace_record) * (size_t)nDue, h->stream));
-    return 0;
-}
-// the trace of the points ptsCur now names, behind everything queued on the engine's stream; outside the engine's launch counters
-// and timing events, like the report's geometry launch.  The geometry writes the trace's own cell centres and tests the trace's
-// own stop word, wantAvg is 0 and no deferred finish rides in it: the loop finds everything it reads as it left it.
-static int qualityTraceQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, smgpu_quality_trace_record* out) {
-    if (!out && slot >= h->qtSlabCap) return fail("mesh quality: quality trace slab overrun");
-    if (!out) out = h->qtSlab + slot;
-    const MeshView& m = h->mv;
-    State ts = h->st;
-    ts.cellCtr = h->qtCellCtr;
-    ts.acc = h->qtAcc;
-    ts.stats = nullptr;
-    const bool fused = qualityTraceFused(h);
-    const int nFB = qualityGrid(m.nFaces);
-    int nCB = qualityGrid(m.nCells);
-    const QCell* cPart = h->qtCellPart;
-    if (h->useTiles) {
-        const int nT = h->gt.nTiles;
-        if (nT > 0) {
-            if (h->geomT == 64) launchQualityGeomTile<64>(h, ts, fused, nT, gate);
-            else if (h->geomT == 128) launchQualityGeomTile<128>(h, ts, fused, nT, gate);
-            else launchQualityGeomTile<256>(h, ts, fused, nT, gate);
-        }
-    } else {
-        if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
-        if (m.nCells > 0) hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
-    }
-    if (nFB > 0)
-        hipLaunchKernelGGL(k_quality_faces<false>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, ts.ptsCur, ts.fCtr, ts.fArea, ts.cellCtr, h->qOwn, h->qNei,
-                           QCoupling<false>{}, h->qtThr, h->qtFacePart, (double*)nullptr, (double*)nullptr);
-    if (fused) {
-        nCB = qualityGrid(h->gt.nTiles);
-        hipLaunchKernelGGL(k_quality_trace_fold, dim3(nCB), dim3(kQualityBlock), 0, h->stream, h->qtCellPart, h->gt.nTiles, h->qtCellFold, gate);
-        cPart = h->qtCellFold;
-    } else if (nCB > 0) {
-        hipLaunchKernelGGL(k_quality_cells, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, ts.fCtr, ts.fArea, h->qtThr, h->qtCellPart, (double*)nullptr,
-                           (double*)nullptr, (double*)nullptr);
-    }
-    hipLaunchKernelGGL(k_quality_trace_final, dim3(1), dim3(kQualityBlock), 0, h->stream, h->qtFacePart, nFB, cPart, nCB, m.nCells, m.nFaces, m.nInternalFaces,
-                       (long long)number, out, gate);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-static int qualityGuardDisarm(smgpu_handle* h, bool release);
-int smgpu_set_quality_trace(smgpu_handle* h, int32_t interval, const smgpu_quality_params* p) {
-    if (!h) return fail("null handle");
-    if (interval < 0) return fail("smgpu_set_quality_trace: interval < 0");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityGuardDisarm(h, true)) return 1;   // the numbering restarts: the guard's iteration numbers would name other points
-    h->qtInterval = interval;
-    h->qtIter = 0;
-    h->qtPending.clear();
-    h->qtThr = qualityThresholds(p);
-    if (interval == 0) {
-        HIP_OK(hipStreamSynchronize(h->stream));
-        qualityTraceFree(h);
-    }
-    return 0;
-}
-int smgpu_get_quality_trace(smgpu_handle* h, smgpu_quality_trace_record* out, int64_t cap, int64_t* n) {
-    if (!h || !n) return fail("null argument");
-    const int64_t have = (int64_t)h->qtPending.size();
-    if (!out) { *n = have; return 0; }
-    if (cap < have) return fail("smgpu_get_quality_trace: cap " + std::to_string(cap) + " is below the " + std::to_string(have) + " pending records");
-    if (have > 0) std::memcpy(out, h->qtPending.data(), sizeof(smgpu_quality_trace_record) * (size_t)have);
-    h->qtPending.clear();
-    *n = have;
-    return 0;
-}
-
-// ---- the guard on the quality history (kernels_quality_guard.hpp, DESIGN.md "Mesh quality", 10.11) ----
-static void qualityGuardFree(smgpu_handle* h) {
-    for (void** p : {(void**)&h->qgDev, (void**)&h->qgRec, (void**)&h->qgPts, (void**)&h->qgNormal})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-}
-static int qualityGuardDisarm(smgpu_handle* h, bool release) {
-    h->qgArmed = false;
-    h->qgTripPending = false;
-    h->qgState.armed = 0;
-    if (release && h->qgDev) {
-        HIP_OK(hipStreamSynchronize(h->stream));
-        qualityGuardFree(h);
-    }
-    return 0;
-}
-// the per-point state an iteration carries to the next (State's non-const pointers that an iteration reads before it writes them:
-// ptsCur, and layerNormal with layers) between the engine and the snapshot, on the engine's stream
-static int qualityGuardCopy(smgpu_handle* h, bool restore, int64_t number, bool needGood) {
-    const long long n = 3 * (long long)h->mv.nPoints;
-    const bool normals = h->layersOn && h->qgNormal && h->st.layerNormal;
-    const double *s0 = restore ? h->qgPts : h->st.ptsCur, *s1 = normals ? (restore ? h->qgNormal : h->st.layerNormal) : nullptr;
-    double *d0 = restore ? h->st.ptsCur : h->qgPts, *d1 = normals ? (restore ? h->st.layerNormal : h->qgNormal) : nullptr;
-    const int grid = (int)std::max<long long>(1, ((n >> 1) + (long long)kGuardBlock * kGuardPer - 1) / ((long long)kGuardBlock * kGuardPer));
-    if (normals) hipLaunchKernelGGL(k_quality_guard_snapshot<true>, dim3(grid), dim3(kGuardBlock), 0, h->stream, s0, d0, s1, d1, n, (long long)number, h->qgDev, needGood ? 1 : 0);
-    else hipLaunchKernelGGL(k_quality_guard_snapshot<false>, dim3(grid), dim3(kGuardBlock), 0, h->stream, s0, d0, s1, d1, n, (long long)number, h->qgDev, needGood ? 1 : 0);
-    HIP_OK(hipGetLastError());
-    if (restore) { h->qEpoch++; h->geomAheadDone = false; }
-    return 0;
-}
-// behind k_quality_trace_final of a traced iteration: the verdict on its record, then the snapshot if it passed
-static int qualityGuardQueue(smgpu_handle* h, const smgpu_quality_trace_record* rec, int64_t number, const smgpu_iter_stats* gate) {
-    hipLaunchKernelGGL(k_quality_guard_verdict, dim3(1), dim3(64), 0, h->stream, rec, h->qgDev, (unsigned)h->qgPrm.criteria, &h->st.acc->stop, gate);
-    HIP_OK(hipGetLastError());
-    return qualityGuardCopy(h, false, number, true);
-}
-// After the read-back of a call that tripped: back to the snapshot; with `refine`, on from it one iteration at a time, a trace and
-// a verdict behind each, until one fails or interval - 1 have passed (the loop is deterministic from the snapshot's state, so
-// these are the iterations of the call over again).  The steps go through smgpu_iterate's body with the trace at interval 1;
-// what they would leave behind -- launch counts, timing events, the near-tie census, trace records -- is put back or not kept.
-static int qualityGuardAfterTrip(smgpu_handle* h) {
-    h->qgTripPending = false;
-    const int64_t ranTo = h->qtIter;   // (the tangle constraint's running number goes back with the trace's: see the end)
-    if (qualityGuardCopy(h, true, -1, false)) return 1;
-    int64_t good = h->qgState.snapshotIteration;
-    const int interval = h->qtInterval;
-    int rc = 0;
-    if (h->qgPrm.refine && interval > 1) {
-        const bool timing = h->timing;
-        int64_t launches[K_COUNT];
-        std::memcpy(launches, h->launches, sizeof(launches));
-        unsigned long long nearSaved[3] = {0, 0, 0};
-        if (h->st.nearTotal) HIP_OK(hipMemcpyAsync(nearSaved, h->st.nearTotal, sizeof(nearSaved), hipMemcpyDeviceToHost, h->stream));
-        HIP_OK(hipMemsetAsync(&h->qgDev->tripped, 0, sizeof(int), h->stream));
-        HIP_OK(hipStreamSynchronize(h->stream));
-        h->timing = false;
-        h->qgRefining = true;
-        h->qtInterval = 1;
-        for (int step = 1; step < interval && !rc; ++step) {
-            h->qtIter = good;
-            int32_t done = 0;
-            rc = iterateBody(h, 1, 0.0, nullptr, &done);
-            if (rc) break;
-            if (done != 1 || h->qgLastVerdict != kGuardGood) {   // the first bad step: the snapshot is the state before it
-                rc = qualityGuardCopy(h, true, -1, false);
-                break;
-            }
-            ++good;
-        }
-        h->qtInterval = interval;
-        h->qgRefining = false;
-        h->timing = timing;
-        std::memcpy(h->launches, launches, sizeof(launches));
-        if (!rc && h->st.nearTotal) HIP_OK(hipMemcpyAsync(h->st.nearTotal, nearSaved, sizeof(nearSaved), hipMemcpyHostToDevice, h->stream));
-        HIP_OK(hipStreamSynchronize(h->stream));
-        if (rc) return 1;
-    }
-    h->qgState.snapshotIteration = good;
-    h->qgState.restoredIteration = good;
-    h->qtIter = good;
-    if (h->tgOn) h->tgIter -= ranTo - good;
-    return qualityGuardDisarm(h, false);
-}
-
-int smgpu_set_quality_guard(smgpu_handle* h, const smgpu_quality_guard_params* p, int32_t on) {
-    if (!h) return fail("null handle");
-    HIP_OK(hipSetDevice(h->device));
-    if (!on) return qualityGuardDisarm(h, true);
-    const smgpu_quality_guard_params prm = p ? *p : smgpu_quality_guard_params{SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED, 1};
-    const uint32_t all = SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED | SMGPU_GUARD_ERROR_NONORTH;
-    if (prm.criteria == 0 || (prm.criteria & ~all)) return fail("smgpu_set_quality_guard: criteria must be a non-empty combination of SMGPU_GUARD_NONPOSITIVE_VOLUME, _WRONG_ORIENTED and _ERROR_NONORTH");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    if (h->bndOn)
-        return fail("smgpu_set_quality_guard: not available on an engine with boundary point smoothing (its point normals are a running blend across the "
-                    "iterations and its corner lists are host state, neither of which the guard's snapshot holds)");
-    if (h->qtInterval <= 0) return fail("smgpu_set_quality_guard: the guard judges the records of the quality trace; switch it on first (smgpu_set_quality_trace)");
-    if (h->iterOpen) return fail("smgpu_set_quality_guard: between smgpu_iter_begin and smgpu_iter_end");
-    if (qualityGuardDisarm(h, true)) return 1;
-    if (flushDeferred(h)) return 1;
-    if (qualityTraceBegin(h, 0)) return 1;
-    const size_t n = sizeof(double) * 3 * (size_t)std::max(1, h->mv.nPoints);
-    hipError_t e = hipMalloc((void**)&h->qgDev, sizeof(GuardDev));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qgRec, sizeof(smgpu_quality_trace_record));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->qgPts, n);
-    if (e == hipSuccess && h->layersOn && h->st.layerNormal) e = hipMalloc((void**)&h->qgNormal, n);
-    if (e != hipSuccess) {
-        qualityGuardFree(h);
-        return fail(std::string("mesh quality: device memory for the quality guard: ") + hipGetErrorString(e));
-    }
-    HIP_OK(hipMemsetAsync(h->qgDev, 0, sizeof(GuardDev), h->stream));
-    HIP_OK(hipMemsetAsync(h->qgRec, 0, sizeof(smgpu_quality_trace_record), h->stream));
-    // the baseline: the trace's launches on the current points, number 0
-    if (qualityTraceQueue(h, 0, 0, nullptr, h->qgRec)) { qualityGuardFree(h); return 1; }
-    HIP_OK(hipMemcpyAsync(&h->qgDev->baseline, h->qgRec, sizeof(smgpu_quality_trace_record), hipMemcpyDeviceToDevice, h->stream));
-    h->qgPrm = prm;
-    h->qgState = smgpu_quality_guard_state{};
-    if (qualityGuardCopy(h, false, h->qtIter, false)) { qualityGuardFree(h); return 1; }
-    HIP_OK(hipMemcpyAsync(&h->qgState.baseline, h->qgRec, sizeof(smgpu_quality_trace_record), hipMemcpyDeviceToHost, h->stream));
-    if (checkDeviceError(h)) { qualityGuardFree(h); return 1; }
-    h->qgState.armed = 1;
-    h->qgState.snapshotIteration = h->qtIter;
-    h->qgArmed = true;
-    return 0;
-}
-int smgpu_get_quality_guard(smgpu_handle* h, smgpu_quality_guard_state* out) {
-    if (!h || !out) return fail("null argument");
-    *out = h->qgState;
-    return 0;
-}
-int smgpu_quality_guard_restore(smgpu_handle* h) {
-    if (!h) return fail("null handle");
-    if (!h->qgArmed) return fail("smgpu_quality_guard_restore: the quality guard is not armed (smgpu_set_quality_guard)");
-    HIP_OK(hipSetDevice(h->device));
-    if (flushDeferred(h)) return 1;
-    if (qualityGuardCopy(h, true, -1, false)) return 1;
-    if (checkDeviceError(h)) return 1;
-    h->qgState.restoredIteration = h->qgState.snapshotIteration;
-    if (h->tgOn) h->tgIter -= h->qtIter - h->qgState.snapshotIteration;   // the two numbers name the same points
-    h->qtIter = h->qgState.snapshotIteration;
-    return 0;
-}
-
-// ---- the tangle constraint (kernels_quality_tangle.hpp, DESIGN.md "Mesh quality", 10.12) ----
-static void tangleFree(smgpu_handle* h) {
-    for (void** p : {(void**)&h->tgExempt, (void**)&h->tgMarks, (void**)&h->tgDev, (void**)&h->tgSlab, (void**)&h->tgCellCtr, (void**)&h->tgAcc})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    h->tgSlabCap = 0;
-}
-static int tangleOff(smgpu_handle* h) {
-    h->tgOn = false;
-    h->tgPending.clear();
-    if (h->tgDev) {
-        HIP_OK(hipStreamSynchronize(h->stream));
-        tangleFree(h);
-    }
-    return 0;
-}
-extern "C++" {
-template <int T, bool ORG>
-static void launchTangleTileAs(smgpu_handle* h, const State& ts, int nT, uint8_t* exemptOut, int pass, const smgpu_iter_stats* gate) {
-    ensureDynLds(k_tangle_tile<T, ORG>, h->device, h->geomLds);
-    hipLaunchKernelGGL((k_tangle_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, nT, h->xcdMap,
-                       exemptOut ? (const uint8_t*)nullptr : (const uint8_t*)h->tgExempt, exemptOut, h->tgMarks, h->tgDev, pass, gate);
-}
-template <int T>
-static void launchTangleTile(smgpu_handle* h, const State& ts, int nT, uint8_t* exemptOut, int pass, const smgpu_iter_stats* gate) {
-    if (h->foamOrg) launchTangleTileAs<T, true>(h, ts, nT, exemptOut, pass, gate);
-    else launchTangleTileAs<T, false>(h, ts, nT, exemptOut, pass, gate);
-}
-}  // extern "C++"
-// one evaluation of the points ptsCur names, behind everything queued on the engine's stream; outside the launch counters and
-// the timing events.  Tiles: nothing the loop reads is written.  Without tiles the direct geometry kernels write the loop's face
-// values (the next geometry launch writes them again before anything reads them), cell centres of the constraint's own, and
-// test a stop word of its own.
-static int tangleEvaluate(smgpu_handle* h, uint8_t* exemptOut, int pass, const smgpu_iter_stats* gate) {
-    const MeshView& m = h->mv;
-    State ts = h->st;
-    ts.stats = nullptr;
-    if (h->useTiles) {
-        const int nT = h->gt.nTiles;
-        if (nT > 0) {
-            if (h->geomT == 64) launchTangleTile<64>(h, ts, nT, exemptOut, pass, gate);
-            else if (h->geomT == 128) launchTangleTile<128>(h, ts, nT, exemptOut, pass, gate);
-            else launchTangleTile<256>(h, ts, nT, exemptOut, pass, gate);
-        }
-    } else {
-        ts.cellCtr = h->tgCellCtr;
-        ts.acc = h->tgAcc;
-        if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
-        if (m.nCells > 0) {
-            hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
-            hipLaunchKernelGGL(k_tangle_cells, dim3((m.nCells + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, m, ts.fCtr, ts.fArea,
-                               ts.cellCtr, exemptOut ? (const uint8_t*)nullptr : (const uint8_t*)h->tgExempt, exemptOut, h->tgMarks, h->tgDev, pass, gate);
-        }
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-// start of a smgpu_iterate call with the constraint on: a zeroed slab with one record per iteration (iteration == 0: not written)
-static int tangleBegin(smgpu_handle* h, int nIters) {
-    if (nIters > h->tgSlabCap) {
-        if (h->tgSlab) {   // outgrown (nothing of the constraint is in flight between two smgpu_iterate calls)
-            HIP_OK(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->tgSlab);
-            h->tgSlab = nullptr;
-            h->tgSlabCap = 0;
-        }
-        const hipError_t e = hipMalloc((void**)&h->tgSlab, sizeof(smgpu_tangle_record) * (size_t)nIters);
-        if (e != hipSuccess) return fail(std::string("mesh quality: device memory for the tangle constraint: ") + hipGetErrorString(e));
-        h->tgSlabCap = nIters;
-    }
-    HIP_OK(hipMemsetAsync(h->tgSlab, 0, sizeof(smgpu_tangle_record) * (size_t)nIters, h->stream));
-    return 0;
-}
-// behind the movePoints of an iteration: the passes on the points ptsCur now names; x: the points the iteration started from
-static int tangleQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x) {
-    if (slot >= h->tgSlabCap) return fail("mesh quality: tangle constraint slab overrun");
-    const int nP = h->mv.nPoints;
-    const int gApply = std::max(1, (int)(((int64_t)nP + kTanglePts - 1) / kTanglePts));
-    smgpu_tangle_record* rec = h->tgSlab + slot;
-    for (int k = 0; k <= h->tgPasses; ++k) {
-        if (tangleEvaluate(h, nullptr, k, gate)) return 1;
-        hipLaunchKernelGGL(k_tangle_verdict, dim3(1), dim3(64), 0, h->stream, h->tgDev, rec, (long long)number, k, h->tgPasses, gate);
-        hipLaunchKernelGGL(k_tangle_apply, dim3(gApply), dim3(kTangleBlock), 0, h->stream, x, h->st.ptsCur, h->tgMarks, nP, (const TangleDev*)h->tgDev, rec, gate);
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-int smgpu_set_tangle_constraint(smgpu_handle* h, const smgpu_tangle_params* p, int32_t on) {
-    if (!h) return fail("null handle");
-    HIP_OK(hipSetDevice(h->device));
-    if (!on) return tangleOff(h);
-    const smgpu_tangle_params prm = p ? *p : smgpu_tangle_params{2};
-    if (prm.passes < 0) return fail("smgpu_set_tangle_constraint: passes < 0");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    if (h->bndOn)
-        return fail("smgpu_set_tangle_constraint: not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
-                    "points from state that a reverted iteration would leave ahead of the points)");
-    if (h->iterOpen) return fail("smgpu_set_tangle_constraint: between smgpu_iter_begin and smgpu_iter_end");
-    if (tangleOff(h)) return 1;
-    if (flushDeferred(h)) return 1;
-    const MeshView& m = h->mv;
-    const size_t nMark = ((size_t)std::max(1, m.nPoints) + 3) & ~(size_t)3, nCell = (size_t)std::max(1, m.nCells);
-    hipError_t e = hipMalloc((void**)&h->tgDev, sizeof(TangleDev));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->tgExempt, nCell);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->tgMarks, nMark);
-    if (e == hipSuccess && !h->useTiles) e = hipMalloc((void**)&h->tgCellCtr, sizeof(double) * 3 * nCell);
-    if (e == hipSuccess && !h->useTiles) e = hipMalloc((void**)&h->tgAcc, sizeof(Accum));
-    if (e != hipSuccess) {
-        tangleFree(h);
-        return fail(std::string("mesh quality: device memory for the tangle constraint: ") + hipGetErrorString(e));
-    }
-    HIP_OK(hipMemsetAsync(h->tgDev, 0, sizeof(TangleDev), h->stream));
-    HIP_OK(hipMemsetAsync(h->tgExempt, 0, nCell, h->stream));
-    HIP_OK(hipMemsetAsync(h->tgMarks, 0, nMark, h->stream));
-    if (h->tgAcc) HIP_OK(hipMemsetAsync(h->tgAcc, 0, sizeof(Accum), h->stream));
-    // the exempt cells: one evaluation of the current points
-    h->tgPasses = prm.passes;
-    if (tangleEvaluate(h, h->tgExempt, 0, nullptr)) { tangleFree(h); return 1; }
-    TangleDev td{};
-    HIP_OK(hipMemcpyAsync(&td, h->tgDev, sizeof(TangleDev), hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipMemsetAsync(h->tgDev, 0, sizeof(TangleDev), h->stream));
-    if (checkDeviceError(h)) { tangleFree(h); return 1; }
-    h->tgNExempt = td.badNow;
-    h->tgIter = 0;
-    h->tgOn = true;
-    return 0;
-}
-int smgpu_get_tangle_records(smgpu_handle* h, smgpu_tangle_record* out, int64_t cap, int64_t* n) {
-    if (!h || !n) return fail("null argument");
-    const int64_t have = (int64_t)h->tgPending.size();
-    if (!out) { *n = have; return 0; }
-    if (cap < have) return fail("smgpu_get_tangle_records: cap " + std::to_string(cap) + " is below the " + std::to_string(have) + " pending records");
-    if (have > 0) std::memcpy(out, h->tgPending.data(), sizeof(smgpu_tangle_record) * (size_t)have);
-    h->tgPending.clear();
-    *n = have;
-    return 0;
-}
-int smgpu_get_tangle_state(smgpu_handle* h, smgpu_tangle_state* out) {
-    if (!h || !out) return fail("null argument");
-    *out = smgpu_tangle_state{h->tgOn ? 1 : 0, h->tgPasses, h->tgOn ? h->tgNExempt : 0, h->tgOn ? h->tgIter : 0};
-    return 0;
-}
-
-int smgpu_mesh_quality(smgpu_handle* h, const smgpu_quality_params* p, smgpu_quality* out) {
-    if (!h || !out) return fail("null argument");
-    if (runQuality(h, nullptr, p, QCoupling<false>{}, kQualityNoFields)) return 1;
-    return qualityCopyOut(h, out, h->qOut);
-}
-int smgpu_quality_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
-    if (!h || !name || !n) return fail("null argument");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    return qualityField(h, kQualityFields, "smgpu_quality_field", name, out, n,
-                        [&](double** o) { return runQuality(h, nullptr, nullptr, QCoupling<false>{}, o); });
-}
-
-int smgpu_mesh_quality_geometry(smgpu_handle* h, const smgpu_quality_geometry_params* p, smgpu_quality_geometry* out) {
-    if (!h || !out) return fail("null argument");
-    if (runQualityGeom(h, nullptr, p, QCoupling<false>{}, kQualityNoFields)) return 1;
-    return qualityCopyOut(h, out, h->qgOut);
-}
-int smgpu_quality_geometry_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
-    if (!h || !name || !n) return fail("null argument");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    return qualityField(h, kQualityGeomFields, "smgpu_quality_geometry_field", name, out, n,
-                        [&](double** o) { return runQualityGeom(h, nullptr, nullptr, QCoupling<false>{}, o); });
-}
-
-int smgpu_mesh_quality_motion(smgpu_handle* h, const smgpu_quality_motion_params* p, smgpu_quality_motion* out) {
-    if (!h || !out) return fail("null argument");
-    if (runQualityMotion(h, nullptr, p, QCoupling<false>{}, kQualityNoFields)) return 1;
-    return qualityCopyOut(h, out, h->qmOut);
-}
-int smgpu_quality_motion_field(smgpu_handle* h, const char* name, double* out, int64_t* n) {
-    if (!h || !name || !n) return fail("null argument");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    return qualityField(h, kQualityMotionFields, "smgpu_quality_motion_field", name, out, n,
-                        [&](double** o) { return runQualityMotion(h, nullptr, nullptr, QCoupling<false>{}, o); });
-}
-
-// ---- the coupled reports of a sub-domain (DESIGN.md "Mesh quality", 10.4 and 10.8) -----------------------------------------
-int smgpu_quality_coupled_pack(smgpu_handle* h, const smgpu_quality_coupling* c, void* sendCc, int64_t* nProcFaces) {
-    if (!h || !c) return fail("null argument");
-    if (h->iterOpen) return fail("smgpu_quality_coupled_pack: not between smgpu_iter_begin and smgpu_iter_end");
-    const MeshView& m = h->mv;
-    if (c->nPatches < 0 || (c->nPatches && (!c->patchStart || !c->patchSize || !c->neighbRank)))
-        return fail("smgpu_quality_coupled_pack: bad coupling description");
-    // the patches, checked: inside the boundary faces, disjoint, one per neighbour, none to this rank
-    std::vector<int32_t> key{c->myRank, c->nPatches};
-    std::vector<std::pair<int, int>> ranges;
-    std::vector<int> seen;
-    int64_t nProc = 0, notCounted = 0;
-    for (int i = 0; i < c->nPatches; ++i) {
-        const int32_t st = c->patchStart[i], sz = c->patchSize[i], o = c->neighbRank[i];
-        if (sz < 0 || st < m.nInternalFaces || (int64_t)st + sz > m.nFaces)
-            return fail("smgpu_quality_coupled_pack: processor patch " + std::to_string(i) + " is not a range of boundary faces");
-        if (o < 0 || o == c->myRank) return fail("smgpu_quality_coupled_pack: processor patch " + std::to_string(i) + " has a bad neighbour rank");
-        if (std::find(seen.begin(), seen.end(), o) != seen.end())
-            return fail("smgpu_quality_coupled_pack: two processor patches to rank " + std::to_string(o) +
-                        " (processorCyclic patches or several patches per neighbour are not supported)");
-        seen.push_back(o);
-        ranges.emplace_back(st, sz);
-        nProc += sz;
-        if (c->myRank > o) notCounted += sz;
-        key.insert(key.end(), {st, sz, o});
-    }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); ++i)
-        if (ranges[i - 1].first + ranges[i - 1].second > ranges[i].first) return fail("smgpu_quality_coupled_pack: processor patches overlap");
-    if (nProc > 0 && !sendCc) return fail("smgpu_quality_coupled_pack: null sendCc");
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityEnsure(h)) return 1;
-    if (!h->qPartOut) HIP_OK(hipMalloc((void**)&h->qPartOut, sizeof(smgpu_quality_part)));
-    if (key != h->qCoupling) {
-        // face list and slots of this coupling (small: the boundary faces), uploaded once per coupling
-        const int nB = m.nFaces - m.nInternalFaces;
-        std::vector<int> procFace((size_t)nProc), slot((size_t)nB, -1);
-        int k = 0;
-        for (int i = 0; i < c->nPatches; ++i) {
-            const int flag = c->myRank > c->neighbRank[i] ? kQualityNotCounted : 0;
-            for (int j = 0; j < c->patchSize[i]; ++j, ++k) {
-                const int f = c->patchStart[i] + j;
-                procFace[(size_t)k] = f;
-                slot[(size_t)(f - m.nInternalFaces)] = k | flag;
-            }
-        }
-        for (void** p : {(void**)&h->qProcFace, (void**)&h->qSlot})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        h->qCoupling.clear();
-        HIP_OK(hipMalloc((void**)&h->qProcFace, sizeof(int) * (size_t)std::max<int64_t>(1, nProc)));
-        HIP_OK(hipMalloc((void**)&h->qSlot, sizeof(int) * (size_t)std::max(1, nB)));
-        if (nProc) HIP_OK(hipMemcpyAsync(h->qProcFace, procFace.data(), sizeof(int) * (size_t)nProc, hipMemcpyHostToDevice, h->stream));
-        if (nB) HIP_OK(hipMemcpyAsync(h->qSlot, slot.data(), sizeof(int) * (size_t)nB, hipMemcpyHostToDevice, h->stream));
-        HIP_OK(hipStreamSynchronize(h->stream));   // (the host vectors go out of scope)
-        h->qCoupling = key;
-        h->qNProc = (int)nProc;
-        h->qNotCounted = (int)notCounted;
-        h->qCountedProc = (int)(nProc - notCounted);
-    }
-    if (qualityGeometry(h)) return 1;
-    if (h->qNProc > 0)
-        hipLaunchKernelGGL(k_quality_pack, dim3(gridFor(h->qNProc)), dim3(kQualityBlock), 0, h->stream, h->qOwn, h->st.cellCtr, h->qProcFace, h->qNProc,
-                           (double*)sendCc);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(h->stream));       // sendCc is the host's to move
-    h->qPackEpoch = h->qEpoch;
-    if (nProcFaces) *nProcFaces = h->qNProc;
-    return 0;
-}
-
-int smgpu_quality_coupled_report(smgpu_handle* h, const smgpu_quality_params* p, const void* recvCc, smgpu_quality_part* out) {
-    if (!h || !out) return fail("null argument");
-    if (runQuality(h, "smgpu_quality_coupled_report", p, qualityCoupling(h, recvCc, nullptr), kQualityNoFields)) return 1;
-    return qualityCopyOut(h, out, h->qPartOut);
-}
-int smgpu_quality_coupled_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n) {
-    if (!h || !name || !n) return fail("null argument");
-    const char* api = "smgpu_quality_coupled_field";
-    return qualityField(h, kQualityFields, api, name, out, n,
-                        [&](double** o) { return runQuality(h, api, nullptr, qualityCoupling(h, recvCc, nullptr), o); });
-}
-
-int smgpu_quality_coupled_pack_volumes(smgpu_handle* h, void* sendVc, int64_t* nProcFaces) {
-    if (!h) return fail("null argument");
-    if (qualityCoupledReady(h, "smgpu_quality_coupled_pack_volumes", sendVc, "sendVc")) return 1;
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityGeomEnsure(h)) return 1;
-    if (!h->qgPartOut) HIP_OK(hipMalloc((void**)&h->qgPartOut, sizeof(smgpu_quality_geometry_part)));
-    const MeshView& m = h->mv;
-    const int nCB = qualityGrid(m.nCells);
-    if (nCB > 0)
-        hipLaunchKernelGGL(k_quality_cell_volumes, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, h->st.fCtr, h->st.fArea, h->qgVol);
-    if (h->qNProc > 0)
-        hipLaunchKernelGGL(k_quality_pack_volumes, dim3(gridFor(h->qNProc)), dim3(kQualityBlock), 0, h->stream, h->qOwn, h->qgVol, h->qProcFace,
-                           h->qNProc, (double*)sendVc);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(h->stream));       // sendVc is the host's to move
-    h->qVolEpoch = h->qEpoch;
-    h->qVolCoupling = h->qCoupling;
-    if (nProcFaces) *nProcFaces = h->qNProc;
-    return 0;
-}
-
-int smgpu_quality_coupled_geometry_report(smgpu_handle* h, const smgpu_quality_geometry_params* p, const void* recvCc, const void* recvVc,
-                                          smgpu_quality_geometry_part* out) {
-    if (!h || !out) return fail("null argument");
-    if (runQualityGeom(h, "smgpu_quality_coupled_geometry_report", p, qualityCoupling(h, recvCc, recvVc), kQualityNoFields)) return 1;
-    return qualityCopyOut(h, out, h->qgPartOut);
-}
-int smgpu_quality_coupled_geometry_field(smgpu_handle* h, const char* name, const void* recvCc, const void* recvVc, double* out, int64_t* n) {
-    if (!h || !name || !n) return fail("null argument");
-    const char* api = "smgpu_quality_coupled_geometry_field";
-    return qualityField(h, kQualityGeomFields, api, name, out, n,
-                        [&](double** o) { return runQualityGeom(h, api, nullptr, qualityCoupling(h, recvCc, recvVc), o); });
-}
-
-int smgpu_quality_coupled_motion_report(smgpu_handle* h, const smgpu_quality_motion_params* p, const void* recvCc, smgpu_quality_motion_part* out) {
-    if (!h || !out) return fail("null argument");
-    if (runQualityMotion(h, "smgpu_quality_coupled_motion_report", p, qualityCoupling(h, recvCc, nullptr), kQualityNoFields)) return 1;
-    return qualityCopyOut(h, out, h->qmPartOut);
-}
-int smgpu_quality_coupled_motion_field(smgpu_handle* h, const char* name, const void* recvCc, double* out, int64_t* n) {
-    if (!h || !name || !n) return fail("null argument");
-    const char* api = "smgpu_quality_coupled_motion_field";
-    return qualityField(h, kQualityMotionFields, api, name, out, n,
-                        [&](double** o) { return runQualityMotion(h, api, nullptr, qualityCoupling(h, recvCc, nullptr), o); });
-}
-
-// ---- the failing elements as sets (DESIGN.md "Mesh quality", 10.5 and 10.9) ------------------------------------------------
-// One sequence for the three reports' sets, <NF, NC> being the report's set layout (NF face sets, then NC cell sets):
-// flags(mask, cnt) launches the report's flag passes (faces: mask[0, F), the cnt rows of the face sets; cells: mask[F, F + C),
-// cnt + NF * nFB); then the scan, one copy of the counts, and when ids fit the scatter and one copy of the ids.  Every buffer is
-// this call's own (outside deviceBytes, as the field buffers).
-extern "C++" {
-template <int NF, int NC, class Flags>
-static int qualitySetsOf(smgpu_handle* h, const char* api, Flags flags, int64_t* counts, int32_t* ids, int64_t cap) {
-    const MeshView& m = h->mv;
-    const int nFB = qualityGrid(m.nFaces), nCB = NC > 0 ? qualityGrid(m.nCells) : 0;
-    const int nCnt = NF * nFB + NC * nCB;
-    uint8_t* mask = nullptr;
-    int* cnt = nullptr;
-    long long *off = nullptr, *dCounts = nullptr;
-    int* dIds = nullptr;
-    int rc = 0;
-    auto hipFail = [&](hipError_t e) { rc = fail(std::string(api) + ": " + hipGetErrorString(e)); };
-    hipError_t e = hipMalloc((void**)&mask, (size_t)std::max<int64_t>(1, (int64_t)m.nFaces + (NC > 0 ? m.nCells : 0)));
-    if (e == hipSuccess) e = hipMalloc((void**)&cnt, sizeof(int) * (size_t)std::max(1, nCnt));
-    if (e == hipSuccess) e = hipMalloc((void**)&off, sizeof(long long) * ((size_t)nCnt + 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&dCounts, sizeof(long long) * (NF + NC));
-    if (e != hipSuccess) hipFail(e);
-    if (rc == 0) {
-        flags(mask, cnt, nFB, nCB);
-        e = hipGetLastError();
-        if (e != hipSuccess) hipFail(e);
-    }
-    if (rc == 0) {
-        hipLaunchKernelGGL((k_quality_set_scan<NF, NC>), dim3(1), dim3(kQualityScanBlock), 0, h->stream, cnt, nCnt, nFB, nCB, off, dCounts);
-        long long hc[NF + NC];
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(hc, dCounts, sizeof(hc), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) hipFail(e);
-        int64_t total = 0;
-        for (int s = 0; s < NF + NC && rc == 0; ++s) { counts[s] = hc[s]; total += hc[s]; }
-        if (rc == 0 && ids && cap < total)
-            rc = fail(std::string(api) + ": ids holds " + std::to_string(cap) + " labels, the sets need " + std::to_string(total));
-        if (rc == 0 && ids && total > 0) {
-            e = hipMalloc((void**)&dIds, sizeof(int) * (size_t)total);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL((k_quality_set_scatter<NF, NC>), dim3(nFB + nCB), dim3(kQualityBlock), 0, h->stream, mask, m.nFaces, m.nCells, nFB,
-                                   nCB, off, dIds, (long long)total);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(ids, dIds, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) hipFail(e);
-        }
-    }
-    (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)mask, (void*)cnt, (void*)off, (void*)dCounts, (void*)dIds})
-        if (p) (void)hipFree(p);
-    return rc;
-}
-
-template <bool Coupled>
-static int qualitySets(smgpu_handle* h, const char* api, const smgpu_quality_params* p, const QCoupling<Coupled>& cp, int64_t counts[7], int32_t* ids,
-                       int64_t cap) {
-    const QualityThresholds thr = qualityThresholds(p);
-    return qualitySetsOf<kQualityFaceSets, kQualityCellSets>(h, api, [&](uint8_t* mask, int* cnt, int nFB, int nCB) {
-        const MeshView& m = h->mv;
-        const State& s = h->st;
-        if (nFB > 0)
-            hipLaunchKernelGGL(k_quality_face_flags<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea, s.cellCtr,
-                               h->qOwn, h->qNei, cp, thr, mask, cnt);
-        if (nCB > 0)
-            hipLaunchKernelGGL(k_quality_cell_flags, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, thr, mask + m.nFaces,
-                               cnt + (size_t)kQualityFaceSets * nFB);
-    }, counts, ids, cap);
-}
-// the sets of the -allGeometry checks (10.9): the cell flag pass first (serial: it leaves the volumes in h->qgVol), then the
-// face flag pass.  The caller has made the refusals and the geometry of the matching report (runQualityGeom).
-template <bool Coupled>
-static int qualityGeomSets(smgpu_handle* h, const char* api, const smgpu_quality_geometry_params* p, const QCoupling<Coupled>& cp, int64_t counts[5],
-                           int32_t* ids, int64_t cap) {
-    const QualityGeomThresholds thr = geomThresholds(p);
-    return qualitySetsOf<kQualityGeomFaceSets, kQualityGeomCellSets>(h, api, [&](uint8_t* mask, int* cnt, int nFB, int nCB) {
-        const MeshView& m = h->mv;
-        const State& s = h->st;
-        if (nCB > 0)
-            hipLaunchKernelGGL(k_quality_geom_cell_flags<Coupled>, dim3(nCB), dim3(kQualityBlock), 0, h->stream, m, s.fCtr, s.fArea, cp, thr, h->qgVol,
-                               mask + m.nFaces, cnt + (size_t)kQualityGeomFaceSets * nFB);
-        if (nFB > 0)
-            hipLaunchKernelGGL(k_quality_geom_face_flags<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, m, s.ptsCur, s.fCtr, s.fArea,
-                               s.cellCtr, h->qgVol, h->qOwn, h->qNei, cp, thr, mask, cnt);
-    }, counts, ids, cap);
-}
-// ... and of the motion criteria: face sets only
-template <bool Coupled>
-static int qualityMotionSets(smgpu_handle* h, const char* api, const smgpu_quality_motion_params* p, const QCoupling<Coupled>& cp, int64_t counts[4],
-                             int32_t* ids, int64_t cap) {
-    const QualityMotionThresholds thr = motionThresholds(p);
-    return qualitySetsOf<kQualityMotionFaceSets, 0>(h, api, [&](uint8_t* mask, int* cnt, int nFB, int) {
-        const State& s = h->st;
-        if (nFB > 0)
-            hipLaunchKernelGGL(k_quality_motion_face_flags<Coupled>, dim3(nFB), dim3(kQualityBlock), 0, h->stream, h->mv, s.ptsCur, s.fCtr, s.cellCtr,
-                               h->qOwn, h->qNei, cp, thr, mask, cnt);
-    }, counts, ids, cap);
-}
-}  // extern "C++"
-
-int smgpu_quality_sets(smgpu_handle* h, const smgpu_quality_params* p, int64_t counts[7], int32_t* ids, int64_t cap) {
-    if (!h || !counts) return fail("null argument");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityEnsure(h)) return 1;
-    if (qualityGeometry(h)) return 1;
-    return qualitySets(h, "smgpu_quality_sets", p, QCoupling<false>{}, counts, ids, cap);
-}
-
-int smgpu_quality_coupled_sets(smgpu_handle* h, const smgpu_quality_params* p, const void* recvCc, int64_t counts[7], int32_t* ids, int64_t cap) {
-    if (!h || !counts) return fail("null argument");
-    const char* api = "smgpu_quality_coupled_sets";
-    if (qualityCoupledReady(h, api, recvCc)) return 1;
-    HIP_OK(hipSetDevice(h->device));
-    return qualitySets(h, api, p, qualityCoupling(h, recvCc, nullptr), counts, ids, cap);
-}
-
-int smgpu_quality_geometry_sets(smgpu_handle* h, const smgpu_quality_geometry_params* p, int64_t counts[5], int32_t* ids, int64_t cap) {
-    if (!h || !counts) return fail("null argument");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityGeomEnsure(h)) return 1;
-    if (qualityGeometry(h)) return 1;
-    return qualityGeomSets(h, "smgpu_quality_geometry_sets", p, QCoupling<false>{}, counts, ids, cap);
-}
-
-int smgpu_quality_motion_sets(smgpu_handle* h, const smgpu_quality_motion_params* p, int64_t counts[4], int32_t* ids, int64_t cap) {
-    if (!h || !counts) return fail("null argument");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
-    HIP_OK(hipSetDevice(h->device));
-    if (qualityEnsure(h)) return 1;
-    if (qualityGeometry(h)) return 1;
-    return qualityMotionSets(h, "smgpu_quality_motion_sets", p, QCoupling<false>{}, counts, ids, cap);
-}
-
-int smgpu_quality_coupled_geometry_sets(smgpu_handle* h, const smgpu_quality_geometry_params* p, const void* recvCc, const void* recvVc,
-                                        int64_t counts[5], int32_t* ids, int64_t cap) {
-    if (!h || !counts) return fail("null argument");
-    const char* api = "smgpu_quality_coupled_geometry_sets";
-    if (qualityCoupledGeomReady(h, api, recvCc, recvVc)) return 1;
-    HIP_OK(hipSetDevice(h->device));
-    return qualityGeomSets(h, api, p, qualityCoupling(h, recvCc, recvVc), counts, ids, cap);
-}
-
-int smgpu_quality_coupled_motion_sets(smgpu_handle* h, const smgpu_quality_motion_params* p, const void* recvCc, int64_t counts[4], int32_t* ids,
-                                      int64_t cap) {
-    if (!h || !counts) return fail("null argument");
-    const char* api = "smgpu_quality_coupled_motion_sets";
-    if (qualityCoupledReady(h, api, recvCc)) return 1;
-    HIP_OK(hipSetDevice(h->device));
-    return qualityMotionSets(h, api, p, qualityCoupling(h, recvCc, nullptr), counts, ids, cap);
 }
 
 // ---- debug / parity access -------------------------------------------------------------------
