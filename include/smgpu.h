@@ -673,6 +673,9 @@ int smgpu_debug_addressing_checksums(smgpu_handle* h, uint64_t* out /* [SMGPU_TO
 /* the same for the geometry tile tables as the kernels read them (device build, csrc/tiles_dev.hip, against SMGPU_DEVICE_TILES=0) */
 int smgpu_debug_tile_checksums(smgpu_handle* h, uint64_t* out /* [SMGPU_TOPO_CHECKSUMS] */);
 int smgpu_debug_halo_mode(smgpu_handle* h, int32_t* multiRole, int32_t* flagged, int32_t* fixInside);
+/* the tile counts the multi-role launches are split on (smgpu_halo_configure; all 0 on the direct-gather kernels): geometry tiles
+ * with / without a shared point, regular smoothing tiles, tiles of the shared points only */
+int smgpu_debug_halo_tiles(smgpu_handle* h, int32_t* geomShared, int32_t* geomInterior, int32_t* smoothTiles, int32_t* sharedPointTiles);
 
 /* self-test of the geometry kernel's range-tested square root / division fast paths (csrc/fpexact.hpp) against the plain
  * IEEE operators on n generated arguments (random, zeros, denormals, inf / nan, both ends of the exponent range) on the

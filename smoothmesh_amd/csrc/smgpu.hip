@@ -2079,6 +2079,17 @@ int smgpu_debug_halo_mode(smgpu_handle* h, int32_t* multiRole, int32_t* flaggedO
     return 0;
 }
 
+int smgpu_debug_halo_tiles(smgpu_handle* h, int32_t* geomShared, int32_t* geomInterior, int32_t* smoothTiles, int32_t* sharedPointTiles) {
+    if (!h || !geomShared || !geomInterior || !smoothTiles || !sharedPointTiles) return fail("null argument");
+    if (!h->haloOn) return fail("halo not configured");
+    const bool t = h->useTiles;
+    *geomShared = t ? h->nGeomShared : 0;
+    *geomInterior = t ? h->nGeomInterior : 0;
+    *smoothTiles = t ? h->stl.nTiles : 0;
+    *sharedPointTiles = t ? h->shr.nTiles : 0;
+    return 0;
+}
+
 int smgpu_get_points(smgpu_handle* h, double* out) {
     if (!h || !out) return fail("null argument");
     HIP_OK(hipSetDevice(h->device));

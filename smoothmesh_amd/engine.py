@@ -941,6 +941,13 @@ class SmoothEngine:
         self._check(self._lib.smgpu_debug_halo_mode(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"multi_role": bool(a.value), "flagged": bool(b.value), "fix_inside": bool(c.value)}
 
+    def debug_halo_tiles(self):
+        """the tile counts the multi-role launches are split on: {"geom_shared", "geom_interior", "smooth_tiles", "shared_point_tiles"}
+        (include/smgpu.h; all 0 on the direct-gather kernels)"""
+        v = [C.c_int32() for _ in range(4)]
+        self._check(self._lib.smgpu_debug_halo_tiles(self._h, *(C.byref(x) for x in v)))
+        return dict(zip(("geom_shared", "geom_interior", "smooth_tiles", "shared_point_tiles"), (x.value for x in v)))
+
     def set_device_share(self, n_engines):
         """n_engines engines compute on this device at the same time: the persistent walk replay takes its share of the chip"""
         self._check(self._lib.smgpu_set_device_share(self._h, int(n_engines)))

@@ -203,30 +203,40 @@ def test_golden_fixture_boundary_hip(oracle_lib):
     assert np.allclose(np.concatenate(res_all), g["residual"], rtol=1e-10, atol=0)
 
 
-@pytest.mark.parametrize("grid,constraints,layers", [((2, 1, 1), False, False), ((2, 2, 1), True, False), ((2, 2, 2), False, True),
-                                                      ((1, 2, 2), True, True), ((3, 3, 3), False, False)])   # 3x3x3: one rank has no boundary
-def test_decomposed_boundary_smoothing(oracle_lib, grid, constraints, layers):
-    """-parallel: every engine holds one sub-domain; the set-up runs in steps with the reference's reductions and syncs
-    between them, the per-iteration fields travel in the L records.  Bit-equal to the oracle's MultiDomain."""
-    from smoothmesh_amd import BoundaryParams, LayerParams, patch_arrays
-    from smoothmesh_amd.halo import LocalMultiSmoother
+def _decomposed_boundary_case(oracle_lib, grid, constraints, layers):
+    """the oracle's MultiDomain with boundary point smoothing (and layers) on a `grid` cut -> (mo, orcs, subs, prm, set_up):
+    set_up(ms) does the same set-up on the engines of a LocalMultiSmoother and checks its classification against the oracle's"""
+    from smoothmesh_amd import BoundaryParams, LayerParams
     from smoothmesh_amd.surfgen import box_feature_edges, box_surface
     from test_oracle_boundary import _multi_boundary_case
     lpatches = ("xmin", "zmax") if layers else ()
     nloc = (3, 3, 4) if grid == (3, 3, 3) else (5, 4, 6)
     mo, orcs, subs, (off, dom, loc), hi = _multi_boundary_case(oracle_lib, grid, nloc, 0.25, constraints, blend=0.4, layerPatches=lpatches)
     prm = mo.params
+    counts = [{k: int(o.boundary_fields()[k].sum()) for k in ("isCornerPoint", "isFeatureEdgePoint", "isSmoothingSurfacePoint")} for o in orcs]
+
+    def set_up(ms):
+        ms.set_params(prm)
+        if layers:
+            assert ms.set_layers(LayerParams(layerPatches=lpatches), prm.minEdgeLength)
+        bp = BoundaryParams(initEdges=box_feature_edges(8, hi=hi), targetSurfaces=box_surface(4, hi=hi), internalSmoothingBlendingFraction=0.4)
+        infos = ms.set_boundary_smoothing(bp, prm.minEdgeLength)
+        assert all(i["enabled"] for i in infos)
+        for c, i in zip(counts, infos):
+            assert i["nCornerPoints"] == c["isCornerPoint"] and i["nFeatureEdgePoints"] == c["isFeatureEdgePoint"]
+            assert i["nSmoothingSurfacePoints"] == c["isSmoothingSurfacePoint"]
+    return mo, orcs, subs, prm, set_up
+
+
+@pytest.mark.parametrize("grid,constraints,layers", [((2, 1, 1), False, False), ((2, 2, 1), True, False), ((2, 2, 2), False, True),
+                                                      ((1, 2, 2), True, True), ((3, 3, 3), False, False)])   # 3x3x3: one rank has no boundary
+def test_decomposed_boundary_smoothing(oracle_lib, grid, constraints, layers):
+    """-parallel: every engine holds one sub-domain; the set-up runs in steps with the reference's reductions and syncs
+    between them, the per-iteration fields travel in the L records.  Bit-equal to the oracle's MultiDomain."""
+    from smoothmesh_amd.halo import LocalMultiSmoother
+    mo, orcs, subs, prm, set_up = _decomposed_boundary_case(oracle_lib, grid, constraints, layers)
     ms = LocalMultiSmoother(subs, device=0)
-    ms.set_params(prm)
-    if layers:
-        assert ms.set_layers(LayerParams(layerPatches=lpatches), prm.minEdgeLength)
-    bp = BoundaryParams(initEdges=box_feature_edges(8, hi=hi), targetSurfaces=box_surface(4, hi=hi), internalSmoothingBlendingFraction=0.4)
-    infos = ms.set_boundary_smoothing(bp, prm.minEdgeLength)
-    assert all(i["enabled"] for i in infos)
-    for o, i in zip(orcs, infos):
-        f = o.boundary_fields()
-        assert i["nCornerPoints"] == f["isCornerPoint"].sum() and i["nFeatureEdgePoints"] == f["isFeatureEdgePoint"].sum()
-        assert i["nSmoothingSurfacePoints"] == f["isSmoothingSurfacePoint"].sum()
+    set_up(ms)
     n_o, res_o, frz_o = mo.iterate(8, 0.0)
     n_g, res_g, frz_g = ms.iterate(8, 0.0)
     assert n_o == n_g and np.array_equal(frz_o, frz_g)

@@ -101,6 +101,58 @@ def test_launch_variants_give_the_same_result(oracle_lib, monkeypatch, env):
     _compare(cavity_mesh(16, jitter=0.2, seed=3), oracle_lib, iters=3)
 
 
+_ORACLE_RUNS = {}      # name -> (mesh, params, oracle run, oracle points): computed once, shared by the cases, left unchanged
+
+
+def _bits(name, make_mesh, oracle_lib, iters, env, monkeypatch):
+    """an engine created and run under `env` (constraints on) gives the oracle's coordinates, residuals and nFrozenPoints bit for bit"""
+    from smoothmesh_amd import SmoothEngine, default_params
+    if name not in _ORACLE_RUNS:
+        mesh = make_mesh()
+        o = oracle_lib.Oracle(mesh)
+        p = default_params(o.mesh_stats()[0])
+        o.set_params(p)
+        _ORACLE_RUNS[name] = (mesh, p, o.iterate(iters, 0.0), o.points())
+    mesh, p, (n_o, res_o, frz_o), pts_o = _ORACLE_RUNS[name]
+    with monkeypatch.context() as mp:
+        for k, v in env.items():
+            mp.setenv(k, str(v))
+        e = SmoothEngine(mesh)
+        e.set_params(p)
+        n_g, res_g, frz_g = e.iterate(iters, 0.0)
+        pts_g = e.get_points()
+        e.close()
+    assert n_o == n_g and np.array_equal(frz_o, frz_g) and np.array_equal(res_o, res_g)
+    assert np.array_equal(pts_g, pts_o)
+    return mesh
+
+
+@pytest.mark.parametrize("walk", ["", "fix"])
+@pytest.mark.parametrize("blocks", [1, 7, 2049])
+def test_star_cache_block_count(oracle_lib, monkeypatch, blocks, walk):
+    """SMGPU_STAR_BLOCKS: the workgroup count of the face-angle walk's predicate kernels (grid-stride loops over the active points) --
+    one workgroup, a count that divides nothing, and one above the min(starBlocks, 2048) of the star cache's build / rest kernels; with
+    SMGPU_WALK=fix the compacted replay, whose star kernels take that count, runs whatever the number of active points.  The mixed
+    tiles of the constrained cavity mesh, the oracle's bits."""
+    from smoothmesh_amd.polymesh import cavity_mesh
+    env = {"SMGPU_STAR_BLOCKS": blocks}
+    if walk:
+        env["SMGPU_WALK"] = walk
+    _bits("cavity16", lambda: cavity_mesh(16, jitter=0.2, seed=3), oracle_lib, 3, env, monkeypatch)
+
+
+@pytest.mark.parametrize("below", [0, 1])
+def test_side_stream_size_threshold(oracle_lib, monkeypatch, below):
+    """SMGPU_SIDE_STREAM_MAX_POINTS: the mesh size up to which the face-angle filter runs on a side stream by default (nPoints <=
+    the value).  At nPoints the side stream stays on, at nPoints - 1 it is off; both give the oracle's bits.  The engine does not
+    report which arrangement it chose (no counter, no set-up line), so the bits are all this test can hold; SMGPU_SIDE_STREAM=0 / 1
+    themselves are held by test_launch_variants_give_the_same_result."""
+    from smoothmesh_amd.meshgen import hex_block
+    nPoints = 25 * 21 * 19
+    m = _bits("hex24", lambda: hex_block(24, 20, 18, jitter=0.25, seed=8), oracle_lib, 4, {"SMGPU_SIDE_STREAM_MAX_POINTS": nPoints - below}, monkeypatch)
+    assert m.nPoints == nPoints
+
+
 @pytest.mark.parametrize("case", ["coincident", "collapsed_cell", "inverted"])
 @pytest.mark.parametrize("constraints", [False, True])
 def test_degenerate_geometry_matches_the_oracle(oracle_lib, case, constraints):

@@ -49,33 +49,77 @@ def test_local_multi_smoother_on_irregular_partitions(oracle_lib, kind, nR, seed
         assert same.any() and np.array_equal(allp[order][1:][same], allp[order][:-1][same])
 
 
+def _run_parallel_cli(case, prm, env=None):
+    return subprocess.run([BIN, "-case", str(case), "-parallel", "-centroidalIters", "6", "-relTol", "0", "-minEdgeLength", repr(prm.minEdgeLength),
+                           "-maxStepLength", repr(prm.maxStepLength)], capture_output=True, text=True, timeout=600, env=env)
+
+
+def _written_points(case, subs):
+    from smoothmesh_amd.polymesh import read_polymesh
+    out = []
+    for s in subs:
+        d = case / f"processor{s.rank}"
+        out.append(read_polymesh(str(d / "constant" / "polyMesh"), pointsDir=str(d / "6" / "polyMesh")).points.reshape(-1))
+    return out
+
+
 @pytest.mark.parametrize("kind,nR,seed", [("hex_island", 3, 31), ("poly_bfs", 5, 32), ("two_blocks", 3, 33), ("hex_baffle", 4, 34)])
-@pytest.mark.parametrize("match", ["ids", "patches"])
+@pytest.mark.parametrize("match", ["ids", "patches", "forced"])
 def test_parallel_cli_on_irregular_processor_directories(tmp_path, oracle_lib, kind, nR, seed, match):
     """match = "patches": the sub-domains WITHOUT pointProcAddressing (a mesh made in parallel, e.g. by snappyHexMesh -parallel, has
     none): the front-end then finds the copies of a point through the processor patches themselves, vertex by vertex of the
-    matching faces, as OpenFOAM's globalPoints does -- same tables, same result."""
-    from smoothmesh_amd.decompose import decompose
-    from smoothmesh_amd.polymesh import read_polymesh, write_decomposed_case
+    matching faces, as OpenFOAM's globalPoints does -- same tables, same result.
+    match = "forced": every pointProcAddressing is there, but processor1's is stale -- a permutation of its own ids, the right size
+    and the wrong matches -- and SMGPU_MATCH_BY_PATCHES=1 makes the front-end ignore the files."""
+    from smoothmesh_amd.polymesh import write_decomposed_case, write_label_list
     mesh, cr = build_case(kind, nR, seed)
     subs, ser, orcs, mo, prm = _oracles(oracle_lib, mesh, cr, nR, True)
     write_decomposed_case(str(tmp_path), subs, binary=True, writeFormat="binary")
+    env = None
     if match == "patches":
         for s in subs:
             os.remove(tmp_path / f"processor{s.rank}" / "constant" / "polyMesh" / "pointProcAddressing")
-    r = subprocess.run([BIN, "-case", str(tmp_path), "-parallel", "-centroidalIters", "6", "-relTol", "0", "-minEdgeLength", repr(prm.minEdgeLength),
-                        "-maxStepLength", repr(prm.maxStepLength)], capture_output=True, text=True, timeout=600)
+    elif match == "forced":
+        _stale_addressing(tmp_path, subs[1], write_label_list)
+        env = dict(os.environ, SMGPU_MATCH_BY_PATCHES="1")
+    r = _run_parallel_cli(tmp_path, prm, env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert f"nProcs : {nR}" in r.stdout
-    assert ("Shared points matched through the processor patches" in r.stdout) == (match == "patches")
+    assert ("Shared points matched through the processor patches" in r.stdout) == (match != "ids")
     n, res, frz = mo.iterate(6, 0.0)
     lines = LINE.findall(r.stdout)
     assert [int(b) for _, b, _ in lines] == frz.tolist()
     assert np.allclose([float(c) for _, _, c in lines], res, rtol=1e-5)
-    for s, o in zip(subs, orcs):
-        d = tmp_path / f"processor{s.rank}"
-        got = read_polymesh(str(d / "constant" / "polyMesh"), pointsDir=str(d / "6" / "polyMesh")).points
-        assert np.array_equal(got.reshape(-1), o.points().reshape(-1))
+    for got, o in zip(_written_points(tmp_path, subs), orcs):
+        assert np.array_equal(got, o.points().reshape(-1))
+
+
+def _stale_addressing(case, sub, write_label_list):
+    """overwrite the sub-domain's pointProcAddressing with its own ids moved on by one point: none of them is right"""
+    ids = np.roll(sub.pointProcAddressing, 1)
+    assert len(np.unique(ids)) == len(ids) and not np.any(ids == sub.pointProcAddressing)
+    write_label_list(str(case / f"processor{sub.rank}" / "constant" / "polyMesh" / "pointProcAddressing"), ids, "constant/polyMesh",
+                     "pointProcAddressing", "labelIOList", True)
+
+
+def test_stale_addressing_is_what_the_patch_matching_ignores(tmp_path, oracle_lib):
+    """the "forced" case without SMGPU_MATCH_BY_PATCHES: the front-end trusts the stale file, so it either refuses the case or
+    smooths with the wrong points matched -- the written points are not the oracle's.  The file was wrong, and the knob is what
+    kept it from being read."""
+    from smoothmesh_amd.polymesh import write_decomposed_case, write_label_list
+    mesh, cr = build_case("hex_island", 3, 31)
+    subs, ser, orcs, mo, prm = _oracles(oracle_lib, mesh, cr, 3, True)
+    write_decomposed_case(str(tmp_path), subs, binary=True, writeFormat="binary")
+    _stale_addressing(tmp_path, subs[1], write_label_list)
+    env = dict(os.environ)
+    env.pop("SMGPU_MATCH_BY_PATCHES", None)
+    r = _run_parallel_cli(tmp_path, prm, env)
+    assert "Shared points matched through the processor patches" not in r.stdout
+    if r.returncode == 0:
+        mo.iterate(6, 0.0)
+        assert any(not np.array_equal(got, o.points().reshape(-1)) for got, o in zip(_written_points(tmp_path, subs), orcs))
+    else:
+        assert "FOAM FATAL ERROR" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 @pytest.mark.parametrize("spec,world,port", [("two_blocks:41", 3, "29541"), ("poly_bfs:42", 3, "29543")])

@@ -9,6 +9,46 @@ from conftest import rel_linf
 pytestmark = pytest.mark.gpu
 
 
+def _hex_case(oracle_lib, grid, sub, constraints, jitter=0.3, seed=9):
+    """hex sub-domains of a `grid` cut with their oracles, parameters, shared-point table and the oracle's MultiDomain"""
+    from smoothmesh_amd import default_params
+    from smoothmesh_amd.decompose import shared_point_table
+    from smoothmesh_amd.meshgen import hex_subdomain
+    world = grid[0] * grid[1] * grid[2]
+    subs = [hex_subdomain(sub, grid, r, jitter=jitter, seed=seed) for r in range(world)]
+    orcs = [oracle_lib.Oracle(s.mesh) for s in subs]
+    prm = default_params(min(o.mesh_stats()[0] for o in orcs), edgeAngleConstraint=constraints, faceAngleConstraint=constraints)
+    for o in orcs:
+        o.set_params(prm)
+    table = shared_point_table(subs)
+    return subs, orcs, prm, table, oracle_lib.MultiOracle(orcs, *table)
+
+
+def _copies_identical(subs, points):
+    """duplicated (shared) points stay bit-identical across the engines that hold them"""
+    g = np.concatenate([s.pointProcAddressing for s in subs])
+    allp = np.concatenate([np.asarray(p).reshape(-1, 3) for p in points])
+    order = np.argsort(g, kind="stable")
+    gs, ps = g[order], allp[order]
+    same = gs[1:] == gs[:-1]
+    assert same.any() and np.array_equal(ps[1:][same], ps[:-1][same])
+
+
+def _check_against_multi_oracle(subs, orcs, oracle_run, gpu_run, points, bits=False):
+    """the project's tolerances for a decomposed run against the oracle's MultiDomain: equal nFrozenPoints, residuals to a
+    relative 1e-10, points to rel_linf <= 1e-13 (bits: np.array_equal), copies of a shared point identical"""
+    (n_o, res_o, frz_o), (n_g, res_g, frz_g) = oracle_run, gpu_run
+    assert n_o == n_g
+    assert np.array_equal(frz_o, frz_g)
+    assert np.max(np.abs(res_o - res_g) / np.maximum(res_o, 1e-300)) <= 1e-10
+    for o, pts in zip(orcs, points):
+        if bits:
+            assert np.array_equal(pts, o.points())
+        else:
+            assert rel_linf(pts, o.points()) <= 1e-13
+    _copies_identical(subs, points)
+
+
 # the (16, 12, 12) sub-domains span several geometry/smoothing tiles, so the interior/shared tile split and the
 # look-ahead geometry (smgpu_iter_ahead) are really exercised
 # overlap = 1: engines compute on their own streams, the exchange runs on torch's stream (smgpu_halo_desc.exchangeStream)
@@ -17,45 +57,23 @@ pytestmark = pytest.mark.gpu
     ((3, 1, 2), True, (5, 4, 4), 0), ((2, 2, 1), False, (16, 12, 12), 0), ((2, 2, 1), False, (16, 12, 12), 1),
     ((2, 1, 2), True, (16, 12, 12), 0), ((2, 1, 2), True, (16, 12, 12), 1)])
 def test_local_multi_smoother_matches_multi_oracle(oracle_lib, grid, constraints, sub, overlap):
-    from smoothmesh_amd import default_params
-    from smoothmesh_amd.decompose import shared_point_table
     from smoothmesh_amd.halo import LocalMultiSmoother
-    from smoothmesh_amd.meshgen import hex_subdomain
-    world = grid[0] * grid[1] * grid[2]
-    subs = [hex_subdomain(sub, grid, r, jitter=0.3, seed=9) for r in range(world)]
+    subs, orcs, prm, table, mo = _hex_case(oracle_lib, grid, sub, constraints)
     ms = LocalMultiSmoother(subs, device=0, overlap=bool(overlap))
-    orcs = [oracle_lib.Oracle(s.mesh) for s in subs]
-    mn = min(o.mesh_stats()[0] for o in orcs)
-    assert mn == ms.global_min_edge()
-    prm = default_params(mn, edgeAngleConstraint=constraints, faceAngleConstraint=constraints)
+    assert min(o.mesh_stats()[0] for o in orcs) == ms.global_min_edge()
     ms.set_params(prm)
-    for o in orcs:
-        o.set_params(prm)
-    off, dom, loc = shared_point_table(subs)
-    mo = oracle_lib.MultiOracle(orcs, off, dom, loc)
-    n_o, res_o, frz_o = mo.iterate(8, 0.0)
+    oracle_run = mo.iterate(8, 0.0)
     big_fused = sub[0] > 8 and not constraints
     if big_fused:
         ms.states[0].eng.enable_timing(True)
-    n_g, res_g, frz_g = ms.iterate(8, 0.0)
+    gpu_run = ms.iterate(8, 0.0)
     if big_fused:
         # with an exchange stream the look-ahead is active: iteration 1 = one full geometry launch, every later one =
         # shared tiles, and every iteration launches the look-ahead for the interior tiles -> 1 + 7 + 8 launches;
         # in order (no exchange stream) nothing would overlap, so the launches are not split: 8
         geom = [c for c in ms.states[0].eng.counters() if c["name"] == "k_geom_tile"]
         assert geom and geom[0]["launches"] == (16 if overlap else 8)
-    assert n_o == n_g
-    assert np.array_equal(frz_o, frz_g)
-    assert np.max(np.abs(res_o - res_g) / np.maximum(res_o, 1e-300)) <= 1e-10
-    for o, pts in zip(orcs, ms.get_points()):
-        assert rel_linf(pts, o.points()) <= 1e-13
-    # duplicated (shared) points stay bit-identical across the engines that hold them
-    g = np.concatenate([s.pointProcAddressing for s in subs])
-    allp = np.concatenate(ms.get_points())
-    order = np.argsort(g, kind="stable")
-    gs, ps = g[order], allp[order]
-    same = gs[1:] == gs[:-1]
-    assert np.array_equal(ps[1:][same], ps[:-1][same])
+    _check_against_multi_oracle(subs, orcs, oracle_run, gpu_run, ms.get_points())
 
 
 def _poly_case(oracle_lib, N, grid, constraints, jitter=0.2, seed=4):
@@ -223,6 +241,33 @@ def test_every_arrangement_of_the_iteration_gives_the_same_bits(transport):
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "arrangements: ok" in r.stdout and "DIFFERENT" not in r.stdout
     assert r.stdout.count("same bits") == (1 if transport == "push" else 4)
+
+
+@pytest.mark.parametrize("n", [26, 6])
+@pytest.mark.parametrize("transport", ["rccl", "push"])
+def test_arrangement_knobs_give_the_same_bits(transport, n):
+    """where the pack role and the fix role sit inside k_geom_halo / k_smooth_halo (scripts/check_arrangements.py, case set "knobs":
+    SMGPU_HALO_FIX_INSIDE on and off, SMGPU_HALO_FIX_AT 0 / 50 / 100, SMGPU_HALO_PACK_AFTER 0 / every interior tile / 8 tiles), flagged
+    and in order with RCCL, in order with the peer-store transport -- the bits of the one-kernel-per-step reference, on the path
+    (multi_role / flagged / fix_inside) each case names.  n = 26: 77 smoothing tiles; n = 6: two, so hs.nA rounds to 0 and the fix
+    role runs ahead of every regular tile.  The script's docstring says why no knob value can make a launch wait for itself;
+    SMGPU_PUSH_TIMEOUT_S=10 and the roles' own 2 s bound end a wrong split with the engine's error word."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SMGPU_PUSH_TIMEOUT_S="10")
+    for k in ("SMGPU_HALO_FIX_INSIDE", "SMGPU_HALO_FIX_AT", "SMGPU_HALO_PACK_AFTER"):
+        env.pop(k, None)
+    if transport == "push":
+        env["SMOOTHMESH_EXCHANGE"] = "push"
+    r = subprocess.run([sys.executable, os.path.join(root, "scripts", "check_arrangements.py"), str(n), "8", "knobs"], capture_output=True, text=True,
+                       env=env, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "arrangements: ok" in r.stdout and "DIFFERENT" not in r.stdout and "another path" not in r.stdout
+    assert r.stdout.count("same bits") == (7 if transport == "push" else 10)
+    assert ("hs.nA = 0" in r.stdout) == (n == 6)
 
 
 @pytest.mark.parametrize("world", [2, 8])
