@@ -287,8 +287,8 @@ int smgpu_quality_guard_restore(smgpu_handle* h);
  * allocated at enabling, outside deviceBytes: nCells + nPoints bytes, and 32 bytes per iteration of the longest call.
  * An engine without tiles (SMGPU_TILES=0) evaluates with the direct geometry kernels: identical points and records.
  *
- * Refused (with the trace's wording where one exists): an engine with a halo -- so no smoothMesh -parallel and none of the
- * smoothers of halo.py; an engine with boundary point smoothing; smgpu_halo_configure and smgpu_set_boundary_smoothing while
+ * Refused (with the trace's wording where one exists): an engine with a halo -- it takes the coupled form below, which the
+ * smoothers of halo.py drive; smoothMesh -parallel has no option for it yet; an engine with boundary point smoothing; smgpu_halo_configure and smgpu_set_boundary_smoothing while
  * the constraint is on; passes < 0.  Layers, both foam variants, the trace and the guard go together with it: the guard's
  * snapshot gains nothing (the exempt mask is static), and its refining steps replay the constraint deterministically; their
  * records are dropped like their statistics.  When the guard rolls the points back (a trip, or smgpu_quality_guard_restore)
@@ -304,6 +304,51 @@ typedef struct smgpu_tangle_state { int32_t on, passes;  int64_t nExemptCells, i
 int smgpu_set_tangle_constraint(smgpu_handle* h, const smgpu_tangle_params* p, int32_t on);
 int smgpu_get_tangle_records(smgpu_handle* h, smgpu_tangle_record* out, int64_t cap, int64_t* n);
 int smgpu_get_tangle_state(smgpu_handle* h, smgpu_tangle_state* out);
+
+/* ---- the tangle constraint on a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.13) --------------------------
+ * The contract above, read on the GLOBAL mesh, for an engine whose halo is configured.  x, x', "bad" and "exempt" are the
+ * definitions above.  A cell is judged by its own volume and its own-side pyramids, a processor face needs no neighbour data,
+ * cells are never duplicated and a rank holds x and x' of every one of its points behind smgpu_iter_end: the evaluation is
+ * local.  Two things cross ranks: the MARKS (a shared point marked by a bad cell of one rank goes back on every rank that holds
+ * it) and the VERDICT ("B is empty", "this pass is the full revert": statements about the whole mesh).
+ *
+ * Exempt cells: one evaluation per rank at enabling; copies of shared points are identical, so this is the global mesh's answer.
+ * Per iteration, behind every rank's smgpu_iter_end, for k = 0 .. passes:
+ *   1. every rank evaluates its x'; B = the union of the ranks' bad cells that are not exempt;
+ *   2. B empty on all ranks: stop;
+ *   3. k == passes: every point of every rank goes back to x (the full revert), stop;
+ *   4. otherwise every point of every face of every cell in B goes back, on every rank that holds a copy of it.
+ * INVARIANT: the one above, on the global mesh; copies of a shared point stay bit-identical after every pass.
+ *
+ * The calls, on every rank, after smgpu_iter_end and before the next smgpu_iter_begin (which refuses while passes are due):
+ *   smgpu_tangle_pass_begin   evaluates the points the engine holds, packs the mark of every shared point into its send slots
+ *                             of sendT (int32, 0 / 1) and returns the rank's count of bad cells that are not exempt -- the one
+ *                             host read of the pass; sendT is complete when it returns.
+ *   the host                  sums the counts over ALL ranks; if the sum is positive and this is not the last pass (k < passes)
+ *                             it moves sendT -> recvT exactly as it moves exchange F (on the exchange stream, if one is set).
+ *   smgpu_tangle_pass_end     nBadGlobal == 0: closes the record, *done = 1.  k == passes: the full revert, the record closes,
+ *                             *done = 1.  Otherwise ORs recvT into the marks of the shared points through combOffsets /
+ *                             combSlots, applies the marked revert, *done = 0: the host begins the next pass.
+ * The engine keeps k; a call out of order is an error.  The verdict is the host's on purpose: a clean iteration costs one
+ * evaluation, one pack and one small closing launch, and none of the serial form's queued no-op passes.  With the peer-store
+ * transport the T records still travel by the host's exchange.
+ *
+ * One smgpu_tangle_record per iteration and rank: `passes` and `fullRevert` are the global values, the same on every rank;
+ * `nBadCells` is the rank's own count at k = 0; `nPointsReverted` the rank's own count, a shared point counting only on its
+ * master, the lowest-rank sharer (the first entry of its combSlots row is -1).  Summed over the ranks (passes and fullRevert
+ * taken from any one) they are the record of the undecomposed mesh.  smgpu_get_tangle_records and smgpu_get_tangle_state serve
+ * both forms (nExemptCells: the rank's own; the records wait on the device until they are asked for, which synchronises).
+ * residual and nFrozenPoints stay the loop's own values, as above.
+ *
+ * Goes together with layers, both foam variants, both sync variants, every transport and arrangement of the iteration.  Refused:
+ * an engine without a halo (smgpu_set_tangle_constraint is its form, and keeps refusing an engine with one), boundary point
+ * smoothing, passes < 0, a call between smgpu_iter_begin and smgpu_iter_end.  The trace and the guard stay refused on an engine
+ * with a halo.  Memory, allocated at enabling outside deviceBytes: nCells + nPoints + nShared bytes and 8 KiB of records; the
+ * caller owns sendT / recvT, 4 (nSend + nRecv) bytes.  on == 0 (either entry point) switches it off and releases everything. */
+typedef struct smgpu_tangle_halo_desc { void* sendT; void* recvT; } smgpu_tangle_halo_desc;   /* device, nSend / nRecv int32, caller-owned */
+int smgpu_set_tangle_constraint_coupled(smgpu_handle* h, const smgpu_tangle_params* p, const smgpu_tangle_halo_desc* d, int32_t on);
+int smgpu_tangle_pass_begin(smgpu_handle* h, int64_t* nBadLocal);                 /* after smgpu_iter_end */
+int smgpu_tangle_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done);
 
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):

@@ -143,6 +143,11 @@ class TangleState(C.Structure):
     _fields_ = [("on", C.c_int32), ("passes", C.c_int32), ("nExemptCells", C.c_int64), ("iteration", C.c_int64)]
 
 
+class TangleHaloDesc(C.Structure):
+    """smgpu_tangle_halo_desc"""
+    _fields_ = [("sendT", C.c_void_p), ("recvT", C.c_void_p)]
+
+
 class QualityGeometryParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("concaveThreshold", "flatnessThreshold", "weightThreshold", "volRatioThreshold",
                                           "determinantThreshold")]
@@ -259,6 +264,9 @@ SYMBOLS = {
     "smgpu_set_tangle_constraint": (C.c_int, [C.c_void_p, C.POINTER(TangleParams), C.c_int32]),
     "smgpu_get_tangle_records": (C.c_int, [C.c_void_p, C.POINTER(TangleRecord), C.c_int64, C.POINTER(C.c_int64)]),
     "smgpu_get_tangle_state": (C.c_int, [C.c_void_p, C.POINTER(TangleState)]),
+    "smgpu_set_tangle_constraint_coupled": (C.c_int, [C.c_void_p, C.POINTER(TangleParams), C.POINTER(TangleHaloDesc), C.c_int32]),
+    "smgpu_tangle_pass_begin": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "smgpu_tangle_pass_end": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "smgpu_quality_coupled_pack": (C.c_int, [C.c_void_p, C.POINTER(QualityCoupling), C.c_void_p, C.POINTER(C.c_int64)]),
     "smgpu_quality_coupled_report": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(QualityPart)]),
     "smgpu_quality_coupled_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),

@@ -291,4 +291,80 @@ __global__ void __launch_bounds__(kTangleBlock) k_tangle_apply(const double* __r
     }
 }
 
+// ---- the coupled form (smgpu_set_tangle_constraint_coupled, DESIGN.md "Mesh quality", 10.13): a sub-domain of a decomposed mesh ----
+// The evaluation is the one above, ungated (gate = NULL, pass = 0).  The verdict is the host's, on the count summed over the ranks,
+// so nothing here reads TangleDev::clean or ::full: the pass and its kind arrive as kernel arguments.
+
+// Exchange T, pack: one lane per send slot, slot -> shared index -> local point -> mark byte, as an int32 (k_halo_packF's shape:
+// consecutive lanes read consecutive sendShared entries and store consecutive sendT words).
+__global__ void __launch_bounds__(kTangleBlock) k_tangle_pack(int nSend, const int* __restrict__ sendShared, const int* __restrict__ sharedLocal,
+                                                               const uint8_t* __restrict__ marks, int* __restrict__ sendT) {
+    const int i = blockIdx.x * kTangleBlock + threadIdx.x;
+    if (i < nSend) sendT[i] = marks[sharedLocal[sendShared[i]]] ? 1 : 0;
+}
+
+// Exchange T, combine: one lane per shared point ORs the other sharers' marks into its own (k_halo_orF's shape).
+__global__ void __launch_bounds__(kTangleBlock) k_tangle_combine(int nShared, const int* __restrict__ sharedLocal, const int* __restrict__ combOff,
+                                                                  const int* __restrict__ combSlots, const int* __restrict__ recvT,
+                                                                  uint8_t* __restrict__ marks) {
+    const int i = blockIdx.x * kTangleBlock + threadIdx.x;
+    if (i >= nShared) return;
+    int any = 0;
+    for (int k = combOff[i]; k < combOff[i + 1]; ++k) {
+        const int sl = combSlots[k];
+        if (sl >= 0) any |= recvT[sl];
+    }
+    if (any) marks[sharedLocal[i]] = 1;
+}
+
+// The revert of the coupled form.  Every lane takes the four points of one word of marks (marks: as k_tangle_apply's), a lane
+// whose word is zero reads nothing else unless `full`; a point that goes back and whose coordinates differ is restored from x.
+// The revert itself is the same on every rank that holds the point; nPointsReverted takes a shared point on its master only:
+// sharedSlot[p] >= 0 names the point's entry of `counted` (one byte per shared point, 0 where a lower rank shares it).
+constexpr int kTangleCountedPts = 4 * kTangleBlock;
+__global__ void __launch_bounds__(kTangleBlock) k_tangle_apply_counted(const double* __restrict__ x, double* __restrict__ xNew, uint8_t* __restrict__ marks,
+                                                                        int nPoints, int full, const int* __restrict__ sharedSlot,
+                                                                        const uint8_t* __restrict__ counted, smgpu_tangle_record* __restrict__ rec) {
+    const int tid = threadIdx.x;
+    const long long p0 = ((long long)blockIdx.x * kTangleBlock + tid) * 4;
+    int changed = 0;
+    if (p0 < nPoints) {
+        unsigned* const mw = reinterpret_cast<unsigned*>(marks) + (p0 >> 2);
+        const unsigned w = *mw;
+        if (full || w) {
+            for (int j = 0; j < 4; ++j) {
+                const long long p = p0 + j;
+                if (p >= nPoints || !(full || ((w >> (8 * j)) & 0xffu))) continue;
+                const V3 a = ldv(x, p), b = ldv(xNew, p);
+                if (a.x != b.x || a.y != b.y || a.z != b.z) {
+                    stv(xNew, p, a);
+                    const int sl = sharedSlot ? sharedSlot[p] : -1;
+                    if (sl < 0 || counted[sl]) ++changed;
+                }
+            }
+        }
+        if (w) *mw = 0u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) changed += __shfl_xor(changed, o, 64);
+    __shared__ int waveChanged[kTangleBlock / 64];
+    if ((tid & 63) == 0) waveChanged[tid >> 6] = changed;
+    __syncthreads();
+    if (tid == 0) {
+        int sum = 0;
+        for (int w = 0; w < kTangleBlock / 64; ++w) sum += waveChanged[w];
+        if (sum > 0) atomicAdd(reinterpret_cast<unsigned long long*>(&rec->nPointsReverted), (unsigned long long)sum);
+    }
+}
+
+// Closes the record of an iteration from the host's verdict; one wave, lane 0 writes every word in plain C++ (nPointsReverted is
+// the applies': the slot was zeroed before the iteration's first pass).
+__global__ void __launch_bounds__(64) k_tangle_close(smgpu_tangle_record* __restrict__ rec, long long number, int passes, int fullRevert, long long nBadCells) {
+    if (threadIdx.x != 0) return;
+    rec->iteration = number;
+    rec->passes = passes;
+    rec->fullRevert = fullRevert;
+    rec->nBadCells = nBadCells;
+}
+
 }  // namespace smgpu

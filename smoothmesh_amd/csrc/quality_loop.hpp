@@ -224,7 +224,7 @@ int smgpu_quality_guard_restore(smgpu_handle* h) {
     return 0;
 }
 
-// ---- the tangle constraint (kernels_quality_tangle.hpp, DESIGN.md "Mesh quality", 10.12) ----
+// ---- the tangle constraint (kernels_quality_tangle.hpp, DESIGN.md "Mesh quality", 10.12, 10.13) ----
 static int tangleOff(smgpu_handle* h) {
     h->tg.on = false;
     h->tg.slab.discard();
@@ -315,13 +315,154 @@ int smgpu_set_tangle_constraint(smgpu_handle* h, const smgpu_tangle_params* p, i
     h->tg.on = true;
     return 0;
 }
+static int tangleCoupledFlush(smgpu_handle* h);
 int smgpu_get_tangle_records(smgpu_handle* h, smgpu_tangle_record* out, int64_t cap, int64_t* n) {
     if (!h || !n) return fail("null argument");
+    if (h->tg.coupled) {   // the records of the chunk in use are still on the device
+        if (h->tg.k >= 0) return fail("smgpu_get_tangle_records: between the passes of an iteration (smgpu_tangle_pass_begin / _end)");
+        HIP_OK(hipSetDevice(h->device));
+        if (tangleCoupledFlush(h)) return 1;
+    }
     return h->tg.slab.drain(out, cap, n, "smgpu_get_tangle_records");
 }
 int smgpu_get_tangle_state(smgpu_handle* h, smgpu_tangle_state* out) {
     if (!h || !out) return fail("null argument");
-    *out = smgpu_tangle_state{h->tg.on ? 1 : 0, h->tg.passes, h->tg.on ? h->tg.nExempt : 0, h->tg.on ? h->iterCount - h->tg.since : 0};
+    const int64_t number = h->tg.coupled ? h->tg.count : h->iterCount - h->tg.since;
+    *out = smgpu_tangle_state{h->tg.on ? 1 : 0, h->tg.passes, h->tg.on ? h->tg.nExempt : 0, h->tg.on ? number : 0};
+    return 0;
+}
+
+// ---- the coupled form on an engine with a halo (DESIGN.md "Mesh quality", 10.13) ----
+// The passes are the host's calls behind smgpu_iter_end: every kernel below goes onto the engine's stream, behind the
+// iteration's own.  x, the points the iteration started from, is the buffer smgpu_iter_end swapped out; the next launch that
+// writes it is the next iteration's smoothing kernel, queued on the same stream behind the passes.
+static int computeAfterExch(smgpu_handle* h);
+// the records written in the chunk in use become pending; the next iteration starts a zeroed chunk
+static int tangleCoupledFlush(smgpu_handle* h) {
+    TangleHost& t = h->tg;
+    if (t.slabUsed > 0) {
+        if (t.slab.readBack(h->stream, t.slabUsed)) return 1;
+        HIP_OK(hipStreamSynchronize(h->stream));
+        t.slab.keep(t.slabUsed);
+    }
+    t.slabUsed = 0;
+    t.slabFresh = false;
+    return 0;
+}
+int smgpu_set_tangle_constraint_coupled(smgpu_handle* h, const smgpu_tangle_params* p, const smgpu_tangle_halo_desc* d, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return tangleOff(h);
+    const smgpu_tangle_params prm = p ? *p : smgpu_tangle_params{2};
+    if (prm.passes < 0) return fail("smgpu_set_tangle_constraint_coupled: passes < 0");
+    if (!h->haloOn)
+        return fail("smgpu_set_tangle_constraint_coupled: the engine has no halo (smgpu_halo_configure); a serial engine takes smgpu_set_tangle_constraint");
+    if (h->bndOn)
+        return fail("smgpu_set_tangle_constraint_coupled: not available on an engine with boundary point smoothing (it rewrites the proposals of the "
+                    "boundary points from state that a reverted iteration would leave ahead of the points)");
+    if (h->iterOpen) return fail("smgpu_set_tangle_constraint_coupled: between smgpu_iter_begin and smgpu_iter_end");
+    if (!d || (h->nSend && !d->sendT) || (h->nRecv && !d->recvT)) return fail("smgpu_set_tangle_constraint_coupled: null exchange buffer");
+    if (tangleOff(h)) return 1;
+    if (flushDeferred(h)) return 1;
+    const MeshView& m = h->mv;
+    const size_t nMark = ((size_t)std::max(1, m.nPoints) + 3) & ~(size_t)3, nCell = (size_t)std::max(1, m.nCells);
+    TangleHost& t = h->tg;
+    if (t.block.alloc(&t.dev, 1) || t.block.alloc(&t.exempt, nCell) || t.block.alloc(&t.marks, nMark) ||
+        t.block.alloc(&t.counted, (size_t)std::max(1, h->nShared)) ||
+        (!h->useTiles && (t.block.alloc(&t.cellCtr, 3 * nCell) || t.block.alloc(&t.acc, 1))))
+        return t.block.failed("the tangle constraint");
+    HIP_OK(hipMemsetAsync(t.dev, 0, sizeof(TangleDev), h->stream));
+    HIP_OK(hipMemsetAsync(t.exempt, 0, nCell, h->stream));
+    HIP_OK(hipMemsetAsync(t.marks, 0, nMark, h->stream));
+    if (t.acc) HIP_OK(hipMemsetAsync(t.acc, 0, sizeof(Accum), h->stream));
+    if (h->nShared > 0) HIP_OK(hipMemcpyAsync(t.counted, h->sharedMasterHost.data(), (size_t)h->nShared, hipMemcpyHostToDevice, h->stream));
+    // the exempt cells: one evaluation of the current points (copies of a shared point are identical: the global mesh's answer)
+    t.passes = prm.passes;
+    if (tangleEvaluate(h, t.exempt, 0, nullptr)) { t.release(); return 1; }
+    TangleDev td{};
+    HIP_OK(hipMemcpyAsync(&td, t.dev, sizeof(TangleDev), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemsetAsync(t.dev, 0, sizeof(TangleDev), h->stream));
+    if (checkDeviceError(h)) { t.release(); return 1; }
+    t.nExempt = td.badNow;
+    t.sendT = (int*)d->sendT; t.recvT = (int*)d->recvT;
+    t.count = 0;
+    t.k = -1;
+    t.coupled = true;
+    t.on = true;
+    return 0;
+}
+// behind smgpu_iter_end: the iteration waits for its passes
+static void tangleCoupledIterEnd(smgpu_handle* h, const double* x) {
+    h->tg.x = x;
+    h->tg.k = 0;
+    h->tg.reverting = 0;
+    h->tg.passOpen = false;
+}
+int smgpu_tangle_pass_begin(smgpu_handle* h, int64_t* nBadLocal) {
+    if (!h || !nBadLocal) return fail("null argument");
+    TangleHost& t = h->tg;
+    if (!t.coupled) return fail("smgpu_tangle_pass_begin: the coupled tangle constraint is not on (smgpu_set_tangle_constraint_coupled)");
+    if (h->iterOpen) return fail("smgpu_tangle_pass_begin: between smgpu_iter_begin and smgpu_iter_end");
+    if (t.k < 0) return fail("smgpu_tangle_pass_begin: no iteration waits for its passes (the passes follow smgpu_iter_end)");
+    if (t.passOpen) return fail("smgpu_tangle_pass_begin: the pass in hand has not been closed (smgpu_tangle_pass_end)");
+    HIP_OK(hipSetDevice(h->device));
+    if (t.k == 0 && (!t.slabFresh || t.slabUsed >= TangleHost::kChunk)) {
+        if (tangleCoupledFlush(h)) return 1;
+        if (t.slab.begin(h->stream, TangleHost::kChunk)) return 1;
+        t.slabFresh = true;
+    }
+    if (tangleEvaluate(h, nullptr, 0, nullptr)) return 1;
+    if (h->nSend > 0)
+        hipLaunchKernelGGL(k_tangle_pack, dim3((h->nSend + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, h->nSend, (const int*)h->dSendShared,
+                           (const int*)h->dSharedLocal, (const uint8_t*)t.marks, t.sendT);
+    HIP_OK(hipGetLastError());
+    // the one host read of the pass; it also waits for sendT, so whichever stream the host moves T on is ordered behind the pack
+    TangleDev td{};
+    HIP_OK(hipMemcpyAsync(&td, t.dev, sizeof(TangleDev), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemsetAsync(t.dev, 0, sizeof(TangleDev), h->stream));
+    if (checkDeviceError(h)) return 1;
+    if (td.err) return fail("smgpu_tangle_pass_begin: the marks of a geometry tile do not fit the LDS of its points");
+    if (t.k == 0) t.nBad0 = td.badNow;
+    t.passOpen = true;
+    *nBadLocal = td.badNow;
+    return 0;
+}
+int smgpu_tangle_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done) {
+    if (!h || !done) return fail("null argument");
+    TangleHost& t = h->tg;
+    if (!t.coupled) return fail("smgpu_tangle_pass_end: the coupled tangle constraint is not on (smgpu_set_tangle_constraint_coupled)");
+    if (!t.passOpen || t.k < 0) return fail("smgpu_tangle_pass_end without smgpu_tangle_pass_begin");
+    if (nBadGlobal < 0) return fail("smgpu_tangle_pass_end: nBadGlobal < 0");
+    HIP_OK(hipSetDevice(h->device));
+    smgpu_tangle_record* rec = nullptr;
+    if (t.slab.slot(t.slabUsed, &rec)) return 1;
+    const int nP = h->mv.nPoints;
+    const bool full = nBadGlobal > 0 && t.k == t.passes;
+    if (nBadGlobal > 0) {
+        if (!full) {
+            if (computeAfterExch(h)) return 1;      // exchange T has been enqueued by the host
+            if (h->nShared > 0 && h->nRecv > 0)
+                hipLaunchKernelGGL(k_tangle_combine, dim3((h->nShared + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, h->nShared,
+                                   (const int*)h->dSharedLocal, (const int*)h->dCombOff, (const int*)h->dCombSlots, (const int*)t.recvT, t.marks);
+            ++t.reverting;
+        }
+        const int grid = std::max(1, (int)(((int64_t)nP + kTangleCountedPts - 1) / kTangleCountedPts));
+        hipLaunchKernelGGL(k_tangle_apply_counted, dim3(grid), dim3(kTangleBlock), 0, h->stream, t.x, h->st.ptsCur, t.marks, nP, full ? 1 : 0,
+                           (const int*)h->dSharedSlot, (const uint8_t*)t.counted, rec);
+        // points went back: the geometry smgpu_iter_ahead left for the next iteration is that of other points
+        h->geomAheadDone = false;
+        h->q.epoch++;
+    }
+    const bool close = nBadGlobal == 0 || full;
+    if (close) {
+        hipLaunchKernelGGL(k_tangle_close, dim3(1), dim3(64), 0, h->stream, rec, (long long)(t.count + 1), t.reverting, full ? 1 : 0, (long long)t.nBad0);
+        ++t.count;
+        ++t.slabUsed;
+        t.k = -1;
+    } else ++t.k;
+    t.passOpen = false;
+    *done = close ? 1 : 0;
+    HIP_OK(hipGetLastError());
     return 0;
 }
 

@@ -172,5 +172,17 @@ struct TangleHost {
     double* cellCtr = nullptr;
     Accum* acc = nullptr;
     RecordSlab<smgpu_tangle_record> slab{"tangle constraint"};       // one record per iteration of the call
-    void release() { block.release(); slab.release(); }
+    // the coupled form (smgpu_set_tangle_constraint_coupled, 10.13) on an engine with a halo.  The host drives the passes, so the
+    // state of the iteration in hand lives here: x (the buffer that holds the points the iteration started from), the pass
+    // counter k (-1: no iteration waits for its passes), the reverting passes so far, the rank's count at k = 0.  count: the
+    // iterations closed since enabling (smgpu_handle::iterCount does not move under a halo).  The slab is used in chunks of
+    // kChunk records: slabUsed of them are written, slabFresh says the chunk has been zeroed and nothing of it read back.
+    static constexpr int kChunk = 256;
+    bool coupled = false, passOpen = false, slabFresh = false;
+    int k = -1, reverting = 0, slabUsed = 0;
+    int64_t count = 0, nBad0 = 0;
+    const double* x = nullptr;
+    uint8_t* counted = nullptr;             // one byte per shared point: 0 where a lower rank shares it (nPointsReverted)
+    int *sendT = nullptr, *recvT = nullptr; // the caller's exchange buffers (device, nSend / nRecv int32)
+    void release() { block.release(); slab.release(); coupled = passOpen = slabFresh = false; k = -1; slabUsed = 0; }
 };

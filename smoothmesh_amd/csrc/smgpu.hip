@@ -89,6 +89,7 @@ struct smgpu_handle {
     int nMulti = 0;
     double *dOwnL = nullptr, *dCombL = nullptr, *sendL = nullptr, *recvL = nullptr;   // boundary layer treatment under -parallel
     std::vector<int> sharedLocalHost;
+    std::vector<uint8_t> sharedMasterHost;      // per shared point: this rank is its lowest-rank sharer
     std::unique_ptr<LayerBuilder> lb;                                                  // set-up in progress
     std::vector<double> lbArea;
     std::vector<uint8_t> lbInternal;
@@ -2254,6 +2255,8 @@ int smgpu_halo_configure(smgpu_handle* h, const smgpu_halo_desc* d) {
     h->sendA = (double*)d->sendA; h->recvA = (double*)d->recvA;
     h->sendL = (double*)d->sendL; h->recvL = (double*)d->recvL;
     h->sharedLocalHost = sharedLocal;
+    h->sharedMasterHost.assign((size_t)d->nShared, 0);      // the lowest-rank sharer: the first entry of the comb row is this rank
+    for (int i = 0; i < d->nShared; ++i) h->sharedMasterHost[(size_t)i] = (combOff[(size_t)i + 1] > combOff[(size_t)i] && combSlots[(size_t)combOff[(size_t)i]] == -1) ? 1 : 0;
     {
         std::vector<int> multi;
         bool tooMany = false;
@@ -2679,6 +2682,8 @@ static int runMergedSmooth(smgpu_handle* h) {
 int smgpu_iter_begin(smgpu_handle* h) {
     if (!h || !h->haloOn) return fail("halo not configured");
     if (!h->prmSet) return fail("smgpu_set_params has not been called");
+    if (h->tg.coupled && h->tg.k >= 0)
+        return fail("smgpu_iter_begin: the coupled tangle constraint has not finished the passes of the last iteration (smgpu_tangle_pass_begin / _end)");
     h->q.epoch++;
     h->iterOpen = true;
     HIP_OK(hipSetDevice(h->device));
@@ -2882,6 +2887,8 @@ int smgpu_iter_end(smgpu_handle* h) {
     } else if (launchK(h, K_FINISH, [&] { hipLaunchKernelGGL(k_finish, dim3(1), dim3(kFinishBlock), 0, h->stream, s, nPart, h->haloIter, -1.0, h->localStats, hist); })) return 1;
     if (swapHalo) std::swap(h->st.ptsCur, h->st.prop);      // the proposal array is the next coordinates (k_apply_swap restored the points that stay)
     else std::swap(h->st.ptsCur, h->st.ptsNext);
+    // the coupled tangle constraint: the buffer just swapped out holds x, the points the iteration started from
+    if (h->tg.coupled) tangleCoupledIterEnd(h, swapHalo ? h->st.prop : h->st.ptsNext);
     h->haloIter++;
     h->interiorDone = false;
     // (flagged arrangement with a stats history: nobody reads localStats per iteration, and an exchange stream that waited for the
@@ -3043,6 +3050,7 @@ int smgpu_boundary_begin(smgpu_handle* h, const smgpu_boundary_desc* d, double m
         (d->nSurfaceTriangles && (!d->surfaceTriangles || !d->surfacePoints)))
         return fail("smgpu_boundary_begin: null geometry array");
     HIP_OK(hipSetDevice(h->device));
+    if (h->tg.coupled) return fail("smgpu_boundary_begin: the coupled tangle constraint is on (smgpu_set_tangle_constraint_coupled), and it is not available on an engine with boundary point smoothing; switch it off first");
     const Topology& t = h->topo;
     h->bndOn = false;
     h->bndPending = false;

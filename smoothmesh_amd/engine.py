@@ -634,8 +634,28 @@ class SmoothEngine:
         self._check(self._lib.smgpu_set_tangle_constraint(self._h, C.byref(p), 1))
 
     def clear_tangle_constraint(self):
-        """Switch the tangle constraint off; discards unread records."""
+        """Switch the tangle constraint (either form) off; discards unread records."""
         self._check(self._lib.smgpu_set_tangle_constraint(self._h, None, 0))
+
+    def set_tangle_constraint_coupled(self, sendT, recvT, passes=2):
+        """The tangle constraint on an engine with a halo (include/smgpu.h, smgpu_set_tangle_constraint_coupled; DESIGN.md "Mesh
+        quality", 10.13).  sendT / recvT: raw device addresses (ints) of nSend / nRecv int32 the caller owns and moves like
+        exchange F.  The passes are the caller's: tangle_pass_begin / tangle_pass_end behind every iter_end."""
+        p = _ffi.TangleParams(int(passes))
+        d = _ffi.TangleHaloDesc(sendT, recvT)
+        self._check(self._lib.smgpu_set_tangle_constraint_coupled(self._h, C.byref(p), C.byref(d), 1))
+
+    def tangle_pass_begin(self) -> int:
+        """evaluates the points, packs the shared points' marks into sendT; this rank's bad cells that are not exempt"""
+        n = C.c_int64(0)
+        self._check(self._lib.smgpu_tangle_pass_begin(self._h, C.byref(n)))
+        return n.value
+
+    def tangle_pass_end(self, nBadGlobal) -> bool:
+        """the pass's revert under the verdict on the all-rank count; True: the iteration's passes are over"""
+        done = C.c_int32(0)
+        self._check(self._lib.smgpu_tangle_pass_end(self._h, int(nBadGlobal), C.byref(done)))
+        return bool(done.value)
 
     def tangle_records(self) -> list:
         """The pending records of the tangle constraint, one per iteration that ran, in ascending iteration; clears them."""

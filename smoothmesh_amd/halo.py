@@ -183,6 +183,20 @@ def setup_boundary_stepwise(engines, exchange, reduce_stats, bp, minEdgeLength, 
     return infos
 
 
+def combine_tangle_records(per_rank):
+    """the records of the undecomposed mesh from every rank's (DESIGN.md "Mesh quality", 10.13): `passes` and `fullRevert` are
+    global values, the same on every rank; nBadCells and nPointsReverted are sums (a shared point counts on its master only)"""
+    from .engine import TangleRecord
+    out = []
+    for recs in zip(*per_rank):
+        r0 = recs[0]
+        assert all((r.iteration, r.passes, r.fullRevert) == (r0.iteration, r0.passes, r0.fullRevert) for r in recs), recs
+        out.append(TangleRecord(iteration=r0.iteration, passes=r0.passes, fullRevert=r0.fullRevert, nBadCells=sum(r.nBadCells for r in recs),
+                                nPointsReverted=sum(r.nPointsReverted for r in recs)))
+    assert all(len(r) == len(per_rank[0]) for r in per_rank)
+    return out
+
+
 def l_view(t, width):
     """the exchange-L records in use: `width` doubles per slot, packed from the start of the (slots, L_DOUBLES) buffer"""
     n = t.shape[0]
@@ -324,6 +338,8 @@ class DistributedSmoother:
             self._probe = {torch.float64: z((self.probe_slots, A_DOUBLES), torch.float64), torch.int32: z((self.probe_slots,), torch.int32),
                            "L": z((self.probe_slots, L_DOUBLES), torch.float64)}
         self.direct = self._open_direct(engine_factory is None)
+        self.tangle_passes = None     # set_tangle_constraint: the passes behind every iter_end
+        self._tangle_err = None
 
     def _open_push(self):
         """exchange the IPC handles and slot counts, map the peers' buffers, describe them to the engine"""
@@ -515,16 +531,18 @@ class DistributedSmoother:
         # cannot, so device tensors are staged through the host for it
         return self.dist.get_backend() == "gloo" and self.device.type != "cpu"
 
-    def _a2a(self, recv, send, overlap=None):
+    def _a2a(self, recv, send, overlap=None, host=False):
         """all_to_all of the packed shared-point records on torch's current stream (= the engine's exchange
         stream), then `overlap` (smgpu_iter_interior / smgpu_iter_ahead: the kernels that do not need the
         exchanged data) on the engine's own stream.  The engine orders the two streams with events inside
         smgpu_iter_begin/mid/end, so compute never leaves its queue and the host only pays for the collective
         call (~17 us on this stack; async_op=True + wait() costs ~70 us, torch stream contexts ~40 us)."""
-        if self.pushbuf is not None:      # peer-store transport: the kernels have moved the records themselves
+        if self.pushbuf is not None and not host:      # peer-store transport: the kernels have moved the records themselves
             if overlap:
                 overlap()
             return
+        # (host: records no kernel stores into a peer -- the marks of the tangle constraint -- travel by the collective under
+        # every transport; with peer stores there is no send / recv communicator, so `collective` below holds)
         n = self.tables.nSend
         counts = self.counts
         if self.world == 1 and self.probe_slots:
@@ -579,13 +597,15 @@ class DistributedSmoother:
             self._a2a(l_view(st.recvL, eng.l_doubles()), l_view(st.sendL, eng.l_doubles()))   # OBB.C:184-198, 490-496
         self._a2a(st.recvA, st.sendA, overlap)   # SM.C:134-148, 402-478
 
-    def _agree_on_error(self):
+    def _agree_on_error(self, err=None):
         """Wait for the engine's stream, read its error word (include/smgpu.h) and let EVERY rank raise when any rank has one: a
         rank raising on its own would leave the others inside the next collective.  The engine clears the word once it has been
-        reported, so the handle keeps a sticky `had_error` for later readers (transport_info, bench.py)."""
+        reported, so the handle keeps a sticky `had_error` for later readers (transport_info, bench.py).  err: what this rank has
+        already caught (a pass of the tangle constraint), or what it caught earlier and carried to this point."""
         torch, eng = self.torch, self.engine
-        err = None
-        if hasattr(eng, "check_error"):
+        if err is None:
+            err, self._tangle_err = self._tangle_err, None
+        if err is None and hasattr(eng, "check_error"):
             try:
                 eng.check_error()
             except Exception as ex:  # noqa: BLE001 -- re-raised below, on every rank
@@ -672,6 +692,7 @@ class DistributedSmoother:
                 eng.iter_mid()
                 self._a2a(st.recvF, st.sendF, eng.iter_ahead)   # SM.C:2374
                 eng.iter_end()
+                self._tangle_passes()
                 self._agree_on_error()                      # (this branch reads the residual on the host every iteration anyway)
                 self._gather_stats()                        # SM.C:1567, 2396
                 hist[i, 0] = self.allStats[:, 0].max()
@@ -687,11 +708,18 @@ class DistributedSmoother:
         local = torch.zeros((n, 2), dtype=torch.float64, device=self.device)
         eng.set_stats_history(local.data_ptr(), n)      # iter_end fills record i: no per-iteration copy
         for i in range(centroidalIters):
-            eng.iter_begin()
-            self._a2a_LA(eng.iter_interior)
-            eng.iter_mid()
-            self._a2a(st.recvF, st.sendF, eng.iter_ahead)
-            eng.iter_end()
+            # (a rank that carries an error of the tangle constraint's last pass leaves its engine alone and answers the
+            # collectives until the next pass's reduction, where every rank learns of it)
+            live = self._tangle_err is None
+            if live:
+                eng.iter_begin()
+            self._a2a_LA(eng.iter_interior if live else None)
+            if live:
+                eng.iter_mid()
+            self._a2a(st.recvF, st.sendF, eng.iter_ahead if live else None)
+            if live:
+                eng.iter_end()
+            self._tangle_passes()
             done += 1
         eng.set_stats_history(None, 0)
         # an error word raised by a kernel of this call (a peer's records that never came, a point without usable neighbours): every
@@ -708,6 +736,75 @@ class DistributedSmoother:
 
     def get_points(self):
         return self.engine.get_points()
+
+    # -- the tangle constraint on the decomposed mesh (include/smgpu.h smgpu_set_tangle_constraint_coupled) --
+    def set_tangle_constraint(self, passes=2):
+        """From now on iterate() puts the points of every cell that its move turned bad back, on every rank that holds them:
+        behind every iter_end, up to `passes` marked passes (the marks of shared points travel like exchange F) and then the
+        full revert, under a verdict on the all-rank count (one all_reduce per pass).  Every rank calls it."""
+        torch, st = self.torch, self.state
+        st.sendT = torch.zeros(max(self.tables.nSend, 1), dtype=torch.int32, device=self.device)
+        st.recvT = torch.zeros(max(self.tables.nRecv, 1), dtype=torch.int32, device=self.device)
+        self.tangle_passes = None
+        self.engine.set_tangle_constraint_coupled(st.sendT.data_ptr(), st.recvT.data_ptr(), passes)
+        self.tangle_passes = int(passes)
+
+    def clear_tangle_constraint(self):
+        self.tangle_passes = None
+        self.engine.clear_tangle_constraint()
+
+    def tangle_state(self):
+        """TangleState of the decomposed mesh: nExemptCells summed over the ranks.  A collective."""
+        s = self.engine.tangle_state()
+        t = self.torch.tensor([s.nExemptCells], dtype=self.torch.int64, device="cpu" if self._staged() else self.device)
+        if self.world > 1:
+            self.dist.all_reduce(t)
+        s.nExemptCells = int(t.item())
+        return s
+
+    def tangle_records(self, per_rank=False):
+        """The pending records, cleared by the read: those of the undecomposed mesh (combine_tangle_records), or with per_rank
+        one list per rank.  A collective: every rank calls it and gets the same answer."""
+        mine = self.engine.tangle_records()
+        everyone = [None] * self.world
+        if self.world > 1:
+            self.dist.all_gather_object(everyone, mine)
+        else:
+            everyone = [mine]
+        return everyone if per_rank else combine_tangle_records(everyone)
+
+    def _tangle_passes(self):
+        """the passes of the iteration iter_end has just closed: per pass one host read (the rank's count), one all_reduce of
+        {count, failed} and, while cells are bad and the pass is not the last, exchange T (the host's exchange under every
+        transport: no kernel stores marks into a peer).  A rank on which a call of a pass fails keeps the error, goes on
+        answering the collectives without touching its engine, and reports failed = 1 in the next reduction; every rank then
+        raises through _agree_on_error.  The host knows the verdict itself, so a failed rank leaves the loop when the others do."""
+        if self.tangle_passes is None:
+            return
+        torch, st, eng = self.torch, self.state, self.engine
+        dev = "cpu" if (self._staged() or self.device.type == "cpu") else self.device
+        for k in range(self.tangle_passes + 1):
+            nb = 0
+            if self._tangle_err is None:
+                try:
+                    nb = eng.tangle_pass_begin()
+                except Exception as ex:  # noqa: BLE001 -- re-raised below, on every rank
+                    self._tangle_err = ex
+            v = torch.tensor([nb, 0 if self._tangle_err is None else 1], dtype=torch.int64, device=dev)
+            if self.world > 1:
+                self.dist.all_reduce(v)
+            total, failed = (int(x) for x in v.tolist())
+            if failed:
+                err, self._tangle_err = self._tangle_err, None
+                self._agree_on_error(err if err is not None else RuntimeError("another rank failed inside a pass of the tangle constraint (see its message)"))
+            if total > 0 and k < self.tangle_passes:
+                self._a2a(st.recvT, st.sendT, host=True)
+            try:
+                eng.tangle_pass_end(total)
+            except Exception as ex:  # noqa: BLE001 -- carried to the next reduction or agreement point
+                self._tangle_err = ex
+            if total == 0 or k == self.tangle_passes:
+                return
 
     def _quality_exchange(self, volumes=False):
         """pack, then every processor patch's owner cell centres to the neighbour and theirs back (one all_to_all_single, staged
@@ -838,6 +935,7 @@ class LocalMultiSmoother:
         self.torch = torch
         self.subs = subs
         self.own_fold = own_fold_default()
+        self.tangle_passes = None     # set_tangle_constraint: the passes behind every iter_end
         if torch_device is None:
             torch_device = torch.device("cuda", device)
         self.device = torch_device
@@ -930,6 +1028,7 @@ class LocalMultiSmoother:
             self._exchange("F")
             for st in self.states:
                 st.eng.iter_end()
+            self._tangle_passes()
             allst = self.torch.stack([st.localStats for st in self.states]).cpu().numpy()
             res.append(float(allst[:, 0].max()))
             frz.append(int(allst[:, 1].sum()))
@@ -939,6 +1038,44 @@ class LocalMultiSmoother:
 
     def get_points(self):
         return [st.eng.get_points() for st in self.states]
+
+    # -- the tangle constraint on the decomposed mesh (include/smgpu.h smgpu_set_tangle_constraint_coupled) --
+    def set_tangle_constraint(self, passes=2):
+        """as DistributedSmoother.set_tangle_constraint; the marks of shared points move by the device-side copies of the exchanges"""
+        torch = self.torch
+        self.tangle_passes = None
+        for st in self.states:
+            st.sendT = torch.zeros(max(st.t.nSend, 1), dtype=torch.int32, device=self.device)
+            st.recvT = torch.zeros(max(st.t.nRecv, 1), dtype=torch.int32, device=self.device)
+            st.eng.set_tangle_constraint_coupled(st.sendT.data_ptr(), st.recvT.data_ptr(), passes)
+        self.tangle_passes = int(passes)
+
+    def clear_tangle_constraint(self):
+        self.tangle_passes = None
+        for st in self.states:
+            st.eng.clear_tangle_constraint()
+
+    def tangle_state(self):
+        """TangleState of the decomposed mesh: nExemptCells summed over the ranks"""
+        ss = [st.eng.tangle_state() for st in self.states]
+        ss[0].nExemptCells = sum(s.nExemptCells for s in ss)
+        return ss[0]
+
+    def tangle_records(self, per_rank=False):
+        """The pending records, cleared by the read: those of the undecomposed mesh, or with per_rank one list per rank"""
+        everyone = [st.eng.tangle_records() for st in self.states]
+        return everyone if per_rank else combine_tangle_records(everyone)
+
+    def _tangle_passes(self):
+        """the passes of the iteration iter_end has just closed on every engine: the verdict on the summed count"""
+        if self.tangle_passes is None:
+            return
+        for k in range(self.tangle_passes + 1):
+            total = sum([st.eng.tangle_pass_begin() for st in self.states])
+            if total > 0 and k < self.tangle_passes:
+                self._exchange("T")
+            if all([st.eng.tangle_pass_end(total) for st in self.states]):
+                return
 
     # The reports of the decomposed mesh at the current points (smoothmesh_amd/quality.py, DESIGN.md 10.4, 10.5, 10.8, 10.9): the cell
     # centres (and volumes) of the processor faces move between the engines' buffers by device-side copies.  Ids are global where
