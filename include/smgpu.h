@@ -350,6 +350,73 @@ int smgpu_set_tangle_constraint_coupled(smgpu_handle* h, const smgpu_tangle_para
 int smgpu_tangle_pass_begin(smgpu_handle* h, int64_t* nBadLocal);                 /* after smgpu_iter_end */
 int smgpu_tangle_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done);
 
+/* ---- the quality constraint (DESIGN.md "Mesh quality", 10.14) --------------------------------------------------------------
+ * The tangle constraint with up to three more criteria, taken from meshQualityDict: a point also stays at its current coordinates
+ * when its move would push a face's non-orthogonality or skewness over a limit.  Opt-in, serial only (an engine without a halo);
+ * with it off nothing the engine launches, prints or returns changes.
+ *
+ * Notation is the tangle constraint's (10.12): x are the points an iteration starts from, x' the points the loop produced, C_f,
+ * S_f, C_c the engine's geometry of a set of points under the current foam variant.  ortho_f and skew_f are the report's values
+ * (10.1) with the same operands and operation order as k_quality_faces; ortho_f exists for internal faces only, and the boundary
+ * form of d applies to skew_f on boundary faces.
+ *
+ * PARAMETERS.  passes: an integer >= 0, default 2.  maxNonOrtho: degrees, default 65; a value >= 180 switches the criterion off.
+ * maxInternalSkewness: default 4; a value <= 0 switches it off.  maxBoundarySkewness: default 20; a value <= 0 switches it off.
+ * cosT = cos(maxNonOrtho) is formed exactly as the report forms its cosine: cos(maxNonOrtho * (pi / 180)) in double on the host.
+ *
+ * A face is BAD when it is internal and ortho_f < cosT (this includes ortho_f <= 0), or internal and skew_f > maxInternalSkewness,
+ * or a boundary face and skew_f > maxBoundarySkewness.
+ * A cell is BAD when 10.12's definition applies (V_c <= VSMALL or an own-side pyramid <= 0), or when it is the owner or the
+ * neighbour of a bad face that is not exempt.
+ *
+ * EXEMPTION.  Enabling evaluates the current points once.  The cells bad there by 10.12's definition are exempt, as they are
+ * under the tangle constraint; the faces bad there are exempt.  An exemption lasts for as long as the constraint stays on, even
+ * if the element heals.  Exempt cells never count through their own volume or pyramids; exempt faces never make a cell bad.  A
+ * cell that is exempt as a cell can still be bad through a bad face that is not exempt.
+ *
+ * Per iteration that ran, behind its movePoints, the loop is 10.12's with B = the bad cells of this definition:
+ *   for k = 0 .. passes:  B empty: stop;  k == passes: x' = x everywhere (the FULL REVERT);
+ *                         otherwise x'_p = x_p for every point p of every face of every cell in B.
+ * Reverting all points of a bad face's owner and neighbour restores that face's C_O, C_N, C_f and S_f to their bits at x, so
+ * 10.12's INVARIANT carries over: if no non-exempt face or cell is bad at x, none is bad at the accepted x'.
+ * EQUIVALENCE.  With all three criteria off the accepted points of every iteration are bit for bit the tangle constraint's, and
+ * so are passes, fullRevert, nBadCells and nPointsReverted.
+ *
+ * Unchanged from 10.12: residual and nFrozenPoints keep the loop's own values; the trace and the guard see the accepted points
+ * and their launches are queued behind the constraint's; no host synchronisation enters the loop; every launch is gated on the
+ * written bit of the iteration's statistics and on the "clean" word; a guard rollback takes the running number back.
+ *
+ * One smgpu_quality_constraint_record per iteration that ran: iteration, passes, fullRevert, nPointsReverted with 10.12's
+ * meaning; nBadCells: |B| at k = 0, each cell counted once; nTangledCells: the cells bad by 10.12's definition alone at k = 0;
+ * nNonOrthoFaces / nSkewFaces: the bad faces that are not exempt at k = 0 by the non-orthogonality criterion / by the skewness
+ * criteria (a face that fails both counts in both).  smgpu_get_quality_constraint_records has the semantics of
+ * smgpu_get_tangle_records.  The record begins with smgpu_tangle_record's five fields at the same offsets.
+ *
+ * Refused: a halo, boundary point smoothing, passes < 0 (10.12's refusals, in their wording); a NaN limit; enabling while the
+ * tangle constraint is on, and enabling the tangle constraint while this one is on; smgpu_halo_configure and
+ * smgpu_set_boundary_smoothing while it is on.  Layers, both foam variants, the trace and the guard go together with it.
+ * Memory, allocated at enabling outside deviceBytes: 3 nCells + nFaces + nPoints bytes, 24 nCells bytes of cell centres, the
+ * report's owner / neighbour lists if no report has made them (4 (nFaces + nInternalFaces) bytes), and 56 bytes per iteration of
+ * the longest call.  p == NULL: the defaults.  on == 0 switches it off, discards unread records and frees its memory. */
+typedef struct smgpu_quality_constraint_params {
+    double maxNonOrtho, maxInternalSkewness, maxBoundarySkewness;
+    int32_t passes;
+} smgpu_quality_constraint_params;            /* NULL params = {65, 4, 20, 2} */
+typedef struct smgpu_quality_constraint_record {
+    int64_t iteration;                      /* 1-based running number since smgpu_set_quality_constraint */
+    int32_t passes, fullRevert;
+    int64_t nBadCells, nPointsReverted;
+    int64_t nTangledCells, nNonOrthoFaces, nSkewFaces;
+} smgpu_quality_constraint_record;
+typedef struct smgpu_quality_constraint_state {
+    int32_t on, passes;
+    double maxNonOrtho, maxInternalSkewness, maxBoundarySkewness;
+    int64_t nExemptCells, nExemptFaces, iteration;
+} smgpu_quality_constraint_state;
+int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint_params* p, int32_t on);
+int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n);
+int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint_state* out);
+
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):
  *   1. smgpu_quality_coupled_pack: the geometry of the current points (the loop's own launch, uncounted), then the owner cell

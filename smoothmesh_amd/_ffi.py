@@ -143,6 +143,23 @@ class TangleState(C.Structure):
     _fields_ = [("on", C.c_int32), ("passes", C.c_int32), ("nExemptCells", C.c_int64), ("iteration", C.c_int64)]
 
 
+class QualityConstraintParams(C.Structure):
+    """smgpu_quality_constraint_params"""
+    _fields_ = [("maxNonOrtho", C.c_double), ("maxInternalSkewness", C.c_double), ("maxBoundarySkewness", C.c_double), ("passes", C.c_int32)]
+
+
+class QualityConstraintRecord(C.Structure):
+    """smgpu_quality_constraint_record"""
+    _fields_ = [("iteration", C.c_int64), ("passes", C.c_int32), ("fullRevert", C.c_int32), ("nBadCells", C.c_int64),
+                ("nPointsReverted", C.c_int64), ("nTangledCells", C.c_int64), ("nNonOrthoFaces", C.c_int64), ("nSkewFaces", C.c_int64)]
+
+
+class QualityConstraintState(C.Structure):
+    """smgpu_quality_constraint_state"""
+    _fields_ = [("on", C.c_int32), ("passes", C.c_int32), ("maxNonOrtho", C.c_double), ("maxInternalSkewness", C.c_double),
+                ("maxBoundarySkewness", C.c_double), ("nExemptCells", C.c_int64), ("nExemptFaces", C.c_int64), ("iteration", C.c_int64)]
+
+
 class TangleHaloDesc(C.Structure):
     """smgpu_tangle_halo_desc"""
     _fields_ = [("sendT", C.c_void_p), ("recvT", C.c_void_p)]
@@ -267,6 +284,9 @@ SYMBOLS = {
     "smgpu_set_tangle_constraint_coupled": (C.c_int, [C.c_void_p, C.POINTER(TangleParams), C.POINTER(TangleHaloDesc), C.c_int32]),
     "smgpu_tangle_pass_begin": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "smgpu_tangle_pass_end": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
+    "smgpu_set_quality_constraint": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintParams), C.c_int32]),
+    "smgpu_get_quality_constraint_records": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintRecord), C.c_int64, C.POINTER(C.c_int64)]),
+    "smgpu_get_quality_constraint_state": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintState)]),
     "smgpu_quality_coupled_pack": (C.c_int, [C.c_void_p, C.POINTER(QualityCoupling), C.c_void_p, C.POINTER(C.c_int64)]),
     "smgpu_quality_coupled_report": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(QualityPart)]),
     "smgpu_quality_coupled_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),

@@ -96,7 +96,8 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "layerMaxBlendingFraction", "layerEdgeLength", "layerExpansionRatio", "minLayers",
                                "maxLayers", "layerPatches", "smoothingPatches", "internalSmoothingBlendingFraction",
                                "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets", "allGeometry",
-                               "meshQuality", "qualityInterval", "qualityGuard", "qualityGuardRefine", "tangleConstraint", "tanglePasses"};
+                               "meshQuality", "qualityInterval", "qualityGuard", "qualityGuardRefine", "tangleConstraint", "tanglePasses",
+                               "qualityConstraint", "maxNonOrtho", "maxInternalSkewness", "maxBoundarySkewness", "qualityConstraintPasses"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -122,6 +123,11 @@ Options parseArgs(int argc, char** argv) {
                       "       [-tangleConstraint b] (freeze, iteration by iteration, the points whose move would turn a cell's volume non-positive\n"
                       "        or a face wrongly oriented; cells that are bad in the initial mesh are exempt; serial runs only)\n"
                       "       [-tanglePasses n]   (with -tangleConstraint: marked passes per iteration before the whole iteration is reverted, default 2)\n"
+                      "       [-qualityConstraint b] (the tangle constraint, and freeze the points whose move would push a face over a limit of\n"
+                      "        meshQualityDict; cells and faces that are bad in the initial mesh are exempt; serial runs only, not with -tangleConstraint)\n"
+                      "       [-maxNonOrtho deg -maxInternalSkewness x -maxBoundarySkewness x]  (with -qualityConstraint: the limits, defaults 65, 4, 20;\n"
+                      "        maxNonOrtho >= 180 or a skewness limit <= 0 switches that criterion off)\n"
+                      "       [-qualityConstraintPasses n]  (with -qualityConstraint: marked passes per iteration before the whole iteration is reverted, default 2)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -550,6 +556,18 @@ int main(int argc, char** argv) {
         fatal("-tangleConstraint is not available with -parallel: it judges the cells by the measure of the quality report, which is serial only");
     if (opt.found("tanglePasses") && !tangleConstraint) fatal("-tanglePasses needs -tangleConstraint true");
     if (tangleConstraint && (tanglePasses < 0 || tanglePasses > 0x7fffffffL)) fatal("tanglePasses must be between 0 and 2147483647");
+    const bool qualityConstraint = opt.getB("qualityConstraint", false);
+    const double qcMaxNonOrtho = opt.getD("maxNonOrtho", 65.0), qcMaxInternalSkewness = opt.getD("maxInternalSkewness", 4.0),
+                 qcMaxBoundarySkewness = opt.getD("maxBoundarySkewness", 20.0);
+    const long qcPasses = opt.getL("qualityConstraintPasses", 2);
+    for (const char* k : {"maxNonOrtho", "maxInternalSkewness", "maxBoundarySkewness", "qualityConstraintPasses"})
+        if (opt.found(k) && !qualityConstraint) fatal(std::string("-") + k + " needs -qualityConstraint true");
+    if (qualityConstraint && opt.parallel)
+        fatal("-qualityConstraint is not available with -parallel: it judges the faces and cells by the measure of the quality report, which is serial only");
+    if (qualityConstraint && tangleConstraint) fatal("-qualityConstraint is not available with -tangleConstraint true: it contains the tangle constraint");
+    if (qualityConstraint && (qcPasses < 0 || qcPasses > 0x7fffffffL)) fatal("qualityConstraintPasses must be between 0 and 2147483647");
+    if (qualityConstraint && (qcMaxNonOrtho != qcMaxNonOrtho || qcMaxInternalSkewness != qcMaxInternalSkewness || qcMaxBoundarySkewness != qcMaxBoundarySkewness))
+        fatal("-maxNonOrtho, -maxInternalSkewness and -maxBoundarySkewness must be numbers");
     // SMOOTHMESH_TIMELINE=1: where this process's wall time goes, one stderr line per stage (seconds since main started)
     const bool timeline = std::getenv("SMOOTHMESH_TIMELINE") && std::atoi(std::getenv("SMOOTHMESH_TIMELINE")) > 0;
     auto mark = [&](const char* what) { if (timeline) std::fprintf(stderr, "[smoothMesh %8.3f s] %s\n", secondsSince(t0), what); };
@@ -735,6 +753,9 @@ int main(int argc, char** argv) {
               "its corner lists are not part of the guard's snapshot (run without -smoothingPatches, or without the guard)");
     if (tangleConstraint && doBoundarySmoothing)
         fatal("-tangleConstraint is not available with boundary point smoothing: it rewrites the boundary points from state that a reverted "
+              "iteration would leave ahead of the points (run without -smoothingPatches, or without the constraint)");
+    if (qualityConstraint && doBoundarySmoothing)
+        fatal("-qualityConstraint is not available with boundary point smoothing: it rewrites the boundary points from state that a reverted "
               "iteration would leave ahead of the points (run without -smoothingPatches, or without the constraint)");
     if (doLayerTreatment && !doBoundarySmoothing)   // SM.C:2095-2098
         OUTS("WARNING: Boundary layer treatment will be done without boundary point smoothing. This can result in distorted boundary cells.\n");
@@ -1271,6 +1292,16 @@ int main(int argc, char** argv) {
         check(smgpu_get_tangle_state(R[0].h, &ts), "smgpu_get_tangle_state");
         OUT("Tangle constraint: %lld exempt cells, %d passes\n", (long long)ts.nExemptCells, (int)ts.passes);
     }
+    // -qualityConstraint: the same with limits on non-orthogonality and skewness (smgpu_set_quality_constraint)
+    std::vector<smgpu_quality_constraint_record> qcRecords;
+    if (qualityConstraint) {
+        const smgpu_quality_constraint_params qp{qcMaxNonOrtho, qcMaxInternalSkewness, qcMaxBoundarySkewness, (int32_t)qcPasses};
+        check(smgpu_set_quality_constraint(R[0].h, &qp, 1), "smgpu_set_quality_constraint");
+        smgpu_quality_constraint_state qs{};
+        check(smgpu_get_quality_constraint_state(R[0].h, &qs), "smgpu_get_quality_constraint_state");
+        OUT("Quality constraint: maxNonOrtho %g maxInternalSkewness %g maxBoundarySkewness %g, %lld exempt cells, %lld exempt faces, %d passes\n", qs.maxNonOrtho,
+            qs.maxInternalSkewness, qs.maxBoundarySkewness, (long long)qs.nExemptCells, (long long)qs.nExemptFaces, (int)qs.passes);
+    }
     // -qualityGuard: the guard on that history (include/smgpu.h, smgpu_set_quality_guard), armed on the initial
     // points with everything set up: the engine stops the loop on the device and rolls the points back itself
     if (qualityGuard) {
@@ -1357,12 +1388,26 @@ int main(int argc, char** argv) {
             tangle.resize((size_t)nRecords);
             if (nRecords > 0) check(smgpu_get_tangle_records(R[0].h, tangle.data(), nRecords, &nRecords), "smgpu_get_tangle_records");
         }
+        size_t nextQc = 0;
+        if (qualityConstraint) {
+            int64_t nRecords = 0;
+            check(smgpu_get_quality_constraint_records(R[0].h, nullptr, 0, &nRecords), "smgpu_get_quality_constraint_records");
+            qcRecords.resize((size_t)nRecords);
+            if (nRecords > 0) check(smgpu_get_quality_constraint_records(R[0].h, qcRecords.data(), nRecords, &nRecords), "smgpu_get_quality_constraint_records");
+        }
         for (int32_t k = 0; k < done; ++k) {
             OUT("Smoothing iteration=%ld nFrozenPoints=%d residual=%g\n", i + k + 1, stats[(size_t)k].nFrozenPoints, stats[(size_t)k].residual);
             if (nextTangle < tangle.size() && tangle[nextTangle].iteration == (int64_t)(i + k + 1)) {
                 const smgpu_tangle_record& t = tangle[nextTangle++];
                 if (t.nBadCells > 0)
                     OUT("    tangle iteration=%lld badCells %lld passes %d pointsReverted %lld%s\n", (long long)t.iteration, (long long)t.nBadCells,
+                        (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
+            }
+            if (nextQc < qcRecords.size() && qcRecords[nextQc].iteration == (int64_t)(i + k + 1)) {
+                const smgpu_quality_constraint_record& t = qcRecords[nextQc++];
+                if (t.nBadCells > 0)
+                    OUT("    quality constraint iteration=%lld badCells %lld tangled %lld nonOrthoFaces %lld skewFaces %lld passes %d pointsReverted %lld%s\n",
+                        (long long)t.iteration, (long long)t.nBadCells, (long long)t.nTangledCells, (long long)t.nNonOrthoFaces, (long long)t.nSkewFaces,
                         (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
             }
             if (!qualityTrace || nextRecord >= trace.size() || trace[nextRecord].iteration != (int64_t)(i + k + 1)) continue;

@@ -1,6 +1,6 @@
-// quality_loop.hpp -- the mesh quality features that follow smgpu_iterate (DESIGN.md "Mesh quality", 10.10 - 10.12): the quality
-// history, the guard on it, the tangle constraint.  Host code; included by smgpu.hip once, inside its extern "C", in front of
-// iterateBody, which calls into it.  State: smgpu_handle::qt, qg, tg (quality_state.hpp), numbered by smgpu_handle::iterCount.
+// quality_loop.hpp -- the mesh quality features that follow smgpu_iterate (DESIGN.md "Mesh quality", 10.10 - 10.14): the quality
+// history, the guard on it, the tangle constraint, the quality constraint.  Host code; included by smgpu.hip once, inside its extern "C", in front of
+// iterateBody, which calls into it.  State: smgpu_handle::qt, qg, tg, qc (quality_state.hpp), numbered by smgpu_handle::iterCount.
 // ---- the quality history (kernels_quality_trace.hpp, 10.10) ----
 // the running number of the points the engine holds, and how many of the next n iterations are due a record
 static int64_t qualityTraceNumber(const smgpu_handle* h) { return h->iterCount - h->qt.since; }
@@ -290,6 +290,7 @@ int smgpu_set_tangle_constraint(smgpu_handle* h, const smgpu_tangle_params* p, i
     if (h->bndOn)
         return fail("smgpu_set_tangle_constraint: not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
                     "points from state that a reverted iteration would leave ahead of the points)");
+    if (h->qc.on) return fail("smgpu_set_tangle_constraint: the quality constraint is on (smgpu_set_quality_constraint), and it contains this one; switch it off first");
     if (h->iterOpen) return fail("smgpu_set_tangle_constraint: between smgpu_iter_begin and smgpu_iter_end");
     if (tangleOff(h)) return 1;
     if (flushDeferred(h)) return 1;
@@ -463,6 +464,136 @@ int smgpu_tangle_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done) {
     t.passOpen = false;
     *done = close ? 1 : 0;
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- the quality constraint (kernels_quality_constraint.hpp, DESIGN.md "Mesh quality", 10.14) ----
+static int qualityConstraintOff(smgpu_handle* h) {
+    h->qc.on = false;
+    h->qc.slab.discard();
+    if (h->qc.block.live()) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        h->qc.release();
+    }
+    return 0;
+}
+// one evaluation of the points ptsCur names, behind everything queued on the engine's stream; outside the launch counters and the
+// timing events.  Tiles: k_qc_tile writes fCtr / fArea, which no kernel of the tiled loop reads, and cell centres of the
+// constraint's own.  Without tiles the direct geometry kernels write the loop's face values (the next geometry launch writes them
+// again before anything reads them), the same cell centres, and test a stop word of the constraint's own.  enabling: the verdicts
+// become the exempt bytes.
+static int qualityConstraintEvaluate(smgpu_handle* h, bool enabling, int pass, const smgpu_iter_stats* gate) {
+    const MeshView& m = h->mv;
+    QualityConstraintHost& q = h->qc;
+    State ts = h->st;
+    ts.cellCtr = q.cellCtr;
+    ts.acc = q.acc;
+    ts.stats = nullptr;
+    if (h->useTiles) {
+        const int nT = h->gt.nTiles;
+        if (nT > 0)
+            withGeomTile(h, [&](auto tile, auto org) {
+                constexpr int T = decltype(tile)::value;
+                constexpr bool ORG = decltype(org)::value;
+                ensureDynLds(k_qc_tile<T, ORG>, h->device, h->geomLds);
+                hipLaunchKernelGGL((k_qc_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, nT, h->xcdMap,
+                                   enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptCell, enabling ? q.exemptCell : (uint8_t*)nullptr, q.tangled, q.dev,
+                                   pass, gate);
+            });
+    } else {
+        if (pass == 0) hipLaunchKernelGGL(k_qc_open, dim3(1), dim3(64), 0, h->stream, q.acc, gate);
+        if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
+        if (m.nCells > 0) hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
+    }
+    if (m.nFaces > 0)
+        hipLaunchKernelGGL(k_qc_faces, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.ptsCur, (const double*)ts.fCtr,
+                           (const double*)ts.fArea, (const double*)ts.cellCtr, (const int*)h->q.own, (const int*)h->q.nei, q.lim,
+                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag, q.dev, pass, gate);
+    const int gCells = (m.nCells + kQcBlock - 1) / kQcBlock;
+    if (m.nCells > 0 && !h->useTiles)
+        hipLaunchKernelGGL(k_qc_cells<true>, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.fCtr, (const double*)ts.fArea, (const double*)ts.cellCtr,
+                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptCell, enabling ? q.exemptCell : (uint8_t*)nullptr, (const uint8_t*)nullptr,
+                           q.cellFlag, q.marks, q.dev, pass, gate);
+    else if (m.nCells > 0 && !enabling)   // (enabling with tiles: k_qc_tile has left the exempt bytes and their count)
+        hipLaunchKernelGGL(k_qc_cells<false>, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr,
+                           (const uint8_t*)nullptr, (uint8_t*)nullptr, (const uint8_t*)q.tangled, q.cellFlag, q.marks, q.dev, pass, gate);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+// behind the movePoints of an iteration: the passes on the points ptsCur now names; x: the points the iteration started from
+static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x) {
+    QualityConstraintHost& q = h->qc;
+    smgpu_quality_constraint_record* rec = nullptr;
+    if (q.slab.slot(slot, &rec)) return 1;
+    const int nP = h->mv.nPoints;
+    const int gApply = std::max(1, (int)(((int64_t)nP + kTanglePts - 1) / kTanglePts));
+    for (int k = 0; k <= q.prm.passes; ++k) {
+        if (qualityConstraintEvaluate(h, false, k, gate)) return 1;
+        hipLaunchKernelGGL(k_qc_verdict, dim3(1), dim3(64), 0, h->stream, q.dev, q.acc, rec, (long long)number, k, (int)q.prm.passes, gate);
+        // the record and the device words begin with the tangle constraint's (kernels_quality_constraint.hpp)
+        hipLaunchKernelGGL(k_tangle_apply, dim3(gApply), dim3(kTangleBlock), 0, h->stream, x, h->st.ptsCur, q.marks, nP, (const TangleDev*)&q.dev->t,
+                           reinterpret_cast<smgpu_tangle_record*>(rec), gate);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint_params* p, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityConstraintOff(h);
+    const smgpu_quality_constraint_params prm = p ? *p : smgpu_quality_constraint_params{65.0, 4.0, 20.0, 2};
+    if (prm.passes < 0) return fail("smgpu_set_quality_constraint: passes < 0");
+    if (std::isnan(prm.maxNonOrtho) || std::isnan(prm.maxInternalSkewness) || std::isnan(prm.maxBoundarySkewness))
+        return fail("smgpu_set_quality_constraint: a limit is NaN");
+    if (h->haloOn) return fail(kQualityHaloRefusal);
+    if (h->bndOn)
+        return fail("smgpu_set_quality_constraint: not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
+                    "points from state that a reverted iteration would leave ahead of the points)");
+    if (h->tg.on) return fail("smgpu_set_quality_constraint: the tangle constraint is on (smgpu_set_tangle_constraint), and this constraint contains it; switch it off first");
+    if (h->iterOpen) return fail("smgpu_set_quality_constraint: between smgpu_iter_begin and smgpu_iter_end");
+    if (qualityConstraintOff(h)) return 1;
+    if (flushDeferred(h)) return 1;
+    if (qualityEnsure(h)) return 1;                  // owner / neighbour by face
+    const MeshView& m = h->mv;
+    const size_t nMark = ((size_t)std::max(1, m.nPoints) + 3) & ~(size_t)3, nCell = (size_t)std::max(1, m.nCells), nFace = (size_t)std::max(1, m.nFaces);
+    QualityConstraintHost& q = h->qc;
+    if (q.block.alloc(&q.dev, 1) || q.block.alloc(&q.exemptCell, nCell) || q.block.alloc(&q.cellFlag, nCell) || q.block.alloc(&q.tangled, nCell) || q.block.alloc(&q.exemptFace, nFace) ||
+        q.block.alloc(&q.marks, nMark) || q.block.alloc(&q.cellCtr, 3 * nCell) || q.block.alloc(&q.acc, 1))
+        return q.block.failed("the quality constraint");
+    HIP_OK(hipMemsetAsync(q.dev, 0, sizeof(QcDev), h->stream));
+    HIP_OK(hipMemsetAsync(q.exemptCell, 0, nCell, h->stream));
+    HIP_OK(hipMemsetAsync(q.cellFlag, 0, nCell, h->stream));
+    HIP_OK(hipMemsetAsync(q.tangled, 0, nCell, h->stream));
+    HIP_OK(hipMemsetAsync(q.exemptFace, 0, nFace, h->stream));
+    HIP_OK(hipMemsetAsync(q.marks, 0, nMark, h->stream));
+    HIP_OK(hipMemsetAsync(q.acc, 0, sizeof(Accum), h->stream));
+    q.prm = prm;
+    // cosT exactly as qualityThresholds() forms the report's cosine
+    const smgpu_quality_params rp{prm.maxNonOrtho, prm.maxInternalSkewness, 1e-6, 1000.0};
+    q.lim = QcLimits{qualityThresholds(&rp).cosNonOrth, prm.maxInternalSkewness, prm.maxBoundarySkewness, prm.maxNonOrtho < 180.0 ? 1 : 0,
+                     prm.maxInternalSkewness > 0.0 ? 1 : 0, prm.maxBoundarySkewness > 0.0 ? 1 : 0};
+    // the exempt cells and faces: one evaluation of the current points
+    if (qualityConstraintEvaluate(h, true, 0, nullptr)) { q.release(); return 1; }
+    QcDev qd{};
+    HIP_OK(hipMemcpyAsync(&qd, q.dev, sizeof(QcDev), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemsetAsync(q.dev, 0, sizeof(QcDev), h->stream));
+    if (checkDeviceError(h)) { q.release(); return 1; }
+    q.nExemptCells = qd.t.badNow;
+    q.nExemptFaces = qd.facesNow;
+    q.since = h->iterCount;
+    q.on = true;
+    return 0;
+}
+int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n) {
+    if (!h || !n) return fail("null argument");
+    return h->qc.slab.drain(out, cap, n, "smgpu_get_quality_constraint_records");
+}
+int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint_state* out) {
+    if (!h || !out) return fail("null argument");
+    const QualityConstraintHost& q = h->qc;
+    *out = smgpu_quality_constraint_state{q.on ? 1 : 0, q.prm.passes, q.prm.maxNonOrtho, q.prm.maxInternalSkewness, q.prm.maxBoundarySkewness,
+                                          q.on ? q.nExemptCells : 0, q.on ? q.nExemptFaces : 0, q.on ? h->iterCount - q.since : 0};
     return 0;
 }
 

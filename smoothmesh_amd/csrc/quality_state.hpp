@@ -186,3 +186,20 @@ struct TangleHost {
     int *sendT = nullptr, *recvT = nullptr; // the caller's exchange buffers (device, nSend / nRecv int32)
     void release() { block.release(); slab.release(); coupled = passOpen = slabFresh = false; k = -1; slabUsed = 0; }
 };
+
+// The quality constraint (smgpu_set_quality_constraint, kernels_quality_constraint.hpp): allocated at enabling.  exemptCell /
+// cellFlag / tangled: one byte per cell; exemptFace: one per face; marks: one per point (rounded up to whole words); cellCtr / acc: the
+// cell centres and the stop word of its geometry launches, with and without tiles
+struct QualityConstraintHost {
+    bool on = false;
+    smgpu_quality_constraint_params prm{65.0, 4.0, 20.0, 2};
+    QcLimits lim{};
+    int64_t since = 0, nExemptCells = 0, nExemptFaces = 0;   // smgpu_handle::iterCount at enabling (numbers as the trace's)
+    DevBlock block;
+    uint8_t *exemptCell = nullptr, *exemptFace = nullptr, *cellFlag = nullptr, *tangled = nullptr, *marks = nullptr;
+    QcDev* dev = nullptr;
+    double* cellCtr = nullptr;
+    Accum* acc = nullptr;
+    RecordSlab<smgpu_quality_constraint_record> slab{"quality constraint"};   // one record per iteration of the call
+    void release() { block.release(); slab.release(); }
+};

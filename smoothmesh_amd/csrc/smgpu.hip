@@ -26,6 +26,7 @@
 #include "kernels_quality_trace.hpp"
 #include "kernels_quality_guard.hpp"
 #include "kernels_quality_tangle.hpp"
+#include "kernels_quality_constraint.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"
@@ -236,6 +237,7 @@ struct smgpu_handle {
     QualityTraceHost qt;
     QualityGuardHost qg;
     TangleHost tg;
+    QualityConstraintHost qc;
     int64_t iterCount = 0;
     bool iterOpen = false;                  // between smgpu_iter_begin and smgpu_iter_end
 };
@@ -1122,7 +1124,7 @@ int smgpu_destroy(smgpu_handle* h) {
     if (h->gtDev.valid)      // (a create that failed before the handle took the device-built tile tables over)
         for (const GeomTilesDev::Arr* a : {&h->gtDev.cellOrder, &h->gtDev.cellBeg, &h->gtDev.tpIds, &h->gtDev.tfIds, &h->gtDev.faceVerts, &h->gtDev.cellFaces, &h->gtDev.meta})
             if (a->p) (void)hipFree(a->p);
-    h->q.release(); h->qt.release(); h->qg.release(); h->tg.release();
+    h->q.release(); h->qt.release(); h->qg.release(); h->tg.release(); h->qc.release();
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
     for (hipEvent_t e : h->evWalkLag) if (e) (void)hipEventDestroy(e);
@@ -1957,15 +1959,17 @@ static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_ite
     // under the tangle constraint: its launches of iteration i are gated on the written bit of stats[i])
     const bool guarded = h->qg.armed;
     const bool tangled = h->tg.on;
-    const bool deferFinish = relTol <= 0.0 && !guarded && !tangled && h->useTiles && h->geomT >= 64 && envInt("SMGPU_DEFER_FINISH", 1);
+    const bool limited = h->qc.on;          // the quality constraint: gated like the tangle constraint
+    const bool deferFinish = relTol <= 0.0 && !guarded && !tangled && !limited && h->useTiles && h->geomT >= 64 && envInt("SMGPU_DEFER_FINISH", 1);
     if (flushDeferred(h)) return 1;
     // quality history: the iterations of this call whose running number is due get a slot of the call's record slab, in order
     const bool traced = h->qt.interval > 0;
     int qtSlots = 0;
     if (traced && qualityTraceBegin(h, nIters)) return 1;
     if (tangled && h->tg.slab.begin(h->stream, nIters)) return 1;
+    if (limited && h->qc.slab.begin(h->stream, nIters)) return 1;
     // iteration i of this call is number qtNumber + i + 1 of the trace and tgNumber + i + 1 of the tangle constraint
-    const int64_t qtNumber = h->iterCount - h->qt.since, tgNumber = h->iterCount - h->tg.since;
+    const int64_t qtNumber = h->iterCount - h->qt.since, tgNumber = h->iterCount - h->tg.since, qcNumber = h->iterCount - h->qc.since;
     for (int i = 0; i < nIters; ++i) {
         if (runBndPre(h)) return 1;
         if (runGeometry(h, nullptr, 0, false, true)) return 1;
@@ -1985,9 +1989,10 @@ static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_ite
         // the tangle constraint: `other` now names x, the points the iteration started from; nothing queued writes them before
         // the next iteration's proposal (fused: ptsNext; k_apply: ptsNext; k_apply_swap: prop), which is queued behind the passes
         if (tangled && tangleQueue(h, i, tgNumber + i + 1, h->dStats + i, other)) return 1;
+        if (limited && qualityConstraintQueue(h, i, qcNumber + i + 1, h->dStats + i, other)) return 1;
         // (with relTol > 0 this iteration may turn out not to have run: k_finish has written stats[i] by then, or has not)
         if (traced && (qtNumber + i + 1) % h->qt.interval == 0) {
-            const smgpu_iter_stats* gate = (relTol > 0.0 || guarded || tangled) ? h->dStats + i : nullptr;
+            const smgpu_iter_stats* gate = (relTol > 0.0 || guarded || tangled || limited) ? h->dStats + i : nullptr;
             smgpu_quality_trace_record* rec = nullptr;
             if (h->qt.slab.slot(qtSlots++, &rec)) return 1;
             if (qualityTraceQueue(h, qtNumber + i + 1, gate, rec)) return 1;
@@ -2012,12 +2017,14 @@ static int iterateBody(smgpu_handle* h, int32_t nIters, double relTol, smgpu_ite
         if (h->tg.slab.readBack(h->stream, launched)) return 1;
         HIP_OK(hipMemcpyAsync(&td, h->tg.dev, sizeof(TangleDev), hipMemcpyDeviceToHost, h->stream));
     }
+    if (limited && h->qc.slab.readBack(h->stream, launched)) return 1;
     if (checkDeviceError(h)) return 1;
     if (td.err) return fail("smgpu_iterate: tangle constraint: the marks of a geometry tile do not fit the LDS of its points");
     int done = 0;
     while (done < launched && (hs[done].nNearTies & kStatsWritten)) ++done;
     if (!h->qg.refining) {   // (the guard's refining steps replay iterations of the call: no records, no numbers)
         if (tangled) h->tg.slab.keep(done);
+        if (limited) h->qc.slab.keep(done);
         if (traced) h->qt.slab.keep(qualityTraceDue(h, done));   // the slots of the iterations that ran
         h->iterCount += done;
     }
@@ -2211,6 +2218,7 @@ int smgpu_halo_set_exchange_stream(smgpu_handle* h, int32_t useExchangeStream, v
 
 int smgpu_halo_configure(smgpu_handle* h, const smgpu_halo_desc* d) {
     if (!h || !d) return fail("null argument");
+    if (h->qc.on) return fail("smgpu_halo_configure: the quality constraint is on (smgpu_set_quality_constraint), and it is not available on an engine with a halo; switch it off first");
     if (h->tg.on) return fail("smgpu_halo_configure: the tangle constraint is on (smgpu_set_tangle_constraint), and it is not available on an engine with a halo; switch it off first");
     if (h->qg.armed) return fail("smgpu_halo_configure: the quality guard is armed (smgpu_set_quality_guard), and a guard is not available on an engine with a halo; disarm it first");
     if (h->qt.interval > 0) return fail("smgpu_halo_configure: the quality trace is on (smgpu_set_quality_trace), and a trace is not available on an engine with a halo; switch it off first");
@@ -3284,6 +3292,7 @@ int smgpu_boundary_shared(smgpu_handle* h, int32_t field, int32_t set, double* v
 int smgpu_set_boundary_smoothing(smgpu_handle* h, const smgpu_boundary_desc* d, smgpu_boundary_info* info) {
     if (!h || !d) return fail("null argument");
     if (h->haloOn) return fail("smgpu_set_boundary_smoothing is the serial set-up; with a halo use smgpu_boundary_stats / begin / step / shared");
+    if (h->qc.on) return fail("smgpu_set_boundary_smoothing: the quality constraint is on (smgpu_set_quality_constraint), and it is not available on an engine with boundary point smoothing; switch it off first");
     if (h->tg.on) return fail("smgpu_set_boundary_smoothing: the tangle constraint is on (smgpu_set_tangle_constraint), and it is not available on an engine with boundary point smoothing; switch it off first");
     if (h->qg.armed) return fail("smgpu_set_boundary_smoothing: the quality guard is armed (smgpu_set_quality_guard), and its snapshot does not hold the state boundary point smoothing carries from one iteration to the next; disarm it first");
     double minEdge = 0.0, bb[6];

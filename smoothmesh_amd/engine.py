@@ -140,6 +140,37 @@ class TangleRecord:
 
 
 @dataclass
+class QualityConstraintRecord:
+    """One record of the quality constraint (include/smgpu.h, smgpu_quality_constraint_record; DESIGN.md "Mesh quality", 10.14), of
+    iteration `iteration` (1-based, counted since set_quality_constraint).  iteration, passes, fullRevert and nPointsReverted are
+    TangleRecord's; `nBadCells` cells were bad after the loop's move -- `nTangledCells` of them by the tangle constraint's
+    definition, the others as the owner or the neighbour of one of the `nNonOrthoFaces` faces over the non-orthogonality limit
+    or the `nSkewFaces` faces over a skewness limit (a face over both counts in both; exempt elements never count)."""
+    iteration: int
+    passes: int
+    fullRevert: int
+    nBadCells: int
+    nPointsReverted: int
+    nTangledCells: int
+    nNonOrthoFaces: int
+    nSkewFaces: int
+
+
+@dataclass
+class QualityConstraintState:
+    """smgpu_quality_constraint_state: whether the constraint is on, its passes and limits, the cells and faces exempt since
+    enabling, the running number"""
+    on: bool
+    passes: int
+    maxNonOrtho: float
+    maxInternalSkewness: float
+    maxBoundarySkewness: float
+    nExemptCells: int
+    nExemptFaces: int
+    iteration: int
+
+
+@dataclass
 class TangleState:
     """smgpu_tangle_state: whether the constraint is on, its passes, the cells exempt since enabling, the running number"""
     on: bool
@@ -671,6 +702,36 @@ class SmoothEngine:
         s = _ffi.TangleState()
         self._check(self._lib.smgpu_get_tangle_state(self._h, C.byref(s)))
         return TangleState(on=bool(s.on), passes=s.passes, nExemptCells=s.nExemptCells, iteration=s.iteration)
+
+    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2):
+        """Quality constraint (include/smgpu.h, smgpu_set_quality_constraint; DESIGN.md "Mesh quality", 10.14): the tangle
+        constraint with limits on face non-orthogonality (degrees; >= 180: off) and on the skewness of internal and of boundary
+        faces (<= 0: off).  From now on iterate() puts the points of every cell that an iteration turned bad -- by the tangle
+        constraint's measure, or as the owner or neighbour of a face over a limit -- back where the iteration found them, in up to
+        `passes` marked passes and then a full revert.  Cells and faces bad at the current points are exempt.  Adds no
+        synchronisation to the loop.  Refused on an engine with a halo, with boundary point smoothing, or with the tangle
+        constraint on."""
+        p = _ffi.QualityConstraintParams(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes))
+        self._check(self._lib.smgpu_set_quality_constraint(self._h, C.byref(p), 1))
+
+    def clear_quality_constraint(self):
+        """Switch the quality constraint off; discards unread records."""
+        self._check(self._lib.smgpu_set_quality_constraint(self._h, None, 0))
+
+    def quality_constraint_records(self) -> list:
+        """The pending records of the quality constraint, one per iteration that ran, in ascending iteration; clears them."""
+        n = C.c_int64(0)
+        self._check(self._lib.smgpu_get_quality_constraint_records(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        buf = (_ffi.QualityConstraintRecord * n.value)()
+        self._check(self._lib.smgpu_get_quality_constraint_records(self._h, buf, n.value, C.byref(n)))
+        return [QualityConstraintRecord(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+
+    def quality_constraint_state(self) -> QualityConstraintState:
+        s = _ffi.QualityConstraintState()
+        self._check(self._lib.smgpu_get_quality_constraint_state(self._h, C.byref(s)))
+        return QualityConstraintState(on=bool(s.on), **{f: getattr(s, f) for f, _ in s._fields_ if f != "on"})
 
     def quality_field(self, name) -> np.ndarray:
         """Per-element quality field in polyMesh order: one of QUALITY_FIELDS (non-orthogonality in degrees, 0 on boundary faces)."""

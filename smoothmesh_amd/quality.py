@@ -18,7 +18,7 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityGuardState, QualityTraceRecord, TangleRecord, TangleState, QUALITY_FIELDS,  # noqa: F401
+from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityGuardState, QualityTraceRecord, TangleRecord, TangleState, QualityConstraintRecord, QualityConstraintState, QUALITY_FIELDS,  # noqa: F401
                      QUALITY_GEOMETRY_FIELDS, QUALITY_MOTION_FIELDS, QUALITY_SETS, QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS)
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
@@ -453,6 +453,13 @@ def format_tangle_line(rec):
     smoothMesh_main.cpp), of a TangleRecord"""
     return (f"    tangle iteration={rec.iteration} badCells {rec.nBadCells} passes {rec.passes} pointsReverted {rec.nPointsReverted}"
             + (" fullRevert" if rec.fullRevert else "") + "\n")
+
+
+def format_quality_constraint_line(rec):
+    """the line smoothMesh -qualityConstraint prints under the iteration line of an iteration whose nBadCells > 0 (csrc/host/
+    smoothMesh_main.cpp), of a QualityConstraintRecord"""
+    return (f"    quality constraint iteration={rec.iteration} badCells {rec.nBadCells} tangled {rec.nTangledCells} nonOrthoFaces {rec.nNonOrthoFaces} "
+            f"skewFaces {rec.nSkewFaces} passes {rec.passes} pointsReverted {rec.nPointsReverted}" + (" fullRevert" if rec.fullRevert else "") + "\n")
 
 
 def format_guard_lines(state):
