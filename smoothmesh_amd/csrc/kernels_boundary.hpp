@@ -192,16 +192,16 @@ __global__ void __launch_bounds__(64) k_bnd_feature(MeshView m, State s, BndView
 // boundary point smoothing); here they cost no launch at all.  nBndBlocks (a multiple of 8, so that the XCD mapping of the
 // geometry workgroups is unchanged) = normals blocks, then feature blocks (T / 64 feature points each).
 template <int T, bool ORG>
-__global__ void __launch_bounds__(T, (SMGPU_GEOM_WAVES * T) / 256) k_geom_tile_bnd(MeshView m, State s, GeomTileView g, int wantAvg, int writeFaces,
-                                                  const int* tileList, int nLaunch, int xcdMap, int deferN, int deferIter, double* deferLocal,
-                                                  double* deferHist, BndView b, int nBndBlocks, int nNormalBlocks) {
+__global__ void __launch_bounds__(T, (SMGPU_GEOM_WAVES * T) / 256) k_geom_tile_bnd(TileLaunch tl, MeshView m, State s, GeomTileView g, int wantAvg, int writeFaces,
+                                                  int deferN, int deferIter, double* deferLocal, double* deferHist, BndView b, int nBndBlocks,
+                                                  int nNormalBlocks) {
     const int bx = (int)blockIdx.x;
     if (bx < nBndBlocks) {
         if (bx < nNormalBlocks) bndNormalsOf(m, s, b, bx * T + (int)threadIdx.x);
         else bndFeatureOf(m, s, b, (bx - nNormalBlocks) * (T / 64) + ((int)threadIdx.x >> 6), (int)threadIdx.x & 63);
         return;
     }
-    geomTileBody<T, ORG>(m, s, g, wantAvg, writeFaces, tileList, nLaunch, xcdMap, deferN, deferIter, deferLocal, deferHist, bx - nBndBlocks);
+    geomTileBody<T, ORG>(tl, m, s, g, wantAvg, writeFaces, deferN, deferIter, deferLocal, deferHist, bx - nBndBlocks);
 }
 
 // OpenFOAM triangle::intersection(orig, dir, intersection::HALF_RAY, tol)

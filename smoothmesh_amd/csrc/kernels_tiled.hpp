@@ -44,13 +44,14 @@ struct GeomTileView {
 struct GeomTileMeta { int tpOff, nPts, tfOff, nFaces, fvBase, fvWidth, cellBeg, nCells, cfBase, cfWidth, flags, pad; };
 constexpr int kGeomMetaInts = 12;
 typedef const __attribute__((address_space(4))) int* const_int_ptr;
-__device__ __forceinline__ GeomTileMeta loadTileMeta(const GeomTileView& g, int tile) {
-    const_int_ptr p = (const_int_ptr)(g.meta + (size_t)kGeomMetaInts * tile);
+__device__ __forceinline__ GeomTileMeta loadGeomMeta(const int* meta, int tile) {
+    const_int_ptr p = (const_int_ptr)(meta + (size_t)kGeomMetaInts * tile);
     GeomTileMeta t;
     t.tpOff = p[0]; t.nPts = p[1]; t.tfOff = p[2]; t.nFaces = p[3]; t.fvBase = p[4]; t.fvWidth = p[5];
     t.cellBeg = p[6]; t.nCells = p[7]; t.cfBase = p[8]; t.cfWidth = p[9]; t.flags = p[10]; t.pad = 0;
     return t;
 }
+__device__ __forceinline__ GeomTileMeta loadTileMeta(const GeomTileView& g, int tile) { return loadGeomMeta(g.meta, tile); }
 
 struct SmoothTileView {
     const int* ptOrder; const int* ptBeg; const int* tcOff; const int* tcIds; const int* tnOff; const int* tnIds;
@@ -77,13 +78,14 @@ __device__ __forceinline__ SmoothTileView pickView(bool a, const SmoothTileView&
 
 struct SmoothTileMeta { int ptBeg, nPts, tcOff, nCells, tnOff, nNbrs, pcBase, pcWidth, ppBase, ppWidth, pfBase, pfWidth; };
 constexpr int kSmoothMetaInts = 12;
-__device__ __forceinline__ SmoothTileMeta loadTileMeta(const SmoothTileView& g, int tile) {
-    const_int_ptr p = (const_int_ptr)(g.meta + (size_t)kSmoothMetaInts * tile);
+__device__ __forceinline__ SmoothTileMeta loadSmoothMeta(const int* meta, int tile) {
+    const_int_ptr p = (const_int_ptr)(meta + (size_t)kSmoothMetaInts * tile);
     SmoothTileMeta t;
     t.ptBeg = p[0]; t.nPts = p[1]; t.tcOff = p[2]; t.nCells = p[3]; t.tnOff = p[4]; t.nNbrs = p[5];
     t.pcBase = p[6]; t.pcWidth = p[7]; t.ppBase = p[8]; t.ppWidth = p[9]; t.pfBase = p[10]; t.pfWidth = p[11];
     return t;
 }
+__device__ __forceinline__ SmoothTileMeta loadTileMeta(const SmoothTileView& g, int tile) { return loadSmoothMeta(g.meta, tile); }
 
 // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2.  With xcdMap the launch has 8*ceil(n/8)
 // workgroups and XCD x walks the contiguous range [x*ceil(n/8), ...) of the Morton-ordered tile sequence, so
@@ -95,6 +97,52 @@ __device__ __forceinline__ int launchTile(int n, int xcdMap, int b = (int)blockI
     return i < n ? i : -1;
 }
 __host__ __device__ inline int tileGrid(int n, int xcdMap) { return xcdMap ? ((n + 7) >> 3) << 3 : n; }
+
+// ---- the scalar part of a tile's prologue -----------------------------------------------------------------------------------
+// The kernels below take ~940 bytes of arguments (MeshView, State, Prm, a tile view: all by value).  The compiler fetches a
+// field where it is first used, and every fetch the next step depends on is a scalar-memory round trip the whole workgroup sits
+// through: four or five of them lay between dispatch and the first vector load (profiles/prologue_chain_parent.txt), of which
+// the data needs two -- what tile am I, and that tile's meta record.
+// scalarBatch(values...): every value is in its scalar register HERE.  The loads behind the values depend on nothing that comes
+// later, so the compiler issues them together in front of this point and waits once; the later uses read the registers.
+// (An empty asm statement per value with the value as an "s" input: no instruction, nothing the optimiser loses -- the value
+// keeps its address space, range and alias facts.  Only wave-uniform values: anything else would be read from lane 0.)
+template <class V>
+__device__ __forceinline__ void scalarUse(const V& v) { asm volatile("" : : "s"(v)); }
+template <class... V>
+__device__ __forceinline__ void scalarBatch(const V&... v) { (scalarUse(v), ...); }
+// The waves of k_geom_tile run at raised issue priority from kernel entry to the staging barrier, so that a new workgroup's
+// address arithmetic and loads are not queued behind the resident waves' FP64 work: 46.7 -> 45.9 us per launch on 100^3, the
+// 10 M-cell polyhedral mesh not slower (profiles/tile_prologue_chain.md).  -DSMGPU_PROLOGUE_PRIO=<bits>: bit 0 k_geom_tile
+// (the default), bit 1 k_smooth_tile -- measured 1.2 % SLOWER there, not kept --, 0 neither
+#ifndef SMGPU_PROLOGUE_PRIO
+#define SMGPU_PROLOGUE_PRIO 1
+#endif
+template <int BIT> __device__ __forceinline__ void prologuePrioUp() { if (SMGPU_PROLOGUE_PRIO & BIT) __builtin_amdgcn_s_setprio(2); }
+template <int BIT> __device__ __forceinline__ void prologuePrioDown() { if (SMGPU_PROLOGUE_PRIO & BIT) __builtin_amdgcn_s_setprio(0); }
+// What a workgroup needs to find its tile and to start the load of the tile's meta record: the FIRST kernel argument of every
+// kernel on tiles, read in one batch at the top (8 dwords at offset 0 of the argument segment).  The multi-role launches fill in
+// tileList / nLaunch (and the pack role `meta`) per role.
+struct TileLaunch {
+    const int* meta;       // the meta table of the launch's tile view (GeomTileView::meta / SmoothTileView::meta)
+    const int* tileList;   // the tiles of this launch, or NULL: all of them
+    const int* stop;       // &Accum::stop, the "loop has stopped" word: one hop, not two through State::acc
+    int nLaunch, xcdMap;
+};
+__host__ __device__ inline TileLaunch tileLaunch(const int* meta, const State& s, const int* tileList, int nLaunch, int xcdMap) {
+    return TileLaunch{meta, tileList, reinterpret_cast<const int*>(reinterpret_cast<const char*>(s.acc) + offsetof(Accum, stop)), nLaunch, xcdMap};
+}
+// The stop word, with a scalar load through the constant address space: no kernel that takes a TileLaunch writes it (the deferred
+// finish inside the geometry launch runs with relTol < 0, finishPartials), so it is constant for the launch's lifetime
+__device__ __forceinline__ int stopWord(const TileLaunch& tl) { return *(const_int_ptr)tl.stop; }
+// First scalar round trip of a workgroup: the launch record -> its tile, or -1 for a padding workgroup.  With a tile list the
+// list entry is one more round trip.  bid: the workgroup's index among those of its role.
+__device__ __forceinline__ int launchedTile(const TileLaunch& tl, int bid) {
+    scalarBatch(tl.meta, tl.tileList, tl.stop, tl.nLaunch, tl.xcdMap);
+    const int li = launchTile(tl.nLaunch, tl.xcdMap, bid);
+    if (li < 0) return -1;
+    return tl.tileList ? ((const_int_ptr)tl.tileList)[li] : li;
+}
 
 __device__ __forceinline__ V3 ldsv(const double* x, const double* y, const double* z, int i) { return v3(x[i], y[i], z[i]); }
 
@@ -413,18 +461,18 @@ __device__ __forceinline__ void geomFace(const State& s, const GeomTileView& g, 
 struct GeomCellIn { bool mine; int c; ushort4 qa, qb; };
 template <int T>
 __device__ __forceinline__ GeomCellIn geomCellLoad(const GeomTileView& g, const GeomTileMeta& tm, int tid, unsigned tflags) {
+    // no branch around the loads (see smoothStage): a lane without a cell, and every lane of a tile without six-faced rows, reads
+    // entry 0 of the table and discards it
     GeomCellIn in;
-    const int ci = tm.cellBeg + tid;
     in.mine = tid < tm.nCells;
-    in.c = 0;
-    in.qa = in.qb = make_ushort4(0, 0, 0, 0);
-    if (in.mine) {
-        in.c = g.cellOrder[ci];
-        if ((tflags & 2u)) {
-            const ushort4* row = reinterpret_cast<const ushort4*>(g.cellFaces + tm.cfBase) + tid;
-            in.qa = row[0]; in.qb = row[T];
-        }
-    }
+    const bool rows = in.mine && (tflags & 2u);
+    const ushort4* cf = reinterpret_cast<const ushort4*>(g.cellFaces);
+    const int r0 = (tm.cfBase >> 2) + tid;       // (cfBase: a multiple of 4, the rows are read as 8-byte chunks)
+    const int c = g.cellOrder[in.mine ? tm.cellBeg + tid : 0];
+    const ushort4 qa = cf[rows ? r0 : 0], qb = cf[rows ? r0 + T : 0];
+    const ushort4 zero = make_ushort4(0, 0, 0, 0);
+    in.c = in.mine ? c : 0;
+    in.qa = rows ? qa : zero; in.qb = rows ? qb : zero;
     return in;
 }
 // coh (workgroup-uniform): the cell centre is read by another workgroup of the SAME launch (the pack role of k_geom_halo):
@@ -493,9 +541,13 @@ __device__ __forceinline__ void geomCell(const State& s, const GeomTileView& g, 
 // round 1 of the prologue for one tile: the point id list (first two rounds of T)
 template <int T>
 __device__ __forceinline__ void geomLoadIds(const GeomTileView& g, const GeomTileMeta& tm, int tid, int (&id)[2]) {
-    const int* ids = g.tpIds + tm.tpOff;
+    // (no branch around the loads: a lane beyond the list reads entry 0 of the table and discards it -- geomCellLoad)
 #pragma unroll
-    for (int u = 0; u < 2; ++u) { const int i = u * T + tid; id[u] = (i < tm.nPts) ? ids[i] : -1; }
+    for (int u = 0; u < 2; ++u) {
+        const int i = u * T + tid;
+        const int v = g.tpIds[(i < tm.nPts) ? tm.tpOff + i : 0];
+        id[u] = (i < tm.nPts) ? v : -1;
+    }
 }
 // ... and what the face and cell phases read from global memory per thread: the vertex rows of the first two face rounds of a
 // quadrilateral tile, the cell's id and face row
@@ -508,7 +560,9 @@ __device__ __forceinline__ GeomRows geomLoadRows(const GeomTileView& g, const Ge
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int i = u * T + tid;
-        r.fq[u] = (r.preFaces && i < tm.nFaces) ? reinterpret_cast<const ushort4*>(g.faceVerts + tm.fvBase)[i] : make_ushort4(0, 0, 0, 0);
+        const bool pre = r.preFaces && i < tm.nFaces;
+        const ushort4 q = reinterpret_cast<const ushort4*>(g.faceVerts)[pre ? (tm.fvBase >> 2) + i : 0];   // (fvBase: a multiple of 4)
+        r.fq[u] = q;      // (read only where `pre` holds: geomFaces.  A select on `pre` here and the compiler puts the load behind a branch again)
     }
     r.cin = geomCellLoad<T>(g, tm, tid, tflags);
     return r;
@@ -546,19 +600,21 @@ __device__ __forceinline__ void geomFaces(const State& s, const GeomTileView& g,
 // bid = the workgroup's index among the geometry workgroups of the launch.  (Two tiles per workgroup with both prologues in
 // flight at once was built and measured: no gain on hex meshes, 17 % slower on the polyhedral one -- DESIGN 9.)
 template <int T, bool ORG>
-__device__ __forceinline__ void geomTileBody(const MeshView& m, const State& s, const GeomTileView& g, int wantAvg, int writeFaces, const int* tileList,
-                                             int nLaunch, int xcdMap, int deferN, int deferIter, double* deferLocal, double* deferHist, int bid, bool coh = false) {
-    // the "loop has stopped" flag (relTol reached, SM.C:2401) is tested after the staging: a dependent global load in front of
-    // everything else put its latency on every workgroup's critical path; a stopped run stages one tile in vain
-    const int stopped = s.acc->stop;
-    const int li = launchTile(nLaunch, xcdMap, bid);
-    if (li < 0) return;
+__device__ __forceinline__ void geomTileBody(const TileLaunch& tl, const MeshView& m, const State& s, const GeomTileView& g, int wantAvg, int writeFaces,
+                                             int deferN, int deferIter, double* deferLocal, double* deferHist, int bid, bool coh = false) {
+    const int tile = launchedTile(tl, bid);                       // scalar round trip 1: the launch record
+    if (tile < 0) return;
+    // scalar round trip 2: the tile's meta record and, requested with it, every kernel argument the two staging rounds read and
+    // the "loop has stopped" flag (relTol reached, SM.C:2401).  The flag is tested after the staging: a dependent load in front
+    // of everything else put its latency on every workgroup's critical path; a stopped run stages one tile in vain
+    const GeomTileMeta tm = loadGeomMeta(tl.meta, tile);
+    const int stopped = stopWord(tl);
+    scalarBatch(tm.tpOff, tm.nPts, tm.tfOff, tm.nFaces, tm.fvBase, tm.fvWidth, tm.cellBeg, tm.nCells, tm.cfBase, tm.cfWidth, tm.flags, stopped,
+                g.tpIds, g.faceVerts, g.cellOrder, g.cellFaces, s.ptsCur, deferN);
     staggerFirstRound(bid, 256 * 4);
     if (deferN > 0 && bid == 0) { if (stopped) return; finishPartials<T>(s, deferN, deferIter, -1.0, deferLocal, deferHist); __syncthreads(); }
     extern __shared__ double lds[];
     const int tid = threadIdx.x;
-    const int tile = tileList ? ((const_int_ptr)tileList)[li] : li;
-    const GeomTileMeta tm = loadTileMeta(g, tile);
     const GeomLds L = geomLds(lds, tm);
     int id[2];
     geomLoadIds<T>(g, tm, tid, id);                               // round 1 (the id list first: the point records depend on it)
@@ -567,6 +623,7 @@ __device__ __forceinline__ void geomTileBody(const MeshView& m, const State& s, 
     geomLoadPoints(s, id, v);                                     // round 2
     geomStorePoints<T>(s, g, tm, L, id, v, tid);
     if (stopped) return;
+    prologuePrioDown<1>();
     __syncthreads();
     if (SMGPU_ABLATE & 32) { if (tid < tm.nCells) stv(s.cellCtr, ((const_int_ptr)g.cellOrder)[tm.cellBeg + tid], v3(L.px[tid], 0.0, 0.0)); return; }   // (timing experiment: staging only)
     geomFaces<T, ORG>(s, g, L, tm, r, tid, wantAvg, writeFaces);  // phase 1: every face of the tile once
@@ -575,10 +632,10 @@ __device__ __forceinline__ void geomTileBody(const MeshView& m, const State& s, 
     geomCell<T, ORG>(s, g, L, tm, tid, (unsigned)tm.flags, r.cin, coh);   // phase 2: one thread per cell
 }
 template <int T, bool ORG>
-__global__ void __launch_bounds__(T, (SMGPU_GEOM_WAVES * T) / 256) k_geom_tile(MeshView m, State s, GeomTileView g, int wantAvg, int writeFaces, const int* tileList,
-                                                  int nLaunch, int xcdMap, int deferN, int deferIter, double* deferLocal,
-                                                  double* deferHist) {
-    geomTileBody<T, ORG>(m, s, g, wantAvg, writeFaces, tileList, nLaunch, xcdMap, deferN, deferIter, deferLocal, deferHist, (int)blockIdx.x);
+__global__ void __launch_bounds__(T, (SMGPU_GEOM_WAVES * T) / 256) k_geom_tile(TileLaunch tl, MeshView m, State s, GeomTileView g, int wantAvg, int writeFaces,
+                                                  int deferN, int deferIter, double* deferLocal, double* deferHist) {
+    prologuePrioUp<1>();
+    geomTileBody<T, ORG>(tl, m, s, g, wantAvg, writeFaces, deferN, deferIter, deferLocal, deferHist, (int)blockIdx.x);
 }
 
 // The fused per-point proposal kernel of kernels.hpp (k_smooth) with the cell centres and neighbour
@@ -653,6 +710,12 @@ struct SlotTabs { const int* slot; const int* peer; const int* dst0; const int* 
 template <int T, bool COHC = false, int SLOTS = 1>
 __device__ __forceinline__ SmoothRow smoothStage(const MeshView& m, const State& s, const SmoothTileView& g, const SmoothTileMeta& tm,
                                                  const SmoothLds& L, int tid, const SlotTabs& tb = SlotTabs{nullptr, nullptr, nullptr, nullptr}) {
+    // ONE scalar round trip for the tile's meta record and every kernel argument the two rounds read (scalarBatch, above): the
+    // caller has just requested the record, the arguments are requested with it instead of where each is first used
+    scalarBatch(tm.ptBeg, tm.nPts, tm.tcOff, tm.nCells, tm.tnOff, tm.nNbrs, tm.pcBase, tm.pcWidth, tm.ppBase, tm.ppWidth,
+                g.tcIds, g.tnIds, g.ptOrder, g.selfLoc, g.ppEll, g.pcEll, g.pairEll, g.usePairShare, s.cellCtr, s.ptsCur, m.pflags);
+    if (SLOTS == 1) scalarBatch(s.sharedSlot);
+    if (SLOTS == 2) scalarBatch(tb.slot, tb.peer, tb.dst0, tb.ndst);
     SmoothRow r;
     r.peer = -1; r.dst0 = -1; r.ndst = 0;
     r.mine = tid < tm.nPts;
@@ -872,18 +935,22 @@ __device__ __forceinline__ void smoothPoint(const MeshView& m, const State& s, c
 }
 
 template <bool FINAL, int T>
-__global__ void __launch_bounds__(T) k_smooth_tile(MeshView m, State s, Prm prm, SmoothTileView g, const int* tileList,
-                                                    int nLaunch, int xcdMap) {
-    const int stopped = s.acc->stop;   // tested after the staging, see k_geom_tile
-    const int li = launchTile(nLaunch, xcdMap);
-    if (li < 0) return;
+__global__ void __launch_bounds__(T) k_smooth_tile(TileLaunch tl, MeshView m, State s, Prm prm, SmoothTileView g) {
+    prologuePrioUp<2>();
+    const int tile = launchedTile(tl, (int)blockIdx.x);   // scalar round trip 1: the launch record
+    if (tile < 0) return;
+    // scalar round trip 2 (completed in smoothStage): the meta record, the stop flag -- tested after the staging, see
+    // geomTileBody -- and the arguments of the two staging rounds
+    const SmoothTileMeta tm = loadSmoothMeta(tl.meta, tile);
+    const int stopped = stopWord(tl);
+    scalarBatch(stopped);
     staggerFirstRound((int)blockIdx.x, 256 * 6);
     extern __shared__ double lds[];
-    const int tile = tileList ? ((const_int_ptr)tileList)[li] : li, tid = threadIdx.x;
-    const SmoothTileMeta tm = loadTileMeta(g, tile);
+    const int tid = threadIdx.x;
     const SmoothLds L = smoothLds(lds, tm);
     const SmoothRow R = smoothStage<T>(m, s, g, tm, L, tid);
     if (stopped) return;
+    prologuePrioDown<2>();
     __syncthreads();
     double dist = 0.0;
     int fcount = 0;
@@ -903,13 +970,12 @@ struct PackView {
 // bid: the workgroup's index among the pack workgroups; COHC: see smoothStage (pack role of k_geom_halo); SP: g = the shared
 // points' own tiles (every point of a tile is a shared point; slots and first send slot by tile position)
 template <int T, bool COHC = false, bool SP = false>
-__device__ __forceinline__ void packTileBody(const MeshView& m, const State& s, const SmoothTileView& g, const PackView& pk, const int* tileList, int nLaunch,
-                                             int xcdMap, int bid) {
-    const int li = launchTile(nLaunch, xcdMap, bid);
-    if (li < 0) return;
+__device__ __forceinline__ void packTileBody(const TileLaunch& tl, const MeshView& m, const State& s, const SmoothTileView& g, const PackView& pk, int bid) {
+    const int tile = launchedTile(tl, bid);
+    if (tile < 0) return;
     extern __shared__ double lds[];
-    const int tile = tileList ? ((const_int_ptr)tileList)[li] : li, tid = threadIdx.x;
-    const SmoothTileMeta tm = loadTileMeta(g, tile);
+    const int tid = threadIdx.x;
+    const SmoothTileMeta tm = loadSmoothMeta(tl.meta, tile);
     const SmoothLds L = smoothLds(lds, tm);
     const SmoothRow R = smoothStage<T, COHC, SP ? 2 : 1>(m, s, g, tm, L, tid, SlotTabs{s.spSlot, s.spPeer, s.spDst0, s.spNDst});
     __syncthreads();
@@ -982,11 +1048,10 @@ __device__ __forceinline__ void packTileBody(const MeshView& m, const State& s, 
     }
 }
 template <int T>
-__global__ void __launch_bounds__(T) k_pack_tile(MeshView m, State s, SmoothTileView g, PackView pk, const int* tileList, int nLaunch,
-                                                  int xcdMap, PackLArgs la, int nLBlocks, unsigned tag) {
-    if (s.acc->stop) return;
+__global__ void __launch_bounds__(T) k_pack_tile(TileLaunch tl, MeshView m, State s, SmoothTileView g, PackView pk, PackLArgs la, int nLBlocks, unsigned tag) {
+    if (stopWord(tl)) return;
     if ((int)blockIdx.x < nLBlocks) haloPackLOf(s, la, (int)blockIdx.x * T + (int)threadIdx.x);
-    else packTileBody<T>(m, s, g, pk, tileList, nLaunch, xcdMap, (int)blockIdx.x - nLBlocks);
+    else packTileBody<T>(tl, m, s, g, pk, (int)blockIdx.x - nLBlocks);
     pushSignal(s.push, 0, tag);      // exchange A and L leave together (no-op without the peer-store transport)
 }
 
@@ -1017,14 +1082,16 @@ struct HaloG {
     int debug;                                                    // measurement aid (SMGPU_HALO_DEBUG): 1 = pack role returns at once, 2 = does not wait
 };
 template <int T, bool ORG>
-__global__ void __launch_bounds__(T, (SMGPU_GEOM_WAVES * T) / 256) k_geom_halo(MeshView m, State s, GeomTileView g, int writeFaces, HaloG hg, int xcdMap, int deferN,
+// tl: the geometry tiles' meta table, the stop word and xcdMap; the roles fill in their tile list and count (the pack role its table)
+__global__ void __launch_bounds__(T, (SMGPU_GEOM_WAVES * T) / 256) k_geom_halo(TileLaunch tl, MeshView m, State s, GeomTileView g, int writeFaces, HaloG hg, int deferN,
                                                                               int deferIter, double* deferLocal, double* deferHist, SmoothTileView sg, PackView pk) {
+    const int xcdMap = tl.xcdMap;
     const int bid = (int)blockIdx.x, gS = tileGrid(hg.nGeomS, xcdMap), g1 = tileGrid(hg.nI1, xcdMap), gP = tileGrid(hg.nPack, xcdMap);
     if (bid >= gS + g1 && bid < gS + g1 + gP) {
-        if (s.acc->stop || (hg.debug & 1)) return;
+        if (stopWord(tl) || (hg.debug & 1)) return;
         __builtin_amdgcn_s_setprio(3);      // (a chain of dependent steps the exchange waits for: issue priority over the tiles' waves)
         if (!(hg.debug & 2)) roleWait(hg.ticket, hg.serial, &s.acc->err);
-        packTileBody<T, true, true>(m, s, sg, pk, nullptr, hg.nPack, xcdMap, bid - gS - g1);
+        packTileBody<T, true, true>(TileLaunch{sg.meta, nullptr, tl.stop, hg.nPack, xcdMap}, m, s, sg, pk, bid - gS - g1);
         pushSignal(s.push, 0, hg.tagA, (unsigned)gP);      // exchange A leaves (peer-store transport)
         return;
     }
@@ -1033,7 +1100,7 @@ __global__ void __launch_bounds__(T, (SMGPU_GEOM_WAVES * T) / 256) k_geom_halo(M
     const int* list = first ? hg.geomS : (second ? hg.geomI : hg.geomI + hg.nI1);
     const int n = first ? hg.nGeomS : (second ? hg.nI1 : hg.nGeomI - hg.nI1);
     const int b = first ? bid : (second ? bid - gS : bid - gS - g1 - gP);
-    geomTileBody<T, ORG>(m, s, g, 0, writeFaces, list, n, xcdMap, first ? deferN : 0, deferIter, deferLocal, deferHist, b, first);
+    geomTileBody<T, ORG>(TileLaunch{tl.meta, list, tl.stop, n, xcdMap}, m, s, g, 0, writeFaces, first ? deferN : 0, deferIter, deferLocal, deferHist, b, first);
     if (first) roleDone(hg.ticket, hg.serial, (unsigned)gS >> 3);      // (every workgroup of the role, padding included)
 }
 
@@ -1081,8 +1148,9 @@ __device__ __forceinline__ void haloFixBody(const MeshView& m, const State& s, c
     blockPublish<T>(s, dist, fcount, hf.partialBase + blk);
 }
 template <int T>
-__global__ void __launch_bounds__(T) k_smooth_halo(MeshView m, State s, Prm prm, SmoothTileView g, SmoothTileView sg, HaloS hs, int xcdMap, HaloFix hf) {
-    const int bid = (int)blockIdx.x, tid = threadIdx.x;
+// tl: the regular tiles' meta table and xcdMap (the roles find their tiles themselves; the launch does not read the stop word)
+__global__ void __launch_bounds__(T) k_smooth_halo(TileLaunch tl, MeshView m, State s, Prm prm, SmoothTileView g, SmoothTileView sg, HaloS hs, HaloFix hf) {
+    const int bid = (int)blockIdx.x, tid = threadIdx.x, xcdMap = tl.xcdMap;
     if (bid < hs.gM) {
         if (bid >= hs.nMultiBlocks) return;
         __builtin_amdgcn_s_setprio(3);
@@ -1109,7 +1177,7 @@ __global__ void __launch_bounds__(T) k_smooth_halo(MeshView m, State s, Prm prm,
     if (li < 0 && !spTile) return;
     if (!spTile && !batchA) li += hs.nA;
     const int tile = li >= 0 ? li : 0;      // (a padding workgroup of the shared points' role stages the first tile in vain: it still signals)
-    const SmoothTileMeta tm = loadTileMeta(v, tile);
+    const SmoothTileMeta tm = loadSmoothMeta(spTile ? sg.meta : tl.meta, tile);
     const SmoothLds L = smoothLds(lds, tm);
     if (spTile) {
         // exchange A's combine for the thread's own point, FIRST -- while nothing else is live in registers (the two ranks' records

@@ -51,8 +51,8 @@ static int qualityTraceQueue(smgpu_handle* h, int64_t number, const smgpu_iter_s
                                        h->xcdMap, h->qt.thr, h->qt.cellPart, gate);
                 } else {   // the report's geometry launch: writeFaces, no face averages, and the engine's deferred finish is not this launch's to close
                     ensureDynLds(k_geom_tile<T, ORG>, h->device, h->geomLds);
-                    hipLaunchKernelGGL((k_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, 0, 1,
-                                       (const int*)nullptr, nT, h->xcdMap, 0, 0, (double*)nullptr, (double*)nullptr);
+                    hipLaunchKernelGGL((k_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream,
+                                       tileLaunch(h->gv.meta, ts, nullptr, nT, h->xcdMap), h->mv, ts, h->gv, 0, 1, 0, 0, (double*)nullptr, (double*)nullptr);
                 }
             });
     } else {

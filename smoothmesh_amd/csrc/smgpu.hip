@@ -1300,8 +1300,8 @@ static void withGeomTile(const smgpu_handle* h, F&& f) {
 template <bool FINAL, int T>
 static void launchSmoothTile(smgpu_handle* h, const MeshView& m, const State& s, const Prm& prm, const int* tileList, int nTiles, hipEvent_t evA, hipEvent_t evB) {
     ensureDynLds(k_smooth_tile<FINAL, T>, h->device, h->smoothLds);
-    hipExtLaunchKernelGGL((k_smooth_tile<FINAL, T>), dim3(tileGrid(nTiles, h->xcdMap)), dim3(T), (uint32_t)h->smoothLds, h->stream, evA, evB, 0, m, s, prm, h->sv,
-                          tileList, nTiles, h->xcdMap);
+    hipExtLaunchKernelGGL((k_smooth_tile<FINAL, T>), dim3(tileGrid(nTiles, h->xcdMap)), dim3(T), (uint32_t)h->smoothLds, h->stream, evA, evB, 0,
+                          tileLaunch(h->sv.meta, s, tileList, nTiles, h->xcdMap), m, s, prm, h->sv);
 }
 template <bool FINAL>
 static int launchBndFix(smgpu_handle* h, int partialBase) {
@@ -1384,13 +1384,14 @@ static int runGeometry(smgpu_handle* h, const int* tileList = nullptr, int nList
                     const int nNormal = (h->bv.nB + T - 1) / T, nFeat = (h->bv.nFeat + (T / 64) - 1) / (T / 64);
                     const int nBnd = ((nNormal + nFeat + 7) / 8) * 8;
                     ensureDynLds(k_geom_tile_bnd<T, ORG>, h->device, h->geomLds);
-                    hipExtLaunchKernelGGL((k_geom_tile_bnd<T, ORG>), dim3(nBnd + tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, evA, evB, 0, m, s,
-                                          h->gv, wantAvg, h->writeFaces ? 1 : 0, tileList, nT, h->xcdMap, h->deferN, h->deferIter, h->deferLocal, h->deferHist, h->bv,
-                                          nBnd, nNormal);
+                    hipExtLaunchKernelGGL((k_geom_tile_bnd<T, ORG>), dim3(nBnd + tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, evA, evB, 0,
+                                          tileLaunch(h->gv.meta, s, tileList, nT, h->xcdMap), m, s, h->gv, wantAvg, h->writeFaces ? 1 : 0, h->deferN, h->deferIter,
+                                          h->deferLocal, h->deferHist, h->bv, nBnd, nNormal);
                 } else {
                     ensureDynLds(k_geom_tile<T, ORG>, h->device, h->geomLds);
-                    hipExtLaunchKernelGGL((k_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, evA, evB, 0, m, s, h->gv,
-                                          wantAvg, h->writeFaces ? 1 : 0, tileList, nT, h->xcdMap, h->deferN, h->deferIter, h->deferLocal, h->deferHist);
+                    hipExtLaunchKernelGGL((k_geom_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, evA, evB, 0,
+                                          tileLaunch(h->gv.meta, s, tileList, nT, h->xcdMap), m, s, h->gv, wantAvg, h->writeFaces ? 1 : 0, h->deferN, h->deferIter,
+                                          h->deferLocal, h->deferHist);
                 }
             });
             h->deferN = 0;
@@ -2637,13 +2638,14 @@ static int runMergedGeomPack(smgpu_handle* h) {
     hg.debug = envInt("SMGPU_HALO_DEBUG", 0);
     const PackView pk{h->dOwnA, h->sendA, h->dSendOff, h->dSendSlots, 0};
     const size_t lds = std::max(h->geomLds, h->haloLds);
+    const TileLaunch tl = tileLaunch(h->gv.meta, s, nullptr, 0, h->xcdMap);      // (the roles have their own lists and counts: hg)
     const int rc = launchKDispatch(h, K_GEOM_TILE, [&](hipEvent_t evA, hipEvent_t evB) {
         if (h->foamOrg)
-            hipExtLaunchKernelGGL((k_geom_halo<256, true>), dim3(gS + g1 + gP + g2), dim3(256), (uint32_t)lds, h->stream, evA, evB, 0, m, s, h->gv, h->writeFaces ? 1 : 0, hg,
-                                  h->xcdMap, h->deferN, h->deferIter, h->deferLocal, h->deferHist, h->hv, pk);
+            hipExtLaunchKernelGGL((k_geom_halo<256, true>), dim3(gS + g1 + gP + g2), dim3(256), (uint32_t)lds, h->stream, evA, evB, 0, tl, m, s, h->gv,
+                                  h->writeFaces ? 1 : 0, hg, h->deferN, h->deferIter, h->deferLocal, h->deferHist, h->hv, pk);
         else
-            hipExtLaunchKernelGGL((k_geom_halo<256, false>), dim3(gS + g1 + gP + g2), dim3(256), (uint32_t)lds, h->stream, evA, evB, 0, m, s, h->gv, h->writeFaces ? 1 : 0, hg,
-                                  h->xcdMap, h->deferN, h->deferIter, h->deferLocal, h->deferHist, h->hv, pk);
+            hipExtLaunchKernelGGL((k_geom_halo<256, false>), dim3(gS + g1 + gP + g2), dim3(256), (uint32_t)lds, h->stream, evA, evB, 0, tl, m, s, h->gv,
+                                  h->writeFaces ? 1 : 0, hg, h->deferN, h->deferIter, h->deferLocal, h->deferHist, h->hv, pk);
     });
     h->deferN = 0;
     h->deferLocal = h->deferHist = nullptr;
@@ -2683,7 +2685,8 @@ static int runMergedSmooth(smgpu_handle* h) {
     if (flagged(h)) s.push = h->flagView;
     s.ownF = h->fixInSmooth ? h->dOwnF : nullptr;
     return launchKDispatch(h, K_SMOOTH_FINAL, [&](hipEvent_t evA, hipEvent_t evB) {
-        hipExtLaunchKernelGGL((k_smooth_halo<256>), dim3(grid), dim3(256), (uint32_t)lds, h->stream, evA, evB, 0, h->mv, s, prm, h->sv, h->hv, hs, h->xcdMap, hf);
+        hipExtLaunchKernelGGL((k_smooth_halo<256>), dim3(grid), dim3(256), (uint32_t)lds, h->stream, evA, evB, 0,
+                              tileLaunch(h->sv.meta, s, nullptr, 0, h->xcdMap), h->mv, s, prm, h->sv, h->hv, hs, hf);
     });
 }
 
@@ -2741,9 +2744,10 @@ int smgpu_iter_begin(smgpu_handle* h) {
                     // exchange L's records are packed by the first workgroups of the same launch
                     const int T = h->smoothT, nL = withL ? (((h->nShared + T - 1) / T + 7) / 8) * 8 : 0;
                     const dim3 grid(nL + tileGrid(h->nSharedTiles, h->xcdMap));
-                    if (T == 64) hipLaunchKernelGGL(k_pack_tile<64>, grid, dim3(64), h->smoothLds, h->stream, m, s, h->sv, pk, h->dSharedTiles, h->nSharedTiles, h->xcdMap, la, nL, tag);
-                    else if (T == 128) hipLaunchKernelGGL(k_pack_tile<128>, grid, dim3(128), h->smoothLds, h->stream, m, s, h->sv, pk, h->dSharedTiles, h->nSharedTiles, h->xcdMap, la, nL, tag);
-                    else hipLaunchKernelGGL(k_pack_tile<256>, grid, dim3(256), h->smoothLds, h->stream, m, s, h->sv, pk, h->dSharedTiles, h->nSharedTiles, h->xcdMap, la, nL, tag);
+                    const TileLaunch tl = tileLaunch(h->sv.meta, s, h->dSharedTiles, h->nSharedTiles, h->xcdMap);
+                    if (T == 64) hipLaunchKernelGGL(k_pack_tile<64>, grid, dim3(64), h->smoothLds, h->stream, tl, m, s, h->sv, pk, la, nL, tag);
+                    else if (T == 128) hipLaunchKernelGGL(k_pack_tile<128>, grid, dim3(128), h->smoothLds, h->stream, tl, m, s, h->sv, pk, la, nL, tag);
+                    else hipLaunchKernelGGL(k_pack_tile<256>, grid, dim3(256), h->smoothLds, h->stream, tl, m, s, h->sv, pk, la, nL, tag);
                 } else {
                     hipLaunchKernelGGL(k_halo_packA, dim3(gridFor(h->nShared)), dim3(kBlock), 0, h->stream, m, s, h->dSharedLocal, h->dOwnA, h->nShared,
                                        h->dSendOff, h->dSendSlots, h->sendA, h->bndOn ? 1 : 0);
