@@ -12,4 +12,4 @@ if "--cold" not in sys.argv:      # the HIP runtime's own first-use work (queues
     t1 = time.perf_counter()
 eng = SmoothEngine(mesh, device=0); t2 = time.perf_counter()
 gb = eng.sizes()["deviceBytes"] / 1e9
-print(f"{wl}: mesh generation {t1-t0:.2f} s, find_internal_points+smgpu_create {t2-t1:.2f} s, points {mesh.nPoints}, device bytes {gb:.2f} GB")
+print(f"{wl}: mesh generation {t1-t0:.2f} s, find_internal_points+smgpu_create {t2-t1:.3f} s, points {mesh.nPoints}, device bytes {gb:.2f} GB")

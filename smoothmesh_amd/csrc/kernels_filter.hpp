@@ -284,8 +284,6 @@ struct EdgeTileView {
     const int* meta;             // per-tile scalars, one record per tile (EdgeTileMeta)
     int maxPoints, maxFaces, maxCells;
 };
-struct EdgeTileMeta { int edgeBeg, nEdges, tpOff, nPts, tfOff, nFaces, tcOff, nCells, efBase, efWidth, ecBase, ecWidth; };
-constexpr int kEdgeMetaInts = 12;
 __device__ __forceinline__ EdgeTileMeta loadTileMeta(const EdgeTileView& g, int tile) {
     const_int_ptr p = (const_int_ptr)(g.meta + (size_t)kEdgeMetaInts * tile);
     EdgeTileMeta t;

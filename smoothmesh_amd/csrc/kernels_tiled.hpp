@@ -4,6 +4,7 @@
 // per lane per load), all indexed access is in LDS.
 #pragma once
 #include "kernels.hpp"
+#include "tile_meta.hpp"
 
 // -DSMGPU_STAGGER=<n> (experiment): the workgroups of a launch's FIRST round start n x 64 cycles apart per wave slot, so that the
 // workgroups sharing a CU are not all staging (or all computing) at the same time
@@ -41,8 +42,7 @@ struct GeomTileView {
 // One tile's scalars, fetched with scalar loads through the constant address space (the tables are written by the host
 // before the first launch).  Read from the separate arrays with ordinary loads -- the compiler cannot prove them
 // invariant -- they were a chain of dependent vector-memory round trips in front of the staging.
-struct GeomTileMeta { int tpOff, nPts, tfOff, nFaces, fvBase, fvWidth, cellBeg, nCells, cfBase, cfWidth, flags, pad; };
-constexpr int kGeomMetaInts = 12;
+// (the record: GeomTileMeta, tile_meta.hpp)
 typedef const __attribute__((address_space(4))) int* const_int_ptr;
 __device__ __forceinline__ GeomTileMeta loadGeomMeta(const int* meta, int tile) {
     const_int_ptr p = (const_int_ptr)(meta + (size_t)kGeomMetaInts * tile);
@@ -76,8 +76,6 @@ __device__ __forceinline__ SmoothTileView pickView(bool a, const SmoothTileView&
     return v;
 }
 
-struct SmoothTileMeta { int ptBeg, nPts, tcOff, nCells, tnOff, nNbrs, pcBase, pcWidth, ppBase, ppWidth, pfBase, pfWidth; };
-constexpr int kSmoothMetaInts = 12;
 __device__ __forceinline__ SmoothTileMeta loadSmoothMeta(const int* meta, int tile) {
     const_int_ptr p = (const_int_ptr)(meta + (size_t)kSmoothMetaInts * tile);
     SmoothTileMeta t;

@@ -11,7 +11,6 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "kernels.hpp"
@@ -139,6 +138,7 @@ struct smgpu_handle {
     PushView flagView{};
     bool mergedIter = false;                        // this iteration's geometry + pack went out as k_geom_halo
     // LDS staging tiles (tiles.hpp)
+    TilePlan plan;             // their knobs, read once (setup_tiles.hpp: makeTilePlan)
     bool useTiles = false;
     int geomT = 128, smoothT = 256;
     GeomTiles gt;
@@ -455,61 +455,8 @@ static void computeAlgoBytes(smgpu_handle* h) {
     h->algoF64[K_GEOM_TILE] = ops;
 }
 
-// the device view of a set of smoothing tiles (the shared points' own tiles, smgpu_halo_configure)
-// Records a tile may stage in total: its LDS footprint, which is what sets the kernels' occupancy (the LDS is allocated in
-// 512-byte steps).  Smoothing tiles of 256 points: 1 112 records of 24 bytes = 26.7 KB -- SIX workgroups per CU; the greedy pass
-// otherwise reaches 512 cells + 619..623 neighbours on the large meshes = 27.2 KB and five (same box, alternating three times: gather
-// kernel 335.4 -> 329.4 us on the 10 M-cell polyhedral mesh, 340.1 -> 333.0 us on hex215; the 1 M-cell block sits below by itself).
-// Edge tiles of 256 edges: 852 records = 20 448 B -- EIGHT workgroups of the face-angle filter per CU instead of seven (the
-// face-angle group 716 -> 705 us on the 10 M-cell mesh, the iteration 3.066 -> 3.047 ms; a tighter cap makes too many tiles: 720 us).
-// largest sum over the tiles of the entries of some per-tile offset lists (a tile's staged records of all kinds)
-static size_t maxTileTotal(int nTiles, std::initializer_list<const std::vector<int32_t>*> offs) {
-    size_t mx = 0;
-    for (int t = 0; t < nTiles; ++t) {
-        size_t n = 0;
-        for (const std::vector<int32_t>* o : offs) n += (size_t)((*o)[(size_t)t + 1] - (*o)[(size_t)t]);
-        mx = std::max(mx, n);
-    }
-    return mx;
-}
-// Geometry tiles: 3 x points + 7 x faces doubles; 3 980 = 31 840 B -- five workgroups per CU (32 256 B each with the kernel's 48
-// static bytes at the 512-byte granularity), which the kernel's 96 VGPRs (SMGPU_GEOM_WAVES = 5) allow.  A hexahedral tile of 128
-// cells (~250 points, ~450 faces = 3 900) fits as it is; the polyhedral ones are cut a little earlier.
-static int defaultGeomCapWeighted(int T) { return (T == 256 && SMGPU_GEOM_WAVES >= 5) ? 3980 : 0x7fffffff; }
-static int defaultSmoothCapTotal(int T) { return T == 256 ? 1112 : 0x7fffffff; }
-static int defaultEdgeCapTotal() { return 852; }
-
-static int uploadSmoothView(smgpu_handle* h, const SmoothTiles& st, SmoothTileView& v, int usePairShare) {
-    int rc = 0;
-    rc |= devUpload(h, &v.ptOrder, st.order);
-    rc |= devUpload(h, &v.ptBeg, st.ptBeg);
-    rc |= devUpload(h, &v.tcOff, st.tcOff);
-    rc |= devUpload(h, &v.tcIds, st.tcIds);
-    rc |= devUpload(h, &v.tnOff, st.tnOff);
-    rc |= devUpload(h, &v.tnIds, st.tnIds);
-    rc |= devUpload(h, &v.selfLoc, st.selfLoc);
-    rc |= devUpload(h, &v.pcBase, st.pcBase);
-    rc |= devUpload(h, &v.pcWidth, st.pcWidth);
-    rc |= devUpload(h, &v.pcEll, st.pcEll);
-    rc |= devUpload(h, &v.ppBase, st.ppBase);
-    rc |= devUpload(h, &v.ppWidth, st.ppWidth);
-    rc |= devUpload(h, &v.ppEll, st.ppEll);
-    rc |= devUpload(h, &v.pairEll, st.pairEll);
-    rc |= devUpload(h, &v.pfBase, st.pfBase);
-    rc |= devUpload(h, &v.pfWidth, st.pfWidth);
-    rc |= devUpload(h, &v.pfEll, st.pfEll);
-    std::vector<int> meta((size_t)kSmoothMetaInts * (size_t)std::max(st.nTiles, 1), 0);
-    for (int t = 0; t < st.nTiles; ++t) {
-        int* r = meta.data() + (size_t)kSmoothMetaInts * t;
-        r[0] = st.ptBeg[t]; r[1] = st.ptBeg[t + 1] - st.ptBeg[t]; r[2] = st.tcOff[t]; r[3] = st.tcOff[t + 1] - st.tcOff[t];
-        r[4] = st.tnOff[t]; r[5] = st.tnOff[t + 1] - st.tnOff[t]; r[6] = st.pcBase[t]; r[7] = st.pcWidth[t];
-        r[8] = st.ppBase[t]; r[9] = st.ppWidth[t]; r[10] = st.pfBase[t]; r[11] = st.pfWidth[t];
-    }
-    rc |= devUpload(h, &v.meta, meta);
-    v.maxCells = st.maxCells; v.maxPoints = st.maxPoints;
-    v.usePairShare = usePairShare;
-    return rc;
-}
+#include "setup_tiles.hpp"
+#include "setup_create.hpp"
 
 extern "C" {
 
@@ -523,588 +470,53 @@ static int ensureHostLists(smgpu_handle* h, int groups) {
     return downloadDeferredLists(h->topo, h->devLists, h->device, why, groups) ? fail("device -> host copy of the addressing: " + why) : 0;
 }
 
-// A device build's owner / neighbour arrays are read by the device builds of the tile tables only and never join the handle's
-// allocation list: freed once those builds are joined (and on every failure path).
-static void freeOwnerNeighbour(DeviceTopologyArrays& dt) {
-    for (DeviceTopologyArrays::Arr* a : {&dt.owner, &dt.neighbour})
-        if (a->p) { (void)hipFree(a->p); a->p = nullptr; a->bytes = 0; }
-}
-static void freeDevTopo(DeviceTopologyArrays& dt) {
-    freeOwnerNeighbour(dt);
-    for (DeviceTopologyArrays::Arr* a : {&dt.faceOff, &dt.facePts, &dt.cfOff, &dt.cfVal, &dt.pcOff, &dt.pcVal, &dt.ppOff, &dt.ppPt, &dt.peEdge, &dt.pfOff, &dt.pfFace,
-                                         &dt.pfPrev, &dt.pfNext, &dt.pfPrevSlot, &dt.pfNextSlot, &dt.ringFace, &dt.ringCell, &dt.edgeRingOk, &dt.edges, &dt.efOff,
-                                         &dt.efFace, &dt.ecOff, &dt.ecCell, &dt.ecF0, &dt.ecF1})
-        if (a->p) { (void)hipFree(a->p); a->p = nullptr; a->bytes = 0; }
-    dt.valid = false;
-}
-
 int smgpu_create(const smgpu_mesh_desc* d, smgpu_handle** out) {
     if (!d || !out) return fail("smgpu_create: null argument");
     *out = nullptr;
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) return fail("smgpu_create: no HIP device available");
     if (d->device < 0 || d->device >= nDev) return fail("smgpu_create: device ordinal out of range");
-    smgpu_handle* h = new smgpu_handle();
+    // every way out below is a plain return: the tasks (declared behind the handle's guard) are joined and what they still own is
+    // freed, then the handle goes
+    std::unique_ptr<smgpu_handle, int (*)(smgpu_handle*)> guard(new smgpu_handle(), smgpu_destroy);
+    SetupTasks tasks;
+    smgpu_handle* h = guard.get();
     h->device = d->device;
-    const auto tCreate0 = std::chrono::steady_clock::now();
-    setupClockStart() = tCreate0;
-    auto sinceCreate = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - tCreate0).count(); };
-    // The one-off host work is pipelined: the Z-curve of the points (needs the coordinates only) starts at once; the geometry
-    // tile tables start as soon as the cell -> face lists stand (Topology::build's afterCells hook) and are built next to the
-    // rest of the addressing; the smoothing and edge tile tables follow the addressing, side by side.
-    const bool wantTiles = envInt("SMGPU_TILES", 1) != 0;
-    const bool mortonTiles = envInt("SMGPU_TILE_MORTON", 1) != 0;
-    // Lattice Z-curve keys by default on meshes of hexahedra alone, bounding-box keys on the others; SMGPU_TILE_LATTICE = 1 / 0 forces
-    // either on any mesh (tiles.hpp, tileLatticeKnob: the measurements behind the default)
-    const bool allHex = tileLatticeDefault(d->nCells, d->nFaces, d->nInternalFaces, d->nFaces > 0 ? (int64_t)d->faceOffsets[d->nFaces] - d->faceOffsets[0] : 0);
-    const bool latticeKeys = tileLatticeKnob(allHex);
-    h->gt.latticeKeys = h->stl.latticeKeys = h->etl.latticeKeys = latticeKeys;
-    std::future<std::vector<int32_t>> fPointOrder;
-    if (wantTiles && mortonTiles) fPointOrder = std::async(std::launch::async, [&] { return mortonOrderOf(d->nPoints, d->points, latticeKeys); });
-    std::future<std::string> fGeom, fSmooth, fEdge;
-    std::function<void()> startEdge;
-    CornerChains chains;       // (tiles_dev.hip; released by the smoothing task's device build, or below)
-    struct ChainsGuard { CornerChains& c; std::future<std::string>& f; ~ChainsGuard() { if (f.valid()) f.wait(); releaseCornerChains(c); } } chainsGuard{chains, fSmooth};
-    static const char* const kHostTablesPending = "\x01host tables pending";      // a tile task of a device build that leaves its tables to the host
-    std::vector<int32_t> pointOrder;
-    std::vector<uint8_t> internalMask;
-    DeviceTopologyArrays devTopo;      // a device build's arrays: the kernels read them as they are (no upload of the host copy)
-    {
-        const int geomT0 = envInt("SMGPU_GEOM_T", 256), smoothT0 = envInt("SMGPU_SMOOTH_T", 256);
-        const int geomCells0 = envInt("SMGPU_GEOM_CELLS", geomT0 / 2);
-        const int capGP0 = envInt("SMGPU_GEOM_CAPP", std::min(6 * geomCells0, 1400)), capGF0 = envInt("SMGPU_GEOM_CAPF", std::min(4 * geomCells0, 1400));
-        const int capSC0 = envInt("SMGPU_SMOOTH_CAPC", std::min(2 * smoothT0, 1500)), capSN0 = envInt("SMGPU_SMOOTH_CAPN", std::min(3 * smoothT0, 1500));
-        const bool geomOk = geomT0 == 64 || geomT0 == 128 || geomT0 == 256, smoothOk = smoothT0 == 64 || smoothT0 == 128 || smoothT0 == 256;
-        // tile boundaries on the host, the tables on the device where the addressing was built there (tiles_dev.hip), else on the host
-        // (SMGPU_DEVICE_TILES=2: as if the device builds handed their tables back -- the tests' way into that path)
-        const bool devTiles = envInt("SMGPU_DEVICE_TILES", 1) != 0;
-        const auto afterCells = [&] {
-                      // (the corner chains of the smoothing tables need the device addressing only: started here, they run beside the
-                      // rest of the download and the host's boundary passes)
-                      if (wantTiles && geomOk && smoothOk && devTiles && devTopo.valid && envInt("SMGPU_DEVICE_TILES", 1) == 1) {
-                          std::string why;
-                          if (startCornerChains(devTopo, d->nPoints, h->device, chains, why) == 2) chains = CornerChains();
-                      }
-                      if (wantTiles && geomOk) fGeom = std::async(std::launch::async, [&, geomT0, geomCells0, capGP0, capGF0, devTiles]() -> std::string {
-                      std::vector<int32_t> cellOrder;      // (a device build: the Z-curve of the cells there too -- the order the host would find)
-                      if (mortonTiles && devTiles && devTopo.valid && envInt("SMGPU_DEVICE_TILES", 1) == 1) {
-                          std::string why;
-                          if (cellMortonOrderOnDevice(devTopo, d->nCells, d->nPoints, d->points, h->device, cellOrder, why, latticeKeys) != 0) cellOrder.clear();
-                      }
-                      const std::string e = h->gt.buildBoundaries(h->topo, d->points, mortonTiles, geomT0, geomCells0, capGP0, capGF0,
-                                                                  envInt("SMGPU_GEOM_CAPWEIGHTED", defaultGeomCapWeighted(geomT0)), SMGPU_GEOM_AOS ? kGF : 6,
-                                                                  cellOrder.empty() ? nullptr : &cellOrder);
-                      if (!e.empty()) return e;
-                      if (devTopo.valid && !devTiles) return std::string(kHostTablesPending);      // (the host's lists are still arriving)
-                      if (devTopo.valid) {
-                          std::string why;
-                          const auto t0 = std::chrono::steady_clock::now();
-                          const int rc = envInt("SMGPU_DEVICE_TILES", 1) == 2 ? 1 : buildGeomTablesOnDevice(h->gt, devTopo, d->nCells, h->device, h->gtDev, why);
-                          if (envInt("SMGPU_VERBOSE", 0) >= 2)
-                              std::fprintf(stderr, "[smgpu] geometry tiles: tables on the %s %.2f s   (done at +%.3f s)\n", rc == 0 ? "device" : "host (device build handed them back)",
-                                           std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), setupClock());
-                          if (rc == 0) return std::string();
-                          return rc == 2 ? "device tile tables: " + why : std::string(kHostTablesPending);      // (the host's lists are still arriving)
-                      }
-                      return h->gt.buildTables(h->topo); }); };
-        const auto afterPoints = [&] {
-                if (!(wantTiles && geomOk && smoothOk)) return;
-                if (fPointOrder.valid()) pointOrder = fPointOrder.get();
-                internalMask.resize((size_t)d->nPoints);
-                for (int p = 0; p < d->nPoints; ++p) internalMask[(size_t)p] = d->isInternalPoint[p] ? 1 : 0;
-                h->isInternalHost = internalMask;
-                fSmooth = std::async(std::launch::async, [&, smoothT0, capSC0, capSN0, devTiles]() -> std::string {
-                    const std::string e = h->stl.buildBoundaries(h->topo, d->points, mortonTiles, smoothT0, capSC0, capSN0, (mortonTiles && !pointOrder.empty()) ? &pointOrder : nullptr, nullptr,
-                                                                  envInt("SMGPU_SMOOTH_CAPTOTAL", defaultSmoothCapTotal(smoothT0)));
-                    if (!e.empty()) return e;
-                    if (devTopo.valid && !devTiles) return std::string(kHostTablesPending);
-                    if (devTopo.valid) {
-                        std::string why;
-                        const auto t0 = std::chrono::steady_clock::now();
-                        const int rc = envInt("SMGPU_DEVICE_TILES", 1) == 2 ? 1 : buildSmoothTablesOnDevice(h->stl, devTopo, d->nPoints, h->topo.maxPointPoints, internalMask.data(), h->device, h->stDev, why, &chains);
-                        if (envInt("SMGPU_VERBOSE", 0) >= 2)
-                            std::fprintf(stderr, "[smgpu] smoothing tiles: tables on the %s %.2f s   (done at +%.3f s)\n", rc == 0 ? "device" : "host (device build handed them back)",
-                                         std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), setupClock());
-                        if (rc == 0) return std::string();
-                        return rc == 2 ? "device tile tables: " + why : std::string(kHostTablesPending);
-                    }
-                    return h->stl.buildTables(h->topo, internalMask.data()); });
-            };
-        // the edge tiles (face-angle filter): behind the edge lists of a device build (its afterEdges hook), else behind the addressing
-        startEdge = [&, devTiles] {
-            if (!wantTiles) return;
-            if (fPointOrder.valid()) pointOrder = fPointOrder.get();
-            const std::vector<int32_t>* po = (mortonTiles && !pointOrder.empty()) ? &pointOrder : nullptr;
-            const bool wantFilter = envInt("SMGPU_FILTER", 1) != 0;
-            const bool devTilesE = devTiles && devTopo.valid, devLists = devTopo.valid;
-            const DeviceTopologyArrays* dt = &devTopo;
-            fEdge = std::async(std::launch::async, [h, d, po, wantFilter, mortonTiles, devTilesE, devLists, dt]() -> std::string {
-                if (!wantFilter) return std::string("not built");
-                const std::string e = h->etl.buildBoundaries(h->topo, d->points, mortonTiles, 256, envInt("SMGPU_EDGE_CAPP", 512), envInt("SMGPU_EDGE_CAPF", 768), envInt("SMGPU_EDGE_CAPC", 512), po,
-                                                                  envInt("SMGPU_EDGE_CAPTOTAL", defaultEdgeCapTotal()));
-                if (!e.empty()) return e;
-                if (devLists && !devTilesE) return std::string(kHostTablesPending);
-                if (devTilesE) {
-                    std::string why;
-                    const auto t0 = std::chrono::steady_clock::now();
-                    const int rc = envInt("SMGPU_DEVICE_TILES", 1) == 2 ? 1 : buildEdgeTablesOnDevice(h->etl, *dt, h->topo.nEdges, h->device, h->etDev, why);
-                    if (envInt("SMGPU_VERBOSE", 0) >= 2)
-                        std::fprintf(stderr, "[smgpu] edge tiles: tables on the %s %.2f s   (done at +%.3f s)\n", rc == 0 ? "device" : "host (device build handed them back)",
-                                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), setupClock());
-                    if (rc == 0) return std::string();
-                    return rc == 2 ? "device tile tables: " + why : std::string(kHostTablesPending);
-                }
-                return h->etl.buildTables(h->topo);
-            });
-        };
-        // the addressing on the device (topology_dev.hip: sorts + per-edge kernels, ~0.2 s for 10 M cells against 3.5 s of host
-        // loops); the host build where the device path hands the mesh back (unusual meshes; it also words the reference's errors)
-        std::string terr;
-        int dev = envInt("SMGPU_DEVICE_TOPOLOGY", 1) ? 1 : -1;
-        if (dev > 0) {
-            std::string why;
-            dev = buildTopologyOnDevice(h->topo, d->nPoints, d->nCells, d->nFaces, d->nInternalFaces, d->faceOffsets, d->facePoints, d->owner, d->neighbour, h->device, why,
-                                        afterCells, afterPoints, &devTopo, startEdge, devTiles && wantTiles);
-            if (dev == 2) {
-                if (fGeom.valid()) fGeom.wait();
-                if (fSmooth.valid()) fSmooth.wait();
-                if (fEdge.valid()) fEdge.wait();
-                if (fPointOrder.valid()) fPointOrder.wait();
-                freeDevTopo(devTopo);       // (arrays the failed device build had already handed over)
-                delete h;
-                return fail("smgpu_create: device addressing: " + why);
-            }
-            if (envInt("SMGPU_VERBOSE", 0) >= 1) std::fprintf(stderr, "[smgpu] addressing on the %s (%.2f s since create)\n", dev == 0 ? "device" : "host (device path handed the mesh back)", sinceCreate());
-        }
-        if (dev != 0) {
-            h->topo = Topology();
-            terr = h->topo.build(d->nPoints, d->nCells, d->nFaces, d->nInternalFaces, d->faceOffsets, d->facePoints, d->owner, d->neighbour, afterCells, afterPoints);
-        }
-        if (!terr.empty()) {
-            if (fGeom.valid()) fGeom.wait();
-            if (fSmooth.valid()) fSmooth.wait();
-            if (fPointOrder.valid()) fPointOrder.wait();
-            delete h;
-            return fail("smgpu_create: " + terr);
-        }
-        if (!fEdge.valid()) startEdge();
-    }
-    bool devAdopted = false;
-    auto cleanup = [&](int rc) {   // (the host threads still read the handle's tables)
-        if (fGeom.valid()) fGeom.wait();
-        if (fSmooth.valid()) fSmooth.wait();
-        if (fPointOrder.valid()) fPointOrder.wait();
-        if (fEdge.valid()) fEdge.wait();
-        if (!devAdopted) freeDevTopo(devTopo);      // a device build's arrays the handle has not taken over yet
-        else freeOwnerNeighbour(devTopo);           // (never adopted: only the tile-table builds read them)
-        smgpu_destroy(h);
-        return rc;
-    };
-    if (hipSetDevice(h->device) != hipSuccess) return cleanup(fail("hipSetDevice failed"));
+    setupClockStart() = std::chrono::steady_clock::now();
+    // plan
+    h->plan = makeTilePlan(d);
+    const TilePlan& plan = h->plan;
+    // the tile tasks and the addressing
+    if (startTasksAndAddressing(h, d, tasks)) return 1;
+    // stream
+    if (hipSetDevice(h->device) != hipSuccess) return fail("hipSetDevice failed");
     if (d->useCallerStream) h->stream = (hipStream_t)d->stream;
     else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return cleanup(fail("hipStreamCreate failed"));
+        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
         h->ownStream = true;
     }
-    const Topology& t = h->topo;
-    MeshView& m = h->mv;
-    const double tTopo = sinceCreate();
+    const double tTopo = setupClock();
     double tLap = tTopo;
-    auto lapC = [&](const char* what) { if (envInt("SMGPU_VERBOSE", 0) >= 2) { const double now = sinceCreate(); std::fprintf(stderr, "[smgpu] create: %-28s %.3f s   (at +%.3f s)\n", what, now - tLap, now); tLap = now; } };
-    auto cleanupE = [&](int rc0) { if (fEdge.valid()) fEdge.wait(); return cleanup(rc0); };
-    m.nPoints = t.nPoints; m.nCells = t.nCells; m.nFaces = t.nFaces; m.nInternalFaces = t.nInternalFaces; m.nEdges = t.nEdges;
-    std::vector<uint8_t> flags(t.nPoints);
-    for (int p = 0; p < t.nPoints; ++p)
-        flags[p] = (d->isInternalPoint[p] ? PF_INTERNAL : 0) |
-                   ((d->isSmoothingSurfacePoint && d->isSmoothingSurfacePoint[p]) ? PF_SMOOTHSURF : 0);
-    int rc = 0;
-    // the addressing on the device: a device build's own arrays (topology_dev.hip), else uploads of the host build's lists
-    auto adopt = [&](auto*& dst, const DeviceTopologyArrays::Arr& a) { dst = (std::remove_reference_t<decltype(dst)>)a.p; h->allocs.push_back(a.p); h->deviceBytes += (int64_t)a.bytes; };
-    if (devTopo.valid) {
-        devAdopted = true;
-        h->devLists = devTopo;
-        adopt(m.faceOff, devTopo.faceOff);
-        adopt(m.facePts, devTopo.facePts);
-        adopt(m.cfOff, devTopo.cfOff);
-        adopt(m.cfVal, devTopo.cfVal);
-        adopt(m.pcOff, devTopo.pcOff);
-        adopt(m.pcVal, devTopo.pcVal);
-        adopt(m.ppOff, devTopo.ppOff);
-        adopt(m.ppPt, devTopo.ppPt);
-        adopt(m.peEdge, devTopo.peEdge);
-        adopt(m.pfOff, devTopo.pfOff);
-        adopt(m.pfFace, devTopo.pfFace);
-        adopt(m.pfPrev, devTopo.pfPrev);
-        adopt(m.pfNext, devTopo.pfNext);
-        adopt(m.pfPrevSlot, devTopo.pfPrevSlot);
-        adopt(m.pfNextSlot, devTopo.pfNextSlot);
-        adopt(m.ringFace, devTopo.ringFace);
-        adopt(m.ringCell, devTopo.ringCell);
-        adopt(m.edgeRingOk, devTopo.edgeRingOk);
-        adopt(m.edges, devTopo.edges);
-        adopt(m.efOff, devTopo.efOff);
-        adopt(m.efFace, devTopo.efFace);
-        adopt(m.ecOff, devTopo.ecOff);
-        adopt(m.ecCell, devTopo.ecCell);
-        adopt(m.ecF0, devTopo.ecF0);
-        adopt(m.ecF1, devTopo.ecF1);
-    } else {
-        rc |= devUpload(h, &m.faceOff, t.facePoints.off);
-        rc |= devUpload(h, &m.facePts, t.facePoints.val);
-        rc |= devUpload(h, &m.cfOff, t.cellFacesGeom.off);
-        rc |= devUpload(h, &m.cfVal, t.cellFacesGeom.val);
-        rc |= devUpload(h, &m.pcOff, t.pointCells.off);
-        rc |= devUpload(h, &m.pcVal, t.pointCells.val);
-        rc |= devUpload(h, &m.ppOff, t.pointEdges.off);
-        rc |= devUpload(h, &m.ppPt, t.pointPoints);
-        rc |= devUpload(h, &m.peEdge, t.pointEdges.val);
-        rc |= devUpload(h, &m.pfOff, t.pointFaces.off);
-        rc |= devUpload(h, &m.pfFace, t.pointFaces.val);
-        rc |= devUpload(h, &m.pfPrev, t.pfPrev);
-        rc |= devUpload(h, &m.pfNext, t.pfNext);
-        rc |= devUpload(h, &m.pfPrevSlot, t.pfPrevSlot);
-        rc |= devUpload(h, &m.pfNextSlot, t.pfNextSlot);
-        rc |= devUpload(h, &m.ringFace, t.ringFace);
-        rc |= devUpload(h, &m.ringCell, t.ringCell);
-        rc |= devUpload(h, &m.edgeRingOk, t.edgeRingOk);
-        rc |= devUpload(h, &m.edges, t.edges);
-        rc |= devUpload(h, &m.efOff, t.edgeFaces.off);
-        rc |= devUpload(h, &m.efFace, t.edgeFaces.val);
-        rc |= devUpload(h, &m.ecOff, t.edgeCells.off);
-        rc |= devUpload(h, &m.ecCell, t.edgeCells.val);
-        rc |= devUpload(h, &m.ecF0, t.ecFace0);
-        rc |= devUpload(h, &m.ecF1, t.ecFace1);
-    }
-    rc |= devUpload(h, &m.pflags, flags);
-    if (rc) return cleanupE(1);
+    const std::function<void(const char*)> lapC = [&](const char* what) { if (plan.verbose >= 2) { const double now = setupClock(); std::fprintf(stderr, "[smgpu] create: %-28s %.3f s   (at +%.3f s)\n", what, now - tLap, now); tLap = now; } };
+    // the addressing, the tile sets
+    if (installAddressing(h, d, tasks)) return 1;
     lapC("addressing adopted / uploaded");
-    // LDS staging tiles; SMGPU_TILES=0 keeps the direct-gather kernels (A/B and fallback)
-    h->useTiles = envInt("SMGPU_TILES", 1) != 0;
-    h->useFilter = envInt("SMGPU_FILTER", 1) != 0;
-    h->xcdMap = envInt("SMGPU_XCD_MAP", 1) != 0;
-    h->walkStar = envInt("SMGPU_WALK_STAR", 1) != 0;
-    h->starBlocks = std::max(1, envInt("SMGPU_STAR_BLOCKS", 256 * 32));
-    h->walkPack = envInt("SMGPU_WALK_PACK", 1) != 0;
-    h->walkCache = envInt("SMGPU_WALK_CACHE", 1) != 0;
-    h->faLists = envInt("SMGPU_FA_LISTS", 1) != 0;
-    h->faSideExact = envInt("SMGPU_FA_SIDE_EXACT", 1) != 0;
-    h->bndInGeom = envInt("SMGPU_BND_IN_GEOM", 1) != 0;
-    h->qt.fusedWanted = envInt("SMGPU_QUALITY_TRACE_FUSED", 1) != 0;
-    { const char* fv = std::getenv("SMGPU_FOAM_VARIANT"); h->foamOrg = fv && std::string(fv) == "org"; }
-    { const char* sv = std::getenv("SMGPU_SYNC_VARIANT"); h->st.ownFold = (sv && std::string(sv) == "own") ? 1 : 0; }
-    if (h->useTiles) {
-        h->geomT = envInt("SMGPU_GEOM_T", 256);
-        h->smoothT = envInt("SMGPU_SMOOTH_T", 256);
-        if (h->geomT != 64 && h->geomT != 128 && h->geomT != 256) return cleanupE(fail("SMGPU_GEOM_T must be 64, 128 or 256"));
-        if (h->smoothT != 64 && h->smoothT != 128 && h->smoothT != 256) return cleanupE(fail("SMGPU_SMOOTH_T must be 64, 128 or 256"));
-        // capacities sized for a 160 KiB LDS: a tile must leave room for >= 2 workgroups per CU
-        const int geomCells = envInt("SMGPU_GEOM_CELLS", h->geomT / 2);   // cells per tile (<= threads)
-        const int capGP = envInt("SMGPU_GEOM_CAPP", std::min(6 * geomCells, 1400));
-        const int capGF = envInt("SMGPU_GEOM_CAPF", std::min(4 * geomCells, 1400));   // two rounds of 256 face threads at 128 cells
-        const int capSC = envInt("SMGPU_SMOOTH_CAPC", std::min(2 * h->smoothT, 1500));
-        const int capSN = envInt("SMGPU_SMOOTH_CAPN", std::min(3 * h->smoothT, 1500));
-        // (the geometry and smoothing tables were started by the addressing's hooks, the edge tables behind it; SMGPU_GEOM_T etc. were read there)
-        (void)geomCells; (void)capGP; (void)capGF; (void)capSC; (void)capSN;
-        std::string e2 = fSmooth.valid() ? fSmooth.get() : std::string("not built");
-        std::string e1 = fGeom.valid() ? fGeom.get() : std::string("not built");
-        std::string e3 = fEdge.valid() ? fEdge.get() : std::string("not built");
-        // (a device build that handed a table set back: the host builds it now that all of its lists have arrived)
-        if (e1 == kHostTablesPending) e1 = h->gt.buildTables(h->topo);
-        std::string whyD;
-        if (e2 == kHostTablesPending) e2 = downloadDeferredLists(h->topo, devTopo, h->device, whyD, 1) ? "device -> host copy of the addressing: " + whyD : h->stl.buildTables(h->topo, internalMask.data());
-        if (e3 == kHostTablesPending) e3 = downloadDeferredLists(h->topo, devTopo, h->device, whyD, 2) ? "device -> host copy of the addressing: " + whyD : h->etl.buildTables(h->topo);
-        if (envInt("SMGPU_VERBOSE", 0))
-            std::fprintf(stderr, "[smgpu] set-up: addressing %.2f s, tile tables (3 host threads) %.2f s\n", tTopo, sinceCreate() - tTopo);
-        freeOwnerNeighbour(devTopo);      // read by the device builds of the tile tables only, all joined now (4 (nFaces + nInternalFaces) bytes)
-        lapC("tile tasks joined");
-        if (!e1.empty() || !e2.empty()) {
-            h->useTiles = false;   // meshes with huge cells / valences: direct-gather kernels still apply
-        } else {
-            GeomTileView& g = h->gv;
-            SmoothTileView& v = h->sv;
-            auto adoptT = [&](auto*& dst, const GeomTilesDev::Arr& a) { dst = (std::remove_reference_t<decltype(dst)>)a.p; h->allocs.push_back(a.p); h->deviceBytes += (int64_t)a.bytes; };
-            if (h->gtDev.valid) {      // a device build's tables stay where they are
-                adoptT(g.cellOrder, h->gtDev.cellOrder); adoptT(g.cellBeg, h->gtDev.cellBeg); adoptT(g.tpIds, h->gtDev.tpIds); adoptT(g.tfIds, h->gtDev.tfIds);
-                adoptT(g.faceVerts, h->gtDev.faceVerts); adoptT(g.cellFaces, h->gtDev.cellFaces); adoptT(g.meta, h->gtDev.meta);
-                h->gtDev.valid = false;      // (the handle's allocation list owns them now)
-            } else {
-                rc |= devUpload(h, &g.cellOrder, h->gt.order);
-                rc |= devUpload(h, &g.cellBeg, h->gt.cellBeg);
-                rc |= devUpload(h, &g.tpIds, h->gt.tpIds);
-                rc |= devUpload(h, &g.tfIds, h->gt.tfIds);
-                rc |= devUpload(h, &g.faceVerts, h->gt.faceVerts);
-                rc |= devUpload(h, &g.cellFaces, h->gt.cellFaces);
-            }
-            rc |= devUpload(h, &g.tpOff, h->gt.tpOff);
-            rc |= devUpload(h, &g.tfOff, h->gt.tfOff);
-            rc |= devUpload(h, &g.fvBase, h->gt.fvBase);
-            rc |= devUpload(h, &g.fvWidth, h->gt.fvWidth);
-            rc |= devUpload(h, &g.cfBase, h->gt.cfBase);
-            rc |= devUpload(h, &g.cfWidth, h->gt.cfWidth);
-            rc |= devUpload(h, &g.tileFlags, h->gt.tileFlags);
-            // Shared topology blocks (tiles.hpp): tiles whose rows are byte-identical read the first copy.  The pass runs on the tables
-            // of whichever side built them (a device build's rows are hashed and compared where they are, tiles_dev.hip) and only changes
-            // the bases in the meta records.
-            const bool shareTiles = tileShareKnob();
-            // (one array of a device build: the pass runs where the rows are)
-            auto shareDev = [&](TileShare& out, int nT, const uint16_t* a, const uint16_t* b, const std::vector<int32_t>& base, auto lenOf, const std::vector<uint8_t>& width) {
-                std::vector<int32_t> len((size_t)nT), key(width.begin(), width.end());
-                for (int t = 0; t < nT; ++t) len[(size_t)t] = (int32_t)lenOf(t);
-                std::string why;
-                if (shareBlocksOnDevice(nT, a, b, base, len, key, h->device, out, why)) rc |= fail("smgpu_create: shared tile blocks: " + why);
-            };
-            auto putMeta = [&](const int*& dst, const std::vector<int>& meta) {      // a device build's records are overwritten in place
-                if (!dst) { rc |= devUpload(h, &dst, meta); return; }
-                if (!meta.empty() && hipMemcpy((void*)dst, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc |= fail("smgpu_create: upload of the tile records failed");
-            };
-            // SMGPU_VERBOSE=1, per tile set: tiles, distinct blocks per array (= tiles where every tile reads its own), staged elements per
-            // element of the mesh
-            const bool sayTiles = envInt("SMGPU_VERBOSE", 0) != 0;
-            int dFv = h->gt.nTiles, dCf = h->gt.nTiles, dPc = h->stl.nTiles, dPp = h->stl.nTiles, dPf = h->stl.nTiles;
-            if (!g.meta || shareTiles) {   // the per-tile scalars once more, one record per tile (GeomTileMeta: scalar loads in the kernel)
-                const auto& gt = h->gt;
-                const int nT = gt.nTiles;
-                TileShare fv, cf;
-                if (gt.faceVerts.empty() && g.faceVerts) {
-                    shareDev(fv, nT, g.faceVerts, nullptr, gt.fvBase, [&](int t) { return (size_t)(gt.tfOff[(size_t)t + 1] - gt.tfOff[(size_t)t]) * gt.fvWidth[(size_t)t]; }, gt.fvWidth);
-                    shareDev(cf, nT, g.cellFaces, nullptr, gt.cfBase, [&](int t) { return (size_t)gt.cfWidth[(size_t)t] * (size_t)gt.threads; }, gt.cfWidth);
-                } else shareGeomBlocks(gt, gt.faceVerts.data(), gt.cellFaces.data(), fv, cf);
-                if (rc) return cleanup(1);
-                std::vector<int> meta((size_t)kGeomMetaInts * (size_t)gt.nTiles, 0);
-                for (int t = 0; t < gt.nTiles; ++t) {
-                    int* r = meta.data() + (size_t)kGeomMetaInts * t;
-                    r[0] = gt.tpOff[t]; r[1] = gt.tpOff[t + 1] - gt.tpOff[t]; r[2] = gt.tfOff[t]; r[3] = gt.tfOff[t + 1] - gt.tfOff[t];
-                    r[4] = fv.remap(gt.fvBase, t); r[5] = gt.fvWidth[t]; r[6] = gt.cellBeg[t]; r[7] = gt.cellBeg[t + 1] - gt.cellBeg[t];
-                    r[8] = cf.remap(gt.cfBase, t); r[9] = gt.cfWidth[t]; r[10] = gt.tileFlags[t];
-                }
-                putMeta(g.meta, meta);
-                dFv = fv.distinct; dCf = cf.distinct;
-            }
-            if (sayTiles)
-                std::fprintf(stderr, "[smgpu] geometry tiles: %d tiles, distinct blocks: faceVerts %d, cellFaces %d (SMGPU_TILE_LATTICE=%d SMGPU_TILE_SHARE=%d), staged faces x%.4f, "
-                             "staged points x%.4f\n", h->gt.nTiles, dFv, dCf, (int)h->gt.latticeKeys, (int)shareTiles, (double)h->gt.tfOff.back() / std::max(1, t.nFaces),
-                             (double)h->gt.tpOff.back() / std::max(1, t.nPoints));
-            g.maxPoints = h->gt.maxPoints; g.maxFaces = h->gt.maxFaces;
-            if (h->stDev.valid) {
-                auto adoptS = [&](auto*& dst, const SmoothTilesDev::Arr& a) { dst = (std::remove_reference_t<decltype(dst)>)a.p; h->allocs.push_back(a.p); h->deviceBytes += (int64_t)a.bytes; };
-                adoptS(v.ptOrder, h->stDev.order); adoptS(v.ptBeg, h->stDev.ptBeg); adoptS(v.tcIds, h->stDev.tcIds); adoptS(v.tnIds, h->stDev.tnIds); adoptS(v.selfLoc, h->stDev.selfLoc);
-                adoptS(v.pcEll, h->stDev.pcEll); adoptS(v.ppEll, h->stDev.ppEll); adoptS(v.pairEll, h->stDev.pairEll); adoptS(v.pfEll, h->stDev.pfEll); adoptS(v.meta, h->stDev.meta);
-                h->stDev.valid = false;
-            } else {
-                rc |= devUpload(h, &v.ptOrder, h->stl.order);
-                rc |= devUpload(h, &v.ptBeg, h->stl.ptBeg);
-                rc |= devUpload(h, &v.tcIds, h->stl.tcIds);
-                rc |= devUpload(h, &v.tnIds, h->stl.tnIds);
-                rc |= devUpload(h, &v.selfLoc, h->stl.selfLoc);
-                rc |= devUpload(h, &v.pcEll, h->stl.pcEll);
-                rc |= devUpload(h, &v.ppEll, h->stl.ppEll);
-                rc |= devUpload(h, &v.pairEll, h->stl.pairEll);
-                rc |= devUpload(h, &v.pfEll, h->stl.pfEll);
-            }
-            rc |= devUpload(h, &v.tcOff, h->stl.tcOff);
-            rc |= devUpload(h, &v.tnOff, h->stl.tnOff);
-            rc |= devUpload(h, &v.pcBase, h->stl.pcBase);
-            rc |= devUpload(h, &v.pcWidth, h->stl.pcWidth);
-            rc |= devUpload(h, &v.ppBase, h->stl.ppBase);
-            rc |= devUpload(h, &v.ppWidth, h->stl.ppWidth);
-            rc |= devUpload(h, &v.pfBase, h->stl.pfBase);
-            rc |= devUpload(h, &v.pfWidth, h->stl.pfWidth);
-            if (!v.meta || shareTiles) {   // SmoothTileMeta records
-                const auto& st = h->stl;
-                const int nS = st.nTiles;
-                TileShare pc, pp, pf;
-                if (st.pcEll.empty() && v.pcEll) {
-                    const size_t T = (size_t)st.threads;
-                    shareDev(pc, nS, v.pcEll, nullptr, st.pcBase, [&](int t) { return st.pcWidth[(size_t)t] * T; }, st.pcWidth);
-                    shareDev(pp, nS, v.ppEll, v.pairEll, st.ppBase, [&](int t) { return st.ppWidth[(size_t)t] * T; }, st.ppWidth);
-                    shareDev(pf, nS, v.pfEll, nullptr, st.pfBase, [&](int t) { return st.pfWidth[(size_t)t] * T; }, st.pfWidth);
-                } else shareSmoothBlocks(st, st.pcEll.data(), st.ppEll.data(), st.pairEll.data(), st.pfEll.data(), pc, pp, pf);
-                if (rc) return cleanup(1);
-                std::vector<int> meta((size_t)kSmoothMetaInts * (size_t)st.nTiles, 0);
-                for (int t = 0; t < st.nTiles; ++t) {
-                    int* r = meta.data() + (size_t)kSmoothMetaInts * t;
-                    r[0] = st.ptBeg[t]; r[1] = st.ptBeg[t + 1] - st.ptBeg[t]; r[2] = st.tcOff[t]; r[3] = st.tcOff[t + 1] - st.tcOff[t];
-                    r[4] = st.tnOff[t]; r[5] = st.tnOff[t + 1] - st.tnOff[t]; r[6] = pc.remap(st.pcBase, t); r[7] = st.pcWidth[t];
-                    r[8] = pp.remap(st.ppBase, t); r[9] = st.ppWidth[t]; r[10] = pf.remap(st.pfBase, t); r[11] = st.pfWidth[t];
-                }
-                putMeta(v.meta, meta);
-                dPc = pc.distinct; dPp = pp.distinct; dPf = pf.distinct;
-            }
-            if (sayTiles)
-                std::fprintf(stderr, "[smgpu] smoothing tiles: %d tiles, distinct blocks: pcEll %d, ppEll+pairEll %d, pfEll %d, staged cell centres x%.4f, staged points x%.4f (per point)\n",
-                             h->stl.nTiles, dPc, dPp, dPf, (double)h->stl.tcOff.back() / std::max(1, t.nPoints), (double)h->stl.tnOff.back() / std::max(1, t.nPoints));
-            v.maxCells = h->stl.maxCells; v.maxPoints = h->stl.maxPoints;
-            v.usePairShare = t.maxPointPoints <= 16 ? 1 : 0;
-            if (h->useFilter) {
-                if (e3.empty()) {
-                    EdgeTileView& ev = h->ev;
-                    // the filter reads the face averages where the geometry tiles store them: position of every face
-                    // in the face list of its owner's tile
-                    const size_t nGeomTf = (size_t)h->gt.tfOff.back();
-                    h->avgPackedCount = nGeomTf;
-                    if (h->etDev.valid) {      // a device build: the remap there too, the tables stay where they are
-                        std::string why;
-                        if (remapEdgeFaceIdsOnDevice(g.tfIds, (long long)nGeomTf, t.nFaces, (int*)h->etDev.tfIds.p, h->etDev.nTf, h->device, why))
-                            return cleanup(fail("smgpu_create: edge tile face positions: " + why));
-                        auto adoptE = [&](auto*& dst, const EdgeTilesDev::Arr& a) { dst = (std::remove_reference_t<decltype(dst)>)a.p; h->allocs.push_back(a.p); h->deviceBytes += (int64_t)a.bytes; };
-                        adoptE(ev.order, h->etDev.order); adoptE(ev.edgeBeg, h->etDev.edgeBeg); adoptE(ev.tpIds, h->etDev.tpIds); adoptE(ev.tfIds, h->etDev.tfIds);
-                        adoptE(ev.tcIds, h->etDev.tcIds); adoptE(ev.epLoc, h->etDev.epLoc); adoptE(ev.efEll, h->etDev.efEll); adoptE(ev.ecEll, h->etDev.ecEll);
-                        adoptE(ev.meta, h->etDev.meta);
-                        h->etDev.valid = false;
-                    } else {
-                        if (h->gt.tfIds.size() != nGeomTf) {      // (a device build of the geometry tables that kept its face ids there)
-                            h->gt.tfIds.resize(nGeomTf);
-                            if (hipMemcpy(h->gt.tfIds.data(), g.tfIds, nGeomTf * 4, hipMemcpyDeviceToHost) != hipSuccess) return cleanup(fail("smgpu_create: download of the tile face ids failed"));
-                        }
-                        std::vector<int32_t> facePos((size_t)t.nFaces, -1);
-                        for (size_t k = 0; k < h->gt.tfIds.size(); ++k)
-                            if (h->gt.tfIds[k] < 0) facePos[(size_t)(h->gt.tfIds[k] & 0x7fffffff)] = (int32_t)k;
-                        for (int32_t& f : h->etl.tfIds) f = facePos[(size_t)f];
-                        rc |= devUpload(h, &ev.order, h->etl.order);
-                        rc |= devUpload(h, &ev.edgeBeg, h->etl.edgeBeg);
-                        rc |= devUpload(h, &ev.tpIds, h->etl.tpIds);
-                        rc |= devUpload(h, &ev.tfIds, h->etl.tfIds);
-                        rc |= devUpload(h, &ev.tcIds, h->etl.tcIds);
-                        rc |= devUpload(h, &ev.epLoc, h->etl.epLoc);
-                        rc |= devUpload(h, &ev.efEll, h->etl.efEll);
-                        rc |= devUpload(h, &ev.ecEll, h->etl.ecEll);
-                    }
-                    rc |= devUpload(h, &ev.tpOff, h->etl.tpOff);
-                    rc |= devUpload(h, &ev.tfOff, h->etl.tfOff);
-                    rc |= devUpload(h, &ev.tcOff, h->etl.tcOff);
-                    rc |= devUpload(h, &ev.efBase, h->etl.efBase);
-                    rc |= devUpload(h, &ev.ecBase, h->etl.ecBase);
-                    rc |= devUpload(h, &ev.efWidth, h->etl.efWidth);
-                    rc |= devUpload(h, &ev.ecWidth, h->etl.ecWidth);
-                    int dEf = h->etl.nTiles, dEc = h->etl.nTiles;
-                    if (!ev.meta || shareTiles) {   // EdgeTileMeta records
-                        const auto& et = h->etl;
-                        const int nE = et.nTiles;
-                        TileShare ef, ec;
-                        if (et.efEll.empty() && ev.efEll) {
-                            const size_t T = (size_t)et.threads;
-                            shareDev(ef, nE, ev.efEll, nullptr, et.efBase, [&](int ti) { return et.efWidth[(size_t)ti] * T; }, et.efWidth);
-                            shareDev(ec, nE, ev.ecEll, nullptr, et.ecBase, [&](int ti) { return et.ecWidth[(size_t)ti] * T; }, et.ecWidth);
-                        } else shareEdgeBlocks(et, et.efEll.data(), et.ecEll.data(), ef, ec);
-                        if (rc) return cleanup(1);
-                        dEf = ef.distinct; dEc = ec.distinct;
-                        std::vector<int> meta((size_t)kEdgeMetaInts * (size_t)et.nTiles, 0);
-                        for (int ti = 0; ti < et.nTiles; ++ti) {
-                            int* r = meta.data() + (size_t)kEdgeMetaInts * ti;
-                            r[0] = et.edgeBeg[ti]; r[1] = et.edgeBeg[ti + 1] - et.edgeBeg[ti]; r[2] = et.tpOff[ti]; r[3] = et.tpOff[ti + 1] - et.tpOff[ti];
-                            r[4] = et.tfOff[ti]; r[5] = et.tfOff[ti + 1] - et.tfOff[ti]; r[6] = et.tcOff[ti]; r[7] = et.tcOff[ti + 1] - et.tcOff[ti];
-                            r[8] = ef.remap(et.efBase, ti); r[9] = et.efWidth[ti]; r[10] = ec.remap(et.ecBase, ti); r[11] = et.ecWidth[ti];
-                        }
-                        putMeta(ev.meta, meta);
-                    }
-                    if (sayTiles)
-                        std::fprintf(stderr, "[smgpu] edge tiles: %d tiles, distinct blocks: efEll %d, ecEll %d, staged points x%.4f, faces x%.4f, cells x%.4f (per edge)\n", h->etl.nTiles, dEf, dEc,
-                                     (double)h->etl.tpOff.back() / std::max(1, t.nEdges), (double)h->etl.tfOff.back() / std::max(1, t.nEdges), (double)h->etl.tcOff.back() / std::max(1, t.nEdges));
-                    ev.maxPoints = h->etl.maxPoints; ev.maxFaces = h->etl.maxFaces; ev.maxCells = h->etl.maxCells;
-                    h->edgeLds = sizeof(double) * 3 * maxTileTotal(h->etl.nTiles, {&h->etl.tpOff, &h->etl.tfOff, &h->etl.tcOff});
-                    h->edgeTilesOk = h->edgeLds <= 64 * 1024;
-                    if (envInt("SMGPU_VERBOSE", 0))
-                        std::fprintf(stderr, "[smgpu] edge tiles: n=%d LDS=%zu B (maxP %d maxF %d maxC %d)\n", h->etl.nTiles, h->edgeLds, ev.maxPoints, ev.maxFaces, ev.maxCells);
-                    if (h->edgeTilesOk && envInt("SMGPU_SIDE_STREAM", sideStreamDefault(t.nPoints))) {
-                        if (depInit(h)) return cleanup(1);
-                        if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess ||
-                            hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming) != hipSuccess ||
-                            hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming) != hipSuccess)
-                            return cleanup(fail("side stream creation failed"));
-                    }
-                }
-            }
-            if (rc) return cleanup(1);
-            {   // the largest footprint of one tile (geomLds lays the arrays out by the tile's own counts)
-                size_t mx = 0;
-                for (int ti = 0; ti < h->gt.nTiles; ++ti)
-                    mx = std::max(mx, 3 * (size_t)(h->gt.tpOff[(size_t)ti + 1] - h->gt.tpOff[(size_t)ti]) +
-                                          (size_t)(SMGPU_GEOM_AOS ? kGF : 6) * (size_t)(h->gt.tfOff[(size_t)ti + 1] - h->gt.tfOff[(size_t)ti]));
-                h->geomLds = sizeof(double) * mx;
-            }
-            h->smoothLds = sizeof(double) * 3 * maxTileTotal(h->stl.nTiles, {&h->stl.tcOff, &h->stl.tnOff});
-            if (envInt("SMGPU_VERBOSE", 0))
-                std::fprintf(stderr, "[smgpu] tiles: geom T=%d n=%d LDS=%zu B (maxP %d maxF %d; staged faces x%.3f, points x%.3f of the mesh's)  smooth T=%d n=%d LDS=%zu B (maxC %d maxN %d)\n",
-                             h->geomT, h->gt.nTiles, h->geomLds, g.maxPoints, g.maxFaces, (double)h->gt.tfOff.back() / std::max(1, t.nFaces),
-                             (double)h->gt.tpOff.back() / std::max(1, t.nPoints), h->smoothT, h->stl.nTiles, h->smoothLds, v.maxCells, v.maxPoints);
-        }
-    }
-    {
-        const char* ea = std::getenv("SMGPU_EDGE_ANGLE");
-        h->eaCoop = !(ea && std::string(ea) == "faithful");
-        for (int p0 = 0; p0 < t.nPoints; p0 += kEaPointsPerBlock) {
-            const int p1 = std::min(t.nPoints, p0 + kEaPointsPerBlock);
-            h->eaMaxEntries = std::max(h->eaMaxEntries, t.pointEdges.off[p1] - t.pointEdges.off[p0]);
-        }
-        if (sizeof(double) * 9 * (size_t)h->eaMaxEntries > 60 * 1024) h->eaCoop = false;   // extreme valences: per-point form
-    }
+    readLoopKnobs(h);
+    if (h->useTiles && installTiles(h, tasks, tTopo, lapC)) return 1;
+    sizeEdgeAngle(h);
     lapC("tile tables adopted / uploaded");
-    State& s = h->st;
-    const size_t P = t.nPoints, C = t.nCells, F = t.nFaces, E = t.nEdges;
-    rc |= devAlloc(h, &h->bufA, 3 * P);
-    rc |= devAlloc(h, &h->bufB, 3 * P);
-    rc |= devAlloc(h, &s.prop, 3 * P);
-    rc |= devAlloc(h, &h->dStepSqr, P + 4);
-    rc |= devAlloc(h, &s.fCtr, 3 * F);
-    rc |= devAlloc(h, &s.fArea, 3 * F);
-    s.avgPacked = (h->useTiles && h->edgeTilesOk && h->avgPackedCount) ? 1 : 0;
-    rc |= devAlloc(h, &s.fAvg, 3 * (s.avgPacked ? h->avgPackedCount : F));
-    rc |= devAlloc(h, &s.cellCtr, 3 * C);
-    rc |= devAlloc(h, &s.frozen, P);
-    rc |= devAlloc(h, &s.edgeMin, E);
-    rc |= devAlloc(h, &s.edgeMax, E);
-    rc |= devAlloc(h, &s.ptMin, P);
-    rc |= devAlloc(h, &s.ptMax, P);
-    rc |= devAlloc(h, &s.faActive, P + 16);    // + 16: the compaction kernels read the marks 16 bytes at a time (chunkMarks)
-    rc |= devAlloc(h, &h->dFaMaybe, P + 16);
-    rc |= devAlloc(h, &s.faEdgeList, E);
-    rc |= devAlloc(h, &s.faPointList, P);
-    rc |= devAlloc(h, &h->dEaMaybe, P);
-    rc |= devAlloc(h, &s.faS, P);
-    rc |= devAlloc(h, &s.faN, t.pointPoints.size());
-    rc |= devAlloc(h, &s.walkStack, P + 64);
-    rc |= devAlloc(h, &s.acc, 1);
-    rc |= devAlloc(h, &s.nearTotal, 4);
-    {
-        // + the boundary points' partials when k_bnd_fix finishes them (smgpu_set_boundary_smoothing)
-        const size_t nPart = (size_t)std::max(gridFor(t.nPoints), h->useTiles ? h->stl.nTiles : 0) + 2 * (size_t)gridFor(t.nPoints) + 1;
-        rc |= devAlloc(h, &s.blkMax, nPart);
-        rc |= devAlloc(h, &s.blkCnt, nPart);
-    }
-    if (rc) return cleanup(1);
+    // work arrays, points, the walk's word
+    if (allocWorkArrays(h)) return 1;
     lapC("work arrays allocated");
-    if (hipMemset(s.acc, 0, sizeof(Accum)) != hipSuccess) return cleanup(fail("hipMemset failed"));
-    if (hipMemsetAsync(s.nearTotal, 0, 4 * sizeof(unsigned long long), h->stream) != hipSuccess) return cleanup(fail("hipMemset failed"));
-    if (hipMemset(s.frozen, 0, P) != hipSuccess) return cleanup(fail("hipMemset failed"));
-    if (hipMemcpy(h->bufA, d->points, 3 * P * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(fail("upload of points failed"));
-    if (hipMemcpy(s.prop, h->bufA, 3 * P * sizeof(double), hipMemcpyDeviceToDevice) != hipSuccess)
-        return cleanup(fail("upload of points failed"));
+    if (uploadPoints(h, d)) return 1;
     lapC("points uploaded");
-    s.ptsCur = h->bufA;
-    s.ptsNext = h->bufB;
-    s.stats = nullptr;
-    s.sharedSlot = nullptr;
-    s.combA = nullptr;
-    {   // the word through which the GPU tells the host how busy the face-angle walk is (updateWalkMode)
-        void* dp = nullptr;
-        if (hipHostMalloc((void**)&h->nActiveHost, 64, hipHostMallocMapped) == hipSuccess &&
-            hipHostGetDevicePointer(&dp, h->nActiveHost, 0) == hipSuccess) {
-            *(volatile int*)h->nActiveHost = -1;
-            s.nActiveHost = (int*)dp;
-        } else {
-            (void)hipGetLastError();
-            if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
-            h->nActiveHost = nullptr;
-            s.nActiveHost = nullptr;      // the replay form then stays as first decided
-        }
-    }
+    mapWalkWord(h);
     computeAlgoBytes(h);
-    if (fEdge.valid()) fEdge.wait();
-    freeOwnerNeighbour(devTopo);          // (meshes without tile tables come past here with the two arrays still held)
-    h->devLists.owner = h->devLists.neighbour = DeviceTopologyArrays::Arr();     // the handle's copy never owns them
-    if (envInt("SMGPU_VERBOSE", 0)) std::fprintf(stderr, "[smgpu] set-up: total %.2f s\n", sinceCreate());
-    *out = h;
+    tasks.join();
+    releaseOwned(tasks.owned);            // (meshes without tile tables come past here with owner / neighbour still held)
+    h->devLists.owner = h->devLists.neighbour = DevArr();     // the handle's copy never owns them
+    if (plan.verbose) std::fprintf(stderr, "[smgpu] set-up: total %.2f s\n", setupClock());
+    *out = guard.release();
     return 0;
 }
 
@@ -1115,15 +527,7 @@ int smgpu_destroy(smgpu_handle* h) {
     for (auto& p : h->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : h->freeEvents) (void)hipEventDestroy(e);
     for (void* p : h->allocs) (void)hipFree(p);
-    if (h->stDev.valid)
-        for (const SmoothTilesDev::Arr* a : {&h->stDev.order, &h->stDev.ptBeg, &h->stDev.tcIds, &h->stDev.tnIds, &h->stDev.selfLoc, &h->stDev.pcEll, &h->stDev.ppEll, &h->stDev.pairEll, &h->stDev.pfEll, &h->stDev.meta})
-            if (a->p) (void)hipFree(a->p);
-    if (h->etDev.valid)
-        for (const EdgeTilesDev::Arr* a : {&h->etDev.order, &h->etDev.edgeBeg, &h->etDev.tpIds, &h->etDev.tfIds, &h->etDev.tcIds, &h->etDev.epLoc, &h->etDev.efEll, &h->etDev.ecEll, &h->etDev.meta})
-            if (a->p) (void)hipFree(a->p);
-    if (h->gtDev.valid)      // (a create that failed before the handle took the device-built tile tables over)
-        for (const GeomTilesDev::Arr* a : {&h->gtDev.cellOrder, &h->gtDev.cellBeg, &h->gtDev.tpIds, &h->gtDev.tfIds, &h->gtDev.faceVerts, &h->gtDev.cellFaces, &h->gtDev.meta})
-            if (a->p) (void)hipFree(a->p);
+    releaseOwned(h->gtDev); releaseOwned(h->stDev); releaseOwned(h->etDev);      // (a create that failed before the handle took device-built tile tables over)
     h->q.release(); h->qt.release(); h->qg.release(); h->tg.release(); h->qc.release();
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->nActiveHost) (void)hipHostFree(h->nActiveHost);
@@ -2352,38 +1756,27 @@ int smgpu_halo_configure(smgpu_handle* h, const smgpu_halo_desc* d) {
             sub.reserve((size_t)d->nShared);
             for (int pi = 0; pi < P; ++pi) if (posSlot[(size_t)pi] >= 0) sub.push_back(h->stl.order[(size_t)pi]);
             std::vector<double> pts(3 * (size_t)P);      // (the builder only reads coordinates when it orders the points itself)
-            const int capSC = envInt("SMGPU_SMOOTH_CAPC", std::min(2 * h->smoothT, 1500)), capSN = envInt("SMGPU_SMOOTH_CAPN", std::min(3 * h->smoothT, 1500));
-            std::string err = h->shr.buildBoundaries(h->topo, pts.data(), false, h->smoothT, capSC, capSN, nullptr, &sub, envInt("SMGPU_SMOOTH_CAPTOTAL", defaultSmoothCapTotal(h->smoothT)));
+            const TilePlan& plan = h->plan;
+            std::string err = h->shr.buildBoundaries(h->topo, pts.data(), false, h->smoothT, plan.capSmoothCells, plan.capSmoothNbrs, nullptr, &sub, plan.capSmoothTotal);
             if (!err.empty()) return fail("shared-point tiles: " + err);
             // the tables on the device where the addressing lives there (tiles_dev.hip; the corner lists they read stayed there),
             // else on the host -- which first fetches those lists
             int onDev = 1;
             SmoothTilesDev sd;
-            if (h->devLists.valid && envInt("SMGPU_DEVICE_TILES", 1) == 1) {
+            if (h->devLists.valid && plan.deviceTiles == 1) {
                 std::string why;
                 onDev = buildSmoothTablesOnDevice(h->shr, h->devLists, P, h->topo.maxPointPoints, h->isInternalHost.data(), h->device, sd, why);
                 if (onDev == 2) return fail("shared-point tiles: " + why);
             }
-            if (onDev == 0) {
-                SmoothTileView& v = h->hv;
-                auto adoptS = [&](auto*& dst, const SmoothTilesDev::Arr& a) { dst = (std::remove_reference_t<decltype(dst)>)a.p; h->allocs.push_back(a.p); h->deviceBytes += (int64_t)a.bytes; };
-                adoptS(v.ptOrder, sd.order); adoptS(v.ptBeg, sd.ptBeg); adoptS(v.tcIds, sd.tcIds); adoptS(v.tnIds, sd.tnIds); adoptS(v.selfLoc, sd.selfLoc);
-                adoptS(v.pcEll, sd.pcEll); adoptS(v.ppEll, sd.ppEll); adoptS(v.pairEll, sd.pairEll); adoptS(v.pfEll, sd.pfEll); adoptS(v.meta, sd.meta);
-                int rcU = 0;
-                rcU |= devUpload(h, &v.tcOff, h->shr.tcOff); rcU |= devUpload(h, &v.tnOff, h->shr.tnOff);
-                rcU |= devUpload(h, &v.pcBase, h->shr.pcBase); rcU |= devUpload(h, &v.pcWidth, h->shr.pcWidth);
-                rcU |= devUpload(h, &v.ppBase, h->shr.ppBase); rcU |= devUpload(h, &v.ppWidth, h->shr.ppWidth);
-                rcU |= devUpload(h, &v.pfBase, h->shr.pfBase); rcU |= devUpload(h, &v.pfWidth, h->shr.pfWidth);
-                if (rcU) return 1;
-                v.maxCells = h->shr.maxCells; v.maxPoints = h->shr.maxPoints;
-                v.usePairShare = h->sv.usePairShare;
-            } else {
+            if (onDev != 0) {
                 if (ensureHostLists(h, 1)) return 1;      // (the tables' corner lists: pointFaces with prev / next)
                 err = h->shr.buildTables(h->topo, h->isInternalHost.data(), true);
                 if (!err.empty()) return fail("shared-point tiles: " + err);
-                if (uploadSmoothView(h, h->shr, h->hv, h->sv.usePairShare)) return 1;
             }
-            if (envInt("SMGPU_VERBOSE", 0) >= 2) std::fprintf(stderr, "[smgpu] shared-point tiles: %d tiles, tables on the %s\n", h->shr.nTiles, onDev == 0 ? "device" : "host");
+            const int rcT = installSmoothTiles(h, h->shr, sd, h->hv, h->sv.usePairShare, false);
+            releaseOwned(sd);      // (nothing, unless the install failed half way)
+            if (rcT) return 1;
+            if (plan.verbose >= 2) std::fprintf(stderr, "[smgpu] shared-point tiles: %d tiles, tables on the %s\n", h->shr.nTiles, onDev == 0 ? "device" : "host");
             h->haloLds = sizeof(double) * 3 * maxTileTotal(h->shr.nTiles, {&h->shr.tcOff, &h->shr.tnOff});
             // per position of those tiles: slot, two-sharer peer code (k_halo_combineA2's table), send slots
             const size_t nS = sub.size();

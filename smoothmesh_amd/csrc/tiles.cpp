@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 namespace smgpu {
 
@@ -851,6 +852,44 @@ std::string EdgeTiles::buildTables(const Topology& t) {
     }
     tm.lap("tables");
     return "";
+}
+
+// ---- the per-tile records (tile_meta.hpp) -----------------------------------------------------------------------------------------
+template <class Meta, class Fill>
+static std::vector<int> metaRecordsOf(int32_t nTiles, Fill&& fill) {
+    std::vector<int> meta(sizeof(Meta) / sizeof(int) * (size_t)nTiles, 0);
+    for (int32_t t = 0; t < nTiles; ++t) {
+        const Meta r = fill(t);
+        std::memcpy(meta.data() + sizeof(Meta) / sizeof(int) * (size_t)t, &r, sizeof(Meta));
+    }
+    return meta;
+}
+std::vector<int> GeomTiles::metaRecords(const TileShare* fvShare, const TileShare* cfShare) const {
+    return metaRecordsOf<GeomTileMeta>(nTiles, [&](int32_t t) {
+        GeomTileMeta r{};
+        r.tpOff = tpOff[t]; r.nPts = tpOff[t + 1] - tpOff[t]; r.tfOff = tfOff[t]; r.nFaces = tfOff[t + 1] - tfOff[t];
+        r.fvBase = TileShare::baseOf(fvShare, fvBase, t); r.fvWidth = fvWidth[t]; r.cellBeg = cellBeg[t]; r.nCells = cellBeg[t + 1] - cellBeg[t];
+        r.cfBase = TileShare::baseOf(cfShare, cfBase, t); r.cfWidth = cfWidth[t]; r.flags = tileFlags[t];
+        return r;
+    });
+}
+std::vector<int> SmoothTiles::metaRecords(const TileShare* pcShare, const TileShare* ppShare, const TileShare* pfShare) const {
+    return metaRecordsOf<SmoothTileMeta>(nTiles, [&](int32_t t) {
+        SmoothTileMeta r{};
+        r.ptBeg = ptBeg[t]; r.nPts = ptBeg[t + 1] - ptBeg[t]; r.tcOff = tcOff[t]; r.nCells = tcOff[t + 1] - tcOff[t];
+        r.tnOff = tnOff[t]; r.nNbrs = tnOff[t + 1] - tnOff[t]; r.pcBase = TileShare::baseOf(pcShare, pcBase, t); r.pcWidth = pcWidth[t];
+        r.ppBase = TileShare::baseOf(ppShare, ppBase, t); r.ppWidth = ppWidth[t]; r.pfBase = TileShare::baseOf(pfShare, pfBase, t); r.pfWidth = pfWidth[t];
+        return r;
+    });
+}
+std::vector<int> EdgeTiles::metaRecords(const TileShare* efShare, const TileShare* ecShare) const {
+    return metaRecordsOf<EdgeTileMeta>(nTiles, [&](int32_t t) {
+        EdgeTileMeta r{};
+        r.edgeBeg = edgeBeg[t]; r.nEdges = edgeBeg[t + 1] - edgeBeg[t]; r.tpOff = tpOff[t]; r.nPts = tpOff[t + 1] - tpOff[t];
+        r.tfOff = tfOff[t]; r.nFaces = tfOff[t + 1] - tfOff[t]; r.tcOff = tcOff[t]; r.nCells = tcOff[t + 1] - tcOff[t];
+        r.efBase = TileShare::baseOf(efShare, efBase, t); r.efWidth = efWidth[t]; r.ecBase = TileShare::baseOf(ecShare, ecBase, t); r.ecWidth = ecWidth[t];
+        return r;
+    });
 }
 
 }  // namespace smgpu

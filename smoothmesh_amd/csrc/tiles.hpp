@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "tile_meta.hpp"
 #include "topology.hpp"
 
 namespace smgpu {
@@ -91,6 +92,8 @@ struct TileShare {
     std::vector<int32_t> rep;
     int32_t distinct = 0;
     int32_t remap(const std::vector<int32_t>& base, int32_t t) const { return base[(size_t)rep[(size_t)t]]; }
+    // the base tile t reads under an optional share (metaRecords)
+    static int32_t baseOf(const TileShare* s, const std::vector<int32_t>& base, int32_t t) { return s && !s->rep.empty() ? s->remap(base, t) : base[(size_t)t]; }
 };
 inline bool tileShareKnob() { const char* e = std::getenv("SMGPU_TILE_SHARE"); return !e || std::atoi(e) != 0; }
 struct GeomTiles; struct SmoothTiles; struct EdgeTiles;
@@ -140,12 +143,15 @@ struct GeomTiles {
                                 int32_t capPoints, int32_t capFaces, int32_t capWeighted = 0x7fffffff, int32_t faceWeight = 7,
                                 const std::vector<int32_t>* cellOrder = nullptr);
     std::string buildTables(const Topology& t);
+    // the tiles' GeomTileMeta records (tile_meta.hpp), kGeomMetaInts ints per tile; a share (the blocks of faceVerts / cellFaces) points
+    // a tile's base at the rows of its representative, none or an identity share leaves the tile's own
+    std::vector<int> metaRecords(const TileShare* fvShare = nullptr, const TileShare* cfShare = nullptr) const;
 };
 // the tables of a device build (tiles_dev.hip) that the kernels read where they were built; the caller owns the arrays
 struct GeomTilesDev {
-    struct Arr { void* p = nullptr; size_t bytes = 0; };
-    Arr cellOrder, cellBeg, tpIds, tfIds, faceVerts, cellFaces, meta;
+    DevArr cellOrder, cellBeg, tpIds, tfIds, faceVerts, cellFaces, meta;
     bool valid = false;
+    template <class F> void each(F&& f) { for (DevArr* a : {&cellOrder, &cellBeg, &tpIds, &tfIds, &faceVerts, &cellFaces, &meta}) f(*a); }
 };
 struct DeviceTopologyArrays;
 // 0: built (gt holds the offsets / widths / flags / tfIds / maxima the host reads, `out` the device arrays); 1: not handled there
@@ -193,11 +199,13 @@ struct SmoothTiles {
     std::string buildBoundaries(const Topology& t, const double* points, bool morton, int32_t threads, int32_t capCells, int32_t capPoints,
                                 const std::vector<int32_t>* pointOrder = nullptr, const std::vector<int32_t>* subset = nullptr, int32_t capTotal = 0x7fffffff);
     std::string buildTables(const Topology& t, const uint8_t* isInternal, bool subset = false);
+    // SmoothTileMeta records, as GeomTiles::metaRecords (shares of pcEll, ppEll + pairEll, pfEll)
+    std::vector<int> metaRecords(const TileShare* pcShare = nullptr, const TileShare* ppShare = nullptr, const TileShare* pfShare = nullptr) const;
 };
 struct SmoothTilesDev {
-    struct Arr { void* p = nullptr; size_t bytes = 0; };
-    Arr order, ptBeg, tcIds, tnIds, selfLoc, pcEll, ppEll, pairEll, pfEll, meta;
+    DevArr order, ptBeg, tcIds, tnIds, selfLoc, pcEll, ppEll, pairEll, pfEll, meta;
     bool valid = false;
+    template <class F> void each(F&& f) { for (DevArr* a : {&order, &ptBeg, &tcIds, &tnIds, &selfLoc, &pcEll, &ppEll, &pairEll, &pfEll, &meta}) f(*a); }
 };
 // the corner chains of all points computed ahead of the tables (tiles_dev.hip: startCornerChains)
 struct CornerChains { int* chPrev = nullptr; int* chNext = nullptr; int* bad = nullptr; int* big = nullptr; void* stream = nullptr; int32_t nPoints = 0; bool started = false; };
@@ -229,13 +237,31 @@ struct EdgeTiles {
     std::string buildBoundaries(const Topology& t, const double* points, bool morton, int32_t threads, int32_t capPoints,
                                 int32_t capFaces, int32_t capCells, const std::vector<int32_t>* pointOrder = nullptr, int32_t capTotal = 0x7fffffff);
     std::string buildTables(const Topology& t);
+    // EdgeTileMeta records, as GeomTiles::metaRecords (shares of efEll, ecEll)
+    std::vector<int> metaRecords(const TileShare* efShare = nullptr, const TileShare* ecShare = nullptr) const;
 };
 struct EdgeTilesDev {
-    struct Arr { void* p = nullptr; size_t bytes = 0; };
-    Arr order, edgeBeg, tpIds, tfIds, tcIds, epLoc, efEll, ecEll, meta;
+    DevArr order, edgeBeg, tpIds, tfIds, tcIds, epLoc, efEll, ecEll, meta;
     long long nTf = 0;
     bool valid = false;
+    template <class F> void each(F&& f) { for (DevArr* a : {&order, &edgeBeg, &tpIds, &tfIds, &tcIds, &epLoc, &efEll, &ecEll, &meta}) f(*a); }
 };
+// ---- the knobs of the three tile sets, read once per engine (smgpu_create: makeTilePlan, setup_tiles.hpp) ---------------------------
+struct TilePlan {
+    bool wantTiles = true, wantFilter = true;      // SMGPU_TILES, SMGPU_FILTER
+    bool morton = true, latticeKeys = true;        // SMGPU_TILE_MORTON; tileLatticeKnob of the mesh's default
+    int deviceTiles = 1;                           // SMGPU_DEVICE_TILES: 0 the tables on the host, 1 on the device where the addressing was built
+                                                   // there, 2 as if the device builds handed their tables back (the tests' way into that path)
+    bool share = true;                             // tileShareKnob
+    int verbose = 0;                               // SMGPU_VERBOSE
+    int geomT = 256, smoothT = 256, geomCells = 128;
+    int capGeomPoints = 0, capGeomFaces = 0, capGeomWeighted = 0;
+    int capSmoothCells = 0, capSmoothNbrs = 0, capSmoothTotal = 0;
+    int capEdgePoints = 0, capEdgeFaces = 0, capEdgeCells = 0, capEdgeTotal = 0;
+    static bool shapeOk(int T) { return T == 64 || T == 128 || T == 256; }
+    bool shapesOk() const { return shapeOk(geomT) && shapeOk(smoothT); }      // (else smgpu_create refuses, once it comes to the tiles)
+};
+
 int buildEdgeTablesOnDevice(EdgeTiles& et, const DeviceTopologyArrays& td, int32_t nEdges, int device, EdgeTilesDev& out, std::string& why);
 int remapEdgeFaceIdsOnDevice(const int* geomTfIds, long long nGeomTf, int32_t nFaces, int* edgeTfIds, long long nEdgeTf, int device, std::string& why);
 

@@ -610,7 +610,7 @@ int buildGeomTablesOnDevice(GeomTiles& gt, const DeviceTopologyArrays& td, int32
         gt.maxPoints = std::max(gt.maxPoints, hN[(size_t)i]); gt.maxFaces = std::max(gt.maxFaces, hF[(size_t)i]);
     }
     gt.tpIds.clear(); gt.faceVerts.clear(); gt.cellFaces.clear();      // (device only: tpIds' length is tpOff.back())
-    auto give = [&](GeomTilesDev::Arr& a, void* p, size_t bytes) { a.p = p; a.bytes = std::max<size_t>(bytes, 1); D.release(p); };
+    auto give = [&](DevArr& a, void* p, size_t bytes) { a.p = p; a.bytes = std::max<size_t>(bytes, 1); D.release(p); };
     give(out.cellOrder, dOrder, (size_t)nCells * 4); give(out.cellBeg, dBeg, ((size_t)nT + 1) * 4);
     give(out.tpIds, tpIds, (size_t)nTp * 4); give(out.tfIds, tfIds, (size_t)nTf * 4);
     give(out.faceVerts, faceVerts, (size_t)nFv * 2); give(out.cellFaces, cellFaces, (size_t)nCf * 2); give(out.meta, meta, 12 * (size_t)nT * 4);
@@ -679,7 +679,7 @@ int buildEdgeTablesOnDevice(EdgeTiles& et, const DeviceTopologyArrays& td, int32
         et.maxPoints = std::max(et.maxPoints, hP[(size_t)i]); et.maxFaces = std::max(et.maxFaces, hF[(size_t)i]); et.maxCells = std::max(et.maxCells, hC[(size_t)i]);
     }
     et.tpIds.clear(); et.tfIds.clear(); et.tcIds.clear(); et.epLoc.clear(); et.efEll.clear(); et.ecEll.clear();
-    auto give = [&](EdgeTilesDev::Arr& a, void* p, size_t bytes) { a.p = p; a.bytes = std::max<size_t>(bytes, 1); D.release(p); };
+    auto give = [&](DevArr& a, void* p, size_t bytes) { a.p = p; a.bytes = std::max<size_t>(bytes, 1); D.release(p); };
     give(out.order, dOrder, (size_t)nEdges * 4); give(out.edgeBeg, dBeg, S * 4);
     give(out.tpIds, tpIds, (size_t)nTp * 4); give(out.tfIds, tfIds, (size_t)nTf * 4); give(out.tcIds, tcIds, (size_t)nTc * 4);
     give(out.epLoc, epLoc, 2 * (size_t)nEdges * 2); give(out.efEll, efEll, (size_t)nEf * 2); give(out.ecEll, ecEll, (size_t)nEc * 2); give(out.meta, meta, 12 * (size_t)nT * 4);
@@ -807,7 +807,7 @@ int buildSmoothTablesOnDevice(SmoothTiles& st, const DeviceTopologyArrays& td, i
         st.maxCells = std::max(st.maxCells, hC[(size_t)i]); st.maxPoints = std::max(st.maxPoints, hN[(size_t)i]);
     }
     st.tcIds.clear(); st.tnIds.clear(); st.selfLoc.clear(); st.pcEll.clear(); st.ppEll.clear(); st.pairEll.clear(); st.pfEll.clear();
-    auto give = [&](SmoothTilesDev::Arr& a, void* p, size_t bytes) { a.p = p; a.bytes = std::max<size_t>(bytes, 1); D.release(p); };
+    auto give = [&](DevArr& a, void* p, size_t bytes) { a.p = p; a.bytes = std::max<size_t>(bytes, 1); D.release(p); };
     give(out.order, dOrder, (size_t)nPos * 4); give(out.ptBeg, dBeg, S * 4); give(out.tcIds, tcIds, (size_t)nTc * 4); give(out.tnIds, tnIds, (size_t)nTn * 4);
     give(out.selfLoc, selfLoc, (size_t)nPos * 2); give(out.pcEll, pcEll, (size_t)nPc * 2); give(out.ppEll, ppEll, (size_t)nPp * 2); give(out.pairEll, pairEll, (size_t)nPp * 2);
     give(out.pfEll, pfEll, (size_t)nPfE * 2); give(out.meta, meta, 12 * (size_t)nT * 4);

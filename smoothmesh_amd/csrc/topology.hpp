@@ -69,13 +69,31 @@ struct Topology {
                       const std::function<void()>& afterPoints = nullptr);
 };
 
+// one array on the device that somebody owns: whoever holds a non-null p frees it, or hands it on and clears his copy
+struct DevArr { void* p = nullptr; size_t bytes = 0; };
+
+// The addressing as the kernels read it, stated once: X(name, list) -- `name` is the MeshView field (kernels.hpp) and the array of
+// a device build below, `list` the member of Topology that holds the same values on the host.
+#define SMGPU_ADDRESSING(X)                                                                                                                     \
+    X(faceOff, facePoints.off) X(facePts, facePoints.val) X(cfOff, cellFacesGeom.off) X(cfVal, cellFacesGeom.val) X(pcOff, pointCells.off)   \
+    X(pcVal, pointCells.val) X(ppOff, pointEdges.off) X(ppPt, pointPoints) X(peEdge, pointEdges.val) X(pfOff, pointFaces.off)                 \
+    X(pfFace, pointFaces.val) X(pfPrev, pfPrev) X(pfNext, pfNext) X(pfPrevSlot, pfPrevSlot) X(pfNextSlot, pfNextSlot) X(ringFace, ringFace)  \
+    X(ringCell, ringCell) X(edgeRingOk, edgeRingOk) X(edges, edges) X(efOff, edgeFaces.off) X(efFace, edgeFaces.val) X(ecOff, edgeCells.off)  \
+    X(ecCell, edgeCells.val) X(ecF0, ecFace0) X(ecF1, ecFace1)
+
 // the device arrays of a device build that the kernels read as they are (MeshView): handed to the caller instead of being freed
 struct DeviceTopologyArrays {
-    struct Arr { void* p = nullptr; size_t bytes = 0; };
-    Arr owner, neighbour;      // (not read by the loop's kernels: the device builds of the tile tables do, tiles_dev.hip)
-    Arr faceOff, facePts, cfOff, cfVal, pcOff, pcVal, ppOff, ppPt, peEdge, pfOff, pfFace, pfPrev, pfNext, pfPrevSlot, pfNextSlot, ringFace, ringCell,
-        edgeRingOk, edges, efOff, efFace, ecOff, ecCell, ecF0, ecF1;
+    DevArr owner, neighbour;      // (not read by the loop's kernels: the device builds of the tile tables do, tiles_dev.hip)
+#define SMGPU_X(name, list) DevArr name;
+    SMGPU_ADDRESSING(SMGPU_X)
+#undef SMGPU_X
     bool valid = false;
+    template <class F> void each(F&& f) {
+        f(owner); f(neighbour);
+#define SMGPU_X(name, list) f(name);
+        SMGPU_ADDRESSING(SMGPU_X)
+#undef SMGPU_X
+    }
 };
 
 // The same addressing built on the device (topology_dev.hip: radix sorts of (row, value) keys + per-edge kernels) and copied into

@@ -562,7 +562,7 @@ int buildTopologyOnDevice(Topology& t, int32_t nP, int32_t nC, int32_t nF, int32
     auto flush = [&]() { if (!runDown(jobs, device)) copyFailed = true; };
     if (keep) {      // what the kernels read as it is stays on the device, owned by the caller -- from here on (the hooks below start
                      // tile-table builds that read these arrays); a later failure leaves the caller to free them
-        auto give = [&](DeviceTopologyArrays::Arr& a, void* p, size_t bytes) { a.p = p; a.bytes = std::max<size_t>(bytes, 1); D.release(p); };
+        auto give = [&](DevArr& a, void* p, size_t bytes) { a.p = p; a.bytes = std::max<size_t>(bytes, 1); D.release(p); };
         give(keep->faceOff, dFo, ((size_t)nF + 1) * 4); give(keep->facePts, dFp, (size_t)nnz * 4);
         give(keep->cfOff, cfOff, ((size_t)nC + 1) * 4); give(keep->cfVal, cfVal, (size_t)nCF * 4);
         give(keep->pcOff, pcOff, ((size_t)nP + 1) * 4); give(keep->pcVal, pcVal, (size_t)nPC * 4);
@@ -616,7 +616,7 @@ int buildTopologyOnDevice(Topology& t, int32_t nP, int32_t nC, int32_t nF, int32
 int downloadDeferredLists(Topology& t, const DeviceTopologyArrays& td, int device, std::string& why, int groups) {
     if (!td.valid) return 0;
     std::vector<DownJob> jobs;
-    auto fetch = [&](auto& vec, const DeviceTopologyArrays::Arr& a, size_t n) {
+    auto fetch = [&](auto& vec, const DevArr& a, size_t n) {
         typedef std::remove_reference_t<decltype(vec[0])> T;
         if (vec.size() != n) wantDown(jobs, vec, (const T*)a.p, n);
     };

@@ -36,6 +36,14 @@ int main(int argc, char** argv) {
         smgpu::EdgeTiles e;
         err = e.build(t, m.points.data(), morton != 0, 256, 768, 1280, 768);
         if (!err.empty()) { std::fprintf(stderr, "edge tiles: %s\n", err.c_str()); return 1; }
+        // the per-tile records, plain and through the shared blocks
+        smgpu::TileShare fv, cf, pc, pp, pf, ef, ec;
+        smgpu::shareGeomBlocks(g, g.faceVerts.data(), g.cellFaces.data(), fv, cf);
+        smgpu::shareSmoothBlocks(s, s.pcEll.data(), s.ppEll.data(), s.pairEll.data(), s.pfEll.data(), pc, pp, pf);
+        smgpu::shareEdgeBlocks(e, e.efEll.data(), e.ecEll.data(), ef, ec);
+        const size_t words = g.metaRecords().size() + g.metaRecords(&fv, &cf).size() + s.metaRecords().size() + s.metaRecords(&pc, &pp, &pf).size() +
+                             e.metaRecords().size() + e.metaRecords(&ef, &ec).size();
+        if (words != 2 * 12 * (size_t)(g.nTiles + s.nTiles + e.nTiles)) { std::fprintf(stderr, "meta records: %zu words\n", words); return 1; }
     }
     // layer set-up on the cavity wall with unit "areas" along x (the values do not matter for memory safety)
     std::vector<smgpu::LayerPatch> patches;

@@ -6,6 +6,8 @@
 // entry for entry, and holds every tile of several elements to capWeighted / capTotal.  Prints one line per knob combination:
 //   "set lattice=L share=S geom tiles=.. fv=.. cf=.. faces_x=.. points_x=.. maxP=.. maxF=.. smooth tiles=.. pc=.. pp=.. pf=.. cells_x=.. nbrs_x=.. edge tiles=.. ef=.. ec=.."
 // (fv, cf, ...: distinct blocks; *_x: staged elements per element of the mesh), "FAIL <what>" lines, and "done fails=<n>".
+// Under every combination the per-tile meta records (metaRecords, tile_meta.hpp) are held to the tables field by field: counts are
+// offset differences, bases are share.remap(base, t), and no share or an identity share gives the tile's own bases.
 #include <algorithm>
 #include <climits>
 #include <cstddef>
@@ -65,6 +67,67 @@ void checkShare(const char* who, const TileShare& s, int32_t nTiles, int lattice
         own += r == t;
     }
     if (own != s.distinct) failLine(std::string(who) + ": distinct count", lattice, share, -1);
+}
+// record t of a metaRecords() result as its struct
+template <class Meta> Meta recordOf(const std::vector<int>& meta, int32_t t) {
+    Meta r;
+    std::memcpy(&r, meta.data() + sizeof(Meta) / sizeof(int) * (size_t)t, sizeof(Meta));
+    return r;
+}
+TileShare identityShare(int32_t nTiles) {
+    TileShare s;
+    s.rep.resize((size_t)nTiles);
+    for (int32_t t = 0; t < nTiles; ++t) s.rep[(size_t)t] = t;
+    s.distinct = nTiles;
+    return s;
+}
+void checkGeomMeta(const GeomTiles& gt, const TileShare& fv, const TileShare& cf, int lattice, int share) {
+    const std::vector<int> meta = gt.metaRecords(&fv, &cf), plain = gt.metaRecords();
+    const TileShare id = identityShare(gt.nTiles);
+    if (meta.size() != (size_t)kGeomMetaInts * (size_t)gt.nTiles || plain.size() != meta.size()) { failLine("geom meta: size", lattice, share, -1); return; }
+    if (gt.metaRecords(&id, &id) != plain || gt.metaRecords(&id, nullptr) != plain) failLine("geom meta: identity share differs from no share", lattice, share, -1);
+    if (!share && meta != plain) failLine("geom meta: SMGPU_TILE_SHARE=0 differs from no share", lattice, share, -1);
+    for (int32_t t = 0; t < gt.nTiles; ++t) {
+        const GeomTileMeta r = recordOf<GeomTileMeta>(meta, t), q = recordOf<GeomTileMeta>(plain, t);
+        const size_t i = (size_t)t;
+        if (r.tpOff != gt.tpOff[i] || r.nPts != gt.tpOff[i + 1] - gt.tpOff[i] || r.tfOff != gt.tfOff[i] || r.nFaces != gt.tfOff[i + 1] - gt.tfOff[i] ||
+            r.cellBeg != gt.cellBeg[i] || r.nCells != gt.cellBeg[i + 1] - gt.cellBeg[i] || r.fvWidth != gt.fvWidth[i] || r.cfWidth != gt.cfWidth[i] ||
+            r.flags != gt.tileFlags[i] || r.pad != 0) failLine("geom meta: counts / widths / flags", lattice, share, t);
+        if (r.fvBase != fv.remap(gt.fvBase, t) || r.cfBase != cf.remap(gt.cfBase, t)) failLine("geom meta: remapped bases", lattice, share, t);
+        if (q.fvBase != gt.fvBase[i] || q.cfBase != gt.cfBase[i]) failLine("geom meta: plain bases", lattice, share, t);
+    }
+}
+void checkSmoothMeta(const SmoothTiles& st, const TileShare& pc, const TileShare& pp, const TileShare& pf, int lattice, int share) {
+    const std::vector<int> meta = st.metaRecords(&pc, &pp, &pf), plain = st.metaRecords();
+    const TileShare id = identityShare(st.nTiles);
+    if (meta.size() != (size_t)kSmoothMetaInts * (size_t)st.nTiles || plain.size() != meta.size()) { failLine("smooth meta: size", lattice, share, -1); return; }
+    if (st.metaRecords(&id, &id, &id) != plain || st.metaRecords(nullptr, &id, nullptr) != plain) failLine("smooth meta: identity share differs from no share", lattice, share, -1);
+    if (!share && meta != plain) failLine("smooth meta: SMGPU_TILE_SHARE=0 differs from no share", lattice, share, -1);
+    for (int32_t t = 0; t < st.nTiles; ++t) {
+        const SmoothTileMeta r = recordOf<SmoothTileMeta>(meta, t), q = recordOf<SmoothTileMeta>(plain, t);
+        const size_t i = (size_t)t;
+        if (r.ptBeg != st.ptBeg[i] || r.nPts != st.ptBeg[i + 1] - st.ptBeg[i] || r.tcOff != st.tcOff[i] || r.nCells != st.tcOff[i + 1] - st.tcOff[i] ||
+            r.tnOff != st.tnOff[i] || r.nNbrs != st.tnOff[i + 1] - st.tnOff[i] || r.pcWidth != st.pcWidth[i] || r.ppWidth != st.ppWidth[i] || r.pfWidth != st.pfWidth[i])
+            failLine("smooth meta: counts / widths", lattice, share, t);
+        if (r.pcBase != pc.remap(st.pcBase, t) || r.ppBase != pp.remap(st.ppBase, t) || r.pfBase != pf.remap(st.pfBase, t)) failLine("smooth meta: remapped bases", lattice, share, t);
+        if (q.pcBase != st.pcBase[i] || q.ppBase != st.ppBase[i] || q.pfBase != st.pfBase[i]) failLine("smooth meta: plain bases", lattice, share, t);
+    }
+}
+void checkEdgeMeta(const EdgeTiles& et, const TileShare& ef, const TileShare& ec, int lattice, int share) {
+    const std::vector<int> meta = et.metaRecords(&ef, &ec), plain = et.metaRecords();
+    const TileShare id = identityShare(et.nTiles);
+    if (meta.size() != (size_t)kEdgeMetaInts * (size_t)et.nTiles || plain.size() != meta.size()) { failLine("edge meta: size", lattice, share, -1); return; }
+    if (et.metaRecords(&id, &id) != plain || et.metaRecords(nullptr, &id) != plain) failLine("edge meta: identity share differs from no share", lattice, share, -1);
+    if (!share && meta != plain) failLine("edge meta: SMGPU_TILE_SHARE=0 differs from no share", lattice, share, -1);
+    for (int32_t t = 0; t < et.nTiles; ++t) {
+        const EdgeTileMeta r = recordOf<EdgeTileMeta>(meta, t), q = recordOf<EdgeTileMeta>(plain, t);
+        const size_t i = (size_t)t;
+        if (r.edgeBeg != et.edgeBeg[i] || r.nEdges != et.edgeBeg[i + 1] - et.edgeBeg[i] || r.tpOff != et.tpOff[i] || r.nPts != et.tpOff[i + 1] - et.tpOff[i] ||
+            r.tfOff != et.tfOff[i] || r.nFaces != et.tfOff[i + 1] - et.tfOff[i] || r.tcOff != et.tcOff[i] || r.nCells != et.tcOff[i + 1] - et.tcOff[i] ||
+            r.efWidth != et.efWidth[i] || r.ecWidth != et.ecWidth[i]) failLine("edge meta: counts / widths", lattice, share, t);
+        if (r.efBase != ef.remap(et.efBase, t) || r.ecBase != ec.remap(et.ecBase, t)) failLine("edge meta: remapped bases", lattice, share, t);
+        if (q.efBase != et.efBase[i] || q.ecBase != et.ecBase[i]) failLine("edge meta: plain bases", lattice, share, t);
+    }
 }
 }  // namespace
 
@@ -134,6 +197,9 @@ int main(int argc, char** argv) {
                 if (!sameRows(et.efEll, et.efBase[(size_t)t], sef.remap(et.efBase, t), (size_t)et.efWidth[(size_t)t] * T)) failLine("edge: efEll through the shared base", lattice, share, t);
                 if (!sameRows(et.ecEll, et.ecBase[(size_t)t], sec.remap(et.ecBase, t), (size_t)et.ecWidth[(size_t)t] * T)) failLine("edge: ecEll through the shared base", lattice, share, t);
             }
+            checkGeomMeta(gt, fv, cf, lattice, share);
+            checkSmoothMeta(st, pc, pp, pf, lattice, share);
+            checkEdgeMeta(et, sef, sec, lattice, share);
             std::printf("set lattice=%d share=%d geom tiles=%d fv=%d cf=%d faces_x=%.4f points_x=%.4f maxP=%d maxF=%d smooth tiles=%d pc=%d pp=%d pf=%d cells_x=%.4f nbrs_x=%.4f "
                         "edge tiles=%d ef=%d ec=%d\n", lattice, share, gt.nTiles, fv.distinct, cf.distinct, (double)gt.tfOff.back() / m.nF, (double)gt.tpOff.back() / m.nP,
                         gt.maxPoints, gt.maxFaces, st.nTiles, pc.distinct, pp.distinct, pf.distinct, (double)st.tcOff.back() / m.nP, (double)st.tnOff.back() / m.nP,

@@ -193,6 +193,23 @@ def test_per_point_pack_kernel_with_layers(oracle_lib, monkeypatch):
     _same_bits(r, _default(("layers4",), subs, prm, 8, True, monkeypatch, set_up))
 
 
+# ---- the shared points' own tiles, their tables built on either side ---------------------------------------------------------------------
+@pytest.mark.parametrize("constraints", [False, True])
+@pytest.mark.parametrize("knob,where", [("1", "device"), ("0", "host"), ("2", "host")])
+def test_shared_point_tiles_on_the_device_and_on_the_host(oracle_lib, monkeypatch, capfd, knob, where, constraints):
+    """SMGPU_DEVICE_TILES=0 / 2: the tables of the tiles over the shared points (smgpu_halo_configure) come from the host's builder and
+    are uploaded, instead of being adopted from the device build -- same coordinates, bit for bit; the SMGPU_VERBOSE=2 line of every
+    rank says where they were built, so that a silent return to the other side cannot pass"""
+    subs, orcs, prm, table, mo = _hex_case(oracle_lib, (2, 2, 2), (5, 4, 4), constraints)
+    base = _default(("hex8", constraints, 0), subs, prm, 8, False, monkeypatch)
+    capfd.readouterr()
+    r = _run(subs, prm, 8, False, {"SMGPU_DEVICE_TILES": knob, "SMGPU_VERBOSE": "2"}, monkeypatch)
+    said = [line for line in capfd.readouterr().err.splitlines() if "shared-point tiles:" in line and "tables on the" in line]
+    assert len(said) == len(subs) and all(line.endswith("tiles, tables on the " + where) for line in said), (knob, said)
+    assert all(r["tiled"]), r["tiled"]
+    _same_bits(r, base)
+
+
 # ---- 1e: the peer-store transport refuses ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("env", [{}, {"SMGPU_TILES": "0"}, {"SMGPU_PACK_TILES": "0"}])
 def test_peer_store_transport_refuses_without_the_tiled_pack_kernel(oracle_lib, monkeypatch, env):
