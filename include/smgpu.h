@@ -798,7 +798,14 @@ int smgpu_debug_selftest_fpexact(int32_t device, uint64_t seed, int64_t n, int64
  * name: "cellCentres" [3C], "faceCentres" [3F], "faceAreas" [3F], "newPoints" [3P] (proposal of the
  * last iteration before restore), "isFrozenPoint" [P], "edgeMinAngle"/"edgeMaxAngle" [E],
  * "pointMinAngle"/"pointMaxAngle" [P].  Values are converted to double.  Returns the element
- * count through *n; out may be NULL to query the size. */
+ * count through *n; out may be NULL to query the size.
+ * "eaMaybe" [P], "faMaybe" [P]: the verdicts of the f32 filters in front of the two angle evaluators
+ * (csrc/kernels_filter.hpp), 0 = GOOD for sure, 1 = left to the exact kernel ("faMaybe": the point
+ * has an edge the face-angle filter could not decide; the mark is compared with the pass's tag, as for
+ * "faActive").  They describe the latest constraint pass and are meant to be read after
+ * smgpu_debug_propose under SMGPU_DEBUG_FILTERED=1; if that pass did not run the filter in question
+ * (debug_propose without that variable, SMGPU_FILTER=0, the constraint off) the call fails with a
+ * message instead of returning the bytes of an earlier pass. */
 int smgpu_debug_get_field(smgpu_handle* h, const char* name, double* out, int64_t* n);
 /* kind: pointCells, pointPoints, pointFaces, pointEdges, edgeFaces, edgeCells, edges (2/row).
  * offsets/values may be NULL to query nnz. */

@@ -24,6 +24,20 @@
 // rounding of the formula itself: 1 - a^2 >= 2e-3 behind the near-clamp guard) keeps the same distance from the f32 error bound.
 // cos decreases on [0, pi] only, so "sum < large" is accepted only with a + b > kFaSumMin (true a + b > 0 <=> the sum is below
 // pi); a sum above pi has c rising again and fails "c < faCosLo" at worst -- UNSURE, never wrongly GOOD.
+//
+// The budget per form, as an error of the COSINE a verdict rests on -- the part of its margin a GOOD verdict may have consumed.
+// tests/test_gpu_filter_boundary.py reads the verdicts back (debug fields "eaMaybe" / "faMaybe"), walks the thresholds across
+// chosen elements and asserts these figures on every element of every pass; DESIGN.md section 4.2 has the measured ones.
+//   k_edge_angle_filter  1e-6.  A unit-vector component is good to 2e-7 (above: the f64 difference rounded to f32, the squared
+//                        length, rsqrtf and the scaling are three f32 ulps of a value <= 1, 1.8e-7).  A cosine is the dot product
+//                        of two such vectors: |error| <= 2e-7 (|u|_1 + |v|_1) <= 2e-7 * 2 sqrt(3) = 6.9e-7, plus three roundings of
+//                        a sum of magnitude <= 1, 1.8e-7: 8.7e-7.  A thousandth of kEaMargin; vectors outside 1e-15 .. 1e15 in length
+//                        go to the exact path (funit).
+//   k_ea_filter_tile     1.7e-4, a sixth of kEaMargin (derived at the kernel: offsets from the tile origin, guard kRelGuard).
+//   k_fa_edges_filter,   2e-4 + 2e-5 against M = kFaMargin + 2e-5 = 2.02e-3: two acos at under 1e-4 each for |cos| < kNearClamp,
+//   k_fa_filter_tile     plus the rounding of the formula for the cosine of the sum.
+// The margins are applied in smgpu.hip (makePrm: faCosLo, faCosHi; runConstraints: cosSmall) and modelled in numpy by
+// tests/filter_probe.py: a change of a margin, a guard or that host code is a change there.
 #pragma once
 #include "kernels.hpp"
 #include "kernels_tiled.hpp"
@@ -137,6 +151,11 @@ __global__ void __launch_bounds__(kBlock) k_edge_angle_filter(MeshView m, State 
 // whose points straddle a jump of the Morton order has a large R, and a tighter guard sent many of its points to the exact kernel.)  With the offsets in f32 the (current,
 // proposed) pair of each neighbour goes through packed two-wide f32 instructions (v_pk_mul_f32 / v_pk_add_f32): the kernel is
 // bound by VALU issue, and the f64 subtract + convert of every vector was a quarter of it.
+// Scale: the only absolute bound is r2 < 1e30 (the per-point form also has n2 > 1e-30).  Measured by the boundary tests on a
+// block scaled down: at an edge length of 1e-19 (squared lengths at the edge of the f32 denormals) the kernel decides one probed
+// point in 48, from 1e-20 down to 1e-23 none, and every verdict it gives is sound -- what the raw rsq makes of a denormal does
+// not pass "< thr" for all corners of a point.  On blocks stretched 150 : 1 and more half of the probed points go to the exact
+// kernel (the block's wall points keep edges below the guard); the others stay decided, with less than 1e-6 of the margin consumed.
 typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f2 pkfma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }      // v_pk_fma_f32 (see fdot)
 constexpr float kRelGuard = 2.0e-6f;

@@ -189,6 +189,8 @@ struct smgpu_handle {
     // f32 filters in front of the two angle evaluators (kernels_filter.hpp); SMGPU_FILTER=0 disables
     bool useFilter = true, exactAll = false;
     uint8_t *dFaMaybe = nullptr, *dEaMaybe = nullptr;
+    // whether the latest constraint pass ran each filter: the debug fields "eaMaybe" / "faMaybe" are its verdicts, not older bytes
+    bool eaFilterRan = false, faFilterRan = false;
     // the face-angle filter only needs the geometry, so it runs on a side stream next to the proposal kernel
     hipStream_t side = nullptr;
     hipEvent_t evFork = nullptr, evJoin = nullptr;
@@ -292,6 +294,7 @@ static Prm makePrm(const smgpu_handle* h) {
     r.largeAngle = SMGPU_PI * p.maxAngle / 180.0;   // SM.C:1365
     // the f32 face-angle filter tests cos(angle sum): GOOD for sure iff faCosHi < cos < faCosLo (and the sum is below pi); out-of-range
     // parameters leave it undecided (every edge then takes the exact path); NaN compares false everywhere
+    // (tests/filter_probe.py models these lines and cosSmall of runConstraints in numpy: a change here is a change there)
     const double M = (double)kFaMargin + 2.0e-5;
     r.faCosLo = (r.smallAngle >= SMGPU_PI) ? -2.0f : (float)(std::cos(std::max(r.smallAngle, 0.0)) - M);
     r.faCosHi = (r.largeAngle <= 0.0) ? 2.0f : (float)(std::cos(std::min(r.largeAngle, SMGPU_PI)) + M);
@@ -1222,10 +1225,11 @@ static int runConstraints(smgpu_handle* h) {
     const Prm prm = makePrm(h);
     const int gP = gridFor(m.nPoints);
     const bool filt = h->useFilter && !h->exactAll;
+    h->eaFilterRan = h->faFilterRan = false;
     if (h->prm.edgeAngleConstraint) {
         const uint8_t* eaMaybe = nullptr;
         if (filt && h->eaCoop) {
-            const float cosSmall = (float)std::cos(prm.smallAngle);
+            const float cosSmall = (float)std::cos(prm.smallAngle);      // (modelled in tests/filter_probe.py, as makePrm)
             if (h->useTiles && h->smoothT == 256) {
                 const size_t ldsB = sizeof(float) * (6 * (size_t)h->sv.maxPoints + 16);
                 if (launchK(h, K_EA_FILTER, [&] {
@@ -1234,6 +1238,7 @@ static int runConstraints(smgpu_handle* h) {
                     })) return 1;
             } else if (launchK(h, K_EA_FILTER, [&] { hipLaunchKernelGGL(k_edge_angle_filter, dim3(gP), dim3(kBlock), 0, h->stream, m, s, prm, cosSmall, h->dEaMaybe); })) return 1;
             eaMaybe = h->dEaMaybe;
+            h->eaFilterRan = true;
         }
         if (h->eaCoop) {
             if (launchK(h, K_EDGE_ANGLE, [&] {
@@ -1265,6 +1270,7 @@ static int runConstraints(smgpu_handle* h) {
             if (nextFaGen(h, h->stream)) return 1;
             s.faGen = h->st.faGen;
         }
+        h->faFilterRan = faMaybe != nullptr;
         if (h->faExactOnSide) h->faExactOnSide = false;          // done behind the filter on the side stream
         else if (runFaExactPass(h, s, faMaybe, h->stream)) return 1;
         if (h->walkMode < 0 && decideWalkMode(h)) return 1;
@@ -2786,6 +2792,14 @@ int smgpu_debug_get_field(smgpu_handle* h, const char* name, double* out, int64_
     else if (s == "pointMaxAngle") { dsrc = st.ptMax; cnt = P; }
     else if (s == "isFrozenPoint") { bsrc = st.frozen; cnt = P; }
     else if (s == "faActive") { bsrc = st.faActive; cnt = P; }
+    else if (s == "eaMaybe") {
+        if (!h->eaFilterRan) return fail("field eaMaybe: the edge-angle filter did not run in the latest constraint pass (smgpu_debug_propose under SMGPU_DEBUG_FILTERED=1, filters and the edge-angle constraint on)");
+        bsrc = h->dEaMaybe; cnt = P;
+    }
+    else if (s == "faMaybe") {
+        if (!h->faFilterRan) return fail("field faMaybe: the face-angle filter did not run in the latest constraint pass (smgpu_debug_propose under SMGPU_DEBUG_FILTERED=1, filters and the face-angle constraint on)");
+        bsrc = h->dFaMaybe; cnt = P;
+    }
     else if (s == "layerNormals" && (h->layersOn || h->bndOn)) { dsrc = st.layerNormal; cnt = 3 * P; }
     else if ((s == "layerHops" || s == "layerOuterMap") && h->layersOn) {
         *n = P;
@@ -2802,7 +2816,7 @@ int smgpu_debug_get_field(smgpu_handle* h, const char* name, double* out, int64_
         std::vector<uint8_t> tmp((size_t)cnt);
         HIP_OK(hipMemcpyAsync(tmp.data(), bsrc, (size_t)cnt, hipMemcpyDeviceToHost, h->stream));
         HIP_OK(hipStreamSynchronize(h->stream));
-        const bool tagged = (bsrc == st.faActive);   // marks carry the iteration's tag
+        const bool tagged = (bsrc == st.faActive) || (bsrc == h->dFaMaybe);   // marks carry the iteration's tag
         for (int64_t i = 0; i < cnt; ++i) out[i] = tagged ? (tmp[(size_t)i] == st.faGen ? 1.0 : 0.0) : (double)tmp[(size_t)i];
     }
     return 0;
