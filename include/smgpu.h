@@ -352,7 +352,8 @@ int smgpu_tangle_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done);
 
 /* ---- the quality constraint (DESIGN.md "Mesh quality", 10.14) --------------------------------------------------------------
  * The tangle constraint with up to three more criteria, taken from meshQualityDict: a point also stays at its current coordinates
- * when its move would push a face's non-orthogonality or skewness over a limit.  Opt-in, serial only (an engine without a halo);
+ * when its move would push a face's non-orthogonality or skewness over a limit.  Opt-in; this entry is for an engine without a halo
+ * (smgpu_set_quality_constraint_coupled below is the form for an engine with one);
  * with it off nothing the engine launches, prints or returns changes.
  *
  * Notation is the tangle constraint's (10.12): x are the points an iteration starts from, x' the points the loop produced, C_f,
@@ -416,6 +417,67 @@ typedef struct smgpu_quality_constraint_state {
 int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint_params* p, int32_t on);
 int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n);
 int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint_state* out);
+
+/* ---- the quality constraint on a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.15) -------------------------
+ * The contract above (10.14), read on the GLOBAL mesh, for an engine whose halo is configured.  Unlike the tangle verdict of
+ * 10.13 a face limit is not local to a rank: a PROCESSOR FACE is an internal face of the global mesh.  It takes the internal-face
+ * definitions of ortho_f and skew_f with C_N = the neighbour rank's owner cell centre at the points being judged, and is tested
+ * against maxNonOrtho and maxInternalSkewness, never against maxBoundarySkewness.  Physical boundary faces and internal faces are
+ * judged as in 10.14.  processorCyclic patches and two patches to one neighbour stay refused, as for the coupled report.
+ *
+ * WHO JUDGES.  Both ranks that hold a processor face judge it, each on its own geometry; a rank that finds it bad (and not
+ * exempt) flags its own cell, the face's owner in that sub-domain.  Reversing a face and swapping its cells leaves both values
+ * unchanged to rounding, so the two sides agree EXCEPT WITHIN ROUNDING OF A LIMIT: at such a tie only one side's cell goes back
+ * in that pass.  The loop still ends, at the latest with the full revert, and the invariant then holds in each rank's own
+ * verdicts.  (A single-sided verdict would cost a third exchange per pass.)
+ *
+ * EXEMPTION.  Enabling evaluates the current points once on every rank, with one exchange of cell centres; a face bad there is
+ * exempt on each rank that holds it; cells are exempt as in 10.13.
+ * Per iteration, behind every rank's smgpu_iter_end, for k = 0 .. passes: 10.13's loop with B = the union of the ranks' bad cells
+ * by the definition above; the marks of shared points and the verdict travel exactly as in 10.13.
+ * INVARIANT: 10.14's, on the global mesh; copies of a shared point stay bit-identical after every pass.
+ *
+ * The calls, on every rank (a call out of order is an error):
+ *   smgpu_set_quality_constraint_coupled(on != 0)  evaluates the current points, packs the owner cell centre of every processor
+ *                             face into sendCc (patch order of `coupling`, as smgpu_quality_coupled_pack) and returns with sendCc
+ *                             complete; the constraint is pending.
+ *   the host                  moves sendCc -> recvCc as for the coupled report.
+ *   smgpu_quality_constraint_coupled_exempt        the face verdicts with recvCc become the exempt faces; the constraint is on.
+ * and behind every smgpu_iter_end, before the next smgpu_iter_begin (which refuses while passes are due), for each pass:
+ *   smgpu_quality_constraint_pass_begin   the geometry of the points the engine holds into buffers of the constraint's own, the
+ *                             pack of ITS cell centres into sendCc; returns with sendCc complete.
+ *   the host                  moves sendCc -> recvCc (on the exchange stream, if one is set).
+ *   smgpu_quality_constraint_pass_faces   the face verdicts with recvCc, the cells, the marks, the pack of sendT; returns the
+ *                             rank's count of bad cells, with sendT complete.
+ *   the host                  sums the counts over ALL ranks; sum > 0 and k < passes: moves sendT -> recvT as exchange F.
+ *   smgpu_quality_constraint_pass_end     as smgpu_tangle_pass_end.
+ *
+ * One smgpu_quality_constraint_record per iteration and rank: passes and fullRevert are the global values; nBadCells and
+ * nTangledCells the rank's own at k = 0; nPointsReverted the rank's own, a shared point counting on its master only (10.13);
+ * nNonOrthoFaces / nSkewFaces the rank's own, a processor face counting only on the side with myRank < neighbRank.  Summed over
+ * the ranks they are the record of the undecomposed mesh.  nExemptFaces of the state follows the same counted-once rule,
+ * nExemptCells is the rank's own.  smgpu_get_quality_constraint_records / _state serve both forms.
+ * EQUIVALENCES.  All three criteria off: the coupled tangle constraint's points and shared record fields, bit for bit.  A single
+ * sub-domain without processor patches: the serial constraint's run, bit for bit.
+ *
+ * Goes together with layers, both foam variants, both sync variants, every transport and arrangement of the iteration.  Refused:
+ * an engine without a halo (smgpu_set_quality_constraint is its form, and keeps refusing an engine with one), boundary point
+ * smoothing, passes < 0, a NaN limit, a null buffer that is needed, a call between smgpu_iter_begin and smgpu_iter_end, enabling
+ * while either tangle form is on and vice versa, smgpu_halo_configure while it is on.  The trace and the guard stay refused on an
+ * engine with a halo.  Memory, allocated at enabling outside deviceBytes: 10.14's, plus nShared bytes, 4 (nProcFaces +
+ * nBoundaryFaces) bytes of tables of its own (a coupled report packed with another coupling does not disturb them) and 14 KiB of
+ * records; the caller owns the four exchange buffers.  on == 0 (either entry point) switches it off and releases everything. */
+struct smgpu_quality_coupling;
+typedef struct smgpu_quality_constraint_halo_desc {
+    void *sendT, *recvT;                    /* device, nSend / nRecv int32, as smgpu_tangle_halo_desc */
+    void *sendCc, *recvCc;                  /* device, 3 doubles per processor face in patch order, as smgpu_quality_coupled_pack */
+    const struct smgpu_quality_coupling* coupling;   /* the processor patches (below); read during the call only */
+} smgpu_quality_constraint_halo_desc;
+int smgpu_set_quality_constraint_coupled(smgpu_handle* h, const smgpu_quality_constraint_params* p, const smgpu_quality_constraint_halo_desc* d, int32_t on);
+int smgpu_quality_constraint_coupled_exempt(smgpu_handle* h);
+int smgpu_quality_constraint_pass_begin(smgpu_handle* h);                                   /* after smgpu_iter_end */
+int smgpu_quality_constraint_pass_faces(smgpu_handle* h, int64_t* nBadLocal);
+int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done);
 
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):

@@ -201,6 +201,11 @@ class QualityCoupling(C.Structure):
     _fields_ = [("myRank", C.c_int32), ("nPatches", C.c_int32), ("patchStart", c_i32p), ("patchSize", c_i32p), ("neighbRank", c_i32p)]
 
 
+class QualityConstraintHaloDesc(C.Structure):
+    """smgpu_quality_constraint_halo_desc"""
+    _fields_ = [("sendT", C.c_void_p), ("recvT", C.c_void_p), ("sendCc", C.c_void_p), ("recvCc", C.c_void_p), ("coupling", C.POINTER(QualityCoupling))]
+
+
 class QualityPart(C.Structure):
     """smgpu_quality_part: Quality with sumNonOrth in place of avgNonOrth"""
     _fields_ = [("sumNonOrth" if n == "avgNonOrth" else n, t) for n, t in Quality._fields_]
@@ -287,6 +292,11 @@ SYMBOLS = {
     "smgpu_set_quality_constraint": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintParams), C.c_int32]),
     "smgpu_get_quality_constraint_records": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintRecord), C.c_int64, C.POINTER(C.c_int64)]),
     "smgpu_get_quality_constraint_state": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintState)]),
+    "smgpu_set_quality_constraint_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintParams), C.POINTER(QualityConstraintHaloDesc), C.c_int32]),
+    "smgpu_quality_constraint_coupled_exempt": (C.c_int, [C.c_void_p]),
+    "smgpu_quality_constraint_pass_begin": (C.c_int, [C.c_void_p]),
+    "smgpu_quality_constraint_pass_faces": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "smgpu_quality_constraint_pass_end": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "smgpu_quality_coupled_pack": (C.c_int, [C.c_void_p, C.POINTER(QualityCoupling), C.c_void_p, C.POINTER(C.c_int64)]),
     "smgpu_quality_coupled_report": (C.c_int, [C.c_void_p, C.POINTER(QualityParams), C.c_void_p, C.POINTER(QualityPart)]),
     "smgpu_quality_coupled_field": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),

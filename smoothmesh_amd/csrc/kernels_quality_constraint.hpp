@@ -222,4 +222,63 @@ __global__ void __launch_bounds__(64) k_qc_verdict(QcDev* __restrict__ d, Accum*
     else { d->t.full = 0; rec->passes += 1; }
 }
 
+// ---- the coupled form (smgpu_set_quality_constraint_coupled, DESIGN.md "Mesh quality", 10.15): a sub-domain of a decomposed mesh ----
+// The evaluation is the one above, ungated (gate = NULL, pass = 0): k_qc_tile (or k_qc_open + the direct geometry kernels), then
+// k_quality_pack of the constraint's own cell centres; the host moves them; then k_qc_faces_coupled, k_qc_cells, k_tangle_pack.
+// The verdict is the host's, on the count summed over the ranks, as in 10.13: k_tangle_combine, k_tangle_apply_counted, k_qc_close.
+
+// k_qc_faces on a sub-domain.  slot[f - nInternalFaces]: 10.4's table (-1: a physical boundary face; else the face's place in
+// recvCc, | kQualityNotCounted on the side with myRank > neighbRank), decoded as qNeighbour decodes it.  A processor face is an
+// internal face of the global mesh: qcFace with internal = true and C_N from recvCc, the two internal limits, the flag on its
+// owner (the neighbour cell is the other rank's, which judges the face itself), and the counts only on the counted side.  Lanes of
+// internal and physical faces take k_qc_faces' path.  exemptOut != NULL: as k_qc_faces.
+__global__ void __launch_bounds__(kQcBlock) k_qc_faces_coupled(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                                const double* __restrict__ fArea, const double* __restrict__ cellCtr,
+                                                                const int* __restrict__ own, const int* __restrict__ nei,
+                                                                const int* __restrict__ slot, const double* __restrict__ recvCc, QcLimits lim,
+                                                                const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
+                                                                uint8_t* __restrict__ cellFlag, QcDev* __restrict__ d) {
+    const int f = blockIdx.x * kQcBlock + threadIdx.x;
+    bool badNO = false, badSk = false, counted = true;
+    if (f < m.nFaces) {
+        const bool inner = f < m.nInternalFaces;
+        const int sl = inner ? -1 : slot[f - m.nInternalFaces];
+        const bool internal = inner || sl >= 0;
+        const int o = own[f], n = inner ? nei[f] : 0;
+        counted = sl < 0 || !(sl & kQualityNotCounted);
+        const V3 CN = inner ? ldv(cellCtr, n) : (sl >= 0 ? ldv(recvCc, sl & kQualitySlotMask) : v3(0, 0, 0));
+        double ortho, skew;
+        qcFace(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, o), internal, CN, f, ortho, skew);
+        badNO = internal && lim.nonOrthoOn && ortho < lim.cosT;
+        badSk = internal ? (lim.internalSkewOn && skew > lim.maxInternalSkew) : (lim.boundarySkewOn && skew > lim.maxBoundarySkew);
+        if (exemptOut) exemptOut[f] = (badNO || badSk) ? 1 : 0;
+        else if (exempt[f]) badNO = badSk = false;
+        if ((badNO || badSk) && !exemptOut) {
+            cellFlag[o] = 1;
+            if (inner) cellFlag[n] = 1;
+        }
+    }
+    const int nNO = __syncthreads_count((badNO && counted) ? 1 : 0), nSk = __syncthreads_count((badSk && counted) ? 1 : 0),
+              nAny = __syncthreads_count(((badNO || badSk) && counted) ? 1 : 0);
+    if (threadIdx.x == 0) {
+        if (nNO > 0) atomicAdd(&d->nonOrthoNow, nNO);
+        if (nSk > 0) atomicAdd(&d->skewNow, nSk);
+        if (nAny > 0) atomicAdd(&d->facesNow, nAny);
+    }
+}
+
+// k_tangle_close's twin: closes the record of an iteration from the host's verdict; one wave, lane 0 writes every word in plain
+// C++ (nPointsReverted is the applies': the slot was zeroed before the iteration's first pass).
+__global__ void __launch_bounds__(64) k_qc_close(smgpu_quality_constraint_record* __restrict__ rec, long long number, int passes, int fullRevert,
+                                                  long long nBadCells, long long nTangledCells, long long nNonOrthoFaces, long long nSkewFaces) {
+    if (threadIdx.x != 0) return;
+    rec->iteration = number;
+    rec->passes = passes;
+    rec->fullRevert = fullRevert;
+    rec->nBadCells = nBadCells;
+    rec->nTangledCells = nTangledCells;
+    rec->nNonOrthoFaces = nNonOrthoFaces;
+    rec->nSkewFaces = nSkewFaces;
+}
+
 }  // namespace smgpu

@@ -361,6 +361,7 @@ int smgpu_set_tangle_constraint_coupled(smgpu_handle* h, const smgpu_tangle_para
     if (h->bndOn)
         return fail("smgpu_set_tangle_constraint_coupled: not available on an engine with boundary point smoothing (it rewrites the proposals of the "
                     "boundary points from state that a reverted iteration would leave ahead of the points)");
+    if (h->qc.on) return fail("smgpu_set_tangle_constraint_coupled: the quality constraint is on (smgpu_set_quality_constraint_coupled), and it contains this one; switch it off first");
     if (h->iterOpen) return fail("smgpu_set_tangle_constraint_coupled: between smgpu_iter_begin and smgpu_iter_end");
     if (!d || (h->nSend && !d->sendT) || (h->nRecv && !d->recvT)) return fail("smgpu_set_tangle_constraint_coupled: null exchange buffer");
     if (tangleOff(h)) return 1;
@@ -585,15 +586,254 @@ int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint
     q.on = true;
     return 0;
 }
+static int qualityConstraintCoupledFlush(smgpu_handle* h);
 int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n) {
     if (!h || !n) return fail("null argument");
+    if (h->qc.coupled) {   // the records of the chunk in use are still on the device
+        if (h->qc.k >= 0) return fail("smgpu_get_quality_constraint_records: between the passes of an iteration (smgpu_quality_constraint_pass_begin / _end)");
+        HIP_OK(hipSetDevice(h->device));
+        if (qualityConstraintCoupledFlush(h)) return 1;
+    }
     return h->qc.slab.drain(out, cap, n, "smgpu_get_quality_constraint_records");
 }
 int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint_state* out) {
     if (!h || !out) return fail("null argument");
     const QualityConstraintHost& q = h->qc;
-    *out = smgpu_quality_constraint_state{q.on ? 1 : 0, q.prm.passes, q.prm.maxNonOrtho, q.prm.maxInternalSkewness, q.prm.maxBoundarySkewness,
-                                          q.on ? q.nExemptCells : 0, q.on ? q.nExemptFaces : 0, q.on ? h->iterCount - q.since : 0};
+    const bool on = q.on && !q.pending;
+    const int64_t number = q.coupled ? q.count : h->iterCount - q.since;
+    *out = smgpu_quality_constraint_state{on ? 1 : 0, q.prm.passes, q.prm.maxNonOrtho, q.prm.maxInternalSkewness, q.prm.maxBoundarySkewness,
+                                          on ? q.nExemptCells : 0, on ? q.nExemptFaces : 0, on ? number : 0};
+    return 0;
+}
+
+// ---- the coupled form on an engine with a halo (DESIGN.md "Mesh quality", 10.15) ----
+// 10.13's protocol with one more exchange per pass: a processor face is an internal face of the global mesh, and its verdict needs
+// the neighbour rank's cell centre at the points being judged.  Every kernel goes onto the engine's stream, behind the iteration's
+// own; x is the buffer smgpu_iter_end swapped out, as in 10.13.
+static int qualityConstraintCoupledFlush(smgpu_handle* h) {
+    QualityConstraintHost& q = h->qc;
+    if (q.slabUsed > 0) {
+        if (q.slab.readBack(h->stream, q.slabUsed)) return 1;
+        HIP_OK(hipStreamSynchronize(h->stream));
+        q.slab.keep(q.slabUsed);
+    }
+    q.slabUsed = 0;
+    q.slabFresh = false;
+    return 0;
+}
+// the first half of an evaluation of the points ptsCur names: qualityConstraintEvaluate's geometry launches (ungated), then the
+// pack of the constraint's own cell centres -- never the loop's, which are those of other points -- and the wait: sendCc is the
+// host's to move
+static int qualityConstraintCoupledGeometry(smgpu_handle* h, bool enabling) {
+    const MeshView& m = h->mv;
+    QualityConstraintHost& q = h->qc;
+    State ts = h->st;
+    ts.cellCtr = q.cellCtr;
+    ts.acc = q.acc;
+    ts.stats = nullptr;
+    if (h->useTiles) {
+        const int nT = h->gt.nTiles;
+        if (nT > 0)
+            withGeomTile(h, [&](auto tile, auto org) {
+                constexpr int T = decltype(tile)::value;
+                constexpr bool ORG = decltype(org)::value;
+                ensureDynLds(k_qc_tile<T, ORG>, h->device, h->geomLds);
+                hipLaunchKernelGGL((k_qc_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, nT, h->xcdMap,
+                                   enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptCell, enabling ? q.exemptCell : (uint8_t*)nullptr, q.tangled, q.dev,
+                                   0, (const smgpu_iter_stats*)nullptr);
+            });
+    } else {
+        hipLaunchKernelGGL(k_qc_open, dim3(1), dim3(64), 0, h->stream, q.acc, (const smgpu_iter_stats*)nullptr);
+        if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
+        if (m.nCells > 0) hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
+    }
+    if (q.nProc > 0)
+        hipLaunchKernelGGL(k_quality_pack, dim3((q.nProc + kQualityBlock - 1) / kQualityBlock), dim3(kQualityBlock), 0, h->stream, (const int*)h->q.own,
+                           (const double*)q.cellCtr, (const int*)q.procFace, q.nProc, q.sendCc);
+    HIP_OK(hipGetLastError());
+    return checkDeviceError(h);
+}
+// the second half, recvCc moved by the host: the face verdicts, the cells, and in a pass the pack of the shared points' marks; *qd:
+// the counts, read with the loop's error word -- sendT is complete when this returns
+static int qualityConstraintCoupledVerdicts(smgpu_handle* h, bool enabling, QcDev* qd) {
+    const MeshView& m = h->mv;
+    QualityConstraintHost& q = h->qc;
+    if (computeAfterExch(h)) return 1;          // exchange Cc has been enqueued by the host
+    const double *fCtr = h->st.fCtr, *fArea = h->st.fArea, *pts = h->st.ptsCur;
+    if (m.nFaces > 0)
+        hipLaunchKernelGGL(k_qc_faces_coupled, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, pts, fCtr, fArea, (const double*)q.cellCtr,
+                           (const int*)h->q.own, (const int*)h->q.nei, (const int*)q.slot, (const double*)q.recvCc, q.lim,
+                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag, q.dev);
+    const int gCells = (m.nCells + kQcBlock - 1) / kQcBlock;
+    if (m.nCells > 0 && !h->useTiles)
+        hipLaunchKernelGGL(k_qc_cells<true>, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, fCtr, fArea, (const double*)q.cellCtr,
+                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptCell, enabling ? q.exemptCell : (uint8_t*)nullptr, (const uint8_t*)nullptr,
+                           q.cellFlag, q.marks, q.dev, 0, (const smgpu_iter_stats*)nullptr);
+    else if (m.nCells > 0 && !enabling)   // (enabling with tiles: k_qc_tile has left the exempt bytes and their count)
+        hipLaunchKernelGGL(k_qc_cells<false>, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr,
+                           (const uint8_t*)nullptr, (uint8_t*)nullptr, (const uint8_t*)q.tangled, q.cellFlag, q.marks, q.dev, 0, (const smgpu_iter_stats*)nullptr);
+    if (!enabling && h->nSend > 0)
+        hipLaunchKernelGGL(k_tangle_pack, dim3((h->nSend + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, h->nSend, (const int*)h->dSendShared,
+                           (const int*)h->dSharedLocal, (const uint8_t*)q.marks, q.sendT);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(qd, q.dev, sizeof(QcDev), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipMemsetAsync(q.dev, 0, sizeof(QcDev), h->stream));
+    return checkDeviceError(h);
+}
+
+int smgpu_set_quality_constraint_coupled(smgpu_handle* h, const smgpu_quality_constraint_params* p, const smgpu_quality_constraint_halo_desc* d, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityConstraintOff(h);
+    const char* api = "smgpu_set_quality_constraint_coupled";
+    const smgpu_quality_constraint_params prm = p ? *p : smgpu_quality_constraint_params{65.0, 4.0, 20.0, 2};
+    if (prm.passes < 0) return fail("smgpu_set_quality_constraint_coupled: passes < 0");
+    if (std::isnan(prm.maxNonOrtho) || std::isnan(prm.maxInternalSkewness) || std::isnan(prm.maxBoundarySkewness))
+        return fail("smgpu_set_quality_constraint_coupled: a limit is NaN");
+    if (!h->haloOn)
+        return fail("smgpu_set_quality_constraint_coupled: the engine has no halo (smgpu_halo_configure); a serial engine takes smgpu_set_quality_constraint");
+    if (h->bndOn)
+        return fail("smgpu_set_quality_constraint_coupled: not available on an engine with boundary point smoothing (it rewrites the proposals of the "
+                    "boundary points from state that a reverted iteration would leave ahead of the points)");
+    if (h->tg.on) return fail("smgpu_set_quality_constraint_coupled: the tangle constraint is on (smgpu_set_tangle_constraint_coupled), and this constraint contains it; switch it off first");
+    if (h->iterOpen) return fail("smgpu_set_quality_constraint_coupled: between smgpu_iter_begin and smgpu_iter_end");
+    if (!d || !d->coupling || (h->nSend && !d->sendT) || (h->nRecv && !d->recvT)) return fail("smgpu_set_quality_constraint_coupled: null exchange buffer");
+    const MeshView& m = h->mv;
+    std::vector<int32_t> key;
+    std::vector<int> procFace, slot;
+    int64_t nProc = 0, notCounted = 0;
+    if (qualityCouplingTables(api, m, d->coupling, key, procFace, slot, nProc, notCounted)) return 1;
+    if (nProc > 0 && (!d->sendCc || !d->recvCc)) return fail("smgpu_set_quality_constraint_coupled: null exchange buffer");
+    if (qualityConstraintOff(h)) return 1;
+    if (flushDeferred(h)) return 1;
+    if (qualityEnsure(h)) return 1;                  // owner / neighbour by face
+    const size_t nMark = ((size_t)std::max(1, m.nPoints) + 3) & ~(size_t)3, nCell = (size_t)std::max(1, m.nCells), nFace = (size_t)std::max(1, m.nFaces);
+    const size_t nB = (size_t)(m.nFaces - m.nInternalFaces);
+    QualityConstraintHost& q = h->qc;
+    if (q.block.alloc(&q.dev, 1) || q.block.alloc(&q.exemptCell, nCell) || q.block.alloc(&q.cellFlag, nCell) || q.block.alloc(&q.tangled, nCell) || q.block.alloc(&q.exemptFace, nFace) ||
+        q.block.alloc(&q.marks, nMark) || q.block.alloc(&q.cellCtr, 3 * nCell) || q.block.alloc(&q.acc, 1) ||
+        q.block.alloc(&q.counted, (size_t)std::max(1, h->nShared)) || q.block.alloc(&q.procFace, (size_t)std::max<int64_t>(1, nProc)) ||
+        q.block.alloc(&q.slot, std::max<size_t>(1, nB)))
+        return q.block.failed("the quality constraint");
+    HIP_OK(hipMemsetAsync(q.dev, 0, sizeof(QcDev), h->stream));
+    HIP_OK(hipMemsetAsync(q.exemptCell, 0, nCell, h->stream));
+    HIP_OK(hipMemsetAsync(q.cellFlag, 0, nCell, h->stream));
+    HIP_OK(hipMemsetAsync(q.tangled, 0, nCell, h->stream));
+    HIP_OK(hipMemsetAsync(q.exemptFace, 0, nFace, h->stream));
+    HIP_OK(hipMemsetAsync(q.marks, 0, nMark, h->stream));
+    HIP_OK(hipMemsetAsync(q.acc, 0, sizeof(Accum), h->stream));
+    if (h->nShared > 0) HIP_OK(hipMemcpyAsync(q.counted, h->sharedMasterHost.data(), (size_t)h->nShared, hipMemcpyHostToDevice, h->stream));
+    if (nProc) HIP_OK(hipMemcpyAsync(q.procFace, procFace.data(), sizeof(int) * (size_t)nProc, hipMemcpyHostToDevice, h->stream));
+    if (nB) HIP_OK(hipMemcpyAsync(q.slot, slot.data(), sizeof(int) * nB, hipMemcpyHostToDevice, h->stream));
+    q.prm = prm;
+    // cosT exactly as qualityThresholds() forms the report's cosine
+    const smgpu_quality_params rp{prm.maxNonOrtho, prm.maxInternalSkewness, 1e-6, 1000.0};
+    q.lim = QcLimits{qualityThresholds(&rp).cosNonOrth, prm.maxInternalSkewness, prm.maxBoundarySkewness, prm.maxNonOrtho < 180.0 ? 1 : 0,
+                     prm.maxInternalSkewness > 0.0 ? 1 : 0, prm.maxBoundarySkewness > 0.0 ? 1 : 0};
+    q.nProc = (int)nProc;
+    q.sendT = (int*)d->sendT; q.recvT = (int*)d->recvT;
+    q.sendCc = (double*)d->sendCc; q.recvCc = (double*)d->recvCc;
+    // the exempt cells and faces: one evaluation of the current points, its second half behind the host's exchange of Cc
+    // (the wait inside also covers the uploads from the host vectors above)
+    if (qualityConstraintCoupledGeometry(h, true)) { q.release(); return 1; }
+    q.count = 0;
+    q.k = -1;
+    q.stage = 0;
+    q.coupled = true;
+    q.pending = true;
+    q.on = true;
+    return 0;
+}
+int smgpu_quality_constraint_coupled_exempt(smgpu_handle* h) {
+    if (!h) return fail("null handle");
+    QualityConstraintHost& q = h->qc;
+    if (!q.coupled || !q.pending)
+        return fail("smgpu_quality_constraint_coupled_exempt: no coupled quality constraint waits for its exempt faces (smgpu_set_quality_constraint_coupled)");
+    if (h->iterOpen) return fail("smgpu_quality_constraint_coupled_exempt: between smgpu_iter_begin and smgpu_iter_end");
+    HIP_OK(hipSetDevice(h->device));
+    QcDev qd{};
+    if (qualityConstraintCoupledVerdicts(h, true, &qd)) { (void)qualityConstraintOff(h); return 1; }
+    q.nExemptCells = qd.t.badNow;
+    q.nExemptFaces = qd.facesNow;
+    q.pending = false;
+    return 0;
+}
+// behind smgpu_iter_end: the iteration waits for its passes
+static void qualityConstraintCoupledIterEnd(smgpu_handle* h, const double* x) {
+    h->qc.x = x;
+    h->qc.k = 0;
+    h->qc.reverting = 0;
+    h->qc.stage = 0;
+}
+int smgpu_quality_constraint_pass_begin(smgpu_handle* h) {
+    if (!h) return fail("null handle");
+    QualityConstraintHost& q = h->qc;
+    if (!q.coupled) return fail("smgpu_quality_constraint_pass_begin: the coupled quality constraint is not on (smgpu_set_quality_constraint_coupled)");
+    if (q.pending) return fail("smgpu_quality_constraint_pass_begin: the exempt faces have not been taken (smgpu_quality_constraint_coupled_exempt)");
+    if (h->iterOpen) return fail("smgpu_quality_constraint_pass_begin: between smgpu_iter_begin and smgpu_iter_end");
+    if (q.k < 0) return fail("smgpu_quality_constraint_pass_begin: no iteration waits for its passes (the passes follow smgpu_iter_end)");
+    if (q.stage != 0) return fail("smgpu_quality_constraint_pass_begin: the pass in hand has not been closed (smgpu_quality_constraint_pass_faces / _end)");
+    HIP_OK(hipSetDevice(h->device));
+    if (q.k == 0 && (!q.slabFresh || q.slabUsed >= QualityConstraintHost::kChunk)) {
+        if (qualityConstraintCoupledFlush(h)) return 1;
+        if (q.slab.begin(h->stream, QualityConstraintHost::kChunk)) return 1;
+        q.slabFresh = true;
+    }
+    if (qualityConstraintCoupledGeometry(h, false)) return 1;
+    q.stage = 1;
+    return 0;
+}
+int smgpu_quality_constraint_pass_faces(smgpu_handle* h, int64_t* nBadLocal) {
+    if (!h || !nBadLocal) return fail("null argument");
+    QualityConstraintHost& q = h->qc;
+    if (!q.coupled) return fail("smgpu_quality_constraint_pass_faces: the coupled quality constraint is not on (smgpu_set_quality_constraint_coupled)");
+    if (q.stage != 1 || q.k < 0) return fail("smgpu_quality_constraint_pass_faces without smgpu_quality_constraint_pass_begin");
+    HIP_OK(hipSetDevice(h->device));
+    QcDev qd{};
+    if (qualityConstraintCoupledVerdicts(h, false, &qd)) return 1;
+    if (q.k == 0) { q.n0[0] = qd.t.badNow; q.n0[1] = qd.tangledNow; q.n0[2] = qd.nonOrthoNow; q.n0[3] = qd.skewNow; }
+    q.stage = 2;
+    *nBadLocal = qd.t.badNow;
+    return 0;
+}
+int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done) {
+    if (!h || !done) return fail("null argument");
+    QualityConstraintHost& q = h->qc;
+    if (!q.coupled) return fail("smgpu_quality_constraint_pass_end: the coupled quality constraint is not on (smgpu_set_quality_constraint_coupled)");
+    if (q.stage != 2 || q.k < 0) return fail("smgpu_quality_constraint_pass_end without smgpu_quality_constraint_pass_faces");
+    if (nBadGlobal < 0) return fail("smgpu_quality_constraint_pass_end: nBadGlobal < 0");
+    HIP_OK(hipSetDevice(h->device));
+    smgpu_quality_constraint_record* rec = nullptr;
+    if (q.slab.slot(q.slabUsed, &rec)) return 1;
+    const int nP = h->mv.nPoints;
+    const bool full = nBadGlobal > 0 && q.k == q.prm.passes;
+    if (nBadGlobal > 0) {
+        if (!full) {
+            if (computeAfterExch(h)) return 1;      // exchange T has been enqueued by the host
+            if (h->nShared > 0 && h->nRecv > 0)
+                hipLaunchKernelGGL(k_tangle_combine, dim3((h->nShared + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, h->nShared,
+                                   (const int*)h->dSharedLocal, (const int*)h->dCombOff, (const int*)h->dCombSlots, (const int*)q.recvT, q.marks);
+            ++q.reverting;
+        }
+        // the record begins with the tangle constraint's (kernels_quality_constraint.hpp)
+        const int grid = std::max(1, (int)(((int64_t)nP + kTangleCountedPts - 1) / kTangleCountedPts));
+        hipLaunchKernelGGL(k_tangle_apply_counted, dim3(grid), dim3(kTangleBlock), 0, h->stream, q.x, h->st.ptsCur, q.marks, nP, full ? 1 : 0,
+                           (const int*)h->dSharedSlot, (const uint8_t*)q.counted, reinterpret_cast<smgpu_tangle_record*>(rec));
+        // points went back: the geometry smgpu_iter_ahead left for the next iteration is that of other points
+        h->geomAheadDone = false;
+        h->q.epoch++;
+    }
+    const bool close = nBadGlobal == 0 || full;
+    if (close) {
+        hipLaunchKernelGGL(k_qc_close, dim3(1), dim3(64), 0, h->stream, rec, (long long)(q.count + 1), q.reverting, full ? 1 : 0, (long long)q.n0[0],
+                           (long long)q.n0[1], (long long)q.n0[2], (long long)q.n0[3]);
+        ++q.count;
+        ++q.slabUsed;
+        q.k = -1;
+    } else ++q.k;
+    q.stage = 0;
+    *done = close ? 1 : 0;
+    HIP_OK(hipGetLastError());
     return 0;
 }
 

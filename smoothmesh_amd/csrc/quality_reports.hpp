@@ -294,24 +294,25 @@ int smgpu_quality_motion_field(smgpu_handle* h, const char* name, double* out, i
 }
 
 // ---- the coupled reports of a sub-domain (DESIGN.md "Mesh quality", 10.4 and 10.8) -----------------------------------------
-int smgpu_quality_coupled_pack(smgpu_handle* h, const smgpu_quality_coupling* c, void* sendCc, int64_t* nProcFaces) {
-    if (!h || !c) return fail("null argument");
-    if (h->iterOpen) return fail("smgpu_quality_coupled_pack: not between smgpu_iter_begin and smgpu_iter_end");
-    const MeshView& m = h->mv;
+// A coupling description, checked (the patches inside the boundary faces, disjoint, one per neighbour, none to this rank), as
+// 10.4's tables: key (what two couplings are compared by), procFace (the processor faces in patch order), slot (by boundary face:
+// -1 on a physical patch, else the face's place in patch order | kQualityNotCounted on the side with myRank > neighbRank)
+extern "C++" {
+static int qualityCouplingTables(const std::string& api, const MeshView& m, const smgpu_quality_coupling* c, std::vector<int32_t>& key,
+                                 std::vector<int>& procFace, std::vector<int>& slot, int64_t& nProc, int64_t& notCounted) {
     if (c->nPatches < 0 || (c->nPatches && (!c->patchStart || !c->patchSize || !c->neighbRank)))
-        return fail("smgpu_quality_coupled_pack: bad coupling description");
-    // the patches, checked: inside the boundary faces, disjoint, one per neighbour, none to this rank
-    std::vector<int32_t> key{c->myRank, c->nPatches};
+        return fail(api + ": bad coupling description");
+    key = {c->myRank, c->nPatches};
     std::vector<std::pair<int, int>> ranges;
     std::vector<int> seen;
-    int64_t nProc = 0, notCounted = 0;
+    nProc = 0; notCounted = 0;
     for (int i = 0; i < c->nPatches; ++i) {
         const int32_t st = c->patchStart[i], sz = c->patchSize[i], o = c->neighbRank[i];
         if (sz < 0 || st < m.nInternalFaces || (int64_t)st + sz > m.nFaces)
-            return fail("smgpu_quality_coupled_pack: processor patch " + std::to_string(i) + " is not a range of boundary faces");
-        if (o < 0 || o == c->myRank) return fail("smgpu_quality_coupled_pack: processor patch " + std::to_string(i) + " has a bad neighbour rank");
+            return fail(api + ": processor patch " + std::to_string(i) + " is not a range of boundary faces");
+        if (o < 0 || o == c->myRank) return fail(api + ": processor patch " + std::to_string(i) + " has a bad neighbour rank");
         if (std::find(seen.begin(), seen.end(), o) != seen.end())
-            return fail("smgpu_quality_coupled_pack: two processor patches to rank " + std::to_string(o) +
+            return fail(api + ": two processor patches to rank " + std::to_string(o) +
                         " (processorCyclic patches or several patches per neighbour are not supported)");
         seen.push_back(o);
         ranges.emplace_back(st, sz);
@@ -321,23 +322,38 @@ int smgpu_quality_coupled_pack(smgpu_handle* h, const smgpu_quality_coupling* c,
     }
     std::sort(ranges.begin(), ranges.end());
     for (size_t i = 1; i < ranges.size(); ++i)
-        if (ranges[i - 1].first + ranges[i - 1].second > ranges[i].first) return fail("smgpu_quality_coupled_pack: processor patches overlap");
+        if (ranges[i - 1].first + ranges[i - 1].second > ranges[i].first) return fail(api + ": processor patches overlap");
+    // face list and slots of this coupling (small: the boundary faces)
+    const int nB = m.nFaces - m.nInternalFaces;
+    procFace.assign((size_t)nProc, 0);
+    slot.assign((size_t)nB, -1);
+    int k = 0;
+    for (int i = 0; i < c->nPatches; ++i) {
+        const int flag = c->myRank > c->neighbRank[i] ? kQualityNotCounted : 0;
+        for (int j = 0; j < c->patchSize[i]; ++j, ++k) {
+            const int f = c->patchStart[i] + j;
+            procFace[(size_t)k] = f;
+            slot[(size_t)(f - m.nInternalFaces)] = k | flag;
+        }
+    }
+    return 0;
+}
+}  // extern "C++"
+
+int smgpu_quality_coupled_pack(smgpu_handle* h, const smgpu_quality_coupling* c, void* sendCc, int64_t* nProcFaces) {
+    if (!h || !c) return fail("null argument");
+    if (h->iterOpen) return fail("smgpu_quality_coupled_pack: not between smgpu_iter_begin and smgpu_iter_end");
+    const MeshView& m = h->mv;
+    std::vector<int32_t> key;
+    std::vector<int> procFace, slot;
+    int64_t nProc = 0, notCounted = 0;
+    if (qualityCouplingTables("smgpu_quality_coupled_pack", m, c, key, procFace, slot, nProc, notCounted)) return 1;
     if (nProc > 0 && !sendCc) return fail("smgpu_quality_coupled_pack: null sendCc");
     HIP_OK(hipSetDevice(h->device));
     if (qualityEnsure(h)) return 1;
     if (key != h->q.coupling) {
-        // face list and slots of this coupling (small: the boundary faces), uploaded once per coupling
+        // uploaded once per coupling
         const int nB = m.nFaces - m.nInternalFaces;
-        std::vector<int> procFace((size_t)nProc), slot((size_t)nB, -1);
-        int k = 0;
-        for (int i = 0; i < c->nPatches; ++i) {
-            const int flag = c->myRank > c->neighbRank[i] ? kQualityNotCounted : 0;
-            for (int j = 0; j < c->patchSize[i]; ++j, ++k) {
-                const int f = c->patchStart[i] + j;
-                procFace[(size_t)k] = f;
-                slot[(size_t)(f - m.nInternalFaces)] = k | flag;
-            }
-        }
         h->q.coupled.release();   // (the three records with it: each comes back with the first call that writes it)
         h->q.coupling.clear();
         HIP_OK(h->q.coupled.alloc(&h->q.procFace, (size_t)std::max<int64_t>(1, nProc)));

@@ -201,5 +201,19 @@ struct QualityConstraintHost {
     double* cellCtr = nullptr;
     Accum* acc = nullptr;
     RecordSlab<smgpu_quality_constraint_record> slab{"quality constraint"};   // one record per iteration of the call
-    void release() { block.release(); slab.release(); }
+    // the coupled form (smgpu_set_quality_constraint_coupled, 10.15) on an engine with a halo: TangleHost's coupled members with
+    // the same meaning (x, k, reverting, count, the slab in chunks, counted, sendT / recvT), and what the face verdicts add.
+    // pending: enabled, the exempt faces not taken yet.  stage: 0 no pass open, 1 behind pass_begin, 2 behind pass_faces.  n0: the
+    // rank's counts at k = 0 (bad cells, tangled cells, non-orthogonal faces, skew faces).  procFace / slot: 10.4's tables of the
+    // coupling given at enabling, the constraint's own copies: a report packed with another coupling releases only the report's.
+    static constexpr int kChunk = 256;
+    bool coupled = false, pending = false, slabFresh = false;
+    int k = -1, stage = 0, reverting = 0, slabUsed = 0, nProc = 0;
+    int64_t count = 0, n0[4] = {0, 0, 0, 0};
+    const double* x = nullptr;
+    uint8_t* counted = nullptr;
+    int *procFace = nullptr, *slot = nullptr;
+    int *sendT = nullptr, *recvT = nullptr;        // the caller's exchange buffers (device, nSend / nRecv int32)
+    double *sendCc = nullptr, *recvCc = nullptr;   // ... (device, 3 doubles per processor face, patch order)
+    void release() { block.release(); slab.release(); coupled = pending = slabFresh = false; k = -1; stage = 0; slabUsed = 0; nProc = 0; }
 };

@@ -1629,6 +1629,7 @@ int smgpu_halo_set_exchange_stream(smgpu_handle* h, int32_t useExchangeStream, v
 
 int smgpu_halo_configure(smgpu_handle* h, const smgpu_halo_desc* d) {
     if (!h || !d) return fail("null argument");
+    if (h->qc.coupled) return fail("smgpu_halo_configure: the coupled quality constraint is on (smgpu_set_quality_constraint_coupled), and its tables are those of this halo; switch it off first");
     if (h->qc.on) return fail("smgpu_halo_configure: the quality constraint is on (smgpu_set_quality_constraint), and it is not available on an engine with a halo; switch it off first");
     if (h->tg.on) return fail("smgpu_halo_configure: the tangle constraint is on (smgpu_set_tangle_constraint), and it is not available on an engine with a halo; switch it off first");
     if (h->qg.armed) return fail("smgpu_halo_configure: the quality guard is armed (smgpu_set_quality_guard), and a guard is not available on an engine with a halo; disarm it first");
@@ -2094,6 +2095,9 @@ int smgpu_iter_begin(smgpu_handle* h) {
     if (!h->prmSet) return fail("smgpu_set_params has not been called");
     if (h->tg.coupled && h->tg.k >= 0)
         return fail("smgpu_iter_begin: the coupled tangle constraint has not finished the passes of the last iteration (smgpu_tangle_pass_begin / _end)");
+    if (h->qc.coupled && (h->qc.k >= 0 || h->qc.pending))
+        return fail(h->qc.pending ? "smgpu_iter_begin: the coupled quality constraint waits for its exempt faces (smgpu_quality_constraint_coupled_exempt)"
+                                  : "smgpu_iter_begin: the coupled quality constraint has not finished the passes of the last iteration (smgpu_quality_constraint_pass_begin / _faces / _end)");
     h->q.epoch++;
     h->iterOpen = true;
     HIP_OK(hipSetDevice(h->device));
@@ -2300,6 +2304,7 @@ int smgpu_iter_end(smgpu_handle* h) {
     else std::swap(h->st.ptsCur, h->st.ptsNext);
     // the coupled tangle constraint: the buffer just swapped out holds x, the points the iteration started from
     if (h->tg.coupled) tangleCoupledIterEnd(h, swapHalo ? h->st.prop : h->st.ptsNext);
+    if (h->qc.coupled) qualityConstraintCoupledIterEnd(h, swapHalo ? h->st.prop : h->st.ptsNext);
     h->haloIter++;
     h->interiorDone = false;
     // (flagged arrangement with a stats history: nobody reads localStats per iteration, and an exchange stream that waited for the
@@ -2462,6 +2467,7 @@ int smgpu_boundary_begin(smgpu_handle* h, const smgpu_boundary_desc* d, double m
         return fail("smgpu_boundary_begin: null geometry array");
     HIP_OK(hipSetDevice(h->device));
     if (h->tg.coupled) return fail("smgpu_boundary_begin: the coupled tangle constraint is on (smgpu_set_tangle_constraint_coupled), and it is not available on an engine with boundary point smoothing; switch it off first");
+    if (h->qc.coupled) return fail("smgpu_boundary_begin: the coupled quality constraint is on (smgpu_set_quality_constraint_coupled), and it is not available on an engine with boundary point smoothing; switch it off first");
     const Topology& t = h->topo;
     h->bndOn = false;
     h->bndPending = false;

@@ -715,8 +715,44 @@ class SmoothEngine:
         self._check(self._lib.smgpu_set_quality_constraint(self._h, C.byref(p), 1))
 
     def clear_quality_constraint(self):
-        """Switch the quality constraint off; discards unread records."""
+        """Switch the quality constraint (either form) off; discards unread records."""
         self._check(self._lib.smgpu_set_quality_constraint(self._h, None, 0))
+
+    def set_quality_constraint_coupled(self, coupling, sendT, recvT, sendCc, recvCc, maxNonOrtho=65.0, maxInternalSkewness=4.0,
+                                       maxBoundarySkewness=20.0, passes=2):
+        """The quality constraint on an engine with a halo (include/smgpu.h, smgpu_set_quality_constraint_coupled; DESIGN.md "Mesh
+        quality", 10.15).  coupling: quality_coupling()'s; sendT / recvT: raw device addresses (ints) of nSend / nRecv int32,
+        sendCc / recvCc: of 3 doubles per processor face, all the caller's.  Returns with sendCc packed at the current points: the
+        caller moves it to the neighbours' recvCc and calls quality_constraint_coupled_exempt.  The passes are the caller's too:
+        quality_constraint_pass_begin / _pass_faces / _pass_end behind every iter_end."""
+        rank, pats = coupling
+        st = np.array([p[0] for p in pats], np.int32)
+        sz = np.array([p[1] for p in pats], np.int32)
+        nb = np.array([p[2] for p in pats], np.int32)
+        c = _ffi.QualityCoupling(int(rank), len(pats), _p(st, _ffi.c_i32p), _p(sz, _ffi.c_i32p), _p(nb, _ffi.c_i32p))
+        p = _ffi.QualityConstraintParams(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes))
+        d = _ffi.QualityConstraintHaloDesc(sendT or None, recvT or None, sendCc or None, recvCc or None, C.pointer(c))
+        self._check(self._lib.smgpu_set_quality_constraint_coupled(self._h, C.byref(p), C.byref(d), 1))
+
+    def quality_constraint_coupled_exempt(self):
+        """the face verdicts of the enabling evaluation, with the neighbours' cell centres in recvCc, become the exempt faces"""
+        self._check(self._lib.smgpu_quality_constraint_coupled_exempt(self._h))
+
+    def quality_constraint_pass_begin(self):
+        """evaluates the geometry of the points and packs the owner cell centres of the processor faces into sendCc"""
+        self._check(self._lib.smgpu_quality_constraint_pass_begin(self._h))
+
+    def quality_constraint_pass_faces(self) -> int:
+        """the face verdicts with recvCc, the cells, the marks, the pack of sendT; this rank's bad cells"""
+        n = C.c_int64(0)
+        self._check(self._lib.smgpu_quality_constraint_pass_faces(self._h, C.byref(n)))
+        return n.value
+
+    def quality_constraint_pass_end(self, nBadGlobal) -> bool:
+        """the pass's revert under the verdict on the all-rank count; True: the iteration's passes are over"""
+        done = C.c_int32(0)
+        self._check(self._lib.smgpu_quality_constraint_pass_end(self._h, int(nBadGlobal), C.byref(done)))
+        return bool(done.value)
 
     def quality_constraint_records(self) -> list:
         """The pending records of the quality constraint, one per iteration that ran, in ascending iteration; clears them."""

@@ -197,6 +197,22 @@ def combine_tangle_records(per_rank):
     return out
 
 
+def combine_quality_constraint_records(per_rank):
+    """the records of the undecomposed mesh from every rank's (DESIGN.md "Mesh quality", 10.15): `passes` and `fullRevert` are
+    global values, the same on every rank; the counts are sums (a shared point counts on its master only, a processor face on
+    the rank with the lower number)"""
+    from .engine import QualityConstraintRecord
+    out = []
+    for recs in zip(*per_rank):
+        r0 = recs[0]
+        assert all((r.iteration, r.passes, r.fullRevert) == (r0.iteration, r0.passes, r0.fullRevert) for r in recs), recs
+        out.append(QualityConstraintRecord(iteration=r0.iteration, passes=r0.passes, fullRevert=r0.fullRevert,
+                                           **{f: sum(getattr(r, f) for r in recs)
+                                              for f in ("nBadCells", "nPointsReverted", "nTangledCells", "nNonOrthoFaces", "nSkewFaces")}))
+    assert all(len(r) == len(per_rank[0]) for r in per_rank)
+    return out
+
+
 def l_view(t, width):
     """the exchange-L records in use: `width` doubles per slot, packed from the start of the (slots, L_DOUBLES) buffer"""
     n = t.shape[0]
@@ -339,6 +355,7 @@ class DistributedSmoother:
                            "L": z((self.probe_slots, L_DOUBLES), torch.float64)}
         self.direct = self._open_direct(engine_factory is None)
         self.tangle_passes = None     # set_tangle_constraint: the passes behind every iter_end
+        self.quality_passes = None    # set_quality_constraint: likewise (the two constraints exclude each other)
         self._tangle_err = None
 
     def _open_push(self):
@@ -601,7 +618,7 @@ class DistributedSmoother:
         """Wait for the engine's stream, read its error word (include/smgpu.h) and let EVERY rank raise when any rank has one: a
         rank raising on its own would leave the others inside the next collective.  The engine clears the word once it has been
         reported, so the handle keeps a sticky `had_error` for later readers (transport_info, bench.py).  err: what this rank has
-        already caught (a pass of the tangle constraint), or what it caught earlier and carried to this point."""
+        already caught (a pass of the tangle or the quality constraint), or what it caught earlier and carried to this point."""
         torch, eng = self.torch, self.engine
         if err is None:
             err, self._tangle_err = self._tangle_err, None
@@ -692,7 +709,7 @@ class DistributedSmoother:
                 eng.iter_mid()
                 self._a2a(st.recvF, st.sendF, eng.iter_ahead)   # SM.C:2374
                 eng.iter_end()
-                self._tangle_passes()
+                self._constraint_passes()
                 self._agree_on_error()                      # (this branch reads the residual on the host every iteration anyway)
                 self._gather_stats()                        # SM.C:1567, 2396
                 hist[i, 0] = self.allStats[:, 0].max()
@@ -708,7 +725,7 @@ class DistributedSmoother:
         local = torch.zeros((n, 2), dtype=torch.float64, device=self.device)
         eng.set_stats_history(local.data_ptr(), n)      # iter_end fills record i: no per-iteration copy
         for i in range(centroidalIters):
-            # (a rank that carries an error of the tangle constraint's last pass leaves its engine alone and answers the
+            # (a rank that carries an error of the last pass of the tangle or the quality constraint leaves its engine alone and answers the
             # collectives until the next pass's reduction, where every rank learns of it)
             live = self._tangle_err is None
             if live:
@@ -719,7 +736,7 @@ class DistributedSmoother:
             self._a2a(st.recvF, st.sendF, eng.iter_ahead if live else None)
             if live:
                 eng.iter_end()
-            self._tangle_passes()
+            self._constraint_passes()
             done += 1
         eng.set_stats_history(None, 0)
         # an error word raised by a kernel of this call (a peer's records that never came, a point without usable neighbours): every
@@ -743,6 +760,8 @@ class DistributedSmoother:
         behind every iter_end, up to `passes` marked passes (the marks of shared points travel like exchange F) and then the
         full revert, under a verdict on the all-rank count (one all_reduce per pass).  Every rank calls it."""
         torch, st = self.torch, self.state
+        if self.quality_passes is not None:
+            raise RuntimeError("set_tangle_constraint: the quality constraint is on, and it contains this one; clear_quality_constraint first")
         st.sendT = torch.zeros(max(self.tables.nSend, 1), dtype=torch.int32, device=self.device)
         st.recvT = torch.zeros(max(self.tables.nRecv, 1), dtype=torch.int32, device=self.device)
         self.tangle_passes = None
@@ -773,38 +792,123 @@ class DistributedSmoother:
             everyone = [mine]
         return everyone if per_rank else combine_tangle_records(everyone)
 
-    def _tangle_passes(self):
-        """the passes of the iteration iter_end has just closed: per pass one host read (the rank's count), one all_reduce of
-        {count, failed} and, while cells are bad and the pass is not the last, exchange T (the host's exchange under every
-        transport: no kernel stores marks into a peer).  A rank on which a call of a pass fails keeps the error, goes on
-        answering the collectives without touching its engine, and reports failed = 1 in the next reduction; every rank then
-        raises through _agree_on_error.  The host knows the verdict itself, so a failed rank leaves the loop when the others do."""
-        if self.tangle_passes is None:
+    def _constraint_passes(self):
+        """the passes of the iteration iter_end has just closed, of whichever constraint is on.  Tangle constraint (10.13): per
+        pass one host read (the rank's count), one all_reduce of {count, failed} and, while cells are bad and the pass is not
+        the last, exchange T (the host's exchange under every transport: no kernel stores marks into a peer).  Quality constraint
+        (10.15): in front of the count the owner cell centres of the processor faces move like the coupled report's slices, so a
+        pass waits for its engine twice.  A rank on which a call of a pass fails keeps the error, goes on answering the
+        collectives without touching its engine, and reports failed = 1 in the next reduction; every rank then raises through
+        _agree_on_error.  The host knows the verdict itself, so a failed rank leaves the loop when the others do."""
+        if self.tangle_passes is not None:
+            name, passes, faces = "tangle", self.tangle_passes, False
+        elif self.quality_passes is not None:
+            name, passes, faces = "quality", self.quality_passes, True
+        else:
             return
         torch, st, eng = self.torch, self.state, self.engine
         dev = "cpu" if (self._staged() or self.device.type == "cpu") else self.device
-        for k in range(self.tangle_passes + 1):
-            nb = 0
+
+        def guarded(call):
             if self._tangle_err is None:
                 try:
-                    nb = eng.tangle_pass_begin()
+                    return call()
                 except Exception as ex:  # noqa: BLE001 -- re-raised below, on every rank
                     self._tangle_err = ex
-            v = torch.tensor([nb, 0 if self._tangle_err is None else 1], dtype=torch.int64, device=dev)
+            return 0
+
+        for k in range(passes + 1):
+            if faces:
+                guarded(eng.quality_constraint_pass_begin)
+                self._move_cc()
+                nb = guarded(eng.quality_constraint_pass_faces)
+            else:
+                nb = guarded(eng.tangle_pass_begin)
+            v = torch.tensor([nb or 0, 0 if self._tangle_err is None else 1], dtype=torch.int64, device=dev)
             if self.world > 1:
                 self.dist.all_reduce(v)
             total, failed = (int(x) for x in v.tolist())
             if failed:
                 err, self._tangle_err = self._tangle_err, None
-                self._agree_on_error(err if err is not None else RuntimeError("another rank failed inside a pass of the tangle constraint (see its message)"))
-            if total > 0 and k < self.tangle_passes:
+                self._agree_on_error(err if err is not None else RuntimeError(f"another rank failed inside a pass of the {name} constraint (see its message)"))
+            if total > 0 and k < passes:
                 self._a2a(st.recvT, st.sendT, host=True)
             try:
-                eng.tangle_pass_end(total)
+                (eng.quality_constraint_pass_end if faces else eng.tangle_pass_end)(total)
             except Exception as ex:  # noqa: BLE001 -- carried to the next reduction or agreement point
                 self._tangle_err = ex
-            if total == 0 or k == self.tangle_passes:
+            if total == 0 or k == passes:
                 return
+
+    # -- the quality constraint on the decomposed mesh (include/smgpu.h smgpu_set_quality_constraint_coupled, DESIGN.md 10.15) --
+    def _move_cc(self):
+        """sendCc -> the neighbours' recvCc: the paired-patch exchange of the coupled report (a collective: every rank takes part,
+        with or without processor patches)"""
+        st = self.state
+        if self.world > 1:
+            st.recvCc.copy_(self._quality_swap(st.qcCoupling[1], st.sendCc, 3))
+
+    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2):
+        """From now on iterate() also keeps face non-orthogonality and skewness under the limits (engine.set_quality_constraint's
+        parameters), on the global mesh: a processor face is judged as the internal face it is, with the neighbour rank's cell
+        centre, which travels once per pass like the coupled report's; marks and verdict as set_tangle_constraint.  Every rank
+        calls it (a collective: the exempt faces need one exchange)."""
+        torch, st, eng = self.torch, self.state, self.engine
+        if self.tangle_passes is not None:
+            raise RuntimeError("set_quality_constraint: the tangle constraint is on, and this constraint contains it; clear_tangle_constraint first")
+        coupling = eng.quality_coupling(self.rank)
+        if self.world <= 1 and coupling[1]:
+            raise RuntimeError("mesh quality: a single rank with processor patches")
+        n = sum(p[1] for p in coupling[1])
+        st.qcCoupling = coupling
+        st.sendT = torch.zeros(max(self.tables.nSend, 1), dtype=torch.int32, device=self.device)
+        st.recvT = torch.zeros(max(self.tables.nRecv, 1), dtype=torch.int32, device=self.device)
+        st.sendCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
+        st.recvCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
+        self.quality_passes = None
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)         # the buffers are zeroed before the engine's stream writes them
+        err = None
+        try:
+            eng.set_quality_constraint_coupled(coupling, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
+                                               maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes)
+        except Exception as ex:  # noqa: BLE001 -- re-raised below, on every rank
+            err = ex
+        self._agree_on_error(err)
+        self._move_cc()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        try:
+            eng.quality_constraint_coupled_exempt()
+        except Exception as ex:  # noqa: BLE001
+            err = ex
+        self._agree_on_error(err)
+        self.quality_passes = int(passes)
+
+    def clear_quality_constraint(self):
+        self.quality_passes = None
+        self.engine.clear_quality_constraint()
+
+    def quality_constraint_state(self):
+        """QualityConstraintState of the decomposed mesh: nExemptCells and nExemptFaces summed over the ranks (a processor face
+        counts on one side).  A collective."""
+        s = self.engine.quality_constraint_state()
+        t = self.torch.tensor([s.nExemptCells, s.nExemptFaces], dtype=self.torch.int64, device="cpu" if self._staged() else self.device)
+        if self.world > 1:
+            self.dist.all_reduce(t)
+        s.nExemptCells, s.nExemptFaces = (int(x) for x in t.tolist())
+        return s
+
+    def quality_constraint_records(self, per_rank=False):
+        """The pending records, cleared by the read: those of the undecomposed mesh (combine_quality_constraint_records), or with
+        per_rank one list per rank.  A collective: every rank calls it and gets the same answer."""
+        mine = self.engine.quality_constraint_records()
+        everyone = [None] * self.world
+        if self.world > 1:
+            self.dist.all_gather_object(everyone, mine)
+        else:
+            everyone = [mine]
+        return everyone if per_rank else combine_quality_constraint_records(everyone)
 
     def _quality_exchange(self, volumes=False):
         """pack, then every processor patch's owner cell centres to the neighbour and theirs back (one all_to_all_single, staged
@@ -936,6 +1040,7 @@ class LocalMultiSmoother:
         self.subs = subs
         self.own_fold = own_fold_default()
         self.tangle_passes = None     # set_tangle_constraint: the passes behind every iter_end
+        self.quality_passes = None    # set_quality_constraint: likewise (the two constraints exclude each other)
         if torch_device is None:
             torch_device = torch.device("cuda", device)
         self.device = torch_device
@@ -1028,7 +1133,7 @@ class LocalMultiSmoother:
             self._exchange("F")
             for st in self.states:
                 st.eng.iter_end()
-            self._tangle_passes()
+            self._constraint_passes()
             allst = self.torch.stack([st.localStats for st in self.states]).cpu().numpy()
             res.append(float(allst[:, 0].max()))
             frz.append(int(allst[:, 1].sum()))
@@ -1043,6 +1148,8 @@ class LocalMultiSmoother:
     def set_tangle_constraint(self, passes=2):
         """as DistributedSmoother.set_tangle_constraint; the marks of shared points move by the device-side copies of the exchanges"""
         torch = self.torch
+        if self.quality_passes is not None:
+            raise RuntimeError("set_tangle_constraint: the quality constraint is on, and it contains this one; clear_quality_constraint first")
         self.tangle_passes = None
         for st in self.states:
             st.sendT = torch.zeros(max(st.t.nSend, 1), dtype=torch.int32, device=self.device)
@@ -1066,16 +1173,80 @@ class LocalMultiSmoother:
         everyone = [st.eng.tangle_records() for st in self.states]
         return everyone if per_rank else combine_tangle_records(everyone)
 
-    def _tangle_passes(self):
-        """the passes of the iteration iter_end has just closed on every engine: the verdict on the summed count"""
-        if self.tangle_passes is None:
+    def _constraint_passes(self):
+        """the passes of the iteration iter_end has just closed on every engine, of whichever constraint is on: the verdict on the
+        summed count; under the quality constraint the cell centres of the processor faces move in front of the count"""
+        faces = self.quality_passes is not None
+        passes = self.quality_passes if faces else self.tangle_passes
+        if passes is None:
             return
-        for k in range(self.tangle_passes + 1):
-            total = sum([st.eng.tangle_pass_begin() for st in self.states])
-            if total > 0 and k < self.tangle_passes:
+        for k in range(passes + 1):
+            if faces:
+                for st in self.states:
+                    st.eng.quality_constraint_pass_begin()
+                self._move_cc()
+                total = sum([st.eng.quality_constraint_pass_faces() for st in self.states])
+            else:
+                total = sum([st.eng.tangle_pass_begin() for st in self.states])
+            if total > 0 and k < passes:
                 self._exchange("T")
-            if all([st.eng.tangle_pass_end(total) for st in self.states]):
+            if all([(st.eng.quality_constraint_pass_end if faces else st.eng.tangle_pass_end)(total) for st in self.states]):
                 return
+
+    # -- the quality constraint on the decomposed mesh (include/smgpu.h smgpu_set_quality_constraint_coupled, DESIGN.md 10.15) --
+    def _move_cc(self):
+        """every engine's sendCc -> its neighbours' recvCc by device-side copies, as the coupled report's local_exchange; the
+        buffers are the constraint's own, not the report's"""
+        for i, off, j, ooff, size in self.ccCopies:
+            self.states[i].recvCc[off:off + size].copy_(self.states[j].sendCc[ooff:ooff + size])
+
+    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2):
+        """as DistributedSmoother.set_quality_constraint; cell centres and marks move by device-side copies"""
+        from .quality import paired_offsets
+        torch = self.torch
+        if self.tangle_passes is not None:
+            raise RuntimeError("set_quality_constraint: the tangle constraint is on, and this constraint contains it; clear_tangle_constraint first")
+        self.quality_passes = None
+        couplings = [st.eng.quality_coupling(r) for r, st in enumerate(self.states)]
+        self.ccCopies = paired_offsets(couplings)
+        for st, c in zip(self.states, couplings):
+            n = sum(p[1] for p in c[1])
+            st.sendT = torch.zeros(max(st.t.nSend, 1), dtype=torch.int32, device=self.device)
+            st.recvT = torch.zeros(max(st.t.nRecv, 1), dtype=torch.int32, device=self.device)
+            st.sendCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
+            st.recvCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)         # the buffers are zeroed before the engines' streams write them
+        try:
+            for st, c in zip(self.states, couplings):
+                st.eng.set_quality_constraint_coupled(c, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
+                                                      maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes)
+            self._move_cc()
+            if self.device.type == "cuda":
+                torch.cuda.synchronize(self.device)
+            for st in self.states:
+                st.eng.quality_constraint_coupled_exempt()
+        except Exception:
+            self.clear_quality_constraint()
+            raise
+        self.quality_passes = int(passes)
+
+    def clear_quality_constraint(self):
+        self.quality_passes = None
+        for st in self.states:
+            st.eng.clear_quality_constraint()
+
+    def quality_constraint_state(self):
+        """QualityConstraintState of the decomposed mesh: nExemptCells and nExemptFaces summed over the ranks"""
+        ss = [st.eng.quality_constraint_state() for st in self.states]
+        ss[0].nExemptCells = sum(s.nExemptCells for s in ss)
+        ss[0].nExemptFaces = sum(s.nExemptFaces for s in ss)
+        return ss[0]
+
+    def quality_constraint_records(self, per_rank=False):
+        """The pending records, cleared by the read: those of the undecomposed mesh, or with per_rank one list per rank"""
+        everyone = [st.eng.quality_constraint_records() for st in self.states]
+        return everyone if per_rank else combine_quality_constraint_records(everyone)
 
     # The reports of the decomposed mesh at the current points (smoothmesh_amd/quality.py, DESIGN.md 10.4, 10.5, 10.8, 10.9): the cell
     # centres (and volumes) of the processor faces move between the engines' buffers by device-side copies.  Ids are global where
