@@ -418,6 +418,75 @@ int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint
 int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n);
 int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint_state* out);
 
+/* ---- the quality constraint: the tet, twist, weight, ratio and determinant limits (DESIGN.md "Mesh quality", 10.16) ---------
+ * Six more criteria of meshQualityDict for the constraint above, for an engine without a halo.  All are off unless asked for; they
+ * are judged behind every iteration by the reports' own measures and act through 10.14's loop, unchanged.  Notation and everything
+ * not said here is 10.14's.
+ *
+ * VALUES, at the points being judged, with the operands and the operation order of the report kernels, so the bits of the report
+ * fields: tet_f = faceTetQuality (10.7: the face-centre tets of both sides); tw_f = faceTwist and tri_f = faceTriangleTwist (faces
+ * with more than 3 vertices only: a triangle is never bad by them); w_f = faceWeight and r_f = faceVolumeRatio (10.6, internal
+ * faces only); det_c = cellDeterminant (10.6); V_c, which r_f needs, has the bits of the report's cell volumes.
+ *
+ * LIMITS.  A face is also BAD when
+ *   tet_f < minTetQuality                        (any face;        off when minTetQuality    <= -1e30)
+ *   tw_f  < minTwist                             (> 3 vertices;    off when minTwist         <= -1)
+ *   tri_f < minTriangleTwist                     (> 3 vertices;    off when minTriangleTwist <= -1)
+ *   it is internal and w_f < minFaceWeight       (                 off when minFaceWeight    <= 0)
+ *   it is internal and r_f < minVolRatio         (                 off when minVolRatio      <= 0)
+ * and a cell is also BAD when it is the owner or the neighbour of a face bad by one of these and not exempt, or when
+ *   det_c < minDeterminant and the cell is not determinant-exempt      (off when minDeterminant <= 0).
+ * The comparisons are the reports' own, strict.  A NaN limit is refused.  The defaults are all off.
+ *
+ * EXEMPTION.  Enabling evaluates the current points once.  A face bad there by any criterion that is on, of 10.14 or of this
+ * section, is exempt: one byte per face, as in 10.14.  A cell under-determined there is exempt from the determinant criterion
+ * only, in a byte of its own: it is no exempt cell in 10.12's sense and can still be bad through its volume, its pyramids or a
+ * face.
+ *
+ * INVARIANT.  10.14's carries over: reverting every point of a bad face's owner and neighbour restores that face's points, C_f,
+ * S_f, C_O, C_N, V_O and V_N to their bits at x, and with them all five face values; reverting every point of a cell restores the
+ * S_f of its faces, and with them det_c.  So if no non-exempt face or cell is bad at x, none is bad at the accepted x'.
+ * EQUIVALENCE.  With all six off the accepted points, the records and the state are bit for bit those of
+ * smgpu_set_quality_constraint with the same three limits, and the engine queues exactly its launches: no further kernel.
+ *
+ * smgpu_quality_constraint_limits: smgpu_quality_constraint_params' four fields at their offsets, then the six limits.  NULL:
+ * {65, 4, 20, 2} and six off values.  smgpu_set_quality_constraint_limits has the refusals of smgpu_set_quality_constraint, and
+ * the two entries and the tangle constraint exclude each other as the one entry and the tangle constraint do; on == 0 is
+ * smgpu_set_quality_constraint's.
+ * smgpu_quality_constraint_record_full: the record above (56 bytes), then, at k = 0, the bad faces that are not exempt by tet
+ * quality, twist, triangle twist, weight and volume ratio (a face that fails several counts in each) and the under-determined
+ * cells that are not determinant-exempt.  Both getters drain the same pending records; the narrow one returns each record's
+ * first 56 bytes.  smgpu_quality_constraint_state_full: the state above, then the six limits and the determinant-exempt cells.
+ * Under smgpu_set_quality_constraint (and the coupled form) the new counts are 0 and the limits the off values.
+ *
+ * Not covered: the base-point tets (their walk is O(nv^2) per face and stays with the report), maxConcave and minFlatness (the
+ * concavity value depends on its own threshold), minVol and minArea, reading system/meshQualityDict, and the coupled form:
+ * smgpu_set_quality_constraint_coupled takes the three limits of 10.14 only.
+ * Memory, beyond 10.14's: 104 bytes per iteration of the longest call in place of 56; with minVolRatio or minDeterminant on,
+ * 8 nCells bytes of volumes and nCells bytes of determinant exemptions. */
+typedef struct smgpu_quality_constraint_limits {
+    double maxNonOrtho, maxInternalSkewness, maxBoundarySkewness;
+    int32_t passes;
+    double minTetQuality, minTwist, minTriangleTwist, minFaceWeight, minVolRatio, minDeterminant;
+} smgpu_quality_constraint_limits;            /* NULL limits = {65, 4, 20, 2, -1e30, -1, -1, 0, 0, 0} */
+typedef struct smgpu_quality_constraint_record_full {
+    int64_t iteration;
+    int32_t passes, fullRevert;
+    int64_t nBadCells, nPointsReverted;
+    int64_t nTangledCells, nNonOrthoFaces, nSkewFaces;
+    int64_t nLowTetFaces, nLowTwistFaces, nLowTriangleTwistFaces, nLowWeightFaces, nLowVolRatioFaces, nUnderdeterminedCells;
+} smgpu_quality_constraint_record_full;
+typedef struct smgpu_quality_constraint_state_full {
+    int32_t on, passes;
+    double maxNonOrtho, maxInternalSkewness, maxBoundarySkewness;
+    int64_t nExemptCells, nExemptFaces, iteration;
+    double minTetQuality, minTwist, minTriangleTwist, minFaceWeight, minVolRatio, minDeterminant;
+    int64_t nExemptDeterminantCells;
+} smgpu_quality_constraint_state_full;
+int smgpu_set_quality_constraint_limits(smgpu_handle* h, const smgpu_quality_constraint_limits* p, int32_t on);
+int smgpu_get_quality_constraint_records_full(smgpu_handle* h, smgpu_quality_constraint_record_full* out, int64_t cap, int64_t* n);
+int smgpu_get_quality_constraint_state_full(smgpu_handle* h, smgpu_quality_constraint_state_full* out);
+
 /* ---- the quality constraint on a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.15) -------------------------
  * The contract above (10.14), read on the GLOBAL mesh, for an engine whose halo is configured.  Unlike the tangle verdict of
  * 10.13 a face limit is not local to a rank: a PROCESSOR FACE is an internal face of the global mesh.  It takes the internal-face

@@ -160,6 +160,25 @@ class QualityConstraintState(C.Structure):
                 ("maxBoundarySkewness", C.c_double), ("nExemptCells", C.c_int64), ("nExemptFaces", C.c_int64), ("iteration", C.c_int64)]
 
 
+_QC_LIMITS = ("minTetQuality", "minTwist", "minTriangleTwist", "minFaceWeight", "minVolRatio", "minDeterminant")
+
+
+class QualityConstraintLimits(C.Structure):
+    """smgpu_quality_constraint_limits: QualityConstraintParams' fields, then the six limits of DESIGN.md 10.16"""
+    _fields_ = QualityConstraintParams._fields_ + [(n, C.c_double) for n in _QC_LIMITS]
+
+
+class QualityConstraintRecordFull(C.Structure):
+    """smgpu_quality_constraint_record_full: QualityConstraintRecord's fields, then the six counts of DESIGN.md 10.16"""
+    _fields_ = QualityConstraintRecord._fields_ + [(n, C.c_int64) for n in ("nLowTetFaces", "nLowTwistFaces", "nLowTriangleTwistFaces", "nLowWeightFaces",
+                                                                             "nLowVolRatioFaces", "nUnderdeterminedCells")]
+
+
+class QualityConstraintStateFull(C.Structure):
+    """smgpu_quality_constraint_state_full"""
+    _fields_ = QualityConstraintState._fields_ + [(n, C.c_double) for n in _QC_LIMITS] + [("nExemptDeterminantCells", C.c_int64)]
+
+
 class TangleHaloDesc(C.Structure):
     """smgpu_tangle_halo_desc"""
     _fields_ = [("sendT", C.c_void_p), ("recvT", C.c_void_p)]
@@ -292,6 +311,9 @@ SYMBOLS = {
     "smgpu_set_quality_constraint": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintParams), C.c_int32]),
     "smgpu_get_quality_constraint_records": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintRecord), C.c_int64, C.POINTER(C.c_int64)]),
     "smgpu_get_quality_constraint_state": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintState)]),
+    "smgpu_set_quality_constraint_limits": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintLimits), C.c_int32]),
+    "smgpu_get_quality_constraint_records_full": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintRecordFull), C.c_int64, C.POINTER(C.c_int64)]),
+    "smgpu_get_quality_constraint_state_full": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintStateFull)]),
     "smgpu_set_quality_constraint_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintParams), C.POINTER(QualityConstraintHaloDesc), C.c_int32]),
     "smgpu_quality_constraint_coupled_exempt": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_begin": (C.c_int, [C.c_void_p]),

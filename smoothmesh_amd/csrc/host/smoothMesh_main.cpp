@@ -97,7 +97,8 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "maxLayers", "layerPatches", "smoothingPatches", "internalSmoothingBlendingFraction",
                                "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets", "allGeometry",
                                "meshQuality", "qualityInterval", "qualityGuard", "qualityGuardRefine", "tangleConstraint", "tanglePasses",
-                               "qualityConstraint", "maxNonOrtho", "maxInternalSkewness", "maxBoundarySkewness", "qualityConstraintPasses"};
+                               "qualityConstraint", "maxNonOrtho", "maxInternalSkewness", "maxBoundarySkewness", "qualityConstraintPasses",
+                               "minTetQuality", "minTwist", "minTriangleTwist", "minFaceWeight", "minVolRatio", "minDeterminant"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -128,6 +129,9 @@ Options parseArgs(int argc, char** argv) {
                       "       [-maxNonOrtho deg -maxInternalSkewness x -maxBoundarySkewness x]  (with -qualityConstraint: the limits, defaults 65, 4, 20;\n"
                       "        maxNonOrtho >= 180 or a skewness limit <= 0 switches that criterion off)\n"
                       "       [-qualityConstraintPasses n]  (with -qualityConstraint: marked passes per iteration before the whole iteration is reverted, default 2)\n"
+                      "       [-minTetQuality x -minTwist x -minTriangleTwist x -minFaceWeight x -minVolRatio x -minDeterminant x]  (with -qualityConstraint:\n"
+                      "        further limits of meshQualityDict, by the measures of -meshQuality and -allGeometry; each is off unless given, and off at\n"
+                      "        minTetQuality <= -1e30, a twist limit <= -1, minFaceWeight, minVolRatio or minDeterminant <= 0)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -562,6 +566,18 @@ int main(int argc, char** argv) {
     const long qcPasses = opt.getL("qualityConstraintPasses", 2);
     for (const char* k : {"maxNonOrtho", "maxInternalSkewness", "maxBoundarySkewness", "qualityConstraintPasses"})
         if (opt.found(k) && !qualityConstraint) fatal(std::string("-") + k + " needs -qualityConstraint true");
+    // the limits of DESIGN.md 10.16, each off unless given
+    const char* const qcMoreNames[6] = {"minTetQuality", "minTwist", "minTriangleTwist", "minFaceWeight", "minVolRatio", "minDeterminant"};
+    const double qcMoreOff[6] = {-1e30, -1.0, -1.0, 0.0, 0.0, 0.0};
+    double qcMore[6];
+    bool qcMoreGiven = false;
+    for (int k = 0; k < 6; ++k) {
+        qcMore[k] = opt.getD(qcMoreNames[k], qcMoreOff[k]);
+        if (!opt.found(qcMoreNames[k])) continue;
+        if (!qualityConstraint) fatal(std::string("-") + qcMoreNames[k] + " needs -qualityConstraint true");
+        if (qcMore[k] != qcMore[k]) fatal(std::string("-") + qcMoreNames[k] + " must be a number");
+        qcMoreGiven = true;
+    }
     if (qualityConstraint && opt.parallel)
         fatal("-qualityConstraint is not available with -parallel: it judges the faces and cells by the measure of the quality report, which is serial only");
     if (qualityConstraint && tangleConstraint) fatal("-qualityConstraint is not available with -tangleConstraint true: it contains the tangle constraint");
@@ -1293,14 +1309,27 @@ int main(int argc, char** argv) {
         OUT("Tangle constraint: %lld exempt cells, %d passes\n", (long long)ts.nExemptCells, (int)ts.passes);
     }
     // -qualityConstraint: the same with limits on non-orthogonality and skewness (smgpu_set_quality_constraint)
-    std::vector<smgpu_quality_constraint_record> qcRecords;
+    // with one of -minTetQuality ... -minDeterminant: the entry, the records and the lines of 10.16; without, those of 10.14 as they were
+    std::vector<smgpu_quality_constraint_record_full> qcRecords;
     if (qualityConstraint) {
         const smgpu_quality_constraint_params qp{qcMaxNonOrtho, qcMaxInternalSkewness, qcMaxBoundarySkewness, (int32_t)qcPasses};
-        check(smgpu_set_quality_constraint(R[0].h, &qp, 1), "smgpu_set_quality_constraint");
+        const smgpu_quality_constraint_limits ql{qcMaxNonOrtho, qcMaxInternalSkewness, qcMaxBoundarySkewness, (int32_t)qcPasses,
+                                                 qcMore[0], qcMore[1], qcMore[2], qcMore[3], qcMore[4], qcMore[5]};
+        if (qcMoreGiven) check(smgpu_set_quality_constraint_limits(R[0].h, &ql, 1), "smgpu_set_quality_constraint_limits");
+        else check(smgpu_set_quality_constraint(R[0].h, &qp, 1), "smgpu_set_quality_constraint");
         smgpu_quality_constraint_state qs{};
         check(smgpu_get_quality_constraint_state(R[0].h, &qs), "smgpu_get_quality_constraint_state");
         OUT("Quality constraint: maxNonOrtho %g maxInternalSkewness %g maxBoundarySkewness %g, %lld exempt cells, %lld exempt faces, %d passes\n", qs.maxNonOrtho,
             qs.maxInternalSkewness, qs.maxBoundarySkewness, (long long)qs.nExemptCells, (long long)qs.nExemptFaces, (int)qs.passes);
+        if (qcMoreGiven) {
+            smgpu_quality_constraint_state_full qf{};
+            check(smgpu_get_quality_constraint_state_full(R[0].h, &qf), "smgpu_get_quality_constraint_state_full");
+            const double now[6] = {qf.minTetQuality, qf.minTwist, qf.minTriangleTwist, qf.minFaceWeight, qf.minVolRatio, qf.minDeterminant};
+            OUT("Quality constraint limits:");
+            for (int k = 0; k < 6; ++k)
+                if (now[k] > qcMoreOff[k]) OUT(" %s %g", qcMoreNames[k], now[k]);
+            OUT(", %lld determinant-exempt cells\n", (long long)qf.nExemptDeterminantCells);
+        }
     }
     // -qualityGuard: the guard on that history (include/smgpu.h, smgpu_set_quality_guard), armed on the initial
     // points with everything set up: the engine stops the loop on the device and rolls the points back itself
@@ -1391,9 +1420,9 @@ int main(int argc, char** argv) {
         size_t nextQc = 0;
         if (qualityConstraint) {
             int64_t nRecords = 0;
-            check(smgpu_get_quality_constraint_records(R[0].h, nullptr, 0, &nRecords), "smgpu_get_quality_constraint_records");
+            check(smgpu_get_quality_constraint_records_full(R[0].h, nullptr, 0, &nRecords), "smgpu_get_quality_constraint_records_full");
             qcRecords.resize((size_t)nRecords);
-            if (nRecords > 0) check(smgpu_get_quality_constraint_records(R[0].h, qcRecords.data(), nRecords, &nRecords), "smgpu_get_quality_constraint_records");
+            if (nRecords > 0) check(smgpu_get_quality_constraint_records_full(R[0].h, qcRecords.data(), nRecords, &nRecords), "smgpu_get_quality_constraint_records_full");
         }
         for (int32_t k = 0; k < done; ++k) {
             OUT("Smoothing iteration=%ld nFrozenPoints=%d residual=%g\n", i + k + 1, stats[(size_t)k].nFrozenPoints, stats[(size_t)k].residual);
@@ -1404,8 +1433,14 @@ int main(int argc, char** argv) {
                         (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
             }
             if (nextQc < qcRecords.size() && qcRecords[nextQc].iteration == (int64_t)(i + k + 1)) {
-                const smgpu_quality_constraint_record& t = qcRecords[nextQc++];
-                if (t.nBadCells > 0)
+                const smgpu_quality_constraint_record_full& t = qcRecords[nextQc++];
+                if (t.nBadCells > 0 && qcMoreGiven)
+                    OUT("    quality constraint iteration=%lld badCells %lld tangled %lld nonOrthoFaces %lld skewFaces %lld lowTetFaces %lld twistedFaces %lld "
+                        "lowTriangleTwistFaces %lld lowWeightFaces %lld lowVolRatioFaces %lld underdeterminedCells %lld passes %d pointsReverted %lld%s\n",
+                        (long long)t.iteration, (long long)t.nBadCells, (long long)t.nTangledCells, (long long)t.nNonOrthoFaces, (long long)t.nSkewFaces,
+                        (long long)t.nLowTetFaces, (long long)t.nLowTwistFaces, (long long)t.nLowTriangleTwistFaces, (long long)t.nLowWeightFaces,
+                        (long long)t.nLowVolRatioFaces, (long long)t.nUnderdeterminedCells, (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
+                else if (t.nBadCells > 0)
                     OUT("    quality constraint iteration=%lld badCells %lld tangled %lld nonOrthoFaces %lld skewFaces %lld passes %d pointsReverted %lld%s\n",
                         (long long)t.iteration, (long long)t.nBadCells, (long long)t.nTangledCells, (long long)t.nNonOrthoFaces, (long long)t.nSkewFaces,
                         (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");

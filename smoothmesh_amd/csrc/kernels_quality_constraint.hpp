@@ -18,6 +18,8 @@
 // word (set while the iteration did not run or a pass was clean), and k_qc_cells forms 10.12's verdict itself with k_tangle_cells'
 // arithmetic: identical points and records.
 // No float atomics; every store is a plain vector store; every kernel takes the trace's gate (qTraceRan) and the clean word.
+// With a limit of 10.16 on (smgpu_set_quality_constraint_limits) kernels_quality_limits.hpp puts a cell pass in front of step 2
+// and its own kernels in the place of steps 2 and 4; with none on the sequence is the one above.
 #pragma once
 #include <cstddef>
 
@@ -32,6 +34,9 @@ struct QcDev {
     int nonOrthoNow;   // bad faces, not exempt, by the non-orthogonality limit
     int skewNow;       // ... by a skewness limit
     int facesNow;      // bad faces by any limit (enabling: the exempt faces)
+    // 10.16 (kernels_quality_limits.hpp): bad faces, not exempt, by tet quality, twist, triangle twist, weight, volume ratio; cells
+    // under the determinant limit, not determinant-exempt (enabling: the determinant-exempt cells).  0 while none of them is on
+    int lowTetNow, lowTwistNow, lowTriNow, lowWeightNow, lowRatioNow, underDetNow;
 };
 static_assert(offsetof(QcDev, t) == 0, "k_tangle_apply takes a QcDev as its TangleDev");
 static_assert(offsetof(smgpu_quality_constraint_record, iteration) == offsetof(smgpu_tangle_record, iteration) &&

@@ -1,0 +1,220 @@
+// kernels_quality_limits.hpp -- the quality constraint's tet, twist, weight, ratio and determinant limits
+// (smgpu_set_quality_constraint_limits: include/smgpu.h, DESIGN.md "Mesh quality", 10.16): six more criteria for the loop of
+// kernels_quality_constraint.hpp, judged by the reports' own measures (kernels_quality_motion.hpp, kernels_quality_geom.hpp).
+//
+// Per evaluation, between step 1 (k_qc_tile, or the direct geometry kernels) and k_qc_cells of that file's sequence:
+//   a. k_qc_cells_more, queued only when minVolRatio or minDeterminant is on: one lane per cell on the fCtr / fArea step 1
+//      published: V_c into a buffer of the constraint's own (qgCellOne's lines, the bits of k_quality_cell_volumes), det_c against
+//      the limit and the determinant-exempt byte; a bad cell gets the byte in cellFlag that k_qc_cells reads as "bad through
+//      something other than 10.12" and clears; one integer atomic per workgroup;
+//   b. k_qc_faces_more in the place of k_qc_faces whenever a new face criterion is on: one lane per face in polyMesh order; ortho_f
+//      and skew_f by qcFace's lines, the new values from the same loads of C_f, S_f, C_O, C_N; with Walk the skewness loop and
+//      qmFaceOne's first walk are one loop that reads every vertex once (the base-point walk is not in it); with Ratio the two
+//      volumes are read.  A criterion that is off costs no loads: which walk and which loads run is a template parameter, which
+//      verdicts count an argument uniform over the launch;
+//   c. k_qc_verdict_more: k_qc_verdict's twin with the wider record and the wider device words.
+// k_qc_cells and k_tangle_apply run as they are.  No float atomics; every store is a plain vector store; every kernel takes the
+// trace's gate (qTraceRan) and the clean word.
+#pragma once
+#include "kernels_quality_constraint.hpp"
+#include "kernels_quality_geom.hpp"
+#include "kernels_quality_motion.hpp"
+
+namespace smgpu {
+
+static_assert(offsetof(smgpu_quality_constraint_record_full, nSkewFaces) == offsetof(smgpu_quality_constraint_record, nSkewFaces) &&
+              offsetof(smgpu_quality_constraint_record_full, nLowTetFaces) == sizeof(smgpu_quality_constraint_record),
+              "the narrow record is the head of the full one: k_qc_verdict, k_qc_close and k_tangle_apply write through it");
+
+// the limits as the kernels test them; k: the tets' normalisation, formed by the host as the motion report forms it
+struct QcMore { double minTet, minTwist, minTri, minWeight, minRatio, minDet, k; int tetOn, twistOn, triOn, weightOn, ratioOn, detOn; };
+
+// V_c into vol and det_c of cell c: qgCellOne's lines (kernels_quality_geom.hpp), nothing else of it -- keep them alike.
+// exemptOut != NULL (enabling): the determinant verdict goes to exemptOut[c], no cell is flagged, underDetNow counts them.
+template <bool Det>
+__global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea, QcMore lim,
+                                                             double* __restrict__ vol, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
+                                                             uint8_t* __restrict__ cellFlag, QcDev* __restrict__ d, int pass, const smgpu_iter_stats* gate) {
+    if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
+    const int c = blockIdx.x * kQcBlock + threadIdx.x;
+    bool bad = false;
+    if (c < m.nCells) {
+        const int b = m.cfOff[c], e = m.cfOff[c + 1];
+        V3 cEst = v3(0, 0, 0);
+        for (int j = b; j < e; ++j) cEst = cEst + ldv(fCtr, m.cfVal[j] & 0x7fffffff);
+        cEst = cEst / (double)(e - b);
+        double pyr = 0.0, sumA = 0.0;
+        int nInt = 0;
+        for (int j = b; j < e; ++j) {
+            const int ev = m.cfVal[j];
+            const int f = ev & 0x7fffffff;
+            const V3 Sf = ldv(fArea, f);
+            double p = dot(Sf, ldv(fCtr, f) - cEst);
+            if (ev < 0) p = -p;
+            pyr += p;
+            if (Det && f < m.nInternalFaces) { sumA += mag(Sf); ++nInt; }
+        }
+        vol[c] = (1.0 / 3.0) * pyr;
+        if constexpr (Det) {
+            double det = 0.0;
+            const double avgA = nInt > 0 ? sumA / (double)nInt : 0.0;
+            if (nInt > 0 && avgA >= SMGPU_ROOTVSMALL) {
+                double xx = 0.0, xy = 0.0, xz = 0.0, yy = 0.0, yz = 0.0, zz = 0.0;
+                for (int j = b; j < e; ++j) {
+                    const int f = m.cfVal[j] & 0x7fffffff;
+                    if (f >= m.nInternalFaces) continue;
+                    const V3 s = ldv(fArea, f) / avgA;
+                    xx += s.x * s.x; xy += s.x * s.y; xz += s.x * s.z;
+                    yy += s.y * s.y; yz += s.y * s.z; zz += s.z * s.z;
+                }
+                det = fabs((xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz)) + xz * (xy * yz - yy * xz)) / 8.0;
+            }
+            bad = det < lim.minDet;
+            if (exemptOut) exemptOut[c] = bad ? 1 : 0;
+            else {
+                bad = bad && !exempt[c];
+                if (bad) cellFlag[c] = 1;
+            }
+        }
+    }
+    if constexpr (Det) {
+        const int nBad = __syncthreads_count(bad ? 1 : 0);
+        if (nBad > 0 && threadIdx.x == 0) atomicAdd(&d->underDetNow, nBad);
+    }
+}
+
+// k_qc_faces with the new face criteria.  The lines up to fd are qcFace's, the walk is qmFaceOne's first walk with the skewness
+// loop's line in it (both read the vertices in the face's order; fmax and fmin do not depend on it), weight and ratio are
+// qgFaceOne's lines: keep each alike.  exemptOut != NULL (enabling): as k_qc_faces.
+template <bool Walk, bool Ratio>
+__global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
+                                                             const double* __restrict__ fArea, const double* __restrict__ cellCtr,
+                                                             const double* __restrict__ vol, const int* __restrict__ own, const int* __restrict__ nei,
+                                                             QcLimits lim, QcMore more, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
+                                                             uint8_t* __restrict__ cellFlag, QcDev* __restrict__ d, int pass, const smgpu_iter_stats* gate) {
+    if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
+    const int f = blockIdx.x * kQcBlock + threadIdx.x;
+    bool badNO = false, badSk = false, badTet = false, badTw = false, badTri = false, badW = false, badR = false;
+    if (f < m.nFaces) {
+        const bool internal = f < m.nInternalFaces;
+        const int o = own[f], n = internal ? nei[f] : 0;
+        const V3 Cf = ldv(fCtr, f), Sf = ldv(fArea, f), CO = ldv(cellCtr, o), CN = internal ? ldv(cellCtr, n) : v3(0, 0, 0);
+        const double magSf = mag(Sf);
+        const V3 Cpf = Cf - CO;
+        V3 dd;
+        double ortho = 1.0;
+        if (internal) {
+            dd = CN - CO;
+            ortho = dot(dd, Sf) / (mag(dd) * magSf + SMGPU_VSMALL);
+        } else {
+            const V3 nb = Sf / (magSf + SMGPU_ROOTVSMALL);
+            dd = dot(nb, Cpf) * nb;
+        }
+        const V3 sv = Cpf - (dot(Sf, Cpf) / (dot(Sf, dd) + SMGPU_ROOTVSMALL)) * dd;
+        const double magSv = mag(sv);
+        const V3 sHat = sv / (magSv + SMGPU_ROOTVSMALL);
+        double fd = 0.2 * mag(dd) + SMGPU_ROOTVSMALL;
+        const int jb = m.faceOff[f], nv = m.faceOff[f + 1] - jb;
+        if constexpr (Walk) {
+            const bool summed = nv > 3;
+            double tet = __builtin_inf(), tw = __builtin_inf(), tri = __builtin_inf();
+            int nValid = 0;
+            if (nv > 0) {
+                const V3 dv = sel3(internal, CN, Cf) - CO;
+                const V3 nHat = dv / (mag(dv) + SMGPU_VSMALL);
+                const V3 p0 = ldv(pts, m.facePts[jb]);
+                V3 cur = p0, hFirst = v3(0, 0, 0), hPrev = v3(0, 0, 0);
+                for (int i = 0; i < nv; ++i) {
+                    fd = fmax(fd, fabs(dot(sHat, cur - Cf)));
+                    const V3 nxt = (i + 1 < nv) ? ldv(pts, m.facePts[jb + i + 1]) : p0;
+                    const V3 u = nxt - cur, v = Cf - cur;
+                    tet = fmin(tet, qmTetPair(cur, u, v, CO, internal, CN, more.k));
+                    if (summed) {
+                        const V3 t = 0.5 * cross(u, v);
+                        const double mt = mag(t);
+                        if (mt > SMGPU_VSMALL) {
+                            const V3 h = t / mt;
+                            tw = fmin(tw, dot(nHat, h));
+                            if (nValid > 0) tri = fmin(tri, dot(hPrev, h));
+                            else hFirst = h;
+                            hPrev = h;
+                            ++nValid;
+                        }
+                    }
+                    cur = nxt;
+                }
+                if (nValid >= 2) tri = fmin(tri, dot(hPrev, hFirst));
+            }
+            if (nValid < 1) tw = 1.0;
+            if (nValid < 2) tri = 1.0;
+            badTet = more.tetOn && tet < more.minTet;
+            badTw = summed && more.twistOn && tw < more.minTwist;
+            badTri = summed && more.triOn && tri < more.minTri;
+        } else {
+            for (int j = jb; j < jb + nv; ++j) fd = fmax(fd, fabs(dot(sHat, ldv(pts, m.facePts[j]) - Cf)));
+        }
+        const double skew = magSv / fd;
+        badNO = internal && lim.nonOrthoOn && ortho < lim.cosT;
+        badSk = internal ? (lim.internalSkewOn && skew > lim.maxInternalSkew) : (lim.boundarySkewOn && skew > lim.maxBoundarySkew);
+        if (internal) {
+            const double dO = fabs(dot(Sf, Cpf)), dN = fabs(dot(Sf, CN - Cf));
+            const double w = fmin(dO, dN) / ((dO + dN) + SMGPU_VSMALL);
+            badW = more.weightOn && w < more.minWeight;
+            if constexpr (Ratio) {
+                const double vO = vol[o], vN = vol[n];
+                const double r = fmin(vO, vN) / (fmax(vO, vN) + SMGPU_VSMALL);
+                badR = more.ratioOn && r < more.minRatio;
+            }
+        }
+        const bool any = badNO || badSk || badTet || badTw || badTri || badW || badR;
+        if (exemptOut) exemptOut[f] = any ? 1 : 0;
+        else if (exempt[f]) badNO = badSk = badTet = badTw = badTri = badW = badR = false;
+        else if (any) {
+            cellFlag[o] = 1;
+            if (internal) cellFlag[n] = 1;
+        }
+    }
+    const bool any = badNO || badSk || badTet || badTw || badTri || badW || badR;
+    const int nNO = __syncthreads_count(badNO ? 1 : 0), nSk = __syncthreads_count(badSk ? 1 : 0), nAny = __syncthreads_count(any ? 1 : 0);
+    int nTet = 0, nTw = 0, nTri = 0, nW = 0, nR = 0;
+    if (Walk && more.tetOn) nTet = __syncthreads_count(badTet ? 1 : 0);
+    if (Walk && more.twistOn) nTw = __syncthreads_count(badTw ? 1 : 0);
+    if (Walk && more.triOn) nTri = __syncthreads_count(badTri ? 1 : 0);
+    if (more.weightOn) nW = __syncthreads_count(badW ? 1 : 0);
+    if (Ratio && more.ratioOn) nR = __syncthreads_count(badR ? 1 : 0);
+    if (threadIdx.x == 0) {
+        if (nNO > 0) atomicAdd(&d->nonOrthoNow, nNO);
+        if (nSk > 0) atomicAdd(&d->skewNow, nSk);
+        if (nAny > 0) atomicAdd(&d->facesNow, nAny);
+        if (nTet > 0) atomicAdd(&d->lowTetNow, nTet);
+        if (nTw > 0) atomicAdd(&d->lowTwistNow, nTw);
+        if (nTri > 0) atomicAdd(&d->lowTriNow, nTri);
+        if (nW > 0) atomicAdd(&d->lowWeightNow, nW);
+        if (nR > 0) atomicAdd(&d->lowRatioNow, nR);
+    }
+}
+
+// k_qc_verdict's twin with the wider record: one wave, lane 0 writes everything in plain C++
+__global__ void __launch_bounds__(64) k_qc_verdict_more(QcDev* __restrict__ d, Accum* __restrict__ acc, smgpu_quality_constraint_record_full* __restrict__ rec,
+                                                         long long number, int pass, int passes, const smgpu_iter_stats* gate) {
+    if (threadIdx.x != 0) return;
+    if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
+    const int nBad = d->t.badNow, nTangled = d->tangledNow, nNO = d->nonOrthoNow, nSk = d->skewNow;
+    const int nTet = d->lowTetNow, nTw = d->lowTwistNow, nTri = d->lowTriNow, nW = d->lowWeightNow, nR = d->lowRatioNow, nDet = d->underDetNow;
+    d->t.badNow = 0; d->tangledNow = 0; d->nonOrthoNow = 0; d->skewNow = 0; d->facesNow = 0;
+    d->lowTetNow = 0; d->lowTwistNow = 0; d->lowTriNow = 0; d->lowWeightNow = 0; d->lowRatioNow = 0; d->underDetNow = 0;
+    if (pass == 0) {
+        smgpu_quality_constraint_record_full r;
+        r.iteration = number; r.passes = 0; r.fullRevert = 0; r.nBadCells = nBad; r.nPointsReverted = 0;
+        r.nTangledCells = nTangled; r.nNonOrthoFaces = nNO; r.nSkewFaces = nSk;
+        r.nLowTetFaces = nTet; r.nLowTwistFaces = nTw; r.nLowTriangleTwistFaces = nTri; r.nLowWeightFaces = nW; r.nLowVolRatioFaces = nR;
+        r.nUnderdeterminedCells = nDet;
+        *rec = r;
+    }
+    if (nBad == 0) { d->t.clean = 1; d->t.full = 0; acc->stop = 1; return; }
+    d->t.clean = 0;
+    if (pass == passes) { d->t.full = 1; rec->fullRevert = 1; }
+    else { d->t.full = 0; rec->passes += 1; }
+}
+
+}  // namespace smgpu

@@ -469,8 +469,18 @@ int smgpu_tangle_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done) {
 }
 
 // ---- the quality constraint (kernels_quality_constraint.hpp, DESIGN.md "Mesh quality", 10.14) ----
+// the limits of 10.16 as the kernels take them: NULL limits, and which criteria a set of limits switches on
+static const smgpu_quality_constraint_limits kQcLimitsDefault{65.0, 4.0, 20.0, 2, -1e30, -1.0, -1.0, 0.0, 0.0, 0.0};
+static QcMore qualityConstraintMore(const smgpu_quality_constraint_limits& l) {
+    return QcMore{l.minTetQuality, l.minTwist, l.minTriangleTwist, l.minFaceWeight, l.minVolRatio, l.minDeterminant, motionThresholds(nullptr).k,
+                  l.minTetQuality > -1e30 ? 1 : 0, l.minTwist > -1.0 ? 1 : 0, l.minTriangleTwist > -1.0 ? 1 : 0,
+                  l.minFaceWeight > 0.0 ? 1 : 0, l.minVolRatio > 0.0 ? 1 : 0, l.minDeterminant > 0.0 ? 1 : 0};
+}
 static int qualityConstraintOff(smgpu_handle* h) {
     h->qc.on = false;
+    h->qc.more = qualityConstraintMore(kQcLimitsDefault);
+    h->qc.faceMore = h->qc.cellMore = false;
+    h->qc.nExemptDet = 0;
     h->qc.slab.discard();
     if (h->qc.block.live()) {
         HIP_OK(hipStreamSynchronize(h->stream));
@@ -506,11 +516,23 @@ static int qualityConstraintEvaluate(smgpu_handle* h, bool enabling, int pass, c
         if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
         if (m.nCells > 0) hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
     }
-    if (m.nFaces > 0)
+    const int gCells = (m.nCells + kQcBlock - 1) / kQcBlock;
+    // 10.16 (kernels_quality_limits.hpp): the cell pass in front of the faces, which read its volumes, and the wider face pass
+    if (q.cellMore && m.nCells > 0) {
+        auto cells = q.more.detOn ? k_qc_cells_more<true> : k_qc_cells_more<false>;
+        hipLaunchKernelGGL(cells, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.fCtr, (const double*)ts.fArea, q.more, q.vol,
+                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptDet, enabling ? q.exemptDet : (uint8_t*)nullptr, q.cellFlag, q.dev, pass, gate);
+    }
+    if (m.nFaces > 0 && q.faceMore) {
+        const bool walk = q.more.tetOn || q.more.twistOn || q.more.triOn, ratio = q.more.ratioOn != 0;
+        auto faces = walk ? (ratio ? k_qc_faces_more<true, true> : k_qc_faces_more<true, false>) : (ratio ? k_qc_faces_more<false, true> : k_qc_faces_more<false, false>);
+        hipLaunchKernelGGL(faces, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.ptsCur, (const double*)ts.fCtr,
+                           (const double*)ts.fArea, (const double*)ts.cellCtr, (const double*)q.vol, (const int*)h->q.own, (const int*)h->q.nei, q.lim, q.more,
+                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag, q.dev, pass, gate);
+    } else if (m.nFaces > 0)
         hipLaunchKernelGGL(k_qc_faces, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.ptsCur, (const double*)ts.fCtr,
                            (const double*)ts.fArea, (const double*)ts.cellCtr, (const int*)h->q.own, (const int*)h->q.nei, q.lim,
                            enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag, q.dev, pass, gate);
-    const int gCells = (m.nCells + kQcBlock - 1) / kQcBlock;
     if (m.nCells > 0 && !h->useTiles)
         hipLaunchKernelGGL(k_qc_cells<true>, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.fCtr, (const double*)ts.fArea, (const double*)ts.cellCtr,
                            enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptCell, enabling ? q.exemptCell : (uint8_t*)nullptr, (const uint8_t*)nullptr,
@@ -524,13 +546,18 @@ static int qualityConstraintEvaluate(smgpu_handle* h, bool enabling, int pass, c
 // behind the movePoints of an iteration: the passes on the points ptsCur now names; x: the points the iteration started from
 static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x) {
     QualityConstraintHost& q = h->qc;
-    smgpu_quality_constraint_record* rec = nullptr;
+    smgpu_quality_constraint_record_full* rec = nullptr;
     if (q.slab.slot(slot, &rec)) return 1;
     const int nP = h->mv.nPoints;
     const int gApply = std::max(1, (int)(((int64_t)nP + kTanglePts - 1) / kTanglePts));
     for (int k = 0; k <= q.prm.passes; ++k) {
         if (qualityConstraintEvaluate(h, false, k, gate)) return 1;
-        hipLaunchKernelGGL(k_qc_verdict, dim3(1), dim3(64), 0, h->stream, q.dev, q.acc, rec, (long long)number, k, (int)q.prm.passes, gate);
+        // (the narrow record is the head of the slot: kernels_quality_limits.hpp)
+        if (q.faceMore || q.cellMore)
+            hipLaunchKernelGGL(k_qc_verdict_more, dim3(1), dim3(64), 0, h->stream, q.dev, q.acc, rec, (long long)number, k, (int)q.prm.passes, gate);
+        else
+            hipLaunchKernelGGL(k_qc_verdict, dim3(1), dim3(64), 0, h->stream, q.dev, q.acc, reinterpret_cast<smgpu_quality_constraint_record*>(rec), (long long)number, k,
+                               (int)q.prm.passes, gate);
         // the record and the device words begin with the tangle constraint's (kernels_quality_constraint.hpp)
         hipLaunchKernelGGL(k_tangle_apply, dim3(gApply), dim3(kTangleBlock), 0, h->stream, x, h->st.ptsCur, q.marks, nP, (const TangleDev*)&q.dev->t,
                            reinterpret_cast<smgpu_tangle_record*>(rec), gate);
@@ -539,20 +566,20 @@ static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, con
     return 0;
 }
 
-int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint_params* p, int32_t on) {
-    if (!h) return fail("null handle");
-    HIP_OK(hipSetDevice(h->device));
-    if (!on) return qualityConstraintOff(h);
-    const smgpu_quality_constraint_params prm = p ? *p : smgpu_quality_constraint_params{65.0, 4.0, 20.0, 2};
-    if (prm.passes < 0) return fail("smgpu_set_quality_constraint: passes < 0");
-    if (std::isnan(prm.maxNonOrtho) || std::isnan(prm.maxInternalSkewness) || std::isnan(prm.maxBoundarySkewness))
-        return fail("smgpu_set_quality_constraint: a limit is NaN");
+// the two entries of the serial constraint: api names the one called, in its refusals; more: the limits of 10.16 (all off under
+// smgpu_set_quality_constraint)
+static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgpu_quality_constraint_params& prm, const QcMore& more) {
+    const std::string api(name);
+    if (prm.passes < 0) return fail(api + ": passes < 0");
+    if (std::isnan(prm.maxNonOrtho) || std::isnan(prm.maxInternalSkewness) || std::isnan(prm.maxBoundarySkewness) || std::isnan(more.minTet) ||
+        std::isnan(more.minTwist) || std::isnan(more.minTri) || std::isnan(more.minWeight) || std::isnan(more.minRatio) || std::isnan(more.minDet))
+        return fail(api + ": a limit is NaN");
     if (h->haloOn) return fail(kQualityHaloRefusal);
     if (h->bndOn)
-        return fail("smgpu_set_quality_constraint: not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
+        return fail(api + ": not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
                     "points from state that a reverted iteration would leave ahead of the points)");
-    if (h->tg.on) return fail("smgpu_set_quality_constraint: the tangle constraint is on (smgpu_set_tangle_constraint), and this constraint contains it; switch it off first");
-    if (h->iterOpen) return fail("smgpu_set_quality_constraint: between smgpu_iter_begin and smgpu_iter_end");
+    if (h->tg.on) return fail(api + ": the tangle constraint is on (smgpu_set_tangle_constraint), and this constraint contains it; switch it off first");
+    if (h->iterOpen) return fail(api + ": between smgpu_iter_begin and smgpu_iter_end");
     if (qualityConstraintOff(h)) return 1;
     if (flushDeferred(h)) return 1;
     if (qualityEnsure(h)) return 1;                  // owner / neighbour by face
@@ -562,6 +589,10 @@ int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint
     if (q.block.alloc(&q.dev, 1) || q.block.alloc(&q.exemptCell, nCell) || q.block.alloc(&q.cellFlag, nCell) || q.block.alloc(&q.tangled, nCell) || q.block.alloc(&q.exemptFace, nFace) ||
         q.block.alloc(&q.marks, nMark) || q.block.alloc(&q.cellCtr, 3 * nCell) || q.block.alloc(&q.acc, 1))
         return q.block.failed("the quality constraint");
+    q.more = more;
+    q.faceMore = more.tetOn || more.twistOn || more.triOn || more.weightOn || more.ratioOn;
+    q.cellMore = more.ratioOn || more.detOn;
+    if (q.cellMore && (q.block.alloc(&q.vol, nCell) || q.block.alloc(&q.exemptDet, nCell))) return q.block.failed("the quality constraint");
     HIP_OK(hipMemsetAsync(q.dev, 0, sizeof(QcDev), h->stream));
     HIP_OK(hipMemsetAsync(q.exemptCell, 0, nCell, h->stream));
     HIP_OK(hipMemsetAsync(q.cellFlag, 0, nCell, h->stream));
@@ -569,6 +600,7 @@ int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint
     HIP_OK(hipMemsetAsync(q.exemptFace, 0, nFace, h->stream));
     HIP_OK(hipMemsetAsync(q.marks, 0, nMark, h->stream));
     HIP_OK(hipMemsetAsync(q.acc, 0, sizeof(Accum), h->stream));
+    if (q.cellMore) HIP_OK(hipMemsetAsync(q.exemptDet, 0, nCell, h->stream));
     q.prm = prm;
     // cosT exactly as qualityThresholds() forms the report's cosine
     const smgpu_quality_params rp{prm.maxNonOrtho, prm.maxInternalSkewness, 1e-6, 1000.0};
@@ -582,9 +614,25 @@ int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint
     if (checkDeviceError(h)) { q.release(); return 1; }
     q.nExemptCells = qd.t.badNow;
     q.nExemptFaces = qd.facesNow;
+    q.nExemptDet = qd.underDetNow;
     q.since = h->iterCount;
     q.on = true;
     return 0;
+}
+int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint_params* p, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityConstraintOff(h);
+    const smgpu_quality_constraint_params prm = p ? *p : smgpu_quality_constraint_params{65.0, 4.0, 20.0, 2};
+    return qualityConstraintEnable(h, "smgpu_set_quality_constraint", prm, qualityConstraintMore(kQcLimitsDefault));
+}
+int smgpu_set_quality_constraint_limits(smgpu_handle* h, const smgpu_quality_constraint_limits* p, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityConstraintOff(h);
+    const smgpu_quality_constraint_limits l = p ? *p : kQcLimitsDefault;
+    return qualityConstraintEnable(h, "smgpu_set_quality_constraint_limits", smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
+                                   qualityConstraintMore(l));
 }
 static int qualityConstraintCoupledFlush(smgpu_handle* h);
 int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n) {
@@ -594,7 +642,25 @@ int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constrai
         HIP_OK(hipSetDevice(h->device));
         if (qualityConstraintCoupledFlush(h)) return 1;
     }
-    return h->qc.slab.drain(out, cap, n, "smgpu_get_quality_constraint_records");
+    return h->qc.slab.drainHeads(out, cap, n, "smgpu_get_quality_constraint_records");
+}
+int smgpu_get_quality_constraint_records_full(smgpu_handle* h, smgpu_quality_constraint_record_full* out, int64_t cap, int64_t* n) {
+    if (!h || !n) return fail("null argument");
+    if (h->qc.coupled) {
+        if (h->qc.k >= 0) return fail("smgpu_get_quality_constraint_records_full: between the passes of an iteration (smgpu_quality_constraint_pass_begin / _end)");
+        HIP_OK(hipSetDevice(h->device));
+        if (qualityConstraintCoupledFlush(h)) return 1;
+    }
+    return h->qc.slab.drain(out, cap, n, "smgpu_get_quality_constraint_records_full");
+}
+int smgpu_get_quality_constraint_state_full(smgpu_handle* h, smgpu_quality_constraint_state_full* out) {
+    if (!h || !out) return fail("null argument");
+    smgpu_quality_constraint_state s{};
+    if (smgpu_get_quality_constraint_state(h, &s)) return 1;
+    const QcMore& m = h->qc.more;
+    *out = smgpu_quality_constraint_state_full{s.on, s.passes, s.maxNonOrtho, s.maxInternalSkewness, s.maxBoundarySkewness, s.nExemptCells, s.nExemptFaces, s.iteration,
+                                               m.minTet, m.minTwist, m.minTri, m.minWeight, m.minRatio, m.minDet, s.on ? h->qc.nExemptDet : 0};
+    return 0;
 }
 int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint_state* out) {
     if (!h || !out) return fail("null argument");
@@ -803,8 +869,9 @@ int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32
     if (q.stage != 2 || q.k < 0) return fail("smgpu_quality_constraint_pass_end without smgpu_quality_constraint_pass_faces");
     if (nBadGlobal < 0) return fail("smgpu_quality_constraint_pass_end: nBadGlobal < 0");
     HIP_OK(hipSetDevice(h->device));
-    smgpu_quality_constraint_record* rec = nullptr;
-    if (q.slab.slot(q.slabUsed, &rec)) return 1;
+    smgpu_quality_constraint_record_full* slot = nullptr;       // (its head is the record this form writes; the rest stays zero)
+    if (q.slab.slot(q.slabUsed, &slot)) return 1;
+    smgpu_quality_constraint_record* rec = reinterpret_cast<smgpu_quality_constraint_record*>(slot);
     const int nP = h->mv.nPoints;
     const bool full = nBadGlobal > 0 && q.k == q.prm.passes;
     if (nBadGlobal > 0) {

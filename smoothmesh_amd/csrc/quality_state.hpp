@@ -89,6 +89,18 @@ class RecordSlab {
         *n = have;
         return 0;
     }
+    // drain() for a caller whose record is the head of Rec: each pending record's first sizeof(Head) bytes
+    template <class Head>
+    int drainHeads(Head* out, int64_t capOut, int64_t* n, const char* api) {
+        static_assert(sizeof(Head) <= sizeof(Rec), "a head is no longer than the record");
+        const int64_t have = (int64_t)pending.size();
+        if (!out) { *n = have; return 0; }
+        if (capOut < have) return fail(std::string(api) + ": cap " + std::to_string(capOut) + " is below the " + std::to_string(have) + " pending records");
+        for (int64_t i = 0; i < have; ++i) std::memcpy(out + i, &pending[(size_t)i], sizeof(Head));
+        pending.clear();
+        *n = have;
+        return 0;
+    }
     // the device slab (the pending records stay)
     void release() { if (dev) (void)hipFree(dev); dev = nullptr; cap = 0; }
 };
@@ -200,7 +212,16 @@ struct QualityConstraintHost {
     QcDev* dev = nullptr;
     double* cellCtr = nullptr;
     Accum* acc = nullptr;
-    RecordSlab<smgpu_quality_constraint_record> slab{"quality constraint"};   // one record per iteration of the call
+    // one record per iteration of the call; without the limits of 10.16 only its head, smgpu_quality_constraint_record, is written
+    RecordSlab<smgpu_quality_constraint_record_full> slab{"quality constraint"};
+    // the limits of 10.16 (smgpu_set_quality_constraint_limits, kernels_quality_limits.hpp).  faceMore: a new face criterion is
+    // on; cellMore: minVolRatio or minDeterminant is; with neither the launches are 10.14's.  vol, exemptDet: allocated with
+    // cellMore, 8 bytes and 1 byte per cell
+    QcMore more{-1e30, -1.0, -1.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0};
+    bool faceMore = false, cellMore = false;
+    int64_t nExemptDet = 0;
+    double* vol = nullptr;
+    uint8_t* exemptDet = nullptr;
     // the coupled form (smgpu_set_quality_constraint_coupled, 10.15) on an engine with a halo: TangleHost's coupled members with
     // the same meaning (x, k, reverting, count, the slab in chunks, counted, sendT / recvT), and what the face verdicts add.
     // pending: enabled, the exempt faces not taken yet.  stage: 0 no pass open, 1 behind pass_begin, 2 behind pass_faces.  n0: the

@@ -26,6 +26,7 @@
 #include "kernels_quality_guard.hpp"
 #include "kernels_quality_tangle.hpp"
 #include "kernels_quality_constraint.hpp"
+#include "kernels_quality_limits.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"

@@ -170,6 +170,46 @@ class QualityConstraintState:
     iteration: int
 
 
+# the limits of DESIGN.md "Mesh quality", 10.16, in the order of smgpu_quality_constraint_limits, with the value at or below
+# which each is off
+QUALITY_CONSTRAINT_LIMITS_OFF = dict(minTetQuality=-1e30, minTwist=-1.0, minTriangleTwist=-1.0, minFaceWeight=0.0, minVolRatio=0.0, minDeterminant=0.0)
+
+
+def quality_constraint_limits_on(**limits):
+    """the limits of QUALITY_CONSTRAINT_LIMITS_OFF among `limits` that are on (None: off; a NaN counts, to be refused), by name"""
+    bad = set(limits) - set(QUALITY_CONSTRAINT_LIMITS_OFF)
+    if bad:
+        raise TypeError(f"set_quality_constraint: unknown limit {sorted(bad)[0]}")
+    return {k: float(v) for k, v in limits.items() if v is not None and not float(v) <= QUALITY_CONSTRAINT_LIMITS_OFF[k]}
+
+
+@dataclass
+class QualityConstraintRecordFull(QualityConstraintRecord):
+    """smgpu_quality_constraint_record_full (DESIGN.md "Mesh quality", 10.16): QualityConstraintRecord, then the faces that were
+    bad after the loop's move by tet quality, twist, triangle twist, interpolation weight and volume ratio and the cells under
+    the determinant limit (a face that fails several counts in each; exempt elements never count).  All 0 while none of these
+    limits is on."""
+    nLowTetFaces: int = 0
+    nLowTwistFaces: int = 0
+    nLowTriangleTwistFaces: int = 0
+    nLowWeightFaces: int = 0
+    nLowVolRatioFaces: int = 0
+    nUnderdeterminedCells: int = 0
+
+
+@dataclass
+class QualityConstraintStateFull(QualityConstraintState):
+    """smgpu_quality_constraint_state_full: QualityConstraintState, then the six limits of 10.16 (their off values while they are
+    off) and the cells exempt from the determinant limit"""
+    minTetQuality: float = -1e30
+    minTwist: float = -1.0
+    minTriangleTwist: float = -1.0
+    minFaceWeight: float = 0.0
+    minVolRatio: float = 0.0
+    minDeterminant: float = 0.0
+    nExemptDeterminantCells: int = 0
+
+
 @dataclass
 class TangleState:
     """smgpu_tangle_state: whether the constraint is on, its passes, the cells exempt since enabling, the running number"""
@@ -703,16 +743,27 @@ class SmoothEngine:
         self._check(self._lib.smgpu_get_tangle_state(self._h, C.byref(s)))
         return TangleState(on=bool(s.on), passes=s.passes, nExemptCells=s.nExemptCells, iteration=s.iteration)
 
-    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2):
+    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
+                               minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None):
         """Quality constraint (include/smgpu.h, smgpu_set_quality_constraint; DESIGN.md "Mesh quality", 10.14): the tangle
         constraint with limits on face non-orthogonality (degrees; >= 180: off) and on the skewness of internal and of boundary
         faces (<= 0: off).  From now on iterate() puts the points of every cell that an iteration turned bad -- by the tangle
         constraint's measure, or as the owner or neighbour of a face over a limit -- back where the iteration found them, in up to
         `passes` marked passes and then a full revert.  Cells and faces bad at the current points are exempt.  Adds no
         synchronisation to the loop.  Refused on an engine with a halo, with boundary point smoothing, or with the tangle
-        constraint on."""
-        p = _ffi.QualityConstraintParams(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes))
-        self._check(self._lib.smgpu_set_quality_constraint(self._h, C.byref(p), 1))
+        constraint on.
+        The six further limits (smgpu_set_quality_constraint_limits; None: off) make a face bad whose face-centre
+        tet quality, twist, triangle twist, interpolation weight or volume ratio lies under them, and a cell whose determinant
+        does, by the measures of mesh_quality_motion / mesh_quality_geometry; with all six None the call is what it was."""
+        more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
+                    minVolRatio=minVolRatio, minDeterminant=minDeterminant)
+        if all(v is None for v in more.values()):
+            p = _ffi.QualityConstraintParams(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes))
+            self._check(self._lib.smgpu_set_quality_constraint(self._h, C.byref(p), 1))
+            return
+        more = {k: QUALITY_CONSTRAINT_LIMITS_OFF[k] if v is None else float(v) for k, v in more.items()}
+        p = _ffi.QualityConstraintLimits(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more)
+        self._check(self._lib.smgpu_set_quality_constraint_limits(self._h, C.byref(p), 1))
 
     def clear_quality_constraint(self):
         """Switch the quality constraint (either form) off; discards unread records."""
@@ -755,19 +806,20 @@ class SmoothEngine:
         return bool(done.value)
 
     def quality_constraint_records(self) -> list:
-        """The pending records of the quality constraint, one per iteration that ran, in ascending iteration; clears them."""
+        """The pending records of the quality constraint (QualityConstraintRecordFull), one per iteration that ran, in ascending
+        iteration; clears them."""
         n = C.c_int64(0)
-        self._check(self._lib.smgpu_get_quality_constraint_records(self._h, None, 0, C.byref(n)))
+        self._check(self._lib.smgpu_get_quality_constraint_records_full(self._h, None, 0, C.byref(n)))
         if n.value == 0:
             return []
-        buf = (_ffi.QualityConstraintRecord * n.value)()
-        self._check(self._lib.smgpu_get_quality_constraint_records(self._h, buf, n.value, C.byref(n)))
-        return [QualityConstraintRecord(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+        buf = (_ffi.QualityConstraintRecordFull * n.value)()
+        self._check(self._lib.smgpu_get_quality_constraint_records_full(self._h, buf, n.value, C.byref(n)))
+        return [QualityConstraintRecordFull(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
 
-    def quality_constraint_state(self) -> QualityConstraintState:
-        s = _ffi.QualityConstraintState()
-        self._check(self._lib.smgpu_get_quality_constraint_state(self._h, C.byref(s)))
-        return QualityConstraintState(on=bool(s.on), **{f: getattr(s, f) for f, _ in s._fields_ if f != "on"})
+    def quality_constraint_state(self) -> QualityConstraintStateFull:
+        s = _ffi.QualityConstraintStateFull()
+        self._check(self._lib.smgpu_get_quality_constraint_state_full(self._h, C.byref(s)))
+        return QualityConstraintStateFull(on=bool(s.on), **{f: getattr(s, f) for f, _ in s._fields_ if f != "on"})
 
     def quality_field(self, name) -> np.ndarray:
         """Per-element quality field in polyMesh order: one of QUALITY_FIELDS (non-orthogonality in degrees, 0 on boundary faces)."""

@@ -197,11 +197,20 @@ def combine_tangle_records(per_rank):
     return out
 
 
+def _refuse_more_limits(more):
+    """the limits of DESIGN.md "Mesh quality", 10.16, are the serial engine's: a decomposed mesh refuses one that is on"""
+    from .engine import quality_constraint_limits_on
+    on = quality_constraint_limits_on(**more)
+    if on:
+        raise ValueError(f"set_quality_constraint: {sorted(on)[0]} is not available on a decomposed mesh (the tet, twist, weight, volume ratio and "
+                         "determinant limits are judged on a serial engine only); leave it out or pass None")
+
+
 def combine_quality_constraint_records(per_rank):
     """the records of the undecomposed mesh from every rank's (DESIGN.md "Mesh quality", 10.15): `passes` and `fullRevert` are
     global values, the same on every rank; the counts are sums (a shared point counts on its master only, a processor face on
     the rank with the lower number)"""
-    from .engine import QualityConstraintRecord
+    from .engine import QualityConstraintRecordFull as QualityConstraintRecord   # (the six counts of 10.16 are 0 on a decomposed mesh)
     out = []
     for recs in zip(*per_rank):
         r0 = recs[0]
@@ -848,11 +857,13 @@ class DistributedSmoother:
         if self.world > 1:
             st.recvCc.copy_(self._quality_swap(st.qcCoupling[1], st.sendCc, 3))
 
-    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2):
+    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
         """From now on iterate() also keeps face non-orthogonality and skewness under the limits (engine.set_quality_constraint's
         parameters), on the global mesh: a processor face is judged as the internal face it is, with the neighbour rank's cell
         centre, which travels once per pass like the coupled report's; marks and verdict as set_tangle_constraint.  Every rank
-        calls it (a collective: the exempt faces need one exchange)."""
+        calls it (a collective: the exempt faces need one exchange).  more: the limits of engine.set_quality_constraint that a
+        decomposed mesh does not take: one that is on is a ValueError."""
+        _refuse_more_limits(more)
         torch, st, eng = self.torch, self.state, self.engine
         if self.tangle_passes is not None:
             raise RuntimeError("set_quality_constraint: the tangle constraint is on, and this constraint contains it; clear_tangle_constraint first")
@@ -1200,8 +1211,9 @@ class LocalMultiSmoother:
         for i, off, j, ooff, size in self.ccCopies:
             self.states[i].recvCc[off:off + size].copy_(self.states[j].sendCc[ooff:ooff + size])
 
-    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2):
+    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
         """as DistributedSmoother.set_quality_constraint; cell centres and marks move by device-side copies"""
+        _refuse_more_limits(more)
         from .quality import paired_offsets
         torch = self.torch
         if self.tangle_passes is not None:

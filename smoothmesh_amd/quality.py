@@ -18,7 +18,7 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityGuardState, QualityTraceRecord, TangleRecord, TangleState, QualityConstraintRecord, QualityConstraintState, QUALITY_FIELDS,  # noqa: F401
+from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityGuardState, QualityTraceRecord, TangleRecord, TangleState, QualityConstraintRecord, QualityConstraintState, QualityConstraintRecordFull, QualityConstraintStateFull, QUALITY_FIELDS,  # noqa: F401
                      QUALITY_GEOMETRY_FIELDS, QUALITY_MOTION_FIELDS, QUALITY_SETS, QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS)
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
@@ -455,11 +455,22 @@ def format_tangle_line(rec):
             + (" fullRevert" if rec.fullRevert else "") + "\n")
 
 
-def format_quality_constraint_line(rec):
+def format_quality_constraint_line(rec, more=False):
     """the line smoothMesh -qualityConstraint prints under the iteration line of an iteration whose nBadCells > 0 (csrc/host/
-    smoothMesh_main.cpp), of a QualityConstraintRecord"""
+    smoothMesh_main.cpp), of a QualityConstraintRecord; more: the line of a run with one of the limits of DESIGN.md 10.16 given
+    (-minTetQuality ... -minDeterminant), of a QualityConstraintRecordFull"""
+    extra = (f" lowTetFaces {rec.nLowTetFaces} twistedFaces {rec.nLowTwistFaces} lowTriangleTwistFaces {rec.nLowTriangleTwistFaces} "
+             f"lowWeightFaces {rec.nLowWeightFaces} lowVolRatioFaces {rec.nLowVolRatioFaces} underdeterminedCells {rec.nUnderdeterminedCells}") if more else ""
     return (f"    quality constraint iteration={rec.iteration} badCells {rec.nBadCells} tangled {rec.nTangledCells} nonOrthoFaces {rec.nNonOrthoFaces} "
-            f"skewFaces {rec.nSkewFaces} passes {rec.passes} pointsReverted {rec.nPointsReverted}" + (" fullRevert" if rec.fullRevert else "") + "\n")
+            f"skewFaces {rec.nSkewFaces}{extra} passes {rec.passes} pointsReverted {rec.nPointsReverted}" + (" fullRevert" if rec.fullRevert else "") + "\n")
+
+
+def format_quality_constraint_limits_line(state):
+    """the second set-up line of smoothMesh -qualityConstraint with one of the limits of DESIGN.md 10.16 given: the limits that are
+    on, in the order of smgpu_quality_constraint_limits, and the determinant-exempt cells; of a QualityConstraintStateFull"""
+    from .engine import QUALITY_CONSTRAINT_LIMITS_OFF
+    on = "".join(f" {k} {getattr(state, k):g}" for k, off in QUALITY_CONSTRAINT_LIMITS_OFF.items() if getattr(state, k) > off)
+    return f"Quality constraint limits:{on}, {state.nExemptDeterminantCells} determinant-exempt cells\n"
 
 
 def format_guard_lines(state):
