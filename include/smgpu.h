@@ -460,8 +460,9 @@ int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint
  * Under smgpu_set_quality_constraint (and the coupled form) the new counts are 0 and the limits the off values.
  *
  * Not covered: the base-point tets (their walk is O(nv^2) per face and stays with the report), maxConcave and minFlatness (the
- * concavity value depends on its own threshold), minVol and minArea, reading system/meshQualityDict, and the coupled form:
- * smgpu_set_quality_constraint_coupled takes the three limits of 10.14 only.
+ * concavity value depends on its own threshold), minVol and minArea, reading system/meshQualityDict.  On a decomposed mesh
+ * smgpu_set_quality_constraint_coupled takes the three limits of 10.14 only; smgpu_set_quality_constraint_limits_coupled (10.17,
+ * below) takes all nine.
  * Memory, beyond 10.14's: 104 bytes per iteration of the longest call in place of 56; with minVolRatio or minDeterminant on,
  * 8 nCells bytes of volumes and nCells bytes of determinant exemptions. */
 typedef struct smgpu_quality_constraint_limits {
@@ -547,6 +548,44 @@ int smgpu_quality_constraint_coupled_exempt(smgpu_handle* h);
 int smgpu_quality_constraint_pass_begin(smgpu_handle* h);                                   /* after smgpu_iter_end */
 int smgpu_quality_constraint_pass_faces(smgpu_handle* h, int64_t* nBadLocal);
 int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done);
+
+/* ---- the six further limits on a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.17) --------------------------
+ * 10.16 read on the GLOBAL mesh, for an engine whose halo is configured.  Everything not said here is 10.15's (passes, marks,
+ * verdict, hazards, refusals) and 10.16's (values, strict <, off values, exemption bytes).
+ *
+ * PROCESSOR FACE (a slot >= 0 in the coupling).  It takes the internal-face branch of every face criterion, with the decomposed
+ * reports' definitions (10.8): the tets with the neighbour side from the received C_N, the twist with d = C_N - C_O, the weight
+ * with dN from the received C_N, the volume ratio with the received signed V_N; the triangle twist is local.  It is tested
+ * against minFaceWeight and minVolRatio like an internal face.  A physical boundary face is judged as in 10.16.
+ * CELL DETERMINANT.  Over the cell's internal AND processor faces, as the decomposed -allGeometry report forms it; S_f is local,
+ * so nothing travels for it.
+ * WHO JUDGES, TIES, COUNTED ONCE: 10.15's.  Both ranks judge a processor face, each flags its own owner cell; the new face
+ * counts of the record and the face's share of nExemptFaces count only on the side with myRank < neighbRank;
+ * nUnderdeterminedCells and nExemptDeterminantCells are the rank's own.  Summed over the ranks the full record and the state are
+ * those of the undecomposed mesh under smgpu_set_quality_constraint_limits.
+ * WHAT TRAVELS.  V_c of the owner cell of every processor face, one double per face in sendCc's slot order, only when minVolRatio
+ * is on.  The volumes (and the determinant) are formed in the first half of an evaluation -- in smgpu_quality_constraint_pass_begin
+ * and in the enabling call -- in front of the packs, so sendVc is complete where sendCc is and the host moves both in one step: a
+ * pass still waits for its engine twice.
+ * EQUIVALENCES.  All six off: smgpu_set_quality_constraint_coupled's run bit for bit -- points, records, state -- and exactly its
+ * launches.  A single sub-domain without processor patches: the serial run under smgpu_set_quality_constraint_limits, bit for bit.
+ *
+ * smgpu_quality_constraint_halo_desc_full: smgpu_quality_constraint_halo_desc at its offsets, then sendVc / recvVc.
+ * smgpu_quality_constraint_coupled_exempt and the three pass calls serve both entries, and so do the getters; the six counts and
+ * nExemptDeterminantCells are filled under this entry and stay 0 and off under smgpu_set_quality_constraint_coupled.
+ * Refused, naming smgpu_set_quality_constraint_limits_coupled: everything smgpu_set_quality_constraint_coupled refuses, a NaN
+ * among the six, minVolRatio on with a null sendVc or recvVc (and a processor face), enabling while a tangle form is on.
+ * Memory, beyond 10.15's: with minVolRatio or minDeterminant on 9 nCells bytes; the caller owns sendVc / recvVc (16 nProcFaces
+ * bytes). */
+typedef struct smgpu_quality_constraint_halo_desc_full {
+    void *sendT, *recvT;
+    void *sendCc, *recvCc;
+    const struct smgpu_quality_coupling* coupling;
+    void *sendVc, *recvVc;                  /* device, one double per processor face in sendCc's slot order; may be NULL while
+                                               minVolRatio is off */
+} smgpu_quality_constraint_halo_desc_full;
+int smgpu_set_quality_constraint_limits_coupled(smgpu_handle* h, const smgpu_quality_constraint_limits* p,
+                                                const smgpu_quality_constraint_halo_desc_full* d, int32_t on);
 
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):

@@ -225,6 +225,11 @@ class QualityConstraintHaloDesc(C.Structure):
     _fields_ = [("sendT", C.c_void_p), ("recvT", C.c_void_p), ("sendCc", C.c_void_p), ("recvCc", C.c_void_p), ("coupling", C.POINTER(QualityCoupling))]
 
 
+class QualityConstraintHaloDescFull(C.Structure):
+    """smgpu_quality_constraint_halo_desc_full: QualityConstraintHaloDesc's fields, then the volume buffers of DESIGN.md 10.17"""
+    _fields_ = QualityConstraintHaloDesc._fields_ + [("sendVc", C.c_void_p), ("recvVc", C.c_void_p)]
+
+
 class QualityPart(C.Structure):
     """smgpu_quality_part: Quality with sumNonOrth in place of avgNonOrth"""
     _fields_ = [("sumNonOrth" if n == "avgNonOrth" else n, t) for n, t in Quality._fields_]
@@ -315,6 +320,7 @@ SYMBOLS = {
     "smgpu_get_quality_constraint_records_full": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintRecordFull), C.c_int64, C.POINTER(C.c_int64)]),
     "smgpu_get_quality_constraint_state_full": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintStateFull)]),
     "smgpu_set_quality_constraint_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintParams), C.POINTER(QualityConstraintHaloDesc), C.c_int32]),
+    "smgpu_set_quality_constraint_limits_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintLimits), C.POINTER(QualityConstraintHaloDescFull), C.c_int32]),
     "smgpu_quality_constraint_coupled_exempt": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_begin": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_faces": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

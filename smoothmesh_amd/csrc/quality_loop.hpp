@@ -713,9 +713,20 @@ static int qualityConstraintCoupledGeometry(smgpu_handle* h, bool enabling) {
         if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
         if (m.nCells > 0) hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
     }
+    // 10.17 (kernels_quality_limits_coupled.hpp): the volumes travel with the cell centres, so the cell pass stands in this half;
+    // the byte it leaves in cellFlag and its count in QcDev wait for the second half
+    if (q.cellMore && m.nCells > 0) {
+        auto cells = q.more.detOn ? k_qc_cells_more_coupled<true> : k_qc_cells_more_coupled<false>;
+        hipLaunchKernelGGL(cells, dim3((m.nCells + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.fCtr, (const double*)ts.fArea,
+                           (const int*)q.slot, q.more, q.vol, enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptDet,
+                           enabling ? q.exemptDet : (uint8_t*)nullptr, q.cellFlag, q.dev);
+    }
     if (q.nProc > 0)
         hipLaunchKernelGGL(k_quality_pack, dim3((q.nProc + kQualityBlock - 1) / kQualityBlock), dim3(kQualityBlock), 0, h->stream, (const int*)h->q.own,
                            (const double*)q.cellCtr, (const int*)q.procFace, q.nProc, q.sendCc);
+    if (q.nProc > 0 && q.more.ratioOn)
+        hipLaunchKernelGGL(k_quality_pack_volumes, dim3((q.nProc + kQualityBlock - 1) / kQualityBlock), dim3(kQualityBlock), 0, h->stream, (const int*)h->q.own,
+                           (const double*)q.vol, (const int*)q.procFace, q.nProc, q.sendVc);
     HIP_OK(hipGetLastError());
     return checkDeviceError(h);
 }
@@ -726,7 +737,15 @@ static int qualityConstraintCoupledVerdicts(smgpu_handle* h, bool enabling, QcDe
     QualityConstraintHost& q = h->qc;
     if (computeAfterExch(h)) return 1;          // exchange Cc has been enqueued by the host
     const double *fCtr = h->st.fCtr, *fArea = h->st.fArea, *pts = h->st.ptsCur;
-    if (m.nFaces > 0)
+    if (m.nFaces > 0 && q.faceMore) {   // 10.17: the wider face pass in the place of k_qc_faces_coupled
+        const bool walk = q.more.tetOn || q.more.twistOn || q.more.triOn, ratio = q.more.ratioOn != 0;
+        auto faces = walk ? (ratio ? k_qc_faces_more_coupled<true, true> : k_qc_faces_more_coupled<true, false>)
+                          : (ratio ? k_qc_faces_more_coupled<false, true> : k_qc_faces_more_coupled<false, false>);
+        hipLaunchKernelGGL(faces, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, pts, fCtr, fArea, (const double*)q.cellCtr,
+                           (const double*)q.vol, (const int*)h->q.own, (const int*)h->q.nei, (const int*)q.slot, (const double*)q.recvCc, (const double*)q.recvVc,
+                           q.lim, q.more, enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag,
+                           q.dev);
+    } else if (m.nFaces > 0)
         hipLaunchKernelGGL(k_qc_faces_coupled, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, pts, fCtr, fArea, (const double*)q.cellCtr,
                            (const int*)h->q.own, (const int*)h->q.nei, (const int*)q.slot, (const double*)q.recvCc, q.lim,
                            enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag, q.dev);
@@ -747,29 +766,34 @@ static int qualityConstraintCoupledVerdicts(smgpu_handle* h, bool enabling, QcDe
     return checkDeviceError(h);
 }
 
-int smgpu_set_quality_constraint_coupled(smgpu_handle* h, const smgpu_quality_constraint_params* p, const smgpu_quality_constraint_halo_desc* d, int32_t on) {
-    if (!h) return fail("null handle");
-    HIP_OK(hipSetDevice(h->device));
-    if (!on) return qualityConstraintOff(h);
-    const char* api = "smgpu_set_quality_constraint_coupled";
-    const smgpu_quality_constraint_params prm = p ? *p : smgpu_quality_constraint_params{65.0, 4.0, 20.0, 2};
-    if (prm.passes < 0) return fail("smgpu_set_quality_constraint_coupled: passes < 0");
-    if (std::isnan(prm.maxNonOrtho) || std::isnan(prm.maxInternalSkewness) || std::isnan(prm.maxBoundarySkewness))
-        return fail("smgpu_set_quality_constraint_coupled: a limit is NaN");
-    if (!h->haloOn)
-        return fail("smgpu_set_quality_constraint_coupled: the engine has no halo (smgpu_halo_configure); a serial engine takes smgpu_set_quality_constraint");
+// the two entries of the coupled constraint, as qualityConstraintEnable is the serial pair's: name names the one called, in its
+// refusals; full: smgpu_set_quality_constraint_limits_coupled (10.17) with the limits of 10.16 in more and its two volume buffers
+// in d; else more is all off and d's tail null
+static int qualityConstraintCoupledEnable(smgpu_handle* h, const char* name, bool full, const smgpu_quality_constraint_params& prm, const QcMore& more,
+                                          const smgpu_quality_constraint_halo_desc_full* d) {
+    const std::string api(name);
+    const char* serial = full ? "smgpu_set_quality_constraint_limits" : "smgpu_set_quality_constraint";
+    if (prm.passes < 0) return fail(api + ": passes < 0");
+    if (std::isnan(prm.maxNonOrtho) || std::isnan(prm.maxInternalSkewness) || std::isnan(prm.maxBoundarySkewness) || std::isnan(more.minTet) ||
+        std::isnan(more.minTwist) || std::isnan(more.minTri) || std::isnan(more.minWeight) || std::isnan(more.minRatio) || std::isnan(more.minDet))
+        return fail(api + ": a limit is NaN");
+    if (!h->haloOn) return fail(api + ": the engine has no halo (smgpu_halo_configure); a serial engine takes " + serial);
     if (h->bndOn)
-        return fail("smgpu_set_quality_constraint_coupled: not available on an engine with boundary point smoothing (it rewrites the proposals of the "
+        return fail(api + ": not available on an engine with boundary point smoothing (it rewrites the proposals of the "
                     "boundary points from state that a reverted iteration would leave ahead of the points)");
-    if (h->tg.on) return fail("smgpu_set_quality_constraint_coupled: the tangle constraint is on (smgpu_set_tangle_constraint_coupled), and this constraint contains it; switch it off first");
-    if (h->iterOpen) return fail("smgpu_set_quality_constraint_coupled: between smgpu_iter_begin and smgpu_iter_end");
-    if (!d || !d->coupling || (h->nSend && !d->sendT) || (h->nRecv && !d->recvT)) return fail("smgpu_set_quality_constraint_coupled: null exchange buffer");
+    if (h->tg.on) return fail(api + ": the tangle constraint is on (smgpu_set_tangle_constraint_coupled), and this constraint contains it; switch it off first");
+    if (h->qc.on && h->qc.coupled && h->qc.full != full)
+        return fail(api + ": the quality constraint is on through " + (full ? "smgpu_set_quality_constraint_coupled" : "smgpu_set_quality_constraint_limits_coupled") +
+                    "; switch it off first");
+    if (h->iterOpen) return fail(api + ": between smgpu_iter_begin and smgpu_iter_end");
+    if (!d || !d->coupling || (h->nSend && !d->sendT) || (h->nRecv && !d->recvT)) return fail(api + ": null exchange buffer");
     const MeshView& m = h->mv;
     std::vector<int32_t> key;
     std::vector<int> procFace, slot;
     int64_t nProc = 0, notCounted = 0;
-    if (qualityCouplingTables(api, m, d->coupling, key, procFace, slot, nProc, notCounted)) return 1;
-    if (nProc > 0 && (!d->sendCc || !d->recvCc)) return fail("smgpu_set_quality_constraint_coupled: null exchange buffer");
+    if (qualityCouplingTables(name, m, d->coupling, key, procFace, slot, nProc, notCounted)) return 1;
+    if (nProc > 0 && (!d->sendCc || !d->recvCc)) return fail(api + ": null exchange buffer");
+    if (nProc > 0 && more.ratioOn && (!d->sendVc || !d->recvVc)) return fail(api + ": null exchange buffer (minVolRatio is on: sendVc / recvVc)");
     if (qualityConstraintOff(h)) return 1;
     if (flushDeferred(h)) return 1;
     if (qualityEnsure(h)) return 1;                  // owner / neighbour by face
@@ -781,6 +805,11 @@ int smgpu_set_quality_constraint_coupled(smgpu_handle* h, const smgpu_quality_co
         q.block.alloc(&q.counted, (size_t)std::max(1, h->nShared)) || q.block.alloc(&q.procFace, (size_t)std::max<int64_t>(1, nProc)) ||
         q.block.alloc(&q.slot, std::max<size_t>(1, nB)))
         return q.block.failed("the quality constraint");
+    q.more = more;
+    q.faceMore = more.tetOn || more.twistOn || more.triOn || more.weightOn || more.ratioOn;
+    q.cellMore = more.ratioOn || more.detOn;
+    if (q.cellMore && (q.block.alloc(&q.vol, nCell) || q.block.alloc(&q.exemptDet, nCell))) return q.block.failed("the quality constraint");
+    if (q.cellMore) HIP_OK(hipMemsetAsync(q.exemptDet, 0, nCell, h->stream));
     HIP_OK(hipMemsetAsync(q.dev, 0, sizeof(QcDev), h->stream));
     HIP_OK(hipMemsetAsync(q.exemptCell, 0, nCell, h->stream));
     HIP_OK(hipMemsetAsync(q.cellFlag, 0, nCell, h->stream));
@@ -799,6 +828,8 @@ int smgpu_set_quality_constraint_coupled(smgpu_handle* h, const smgpu_quality_co
     q.nProc = (int)nProc;
     q.sendT = (int*)d->sendT; q.recvT = (int*)d->recvT;
     q.sendCc = (double*)d->sendCc; q.recvCc = (double*)d->recvCc;
+    q.sendVc = (double*)d->sendVc; q.recvVc = (double*)d->recvVc;
+    q.full = full;
     // the exempt cells and faces: one evaluation of the current points, its second half behind the host's exchange of Cc
     // (the wait inside also covers the uploads from the host vectors above)
     if (qualityConstraintCoupledGeometry(h, true)) { q.release(); return 1; }
@@ -809,6 +840,32 @@ int smgpu_set_quality_constraint_coupled(smgpu_handle* h, const smgpu_quality_co
     q.pending = true;
     q.on = true;
     return 0;
+}
+int smgpu_set_quality_constraint_coupled(smgpu_handle* h, const smgpu_quality_constraint_params* p, const smgpu_quality_constraint_halo_desc* d, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityConstraintOff(h);
+    const smgpu_quality_constraint_params prm = p ? *p : smgpu_quality_constraint_params{65.0, 4.0, 20.0, 2};
+    smgpu_quality_constraint_halo_desc_full df{};
+    if (d) df = smgpu_quality_constraint_halo_desc_full{d->sendT, d->recvT, d->sendCc, d->recvCc, d->coupling, nullptr, nullptr};
+    return qualityConstraintCoupledEnable(h, "smgpu_set_quality_constraint_coupled", false, prm, qualityConstraintMore(kQcLimitsDefault), d ? &df : nullptr);
+}
+static_assert(offsetof(smgpu_quality_constraint_halo_desc_full, sendT) == offsetof(smgpu_quality_constraint_halo_desc, sendT) &&
+              offsetof(smgpu_quality_constraint_halo_desc_full, recvT) == offsetof(smgpu_quality_constraint_halo_desc, recvT) &&
+              offsetof(smgpu_quality_constraint_halo_desc_full, sendCc) == offsetof(smgpu_quality_constraint_halo_desc, sendCc) &&
+              offsetof(smgpu_quality_constraint_halo_desc_full, recvCc) == offsetof(smgpu_quality_constraint_halo_desc, recvCc) &&
+              offsetof(smgpu_quality_constraint_halo_desc_full, coupling) == offsetof(smgpu_quality_constraint_halo_desc, coupling) &&
+              offsetof(smgpu_quality_constraint_halo_desc_full, sendVc) == sizeof(smgpu_quality_constraint_halo_desc),
+              "smgpu_quality_constraint_halo_desc is the head of the full descriptor");
+int smgpu_set_quality_constraint_limits_coupled(smgpu_handle* h, const smgpu_quality_constraint_limits* p, const smgpu_quality_constraint_halo_desc_full* d,
+                                                int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityConstraintOff(h);
+    const smgpu_quality_constraint_limits l = p ? *p : kQcLimitsDefault;
+    return qualityConstraintCoupledEnable(h, "smgpu_set_quality_constraint_limits_coupled", true,
+                                          smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
+                                          qualityConstraintMore(l), d);
 }
 int smgpu_quality_constraint_coupled_exempt(smgpu_handle* h) {
     if (!h) return fail("null handle");
@@ -821,6 +878,7 @@ int smgpu_quality_constraint_coupled_exempt(smgpu_handle* h) {
     if (qualityConstraintCoupledVerdicts(h, true, &qd)) { (void)qualityConstraintOff(h); return 1; }
     q.nExemptCells = qd.t.badNow;
     q.nExemptFaces = qd.facesNow;
+    q.nExemptDet = qd.underDetNow;
     q.pending = false;
     return 0;
 }
@@ -857,7 +915,10 @@ int smgpu_quality_constraint_pass_faces(smgpu_handle* h, int64_t* nBadLocal) {
     HIP_OK(hipSetDevice(h->device));
     QcDev qd{};
     if (qualityConstraintCoupledVerdicts(h, false, &qd)) return 1;
-    if (q.k == 0) { q.n0[0] = qd.t.badNow; q.n0[1] = qd.tangledNow; q.n0[2] = qd.nonOrthoNow; q.n0[3] = qd.skewNow; }
+    if (q.k == 0) {
+        q.n0[0] = qd.t.badNow; q.n0[1] = qd.tangledNow; q.n0[2] = qd.nonOrthoNow; q.n0[3] = qd.skewNow;
+        q.n0[4] = qd.lowTetNow; q.n0[5] = qd.lowTwistNow; q.n0[6] = qd.lowTriNow; q.n0[7] = qd.lowWeightNow; q.n0[8] = qd.lowRatioNow; q.n0[9] = qd.underDetNow;
+    }
     q.stage = 2;
     *nBadLocal = qd.t.badNow;
     return 0;
@@ -869,7 +930,7 @@ int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32
     if (q.stage != 2 || q.k < 0) return fail("smgpu_quality_constraint_pass_end without smgpu_quality_constraint_pass_faces");
     if (nBadGlobal < 0) return fail("smgpu_quality_constraint_pass_end: nBadGlobal < 0");
     HIP_OK(hipSetDevice(h->device));
-    smgpu_quality_constraint_record_full* slot = nullptr;       // (its head is the record this form writes; the rest stays zero)
+    smgpu_quality_constraint_record_full* slot = nullptr;       // (10.15's entry writes its head, the rest stays zero; 10.17's all of it)
     if (q.slab.slot(q.slabUsed, &slot)) return 1;
     smgpu_quality_constraint_record* rec = reinterpret_cast<smgpu_quality_constraint_record*>(slot);
     const int nP = h->mv.nPoints;
@@ -892,8 +953,13 @@ int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32
     }
     const bool close = nBadGlobal == 0 || full;
     if (close) {
-        hipLaunchKernelGGL(k_qc_close, dim3(1), dim3(64), 0, h->stream, rec, (long long)(q.count + 1), q.reverting, full ? 1 : 0, (long long)q.n0[0],
-                           (long long)q.n0[1], (long long)q.n0[2], (long long)q.n0[3]);
+        if (q.full) {   // 10.17: the wider record
+            QcCounts c{};
+            for (int i = 0; i < 10; ++i) c.n[i] = (long long)q.n0[i];
+            hipLaunchKernelGGL(k_qc_close_full, dim3(1), dim3(64), 0, h->stream, slot, (long long)(q.count + 1), q.reverting, full ? 1 : 0, c);
+        } else
+            hipLaunchKernelGGL(k_qc_close, dim3(1), dim3(64), 0, h->stream, rec, (long long)(q.count + 1), q.reverting, full ? 1 : 0, (long long)q.n0[0],
+                               (long long)q.n0[1], (long long)q.n0[2], (long long)q.n0[3]);
         ++q.count;
         ++q.slabUsed;
         q.k = -1;

@@ -230,11 +230,15 @@ struct QualityConstraintHost {
     static constexpr int kChunk = 256;
     bool coupled = false, pending = false, slabFresh = false;
     int k = -1, stage = 0, reverting = 0, slabUsed = 0, nProc = 0;
-    int64_t count = 0, n0[4] = {0, 0, 0, 0};
+    // (under smgpu_set_quality_constraint_limits_coupled, 10.17 -- `full`: then the six counts of 10.16, and k_qc_close_full
+    // closes the record; sendVc / recvVc: the caller's volume buffers, one double per processor face, used while minVolRatio is on)
+    bool full = false;
+    int64_t count = 0, n0[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double *sendVc = nullptr, *recvVc = nullptr;
     const double* x = nullptr;
     uint8_t* counted = nullptr;
     int *procFace = nullptr, *slot = nullptr;
     int *sendT = nullptr, *recvT = nullptr;        // the caller's exchange buffers (device, nSend / nRecv int32)
     double *sendCc = nullptr, *recvCc = nullptr;   // ... (device, 3 doubles per processor face, patch order)
-    void release() { block.release(); slab.release(); coupled = pending = slabFresh = false; k = -1; stage = 0; slabUsed = 0; nProc = 0; }
+    void release() { block.release(); slab.release(); coupled = pending = slabFresh = full = false; sendVc = recvVc = nullptr; k = -1; stage = 0; slabUsed = 0; nProc = 0; }
 };

@@ -785,6 +785,25 @@ class SmoothEngine:
         d = _ffi.QualityConstraintHaloDesc(sendT or None, recvT or None, sendCc or None, recvCc or None, C.pointer(c))
         self._check(self._lib.smgpu_set_quality_constraint_coupled(self._h, C.byref(p), C.byref(d), 1))
 
+    def set_quality_constraint_limits_coupled(self, coupling, sendT, recvT, sendCc, recvCc, sendVc=0, recvVc=0, maxNonOrtho=65.0,
+                                              maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None, minTwist=None,
+                                              minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None):
+        """set_quality_constraint_coupled with the six further limits (include/smgpu.h, smgpu_set_quality_constraint_limits_coupled;
+        DESIGN.md "Mesh quality", 10.17; None: off).  sendVc / recvVc: raw device addresses of one double per processor face, needed
+        while minVolRatio is on: the call returns with sendVc packed next to sendCc, the caller moves both, and so behind every
+        quality_constraint_pass_begin."""
+        rank, pats = coupling
+        st = np.array([p[0] for p in pats], np.int32)
+        sz = np.array([p[1] for p in pats], np.int32)
+        nb = np.array([p[2] for p in pats], np.int32)
+        c = _ffi.QualityCoupling(int(rank), len(pats), _p(st, _ffi.c_i32p), _p(sz, _ffi.c_i32p), _p(nb, _ffi.c_i32p))
+        more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
+                    minVolRatio=minVolRatio, minDeterminant=minDeterminant)
+        more = {k: QUALITY_CONSTRAINT_LIMITS_OFF[k] if v is None else float(v) for k, v in more.items()}
+        p = _ffi.QualityConstraintLimits(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more)
+        d = _ffi.QualityConstraintHaloDescFull(sendT or None, recvT or None, sendCc or None, recvCc or None, C.pointer(c), sendVc or None, recvVc or None)
+        self._check(self._lib.smgpu_set_quality_constraint_limits_coupled(self._h, C.byref(p), C.byref(d), 1))
+
     def quality_constraint_coupled_exempt(self):
         """the face verdicts of the enabling evaluation, with the neighbours' cell centres in recvCc, become the exempt faces"""
         self._check(self._lib.smgpu_quality_constraint_coupled_exempt(self._h))

@@ -210,14 +210,16 @@ def combine_quality_constraint_records(per_rank):
     """the records of the undecomposed mesh from every rank's (DESIGN.md "Mesh quality", 10.15): `passes` and `fullRevert` are
     global values, the same on every rank; the counts are sums (a shared point counts on its master only, a processor face on
     the rank with the lower number)"""
-    from .engine import QualityConstraintRecordFull as QualityConstraintRecord   # (the six counts of 10.16 are 0 on a decomposed mesh)
+    from .engine import QualityConstraintRecordFull as QualityConstraintRecord   # (the six counts of 10.16 are 0 under set_quality_constraint)
     out = []
     for recs in zip(*per_rank):
         r0 = recs[0]
         assert all((r.iteration, r.passes, r.fullRevert) == (r0.iteration, r0.passes, r0.fullRevert) for r in recs), recs
         out.append(QualityConstraintRecord(iteration=r0.iteration, passes=r0.passes, fullRevert=r0.fullRevert,
                                            **{f: sum(getattr(r, f) for r in recs)
-                                              for f in ("nBadCells", "nPointsReverted", "nTangledCells", "nNonOrthoFaces", "nSkewFaces")}))
+                                              for f in ("nBadCells", "nPointsReverted", "nTangledCells", "nNonOrthoFaces", "nSkewFaces", "nLowTetFaces",
+                                                        "nLowTwistFaces", "nLowTriangleTwistFaces", "nLowWeightFaces", "nLowVolRatioFaces",
+                                                        "nUnderdeterminedCells")}))
     assert all(len(r) == len(per_rank[0]) for r in per_rank)
     return out
 
@@ -856,6 +858,19 @@ class DistributedSmoother:
         st = self.state
         if self.world > 1:
             st.recvCc.copy_(self._quality_swap(st.qcCoupling[1], st.sendCc, 3))
+            if getattr(st, "sendVc", None) is not None:         # (10.17: the owner cells' volumes ride the same move)
+                st.recvVc.copy_(self._quality_swap(st.qcCoupling[1], st.sendVc, 1))
+
+    def set_quality_constraint_limits(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
+                                      minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None):
+        """set_quality_constraint with the six further limits of engine.set_quality_constraint (None: off), on the global mesh
+        (smgpu_set_quality_constraint_limits_coupled): a processor face takes the internal branch of every face
+        criterion with the neighbour rank's cell centre and cell volume, a cell's determinant runs over its internal and its
+        processor faces.  With minVolRatio on the owner cells' volumes travel with the cell centres.  Every rank calls it, with
+        the same limits."""
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes,
+                                        dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist,
+                                             minFaceWeight=minFaceWeight, minVolRatio=minVolRatio, minDeterminant=minDeterminant))
 
     def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
         """From now on iterate() also keeps face non-orthogonality and skewness under the limits (engine.set_quality_constraint's
@@ -864,6 +879,12 @@ class DistributedSmoother:
         calls it (a collective: the exempt faces need one exchange).  more: the limits of engine.set_quality_constraint that a
         decomposed mesh does not take: one that is on is a ValueError."""
         _refuse_more_limits(more)
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, None)
+
+    def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more):
+        """the body of set_quality_constraint (more = None: smgpu_set_quality_constraint_coupled) and of
+        set_quality_constraint_limits (more: the six limits by name, smgpu_set_quality_constraint_limits_coupled)"""
+        from .engine import quality_constraint_limits_on
         torch, st, eng = self.torch, self.state, self.engine
         if self.tangle_passes is not None:
             raise RuntimeError("set_quality_constraint: the tangle constraint is on, and this constraint contains it; clear_tangle_constraint first")
@@ -876,13 +897,22 @@ class DistributedSmoother:
         st.recvT = torch.zeros(max(self.tables.nRecv, 1), dtype=torch.int32, device=self.device)
         st.sendCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
         st.recvCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
+        st.sendVc = st.recvVc = None
+        if more is not None and "minVolRatio" in quality_constraint_limits_on(**more):
+            st.sendVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
+            st.recvVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
         self.quality_passes = None
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)         # the buffers are zeroed before the engine's stream writes them
         err = None
         try:
-            eng.set_quality_constraint_coupled(coupling, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
-                                               maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes)
+            if more is None:
+                eng.set_quality_constraint_coupled(coupling, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
+                                                   maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes)
+            else:
+                eng.set_quality_constraint_limits_coupled(coupling, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
+                                                          0 if st.sendVc is None else st.sendVc.data_ptr(), 0 if st.recvVc is None else st.recvVc.data_ptr(),
+                                                          maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, **more)
         except Exception as ex:  # noqa: BLE001 -- re-raised below, on every rank
             err = ex
         self._agree_on_error(err)
@@ -904,10 +934,11 @@ class DistributedSmoother:
         """QualityConstraintState of the decomposed mesh: nExemptCells and nExemptFaces summed over the ranks (a processor face
         counts on one side).  A collective."""
         s = self.engine.quality_constraint_state()
-        t = self.torch.tensor([s.nExemptCells, s.nExemptFaces], dtype=self.torch.int64, device="cpu" if self._staged() else self.device)
+        t = self.torch.tensor([s.nExemptCells, s.nExemptFaces, s.nExemptDeterminantCells], dtype=self.torch.int64,
+                              device="cpu" if self._staged() else self.device)
         if self.world > 1:
             self.dist.all_reduce(t)
-        s.nExemptCells, s.nExemptFaces = (int(x) for x in t.tolist())
+        s.nExemptCells, s.nExemptFaces, s.nExemptDeterminantCells = (int(x) for x in t.tolist())
         return s
 
     def quality_constraint_records(self, per_rank=False):
@@ -1210,10 +1241,24 @@ class LocalMultiSmoother:
         buffers are the constraint's own, not the report's"""
         for i, off, j, ooff, size in self.ccCopies:
             self.states[i].recvCc[off:off + size].copy_(self.states[j].sendCc[ooff:ooff + size])
+            if getattr(self.states[i], "sendVc", None) is not None:         # (10.17: the owner cells' volumes ride the same move)
+                self.states[i].recvVc[off:off + size].copy_(self.states[j].sendVc[ooff:ooff + size])
+
+    def set_quality_constraint_limits(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
+                                      minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None):
+        """as DistributedSmoother.set_quality_constraint_limits; cell centres, volumes and marks move by device-side copies"""
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes,
+                                        dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist,
+                                             minFaceWeight=minFaceWeight, minVolRatio=minVolRatio, minDeterminant=minDeterminant))
 
     def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
         """as DistributedSmoother.set_quality_constraint; cell centres and marks move by device-side copies"""
         _refuse_more_limits(more)
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, None)
+
+    def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more):
+        """as DistributedSmoother._enable_quality_constraint"""
+        from .engine import quality_constraint_limits_on
         from .quality import paired_offsets
         torch = self.torch
         if self.tangle_passes is not None:
@@ -1227,12 +1272,22 @@ class LocalMultiSmoother:
             st.recvT = torch.zeros(max(st.t.nRecv, 1), dtype=torch.int32, device=self.device)
             st.sendCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
             st.recvCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
+            st.sendVc = st.recvVc = None
+            if more is not None and "minVolRatio" in quality_constraint_limits_on(**more):
+                st.sendVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
+                st.recvVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)         # the buffers are zeroed before the engines' streams write them
         try:
             for st, c in zip(self.states, couplings):
-                st.eng.set_quality_constraint_coupled(c, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
-                                                      maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes)
+                if more is None:
+                    st.eng.set_quality_constraint_coupled(c, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
+                                                          maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes)
+                else:
+                    st.eng.set_quality_constraint_limits_coupled(c, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
+                                                                 0 if st.sendVc is None else st.sendVc.data_ptr(),
+                                                                 0 if st.recvVc is None else st.recvVc.data_ptr(), maxNonOrtho, maxInternalSkewness,
+                                                                 maxBoundarySkewness, passes, **more)
             self._move_cc()
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
@@ -1253,6 +1308,7 @@ class LocalMultiSmoother:
         ss = [st.eng.quality_constraint_state() for st in self.states]
         ss[0].nExemptCells = sum(s.nExemptCells for s in ss)
         ss[0].nExemptFaces = sum(s.nExemptFaces for s in ss)
+        ss[0].nExemptDeterminantCells = sum(s.nExemptDeterminantCells for s in ss)
         return ss[0]
 
     def quality_constraint_records(self, per_rank=False):
