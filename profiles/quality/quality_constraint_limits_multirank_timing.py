@@ -13,8 +13,8 @@ alternates the legs in pairs and swaps the order in every second pair.
     local STEPS LEG:    the same through LocalMultiSmoother on the two halves, 100 x 100 x 50 cells each, of a hex block.
     kernels:            under `rocprofv3 --kernel-trace --stats` (profiles/quality/README.md), no counters, one process: those
                         halves with all nine criteria on for a few iterations, and then the serial constraint under the same
-                        limits on one half as a mesh of its own, for k_qc_faces_more beside k_qc_faces_more_coupled and
-                        k_qc_cells_more beside k_qc_cells_more_coupled."""
+                        limits on one half as a mesh of its own, for k_qc_faces_more<..., false> beside k_qc_faces_more<..., true> and
+                        k_qc_cells_more<..., false> beside k_qc_cells_more<..., true>."""
 import os
 import socket
 import sys

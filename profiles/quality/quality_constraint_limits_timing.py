@@ -4,8 +4,8 @@
     kernels:   run under `rocprofv3 --kernel-trace --stats` (profiles/quality/README.md), no counters, one process: one engine on
                cavity_mesh(N) with the reference's constraints off.  The three reports once (k_quality_faces,
                k_quality_motion_faces, k_quality_geom_faces, k_quality_geom_cells: the yardsticks), four iterations under the
-               quality constraint with its three limits (k_qc_faces), four with all six new limits on (k_qc_cells_more<true>,
-               k_qc_faces_more<true, true>, k_qc_verdict_more).
+               quality constraint with its three limits (k_qc_faces<false>), four with all six new limits on (k_qc_cells_more<true, false>,
+               k_qc_faces_more<true, true, false>, k_qc_verdict).
     overhead:  no profiler: ms per iteration of iterate(STEPS) with the reference's constraints on (configs[3]), in alternating
                pairs on one engine, the order swapped in every second pair.  The "off" run of a pair is the quality constraint
                with its three limits at their defaults through the old entry; the "on" run is (a) the new entry with all six off,

@@ -12,7 +12,7 @@ the legs in pairs and swaps the order in every second pair.
     kernels:            under `rocprofv3 --kernel-trace --stats` (profiles/quality/README.md), no counters, one process: those
                         halves with passes = 1 and one point next to the processor plane folded through its cells -- a marked pass
                         and the full revert behind it -- and then the serial constraint on one half as a mesh of its own, for
-                        k_qc_faces beside k_qc_faces_coupled."""
+                        k_qc_faces<false> beside k_qc_faces<true>."""
 import os
 import socket
 import sys

@@ -4,7 +4,7 @@ constraint costs per iteration.
     kernels:   run under `rocprofv3 --kernel-trace --stats` (profiles/quality/README.md), no counters, one process: one engine on
                cavity_mesh(N) with the reference's constraints off and a trace at every iteration.  Four iterations with the
                tangle constraint on, then four with the quality constraint on at its default limits: k_tangle_tile,
-               k_quality_geom_tile and k_quality_faces (the yardsticks, the parent's code paths) and k_qc_tile, k_qc_faces,
+               k_quality_geom_tile and k_quality_faces (the yardsticks, the parent's code paths) and k_qc_tile, k_qc_faces<false>,
                k_qc_cells, k_qc_verdict run on the same mesh in the same process.
     overhead:  no profiler: ms per iteration of iterate(STEPS) with the reference's constraints on (configs[3]), in alternating
                off / on pairs on one engine with the order swapped in every second pair, the number of iterations with a bad element printed (0 on this mesh): the quality

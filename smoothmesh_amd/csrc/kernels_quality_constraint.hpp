@@ -12,14 +12,20 @@
 //      value) and counts, one integer atomic per workgroup and criterion;
 //   3. k_qc_cells: one lane per cell: the byte of step 1, the flag of step 2 (cleared here), the marks of the points of a bad
 //      cell's faces by k_tangle_cells' loop, |B| and the tangled cells, one integer atomic per workgroup each;
-//   4. k_qc_verdict: k_tangle_verdict's twin with the wider record and the stop word;
+//   4. k_qc_verdict: k_tangle_verdict's twin with the wider record, the wider device words and the stop word;
 //   5. k_tangle_apply itself: the record and the device words begin with the tangle constraint's (static_asserts below).
 // Without tiles (SMGPU_TILES=0) step 1 is k_qc_open + k_face_geom + k_cell_centres on the constraint's cell centres and stop
 // word (set while the iteration did not run or a pass was clean), and k_qc_cells forms 10.12's verdict itself with k_tangle_cells'
 // arithmetic: identical points and records.
 // No float atomics; every store is a plain vector store; every kernel takes the trace's gate (qTraceRan) and the clean word.
 // With a limit of 10.16 on (smgpu_set_quality_constraint_limits) kernels_quality_limits.hpp puts a cell pass in front of step 2
-// and its own kernels in the place of steps 2 and 4; with none on the sequence is the one above.
+// and its own face kernel in the place of step 2; with none on the sequence is the one above.
+//
+// The coupled form (smgpu_set_quality_constraint_coupled, DESIGN.md "Mesh quality", 10.15 and 10.17): a sub-domain of a decomposed
+// mesh.  The kernels are the ones above, instantiated with Coupled = true where a processor face changes a line, and ungated
+// (gate = NULL, pass = 0): step 1, then k_quality_pack of the constraint's own cell centres; the host moves them; then
+// k_qc_faces<true>, k_qc_cells, k_tangle_pack.  The verdict is the host's, on the count summed over the ranks, as in 10.13:
+// k_tangle_combine, k_tangle_apply_counted, k_qc_close.
 #pragma once
 #include <cstddef>
 
@@ -46,8 +52,29 @@ static_assert(offsetof(smgpu_quality_constraint_record, iteration) == offsetof(s
               offsetof(smgpu_quality_constraint_record, nPointsReverted) == offsetof(smgpu_tangle_record, nPointsReverted),
               "k_tangle_apply adds nPointsReverted through a smgpu_tangle_record*");
 
+static_assert(offsetof(smgpu_quality_constraint_record_full, nSkewFaces) == offsetof(smgpu_quality_constraint_record, nSkewFaces) &&
+              offsetof(smgpu_quality_constraint_record_full, nLowTetFaces) == sizeof(smgpu_quality_constraint_record),
+              "the narrow record is the head of the full one: smgpu_get_quality_constraint_records copies it out of the full slots");
+
 // the limits as the kernels test them; a criterion that is off never fires
 struct QcLimits { double cosT, maxInternalSkew, maxBoundarySkew; int nonOrthoOn, internalSkewOn, boundarySkewOn; };
+
+// What a sub-domain changes for a face kernel (QCoupling<true>, kernels_quality.hpp: 10.4's slot table, decoded as qNeighbour
+// decodes it, and the neighbour rank's cell centres and volumes in patch order).  qcSlot: -1 for an internal or a physical
+// boundary face, else the processor face's place in recvCc / recvVc, | kQualityNotCounted on the side with myRank > neighbRank.
+// Serial, it is the constant -1, and what the kernels derive from it folds to the serial lines: `internal` (an internal face of
+// the global mesh) is `inner` (both cells are this rank's), every face is counted.
+template <bool Coupled>
+__device__ __forceinline__ int qcSlot(const MeshView& m, const QCoupling<Coupled>& cp, int f) {
+    if constexpr (Coupled) return f < m.nInternalFaces ? -1 : cp.slot[f - m.nInternalFaces];
+    else return -1;
+}
+// C_N of face f, valid where the face is internal to the global mesh: the neighbour cell's, or across a processor face recvCc's
+template <bool Coupled>
+__device__ __forceinline__ V3 qcNeighbourCentre(const double* __restrict__ cellCtr, const QCoupling<Coupled>& cp, bool inner, int n, int sl) {
+    if constexpr (Coupled) return inner ? ldv(cellCtr, n) : (sl >= 0 ? ldv(cp.recvCc, sl & kQualitySlotMask) : v3(0, 0, 0));
+    else return inner ? ldv(cellCtr, n) : v3(0, 0, 0);
+}
 
 // The geometry tile of s.ptsCur with writeFaces and the cell centres (s.cellCtr: the constraint's own buffer) -- the body of
 // k_quality_geom_tile (kernels_quality_trace.hpp) up to geomCell: no stop word of the loop, no deferred finish, wantAvg = 0 -- then
@@ -118,30 +145,38 @@ __device__ __forceinline__ void qcFace(const MeshView& m, const double* __restri
 }
 
 // exemptOut != NULL (enabling): every face's verdict goes to exemptOut[f], no cell is flagged, facesNow counts the exempt faces.
+// Coupled: a processor face is an internal face of the global mesh: qcFace with internal = true and C_N from recvCc, the two
+// internal limits, the flag on its owner (the neighbour cell is the other rank's, which judges the face itself), and the counts
+// only on the counted side.  Lanes of internal and physical faces take the serial path.
 constexpr int kQcBlock = 256;
+template <bool Coupled>
 __global__ void __launch_bounds__(kQcBlock) k_qc_faces(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
                                                         const double* __restrict__ fArea, const double* __restrict__ cellCtr,
-                                                        const int* __restrict__ own, const int* __restrict__ nei, QcLimits lim,
+                                                        const int* __restrict__ own, const int* __restrict__ nei, QCoupling<Coupled> cp, QcLimits lim,
                                                         const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
                                                         uint8_t* __restrict__ cellFlag, QcDev* __restrict__ d, int pass, const smgpu_iter_stats* gate) {
     if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
     const int f = blockIdx.x * kQcBlock + threadIdx.x;
-    bool badNO = false, badSk = false;
+    bool badNO = false, badSk = false, counted = true;
     if (f < m.nFaces) {
-        const bool internal = f < m.nInternalFaces;
-        const int o = own[f], n = internal ? nei[f] : 0;
+        const bool inner = f < m.nInternalFaces;
+        const int sl = qcSlot(m, cp, f);
+        const bool internal = inner || sl >= 0;
+        const int o = own[f], n = inner ? nei[f] : 0;
+        counted = sl < 0 || !(sl & kQualityNotCounted);
         double ortho, skew;
-        qcFace(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, o), internal, internal ? ldv(cellCtr, n) : v3(0, 0, 0), f, ortho, skew);
+        qcFace(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, o), internal, qcNeighbourCentre(cellCtr, cp, inner, n, sl), f, ortho, skew);
         badNO = internal && lim.nonOrthoOn && ortho < lim.cosT;
         badSk = internal ? (lim.internalSkewOn && skew > lim.maxInternalSkew) : (lim.boundarySkewOn && skew > lim.maxBoundarySkew);
         if (exemptOut) exemptOut[f] = (badNO || badSk) ? 1 : 0;
         else if (exempt[f]) badNO = badSk = false;
         if ((badNO || badSk) && !exemptOut) {
             cellFlag[o] = 1;
-            if (internal) cellFlag[n] = 1;
+            if (inner) cellFlag[n] = 1;
         }
     }
-    const int nNO = __syncthreads_count(badNO ? 1 : 0), nSk = __syncthreads_count(badSk ? 1 : 0), nAny = __syncthreads_count((badNO || badSk) ? 1 : 0);
+    const int nNO = __syncthreads_count((badNO && counted) ? 1 : 0), nSk = __syncthreads_count((badSk && counted) ? 1 : 0),
+              nAny = __syncthreads_count(((badNO || badSk) && counted) ? 1 : 0);
     if (threadIdx.x == 0) {
         if (nNO > 0) atomicAdd(&d->nonOrthoNow, nNO);
         if (nSk > 0) atomicAdd(&d->skewNow, nSk);
@@ -208,17 +243,22 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_cells(MeshView m, const double*
 }
 
 // k_tangle_verdict's twin: one wave, lane 0 writes everything in plain C++.  It also keeps the stop word of the next pass's
-// geometry launch.  rec: the iteration's slot of the call's record slab (zeroed by the call).
-__global__ void __launch_bounds__(64) k_qc_verdict(QcDev* __restrict__ d, Accum* __restrict__ acc, smgpu_quality_constraint_record* __restrict__ rec,
+// geometry launch.  rec: the iteration's slot of the call's record slab (zeroed by the call).  The six words of 10.16 are 0 while
+// none of its limits is on, and so are the record's six counts.
+__global__ void __launch_bounds__(64) k_qc_verdict(QcDev* __restrict__ d, Accum* __restrict__ acc, smgpu_quality_constraint_record_full* __restrict__ rec,
                                                     long long number, int pass, int passes, const smgpu_iter_stats* gate) {
     if (threadIdx.x != 0) return;
     if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
     const int nBad = d->t.badNow, nTangled = d->tangledNow, nNO = d->nonOrthoNow, nSk = d->skewNow;
+    const int nTet = d->lowTetNow, nTw = d->lowTwistNow, nTri = d->lowTriNow, nW = d->lowWeightNow, nR = d->lowRatioNow, nDet = d->underDetNow;
     d->t.badNow = 0; d->tangledNow = 0; d->nonOrthoNow = 0; d->skewNow = 0; d->facesNow = 0;
+    d->lowTetNow = 0; d->lowTwistNow = 0; d->lowTriNow = 0; d->lowWeightNow = 0; d->lowRatioNow = 0; d->underDetNow = 0;
     if (pass == 0) {
-        smgpu_quality_constraint_record r;
+        smgpu_quality_constraint_record_full r;
         r.iteration = number; r.passes = 0; r.fullRevert = 0; r.nBadCells = nBad; r.nPointsReverted = 0;
         r.nTangledCells = nTangled; r.nNonOrthoFaces = nNO; r.nSkewFaces = nSk;
+        r.nLowTetFaces = nTet; r.nLowTwistFaces = nTw; r.nLowTriangleTwistFaces = nTri; r.nLowWeightFaces = nW; r.nLowVolRatioFaces = nR;
+        r.nUnderdeterminedCells = nDet;
         *rec = r;
     }
     if (nBad == 0) { d->t.clean = 1; d->t.full = 0; acc->stop = 1; return; }
@@ -227,63 +267,26 @@ __global__ void __launch_bounds__(64) k_qc_verdict(QcDev* __restrict__ d, Accum*
     else { d->t.full = 0; rec->passes += 1; }
 }
 
-// ---- the coupled form (smgpu_set_quality_constraint_coupled, DESIGN.md "Mesh quality", 10.15): a sub-domain of a decomposed mesh ----
-// The evaluation is the one above, ungated (gate = NULL, pass = 0): k_qc_tile (or k_qc_open + the direct geometry kernels), then
-// k_quality_pack of the constraint's own cell centres; the host moves them; then k_qc_faces_coupled, k_qc_cells, k_tangle_pack.
-// The verdict is the host's, on the count summed over the ranks, as in 10.13: k_tangle_combine, k_tangle_apply_counted, k_qc_close.
-
-// k_qc_faces on a sub-domain.  slot[f - nInternalFaces]: 10.4's table (-1: a physical boundary face; else the face's place in
-// recvCc, | kQualityNotCounted on the side with myRank > neighbRank), decoded as qNeighbour decodes it.  A processor face is an
-// internal face of the global mesh: qcFace with internal = true and C_N from recvCc, the two internal limits, the flag on its
-// owner (the neighbour cell is the other rank's, which judges the face itself), and the counts only on the counted side.  Lanes of
-// internal and physical faces take k_qc_faces' path.  exemptOut != NULL: as k_qc_faces.
-__global__ void __launch_bounds__(kQcBlock) k_qc_faces_coupled(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
-                                                                const double* __restrict__ fArea, const double* __restrict__ cellCtr,
-                                                                const int* __restrict__ own, const int* __restrict__ nei,
-                                                                const int* __restrict__ slot, const double* __restrict__ recvCc, QcLimits lim,
-                                                                const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
-                                                                uint8_t* __restrict__ cellFlag, QcDev* __restrict__ d) {
-    const int f = blockIdx.x * kQcBlock + threadIdx.x;
-    bool badNO = false, badSk = false, counted = true;
-    if (f < m.nFaces) {
-        const bool inner = f < m.nInternalFaces;
-        const int sl = inner ? -1 : slot[f - m.nInternalFaces];
-        const bool internal = inner || sl >= 0;
-        const int o = own[f], n = inner ? nei[f] : 0;
-        counted = sl < 0 || !(sl & kQualityNotCounted);
-        const V3 CN = inner ? ldv(cellCtr, n) : (sl >= 0 ? ldv(recvCc, sl & kQualitySlotMask) : v3(0, 0, 0));
-        double ortho, skew;
-        qcFace(m, pts, ldv(fCtr, f), ldv(fArea, f), ldv(cellCtr, o), internal, CN, f, ortho, skew);
-        badNO = internal && lim.nonOrthoOn && ortho < lim.cosT;
-        badSk = internal ? (lim.internalSkewOn && skew > lim.maxInternalSkew) : (lim.boundarySkewOn && skew > lim.maxBoundarySkew);
-        if (exemptOut) exemptOut[f] = (badNO || badSk) ? 1 : 0;
-        else if (exempt[f]) badNO = badSk = false;
-        if ((badNO || badSk) && !exemptOut) {
-            cellFlag[o] = 1;
-            if (inner) cellFlag[n] = 1;
-        }
-    }
-    const int nNO = __syncthreads_count((badNO && counted) ? 1 : 0), nSk = __syncthreads_count((badSk && counted) ? 1 : 0),
-              nAny = __syncthreads_count(((badNO || badSk) && counted) ? 1 : 0);
-    if (threadIdx.x == 0) {
-        if (nNO > 0) atomicAdd(&d->nonOrthoNow, nNO);
-        if (nSk > 0) atomicAdd(&d->skewNow, nSk);
-        if (nAny > 0) atomicAdd(&d->facesNow, nAny);
-    }
-}
-
-// k_tangle_close's twin: closes the record of an iteration from the host's verdict; one wave, lane 0 writes every word in plain
-// C++ (nPointsReverted is the applies': the slot was zeroed before the iteration's first pass).
-__global__ void __launch_bounds__(64) k_qc_close(smgpu_quality_constraint_record* __restrict__ rec, long long number, int passes, int fullRevert,
-                                                  long long nBadCells, long long nTangledCells, long long nNonOrthoFaces, long long nSkewFaces) {
+// k_tangle_close's twin: closes the record of an iteration of the coupled form from the host's verdict.  n: the rank's ten counts
+// at k = 0 in the record's order from nBadCells on, without nPointsReverted (the applies': the slot was zeroed before the
+// iteration's first pass).  One wave, lane 0 writes every word in plain C++.
+struct QcCounts { long long n[10]; };
+__global__ void __launch_bounds__(64) k_qc_close(smgpu_quality_constraint_record_full* __restrict__ rec, long long number, int passes, int fullRevert,
+                                                  QcCounts c) {
     if (threadIdx.x != 0) return;
     rec->iteration = number;
     rec->passes = passes;
     rec->fullRevert = fullRevert;
-    rec->nBadCells = nBadCells;
-    rec->nTangledCells = nTangledCells;
-    rec->nNonOrthoFaces = nNonOrthoFaces;
-    rec->nSkewFaces = nSkewFaces;
+    rec->nBadCells = c.n[0];
+    rec->nTangledCells = c.n[1];
+    rec->nNonOrthoFaces = c.n[2];
+    rec->nSkewFaces = c.n[3];
+    rec->nLowTetFaces = c.n[4];
+    rec->nLowTwistFaces = c.n[5];
+    rec->nLowTriangleTwistFaces = c.n[6];
+    rec->nLowWeightFaces = c.n[7];
+    rec->nLowVolRatioFaces = c.n[8];
+    rec->nUnderdeterminedCells = c.n[9];
 }
 
 }  // namespace smgpu

@@ -11,10 +11,22 @@
 //      and skew_f by qcFace's lines, the new values from the same loads of C_f, S_f, C_O, C_N; with Walk the skewness loop and
 //      qmFaceOne's first walk are one loop that reads every vertex once (the base-point walk is not in it); with Ratio the two
 //      volumes are read.  A criterion that is off costs no loads: which walk and which loads run is a template parameter, which
-//      verdicts count an argument uniform over the launch;
-//   c. k_qc_verdict_more: k_qc_verdict's twin with the wider record and the wider device words.
-// k_qc_cells and k_tangle_apply run as they are.  No float atomics; every store is a plain vector store; every kernel takes the
-// trace's gate (qTraceRan) and the clean word.
+//      verdicts count an argument uniform over the launch.
+// k_qc_cells, k_qc_verdict and k_tangle_apply run as they are.  No float atomics; every store is a plain vector store; every
+// kernel takes the trace's gate (qTraceRan) and the clean word.
+//
+// On a sub-domain of a decomposed mesh (smgpu_set_quality_constraint_limits_coupled, 10.17) the two kernels are instantiated with
+// Coupled = true and run ungated (they compile no gate test: pass and gate are the serial form's), in the two halves of 10.15's
+// evaluation:
+//   first half, behind k_qc_tile (or the direct geometry kernels), in front of the packs: k_qc_cells_more<Det, true>, the
+//     determinant over the cell's internal and processor faces (the constraint's own slot table).  The byte it leaves in cellFlag
+//     waits for k_qc_cells of the second half, underDetNow for the host's read of QcDev there; then k_quality_pack_volumes
+//     (kernels_quality_geom.hpp) of the constraint's own volumes into sendVc, only when minVolRatio is on;
+//   second half, behind the host's move of Cc and Vc: k_qc_faces_more<Walk, Ratio, true> in the place of k_qc_faces<true>: a
+//     processor face takes the internal branch of every criterion with C_N from recvCc and V_N from recvVc, flags its owner only,
+//     and counts only on the counted side.
+// Every difference between the two forms is an `if constexpr (Coupled)` of the helpers qcSlot, qcNeighbourCentre
+// (kernels_quality_constraint.hpp), qcCounts and qcNeighbourVolume: the serial instantiation compiles the serial lines alone.
 #pragma once
 #include "kernels_quality_constraint.hpp"
 #include "kernels_quality_geom.hpp"
@@ -22,20 +34,32 @@
 
 namespace smgpu {
 
-static_assert(offsetof(smgpu_quality_constraint_record_full, nSkewFaces) == offsetof(smgpu_quality_constraint_record, nSkewFaces) &&
-              offsetof(smgpu_quality_constraint_record_full, nLowTetFaces) == sizeof(smgpu_quality_constraint_record),
-              "the narrow record is the head of the full one: k_qc_verdict, k_qc_close and k_tangle_apply write through it");
-
 // the limits as the kernels test them; k: the tets' normalisation, formed by the host as the motion report forms it
 struct QcMore { double minTet, minTwist, minTri, minWeight, minRatio, minDet, k; int tetOn, twistOn, triOn, weightOn, ratioOn, detOn; };
 
+// does face f enter a cell's determinant: an internal face of the global mesh -- on a sub-domain qgcCounts
+// (kernels_quality_geom.hpp), without processor faces the same bits
+template <bool Coupled>
+__device__ __forceinline__ bool qcCounts(const MeshView& m, const QCoupling<Coupled>& cp, int f) {
+    if constexpr (Coupled) return qgcCounts(m, cp.slot, f);
+    else return f < m.nInternalFaces;
+}
+// V_N of a face that is internal to the global mesh: the neighbour cell's, or across a processor face recvVc's
+template <bool Coupled>
+__device__ __forceinline__ double qcNeighbourVolume(const double* __restrict__ vol, const QCoupling<Coupled>& cp, bool inner, int n, int sl) {
+    if constexpr (Coupled) return inner ? vol[n] : cp.recvVc[sl & kQualitySlotMask];
+    else return vol[n];
+}
+
 // V_c into vol and det_c of cell c: qgCellOne's lines (kernels_quality_geom.hpp), nothing else of it -- keep them alike.
 // exemptOut != NULL (enabling): the determinant verdict goes to exemptOut[c], no cell is flagged, underDetNow counts them.
-template <bool Det>
-__global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea, QcMore lim,
-                                                             double* __restrict__ vol, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
+template <bool Det, bool Coupled>
+__global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea,
+                                                             QCoupling<Coupled> cp, QcMore lim, double* __restrict__ vol, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
                                                              uint8_t* __restrict__ cellFlag, QcDev* __restrict__ d, int pass, const smgpu_iter_stats* gate) {
-    if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
+    if constexpr (!Coupled) {   // (the coupled form is never gated, and the test cost it 0.05 - 0.2 %: profiles/quality/README.md)
+        if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
+    }
     const int c = blockIdx.x * kQcBlock + threadIdx.x;
     bool bad = false;
     if (c < m.nCells) {
@@ -52,7 +76,7 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const do
             double p = dot(Sf, ldv(fCtr, f) - cEst);
             if (ev < 0) p = -p;
             pyr += p;
-            if (Det && f < m.nInternalFaces) { sumA += mag(Sf); ++nInt; }
+            if (Det && qcCounts(m, cp, f)) { sumA += mag(Sf); ++nInt; }
         }
         vol[c] = (1.0 / 3.0) * pyr;
         if constexpr (Det) {
@@ -62,7 +86,7 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const do
                 double xx = 0.0, xy = 0.0, xz = 0.0, yy = 0.0, yz = 0.0, zz = 0.0;
                 for (int j = b; j < e; ++j) {
                     const int f = m.cfVal[j] & 0x7fffffff;
-                    if (f >= m.nInternalFaces) continue;
+                    if (!qcCounts(m, cp, f)) continue;
                     const V3 s = ldv(fArea, f) / avgA;
                     xx += s.x * s.x; xy += s.x * s.y; xz += s.x * s.z;
                     yy += s.y * s.y; yz += s.y * s.z; zz += s.z * s.z;
@@ -85,20 +109,26 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const do
 
 // k_qc_faces with the new face criteria.  The lines up to fd are qcFace's, the walk is qmFaceOne's first walk with the skewness
 // loop's line in it (both read the vertices in the face's order; fmax and fmin do not depend on it), weight and ratio are
-// qgFaceOne's lines: keep each alike.  exemptOut != NULL (enabling): as k_qc_faces.
-template <bool Walk, bool Ratio>
+// qgFaceOne's lines: keep each alike.  exemptOut != NULL (enabling): as k_qc_faces.  Coupled: the slot is decoded as k_qc_faces
+// decodes it; `internal` is "internal face of the global mesh", `inner` "both cells are this rank's".
+template <bool Walk, bool Ratio, bool Coupled>
 __global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
                                                              const double* __restrict__ fArea, const double* __restrict__ cellCtr,
                                                              const double* __restrict__ vol, const int* __restrict__ own, const int* __restrict__ nei,
-                                                             QcLimits lim, QcMore more, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
+                                                             QCoupling<Coupled> cp, QcLimits lim, QcMore more, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
                                                              uint8_t* __restrict__ cellFlag, QcDev* __restrict__ d, int pass, const smgpu_iter_stats* gate) {
-    if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
+    if constexpr (!Coupled) {   // (the coupled form is never gated, and the test cost it 0.05 - 0.2 %: profiles/quality/README.md)
+        if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
+    }
     const int f = blockIdx.x * kQcBlock + threadIdx.x;
-    bool badNO = false, badSk = false, badTet = false, badTw = false, badTri = false, badW = false, badR = false;
+    bool badNO = false, badSk = false, badTet = false, badTw = false, badTri = false, badW = false, badR = false, counted = true;
     if (f < m.nFaces) {
-        const bool internal = f < m.nInternalFaces;
-        const int o = own[f], n = internal ? nei[f] : 0;
-        const V3 Cf = ldv(fCtr, f), Sf = ldv(fArea, f), CO = ldv(cellCtr, o), CN = internal ? ldv(cellCtr, n) : v3(0, 0, 0);
+        const bool inner = f < m.nInternalFaces;
+        const int sl = qcSlot(m, cp, f);
+        const bool internal = inner || sl >= 0;
+        counted = sl < 0 || !(sl & kQualityNotCounted);
+        const int o = own[f], n = inner ? nei[f] : 0;
+        const V3 Cf = ldv(fCtr, f), Sf = ldv(fArea, f), CO = ldv(cellCtr, o), CN = qcNeighbourCentre(cellCtr, cp, inner, n, sl);
         const double magSf = mag(Sf);
         const V3 Cpf = Cf - CO;
         V3 dd;
@@ -161,7 +191,7 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const do
             const double w = fmin(dO, dN) / ((dO + dN) + SMGPU_VSMALL);
             badW = more.weightOn && w < more.minWeight;
             if constexpr (Ratio) {
-                const double vO = vol[o], vN = vol[n];
+                const double vO = vol[o], vN = qcNeighbourVolume(vol, cp, inner, n, sl);
                 const double r = fmin(vO, vN) / (fmax(vO, vN) + SMGPU_VSMALL);
                 badR = more.ratioOn && r < more.minRatio;
             }
@@ -171,17 +201,18 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const do
         else if (exempt[f]) badNO = badSk = badTet = badTw = badTri = badW = badR = false;
         else if (any) {
             cellFlag[o] = 1;
-            if (internal) cellFlag[n] = 1;
+            if (inner) cellFlag[n] = 1;
         }
     }
     const bool any = badNO || badSk || badTet || badTw || badTri || badW || badR;
-    const int nNO = __syncthreads_count(badNO ? 1 : 0), nSk = __syncthreads_count(badSk ? 1 : 0), nAny = __syncthreads_count(any ? 1 : 0);
+    const int nNO = __syncthreads_count((badNO && counted) ? 1 : 0), nSk = __syncthreads_count((badSk && counted) ? 1 : 0),
+              nAny = __syncthreads_count((any && counted) ? 1 : 0);
     int nTet = 0, nTw = 0, nTri = 0, nW = 0, nR = 0;
-    if (Walk && more.tetOn) nTet = __syncthreads_count(badTet ? 1 : 0);
-    if (Walk && more.twistOn) nTw = __syncthreads_count(badTw ? 1 : 0);
-    if (Walk && more.triOn) nTri = __syncthreads_count(badTri ? 1 : 0);
-    if (more.weightOn) nW = __syncthreads_count(badW ? 1 : 0);
-    if (Ratio && more.ratioOn) nR = __syncthreads_count(badR ? 1 : 0);
+    if (Walk && more.tetOn) nTet = __syncthreads_count((badTet && counted) ? 1 : 0);
+    if (Walk && more.twistOn) nTw = __syncthreads_count((badTw && counted) ? 1 : 0);
+    if (Walk && more.triOn) nTri = __syncthreads_count((badTri && counted) ? 1 : 0);
+    if (more.weightOn) nW = __syncthreads_count((badW && counted) ? 1 : 0);
+    if (Ratio && more.ratioOn) nR = __syncthreads_count((badR && counted) ? 1 : 0);
     if (threadIdx.x == 0) {
         if (nNO > 0) atomicAdd(&d->nonOrthoNow, nNO);
         if (nSk > 0) atomicAdd(&d->skewNow, nSk);
@@ -192,29 +223,6 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const do
         if (nW > 0) atomicAdd(&d->lowWeightNow, nW);
         if (nR > 0) atomicAdd(&d->lowRatioNow, nR);
     }
-}
-
-// k_qc_verdict's twin with the wider record: one wave, lane 0 writes everything in plain C++
-__global__ void __launch_bounds__(64) k_qc_verdict_more(QcDev* __restrict__ d, Accum* __restrict__ acc, smgpu_quality_constraint_record_full* __restrict__ rec,
-                                                         long long number, int pass, int passes, const smgpu_iter_stats* gate) {
-    if (threadIdx.x != 0) return;
-    if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
-    const int nBad = d->t.badNow, nTangled = d->tangledNow, nNO = d->nonOrthoNow, nSk = d->skewNow;
-    const int nTet = d->lowTetNow, nTw = d->lowTwistNow, nTri = d->lowTriNow, nW = d->lowWeightNow, nR = d->lowRatioNow, nDet = d->underDetNow;
-    d->t.badNow = 0; d->tangledNow = 0; d->nonOrthoNow = 0; d->skewNow = 0; d->facesNow = 0;
-    d->lowTetNow = 0; d->lowTwistNow = 0; d->lowTriNow = 0; d->lowWeightNow = 0; d->lowRatioNow = 0; d->underDetNow = 0;
-    if (pass == 0) {
-        smgpu_quality_constraint_record_full r;
-        r.iteration = number; r.passes = 0; r.fullRevert = 0; r.nBadCells = nBad; r.nPointsReverted = 0;
-        r.nTangledCells = nTangled; r.nNonOrthoFaces = nNO; r.nSkewFaces = nSk;
-        r.nLowTetFaces = nTet; r.nLowTwistFaces = nTw; r.nLowTriangleTwistFaces = nTri; r.nLowWeightFaces = nW; r.nLowVolRatioFaces = nR;
-        r.nUnderdeterminedCells = nDet;
-        *rec = r;
-    }
-    if (nBad == 0) { d->t.clean = 1; d->t.full = 0; acc->stop = 1; return; }
-    d->t.clean = 0;
-    if (pass == passes) { d->t.full = 1; rec->fullRevert = 1; }
-    else { d->t.full = 0; rec->passes += 1; }
 }
 
 }  // namespace smgpu

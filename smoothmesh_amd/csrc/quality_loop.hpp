@@ -429,6 +429,27 @@ int smgpu_tangle_pass_begin(smgpu_handle* h, int64_t* nBadLocal) {
     *nBadLocal = td.badNow;
     return 0;
 }
+// The revert of a pass that found bad cells somewhere, for the two coupled constraints: unless the revert is the full one, the
+// marks the other ranks sent for the shared points (recvT) join this rank's and the pass counts as a reverting one; then the marked
+// points -- all of them when full -- go back to x.  rec: the iteration's record, whose head is the tangle constraint's.
+static int coupledRevert(smgpu_handle* h, bool full, const int* recvT, uint8_t* marks, const double* x, const uint8_t* counted, smgpu_tangle_record* rec,
+                         int& reverting) {
+    const int nP = h->mv.nPoints;
+    if (!full) {
+        if (computeAfterExch(h)) return 1;      // exchange T has been enqueued by the host
+        if (h->nShared > 0 && h->nRecv > 0)
+            hipLaunchKernelGGL(k_tangle_combine, dim3((h->nShared + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, h->nShared,
+                               (const int*)h->dSharedLocal, (const int*)h->dCombOff, (const int*)h->dCombSlots, recvT, marks);
+        ++reverting;
+    }
+    const int grid = std::max(1, (int)(((int64_t)nP + kTangleCountedPts - 1) / kTangleCountedPts));
+    hipLaunchKernelGGL(k_tangle_apply_counted, dim3(grid), dim3(kTangleBlock), 0, h->stream, x, h->st.ptsCur, marks, nP, full ? 1 : 0, (const int*)h->dSharedSlot,
+                       counted, rec);
+    // points went back: the geometry smgpu_iter_ahead left for the next iteration is that of other points
+    h->geomAheadDone = false;
+    h->q.epoch++;
+    return 0;
+}
 int smgpu_tangle_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done) {
     if (!h || !done) return fail("null argument");
     TangleHost& t = h->tg;
@@ -438,23 +459,8 @@ int smgpu_tangle_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done) {
     HIP_OK(hipSetDevice(h->device));
     smgpu_tangle_record* rec = nullptr;
     if (t.slab.slot(t.slabUsed, &rec)) return 1;
-    const int nP = h->mv.nPoints;
     const bool full = nBadGlobal > 0 && t.k == t.passes;
-    if (nBadGlobal > 0) {
-        if (!full) {
-            if (computeAfterExch(h)) return 1;      // exchange T has been enqueued by the host
-            if (h->nShared > 0 && h->nRecv > 0)
-                hipLaunchKernelGGL(k_tangle_combine, dim3((h->nShared + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, h->nShared,
-                                   (const int*)h->dSharedLocal, (const int*)h->dCombOff, (const int*)h->dCombSlots, (const int*)t.recvT, t.marks);
-            ++t.reverting;
-        }
-        const int grid = std::max(1, (int)(((int64_t)nP + kTangleCountedPts - 1) / kTangleCountedPts));
-        hipLaunchKernelGGL(k_tangle_apply_counted, dim3(grid), dim3(kTangleBlock), 0, h->stream, t.x, h->st.ptsCur, t.marks, nP, full ? 1 : 0,
-                           (const int*)h->dSharedSlot, (const uint8_t*)t.counted, rec);
-        // points went back: the geometry smgpu_iter_ahead left for the next iteration is that of other points
-        h->geomAheadDone = false;
-        h->q.epoch++;
-    }
+    if (nBadGlobal > 0 && coupledRevert(h, full, t.recvT, t.marks, t.x, t.counted, rec, t.reverting)) return 1;
     const bool close = nBadGlobal == 0 || full;
     if (close) {
         hipLaunchKernelGGL(k_tangle_close, dim3(1), dim3(64), 0, h->stream, rec, (long long)(t.count + 1), t.reverting, full ? 1 : 0, (long long)t.nBad0);
@@ -488,12 +494,24 @@ static int qualityConstraintOff(smgpu_handle* h) {
     }
     return 0;
 }
-// one evaluation of the points ptsCur names, behind everything queued on the engine's stream; outside the launch counters and the
-// timing events.  Tiles: k_qc_tile writes fCtr / fArea, which no kernel of the tiled loop reads, and cell centres of the
+// One evaluation of the points ptsCur names, behind everything queued on the engine's stream; outside the launch counters and the
+// timing events.  It has two halves, which the serial form queues back to back (qualityConstraintEvaluate) and the coupled form
+// on either side of the host's move of the cell centres (qualityConstraintCoupledGeometry / _Verdicts, ungated: pass = 0, gate =
+// NULL).  enabling: the verdicts become the exempt bytes.  The kernels take the form as their coupling argument:
+extern "C++" {
+template <class Fn>
+static void withQcCoupling(const QualityConstraintHost& q, Fn fn) {
+    if (q.coupled) fn(std::true_type{}, QCoupling<true>{q.slot, q.recvCc, q.recvVc});
+    else fn(std::false_type{}, QCoupling<false>{});
+}
+}
+// The geometry half.  Tiles: k_qc_tile writes fCtr / fArea, which no kernel of the tiled loop reads, and cell centres of the
 // constraint's own.  Without tiles the direct geometry kernels write the loop's face values (the next geometry launch writes them
-// again before anything reads them), the same cell centres, and test a stop word of the constraint's own.  enabling: the verdicts
-// become the exempt bytes.
-static int qualityConstraintEvaluate(smgpu_handle* h, bool enabling, int pass, const smgpu_iter_stats* gate) {
+// again before anything reads them), the same cell centres, and test a stop word of the constraint's own, which k_qc_open sets
+// in front of pass 0 -- in the coupled form in front of every evaluation.  Then 10.16's cell pass (kernels_quality_limits.hpp), in
+// front of the faces, which read its volumes: coupled, the volumes travel with the cell centres, and the byte the pass leaves in
+// cellFlag and its count in QcDev wait for the second half.
+static int qualityConstraintGeometry(smgpu_handle* h, bool enabling, int pass, const smgpu_iter_stats* gate) {
     const MeshView& m = h->mv;
     QualityConstraintHost& q = h->qc;
     State ts = h->st;
@@ -516,25 +534,41 @@ static int qualityConstraintEvaluate(smgpu_handle* h, bool enabling, int pass, c
         if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
         if (m.nCells > 0) hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
     }
+    if (q.cellMore && m.nCells > 0)
+        withQcCoupling(q, [&](auto coupled, auto cp) {
+            constexpr bool C = decltype(coupled)::value;
+            auto cells = q.more.detOn ? k_qc_cells_more<true, C> : k_qc_cells_more<false, C>;
+            hipLaunchKernelGGL(cells, dim3((m.nCells + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.fCtr, (const double*)ts.fArea, cp,
+                               q.more, q.vol, enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptDet, enabling ? q.exemptDet : (uint8_t*)nullptr, q.cellFlag,
+                               q.dev, pass, gate);
+        });
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+// The verdict half: the faces -- 10.16's wider pass when one of its face criteria is on -- then the cells
+static int qualityConstraintVerdicts(smgpu_handle* h, bool enabling, int pass, const smgpu_iter_stats* gate) {
+    const MeshView& m = h->mv;
+    QualityConstraintHost& q = h->qc;
+    const double *fCtr = h->st.fCtr, *fArea = h->st.fArea, *pts = h->st.ptsCur, *cellCtr = q.cellCtr;
+    const uint8_t* exemptFace = enabling ? nullptr : q.exemptFace;
+    uint8_t* exemptFaceOut = enabling ? q.exemptFace : nullptr;
+    if (m.nFaces > 0)
+        withQcCoupling(q, [&](auto coupled, auto cp) {
+            constexpr bool C = decltype(coupled)::value;
+            const dim3 grid((m.nFaces + kQcBlock - 1) / kQcBlock);
+            if (q.faceMore) {
+                const bool walk = q.more.tetOn || q.more.twistOn || q.more.triOn, ratio = q.more.ratioOn != 0;
+                auto faces = walk ? (ratio ? k_qc_faces_more<true, true, C> : k_qc_faces_more<true, false, C>)
+                                  : (ratio ? k_qc_faces_more<false, true, C> : k_qc_faces_more<false, false, C>);
+                hipLaunchKernelGGL(faces, grid, dim3(kQcBlock), 0, h->stream, m, pts, fCtr, fArea, cellCtr, (const double*)q.vol, (const int*)h->q.own,
+                                   (const int*)h->q.nei, cp, q.lim, q.more, exemptFace, exemptFaceOut, q.cellFlag, q.dev, pass, gate);
+            } else
+                hipLaunchKernelGGL(k_qc_faces<C>, grid, dim3(kQcBlock), 0, h->stream, m, pts, fCtr, fArea, cellCtr, (const int*)h->q.own, (const int*)h->q.nei, cp,
+                                   q.lim, exemptFace, exemptFaceOut, q.cellFlag, q.dev, pass, gate);
+        });
     const int gCells = (m.nCells + kQcBlock - 1) / kQcBlock;
-    // 10.16 (kernels_quality_limits.hpp): the cell pass in front of the faces, which read its volumes, and the wider face pass
-    if (q.cellMore && m.nCells > 0) {
-        auto cells = q.more.detOn ? k_qc_cells_more<true> : k_qc_cells_more<false>;
-        hipLaunchKernelGGL(cells, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.fCtr, (const double*)ts.fArea, q.more, q.vol,
-                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptDet, enabling ? q.exemptDet : (uint8_t*)nullptr, q.cellFlag, q.dev, pass, gate);
-    }
-    if (m.nFaces > 0 && q.faceMore) {
-        const bool walk = q.more.tetOn || q.more.twistOn || q.more.triOn, ratio = q.more.ratioOn != 0;
-        auto faces = walk ? (ratio ? k_qc_faces_more<true, true> : k_qc_faces_more<true, false>) : (ratio ? k_qc_faces_more<false, true> : k_qc_faces_more<false, false>);
-        hipLaunchKernelGGL(faces, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.ptsCur, (const double*)ts.fCtr,
-                           (const double*)ts.fArea, (const double*)ts.cellCtr, (const double*)q.vol, (const int*)h->q.own, (const int*)h->q.nei, q.lim, q.more,
-                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag, q.dev, pass, gate);
-    } else if (m.nFaces > 0)
-        hipLaunchKernelGGL(k_qc_faces, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.ptsCur, (const double*)ts.fCtr,
-                           (const double*)ts.fArea, (const double*)ts.cellCtr, (const int*)h->q.own, (const int*)h->q.nei, q.lim,
-                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag, q.dev, pass, gate);
     if (m.nCells > 0 && !h->useTiles)
-        hipLaunchKernelGGL(k_qc_cells<true>, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.fCtr, (const double*)ts.fArea, (const double*)ts.cellCtr,
+        hipLaunchKernelGGL(k_qc_cells<true>, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, fCtr, fArea, cellCtr,
                            enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptCell, enabling ? q.exemptCell : (uint8_t*)nullptr, (const uint8_t*)nullptr,
                            q.cellFlag, q.marks, q.dev, pass, gate);
     else if (m.nCells > 0 && !enabling)   // (enabling with tiles: k_qc_tile has left the exempt bytes and their count)
@@ -542,6 +576,9 @@ static int qualityConstraintEvaluate(smgpu_handle* h, bool enabling, int pass, c
                            (const uint8_t*)nullptr, (uint8_t*)nullptr, (const uint8_t*)q.tangled, q.cellFlag, q.marks, q.dev, pass, gate);
     HIP_OK(hipGetLastError());
     return 0;
+}
+static int qualityConstraintEvaluate(smgpu_handle* h, bool enabling, int pass, const smgpu_iter_stats* gate) {
+    return qualityConstraintGeometry(h, enabling, pass, gate) || qualityConstraintVerdicts(h, enabling, pass, gate);
 }
 // behind the movePoints of an iteration: the passes on the points ptsCur now names; x: the points the iteration started from
 static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x) {
@@ -552,12 +589,7 @@ static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, con
     const int gApply = std::max(1, (int)(((int64_t)nP + kTanglePts - 1) / kTanglePts));
     for (int k = 0; k <= q.prm.passes; ++k) {
         if (qualityConstraintEvaluate(h, false, k, gate)) return 1;
-        // (the narrow record is the head of the slot: kernels_quality_limits.hpp)
-        if (q.faceMore || q.cellMore)
-            hipLaunchKernelGGL(k_qc_verdict_more, dim3(1), dim3(64), 0, h->stream, q.dev, q.acc, rec, (long long)number, k, (int)q.prm.passes, gate);
-        else
-            hipLaunchKernelGGL(k_qc_verdict, dim3(1), dim3(64), 0, h->stream, q.dev, q.acc, reinterpret_cast<smgpu_quality_constraint_record*>(rec), (long long)number, k,
-                               (int)q.prm.passes, gate);
+        hipLaunchKernelGGL(k_qc_verdict, dim3(1), dim3(64), 0, h->stream, q.dev, q.acc, rec, (long long)number, k, (int)q.prm.passes, gate);
         // the record and the device words begin with the tangle constraint's (kernels_quality_constraint.hpp)
         hipLaunchKernelGGL(k_tangle_apply, dim3(gApply), dim3(kTangleBlock), 0, h->stream, x, h->st.ptsCur, q.marks, nP, (const TangleDev*)&q.dev->t,
                            reinterpret_cast<smgpu_tangle_record*>(rec), gate);
@@ -566,20 +598,26 @@ static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, con
     return 0;
 }
 
-// the two entries of the serial constraint: api names the one called, in its refusals; more: the limits of 10.16 (all off under
-// smgpu_set_quality_constraint)
-static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgpu_quality_constraint_params& prm, const QcMore& more) {
-    const std::string api(name);
+// What enabling shares between the serial and the coupled form.  First the refusals both make first, in their order; api names
+// the entry called; coupled: the form, which wants an engine with a halo, where `serial` names the entry a serial engine takes
+static int qualityConstraintRefusals(smgpu_handle* h, const std::string& api, const smgpu_quality_constraint_params& prm, const QcMore& more, bool coupled,
+                                     const char* serial) {
     if (prm.passes < 0) return fail(api + ": passes < 0");
     if (std::isnan(prm.maxNonOrtho) || std::isnan(prm.maxInternalSkewness) || std::isnan(prm.maxBoundarySkewness) || std::isnan(more.minTet) ||
         std::isnan(more.minTwist) || std::isnan(more.minTri) || std::isnan(more.minWeight) || std::isnan(more.minRatio) || std::isnan(more.minDet))
         return fail(api + ": a limit is NaN");
-    if (h->haloOn) return fail(kQualityHaloRefusal);
+    if (!coupled && h->haloOn) return fail(kQualityHaloRefusal);
+    if (coupled && !h->haloOn) return fail(api + ": the engine has no halo (smgpu_halo_configure); a serial engine takes " + serial);
     if (h->bndOn)
         return fail(api + ": not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
                     "points from state that a reverted iteration would leave ahead of the points)");
-    if (h->tg.on) return fail(api + ": the tangle constraint is on (smgpu_set_tangle_constraint), and this constraint contains it; switch it off first");
-    if (h->iterOpen) return fail(api + ": between smgpu_iter_begin and smgpu_iter_end");
+    if (h->tg.on)
+        return fail(api + ": the tangle constraint is on (" + (coupled ? "smgpu_set_tangle_constraint_coupled" : "smgpu_set_tangle_constraint") +
+                    "), and this constraint contains it; switch it off first");
+    return 0;
+}
+// ... then, every refusal made: the constraint that was on goes, and the buffers, limits and launch choices of the new one are set
+static int qualityConstraintAllocate(smgpu_handle* h, const smgpu_quality_constraint_params& prm, const QcMore& more) {
     if (qualityConstraintOff(h)) return 1;
     if (flushDeferred(h)) return 1;
     if (qualityEnsure(h)) return 1;                  // owner / neighbour by face
@@ -606,6 +644,17 @@ static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgp
     const smgpu_quality_params rp{prm.maxNonOrtho, prm.maxInternalSkewness, 1e-6, 1000.0};
     q.lim = QcLimits{qualityThresholds(&rp).cosNonOrth, prm.maxInternalSkewness, prm.maxBoundarySkewness, prm.maxNonOrtho < 180.0 ? 1 : 0,
                      prm.maxInternalSkewness > 0.0 ? 1 : 0, prm.maxBoundarySkewness > 0.0 ? 1 : 0};
+    return 0;
+}
+
+// the two entries of the serial constraint: name names the one called, in its refusals; more: the limits of 10.16 (all off under
+// smgpu_set_quality_constraint)
+static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgpu_quality_constraint_params& prm, const QcMore& more) {
+    const std::string api(name);
+    if (qualityConstraintRefusals(h, api, prm, more, false, nullptr)) return 1;
+    if (h->iterOpen) return fail(api + ": between smgpu_iter_begin and smgpu_iter_end");
+    if (qualityConstraintAllocate(h, prm, more)) return 1;
+    QualityConstraintHost& q = h->qc;
     // the exempt cells and faces: one evaluation of the current points
     if (qualityConstraintEvaluate(h, true, 0, nullptr)) { q.release(); return 1; }
     QcDev qd{};
@@ -687,40 +736,12 @@ static int qualityConstraintCoupledFlush(smgpu_handle* h) {
     q.slabFresh = false;
     return 0;
 }
-// the first half of an evaluation of the points ptsCur names: qualityConstraintEvaluate's geometry launches (ungated), then the
-// pack of the constraint's own cell centres -- never the loop's, which are those of other points -- and the wait: sendCc is the
-// host's to move
+// the first half of an evaluation of the points ptsCur names: the geometry half, ungated, then the pack of the constraint's own
+// cell centres -- never the loop's, which are those of other points -- and with minVolRatio on of its volumes (10.17), and the
+// wait: sendCc and sendVc are the host's to move
 static int qualityConstraintCoupledGeometry(smgpu_handle* h, bool enabling) {
-    const MeshView& m = h->mv;
     QualityConstraintHost& q = h->qc;
-    State ts = h->st;
-    ts.cellCtr = q.cellCtr;
-    ts.acc = q.acc;
-    ts.stats = nullptr;
-    if (h->useTiles) {
-        const int nT = h->gt.nTiles;
-        if (nT > 0)
-            withGeomTile(h, [&](auto tile, auto org) {
-                constexpr int T = decltype(tile)::value;
-                constexpr bool ORG = decltype(org)::value;
-                ensureDynLds(k_qc_tile<T, ORG>, h->device, h->geomLds);
-                hipLaunchKernelGGL((k_qc_tile<T, ORG>), dim3(tileGrid(nT, h->xcdMap)), dim3(T), (uint32_t)h->geomLds, h->stream, h->mv, ts, h->gv, nT, h->xcdMap,
-                                   enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptCell, enabling ? q.exemptCell : (uint8_t*)nullptr, q.tangled, q.dev,
-                                   0, (const smgpu_iter_stats*)nullptr);
-            });
-    } else {
-        hipLaunchKernelGGL(k_qc_open, dim3(1), dim3(64), 0, h->stream, q.acc, (const smgpu_iter_stats*)nullptr);
-        if (m.nFaces > 0) hipLaunchKernelGGL(k_face_geom, dim3(gridFor(m.nFaces)), dim3(kBlock), 0, h->stream, m, ts, 0, h->foamOrg ? 1 : 0);
-        if (m.nCells > 0) hipLaunchKernelGGL(k_cell_centres, dim3(gridFor(m.nCells)), dim3(kBlock), 0, h->stream, m, ts, h->foamOrg ? 1 : 0);
-    }
-    // 10.17 (kernels_quality_limits_coupled.hpp): the volumes travel with the cell centres, so the cell pass stands in this half;
-    // the byte it leaves in cellFlag and its count in QcDev wait for the second half
-    if (q.cellMore && m.nCells > 0) {
-        auto cells = q.more.detOn ? k_qc_cells_more_coupled<true> : k_qc_cells_more_coupled<false>;
-        hipLaunchKernelGGL(cells, dim3((m.nCells + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.fCtr, (const double*)ts.fArea,
-                           (const int*)q.slot, q.more, q.vol, enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptDet,
-                           enabling ? q.exemptDet : (uint8_t*)nullptr, q.cellFlag, q.dev);
-    }
+    if (qualityConstraintGeometry(h, enabling, 0, nullptr)) return 1;
     if (q.nProc > 0)
         hipLaunchKernelGGL(k_quality_pack, dim3((q.nProc + kQualityBlock - 1) / kQualityBlock), dim3(kQualityBlock), 0, h->stream, (const int*)h->q.own,
                            (const double*)q.cellCtr, (const int*)q.procFace, q.nProc, q.sendCc);
@@ -730,33 +751,12 @@ static int qualityConstraintCoupledGeometry(smgpu_handle* h, bool enabling) {
     HIP_OK(hipGetLastError());
     return checkDeviceError(h);
 }
-// the second half, recvCc moved by the host: the face verdicts, the cells, and in a pass the pack of the shared points' marks; *qd:
-// the counts, read with the loop's error word -- sendT is complete when this returns
+// the second half, recvCc (and recvVc) moved by the host: the verdict half, ungated, and in a pass the pack of the shared points'
+// marks; *qd: the counts, read with the loop's error word -- sendT is complete when this returns
 static int qualityConstraintCoupledVerdicts(smgpu_handle* h, bool enabling, QcDev* qd) {
-    const MeshView& m = h->mv;
     QualityConstraintHost& q = h->qc;
     if (computeAfterExch(h)) return 1;          // exchange Cc has been enqueued by the host
-    const double *fCtr = h->st.fCtr, *fArea = h->st.fArea, *pts = h->st.ptsCur;
-    if (m.nFaces > 0 && q.faceMore) {   // 10.17: the wider face pass in the place of k_qc_faces_coupled
-        const bool walk = q.more.tetOn || q.more.twistOn || q.more.triOn, ratio = q.more.ratioOn != 0;
-        auto faces = walk ? (ratio ? k_qc_faces_more_coupled<true, true> : k_qc_faces_more_coupled<true, false>)
-                          : (ratio ? k_qc_faces_more_coupled<false, true> : k_qc_faces_more_coupled<false, false>);
-        hipLaunchKernelGGL(faces, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, pts, fCtr, fArea, (const double*)q.cellCtr,
-                           (const double*)q.vol, (const int*)h->q.own, (const int*)h->q.nei, (const int*)q.slot, (const double*)q.recvCc, (const double*)q.recvVc,
-                           q.lim, q.more, enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag,
-                           q.dev);
-    } else if (m.nFaces > 0)
-        hipLaunchKernelGGL(k_qc_faces_coupled, dim3((m.nFaces + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, pts, fCtr, fArea, (const double*)q.cellCtr,
-                           (const int*)h->q.own, (const int*)h->q.nei, (const int*)q.slot, (const double*)q.recvCc, q.lim,
-                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptFace, enabling ? q.exemptFace : (uint8_t*)nullptr, q.cellFlag, q.dev);
-    const int gCells = (m.nCells + kQcBlock - 1) / kQcBlock;
-    if (m.nCells > 0 && !h->useTiles)
-        hipLaunchKernelGGL(k_qc_cells<true>, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, fCtr, fArea, (const double*)q.cellCtr,
-                           enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptCell, enabling ? q.exemptCell : (uint8_t*)nullptr, (const uint8_t*)nullptr,
-                           q.cellFlag, q.marks, q.dev, 0, (const smgpu_iter_stats*)nullptr);
-    else if (m.nCells > 0 && !enabling)   // (enabling with tiles: k_qc_tile has left the exempt bytes and their count)
-        hipLaunchKernelGGL(k_qc_cells<false>, dim3(gCells), dim3(kQcBlock), 0, h->stream, m, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr,
-                           (const uint8_t*)nullptr, (uint8_t*)nullptr, (const uint8_t*)q.tangled, q.cellFlag, q.marks, q.dev, 0, (const smgpu_iter_stats*)nullptr);
+    if (qualityConstraintVerdicts(h, enabling, 0, nullptr)) return 1;
     if (!enabling && h->nSend > 0)
         hipLaunchKernelGGL(k_tangle_pack, dim3((h->nSend + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, h->nSend, (const int*)h->dSendShared,
                            (const int*)h->dSharedLocal, (const uint8_t*)q.marks, q.sendT);
@@ -772,16 +772,7 @@ static int qualityConstraintCoupledVerdicts(smgpu_handle* h, bool enabling, QcDe
 static int qualityConstraintCoupledEnable(smgpu_handle* h, const char* name, bool full, const smgpu_quality_constraint_params& prm, const QcMore& more,
                                           const smgpu_quality_constraint_halo_desc_full* d) {
     const std::string api(name);
-    const char* serial = full ? "smgpu_set_quality_constraint_limits" : "smgpu_set_quality_constraint";
-    if (prm.passes < 0) return fail(api + ": passes < 0");
-    if (std::isnan(prm.maxNonOrtho) || std::isnan(prm.maxInternalSkewness) || std::isnan(prm.maxBoundarySkewness) || std::isnan(more.minTet) ||
-        std::isnan(more.minTwist) || std::isnan(more.minTri) || std::isnan(more.minWeight) || std::isnan(more.minRatio) || std::isnan(more.minDet))
-        return fail(api + ": a limit is NaN");
-    if (!h->haloOn) return fail(api + ": the engine has no halo (smgpu_halo_configure); a serial engine takes " + serial);
-    if (h->bndOn)
-        return fail(api + ": not available on an engine with boundary point smoothing (it rewrites the proposals of the "
-                    "boundary points from state that a reverted iteration would leave ahead of the points)");
-    if (h->tg.on) return fail(api + ": the tangle constraint is on (smgpu_set_tangle_constraint_coupled), and this constraint contains it; switch it off first");
+    if (qualityConstraintRefusals(h, api, prm, more, true, full ? "smgpu_set_quality_constraint_limits" : "smgpu_set_quality_constraint")) return 1;
     if (h->qc.on && h->qc.coupled && h->qc.full != full)
         return fail(api + ": the quality constraint is on through " + (full ? "smgpu_set_quality_constraint_coupled" : "smgpu_set_quality_constraint_limits_coupled") +
                     "; switch it off first");
@@ -794,49 +785,27 @@ static int qualityConstraintCoupledEnable(smgpu_handle* h, const char* name, boo
     if (qualityCouplingTables(name, m, d->coupling, key, procFace, slot, nProc, notCounted)) return 1;
     if (nProc > 0 && (!d->sendCc || !d->recvCc)) return fail(api + ": null exchange buffer");
     if (nProc > 0 && more.ratioOn && (!d->sendVc || !d->recvVc)) return fail(api + ": null exchange buffer (minVolRatio is on: sendVc / recvVc)");
-    if (qualityConstraintOff(h)) return 1;
-    if (flushDeferred(h)) return 1;
-    if (qualityEnsure(h)) return 1;                  // owner / neighbour by face
-    const size_t nMark = ((size_t)std::max(1, m.nPoints) + 3) & ~(size_t)3, nCell = (size_t)std::max(1, m.nCells), nFace = (size_t)std::max(1, m.nFaces);
+    if (qualityConstraintAllocate(h, prm, more)) return 1;
     const size_t nB = (size_t)(m.nFaces - m.nInternalFaces);
     QualityConstraintHost& q = h->qc;
-    if (q.block.alloc(&q.dev, 1) || q.block.alloc(&q.exemptCell, nCell) || q.block.alloc(&q.cellFlag, nCell) || q.block.alloc(&q.tangled, nCell) || q.block.alloc(&q.exemptFace, nFace) ||
-        q.block.alloc(&q.marks, nMark) || q.block.alloc(&q.cellCtr, 3 * nCell) || q.block.alloc(&q.acc, 1) ||
-        q.block.alloc(&q.counted, (size_t)std::max(1, h->nShared)) || q.block.alloc(&q.procFace, (size_t)std::max<int64_t>(1, nProc)) ||
+    if (q.block.alloc(&q.counted, (size_t)std::max(1, h->nShared)) || q.block.alloc(&q.procFace, (size_t)std::max<int64_t>(1, nProc)) ||
         q.block.alloc(&q.slot, std::max<size_t>(1, nB)))
         return q.block.failed("the quality constraint");
-    q.more = more;
-    q.faceMore = more.tetOn || more.twistOn || more.triOn || more.weightOn || more.ratioOn;
-    q.cellMore = more.ratioOn || more.detOn;
-    if (q.cellMore && (q.block.alloc(&q.vol, nCell) || q.block.alloc(&q.exemptDet, nCell))) return q.block.failed("the quality constraint");
-    if (q.cellMore) HIP_OK(hipMemsetAsync(q.exemptDet, 0, nCell, h->stream));
-    HIP_OK(hipMemsetAsync(q.dev, 0, sizeof(QcDev), h->stream));
-    HIP_OK(hipMemsetAsync(q.exemptCell, 0, nCell, h->stream));
-    HIP_OK(hipMemsetAsync(q.cellFlag, 0, nCell, h->stream));
-    HIP_OK(hipMemsetAsync(q.tangled, 0, nCell, h->stream));
-    HIP_OK(hipMemsetAsync(q.exemptFace, 0, nFace, h->stream));
-    HIP_OK(hipMemsetAsync(q.marks, 0, nMark, h->stream));
-    HIP_OK(hipMemsetAsync(q.acc, 0, sizeof(Accum), h->stream));
     if (h->nShared > 0) HIP_OK(hipMemcpyAsync(q.counted, h->sharedMasterHost.data(), (size_t)h->nShared, hipMemcpyHostToDevice, h->stream));
     if (nProc) HIP_OK(hipMemcpyAsync(q.procFace, procFace.data(), sizeof(int) * (size_t)nProc, hipMemcpyHostToDevice, h->stream));
     if (nB) HIP_OK(hipMemcpyAsync(q.slot, slot.data(), sizeof(int) * nB, hipMemcpyHostToDevice, h->stream));
-    q.prm = prm;
-    // cosT exactly as qualityThresholds() forms the report's cosine
-    const smgpu_quality_params rp{prm.maxNonOrtho, prm.maxInternalSkewness, 1e-6, 1000.0};
-    q.lim = QcLimits{qualityThresholds(&rp).cosNonOrth, prm.maxInternalSkewness, prm.maxBoundarySkewness, prm.maxNonOrtho < 180.0 ? 1 : 0,
-                     prm.maxInternalSkewness > 0.0 ? 1 : 0, prm.maxBoundarySkewness > 0.0 ? 1 : 0};
     q.nProc = (int)nProc;
     q.sendT = (int*)d->sendT; q.recvT = (int*)d->recvT;
     q.sendCc = (double*)d->sendCc; q.recvCc = (double*)d->recvCc;
     q.sendVc = (double*)d->sendVc; q.recvVc = (double*)d->recvVc;
     q.full = full;
+    q.coupled = true;                                // from here the evaluation's kernels take the coupling
     // the exempt cells and faces: one evaluation of the current points, its second half behind the host's exchange of Cc
     // (the wait inside also covers the uploads from the host vectors above)
     if (qualityConstraintCoupledGeometry(h, true)) { q.release(); return 1; }
     q.count = 0;
     q.k = -1;
     q.stage = 0;
-    q.coupled = true;
     q.pending = true;
     q.on = true;
     return 0;
@@ -930,36 +899,16 @@ int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32
     if (q.stage != 2 || q.k < 0) return fail("smgpu_quality_constraint_pass_end without smgpu_quality_constraint_pass_faces");
     if (nBadGlobal < 0) return fail("smgpu_quality_constraint_pass_end: nBadGlobal < 0");
     HIP_OK(hipSetDevice(h->device));
-    smgpu_quality_constraint_record_full* slot = nullptr;       // (10.15's entry writes its head, the rest stays zero; 10.17's all of it)
-    if (q.slab.slot(q.slabUsed, &slot)) return 1;
-    smgpu_quality_constraint_record* rec = reinterpret_cast<smgpu_quality_constraint_record*>(slot);
-    const int nP = h->mv.nPoints;
+    smgpu_quality_constraint_record_full* rec = nullptr;
+    if (q.slab.slot(q.slabUsed, &rec)) return 1;
     const bool full = nBadGlobal > 0 && q.k == q.prm.passes;
-    if (nBadGlobal > 0) {
-        if (!full) {
-            if (computeAfterExch(h)) return 1;      // exchange T has been enqueued by the host
-            if (h->nShared > 0 && h->nRecv > 0)
-                hipLaunchKernelGGL(k_tangle_combine, dim3((h->nShared + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, h->nShared,
-                                   (const int*)h->dSharedLocal, (const int*)h->dCombOff, (const int*)h->dCombSlots, (const int*)q.recvT, q.marks);
-            ++q.reverting;
-        }
-        // the record begins with the tangle constraint's (kernels_quality_constraint.hpp)
-        const int grid = std::max(1, (int)(((int64_t)nP + kTangleCountedPts - 1) / kTangleCountedPts));
-        hipLaunchKernelGGL(k_tangle_apply_counted, dim3(grid), dim3(kTangleBlock), 0, h->stream, q.x, h->st.ptsCur, q.marks, nP, full ? 1 : 0,
-                           (const int*)h->dSharedSlot, (const uint8_t*)q.counted, reinterpret_cast<smgpu_tangle_record*>(rec));
-        // points went back: the geometry smgpu_iter_ahead left for the next iteration is that of other points
-        h->geomAheadDone = false;
-        h->q.epoch++;
-    }
+    // the record begins with the tangle constraint's (kernels_quality_constraint.hpp)
+    if (nBadGlobal > 0 && coupledRevert(h, full, q.recvT, q.marks, q.x, q.counted, reinterpret_cast<smgpu_tangle_record*>(rec), q.reverting)) return 1;
     const bool close = nBadGlobal == 0 || full;
     if (close) {
-        if (q.full) {   // 10.17: the wider record
-            QcCounts c{};
-            for (int i = 0; i < 10; ++i) c.n[i] = (long long)q.n0[i];
-            hipLaunchKernelGGL(k_qc_close_full, dim3(1), dim3(64), 0, h->stream, slot, (long long)(q.count + 1), q.reverting, full ? 1 : 0, c);
-        } else
-            hipLaunchKernelGGL(k_qc_close, dim3(1), dim3(64), 0, h->stream, rec, (long long)(q.count + 1), q.reverting, full ? 1 : 0, (long long)q.n0[0],
-                               (long long)q.n0[1], (long long)q.n0[2], (long long)q.n0[3]);
+        QcCounts c{};   // (10.15's entry: the six counts of 10.16 are 0, as the zeroed slot's were)
+        for (int i = 0; i < 10; ++i) c.n[i] = (long long)q.n0[i];
+        hipLaunchKernelGGL(k_qc_close, dim3(1), dim3(64), 0, h->stream, rec, (long long)(q.count + 1), q.reverting, full ? 1 : 0, c);
         ++q.count;
         ++q.slabUsed;
         q.k = -1;

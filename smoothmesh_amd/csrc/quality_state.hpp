@@ -212,7 +212,8 @@ struct QualityConstraintHost {
     QcDev* dev = nullptr;
     double* cellCtr = nullptr;
     Accum* acc = nullptr;
-    // one record per iteration of the call; without the limits of 10.16 only its head, smgpu_quality_constraint_record, is written
+    // one record per iteration of the call; without the limits of 10.16 the six counts behind its head,
+    // smgpu_quality_constraint_record, are 0
     RecordSlab<smgpu_quality_constraint_record_full> slab{"quality constraint"};
     // the limits of 10.16 (smgpu_set_quality_constraint_limits, kernels_quality_limits.hpp).  faceMore: a new face criterion is
     // on; cellMore: minVolRatio or minDeterminant is; with neither the launches are 10.14's.  vol, exemptDet: allocated with
@@ -225,13 +226,14 @@ struct QualityConstraintHost {
     // the coupled form (smgpu_set_quality_constraint_coupled, 10.15) on an engine with a halo: TangleHost's coupled members with
     // the same meaning (x, k, reverting, count, the slab in chunks, counted, sendT / recvT), and what the face verdicts add.
     // pending: enabled, the exempt faces not taken yet.  stage: 0 no pass open, 1 behind pass_begin, 2 behind pass_faces.  n0: the
-    // rank's counts at k = 0 (bad cells, tangled cells, non-orthogonal faces, skew faces).  procFace / slot: 10.4's tables of the
-    // coupling given at enabling, the constraint's own copies: a report packed with another coupling releases only the report's.
+    // rank's counts at k = 0 in the record's order from nBadCells on, as k_qc_close takes them.  procFace / slot: 10.4's tables of
+    // the coupling given at enabling, the constraint's own copies: a report packed with another coupling releases only the report's.
+    // coupled is set before the enabling evaluation: its kernels take the form from it (withQcCoupling, quality_loop.hpp).
     static constexpr int kChunk = 256;
     bool coupled = false, pending = false, slabFresh = false;
     int k = -1, stage = 0, reverting = 0, slabUsed = 0, nProc = 0;
-    // (under smgpu_set_quality_constraint_limits_coupled, 10.17 -- `full`: then the six counts of 10.16, and k_qc_close_full
-    // closes the record; sendVc / recvVc: the caller's volume buffers, one double per processor face, used while minVolRatio is on)
+    // (full: enabled through smgpu_set_quality_constraint_limits_coupled, 10.17, which the refusal of the other coupled entry
+    // names; sendVc / recvVc: the caller's volume buffers, one double per processor face, used while minVolRatio is on)
     bool full = false;
     int64_t count = 0, n0[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     double *sendVc = nullptr, *recvVc = nullptr;

@@ -27,7 +27,6 @@
 #include "kernels_quality_tangle.hpp"
 #include "kernels_quality_constraint.hpp"
 #include "kernels_quality_limits.hpp"
-#include "kernels_quality_limits_coupled.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"

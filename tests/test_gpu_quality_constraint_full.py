@@ -142,6 +142,19 @@ def test_all_six_off_is_the_old_entry(name, lim):
     assert {c["name"]: c["launches"] for c in a.counters()} == {c["name"]: c["launches"] for c in b.counters()}
 
 
+def test_old_entry_leaves_the_six_new_counts_zero():
+    """under smgpu_set_quality_constraint one verdict kernel writes the whole slot: drained through the full getter, the six counts
+    of 10.16 are exactly 0 in every record, as the zeroed slot's were while only its head was written"""
+    name = "dented_tiles"
+    _, over, n = CASES[name]
+    e = _engine(_mesh(name), "com", False, **over)
+    e.set_quality_constraint(**{**OFF, **dict(maxInternalSkewness=0.4, maxBoundarySkewness=0.1)})
+    assert e.iterate(n, 0.0)[0] == n
+    recs = e.quality_constraint_records()                                       # (smgpu_get_quality_constraint_records_full)
+    assert len(recs) == n and any(r.nBadCells > 0 for r in recs)
+    assert all(getattr(r, MORE[k][1]) == 0 for r in recs for k in MORE)
+
+
 # ---- 3. the invariant, through the engine's own reports ----------------------------------------------------------------
 @pytest.mark.parametrize("case", ["all", "tiles_weight"])
 def test_invariant_through_the_reports(oracle_lib, case):

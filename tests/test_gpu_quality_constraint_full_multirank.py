@@ -1,5 +1,5 @@
 """The quality constraint's tet, twist, weight, ratio and determinant limits on a decomposed mesh (include/smgpu.h
-smgpu_set_quality_constraint_limits_coupled, csrc/kernels_quality_limits_coupled.hpp, DESIGN.md "Mesh quality" 10.17) through the two
+smgpu_set_quality_constraint_limits_coupled, csrc/kernels_quality_limits.hpp Coupled = true, DESIGN.md "Mesh quality" 10.17) through the two
 smoothers of halo.py, against the CPU restatement (tests/quality_constraint_full_multi_reference.py, pinned against the serial
 restatement by tests/test_quality_constraint_full_multi_reference.py): per-rank and combined full records exactly, the per-rank
 exempt counts, the points of every iteration at the project's decomposed tolerance, copies of shared points bit-identical; the
@@ -152,6 +152,23 @@ def test_all_six_off_is_the_old_coupled_entry(oracle_lib, monkeypatch, env):
     assert all(getattr(r, MORE[k][1]) == 0 for rr in qa for r in rr for k in MORE)
     assert a.quality_constraint_state() == b.quality_constraint_state()
     _close(a), _close(b)
+
+
+def test_old_coupled_entry_leaves_the_six_new_counts_zero(oracle_lib, monkeypatch):
+    """under smgpu_set_quality_constraint_coupled one close kernel writes the whole slot: dented_tiles cut (6, 1, 1), which ends
+    iterations with reverting passes and with the full revert, drained through the full getter: the six counts of 10.16 are
+    exactly 0 in every record of every rank"""
+    from test_quality_constraint_multi_reference import MULTI_CASES, limits_of, multi_reference
+    name = "tiles_611_both"
+    want = multi_reference(oracle_lib, name, "com", False, 2)
+    n = MULTI_CASES[name][3]
+    ms = _smoother(want["ref"], "com", 2, {}, monkeypatch, limits_of(name), old=True)
+    assert ms.iterate(n, 0.0)[0] == n
+    raw = ms.quality_constraint_records(per_rank=True)                          # (smgpu_get_quality_constraint_records_full)
+    assert [_records(r) for r in raw] == want["per_rank"]
+    assert any(r.fullRevert for rr in raw for r in rr) and any(r.passes > 0 and not r.fullRevert for rr in raw for r in rr)
+    assert all(getattr(r, MORE[k][1]) == 0 for rr in raw for r in rr for k in MORE)
+    _close(ms)
 
 
 # ---- 4. a constraint that is on and never fires leaves the run untouched ---------------------------------------------------

@@ -1,5 +1,5 @@
 """The quality constraint on a decomposed mesh (include/smgpu.h smgpu_set_quality_constraint_coupled / smgpu_quality_constraint_pass_*,
-csrc/kernels_quality_constraint.hpp k_qc_faces_coupled, DESIGN.md "Mesh quality" 10.15) through the two smoothers of halo.py, against
+csrc/kernels_quality_constraint.hpp k_qc_faces<true>, DESIGN.md "Mesh quality" 10.15) through the two smoothers of halo.py, against
 its CPU restatement (tests/quality_constraint_multi_reference.py, pinned against the serial restatement by
 tests/test_quality_constraint_multi_reference.py): per-rank and combined records exactly and the points of every iteration at the
 project's decomposed tolerance, copies of shared points bit-identical; the invariant through the decomposed report and its sets,
