@@ -459,8 +459,8 @@ int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint
  * first 56 bytes.  smgpu_quality_constraint_state_full: the state above, then the six limits and the determinant-exempt cells.
  * Under smgpu_set_quality_constraint (and the coupled form) the new counts are 0 and the limits the off values.
  *
- * Not covered: the base-point tets (their walk is O(nv^2) per face and stays with the report), maxConcave and minFlatness (the
- * concavity value depends on its own threshold), minVol and minArea, reading system/meshQualityDict.  On a decomposed mesh
+ * Not covered: the base-point tets (their walk is O(nv^2) per face and stays with the report), reading system/meshQualityDict;
+ * maxConcave, minFlatness, minVol and minArea are smgpu_set_quality_constraint_limits_all's (10.18, below).  On a decomposed mesh
  * smgpu_set_quality_constraint_coupled takes the three limits of 10.14 only; smgpu_set_quality_constraint_limits_coupled (10.17,
  * below) takes all nine.
  * Memory, beyond 10.14's: 104 bytes per iteration of the longest call in place of 56; with minVolRatio or minDeterminant on,
@@ -586,6 +586,63 @@ typedef struct smgpu_quality_constraint_halo_desc_full {
 } smgpu_quality_constraint_halo_desc_full;
 int smgpu_set_quality_constraint_limits_coupled(smgpu_handle* h, const smgpu_quality_constraint_limits* p,
                                                 const smgpu_quality_constraint_halo_desc_full* d, int32_t on);
+
+/* ---- the last four meshQualityDict limits: concavity, flatness, volume, area (DESIGN.md "Mesh quality", 10.18) -------------
+ * 10.16 and 10.17 with four more criteria; everything not said here is theirs.  The values are taken at the points being judged,
+ * with the operands and the operation order of the reports (smgpu_mesh_quality_geometry for concavity and flatness, |S_f| of the
+ * face areas, V_c of smgpu_mesh_quality's cell volumes).  A face is also BAD when
+ *   faceConcavity_f, evaluated with concaveThreshold = maxConcave, is > SMALL: a corner with both edges > SMALL,
+ *     s >= sin(maxConcave) and (c/s).n < SMALL                         (degrees; off when maxConcave >= 180; < 0 refused)
+ *   it is summed (nv > 3, |S_f| > ROOTVSMALL) and flat_f < minFlatness  (off when minFlatness <= 0)
+ *   |S_f| < minArea                                                    (off when minArea     <= 0)
+ * and a cell when it is the owner or the neighbour of such a face that is not exempt, or when
+ *   V_c < minVol and the cell is not volume-exempt                     (off when minVol      <= 0: 10.12 holds V_c > 0).
+ * sin(maxConcave) is formed as the geometry report forms sin(concaveThreshold).  Strict comparisons; NaN refused; all four off
+ * by default.
+ * EXEMPTION.  The face byte is set by any criterion that is on; a cell under minVol at enabling is exempt from the volume
+ * criterion only (the determinant-exempt byte is a bit set: bit 0 determinant, bit 1 volume).
+ * INVARIANT.  10.16's carries over: the three face values are functions of the face's own points and S_f, V_c of the cell's
+ * points; reverting every point of a bad face's two cells, or of a bad cell, restores their bits at x.
+ * EQUIVALENCE.  All four off: smgpu_set_quality_constraint_limits' (coupled: _limits_coupled's) run bit for bit -- points,
+ * records, state -- and exactly its launches.
+ * On a sub-domain (smgpu_set_quality_constraint_limits_all_coupled) a processor face is judged on the rank's own vertex order,
+ * flags its owner only and counts on the counted side; nothing new travels.
+ *
+ * smgpu_quality_constraint_limits_all: smgpu_quality_constraint_limits at its offsets, then the four.  NULL: the old NULL and
+ * {180, 0, 0, 0}.  smgpu_quality_constraint_record_all: the full record (104 bytes), then at k = 0 the bad, non-exempt concave,
+ * warped and small-area faces (a face that fails several counts in each) and the cells under minVol that are not volume-exempt.
+ * smgpu_quality_constraint_state_all: the full state, then the four limits and the volume-exempt cells.  All getters drain the
+ * one pending list; the narrower ones return each record's prefix.  Under the older entries the four counts are 0 and the four
+ * limits at their off values.  Memory, beyond 10.16's: 136 bytes per record in place of 104; minVol on allocates what
+ * minVolRatio does. */
+typedef struct smgpu_quality_constraint_limits_all {
+    double maxNonOrtho, maxInternalSkewness, maxBoundarySkewness;
+    int32_t passes;
+    double minTetQuality, minTwist, minTriangleTwist, minFaceWeight, minVolRatio, minDeterminant;
+    double maxConcave, minFlatness, minVol, minArea;
+} smgpu_quality_constraint_limits_all;        /* NULL limits = {65, 4, 20, 2, -1e30, -1, -1, 0, 0, 0, 180, 0, 0, 0} */
+typedef struct smgpu_quality_constraint_record_all {
+    int64_t iteration;
+    int32_t passes, fullRevert;
+    int64_t nBadCells, nPointsReverted;
+    int64_t nTangledCells, nNonOrthoFaces, nSkewFaces;
+    int64_t nLowTetFaces, nLowTwistFaces, nLowTriangleTwistFaces, nLowWeightFaces, nLowVolRatioFaces, nUnderdeterminedCells;
+    int64_t nConcaveFaces, nWarpedFaces, nSmallAreaFaces, nSmallVolumeCells;
+} smgpu_quality_constraint_record_all;
+typedef struct smgpu_quality_constraint_state_all {
+    int32_t on, passes;
+    double maxNonOrtho, maxInternalSkewness, maxBoundarySkewness;
+    int64_t nExemptCells, nExemptFaces, iteration;
+    double minTetQuality, minTwist, minTriangleTwist, minFaceWeight, minVolRatio, minDeterminant;
+    int64_t nExemptDeterminantCells;
+    double maxConcave, minFlatness, minVol, minArea;
+    int64_t nExemptVolumeCells;
+} smgpu_quality_constraint_state_all;
+int smgpu_set_quality_constraint_limits_all(smgpu_handle* h, const smgpu_quality_constraint_limits_all* p, int32_t on);
+int smgpu_set_quality_constraint_limits_all_coupled(smgpu_handle* h, const smgpu_quality_constraint_limits_all* p,
+                                                    const smgpu_quality_constraint_halo_desc_full* d, int32_t on);
+int smgpu_get_quality_constraint_records_all(smgpu_handle* h, smgpu_quality_constraint_record_all* out, int64_t cap, int64_t* n);
+int smgpu_get_quality_constraint_state_all(smgpu_handle* h, smgpu_quality_constraint_state_all* out);
 
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):

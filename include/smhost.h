@@ -70,6 +70,17 @@ int smhost_gen_cavity_subdomain(int32_t N, double radius, double shell, double j
  * shared-point tables), per cell 8 * coarse cell index + child (ascending with the global cell id). */
 int smhost_mesh_global_ids(const smhost_mesh* m, int64_t* pointGlobal, int64_t* cellGlobal);
 
+/* The limits of an OpenFOAM system/meshQualityDict (DESIGN.md "Mesh quality", 10.18; csrc/host/quality_dict.hpp has the grammar
+ * and the errors, each of which names file and line).  The keys that are read, in the order of values / found (13 each):
+ *   maxNonOrtho maxBoundarySkewness maxInternalSkewness maxConcave minFlatness minVol minTetQuality minArea minTwist
+ *   minDeterminant minFaceWeight minVolRatio minTriangleTwist
+ * found[i] != 0: the file (or one it includes) gives key i, and values[i] is its last value.  etcDirs (nEtcDirs of them): where
+ * #includeEtc "X" looks for X, in order.  ignored: every other top-level key, one per line, NUL-terminated; *ignoredLen holds the
+ * buffer's size on entry and the bytes needed on return -- where that is more than was given (or ignored is NULL) nothing is
+ * written and the caller asks again.  No defaults of any OpenFOAM release are compiled in. */
+int smhost_read_mesh_quality_dict(const char* path, const char* const* etcDirs, int32_t nEtcDirs, double* values, int32_t* found,
+                                  char* ignored, int64_t* ignoredLen);
+
 #ifdef __cplusplus
 }
 #endif

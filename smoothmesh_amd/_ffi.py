@@ -179,6 +179,24 @@ class QualityConstraintStateFull(C.Structure):
     _fields_ = QualityConstraintState._fields_ + [(n, C.c_double) for n in _QC_LIMITS] + [("nExemptDeterminantCells", C.c_int64)]
 
 
+_QC_LIMITS_ALL = ("maxConcave", "minFlatness", "minVol", "minArea")
+
+
+class QualityConstraintLimitsAll(C.Structure):
+    """smgpu_quality_constraint_limits_all: QualityConstraintLimits' fields, then the four limits of DESIGN.md 10.18"""
+    _fields_ = QualityConstraintLimits._fields_ + [(n, C.c_double) for n in _QC_LIMITS_ALL]
+
+
+class QualityConstraintRecordAll(C.Structure):
+    """smgpu_quality_constraint_record_all: QualityConstraintRecordFull's fields, then the four counts of DESIGN.md 10.18"""
+    _fields_ = QualityConstraintRecordFull._fields_ + [(n, C.c_int64) for n in ("nConcaveFaces", "nWarpedFaces", "nSmallAreaFaces", "nSmallVolumeCells")]
+
+
+class QualityConstraintStateAll(C.Structure):
+    """smgpu_quality_constraint_state_all"""
+    _fields_ = QualityConstraintStateFull._fields_ + [(n, C.c_double) for n in _QC_LIMITS_ALL] + [("nExemptVolumeCells", C.c_int64)]
+
+
 class TangleHaloDesc(C.Structure):
     """smgpu_tangle_halo_desc"""
     _fields_ = [("sendT", C.c_void_p), ("recvT", C.c_void_p)]
@@ -321,6 +339,10 @@ SYMBOLS = {
     "smgpu_get_quality_constraint_state_full": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintStateFull)]),
     "smgpu_set_quality_constraint_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintParams), C.POINTER(QualityConstraintHaloDesc), C.c_int32]),
     "smgpu_set_quality_constraint_limits_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintLimits), C.POINTER(QualityConstraintHaloDescFull), C.c_int32]),
+    "smgpu_set_quality_constraint_limits_all": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintLimitsAll), C.c_int32]),
+    "smgpu_set_quality_constraint_limits_all_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintLimitsAll), C.POINTER(QualityConstraintHaloDescFull), C.c_int32]),
+    "smgpu_get_quality_constraint_records_all": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintRecordAll), C.c_int64, C.POINTER(C.c_int64)]),
+    "smgpu_get_quality_constraint_state_all": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintStateAll)]),
     "smgpu_quality_constraint_coupled_exempt": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_begin": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_faces": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

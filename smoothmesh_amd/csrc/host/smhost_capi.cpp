@@ -5,6 +5,7 @@
 
 #include "../../../include/smhost.h"
 #include "polymesh_io.hpp"
+#include "quality_dict.hpp"
 
 using namespace smhost;
 namespace smhost {
@@ -34,6 +35,23 @@ int smhost_read_polymesh(const char* dir, const char* pointsDir, smhost_mesh** o
     });
 }
 void smhost_mesh_free(smhost_mesh* m) { delete m; }
+
+int smhost_read_mesh_quality_dict(const char* path, const char* const* etcDirs, int32_t nEtcDirs, double* values, int32_t* found, char* ignored,
+                                  int64_t* ignoredLen) {
+    if (!path || !values || !found || !ignoredLen || (nEtcDirs > 0 && !etcDirs)) { g_err = "smhost_read_mesh_quality_dict: null argument"; return 1; }
+    return guarded([&] {
+        std::vector<std::string> dirs;
+        for (int32_t i = 0; i < nEtcDirs; ++i) dirs.push_back(etcDirs[i] ? etcDirs[i] : "");
+        MeshQualityDict d;
+        readMeshQualityDict(path, dirs, d);
+        for (int i = 0; i < kQualityDictKeys; ++i) { values[i] = d.value[i]; found[i] = d.found[i] ? 1 : 0; }
+        std::string all;
+        for (const std::string& k : d.ignored) all += k + "\n";
+        const int64_t need = (int64_t)all.size() + 1, have = ignored ? *ignoredLen : 0;
+        if (have >= need) std::memcpy(ignored, all.c_str(), (size_t)need);
+        *ignoredLen = need;
+    });
+}
 
 int smhost_mesh_sizes(const smhost_mesh* m, int32_t* nPoints, int32_t* nCells, int32_t* nFaces, int32_t* nInternalFaces,
                       int32_t* nPatches, int64_t* nnz) {

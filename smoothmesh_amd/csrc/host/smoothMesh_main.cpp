@@ -42,6 +42,7 @@
 #include "../../../include/smgpu.h"
 #include "node_comm.hpp"
 #include "polymesh_io.hpp"
+#include "quality_dict.hpp"
 
 using namespace smhost;
 
@@ -98,7 +99,8 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "relTol", "writeInterval", "case", "writeFormat", "device", "checkQuality", "writeSets", "allGeometry",
                                "meshQuality", "qualityInterval", "qualityGuard", "qualityGuardRefine", "tangleConstraint", "tanglePasses",
                                "qualityConstraint", "maxNonOrtho", "maxInternalSkewness", "maxBoundarySkewness", "qualityConstraintPasses",
-                               "minTetQuality", "minTwist", "minTriangleTwist", "minFaceWeight", "minVolRatio", "minDeterminant"};
+                               "minTetQuality", "minTwist", "minTriangleTwist", "minFaceWeight", "minVolRatio", "minDeterminant",
+                               "maxConcave", "minFlatness", "minVol", "minArea", "meshQualityDict"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -132,6 +134,12 @@ Options parseArgs(int argc, char** argv) {
                       "       [-minTetQuality x -minTwist x -minTriangleTwist x -minFaceWeight x -minVolRatio x -minDeterminant x]  (with -qualityConstraint:\n"
                       "        further limits of meshQualityDict, by the measures of -meshQuality and -allGeometry; each is off unless given, and off at\n"
                       "        minTetQuality <= -1e30, a twist limit <= -1, minFaceWeight, minVolRatio or minDeterminant <= 0)\n"
+                      "       [-maxConcave deg -minFlatness x -minVol x -minArea x]  (with -qualityConstraint: the last four limits of meshQualityDict:\n"
+                      "        the sharpest concave corner of a face, face flatness, cell volume and face area, by the measures of -allGeometry and\n"
+                      "        -checkQuality; each is off unless given, and off at maxConcave >= 180 and at a limit <= 0)\n"
+                      "       [-meshQualityDict true|file]  (with -qualityConstraint: take the thirteen limits from system/meshQualityDict, or from file,\n"
+                      "        relative to the case; an option given on the command line wins over the file's entry, a key in neither keeps the option's\n"
+                      "        default; #includeEtc looks under $WM_PROJECT_DIR/etc and $FOAM_ETC; the relaxed sub-dictionary is not read)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -561,8 +569,33 @@ int main(int argc, char** argv) {
     if (opt.found("tanglePasses") && !tangleConstraint) fatal("-tanglePasses needs -tangleConstraint true");
     if (tangleConstraint && (tanglePasses < 0 || tanglePasses > 0x7fffffffL)) fatal("tanglePasses must be between 0 and 2147483647");
     const bool qualityConstraint = opt.getB("qualityConstraint", false);
-    const double qcMaxNonOrtho = opt.getD("maxNonOrtho", 65.0), qcMaxInternalSkewness = opt.getD("maxInternalSkewness", 4.0),
-                 qcMaxBoundarySkewness = opt.getD("maxBoundarySkewness", 20.0);
+    // -meshQualityDict true|<file>: the limits of system/meshQualityDict, read before any device work; an option
+    // given on the command line wins over the file's entry, a key absent from both keeps the option's default
+    MeshQualityDict qcDict;
+    std::string qcDictPath;
+    if (opt.found("meshQualityDict")) {
+        if (!qualityConstraint) fatal("-meshQualityDict needs -qualityConstraint true");
+        std::string v = opt.kv.at("meshQualityDict"), low = v;
+        std::transform(low.begin(), low.end(), low.begin(), ::tolower);
+        if (low == "true" || low == "on" || low == "yes") v = "system/meshQualityDict";
+        if (!(low == "false" || low == "off" || low == "no" || low == "none")) {
+            qcDictPath = (!v.empty() && v[0] == '/') ? v : opt.caseDir + "/" + v;
+            std::vector<std::string> etc;
+            if (const char* w = std::getenv("WM_PROJECT_DIR")) etc.push_back(std::string(w) + "/etc");
+            if (const char* f = std::getenv("FOAM_ETC")) etc.push_back(f);
+            try { readMeshQualityDict(qcDictPath, etc, qcDict); }
+            catch (const std::exception& e) { fatal(std::string("-meshQualityDict: ") + e.what()); }
+        }
+    }
+    // (the value of limit `name`: the option's, else the file's, else def; given: from either source)
+    auto qcLimit = [&](const char* name, double def, bool* given) {
+        if (opt.found(name)) { if (given) *given = true; return opt.getD(name, def); }
+        for (int k = 0; k < kQualityDictKeys; ++k)
+            if (qcDict.found[k] && std::string(kQualityDictKeyNames[k]) == name) { if (given) *given = true; return qcDict.value[k]; }
+        return def;
+    };
+    const double qcMaxNonOrtho = qcLimit("maxNonOrtho", 65.0, nullptr), qcMaxInternalSkewness = qcLimit("maxInternalSkewness", 4.0, nullptr),
+                 qcMaxBoundarySkewness = qcLimit("maxBoundarySkewness", 20.0, nullptr);
     const long qcPasses = opt.getL("qualityConstraintPasses", 2);
     for (const char* k : {"maxNonOrtho", "maxInternalSkewness", "maxBoundarySkewness", "qualityConstraintPasses"})
         if (opt.found(k) && !qualityConstraint) fatal(std::string("-") + k + " needs -qualityConstraint true");
@@ -572,11 +605,27 @@ int main(int argc, char** argv) {
     double qcMore[6];
     bool qcMoreGiven = false;
     for (int k = 0; k < 6; ++k) {
-        qcMore[k] = opt.getD(qcMoreNames[k], qcMoreOff[k]);
-        if (!opt.found(qcMoreNames[k])) continue;
+        bool given = false;
+        qcMore[k] = qcLimit(qcMoreNames[k], qcMoreOff[k], &given);
+        if (!given) continue;
         if (!qualityConstraint) fatal(std::string("-") + qcMoreNames[k] + " needs -qualityConstraint true");
         if (qcMore[k] != qcMore[k]) fatal(std::string("-") + qcMoreNames[k] + " must be a number");
         qcMoreGiven = true;
+    }
+    // the limits of DESIGN.md 10.18, each off unless given; qcLastOn: one of them is on, from either source -- then the entry, the
+    // records and the lines are 10.18's, else every line is what it was
+    const char* const qcLastNames[4] = {"maxConcave", "minFlatness", "minVol", "minArea"};
+    const double qcLastOff[4] = {180.0, 0.0, 0.0, 0.0};
+    double qcLast[4];
+    bool qcLastOn = false;
+    for (int k = 0; k < 4; ++k) {
+        bool given = false;
+        qcLast[k] = qcLimit(qcLastNames[k], qcLastOff[k], &given);
+        if (!given) continue;
+        if (!qualityConstraint) fatal(std::string("-") + qcLastNames[k] + " needs -qualityConstraint true");
+        if (qcLast[k] != qcLast[k]) fatal(std::string("-") + qcLastNames[k] + " must be a number");
+        if (k == 0 && qcLast[k] < 0.0) fatal("-maxConcave must not be negative");
+        qcLastOn = qcLastOn || (k == 0 ? qcLast[k] < 180.0 : qcLast[k] > 0.0);
     }
     if (qualityConstraint && opt.parallel)
         fatal("-qualityConstraint is not available with -parallel: it judges the faces and cells by the measure of the quality report, which is serial only");
@@ -1310,25 +1359,39 @@ int main(int argc, char** argv) {
     }
     // -qualityConstraint: the same with limits on non-orthogonality and skewness (smgpu_set_quality_constraint)
     // with one of -minTetQuality ... -minDeterminant: the entry, the records and the lines of 10.16; without, those of 10.14 as they were
-    std::vector<smgpu_quality_constraint_record_full> qcRecords;
+    // with one of -maxConcave -minFlatness -minVol -minArea on: the entry, the records and the lines of 10.18
+    std::vector<smgpu_quality_constraint_record_all> qcRecords;
     if (qualityConstraint) {
         const smgpu_quality_constraint_params qp{qcMaxNonOrtho, qcMaxInternalSkewness, qcMaxBoundarySkewness, (int32_t)qcPasses};
         const smgpu_quality_constraint_limits ql{qcMaxNonOrtho, qcMaxInternalSkewness, qcMaxBoundarySkewness, (int32_t)qcPasses,
                                                  qcMore[0], qcMore[1], qcMore[2], qcMore[3], qcMore[4], qcMore[5]};
-        if (qcMoreGiven) check(smgpu_set_quality_constraint_limits(R[0].h, &ql, 1), "smgpu_set_quality_constraint_limits");
+        const smgpu_quality_constraint_limits_all qa{qcMaxNonOrtho, qcMaxInternalSkewness, qcMaxBoundarySkewness, (int32_t)qcPasses,
+                                                     qcMore[0], qcMore[1], qcMore[2], qcMore[3], qcMore[4], qcMore[5], qcLast[0], qcLast[1], qcLast[2], qcLast[3]};
+        if (qcLastOn) check(smgpu_set_quality_constraint_limits_all(R[0].h, &qa, 1), "smgpu_set_quality_constraint_limits_all");
+        else if (qcMoreGiven) check(smgpu_set_quality_constraint_limits(R[0].h, &ql, 1), "smgpu_set_quality_constraint_limits");
         else check(smgpu_set_quality_constraint(R[0].h, &qp, 1), "smgpu_set_quality_constraint");
         smgpu_quality_constraint_state qs{};
         check(smgpu_get_quality_constraint_state(R[0].h, &qs), "smgpu_get_quality_constraint_state");
         OUT("Quality constraint: maxNonOrtho %g maxInternalSkewness %g maxBoundarySkewness %g, %lld exempt cells, %lld exempt faces, %d passes\n", qs.maxNonOrtho,
             qs.maxInternalSkewness, qs.maxBoundarySkewness, (long long)qs.nExemptCells, (long long)qs.nExemptFaces, (int)qs.passes);
-        if (qcMoreGiven) {
-            smgpu_quality_constraint_state_full qf{};
-            check(smgpu_get_quality_constraint_state_full(R[0].h, &qf), "smgpu_get_quality_constraint_state_full");
+        if (qcMoreGiven || qcLastOn) {
+            smgpu_quality_constraint_state_all qf{};
+            check(smgpu_get_quality_constraint_state_all(R[0].h, &qf), "smgpu_get_quality_constraint_state_all");
             const double now[6] = {qf.minTetQuality, qf.minTwist, qf.minTriangleTwist, qf.minFaceWeight, qf.minVolRatio, qf.minDeterminant};
+            const double last[4] = {qf.maxConcave, qf.minFlatness, qf.minVol, qf.minArea};
             OUT("Quality constraint limits:");
             for (int k = 0; k < 6; ++k)
                 if (now[k] > qcMoreOff[k]) OUT(" %s %g", qcMoreNames[k], now[k]);
-            OUT(", %lld determinant-exempt cells\n", (long long)qf.nExemptDeterminantCells);
+            for (int k = 0; k < 4; ++k)
+                if (k == 0 ? last[k] < 180.0 : last[k] > 0.0) OUT(" %s %g", qcLastNames[k], last[k]);
+            OUT(", %lld determinant-exempt cells", (long long)qf.nExemptDeterminantCells);
+            if (qcLastOn) OUT(", %lld volume-exempt cells", (long long)qf.nExemptVolumeCells);
+            OUT("\n");
+        }
+        if (!qcDictPath.empty()) {
+            OUT("Quality constraint: limits from %s", qcDictPath.c_str());
+            for (size_t k = 0; k < qcDict.ignored.size(); ++k) OUT("%s%s", k == 0 ? ", ignored: " : " ", qcDict.ignored[k].c_str());
+            OUT("\n");
         }
     }
     // -qualityGuard: the guard on that history (include/smgpu.h, smgpu_set_quality_guard), armed on the initial
@@ -1420,9 +1483,9 @@ int main(int argc, char** argv) {
         size_t nextQc = 0;
         if (qualityConstraint) {
             int64_t nRecords = 0;
-            check(smgpu_get_quality_constraint_records_full(R[0].h, nullptr, 0, &nRecords), "smgpu_get_quality_constraint_records_full");
+            check(smgpu_get_quality_constraint_records_all(R[0].h, nullptr, 0, &nRecords), "smgpu_get_quality_constraint_records_all");
             qcRecords.resize((size_t)nRecords);
-            if (nRecords > 0) check(smgpu_get_quality_constraint_records_full(R[0].h, qcRecords.data(), nRecords, &nRecords), "smgpu_get_quality_constraint_records_full");
+            if (nRecords > 0) check(smgpu_get_quality_constraint_records_all(R[0].h, qcRecords.data(), nRecords, &nRecords), "smgpu_get_quality_constraint_records_all");
         }
         for (int32_t k = 0; k < done; ++k) {
             OUT("Smoothing iteration=%ld nFrozenPoints=%d residual=%g\n", i + k + 1, stats[(size_t)k].nFrozenPoints, stats[(size_t)k].residual);
@@ -1433,8 +1496,16 @@ int main(int argc, char** argv) {
                         (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
             }
             if (nextQc < qcRecords.size() && qcRecords[nextQc].iteration == (int64_t)(i + k + 1)) {
-                const smgpu_quality_constraint_record_full& t = qcRecords[nextQc++];
-                if (t.nBadCells > 0 && qcMoreGiven)
+                const smgpu_quality_constraint_record_all& t = qcRecords[nextQc++];
+                if (t.nBadCells > 0 && qcLastOn)
+                    OUT("    quality constraint iteration=%lld badCells %lld tangled %lld nonOrthoFaces %lld skewFaces %lld lowTetFaces %lld twistedFaces %lld "
+                        "lowTriangleTwistFaces %lld lowWeightFaces %lld lowVolRatioFaces %lld underdeterminedCells %lld concaveFaces %lld warpedFaces %lld "
+                        "smallAreaFaces %lld smallVolumeCells %lld passes %d pointsReverted %lld%s\n",
+                        (long long)t.iteration, (long long)t.nBadCells, (long long)t.nTangledCells, (long long)t.nNonOrthoFaces, (long long)t.nSkewFaces,
+                        (long long)t.nLowTetFaces, (long long)t.nLowTwistFaces, (long long)t.nLowTriangleTwistFaces, (long long)t.nLowWeightFaces,
+                        (long long)t.nLowVolRatioFaces, (long long)t.nUnderdeterminedCells, (long long)t.nConcaveFaces, (long long)t.nWarpedFaces,
+                        (long long)t.nSmallAreaFaces, (long long)t.nSmallVolumeCells, (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
+                else if (t.nBadCells > 0 && qcMoreGiven)
                     OUT("    quality constraint iteration=%lld badCells %lld tangled %lld nonOrthoFaces %lld skewFaces %lld lowTetFaces %lld twistedFaces %lld "
                         "lowTriangleTwistFaces %lld lowWeightFaces %lld lowVolRatioFaces %lld underdeterminedCells %lld passes %d pointsReverted %lld%s\n",
                         (long long)t.iteration, (long long)t.nBadCells, (long long)t.nTangledCells, (long long)t.nNonOrthoFaces, (long long)t.nSkewFaces,

@@ -43,6 +43,9 @@ struct QcDev {
     // 10.16 (kernels_quality_limits.hpp): bad faces, not exempt, by tet quality, twist, triangle twist, weight, volume ratio; cells
     // under the determinant limit, not determinant-exempt (enabling: the determinant-exempt cells).  0 while none of them is on
     int lowTetNow, lowTwistNow, lowTriNow, lowWeightNow, lowRatioNow, underDetNow;
+    // 10.18: bad faces, not exempt, by concavity, flatness, area; cells under the volume limit, not volume-exempt (enabling: the
+    // volume-exempt cells).  0 while none of them is on
+    int concaveNow, warpedNow, smallAreaNow, smallVolNow;
 };
 static_assert(offsetof(QcDev, t) == 0, "k_tangle_apply takes a QcDev as its TangleDev");
 static_assert(offsetof(smgpu_quality_constraint_record, iteration) == offsetof(smgpu_tangle_record, iteration) &&
@@ -55,6 +58,9 @@ static_assert(offsetof(smgpu_quality_constraint_record, iteration) == offsetof(s
 static_assert(offsetof(smgpu_quality_constraint_record_full, nSkewFaces) == offsetof(smgpu_quality_constraint_record, nSkewFaces) &&
               offsetof(smgpu_quality_constraint_record_full, nLowTetFaces) == sizeof(smgpu_quality_constraint_record),
               "the narrow record is the head of the full one: smgpu_get_quality_constraint_records copies it out of the full slots");
+static_assert(offsetof(smgpu_quality_constraint_record_all, nUnderdeterminedCells) == offsetof(smgpu_quality_constraint_record_full, nUnderdeterminedCells) &&
+              offsetof(smgpu_quality_constraint_record_all, nConcaveFaces) == sizeof(smgpu_quality_constraint_record_full),
+              "the full record is the head of the widest one, which the slab holds: the narrower getters copy their prefix");
 
 // the limits as the kernels test them; a criterion that is off never fires
 struct QcLimits { double cosT, maxInternalSkew, maxBoundarySkew; int nonOrthoOn, internalSkewOn, boundarySkewOn; };
@@ -244,21 +250,24 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_cells(MeshView m, const double*
 
 // k_tangle_verdict's twin: one wave, lane 0 writes everything in plain C++.  It also keeps the stop word of the next pass's
 // geometry launch.  rec: the iteration's slot of the call's record slab (zeroed by the call).  The six words of 10.16 are 0 while
-// none of its limits is on, and so are the record's six counts.
-__global__ void __launch_bounds__(64) k_qc_verdict(QcDev* __restrict__ d, Accum* __restrict__ acc, smgpu_quality_constraint_record_full* __restrict__ rec,
+// none of its limits is on, and so are the record's six counts; likewise the four of 10.18.
+__global__ void __launch_bounds__(64) k_qc_verdict(QcDev* __restrict__ d, Accum* __restrict__ acc, smgpu_quality_constraint_record_all* __restrict__ rec,
                                                     long long number, int pass, int passes, const smgpu_iter_stats* gate) {
     if (threadIdx.x != 0) return;
     if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
     const int nBad = d->t.badNow, nTangled = d->tangledNow, nNO = d->nonOrthoNow, nSk = d->skewNow;
     const int nTet = d->lowTetNow, nTw = d->lowTwistNow, nTri = d->lowTriNow, nW = d->lowWeightNow, nR = d->lowRatioNow, nDet = d->underDetNow;
     d->t.badNow = 0; d->tangledNow = 0; d->nonOrthoNow = 0; d->skewNow = 0; d->facesNow = 0;
+    const int nConc = d->concaveNow, nWarp = d->warpedNow, nArea = d->smallAreaNow, nVol = d->smallVolNow;
     d->lowTetNow = 0; d->lowTwistNow = 0; d->lowTriNow = 0; d->lowWeightNow = 0; d->lowRatioNow = 0; d->underDetNow = 0;
+    d->concaveNow = 0; d->warpedNow = 0; d->smallAreaNow = 0; d->smallVolNow = 0;
     if (pass == 0) {
-        smgpu_quality_constraint_record_full r;
+        smgpu_quality_constraint_record_all r;
         r.iteration = number; r.passes = 0; r.fullRevert = 0; r.nBadCells = nBad; r.nPointsReverted = 0;
         r.nTangledCells = nTangled; r.nNonOrthoFaces = nNO; r.nSkewFaces = nSk;
         r.nLowTetFaces = nTet; r.nLowTwistFaces = nTw; r.nLowTriangleTwistFaces = nTri; r.nLowWeightFaces = nW; r.nLowVolRatioFaces = nR;
         r.nUnderdeterminedCells = nDet;
+        r.nConcaveFaces = nConc; r.nWarpedFaces = nWarp; r.nSmallAreaFaces = nArea; r.nSmallVolumeCells = nVol;
         *rec = r;
     }
     if (nBad == 0) { d->t.clean = 1; d->t.full = 0; acc->stop = 1; return; }
@@ -267,11 +276,11 @@ __global__ void __launch_bounds__(64) k_qc_verdict(QcDev* __restrict__ d, Accum*
     else { d->t.full = 0; rec->passes += 1; }
 }
 
-// k_tangle_close's twin: closes the record of an iteration of the coupled form from the host's verdict.  n: the rank's ten counts
+// k_tangle_close's twin: closes the record of an iteration of the coupled form from the host's verdict.  n: the rank's fourteen counts
 // at k = 0 in the record's order from nBadCells on, without nPointsReverted (the applies': the slot was zeroed before the
 // iteration's first pass).  One wave, lane 0 writes every word in plain C++.
-struct QcCounts { long long n[10]; };
-__global__ void __launch_bounds__(64) k_qc_close(smgpu_quality_constraint_record_full* __restrict__ rec, long long number, int passes, int fullRevert,
+struct QcCounts { long long n[14]; };
+__global__ void __launch_bounds__(64) k_qc_close(smgpu_quality_constraint_record_all* __restrict__ rec, long long number, int passes, int fullRevert,
                                                   QcCounts c) {
     if (threadIdx.x != 0) return;
     rec->iteration = number;
@@ -287,6 +296,10 @@ __global__ void __launch_bounds__(64) k_qc_close(smgpu_quality_constraint_record
     rec->nLowWeightFaces = c.n[7];
     rec->nLowVolRatioFaces = c.n[8];
     rec->nUnderdeterminedCells = c.n[9];
+    rec->nConcaveFaces = c.n[10];
+    rec->nWarpedFaces = c.n[11];
+    rec->nSmallAreaFaces = c.n[12];
+    rec->nSmallVolumeCells = c.n[13];
 }
 
 }  // namespace smgpu

@@ -27,6 +27,13 @@
 //     and counts only on the counted side.
 // Every difference between the two forms is an `if constexpr (Coupled)` of the helpers qcSlot, qcNeighbourCentre
 // (kernels_quality_constraint.hpp), qcCounts and qcNeighbourVolume: the serial instantiation compiles the serial lines alone.
+//
+// The last four limits (smgpu_set_quality_constraint_limits_all, 10.18) ride in the same two kernels behind a template parameter
+// of their own, so that an instantiation without them is the one of 10.16, register for register:
+//   k_qc_cells_more<.., Vol>: minVol on the V_c it forms; bit 1 of the exemption byte (bit 0: the determinant), smallVolNow;
+//   k_qc_faces_more<.., Shape>: 0 none; 1 minArea on |S_f|; 2 also maxConcave and minFlatness by qgFaceOne's lines
+//     (kernels_quality_geom.hpp) in the one vertex walk the kernel makes -- Walk's loop, or with Walk off a loop of their own with
+//     the skewness line in it.  A processor face is judged on the rank's own vertex order, as 10.8's report does.
 #pragma once
 #include "kernels_quality_constraint.hpp"
 #include "kernels_quality_geom.hpp"
@@ -36,6 +43,9 @@ namespace smgpu {
 
 // the limits as the kernels test them; k: the tets' normalisation, formed by the host as the motion report forms it
 struct QcMore { double minTet, minTwist, minTri, minWeight, minRatio, minDet, k; int tetOn, twistOn, triOn, weightOn, ratioOn, detOn; };
+
+// the limits of 10.18 as the kernels test them; sinConcave: formed by the host as the geometry report forms its own
+struct QcShape { double sinConcave, minFlat, minArea, minVol; int concaveOn, flatOn, areaOn, volOn; };
 
 // does face f enter a cell's determinant: an internal face of the global mesh -- on a sub-domain qgcCounts
 // (kernels_quality_geom.hpp), without processor faces the same bits
@@ -53,15 +63,16 @@ __device__ __forceinline__ double qcNeighbourVolume(const double* __restrict__ v
 
 // V_c into vol and det_c of cell c: qgCellOne's lines (kernels_quality_geom.hpp), nothing else of it -- keep them alike.
 // exemptOut != NULL (enabling): the determinant verdict goes to exemptOut[c], no cell is flagged, underDetNow counts them.
-template <bool Det, bool Coupled>
+// Vol (10.18): V_c < minVol; the exemption byte is then a bit set -- bit 0 determinant, bit 1 volume -- and smallVolNow counts.
+template <bool Det, bool Coupled, bool Vol>
 __global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const double* __restrict__ fCtr, const double* __restrict__ fArea,
-                                                             QCoupling<Coupled> cp, QcMore lim, double* __restrict__ vol, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
+                                                             QCoupling<Coupled> cp, QcMore lim, QcShape sh, double* __restrict__ vol, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
                                                              uint8_t* __restrict__ cellFlag, QcDev* __restrict__ d, int pass, const smgpu_iter_stats* gate) {
     if constexpr (!Coupled) {   // (the coupled form is never gated, and the test cost it 0.05 - 0.2 %: profiles/quality/README.md)
         if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
     }
     const int c = blockIdx.x * kQcBlock + threadIdx.x;
-    bool bad = false;
+    bool bad = false, badV = false;
     if (c < m.nCells) {
         const int b = m.cfOff[c], e = m.cfOff[c + 1];
         V3 cEst = v3(0, 0, 0);
@@ -78,7 +89,9 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const do
             pyr += p;
             if (Det && qcCounts(m, cp, f)) { sumA += mag(Sf); ++nInt; }
         }
-        vol[c] = (1.0 / 3.0) * pyr;
+        const double Vc = (1.0 / 3.0) * pyr;
+        vol[c] = Vc;
+        if constexpr (Vol) badV = sh.volOn && Vc < sh.minVol;
         if constexpr (Det) {
             double det = 0.0;
             const double avgA = nInt > 0 ? sumA / (double)nInt : 0.0;
@@ -94,10 +107,21 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const do
                 det = fabs((xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz)) + xz * (xy * yz - yy * xz)) / 8.0;
             }
             bad = det < lim.minDet;
-            if (exemptOut) exemptOut[c] = bad ? 1 : 0;
+            if constexpr (!Vol) {
+                if (exemptOut) exemptOut[c] = bad ? 1 : 0;
+                else {
+                    bad = bad && !exempt[c];
+                    if (bad) cellFlag[c] = 1;
+                }
+            }
+        }
+        if constexpr (Vol) {
+            if (exemptOut) exemptOut[c] = (uint8_t)((bad ? 1 : 0) | (badV ? 2 : 0));
             else {
-                bad = bad && !exempt[c];
-                if (bad) cellFlag[c] = 1;
+                const int ex = exempt[c];
+                bad = bad && !(ex & 1);
+                badV = badV && !(ex & 2);
+                if (bad || badV) cellFlag[c] = 1;
             }
         }
     }
@@ -105,23 +129,31 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_cells_more(MeshView m, const do
         const int nBad = __syncthreads_count(bad ? 1 : 0);
         if (nBad > 0 && threadIdx.x == 0) atomicAdd(&d->underDetNow, nBad);
     }
+    if constexpr (Vol) {
+        const int nBadV = __syncthreads_count(badV ? 1 : 0);
+        if (nBadV > 0 && threadIdx.x == 0) atomicAdd(&d->smallVolNow, nBadV);
+    }
 }
 
 // k_qc_faces with the new face criteria.  The lines up to fd are qcFace's, the walk is qmFaceOne's first walk with the skewness
 // loop's line in it (both read the vertices in the face's order; fmax and fmin do not depend on it), weight and ratio are
 // qgFaceOne's lines: keep each alike.  exemptOut != NULL (enabling): as k_qc_faces.  Coupled: the slot is decoded as k_qc_faces
 // decodes it; `internal` is "internal face of the global mesh", `inner` "both cells are this rank's".
-template <bool Walk, bool Ratio, bool Coupled>
+// Shape (10.18): 1 the area verdict on magSf; 2 also concavity and flatness, qgFaceOne's lines (kernels_quality_geom.hpp: the unit
+// edge that ends in the current point carried, the first kept for corner 0; the triangles' magnitudes summed in ascending i,
+// without the twist's mt > VSMALL test) -- keep them alike.  They share Walk's loop; with Walk off the loop is theirs.
+template <bool Walk, bool Ratio, bool Coupled, int Shape>
 __global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const double* __restrict__ pts, const double* __restrict__ fCtr,
                                                              const double* __restrict__ fArea, const double* __restrict__ cellCtr,
                                                              const double* __restrict__ vol, const int* __restrict__ own, const int* __restrict__ nei,
-                                                             QCoupling<Coupled> cp, QcLimits lim, QcMore more, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
+                                                             QCoupling<Coupled> cp, QcLimits lim, QcMore more, QcShape sh, const uint8_t* __restrict__ exempt, uint8_t* __restrict__ exemptOut,
                                                              uint8_t* __restrict__ cellFlag, QcDev* __restrict__ d, int pass, const smgpu_iter_stats* gate) {
     if constexpr (!Coupled) {   // (the coupled form is never gated, and the test cost it 0.05 - 0.2 %: profiles/quality/README.md)
         if (!qTraceRan(gate) || (pass > 0 && d->t.clean)) return;
     }
     const int f = blockIdx.x * kQcBlock + threadIdx.x;
     bool badNO = false, badSk = false, badTet = false, badTw = false, badTri = false, badW = false, badR = false, counted = true;
+    bool badConc = false, badFlat = false, badArea = false;
     if (f < m.nFaces) {
         const bool inner = f < m.nInternalFaces;
         const int sl = qcSlot(m, cp, f);
@@ -145,21 +177,34 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const do
         const V3 sHat = sv / (magSv + SMGPU_ROOTVSMALL);
         double fd = 0.2 * mag(dd) + SMGPU_ROOTVSMALL;
         const int jb = m.faceOff[f], nv = m.faceOff[f + 1] - jb;
-        if constexpr (Walk) {
+        if constexpr (Walk || Shape == 2) {
             const bool summed = nv > 3;
             double tet = __builtin_inf(), tw = __builtin_inf(), tri = __builtin_inf();
+            double conc = 0.0, area = 0.0;
             int nValid = 0;
             if (nv > 0) {
                 const V3 dv = sel3(internal, CN, Cf) - CO;
                 const V3 nHat = dv / (mag(dv) + SMGPU_VSMALL);
+                const V3 nS = Sf / (magSf + SMGPU_ROOTVSMALL);
                 const V3 p0 = ldv(pts, m.facePts[jb]);
                 V3 cur = p0, hFirst = v3(0, 0, 0), hPrev = v3(0, 0, 0);
+                V3 eFirst = v3(0, 0, 0), ePrev = v3(0, 0, 0);
+                bool okFirst = false, okPrev = false;
                 for (int i = 0; i < nv; ++i) {
                     fd = fmax(fd, fabs(dot(sHat, cur - Cf)));
                     const V3 nxt = (i + 1 < nv) ? ldv(pts, m.facePts[jb + i + 1]) : p0;
                     const V3 u = nxt - cur, v = Cf - cur;
-                    tet = fmin(tet, qmTetPair(cur, u, v, CO, internal, CN, more.k));
-                    if (summed) {
+                    if constexpr (Walk) tet = fmin(tet, qmTetPair(cur, u, v, CO, internal, CN, more.k));
+                    if constexpr (Shape == 2) {
+                        const double len = mag(u);
+                        const V3 eNext = u / (len + SMGPU_ROOTVSMALL);
+                        const bool okNext = len > kQualitySmall;
+                        area += 0.5 * mag(cross(u, v));
+                        if (i > 0) conc = fmax(conc, qgCorner(ePrev, eNext, okPrev && okNext, nS, sh.sinConcave));
+                        else { eFirst = eNext; okFirst = okNext; }
+                        ePrev = eNext; okPrev = okNext;
+                    }
+                    if (Walk && summed) {
                         const V3 t = 0.5 * cross(u, v);
                         const double mt = mag(t);
                         if (mt > SMGPU_VSMALL) {
@@ -174,15 +219,23 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const do
                     cur = nxt;
                 }
                 if (nValid >= 2) tri = fmin(tri, dot(hPrev, hFirst));
+                if constexpr (Shape == 2) conc = fmax(conc, qgCorner(ePrev, eFirst, okPrev && okFirst, nS, sh.sinConcave));   // corner 0
             }
-            if (nValid < 1) tw = 1.0;
-            if (nValid < 2) tri = 1.0;
-            badTet = more.tetOn && tet < more.minTet;
-            badTw = summed && more.twistOn && tw < more.minTwist;
-            badTri = summed && more.triOn && tri < more.minTri;
+            if constexpr (Walk) {
+                if (nValid < 1) tw = 1.0;
+                if (nValid < 2) tri = 1.0;
+                badTet = more.tetOn && tet < more.minTet;
+                badTw = summed && more.twistOn && tw < more.minTwist;
+                badTri = summed && more.triOn && tri < more.minTri;
+            }
+            if constexpr (Shape == 2) {
+                badConc = sh.concaveOn && conc > kQualitySmall;
+                badFlat = sh.flatOn && summed && magSf > SMGPU_ROOTVSMALL && magSf / (area + SMGPU_ROOTVSMALL) < sh.minFlat;
+            }
         } else {
             for (int j = jb; j < jb + nv; ++j) fd = fmax(fd, fabs(dot(sHat, ldv(pts, m.facePts[j]) - Cf)));
         }
+        if constexpr (Shape >= 1) badArea = sh.areaOn && magSf < sh.minArea;
         const double skew = magSv / fd;
         badNO = internal && lim.nonOrthoOn && ortho < lim.cosT;
         badSk = internal ? (lim.internalSkewOn && skew > lim.maxInternalSkew) : (lim.boundarySkewOn && skew > lim.maxBoundarySkew);
@@ -196,23 +249,30 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const do
                 badR = more.ratioOn && r < more.minRatio;
             }
         }
-        const bool any = badNO || badSk || badTet || badTw || badTri || badW || badR;
+        const bool any = badNO || badSk || badTet || badTw || badTri || badW || badR || badConc || badFlat || badArea;
         if (exemptOut) exemptOut[f] = any ? 1 : 0;
-        else if (exempt[f]) badNO = badSk = badTet = badTw = badTri = badW = badR = false;
+        else if (exempt[f]) badNO = badSk = badTet = badTw = badTri = badW = badR = badConc = badFlat = badArea = false;
         else if (any) {
             cellFlag[o] = 1;
             if (inner) cellFlag[n] = 1;
         }
     }
-    const bool any = badNO || badSk || badTet || badTw || badTri || badW || badR;
+    const bool any = badNO || badSk || badTet || badTw || badTri || badW || badR || badConc || badFlat || badArea;
     const int nNO = __syncthreads_count((badNO && counted) ? 1 : 0), nSk = __syncthreads_count((badSk && counted) ? 1 : 0),
               nAny = __syncthreads_count((any && counted) ? 1 : 0);
-    int nTet = 0, nTw = 0, nTri = 0, nW = 0, nR = 0;
+    int nTet = 0, nTw = 0, nTri = 0, nW = 0, nR = 0, nConc = 0, nFlat = 0, nArea = 0;
     if (Walk && more.tetOn) nTet = __syncthreads_count((badTet && counted) ? 1 : 0);
     if (Walk && more.twistOn) nTw = __syncthreads_count((badTw && counted) ? 1 : 0);
     if (Walk && more.triOn) nTri = __syncthreads_count((badTri && counted) ? 1 : 0);
     if (more.weightOn) nW = __syncthreads_count((badW && counted) ? 1 : 0);
     if (Ratio && more.ratioOn) nR = __syncthreads_count((badR && counted) ? 1 : 0);
+    if constexpr (Shape == 2) {
+        if (sh.concaveOn) nConc = __syncthreads_count((badConc && counted) ? 1 : 0);
+        if (sh.flatOn) nFlat = __syncthreads_count((badFlat && counted) ? 1 : 0);
+    }
+    if constexpr (Shape >= 1) {
+        if (sh.areaOn) nArea = __syncthreads_count((badArea && counted) ? 1 : 0);
+    }
     if (threadIdx.x == 0) {
         if (nNO > 0) atomicAdd(&d->nonOrthoNow, nNO);
         if (nSk > 0) atomicAdd(&d->skewNow, nSk);
@@ -222,6 +282,9 @@ __global__ void __launch_bounds__(kQcBlock) k_qc_faces_more(MeshView m, const do
         if (nTri > 0) atomicAdd(&d->lowTriNow, nTri);
         if (nW > 0) atomicAdd(&d->lowWeightNow, nW);
         if (nR > 0) atomicAdd(&d->lowRatioNow, nR);
+        if (nConc > 0) atomicAdd(&d->concaveNow, nConc);
+        if (nFlat > 0) atomicAdd(&d->warpedNow, nFlat);
+        if (nArea > 0) atomicAdd(&d->smallAreaNow, nArea);
     }
 }
 

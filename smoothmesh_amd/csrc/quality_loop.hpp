@@ -482,11 +482,22 @@ static QcMore qualityConstraintMore(const smgpu_quality_constraint_limits& l) {
                   l.minTetQuality > -1e30 ? 1 : 0, l.minTwist > -1.0 ? 1 : 0, l.minTriangleTwist > -1.0 ? 1 : 0,
                   l.minFaceWeight > 0.0 ? 1 : 0, l.minVolRatio > 0.0 ? 1 : 0, l.minDeterminant > 0.0 ? 1 : 0};
 }
+// the limits of 10.18 as the kernels take them, and maxConcave as given (the state's); sinConcave exactly as
+// qualityGeomThresholds() (quality_reports.hpp) forms the geometry report's sine
+struct QcShapeLimits { QcShape k; double maxConcave; };
+static QcShapeLimits qualityConstraintShape(double maxConcave, double minFlatness, double minVol, double minArea) {
+    return QcShapeLimits{QcShape{std::sin(maxConcave * (SMGPU_PI / 180.0)), minFlatness, minArea, minVol, maxConcave < 180.0 ? 1 : 0, minFlatness > 0.0 ? 1 : 0,
+                                 minArea > 0.0 ? 1 : 0, minVol > 0.0 ? 1 : 0},
+                         maxConcave};
+}
+static const QcShapeLimits kQcShapeOff = qualityConstraintShape(180.0, 0.0, 0.0, 0.0);
 static int qualityConstraintOff(smgpu_handle* h) {
     h->qc.on = false;
     h->qc.more = qualityConstraintMore(kQcLimitsDefault);
+    h->qc.shape = kQcShapeOff.k;
+    h->qc.maxConcave = kQcShapeOff.maxConcave;
     h->qc.faceMore = h->qc.cellMore = false;
-    h->qc.nExemptDet = 0;
+    h->qc.nExemptDet = h->qc.nExemptVol = 0;
     h->qc.slab.discard();
     if (h->qc.block.live()) {
         HIP_OK(hipStreamSynchronize(h->stream));
@@ -503,6 +514,14 @@ template <class Fn>
 static void withQcCoupling(const QualityConstraintHost& q, Fn fn) {
     if (q.coupled) fn(std::true_type{}, QCoupling<true>{q.slot, q.recvCc, q.recvVc});
     else fn(std::false_type{}, QCoupling<false>{});
+}
+// the instantiations of kernels_quality_limits.hpp's two kernels a set of limits takes
+template <bool C, bool Vol>
+static auto qcCellsMoreOf(bool det) { return det ? k_qc_cells_more<true, C, Vol> : k_qc_cells_more<false, C, Vol>; }
+template <bool C, int Shape>
+static auto qcFacesMoreOf(bool walk, bool ratio) {
+    return walk ? (ratio ? k_qc_faces_more<true, true, C, Shape> : k_qc_faces_more<true, false, C, Shape>)
+                : (ratio ? k_qc_faces_more<false, true, C, Shape> : k_qc_faces_more<false, false, C, Shape>);
 }
 }
 // The geometry half.  Tiles: k_qc_tile writes fCtr / fArea, which no kernel of the tiled loop reads, and cell centres of the
@@ -537,9 +556,9 @@ static int qualityConstraintGeometry(smgpu_handle* h, bool enabling, int pass, c
     if (q.cellMore && m.nCells > 0)
         withQcCoupling(q, [&](auto coupled, auto cp) {
             constexpr bool C = decltype(coupled)::value;
-            auto cells = q.more.detOn ? k_qc_cells_more<true, C> : k_qc_cells_more<false, C>;
+            auto cells = q.shape.volOn ? qcCellsMoreOf<C, true>(q.more.detOn != 0) : qcCellsMoreOf<C, false>(q.more.detOn != 0);
             hipLaunchKernelGGL(cells, dim3((m.nCells + kQcBlock - 1) / kQcBlock), dim3(kQcBlock), 0, h->stream, m, (const double*)ts.fCtr, (const double*)ts.fArea, cp,
-                               q.more, q.vol, enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptDet, enabling ? q.exemptDet : (uint8_t*)nullptr, q.cellFlag,
+                               q.more, q.shape, q.vol, enabling ? (const uint8_t*)nullptr : (const uint8_t*)q.exemptDet, enabling ? q.exemptDet : (uint8_t*)nullptr, q.cellFlag,
                                q.dev, pass, gate);
         });
     HIP_OK(hipGetLastError());
@@ -558,10 +577,12 @@ static int qualityConstraintVerdicts(smgpu_handle* h, bool enabling, int pass, c
             const dim3 grid((m.nFaces + kQcBlock - 1) / kQcBlock);
             if (q.faceMore) {
                 const bool walk = q.more.tetOn || q.more.twistOn || q.more.triOn, ratio = q.more.ratioOn != 0;
-                auto faces = walk ? (ratio ? k_qc_faces_more<true, true, C> : k_qc_faces_more<true, false, C>)
-                                  : (ratio ? k_qc_faces_more<false, true, C> : k_qc_faces_more<false, false, C>);
+                // (10.18: the area verdict alone needs no walk; concavity and flatness share the one the kernel makes)
+                auto faces = (q.shape.concaveOn || q.shape.flatOn) ? qcFacesMoreOf<C, 2>(walk, ratio)
+                             : q.shape.areaOn                      ? qcFacesMoreOf<C, 1>(walk, ratio)
+                                                                   : qcFacesMoreOf<C, 0>(walk, ratio);
                 hipLaunchKernelGGL(faces, grid, dim3(kQcBlock), 0, h->stream, m, pts, fCtr, fArea, cellCtr, (const double*)q.vol, (const int*)h->q.own,
-                                   (const int*)h->q.nei, cp, q.lim, q.more, exemptFace, exemptFaceOut, q.cellFlag, q.dev, pass, gate);
+                                   (const int*)h->q.nei, cp, q.lim, q.more, q.shape, exemptFace, exemptFaceOut, q.cellFlag, q.dev, pass, gate);
             } else
                 hipLaunchKernelGGL(k_qc_faces<C>, grid, dim3(kQcBlock), 0, h->stream, m, pts, fCtr, fArea, cellCtr, (const int*)h->q.own, (const int*)h->q.nei, cp,
                                    q.lim, exemptFace, exemptFaceOut, q.cellFlag, q.dev, pass, gate);
@@ -583,7 +604,7 @@ static int qualityConstraintEvaluate(smgpu_handle* h, bool enabling, int pass, c
 // behind the movePoints of an iteration: the passes on the points ptsCur now names; x: the points the iteration started from
 static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x) {
     QualityConstraintHost& q = h->qc;
-    smgpu_quality_constraint_record_full* rec = nullptr;
+    smgpu_quality_constraint_record_all* rec = nullptr;
     if (q.slab.slot(slot, &rec)) return 1;
     const int nP = h->mv.nPoints;
     const int gApply = std::max(1, (int)(((int64_t)nP + kTanglePts - 1) / kTanglePts));
@@ -600,12 +621,14 @@ static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, con
 
 // What enabling shares between the serial and the coupled form.  First the refusals both make first, in their order; api names
 // the entry called; coupled: the form, which wants an engine with a halo, where `serial` names the entry a serial engine takes
-static int qualityConstraintRefusals(smgpu_handle* h, const std::string& api, const smgpu_quality_constraint_params& prm, const QcMore& more, bool coupled,
-                                     const char* serial) {
+static int qualityConstraintRefusals(smgpu_handle* h, const std::string& api, const smgpu_quality_constraint_params& prm, const QcMore& more,
+                                     const QcShapeLimits& shape, bool coupled, const char* serial) {
     if (prm.passes < 0) return fail(api + ": passes < 0");
     if (std::isnan(prm.maxNonOrtho) || std::isnan(prm.maxInternalSkewness) || std::isnan(prm.maxBoundarySkewness) || std::isnan(more.minTet) ||
-        std::isnan(more.minTwist) || std::isnan(more.minTri) || std::isnan(more.minWeight) || std::isnan(more.minRatio) || std::isnan(more.minDet))
+        std::isnan(more.minTwist) || std::isnan(more.minTri) || std::isnan(more.minWeight) || std::isnan(more.minRatio) || std::isnan(more.minDet) ||
+        std::isnan(shape.maxConcave) || std::isnan(shape.k.minFlat) || std::isnan(shape.k.minVol) || std::isnan(shape.k.minArea))
         return fail(api + ": a limit is NaN");
+    if (shape.maxConcave < 0.0) return fail(api + ": maxConcave < 0");
     if (!coupled && h->haloOn) return fail(kQualityHaloRefusal);
     if (coupled && !h->haloOn) return fail(api + ": the engine has no halo (smgpu_halo_configure); a serial engine takes " + serial);
     if (h->bndOn)
@@ -617,7 +640,7 @@ static int qualityConstraintRefusals(smgpu_handle* h, const std::string& api, co
     return 0;
 }
 // ... then, every refusal made: the constraint that was on goes, and the buffers, limits and launch choices of the new one are set
-static int qualityConstraintAllocate(smgpu_handle* h, const smgpu_quality_constraint_params& prm, const QcMore& more) {
+static int qualityConstraintAllocate(smgpu_handle* h, const smgpu_quality_constraint_params& prm, const QcMore& more, const QcShapeLimits& shape) {
     if (qualityConstraintOff(h)) return 1;
     if (flushDeferred(h)) return 1;
     if (qualityEnsure(h)) return 1;                  // owner / neighbour by face
@@ -628,8 +651,10 @@ static int qualityConstraintAllocate(smgpu_handle* h, const smgpu_quality_constr
         q.block.alloc(&q.marks, nMark) || q.block.alloc(&q.cellCtr, 3 * nCell) || q.block.alloc(&q.acc, 1))
         return q.block.failed("the quality constraint");
     q.more = more;
-    q.faceMore = more.tetOn || more.twistOn || more.triOn || more.weightOn || more.ratioOn;
-    q.cellMore = more.ratioOn || more.detOn;
+    q.shape = shape.k;
+    q.maxConcave = shape.maxConcave;
+    q.faceMore = more.tetOn || more.twistOn || more.triOn || more.weightOn || more.ratioOn || shape.k.concaveOn || shape.k.flatOn || shape.k.areaOn;
+    q.cellMore = more.ratioOn || more.detOn || shape.k.volOn;
     if (q.cellMore && (q.block.alloc(&q.vol, nCell) || q.block.alloc(&q.exemptDet, nCell))) return q.block.failed("the quality constraint");
     HIP_OK(hipMemsetAsync(q.dev, 0, sizeof(QcDev), h->stream));
     HIP_OK(hipMemsetAsync(q.exemptCell, 0, nCell, h->stream));
@@ -647,13 +672,14 @@ static int qualityConstraintAllocate(smgpu_handle* h, const smgpu_quality_constr
     return 0;
 }
 
-// the two entries of the serial constraint: name names the one called, in its refusals; more: the limits of 10.16 (all off under
-// smgpu_set_quality_constraint)
-static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgpu_quality_constraint_params& prm, const QcMore& more) {
+// the three entries of the serial constraint: name names the one called, in its refusals; more: the limits of 10.16 (all off
+// under smgpu_set_quality_constraint); shape: those of 10.18 (all off under the two older entries)
+static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgpu_quality_constraint_params& prm, const QcMore& more,
+                                   const QcShapeLimits& shape = kQcShapeOff) {
     const std::string api(name);
-    if (qualityConstraintRefusals(h, api, prm, more, false, nullptr)) return 1;
+    if (qualityConstraintRefusals(h, api, prm, more, shape, false, nullptr)) return 1;
     if (h->iterOpen) return fail(api + ": between smgpu_iter_begin and smgpu_iter_end");
-    if (qualityConstraintAllocate(h, prm, more)) return 1;
+    if (qualityConstraintAllocate(h, prm, more, shape)) return 1;
     QualityConstraintHost& q = h->qc;
     // the exempt cells and faces: one evaluation of the current points
     if (qualityConstraintEvaluate(h, true, 0, nullptr)) { q.release(); return 1; }
@@ -664,6 +690,7 @@ static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgp
     q.nExemptCells = qd.t.badNow;
     q.nExemptFaces = qd.facesNow;
     q.nExemptDet = qd.underDetNow;
+    q.nExemptVol = qd.smallVolNow;
     q.since = h->iterCount;
     q.on = true;
     return 0;
@@ -683,7 +710,49 @@ int smgpu_set_quality_constraint_limits(smgpu_handle* h, const smgpu_quality_con
     return qualityConstraintEnable(h, "smgpu_set_quality_constraint_limits", smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
                                    qualityConstraintMore(l));
 }
+// 10.18's limits: the head of the struct is smgpu_quality_constraint_limits at its offsets
+static_assert(offsetof(smgpu_quality_constraint_limits_all, passes) == offsetof(smgpu_quality_constraint_limits, passes) &&
+              offsetof(smgpu_quality_constraint_limits_all, minTetQuality) == offsetof(smgpu_quality_constraint_limits, minTetQuality) &&
+              offsetof(smgpu_quality_constraint_limits_all, minDeterminant) == offsetof(smgpu_quality_constraint_limits, minDeterminant) &&
+              offsetof(smgpu_quality_constraint_limits_all, maxConcave) == sizeof(smgpu_quality_constraint_limits),
+              "smgpu_quality_constraint_limits is the head of smgpu_quality_constraint_limits_all");
+static_assert(offsetof(smgpu_quality_constraint_state_all, nExemptDeterminantCells) == offsetof(smgpu_quality_constraint_state_full, nExemptDeterminantCells) &&
+              offsetof(smgpu_quality_constraint_state_all, maxConcave) == sizeof(smgpu_quality_constraint_state_full),
+              "smgpu_quality_constraint_state_full is the head of smgpu_quality_constraint_state_all");
+static const smgpu_quality_constraint_limits_all kQcLimitsAllDefault{65.0, 4.0, 20.0, 2, -1e30, -1.0, -1.0, 0.0, 0.0, 0.0, 180.0, 0.0, 0.0, 0.0};
+static smgpu_quality_constraint_limits qualityConstraintHead(const smgpu_quality_constraint_limits_all& l) {
+    return smgpu_quality_constraint_limits{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes, l.minTetQuality, l.minTwist, l.minTriangleTwist,
+                                           l.minFaceWeight, l.minVolRatio, l.minDeterminant};
+}
+int smgpu_set_quality_constraint_limits_all(smgpu_handle* h, const smgpu_quality_constraint_limits_all* p, int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityConstraintOff(h);
+    const smgpu_quality_constraint_limits_all l = p ? *p : kQcLimitsAllDefault;
+    return qualityConstraintEnable(h, "smgpu_set_quality_constraint_limits_all",
+                                   smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
+                                   qualityConstraintMore(qualityConstraintHead(l)), qualityConstraintShape(l.maxConcave, l.minFlatness, l.minVol, l.minArea));
+}
 static int qualityConstraintCoupledFlush(smgpu_handle* h);
+int smgpu_get_quality_constraint_records_all(smgpu_handle* h, smgpu_quality_constraint_record_all* out, int64_t cap, int64_t* n) {
+    if (!h || !n) return fail("null argument");
+    if (h->qc.coupled) {
+        if (h->qc.k >= 0) return fail("smgpu_get_quality_constraint_records_all: between the passes of an iteration (smgpu_quality_constraint_pass_begin / _end)");
+        HIP_OK(hipSetDevice(h->device));
+        if (qualityConstraintCoupledFlush(h)) return 1;
+    }
+    return h->qc.slab.drain(out, cap, n, "smgpu_get_quality_constraint_records_all");
+}
+int smgpu_get_quality_constraint_state_all(smgpu_handle* h, smgpu_quality_constraint_state_all* out) {
+    if (!h || !out) return fail("null argument");
+    smgpu_quality_constraint_state_full s{};
+    if (smgpu_get_quality_constraint_state_full(h, &s)) return 1;
+    const QualityConstraintHost& q = h->qc;
+    *out = smgpu_quality_constraint_state_all{s.on, s.passes, s.maxNonOrtho, s.maxInternalSkewness, s.maxBoundarySkewness, s.nExemptCells, s.nExemptFaces, s.iteration,
+                                              s.minTetQuality, s.minTwist, s.minTriangleTwist, s.minFaceWeight, s.minVolRatio, s.minDeterminant,
+                                              s.nExemptDeterminantCells, q.maxConcave, q.shape.minFlat, q.shape.minVol, q.shape.minArea, s.on ? q.nExemptVol : 0};
+    return 0;
+}
 int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n) {
     if (!h || !n) return fail("null argument");
     if (h->qc.coupled) {   // the records of the chunk in use are still on the device
@@ -700,7 +769,7 @@ int smgpu_get_quality_constraint_records_full(smgpu_handle* h, smgpu_quality_con
         HIP_OK(hipSetDevice(h->device));
         if (qualityConstraintCoupledFlush(h)) return 1;
     }
-    return h->qc.slab.drain(out, cap, n, "smgpu_get_quality_constraint_records_full");
+    return h->qc.slab.drainHeads(out, cap, n, "smgpu_get_quality_constraint_records_full");
 }
 int smgpu_get_quality_constraint_state_full(smgpu_handle* h, smgpu_quality_constraint_state_full* out) {
     if (!h || !out) return fail("null argument");
@@ -770,9 +839,10 @@ static int qualityConstraintCoupledVerdicts(smgpu_handle* h, bool enabling, QcDe
 // refusals; full: smgpu_set_quality_constraint_limits_coupled (10.17) with the limits of 10.16 in more and its two volume buffers
 // in d; else more is all off and d's tail null
 static int qualityConstraintCoupledEnable(smgpu_handle* h, const char* name, bool full, const smgpu_quality_constraint_params& prm, const QcMore& more,
-                                          const smgpu_quality_constraint_halo_desc_full* d) {
+                                          const smgpu_quality_constraint_halo_desc_full* d, const QcShapeLimits& shape = kQcShapeOff, const char* serial = nullptr) {
     const std::string api(name);
-    if (qualityConstraintRefusals(h, api, prm, more, true, full ? "smgpu_set_quality_constraint_limits" : "smgpu_set_quality_constraint")) return 1;
+    if (!serial) serial = full ? "smgpu_set_quality_constraint_limits" : "smgpu_set_quality_constraint";
+    if (qualityConstraintRefusals(h, api, prm, more, shape, true, serial)) return 1;
     if (h->qc.on && h->qc.coupled && h->qc.full != full)
         return fail(api + ": the quality constraint is on through " + (full ? "smgpu_set_quality_constraint_coupled" : "smgpu_set_quality_constraint_limits_coupled") +
                     "; switch it off first");
@@ -785,7 +855,7 @@ static int qualityConstraintCoupledEnable(smgpu_handle* h, const char* name, boo
     if (qualityCouplingTables(name, m, d->coupling, key, procFace, slot, nProc, notCounted)) return 1;
     if (nProc > 0 && (!d->sendCc || !d->recvCc)) return fail(api + ": null exchange buffer");
     if (nProc > 0 && more.ratioOn && (!d->sendVc || !d->recvVc)) return fail(api + ": null exchange buffer (minVolRatio is on: sendVc / recvVc)");
-    if (qualityConstraintAllocate(h, prm, more)) return 1;
+    if (qualityConstraintAllocate(h, prm, more, shape)) return 1;
     const size_t nB = (size_t)(m.nFaces - m.nInternalFaces);
     QualityConstraintHost& q = h->qc;
     if (q.block.alloc(&q.counted, (size_t)std::max(1, h->nShared)) || q.block.alloc(&q.procFace, (size_t)std::max<int64_t>(1, nProc)) ||
@@ -836,6 +906,17 @@ int smgpu_set_quality_constraint_limits_coupled(smgpu_handle* h, const smgpu_qua
                                           smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
                                           qualityConstraintMore(l), d);
 }
+int smgpu_set_quality_constraint_limits_all_coupled(smgpu_handle* h, const smgpu_quality_constraint_limits_all* p, const smgpu_quality_constraint_halo_desc_full* d,
+                                                    int32_t on) {
+    if (!h) return fail("null handle");
+    HIP_OK(hipSetDevice(h->device));
+    if (!on) return qualityConstraintOff(h);
+    const smgpu_quality_constraint_limits_all l = p ? *p : kQcLimitsAllDefault;
+    return qualityConstraintCoupledEnable(h, "smgpu_set_quality_constraint_limits_all_coupled", true,
+                                          smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
+                                          qualityConstraintMore(qualityConstraintHead(l)), d, qualityConstraintShape(l.maxConcave, l.minFlatness, l.minVol, l.minArea),
+                                          "smgpu_set_quality_constraint_limits_all");
+}
 int smgpu_quality_constraint_coupled_exempt(smgpu_handle* h) {
     if (!h) return fail("null handle");
     QualityConstraintHost& q = h->qc;
@@ -848,6 +929,7 @@ int smgpu_quality_constraint_coupled_exempt(smgpu_handle* h) {
     q.nExemptCells = qd.t.badNow;
     q.nExemptFaces = qd.facesNow;
     q.nExemptDet = qd.underDetNow;
+    q.nExemptVol = qd.smallVolNow;
     q.pending = false;
     return 0;
 }
@@ -887,6 +969,7 @@ int smgpu_quality_constraint_pass_faces(smgpu_handle* h, int64_t* nBadLocal) {
     if (q.k == 0) {
         q.n0[0] = qd.t.badNow; q.n0[1] = qd.tangledNow; q.n0[2] = qd.nonOrthoNow; q.n0[3] = qd.skewNow;
         q.n0[4] = qd.lowTetNow; q.n0[5] = qd.lowTwistNow; q.n0[6] = qd.lowTriNow; q.n0[7] = qd.lowWeightNow; q.n0[8] = qd.lowRatioNow; q.n0[9] = qd.underDetNow;
+        q.n0[10] = qd.concaveNow; q.n0[11] = qd.warpedNow; q.n0[12] = qd.smallAreaNow; q.n0[13] = qd.smallVolNow;
     }
     q.stage = 2;
     *nBadLocal = qd.t.badNow;
@@ -899,15 +982,15 @@ int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32
     if (q.stage != 2 || q.k < 0) return fail("smgpu_quality_constraint_pass_end without smgpu_quality_constraint_pass_faces");
     if (nBadGlobal < 0) return fail("smgpu_quality_constraint_pass_end: nBadGlobal < 0");
     HIP_OK(hipSetDevice(h->device));
-    smgpu_quality_constraint_record_full* rec = nullptr;
+    smgpu_quality_constraint_record_all* rec = nullptr;
     if (q.slab.slot(q.slabUsed, &rec)) return 1;
     const bool full = nBadGlobal > 0 && q.k == q.prm.passes;
     // the record begins with the tangle constraint's (kernels_quality_constraint.hpp)
     if (nBadGlobal > 0 && coupledRevert(h, full, q.recvT, q.marks, q.x, q.counted, reinterpret_cast<smgpu_tangle_record*>(rec), q.reverting)) return 1;
     const bool close = nBadGlobal == 0 || full;
     if (close) {
-        QcCounts c{};   // (10.15's entry: the six counts of 10.16 are 0, as the zeroed slot's were)
-        for (int i = 0; i < 10; ++i) c.n[i] = (long long)q.n0[i];
+        QcCounts c{};   // (10.15's entry: the counts of 10.16 and 10.18 are 0, as the zeroed slot's were)
+        for (int i = 0; i < 14; ++i) c.n[i] = (long long)q.n0[i];
         hipLaunchKernelGGL(k_qc_close, dim3(1), dim3(64), 0, h->stream, rec, (long long)(q.count + 1), q.reverting, full ? 1 : 0, c);
         ++q.count;
         ++q.slabUsed;

@@ -212,15 +212,20 @@ struct QualityConstraintHost {
     QcDev* dev = nullptr;
     double* cellCtr = nullptr;
     Accum* acc = nullptr;
-    // one record per iteration of the call; without the limits of 10.16 the six counts behind its head,
-    // smgpu_quality_constraint_record, are 0
-    RecordSlab<smgpu_quality_constraint_record_full> slab{"quality constraint"};
+    // one record per iteration of the call, the widest for every entry; without the limits of 10.16 the six counts behind its
+    // head, smgpu_quality_constraint_record, are 0, and without those of 10.18 the four behind them
+    RecordSlab<smgpu_quality_constraint_record_all> slab{"quality constraint"};
     // the limits of 10.16 (smgpu_set_quality_constraint_limits, kernels_quality_limits.hpp).  faceMore: a new face criterion is
     // on; cellMore: minVolRatio or minDeterminant is; with neither the launches are 10.14's.  vol, exemptDet: allocated with
     // cellMore, 8 bytes and 1 byte per cell
     QcMore more{-1e30, -1.0, -1.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0};
     bool faceMore = false, cellMore = false;
     int64_t nExemptDet = 0;
+    // the limits of 10.18 (smgpu_set_quality_constraint_limits_all): maxConcave in degrees as given, its sine in shape; a face
+    // criterion of theirs sets faceMore, minVol cellMore; exemptDet then holds a bit set (bit 0 determinant, bit 1 volume)
+    double maxConcave = 180.0;
+    QcShape shape{0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0};
+    int64_t nExemptVol = 0;
     double* vol = nullptr;
     uint8_t* exemptDet = nullptr;
     // the coupled form (smgpu_set_quality_constraint_coupled, 10.15) on an engine with a halo: TangleHost's coupled members with
@@ -232,10 +237,10 @@ struct QualityConstraintHost {
     static constexpr int kChunk = 256;
     bool coupled = false, pending = false, slabFresh = false;
     int k = -1, stage = 0, reverting = 0, slabUsed = 0, nProc = 0;
-    // (full: enabled through smgpu_set_quality_constraint_limits_coupled, 10.17, which the refusal of the other coupled entry
-    // names; sendVc / recvVc: the caller's volume buffers, one double per processor face, used while minVolRatio is on)
+    // (full: enabled through smgpu_set_quality_constraint_limits_coupled, 10.17, or _limits_all_coupled, 10.18, which the
+    // refusal of the other coupled entry names; sendVc / recvVc: the caller's volume buffers, one double per processor face, used while minVolRatio is on)
     bool full = false;
-    int64_t count = 0, n0[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t count = 0, n0[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     double *sendVc = nullptr, *recvVc = nullptr;
     const double* x = nullptr;
     uint8_t* counted = nullptr;

@@ -210,6 +210,42 @@ class QualityConstraintStateFull(QualityConstraintState):
     nExemptDeterminantCells: int = 0
 
 
+# the limits of DESIGN.md "Mesh quality", 10.18, in the order of smgpu_quality_constraint_limits_all's tail, with the value at
+# which each is off (maxConcave: at or above it; the others: at or below it)
+QUALITY_CONSTRAINT_LIMITS_ALL_OFF = dict(maxConcave=180.0, minFlatness=0.0, minVol=0.0, minArea=0.0)
+
+
+def quality_constraint_limits_all_on(**limits):
+    """the limits of QUALITY_CONSTRAINT_LIMITS_ALL_OFF among `limits` that are on (None: off; a NaN counts, to be refused), by name"""
+    bad = set(limits) - set(QUALITY_CONSTRAINT_LIMITS_ALL_OFF)
+    if bad:
+        raise TypeError(f"set_quality_constraint: unknown limit {sorted(bad)[0]}")
+    return {k: float(v) for k, v in limits.items()
+            if v is not None and not (float(v) >= 180.0 if k == "maxConcave" else float(v) <= QUALITY_CONSTRAINT_LIMITS_ALL_OFF[k])}
+
+
+@dataclass
+class QualityConstraintRecordAll(QualityConstraintRecordFull):
+    """smgpu_quality_constraint_record_all (DESIGN.md "Mesh quality", 10.18): QualityConstraintRecordFull, then the faces that were
+    bad after the loop's move by concavity, flatness and area and the cells under the volume limit (a face that fails several
+    counts in each; exempt elements never count).  All 0 while none of these limits is on."""
+    nConcaveFaces: int = 0
+    nWarpedFaces: int = 0
+    nSmallAreaFaces: int = 0
+    nSmallVolumeCells: int = 0
+
+
+@dataclass
+class QualityConstraintStateAll(QualityConstraintStateFull):
+    """smgpu_quality_constraint_state_all: QualityConstraintStateFull, then the four limits of 10.18 (their off values while they
+    are off) and the cells exempt from the volume limit"""
+    maxConcave: float = 180.0
+    minFlatness: float = 0.0
+    minVol: float = 0.0
+    minArea: float = 0.0
+    nExemptVolumeCells: int = 0
+
+
 @dataclass
 class TangleState:
     """smgpu_tangle_state: whether the constraint is on, its passes, the cells exempt since enabling, the running number"""
@@ -744,7 +780,8 @@ class SmoothEngine:
         return TangleState(on=bool(s.on), passes=s.passes, nExemptCells=s.nExemptCells, iteration=s.iteration)
 
     def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
-                               minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None):
+                               minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
+                               maxConcave=None, minFlatness=None, minVol=None, minArea=None):
         """Quality constraint (include/smgpu.h, smgpu_set_quality_constraint; DESIGN.md "Mesh quality", 10.14): the tangle
         constraint with limits on face non-orthogonality (degrees; >= 180: off) and on the skewness of internal and of boundary
         faces (<= 0: off).  From now on iterate() puts the points of every cell that an iteration turned bad -- by the tangle
@@ -754,9 +791,20 @@ class SmoothEngine:
         constraint on.
         The six further limits (smgpu_set_quality_constraint_limits; None: off) make a face bad whose face-centre
         tet quality, twist, triangle twist, interpolation weight or volume ratio lies under them, and a cell whose determinant
-        does, by the measures of mesh_quality_motion / mesh_quality_geometry; with all six None the call is what it was."""
+        does, by the measures of mesh_quality_motion / mesh_quality_geometry; with all six None the call is what it was.
+        The last four (smgpu_set_quality_constraint_limits_all; None: off) make a face bad that has a concave
+        corner sharper than maxConcave degrees (mesh_quality_geometry's faceConcavity with concaveThreshold = maxConcave), whose
+        flatness lies under minFlatness or whose area under minArea, and a cell whose volume lies under minVol; with all four
+        None the call goes through the entry it went through before."""
         more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
                     minVolRatio=minVolRatio, minDeterminant=minDeterminant)
+        last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
+        if any(v is not None for v in last.values()):
+            more = {k: QUALITY_CONSTRAINT_LIMITS_OFF[k] if v is None else float(v) for k, v in more.items()}
+            last = {k: QUALITY_CONSTRAINT_LIMITS_ALL_OFF[k] if v is None else float(v) for k, v in last.items()}
+            p = _ffi.QualityConstraintLimitsAll(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more, **last)
+            self._check(self._lib.smgpu_set_quality_constraint_limits_all(self._h, C.byref(p), 1))
+            return
         if all(v is None for v in more.values()):
             p = _ffi.QualityConstraintParams(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes))
             self._check(self._lib.smgpu_set_quality_constraint(self._h, C.byref(p), 1))
@@ -787,7 +835,8 @@ class SmoothEngine:
 
     def set_quality_constraint_limits_coupled(self, coupling, sendT, recvT, sendCc, recvCc, sendVc=0, recvVc=0, maxNonOrtho=65.0,
                                               maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None, minTwist=None,
-                                              minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None):
+                                              minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None, maxConcave=None,
+                                              minFlatness=None, minVol=None, minArea=None):
         """set_quality_constraint_coupled with the six further limits (include/smgpu.h, smgpu_set_quality_constraint_limits_coupled;
         DESIGN.md "Mesh quality", 10.17; None: off).  sendVc / recvVc: raw device addresses of one double per processor face, needed
         while minVolRatio is on: the call returns with sendVc packed next to sendCc, the caller moves both, and so behind every
@@ -800,8 +849,14 @@ class SmoothEngine:
         more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
                     minVolRatio=minVolRatio, minDeterminant=minDeterminant)
         more = {k: QUALITY_CONSTRAINT_LIMITS_OFF[k] if v is None else float(v) for k, v in more.items()}
-        p = _ffi.QualityConstraintLimits(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more)
         d = _ffi.QualityConstraintHaloDescFull(sendT or None, recvT or None, sendCc or None, recvCc or None, C.pointer(c), sendVc or None, recvVc or None)
+        last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
+        if any(v is not None for v in last.values()):   # (with all four None: the entry of 10.17, as before)
+            last = {k: QUALITY_CONSTRAINT_LIMITS_ALL_OFF[k] if v is None else float(v) for k, v in last.items()}
+            p = _ffi.QualityConstraintLimitsAll(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more, **last)
+            self._check(self._lib.smgpu_set_quality_constraint_limits_all_coupled(self._h, C.byref(p), C.byref(d), 1))
+            return
+        p = _ffi.QualityConstraintLimits(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more)
         self._check(self._lib.smgpu_set_quality_constraint_limits_coupled(self._h, C.byref(p), C.byref(d), 1))
 
     def quality_constraint_coupled_exempt(self):
@@ -825,20 +880,20 @@ class SmoothEngine:
         return bool(done.value)
 
     def quality_constraint_records(self) -> list:
-        """The pending records of the quality constraint (QualityConstraintRecordFull), one per iteration that ran, in ascending
+        """The pending records of the quality constraint (QualityConstraintRecordAll), one per iteration that ran, in ascending
         iteration; clears them."""
         n = C.c_int64(0)
-        self._check(self._lib.smgpu_get_quality_constraint_records_full(self._h, None, 0, C.byref(n)))
+        self._check(self._lib.smgpu_get_quality_constraint_records_all(self._h, None, 0, C.byref(n)))
         if n.value == 0:
             return []
-        buf = (_ffi.QualityConstraintRecordFull * n.value)()
-        self._check(self._lib.smgpu_get_quality_constraint_records_full(self._h, buf, n.value, C.byref(n)))
-        return [QualityConstraintRecordFull(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+        buf = (_ffi.QualityConstraintRecordAll * n.value)()
+        self._check(self._lib.smgpu_get_quality_constraint_records_all(self._h, buf, n.value, C.byref(n)))
+        return [QualityConstraintRecordAll(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
 
-    def quality_constraint_state(self) -> QualityConstraintStateFull:
-        s = _ffi.QualityConstraintStateFull()
-        self._check(self._lib.smgpu_get_quality_constraint_state_full(self._h, C.byref(s)))
-        return QualityConstraintStateFull(on=bool(s.on), **{f: getattr(s, f) for f, _ in s._fields_ if f != "on"})
+    def quality_constraint_state(self) -> QualityConstraintStateAll:
+        s = _ffi.QualityConstraintStateAll()
+        self._check(self._lib.smgpu_get_quality_constraint_state_all(self._h, C.byref(s)))
+        return QualityConstraintStateAll(on=bool(s.on), **{f: getattr(s, f) for f, _ in s._fields_ if f != "on"})
 
     def quality_field(self, name) -> np.ndarray:
         """Per-element quality field in polyMesh order: one of QUALITY_FIELDS (non-orthogonality in degrees, 0 on boundary faces)."""

@@ -197,10 +197,21 @@ def combine_tangle_records(per_rank):
     return out
 
 
+def _wants_volumes(more):
+    """do the limits given to _enable_quality_constraint need sendVc / recvVc: minVolRatio is on"""
+    v = None if more is None else more.get("minVolRatio")
+    return v is not None and not float(v) <= 0.0
+
+
 def _refuse_more_limits(more):
-    """the limits of DESIGN.md "Mesh quality", 10.16, are the serial engine's: a decomposed mesh refuses one that is on"""
-    from .engine import quality_constraint_limits_on
-    on = quality_constraint_limits_on(**more)
+    """the limits of DESIGN.md "Mesh quality", 10.16 and 10.18, are set_quality_constraint_limits' and _limits_all's:
+    set_quality_constraint on a decomposed mesh refuses one that is on"""
+    from .engine import QUALITY_CONSTRAINT_LIMITS_ALL_OFF, quality_constraint_limits_all_on, quality_constraint_limits_on
+    last = quality_constraint_limits_all_on(**{k: v for k, v in more.items() if k in QUALITY_CONSTRAINT_LIMITS_ALL_OFF})
+    if last:
+        raise ValueError(f"set_quality_constraint: {sorted(last)[0]} is not available through set_quality_constraint on a decomposed mesh "
+                         "(set_quality_constraint_limits_all takes the concavity, flatness, volume and area limits); leave it out or pass None")
+    on = quality_constraint_limits_on(**{k: v for k, v in more.items() if k not in QUALITY_CONSTRAINT_LIMITS_ALL_OFF})
     if on:
         raise ValueError(f"set_quality_constraint: {sorted(on)[0]} is not available on a decomposed mesh (the tet, twist, weight, volume ratio and "
                          "determinant limits are judged on a serial engine only); leave it out or pass None")
@@ -210,16 +221,15 @@ def combine_quality_constraint_records(per_rank):
     """the records of the undecomposed mesh from every rank's (DESIGN.md "Mesh quality", 10.15): `passes` and `fullRevert` are
     global values, the same on every rank; the counts are sums (a shared point counts on its master only, a processor face on
     the rank with the lower number)"""
-    from .engine import QualityConstraintRecordFull as QualityConstraintRecord   # (the six counts of 10.16 are 0 under set_quality_constraint)
+    import dataclasses
     out = []
     for recs in zip(*per_rank):
         r0 = recs[0]
         assert all((r.iteration, r.passes, r.fullRevert) == (r0.iteration, r0.passes, r0.fullRevert) for r in recs), recs
-        out.append(QualityConstraintRecord(iteration=r0.iteration, passes=r0.passes, fullRevert=r0.fullRevert,
-                                           **{f: sum(getattr(r, f) for r in recs)
-                                              for f in ("nBadCells", "nPointsReverted", "nTangledCells", "nNonOrthoFaces", "nSkewFaces", "nLowTetFaces",
-                                                        "nLowTwistFaces", "nLowTriangleTwistFaces", "nLowWeightFaces", "nLowVolRatioFaces",
-                                                        "nUnderdeterminedCells")}))
+        # (a record of the ranks' own class: the engine's QualityConstraintRecordAll, whose counts of 10.16 and 10.18 are 0 under
+        # set_quality_constraint; every field behind the three global ones is a count)
+        counts = [f.name for f in dataclasses.fields(r0) if f.name not in ("iteration", "passes", "fullRevert")]
+        out.append(type(r0)(iteration=r0.iteration, passes=r0.passes, fullRevert=r0.fullRevert, **{f: sum(getattr(r, f) for r in recs) for f in counts}))
     assert all(len(r) == len(per_rank[0]) for r in per_rank)
     return out
 
@@ -872,6 +882,21 @@ class DistributedSmoother:
                                         dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist,
                                              minFaceWeight=minFaceWeight, minVolRatio=minVolRatio, minDeterminant=minDeterminant))
 
+    def set_quality_constraint_limits_all(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
+                                          minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
+                                          maxConcave=None, minFlatness=None, minVol=None, minArea=None):
+        """set_quality_constraint_limits with the last four limits of engine.set_quality_constraint behind the six (None: off;
+        smgpu_set_quality_constraint_limits_all_coupled): the keyword arguments that read_mesh_quality_dict
+        returns.  The four are local to a rank: a processor face is judged on the rank's own vertex order, and nothing more
+        travels.  With all four None the engine is called as set_quality_constraint_limits calls it.  Every rank calls it, with
+        the same limits."""
+        more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
+                    minVolRatio=minVolRatio, minDeterminant=minDeterminant)
+        last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
+        if any(v is not None for v in last.values()):
+            more.update(last)
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more)
+
     def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
         """From now on iterate() also keeps face non-orthogonality and skewness under the limits (engine.set_quality_constraint's
         parameters), on the global mesh: a processor face is judged as the internal face it is, with the neighbour rank's cell
@@ -883,8 +908,8 @@ class DistributedSmoother:
 
     def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more):
         """the body of set_quality_constraint (more = None: smgpu_set_quality_constraint_coupled) and of
-        set_quality_constraint_limits (more: the six limits by name, smgpu_set_quality_constraint_limits_coupled)"""
-        from .engine import quality_constraint_limits_on
+        set_quality_constraint_limits (more: the six limits by name, smgpu_set_quality_constraint_limits_coupled) and _limits_all
+        (more: with the four of 10.18 where one is given, smgpu_set_quality_constraint_limits_all_coupled)"""
         torch, st, eng = self.torch, self.state, self.engine
         if self.tangle_passes is not None:
             raise RuntimeError("set_quality_constraint: the tangle constraint is on, and this constraint contains it; clear_tangle_constraint first")
@@ -898,7 +923,7 @@ class DistributedSmoother:
         st.sendCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
         st.recvCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
         st.sendVc = st.recvVc = None
-        if more is not None and "minVolRatio" in quality_constraint_limits_on(**more):
+        if _wants_volumes(more):
             st.sendVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
             st.recvVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
         self.quality_passes = None
@@ -934,11 +959,11 @@ class DistributedSmoother:
         """QualityConstraintState of the decomposed mesh: nExemptCells and nExemptFaces summed over the ranks (a processor face
         counts on one side).  A collective."""
         s = self.engine.quality_constraint_state()
-        t = self.torch.tensor([s.nExemptCells, s.nExemptFaces, s.nExemptDeterminantCells], dtype=self.torch.int64,
+        t = self.torch.tensor([s.nExemptCells, s.nExemptFaces, s.nExemptDeterminantCells, s.nExemptVolumeCells], dtype=self.torch.int64,
                               device="cpu" if self._staged() else self.device)
         if self.world > 1:
             self.dist.all_reduce(t)
-        s.nExemptCells, s.nExemptFaces, s.nExemptDeterminantCells = (int(x) for x in t.tolist())
+        s.nExemptCells, s.nExemptFaces, s.nExemptDeterminantCells, s.nExemptVolumeCells = (int(x) for x in t.tolist())
         return s
 
     def quality_constraint_records(self, per_rank=False):
@@ -1251,6 +1276,17 @@ class LocalMultiSmoother:
                                         dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist,
                                              minFaceWeight=minFaceWeight, minVolRatio=minVolRatio, minDeterminant=minDeterminant))
 
+    def set_quality_constraint_limits_all(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
+                                          minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
+                                          maxConcave=None, minFlatness=None, minVol=None, minArea=None):
+        """as DistributedSmoother.set_quality_constraint_limits_all; nothing more moves for the four"""
+        more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
+                    minVolRatio=minVolRatio, minDeterminant=minDeterminant)
+        last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
+        if any(v is not None for v in last.values()):
+            more.update(last)
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more)
+
     def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
         """as DistributedSmoother.set_quality_constraint; cell centres and marks move by device-side copies"""
         _refuse_more_limits(more)
@@ -1258,7 +1294,6 @@ class LocalMultiSmoother:
 
     def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more):
         """as DistributedSmoother._enable_quality_constraint"""
-        from .engine import quality_constraint_limits_on
         from .quality import paired_offsets
         torch = self.torch
         if self.tangle_passes is not None:
@@ -1273,7 +1308,7 @@ class LocalMultiSmoother:
             st.sendCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
             st.recvCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
             st.sendVc = st.recvVc = None
-            if more is not None and "minVolRatio" in quality_constraint_limits_on(**more):
+            if _wants_volumes(more):
                 st.sendVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
                 st.recvVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
         if self.device.type == "cuda":
@@ -1309,6 +1344,7 @@ class LocalMultiSmoother:
         ss[0].nExemptCells = sum(s.nExemptCells for s in ss)
         ss[0].nExemptFaces = sum(s.nExemptFaces for s in ss)
         ss[0].nExemptDeterminantCells = sum(s.nExemptDeterminantCells for s in ss)
+        ss[0].nExemptVolumeCells = sum(s.nExemptVolumeCells for s in ss)
         return ss[0]
 
     def quality_constraint_records(self, per_rank=False):

@@ -18,7 +18,7 @@ from dataclasses import dataclass, fields
 
 import numpy as np
 
-from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityGuardState, QualityTraceRecord, TangleRecord, TangleState, QualityConstraintRecord, QualityConstraintState, QualityConstraintRecordFull, QualityConstraintStateFull, QUALITY_FIELDS,  # noqa: F401
+from .engine import (MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityGuardState, QualityTraceRecord, TangleRecord, TangleState, QualityConstraintRecord, QualityConstraintState, QualityConstraintRecordFull, QualityConstraintStateFull, QualityConstraintRecordAll, QualityConstraintStateAll, QUALITY_FIELDS,  # noqa: F401
                      QUALITY_GEOMETRY_FIELDS, QUALITY_MOTION_FIELDS, QUALITY_SETS, QUALITY_GEOMETRY_SETS, QUALITY_MOTION_SETS)
 
 QUALITY_DEFAULTS = dict(nonOrthThreshold=70.0, skewThreshold=4.0, closedThreshold=1e-6, aspectThreshold=1000.0)
@@ -455,22 +455,75 @@ def format_tangle_line(rec):
             + (" fullRevert" if rec.fullRevert else "") + "\n")
 
 
-def format_quality_constraint_line(rec, more=False):
+def format_quality_constraint_line(rec, more=False, last=False):
     """the line smoothMesh -qualityConstraint prints under the iteration line of an iteration whose nBadCells > 0 (csrc/host/
     smoothMesh_main.cpp), of a QualityConstraintRecord; more: the line of a run with one of the limits of DESIGN.md 10.16 given
-    (-minTetQuality ... -minDeterminant), of a QualityConstraintRecordFull"""
+    (-minTetQuality ... -minDeterminant), of a QualityConstraintRecordFull; last: the line of a run with one of the limits of 10.18
+    on (-maxConcave -minFlatness -minVol -minArea), which carries the six counts of 10.16 too, of a QualityConstraintRecordAll"""
     extra = (f" lowTetFaces {rec.nLowTetFaces} twistedFaces {rec.nLowTwistFaces} lowTriangleTwistFaces {rec.nLowTriangleTwistFaces} "
-             f"lowWeightFaces {rec.nLowWeightFaces} lowVolRatioFaces {rec.nLowVolRatioFaces} underdeterminedCells {rec.nUnderdeterminedCells}") if more else ""
+             f"lowWeightFaces {rec.nLowWeightFaces} lowVolRatioFaces {rec.nLowVolRatioFaces} underdeterminedCells {rec.nUnderdeterminedCells}") if (more or last) else ""
+    if last:
+        extra += f" concaveFaces {rec.nConcaveFaces} warpedFaces {rec.nWarpedFaces} smallAreaFaces {rec.nSmallAreaFaces} smallVolumeCells {rec.nSmallVolumeCells}"
     return (f"    quality constraint iteration={rec.iteration} badCells {rec.nBadCells} tangled {rec.nTangledCells} nonOrthoFaces {rec.nNonOrthoFaces} "
             f"skewFaces {rec.nSkewFaces}{extra} passes {rec.passes} pointsReverted {rec.nPointsReverted}" + (" fullRevert" if rec.fullRevert else "") + "\n")
 
 
 def format_quality_constraint_limits_line(state):
     """the second set-up line of smoothMesh -qualityConstraint with one of the limits of DESIGN.md 10.16 given: the limits that are
-    on, in the order of smgpu_quality_constraint_limits, and the determinant-exempt cells; of a QualityConstraintStateFull"""
-    from .engine import QUALITY_CONSTRAINT_LIMITS_OFF
+    on, in the order of smgpu_quality_constraint_limits, and the determinant-exempt cells; of a QualityConstraintStateFull.  With one
+    of the limits of 10.18 on (a QualityConstraintStateAll) the line lists it behind the six and gains the volume-exempt cells"""
+    from .engine import QUALITY_CONSTRAINT_LIMITS_ALL_OFF, QUALITY_CONSTRAINT_LIMITS_OFF, quality_constraint_limits_all_on
     on = "".join(f" {k} {getattr(state, k):g}" for k, off in QUALITY_CONSTRAINT_LIMITS_OFF.items() if getattr(state, k) > off)
-    return f"Quality constraint limits:{on}, {state.nExemptDeterminantCells} determinant-exempt cells\n"
+    last = quality_constraint_limits_all_on(**{k: getattr(state, k, None) for k in QUALITY_CONSTRAINT_LIMITS_ALL_OFF})
+    on += "".join(f" {k} {v:g}" for k, v in last.items())
+    tail = f", {state.nExemptVolumeCells} volume-exempt cells" if last else ""
+    return f"Quality constraint limits:{on}, {state.nExemptDeterminantCells} determinant-exempt cells{tail}\n"
+
+
+# the keys smhost_read_mesh_quality_dict reads, in the order of its arrays (include/smhost.h)
+MESH_QUALITY_DICT_KEYS = ("maxNonOrtho", "maxBoundarySkewness", "maxInternalSkewness", "maxConcave", "minFlatness", "minVol", "minTetQuality", "minArea",
+                          "minTwist", "minDeterminant", "minFaceWeight", "minVolRatio", "minTriangleTwist")
+
+
+class MeshQualityLimits(dict):
+    """read_mesh_quality_dict's answer: {limit: value} of the keys the file gives, keyword arguments of
+    SmoothEngine.set_quality_constraint and of the smoothers' set_quality_constraint_limits_all; `ignored`: the file's other top-level
+    keys; `path`: the file"""
+    ignored = ()
+    path = None
+
+
+def read_mesh_quality_dict(path, etc_dirs=None):
+    """The limits of an OpenFOAM system/meshQualityDict (DESIGN.md "Mesh quality", 10.18), read by the host library's parser
+    (include/smhost.h, smhost_read_mesh_quality_dict: the one `smoothMesh -meshQualityDict` uses): a MeshQualityLimits, so that
+    eng.set_quality_constraint(**d) and ms.set_quality_constraint_limits_all(**d) apply the file.  A key the file does not give is
+    absent and keeps the call's default; OpenFOAM's disabling values (-1e30, -1, 180, 0) lie in the engine's off ranges.
+    etc_dirs: where #includeEtc looks, in order; None: $WM_PROJECT_DIR/etc and $FOAM_ETC, where set.  The relaxed sub-dictionary
+    and snappyHexMesh's own keys are not read: they are listed in `ignored`.  A malformed file raises RuntimeError naming file
+    and line."""
+    import ctypes as C
+    import os
+    from . import polymesh
+    if etc_dirs is None:
+        etc_dirs = [os.path.join(os.environ["WM_PROJECT_DIR"], "etc")] if os.environ.get("WM_PROJECT_DIR") else []
+        etc_dirs += [os.environ["FOAM_ETC"]] if os.environ.get("FOAM_ETC") else []
+    lib = polymesh.lib()
+    lib.smhost_read_mesh_quality_dict.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_char_p,
+                                                  C.POINTER(C.c_int64)]
+    n = len(MESH_QUALITY_DICT_KEYS)
+    dirs = (C.c_char_p * max(1, len(etc_dirs)))(*[os.fspath(d).encode() for d in etc_dirs])
+    values, found, size = (C.c_double * n)(), (C.c_int32 * n)(), C.c_int64(4096)
+    while True:
+        buf = C.create_string_buffer(size.value)
+        have = size.value
+        if lib.smhost_read_mesh_quality_dict(os.fspath(path).encode(), dirs, len(etc_dirs), values, found, buf, C.byref(size)):
+            raise RuntimeError(lib.smhost_last_error().decode())
+        if size.value <= have:
+            break
+    out = MeshQualityLimits((k, float(values[i])) for i, k in enumerate(MESH_QUALITY_DICT_KEYS) if found[i])
+    out.ignored = tuple(x for x in buf.value.decode().split("\n") if x)
+    out.path = os.fspath(path)
+    return out
 
 
 def format_guard_lines(state):
