@@ -644,6 +644,74 @@ int smgpu_set_quality_constraint_limits_all_coupled(smgpu_handle* h, const smgpu
 int smgpu_get_quality_constraint_records_all(smgpu_handle* h, smgpu_quality_constraint_record_all* out, int64_t cap, int64_t* n);
 int smgpu_get_quality_constraint_state_all(smgpu_handle* h, smgpu_quality_constraint_state_all* out);
 
+/* ---- scaling passes: a bad cell's points keep a fraction of their move before they go back (DESIGN.md "Mesh quality", 10.19) --
+ * An opt-in extension of the SERIAL quality constraint (any of its three entries).  Off (scalePasses = 0, the state after
+ * every smgpu_set_quality_constraint*): every launch, record and bit is what it is without this section.
+ * Notation of 10.12 / 10.14: x the points the iteration started from, L the points the loop produced, B the bad, non-exempt
+ * cells by whatever criteria are on.  Verdicts, exemptions and evaluation kernels are unchanged.
+ * PARAMETERS.  scalePasses S >= 0 (0: off; < 0 refused); errorReduction r (refused outside 0 <= r < 1, and NaN);
+ * nSmoothScale n >= 0 (< 0 refused); passes P, the constraint's own, keeps its meaning: marked revert passes before the full
+ * revert.
+ * PER ITERATION THAT RAN.
+ *   1. A scale s_p = 1 for every point.
+ *   2. For k = 0 .. S+P: evaluate the current points.  B empty: stop.  k == S+P: the full revert, s_p = 0 for every point.
+ *      Otherwise, with M the points of every face of every cell in B (10.12's marks):
+ *        k < S:        s_p <- s_p * r for p in M;
+ *        S <= k < S+P: s_p <- 0       for p in M;
+ *      then n Jacobi sweeps over ALL points, each reading the old field and writing the new:
+ *        s_p <- min(s_p, 0.5 s_p + 0.5 (sum_q s_q) / deg_p),
+ *      q over the engine's pointPoints row of p in row order, the sum a left fold from 0.0, the division one correctly rounded
+ *      division, no contraction; a point with an empty row keeps its value.
+ *   3. The current points become, per point: L_p where s_p == 1, with the loop's own bits, untouched; x_p where s_p == 0;
+ *      x_p + s_p (L_p - x_p) per component otherwise.
+ *   4. Scales only fall within an iteration.  They are 1 again at the next one.
+ * INVARIANT.  10.14's holds unchanged: the last fallback is still the full revert.
+ * EQUIVALENCES, both bit for bit.  S = 0: the constraint without this section -- points, every record field, launches.
+ * S > 0, r = 0, n = 0: the accepted points of the constraint with passes = S + P.
+ * RECORDS.  smgpu_quality_constraint_record_scaled: smgpu_quality_constraint_record_all's fields at their offsets (136 bytes),
+ * then nScalePasses (the marked passes with k < S that ran), nPointsScaled (points with accepted 0 < s_p < 1 and L_p != x_p)
+ * and minScale (the smallest accepted s_p: 1.0 in a clean iteration, 0 after a full revert).  nPointsReverted keeps its
+ * definition, read on the accepted points: accepted point == x_p and L_p != x_p (a point scaled in one pass and reverted in a
+ * later one counts once, as reverted); passes counts all marked passes, scaling and reverting.  While scaling is off the three
+ * new fields are 0.  smgpu_quality_constraint_state_scaled: the _all state, then the three parameters ({0, 4, 0.75} while off).
+ * The older getters keep working and return their prefixes; all drain the one pending list.
+ * smgpu_set_quality_constraint_scaling is valid while the serial quality constraint is on; scalePasses = 0 (or p = NULL)
+ * switches scaling off and frees its memory; clearing or re-enabling the constraint switches it off too.
+ * REFUSED, by name: an engine with a halo (the coupled form has no scaling); boundary point smoothing; the tangle constraint
+ * (it has no scaling: the quality constraint with its three criteria off is the tangle constraint); the quality constraint
+ * off; between smgpu_iter_begin and smgpu_iter_end; scalePasses + passes above 2147483647.
+ * ALLOWED TOGETHER: layers, both foam variants, all thirteen limits, the trace, the guard (its refining steps replay
+ * deterministically: the scale state does not outlive an iteration), SMGPU_TILES=0.
+ * Memory, outside deviceBytes, held while scaling is on: 40 bytes per point (L, and two scale fields); 160 bytes per record. */
+typedef struct smgpu_quality_constraint_scaling {
+    int32_t scalePasses, nSmoothScale;
+    double errorReduction;
+} smgpu_quality_constraint_scaling;           /* NULL = {0, 4, 0.75}: off */
+typedef struct smgpu_quality_constraint_record_scaled {
+    int64_t iteration;
+    int32_t passes, fullRevert;
+    int64_t nBadCells, nPointsReverted;
+    int64_t nTangledCells, nNonOrthoFaces, nSkewFaces;
+    int64_t nLowTetFaces, nLowTwistFaces, nLowTriangleTwistFaces, nLowWeightFaces, nLowVolRatioFaces, nUnderdeterminedCells;
+    int64_t nConcaveFaces, nWarpedFaces, nSmallAreaFaces, nSmallVolumeCells;
+    int64_t nScalePasses, nPointsScaled;
+    double minScale;
+} smgpu_quality_constraint_record_scaled;
+typedef struct smgpu_quality_constraint_state_scaled {
+    int32_t on, passes;
+    double maxNonOrtho, maxInternalSkewness, maxBoundarySkewness;
+    int64_t nExemptCells, nExemptFaces, iteration;
+    double minTetQuality, minTwist, minTriangleTwist, minFaceWeight, minVolRatio, minDeterminant;
+    int64_t nExemptDeterminantCells;
+    double maxConcave, minFlatness, minVol, minArea;
+    int64_t nExemptVolumeCells;
+    int32_t scalePasses, nSmoothScale;
+    double errorReduction;
+} smgpu_quality_constraint_state_scaled;
+int smgpu_set_quality_constraint_scaling(smgpu_handle* h, const smgpu_quality_constraint_scaling* p);
+int smgpu_get_quality_constraint_records_scaled(smgpu_handle* h, smgpu_quality_constraint_record_scaled* out, int64_t cap, int64_t* n);
+int smgpu_get_quality_constraint_state_scaled(smgpu_handle* h, smgpu_quality_constraint_state_scaled* out);
+
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):
  *   1. smgpu_quality_coupled_pack: the geometry of the current points (the loop's own launch, uncounted), then the owner cell

@@ -7,4 +7,4 @@ path runs in csrc/libsmgpu.so (hand-written HIP); there is no CPU fallback: load
 the library has not been built.
 """
 from .mesh import PolyMesh, Patch  # noqa: F401
-from .engine import BoundaryParams, LayerParams, MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityConstraintRecord, QualityConstraintRecordFull, QualityConstraintRecordAll, QualityConstraintState, QualityConstraintStateFull, QualityConstraintStateAll, QualityGuardState, QualityTraceRecord, SmoothEngine, TangleRecord, TangleState, SmoothParams, SmgpuError, default_params, patch_arrays  # noqa: F401
+from .engine import BoundaryParams, LayerParams, MeshQuality, MeshQualityGeometry, MeshQualityMotion, QualityConstraintRecord, QualityConstraintRecordFull, QualityConstraintRecordAll, QualityConstraintRecordScaled, QualityConstraintState, QualityConstraintStateFull, QualityConstraintStateAll, QualityConstraintStateScaled, QualityGuardState, QualityTraceRecord, SmoothEngine, TangleRecord, TangleState, SmoothParams, SmgpuError, default_params, patch_arrays  # noqa: F401

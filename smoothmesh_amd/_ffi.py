@@ -197,6 +197,21 @@ class QualityConstraintStateAll(C.Structure):
     _fields_ = QualityConstraintStateFull._fields_ + [(n, C.c_double) for n in _QC_LIMITS_ALL] + [("nExemptVolumeCells", C.c_int64)]
 
 
+class QualityConstraintScaling(C.Structure):
+    """smgpu_quality_constraint_scaling"""
+    _fields_ = [("scalePasses", C.c_int32), ("nSmoothScale", C.c_int32), ("errorReduction", C.c_double)]
+
+
+class QualityConstraintRecordScaled(C.Structure):
+    """smgpu_quality_constraint_record_scaled: QualityConstraintRecordAll's fields, then the three of DESIGN.md 10.19"""
+    _fields_ = QualityConstraintRecordAll._fields_ + [("nScalePasses", C.c_int64), ("nPointsScaled", C.c_int64), ("minScale", C.c_double)]
+
+
+class QualityConstraintStateScaled(C.Structure):
+    """smgpu_quality_constraint_state_scaled: QualityConstraintStateAll's fields, then the three parameters of DESIGN.md 10.19"""
+    _fields_ = QualityConstraintStateAll._fields_ + QualityConstraintScaling._fields_
+
+
 class TangleHaloDesc(C.Structure):
     """smgpu_tangle_halo_desc"""
     _fields_ = [("sendT", C.c_void_p), ("recvT", C.c_void_p)]
@@ -343,6 +358,9 @@ SYMBOLS = {
     "smgpu_set_quality_constraint_limits_all_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintLimitsAll), C.POINTER(QualityConstraintHaloDescFull), C.c_int32]),
     "smgpu_get_quality_constraint_records_all": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintRecordAll), C.c_int64, C.POINTER(C.c_int64)]),
     "smgpu_get_quality_constraint_state_all": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintStateAll)]),
+    "smgpu_set_quality_constraint_scaling": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintScaling)]),
+    "smgpu_get_quality_constraint_records_scaled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintRecordScaled), C.c_int64, C.POINTER(C.c_int64)]),
+    "smgpu_get_quality_constraint_state_scaled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintStateScaled)]),
     "smgpu_quality_constraint_coupled_exempt": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_begin": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_faces": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -100,7 +100,7 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "meshQuality", "qualityInterval", "qualityGuard", "qualityGuardRefine", "tangleConstraint", "tanglePasses",
                                "qualityConstraint", "maxNonOrtho", "maxInternalSkewness", "maxBoundarySkewness", "qualityConstraintPasses",
                                "minTetQuality", "minTwist", "minTriangleTwist", "minFaceWeight", "minVolRatio", "minDeterminant",
-                               "maxConcave", "minFlatness", "minVol", "minArea", "meshQualityDict"};
+                               "maxConcave", "minFlatness", "minVol", "minArea", "meshQualityDict", "scalePasses", "errorReduction", "nSmoothScale"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -140,6 +140,10 @@ Options parseArgs(int argc, char** argv) {
                       "       [-meshQualityDict true|file]  (with -qualityConstraint: take the thirteen limits from system/meshQualityDict, or from file,\n"
                       "        relative to the case; an option given on the command line wins over the file's entry, a key in neither keeps the option's\n"
                       "        default; #includeEtc looks under $WM_PROJECT_DIR/etc and $FOAM_ETC; the relaxed sub-dictionary is not read)\n"
+                      "       [-scalePasses n -errorReduction x -nSmoothScale n]  (with -qualityConstraint: in the first n marked passes of an iteration the\n"
+                      "        points of a bad cell keep x times their scale of the move instead of going back, and nSmoothScale Jacobi sweeps smooth the\n"
+                      "        scale field behind every marked pass; then the reverting passes; defaults 0 (off), 0.75, 4; the last two need -scalePasses > 0;\n"
+                      "        the values come from the options only, never from meshQualityDict)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
@@ -627,6 +631,20 @@ int main(int argc, char** argv) {
         if (k == 0 && qcLast[k] < 0.0) fatal("-maxConcave must not be negative");
         qcLastOn = qcLastOn || (k == 0 ? qcLast[k] < 180.0 : qcLast[k] > 0.0);
     }
+    // the scaling passes of DESIGN.md 10.19: from the options only
+    const long qcScalePasses = opt.getL("scalePasses", 0), qcSmoothScale = opt.getL("nSmoothScale", 4);
+    const double qcErrorReduction = opt.getD("errorReduction", 0.75);
+    for (const char* k : {"scalePasses", "errorReduction", "nSmoothScale"}) {
+        if (opt.found(k) && !qualityConstraint && tangleConstraint)
+            fatal(std::string("-") + k + " is not available with -tangleConstraint: the tangle constraint has no scaling passes; -qualityConstraint true with "
+                  "-maxNonOrtho 180 -maxInternalSkewness 0 -maxBoundarySkewness 0 is the tangle constraint");
+        if (opt.found(k) && !qualityConstraint) fatal(std::string("-") + k + " needs -qualityConstraint true");
+    }
+    if (qcScalePasses < 0 || qcScalePasses > 0x7fffffffL) fatal("scalePasses must be between 0 and 2147483647");
+    for (const char* k : {"errorReduction", "nSmoothScale"})
+        if (opt.found(k) && qcScalePasses == 0) fatal(std::string("-") + k + " needs -scalePasses > 0");
+    if (!(qcErrorReduction >= 0.0 && qcErrorReduction < 1.0)) fatal("errorReduction must be a number with 0 <= errorReduction < 1");
+    if (qcSmoothScale < 0 || qcSmoothScale > 0x7fffffffL) fatal("nSmoothScale must be between 0 and 2147483647");
     if (qualityConstraint && opt.parallel)
         fatal("-qualityConstraint is not available with -parallel: it judges the faces and cells by the measure of the quality report, which is serial only");
     if (qualityConstraint && tangleConstraint) fatal("-qualityConstraint is not available with -tangleConstraint true: it contains the tangle constraint");
@@ -1360,7 +1378,8 @@ int main(int argc, char** argv) {
     // -qualityConstraint: the same with limits on non-orthogonality and skewness (smgpu_set_quality_constraint)
     // with one of -minTetQuality ... -minDeterminant: the entry, the records and the lines of 10.16; without, those of 10.14 as they were
     // with one of -maxConcave -minFlatness -minVol -minArea on: the entry, the records and the lines of 10.18
-    std::vector<smgpu_quality_constraint_record_all> qcRecords;
+    // with -scalePasses > 0: 10.19's scaling passes on top of whichever entry, one more set-up line and three more values per line
+    std::vector<smgpu_quality_constraint_record_scaled> qcRecords;
     if (qualityConstraint) {
         const smgpu_quality_constraint_params qp{qcMaxNonOrtho, qcMaxInternalSkewness, qcMaxBoundarySkewness, (int32_t)qcPasses};
         const smgpu_quality_constraint_limits ql{qcMaxNonOrtho, qcMaxInternalSkewness, qcMaxBoundarySkewness, (int32_t)qcPasses,
@@ -1387,6 +1406,13 @@ int main(int argc, char** argv) {
             OUT(", %lld determinant-exempt cells", (long long)qf.nExemptDeterminantCells);
             if (qcLastOn) OUT(", %lld volume-exempt cells", (long long)qf.nExemptVolumeCells);
             OUT("\n");
+        }
+        if (qcScalePasses > 0) {
+            const smgpu_quality_constraint_scaling sc{(int32_t)qcScalePasses, (int32_t)qcSmoothScale, qcErrorReduction};
+            check(smgpu_set_quality_constraint_scaling(R[0].h, &sc), "smgpu_set_quality_constraint_scaling");
+            smgpu_quality_constraint_state_scaled ss{};
+            check(smgpu_get_quality_constraint_state_scaled(R[0].h, &ss), "smgpu_get_quality_constraint_state_scaled");
+            OUT("Quality constraint scaling: scalePasses %d errorReduction %g nSmoothScale %d\n", (int)ss.scalePasses, ss.errorReduction, (int)ss.nSmoothScale);
         }
         if (!qcDictPath.empty()) {
             OUT("Quality constraint: limits from %s", qcDictPath.c_str());
@@ -1483,9 +1509,9 @@ int main(int argc, char** argv) {
         size_t nextQc = 0;
         if (qualityConstraint) {
             int64_t nRecords = 0;
-            check(smgpu_get_quality_constraint_records_all(R[0].h, nullptr, 0, &nRecords), "smgpu_get_quality_constraint_records_all");
+            check(smgpu_get_quality_constraint_records_scaled(R[0].h, nullptr, 0, &nRecords), "smgpu_get_quality_constraint_records_scaled");
             qcRecords.resize((size_t)nRecords);
-            if (nRecords > 0) check(smgpu_get_quality_constraint_records_all(R[0].h, qcRecords.data(), nRecords, &nRecords), "smgpu_get_quality_constraint_records_all");
+            if (nRecords > 0) check(smgpu_get_quality_constraint_records_scaled(R[0].h, qcRecords.data(), nRecords, &nRecords), "smgpu_get_quality_constraint_records_scaled");
         }
         for (int32_t k = 0; k < done; ++k) {
             OUT("Smoothing iteration=%ld nFrozenPoints=%d residual=%g\n", i + k + 1, stats[(size_t)k].nFrozenPoints, stats[(size_t)k].residual);
@@ -1496,25 +1522,20 @@ int main(int argc, char** argv) {
                         (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
             }
             if (nextQc < qcRecords.size() && qcRecords[nextQc].iteration == (int64_t)(i + k + 1)) {
-                const smgpu_quality_constraint_record_all& t = qcRecords[nextQc++];
-                if (t.nBadCells > 0 && qcLastOn)
-                    OUT("    quality constraint iteration=%lld badCells %lld tangled %lld nonOrthoFaces %lld skewFaces %lld lowTetFaces %lld twistedFaces %lld "
-                        "lowTriangleTwistFaces %lld lowWeightFaces %lld lowVolRatioFaces %lld underdeterminedCells %lld concaveFaces %lld warpedFaces %lld "
-                        "smallAreaFaces %lld smallVolumeCells %lld passes %d pointsReverted %lld%s\n",
-                        (long long)t.iteration, (long long)t.nBadCells, (long long)t.nTangledCells, (long long)t.nNonOrthoFaces, (long long)t.nSkewFaces,
-                        (long long)t.nLowTetFaces, (long long)t.nLowTwistFaces, (long long)t.nLowTriangleTwistFaces, (long long)t.nLowWeightFaces,
-                        (long long)t.nLowVolRatioFaces, (long long)t.nUnderdeterminedCells, (long long)t.nConcaveFaces, (long long)t.nWarpedFaces,
-                        (long long)t.nSmallAreaFaces, (long long)t.nSmallVolumeCells, (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
-                else if (t.nBadCells > 0 && qcMoreGiven)
-                    OUT("    quality constraint iteration=%lld badCells %lld tangled %lld nonOrthoFaces %lld skewFaces %lld lowTetFaces %lld twistedFaces %lld "
-                        "lowTriangleTwistFaces %lld lowWeightFaces %lld lowVolRatioFaces %lld underdeterminedCells %lld passes %d pointsReverted %lld%s\n",
-                        (long long)t.iteration, (long long)t.nBadCells, (long long)t.nTangledCells, (long long)t.nNonOrthoFaces, (long long)t.nSkewFaces,
-                        (long long)t.nLowTetFaces, (long long)t.nLowTwistFaces, (long long)t.nLowTriangleTwistFaces, (long long)t.nLowWeightFaces,
-                        (long long)t.nLowVolRatioFaces, (long long)t.nUnderdeterminedCells, (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
-                else if (t.nBadCells > 0)
-                    OUT("    quality constraint iteration=%lld badCells %lld tangled %lld nonOrthoFaces %lld skewFaces %lld passes %d pointsReverted %lld%s\n",
-                        (long long)t.iteration, (long long)t.nBadCells, (long long)t.nTangledCells, (long long)t.nNonOrthoFaces, (long long)t.nSkewFaces,
-                        (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
+                const smgpu_quality_constraint_record_scaled& t = qcRecords[nextQc++];
+                if (t.nBadCells > 0) {
+                    OUT("    quality constraint iteration=%lld badCells %lld tangled %lld nonOrthoFaces %lld skewFaces %lld", (long long)t.iteration, (long long)t.nBadCells,
+                        (long long)t.nTangledCells, (long long)t.nNonOrthoFaces, (long long)t.nSkewFaces);
+                    if (qcLastOn || qcMoreGiven)
+                        OUT(" lowTetFaces %lld twistedFaces %lld lowTriangleTwistFaces %lld lowWeightFaces %lld lowVolRatioFaces %lld underdeterminedCells %lld",
+                            (long long)t.nLowTetFaces, (long long)t.nLowTwistFaces, (long long)t.nLowTriangleTwistFaces, (long long)t.nLowWeightFaces,
+                            (long long)t.nLowVolRatioFaces, (long long)t.nUnderdeterminedCells);
+                    if (qcLastOn)
+                        OUT(" concaveFaces %lld warpedFaces %lld smallAreaFaces %lld smallVolumeCells %lld", (long long)t.nConcaveFaces, (long long)t.nWarpedFaces,
+                            (long long)t.nSmallAreaFaces, (long long)t.nSmallVolumeCells);
+                    if (qcScalePasses > 0) OUT(" scalePasses %lld pointsScaled %lld minScale %g", (long long)t.nScalePasses, (long long)t.nPointsScaled, t.minScale);
+                    OUT(" passes %d pointsReverted %lld%s\n", (int)t.passes, (long long)t.nPointsReverted, t.fullRevert ? " fullRevert" : "");
+                }
             }
             if (!qualityTrace || nextRecord >= trace.size() || trace[nextRecord].iteration != (int64_t)(i + k + 1)) continue;
             const smgpu_quality_trace_record& t = trace[nextRecord++];

@@ -602,10 +602,14 @@ static int qualityConstraintEvaluate(smgpu_handle* h, bool enabling, int pass, c
     return qualityConstraintGeometry(h, enabling, pass, gate) || qualityConstraintVerdicts(h, enabling, pass, gate);
 }
 // behind the movePoints of an iteration: the passes on the points ptsCur now names; x: the points the iteration started from
+// (the slab's slots are the scaled records of 10.19, whose head is the widest record of 10.18: kernels_quality_scale.hpp)
+static int qualityConstraintQueueScaled(smgpu_handle* h, smgpu_quality_constraint_record_scaled* rec, int64_t number, const smgpu_iter_stats* gate, const double* x);
 static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, const smgpu_iter_stats* gate, const double* x) {
     QualityConstraintHost& q = h->qc;
-    smgpu_quality_constraint_record_all* rec = nullptr;
-    if (q.slab.slot(slot, &rec)) return 1;
+    smgpu_quality_constraint_record_scaled* wide = nullptr;
+    if (q.slab.slot(slot, &wide)) return 1;
+    if (q.scaling.scalePasses > 0) return qualityConstraintQueueScaled(h, wide, number, gate, x);
+    smgpu_quality_constraint_record_all* const rec = reinterpret_cast<smgpu_quality_constraint_record_all*>(wide);
     const int nP = h->mv.nPoints;
     const int gApply = std::max(1, (int)(((int64_t)nP + kTanglePts - 1) / kTanglePts));
     for (int k = 0; k <= q.prm.passes; ++k) {
@@ -614,6 +618,33 @@ static int qualityConstraintQueue(smgpu_handle* h, int slot, int64_t number, con
         // the record and the device words begin with the tangle constraint's (kernels_quality_constraint.hpp)
         hipLaunchKernelGGL(k_tangle_apply, dim3(gApply), dim3(kTangleBlock), 0, h->stream, x, h->st.ptsCur, q.marks, nP, (const TangleDev*)&q.dev->t,
                            reinterpret_cast<smgpu_tangle_record*>(rec), gate);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+// 10.19, scaling on: the evaluations are the ones above and run to S + P; what follows a verdict is kernels_quality_scale.hpp's.
+// Which of the two scale fields is current behind a launch is the host's to know: every launch of an iteration runs, or from
+// some verdict on none does.
+static int qualityConstraintQueueScaled(smgpu_handle* h, smgpu_quality_constraint_record_scaled* rec, int64_t number, const smgpu_iter_stats* gate, const double* x) {
+    QualityConstraintHost& q = h->qc;
+    const int nP = h->mv.nPoints, S = q.scaling.scalePasses, total = S + q.prm.passes, nSweeps = q.scaling.nSmoothScale;
+    const long long nL = 3 * (long long)nP;
+    const int gKeep = (int)std::max<long long>(1, ((nL >> 1) + (long long)kGuardBlock * kGuardPer - 1) / ((long long)kGuardBlock * kGuardPer));
+    const int gWord = std::max(1, (int)((((int64_t)nP + 3) / 4 + kQsBlock - 1) / kQsBlock)), gPoint = std::max(1, (int)std::min<int64_t>(q.maxGrid, ((int64_t)nP + kQsBlock - 1) / kQsBlock));
+    double *sCur = q.scaleA, *sNext = q.scaleB;
+    for (int k = 0; k <= total; ++k) {
+        if (qualityConstraintEvaluate(h, false, k, gate)) return 1;
+        hipLaunchKernelGGL(k_qs_verdict, dim3(1), dim3(64), 0, h->stream, q.dev, q.acc, rec, (long long)number, k, S, total, gate);
+        if (k == 0)
+            hipLaunchKernelGGL(k_qs_keep, dim3(gKeep), dim3(kGuardBlock), 0, h->stream, (const double*)h->st.ptsCur, q.L, nL, sCur, q.nScale, (const QcDev*)q.dev, gate);
+        hipLaunchKernelGGL(k_qs_mark, dim3(gWord), dim3(kQsBlock), 0, h->stream, q.marks, sCur, nP, q.scaling.errorReduction,
+                           k == total ? (int)kQsFull : (k < S ? (int)kQsScale : (int)kQsZero), (const QcDev*)q.dev, gate);
+        for (int i = 0; i < nSweeps && k < total; ++i) {
+            hipLaunchKernelGGL(k_qs_sweep, dim3(gPoint), dim3(kQsBlock), 0, h->stream, h->mv, (const double*)sCur, sNext, (const QcDev*)q.dev, gate);
+            std::swap(sCur, sNext);
+        }
+        hipLaunchKernelGGL(k_qs_apply, dim3(gPoint), dim3(kQsBlock), 0, h->stream, x, (const double*)q.L, h->st.ptsCur, (const double*)sCur, nP, (const QcDev*)q.dev, rec,
+                           gate);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -741,7 +772,7 @@ int smgpu_get_quality_constraint_records_all(smgpu_handle* h, smgpu_quality_cons
         HIP_OK(hipSetDevice(h->device));
         if (qualityConstraintCoupledFlush(h)) return 1;
     }
-    return h->qc.slab.drain(out, cap, n, "smgpu_get_quality_constraint_records_all");
+    return h->qc.slab.drainHeads(out, cap, n, "smgpu_get_quality_constraint_records_all");
 }
 int smgpu_get_quality_constraint_state_all(smgpu_handle* h, smgpu_quality_constraint_state_all* out) {
     if (!h || !out) return fail("null argument");
@@ -751,6 +782,61 @@ int smgpu_get_quality_constraint_state_all(smgpu_handle* h, smgpu_quality_constr
     *out = smgpu_quality_constraint_state_all{s.on, s.passes, s.maxNonOrtho, s.maxInternalSkewness, s.maxBoundarySkewness, s.nExemptCells, s.nExemptFaces, s.iteration,
                                               s.minTetQuality, s.minTwist, s.minTriangleTwist, s.minFaceWeight, s.minVolRatio, s.minDeterminant,
                                               s.nExemptDeterminantCells, q.maxConcave, q.shape.minFlat, q.shape.minVol, q.shape.minArea, s.on ? q.nExemptVol : 0};
+    return 0;
+}
+// 10.19: the scaling passes of the serial constraint.  Their memory is the constraint's own second block: allocated here, freed
+// here with scalePasses = 0 and by everything that switches the constraint off (QualityConstraintHost::release)
+int smgpu_set_quality_constraint_scaling(smgpu_handle* h, const smgpu_quality_constraint_scaling* p) {
+    if (!h) return fail("null handle");
+    const std::string api("smgpu_set_quality_constraint_scaling");
+    const smgpu_quality_constraint_scaling prm = p ? *p : smgpu_quality_constraint_scaling{0, 4, 0.75};
+    if (prm.scalePasses < 0) return fail(api + ": scalePasses < 0");
+    if (!(prm.errorReduction >= 0.0 && prm.errorReduction < 1.0)) return fail(api + ": errorReduction is outside 0 <= errorReduction < 1");
+    if (prm.nSmoothScale < 0) return fail(api + ": nSmoothScale < 0");
+    if (h->haloOn) return fail(api + ": not available on an engine with a halo (the coupled form of the quality constraint has no scaling passes)");
+    if (h->bndOn) return fail(api + ": not available on an engine with boundary point smoothing (nor is the quality constraint)");
+    if (h->tg.on)
+        return fail(api + ": the tangle constraint is on (smgpu_set_tangle_constraint), and it has no scaling passes; the quality constraint with its "
+                    "three criteria off is the tangle constraint");
+    if (!h->qc.on) return fail(api + ": the quality constraint is off (smgpu_set_quality_constraint); switch it on first");
+    if (h->iterOpen) return fail(api + ": between smgpu_iter_begin and smgpu_iter_end");
+    if ((int64_t)prm.scalePasses + (int64_t)h->qc.prm.passes > 0x7fffffffLL) return fail(api + ": scalePasses + passes is above 2147483647");
+    HIP_OK(hipSetDevice(h->device));
+    QualityConstraintHost& q = h->qc;
+    if (q.scaleBlock.live()) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        q.releaseScaling();
+    }
+    if (prm.scalePasses == 0) return 0;
+    const size_t nP = (size_t)std::max(1, h->mv.nPoints), nScale = (nP + 1) & ~(size_t)1;
+    if (q.scaleBlock.alloc(&q.L, 3 * nP) || q.scaleBlock.alloc(&q.scaleA, nScale) || q.scaleBlock.alloc(&q.scaleB, nScale)) {
+        const int rc = q.scaleBlock.failed("the quality constraint's scaling passes");
+        q.releaseScaling();
+        return rc;
+    }
+    q.nScale = (long long)nScale;
+    q.maxGrid = std::max(1, envInt("SMGPU_QS_MAX_GRID", kQsMaxGrid));   // (tests: several trips per lane on a small mesh)
+    q.scaling = prm;
+    return 0;
+}
+int smgpu_get_quality_constraint_records_scaled(smgpu_handle* h, smgpu_quality_constraint_record_scaled* out, int64_t cap, int64_t* n) {
+    if (!h || !n) return fail("null argument");
+    if (h->qc.coupled) {
+        if (h->qc.k >= 0) return fail("smgpu_get_quality_constraint_records_scaled: between the passes of an iteration (smgpu_quality_constraint_pass_begin / _end)");
+        HIP_OK(hipSetDevice(h->device));
+        if (qualityConstraintCoupledFlush(h)) return 1;
+    }
+    return h->qc.slab.drain(out, cap, n, "smgpu_get_quality_constraint_records_scaled");
+}
+int smgpu_get_quality_constraint_state_scaled(smgpu_handle* h, smgpu_quality_constraint_state_scaled* out) {
+    if (!h || !out) return fail("null argument");
+    smgpu_quality_constraint_state_all s{};
+    if (smgpu_get_quality_constraint_state_all(h, &s)) return 1;
+    const smgpu_quality_constraint_scaling& c = h->qc.scaling;
+    *out = smgpu_quality_constraint_state_scaled{s.on, s.passes, s.maxNonOrtho, s.maxInternalSkewness, s.maxBoundarySkewness, s.nExemptCells, s.nExemptFaces, s.iteration,
+                                                 s.minTetQuality, s.minTwist, s.minTriangleTwist, s.minFaceWeight, s.minVolRatio, s.minDeterminant,
+                                                 s.nExemptDeterminantCells, s.maxConcave, s.minFlatness, s.minVol, s.minArea, s.nExemptVolumeCells,
+                                                 c.scalePasses, c.nSmoothScale, c.errorReduction};
     return 0;
 }
 int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n) {
@@ -982,8 +1068,9 @@ int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32
     if (q.stage != 2 || q.k < 0) return fail("smgpu_quality_constraint_pass_end without smgpu_quality_constraint_pass_faces");
     if (nBadGlobal < 0) return fail("smgpu_quality_constraint_pass_end: nBadGlobal < 0");
     HIP_OK(hipSetDevice(h->device));
-    smgpu_quality_constraint_record_all* rec = nullptr;
-    if (q.slab.slot(q.slabUsed, &rec)) return 1;
+    smgpu_quality_constraint_record_scaled* wide = nullptr;
+    if (q.slab.slot(q.slabUsed, &wide)) return 1;
+    smgpu_quality_constraint_record_all* const rec = reinterpret_cast<smgpu_quality_constraint_record_all*>(wide);   // (its head; no scaling in the coupled form)
     const bool full = nBadGlobal > 0 && q.k == q.prm.passes;
     // the record begins with the tangle constraint's (kernels_quality_constraint.hpp)
     if (nBadGlobal > 0 && coupledRevert(h, full, q.recvT, q.marks, q.x, q.counted, reinterpret_cast<smgpu_tangle_record*>(rec), q.reverting)) return 1;

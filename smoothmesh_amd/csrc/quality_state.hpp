@@ -213,8 +213,18 @@ struct QualityConstraintHost {
     double* cellCtr = nullptr;
     Accum* acc = nullptr;
     // one record per iteration of the call, the widest for every entry; without the limits of 10.16 the six counts behind its
-    // head, smgpu_quality_constraint_record, are 0, and without those of 10.18 the four behind them
-    RecordSlab<smgpu_quality_constraint_record_all> slab{"quality constraint"};
+    // head, smgpu_quality_constraint_record, are 0, without those of 10.18 the four behind them, and without the scaling of 10.19
+    // the three behind those
+    RecordSlab<smgpu_quality_constraint_record_scaled> slab{"quality constraint"};
+    // the scaling passes of 10.19 (smgpu_set_quality_constraint_scaling, kernels_quality_scale.hpp; serial form only), off while
+    // scaling.scalePasses is 0.  Allocated when they are switched on: L, the points the loop produced (3 doubles per point), and
+    // the two scale fields the sweeps alternate between (nScale doubles each: one per point, rounded up to an even number)
+    smgpu_quality_constraint_scaling scaling{0, 4, 0.75};
+    DevBlock scaleBlock;
+    double *L = nullptr, *scaleA = nullptr, *scaleB = nullptr;
+    long long nScale = 0;
+    int maxGrid = 8192;                     // workgroups of a sweep / apply launch at most (kQsMaxGrid; SMGPU_QS_MAX_GRID)
+    void releaseScaling() { scaleBlock.release(); scaling = smgpu_quality_constraint_scaling{0, 4, 0.75}; nScale = 0; }
     // the limits of 10.16 (smgpu_set_quality_constraint_limits, kernels_quality_limits.hpp).  faceMore: a new face criterion is
     // on; cellMore: minVolRatio or minDeterminant is; with neither the launches are 10.14's.  vol, exemptDet: allocated with
     // cellMore, 8 bytes and 1 byte per cell
@@ -247,5 +257,5 @@ struct QualityConstraintHost {
     int *procFace = nullptr, *slot = nullptr;
     int *sendT = nullptr, *recvT = nullptr;        // the caller's exchange buffers (device, nSend / nRecv int32)
     double *sendCc = nullptr, *recvCc = nullptr;   // ... (device, 3 doubles per processor face, patch order)
-    void release() { block.release(); slab.release(); coupled = pending = slabFresh = full = false; sendVc = recvVc = nullptr; k = -1; stage = 0; slabUsed = 0; nProc = 0; }
+    void release() { block.release(); releaseScaling(); slab.release(); coupled = pending = slabFresh = full = false; sendVc = recvVc = nullptr; k = -1; stage = 0; slabUsed = 0; nProc = 0; }
 };

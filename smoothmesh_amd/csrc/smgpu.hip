@@ -27,6 +27,7 @@
 #include "kernels_quality_tangle.hpp"
 #include "kernels_quality_constraint.hpp"
 #include "kernels_quality_limits.hpp"
+#include "kernels_quality_scale.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"

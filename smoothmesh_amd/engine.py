@@ -247,6 +247,25 @@ class QualityConstraintStateAll(QualityConstraintStateFull):
 
 
 @dataclass
+class QualityConstraintRecordScaled(QualityConstraintRecordAll):
+    """smgpu_quality_constraint_record_scaled (DESIGN.md "Mesh quality", 10.19): QualityConstraintRecordAll, then the marked passes
+    that scaled (k < scalePasses), the points that keep a fraction of their move (accepted 0 < s < 1, moved by the loop) and the
+    smallest accepted scale (1.0 in a clean iteration, 0 after a full revert).  nPointsReverted reads the accepted points; passes
+    counts scaling and reverting passes.  All three 0 while scaling is off."""
+    nScalePasses: int = 0
+    nPointsScaled: int = 0
+    minScale: float = 0.0
+
+
+@dataclass
+class QualityConstraintStateScaled(QualityConstraintStateAll):
+    """smgpu_quality_constraint_state_scaled: QualityConstraintStateAll, then the parameters of 10.19 (scalePasses 0: off)"""
+    scalePasses: int = 0
+    nSmoothScale: int = 4
+    errorReduction: float = 0.75
+
+
+@dataclass
 class TangleState:
     """smgpu_tangle_state: whether the constraint is on, its passes, the cells exempt since enabling, the running number"""
     on: bool
@@ -781,7 +800,7 @@ class SmoothEngine:
 
     def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
                                minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
-                               maxConcave=None, minFlatness=None, minVol=None, minArea=None):
+                               maxConcave=None, minFlatness=None, minVol=None, minArea=None, scalePasses=0, errorReduction=0.75, nSmoothScale=4):
         """Quality constraint (include/smgpu.h, smgpu_set_quality_constraint; DESIGN.md "Mesh quality", 10.14): the tangle
         constraint with limits on face non-orthogonality (degrees; >= 180: off) and on the skewness of internal and of boundary
         faces (<= 0: off).  From now on iterate() puts the points of every cell that an iteration turned bad -- by the tangle
@@ -795,7 +814,30 @@ class SmoothEngine:
         The last four (smgpu_set_quality_constraint_limits_all; None: off) make a face bad that has a concave
         corner sharper than maxConcave degrees (mesh_quality_geometry's faceConcavity with concaveThreshold = maxConcave), whose
         flatness lies under minFlatness or whose area under minArea, and a cell whose volume lies under minVol; with all four
-        None the call goes through the entry it went through before."""
+        None the call goes through the entry it went through before.
+        scalePasses > 0 then switches the scaling passes on: set_quality_constraint_scaling with the three
+        keywords; if that is refused the constraint is left off.  With scalePasses = 0 the call is what it was."""
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, minTetQuality, minTwist, minTriangleTwist,
+                                        minFaceWeight, minVolRatio, minDeterminant, maxConcave, minFlatness, minVol, minArea)
+        if scalePasses != 0:
+            try:
+                self.set_quality_constraint_scaling(scalePasses, errorReduction, nSmoothScale)
+            except SmgpuError:
+                self.clear_quality_constraint()
+                raise
+
+    def set_quality_constraint_scaling(self, scalePasses=0, errorReduction=0.75, nSmoothScale=4):
+        """The scaling passes of the serial quality constraint (include/smgpu.h, smgpu_set_quality_constraint_scaling; DESIGN.md
+        "Mesh quality", 10.19), valid while it is on: in the first `scalePasses` marked passes of an iteration the points of a bad
+        cell keep `errorReduction` times their scale of the move instead of going back; `nSmoothScale` Jacobi sweeps smooth the
+        scale field behind every marked pass; the constraint's `passes` reverting passes and the full revert follow.
+        scalePasses = 0 switches the scaling off and frees its memory, and so does clearing or re-enabling the constraint."""
+        p = _ffi.QualityConstraintScaling(int(scalePasses), int(nSmoothScale), float(errorReduction))
+        self._check(self._lib.smgpu_set_quality_constraint_scaling(self._h, C.byref(p)))
+
+    def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, minTetQuality, minTwist, minTriangleTwist,
+                                   minFaceWeight, minVolRatio, minDeterminant, maxConcave, minFlatness, minVol, minArea):
+        """the entry of include/smgpu.h a set of limits takes: the narrowest that holds every limit given"""
         more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
                     minVolRatio=minVolRatio, minDeterminant=minDeterminant)
         last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
@@ -889,6 +931,22 @@ class SmoothEngine:
         buf = (_ffi.QualityConstraintRecordAll * n.value)()
         self._check(self._lib.smgpu_get_quality_constraint_records_all(self._h, buf, n.value, C.byref(n)))
         return [QualityConstraintRecordAll(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+
+    def quality_constraint_records_scaled(self) -> list:
+        """quality_constraint_records() with the three fields of DESIGN.md 10.19 (QualityConstraintRecordScaled); the two getters
+        drain the same pending list."""
+        n = C.c_int64(0)
+        self._check(self._lib.smgpu_get_quality_constraint_records_scaled(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        buf = (_ffi.QualityConstraintRecordScaled * n.value)()
+        self._check(self._lib.smgpu_get_quality_constraint_records_scaled(self._h, buf, n.value, C.byref(n)))
+        return [QualityConstraintRecordScaled(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+
+    def quality_constraint_state_scaled(self) -> QualityConstraintStateScaled:
+        s = _ffi.QualityConstraintStateScaled()
+        self._check(self._lib.smgpu_get_quality_constraint_state_scaled(self._h, C.byref(s)))
+        return QualityConstraintStateScaled(on=bool(s.on), **{f: getattr(s, f) for f, _ in s._fields_ if f != "on"})
 
     def quality_constraint_state(self) -> QualityConstraintStateAll:
         s = _ffi.QualityConstraintStateAll()

@@ -217,6 +217,15 @@ def _refuse_more_limits(more):
                          "determinant limits are judged on a serial engine only); leave it out or pass None")
 
 
+def _refuse_scaling(scalePasses=0, errorReduction=0.75, nSmoothScale=4):
+    """the scaling passes of DESIGN.md "Mesh quality", 10.19, are a serial engine's: the quality constraint of a decomposed mesh
+    takes the three keywords of engine.set_quality_constraint and refuses them when they would switch the passes on"""
+    if int(scalePasses) > 0:
+        raise ValueError(f"set_quality_constraint: scalePasses={int(scalePasses)} (with errorReduction={errorReduction!r}, nSmoothScale={nSmoothScale!r}) is not "
+                         "available on a decomposed mesh (the scale of a shared point needs its neighbours' scales across the ranks); leave "
+                         "scalePasses, errorReduction and nSmoothScale out or pass scalePasses=0")
+
+
 def combine_quality_constraint_records(per_rank):
     """the records of the undecomposed mesh from every rank's (DESIGN.md "Mesh quality", 10.15): `passes` and `fullRevert` are
     global values, the same on every rank; the counts are sums (a shared point counts on its master only, a processor face on
@@ -877,19 +886,21 @@ class DistributedSmoother:
         (smgpu_set_quality_constraint_limits_coupled): a processor face takes the internal branch of every face
         criterion with the neighbour rank's cell centre and cell volume, a cell's determinant runs over its internal and its
         processor faces.  With minVolRatio on the owner cells' volumes travel with the cell centres.  Every rank calls it, with
-        the same limits."""
+        the same limits.  (The scaling passes of DESIGN.md 10.19 are a serial engine's: this entry keeps its signature and does
+        not know their keywords; set_quality_constraint and set_quality_constraint_limits_all take and refuse them.)"""
         self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes,
                                         dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist,
                                              minFaceWeight=minFaceWeight, minVolRatio=minVolRatio, minDeterminant=minDeterminant))
 
     def set_quality_constraint_limits_all(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
                                           minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
-                                          maxConcave=None, minFlatness=None, minVol=None, minArea=None):
+                                          maxConcave=None, minFlatness=None, minVol=None, minArea=None, scalePasses=0, errorReduction=0.75, nSmoothScale=4):
         """set_quality_constraint_limits with the last four limits of engine.set_quality_constraint behind the six (None: off;
         smgpu_set_quality_constraint_limits_all_coupled): the keyword arguments that read_mesh_quality_dict
         returns.  The four are local to a rank: a processor face is judged on the rank's own vertex order, and nothing more
         travels.  With all four None the engine is called as set_quality_constraint_limits calls it.  Every rank calls it, with
-        the same limits."""
+        the same limits.  scalePasses > 0 is refused (a serial engine's)."""
+        _refuse_scaling(scalePasses, errorReduction, nSmoothScale)
         more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
                     minVolRatio=minVolRatio, minDeterminant=minDeterminant)
         last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
@@ -902,7 +913,8 @@ class DistributedSmoother:
         parameters), on the global mesh: a processor face is judged as the internal face it is, with the neighbour rank's cell
         centre, which travels once per pass like the coupled report's; marks and verdict as set_tangle_constraint.  Every rank
         calls it (a collective: the exempt faces need one exchange).  more: the limits of engine.set_quality_constraint that a
-        decomposed mesh does not take: one that is on is a ValueError."""
+        decomposed mesh does not take: one that is on is a ValueError, and so is scalePasses > 0 (10.19)."""
+        _refuse_scaling(**{k: more.pop(k) for k in ("scalePasses", "errorReduction", "nSmoothScale") if k in more})
         _refuse_more_limits(more)
         self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, None)
 
@@ -1278,8 +1290,9 @@ class LocalMultiSmoother:
 
     def set_quality_constraint_limits_all(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
                                           minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
-                                          maxConcave=None, minFlatness=None, minVol=None, minArea=None):
+                                          maxConcave=None, minFlatness=None, minVol=None, minArea=None, scalePasses=0, errorReduction=0.75, nSmoothScale=4):
         """as DistributedSmoother.set_quality_constraint_limits_all; nothing more moves for the four"""
+        _refuse_scaling(scalePasses, errorReduction, nSmoothScale)
         more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
                     minVolRatio=minVolRatio, minDeterminant=minDeterminant)
         last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
@@ -1289,6 +1302,7 @@ class LocalMultiSmoother:
 
     def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
         """as DistributedSmoother.set_quality_constraint; cell centres and marks move by device-side copies"""
+        _refuse_scaling(**{k: more.pop(k) for k in ("scalePasses", "errorReduction", "nSmoothScale") if k in more})
         _refuse_more_limits(more)
         self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, None)
 

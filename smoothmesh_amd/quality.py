@@ -455,17 +455,20 @@ def format_tangle_line(rec):
             + (" fullRevert" if rec.fullRevert else "") + "\n")
 
 
-def format_quality_constraint_line(rec, more=False, last=False):
+def format_quality_constraint_line(rec, more=False, last=False, scaled=False):
     """the line smoothMesh -qualityConstraint prints under the iteration line of an iteration whose nBadCells > 0 (csrc/host/
     smoothMesh_main.cpp), of a QualityConstraintRecord; more: the line of a run with one of the limits of DESIGN.md 10.16 given
     (-minTetQuality ... -minDeterminant), of a QualityConstraintRecordFull; last: the line of a run with one of the limits of 10.18
-    on (-maxConcave -minFlatness -minVol -minArea), which carries the six counts of 10.16 too, of a QualityConstraintRecordAll"""
+    on (-maxConcave -minFlatness -minVol -minArea), which carries the six counts of 10.16 too, of a QualityConstraintRecordAll;
+    scaled: the line of a run with -scalePasses > 0 (10.19), of a QualityConstraintRecordScaled: the three values of the scaling
+    passes directly in front of `passes`"""
     extra = (f" lowTetFaces {rec.nLowTetFaces} twistedFaces {rec.nLowTwistFaces} lowTriangleTwistFaces {rec.nLowTriangleTwistFaces} "
              f"lowWeightFaces {rec.nLowWeightFaces} lowVolRatioFaces {rec.nLowVolRatioFaces} underdeterminedCells {rec.nUnderdeterminedCells}") if (more or last) else ""
     if last:
         extra += f" concaveFaces {rec.nConcaveFaces} warpedFaces {rec.nWarpedFaces} smallAreaFaces {rec.nSmallAreaFaces} smallVolumeCells {rec.nSmallVolumeCells}"
+    scaling = f" scalePasses {rec.nScalePasses} pointsScaled {rec.nPointsScaled} minScale {rec.minScale:g}" if scaled else ""
     return (f"    quality constraint iteration={rec.iteration} badCells {rec.nBadCells} tangled {rec.nTangledCells} nonOrthoFaces {rec.nNonOrthoFaces} "
-            f"skewFaces {rec.nSkewFaces}{extra} passes {rec.passes} pointsReverted {rec.nPointsReverted}" + (" fullRevert" if rec.fullRevert else "") + "\n")
+            f"skewFaces {rec.nSkewFaces}{extra}{scaling} passes {rec.passes} pointsReverted {rec.nPointsReverted}" + (" fullRevert" if rec.fullRevert else "") + "\n")
 
 
 def format_quality_constraint_limits_line(state):
@@ -478,6 +481,12 @@ def format_quality_constraint_limits_line(state):
     on += "".join(f" {k} {v:g}" for k, v in last.items())
     tail = f", {state.nExemptVolumeCells} volume-exempt cells" if last else ""
     return f"Quality constraint limits:{on}, {state.nExemptDeterminantCells} determinant-exempt cells{tail}\n"
+
+
+def format_quality_constraint_scaling_line(state):
+    """the set-up line of smoothMesh -qualityConstraint with -scalePasses > 0, behind the other set-up lines of
+    the constraint; of a QualityConstraintStateScaled"""
+    return f"Quality constraint scaling: scalePasses {state.scalePasses} errorReduction {state.errorReduction:g} nSmoothScale {state.nSmoothScale}\n"
 
 
 # the keys smhost_read_mesh_quality_dict reads, in the order of its arrays (include/smhost.h)
