@@ -1,5 +1,6 @@
-// quality_loop.hpp -- the mesh quality features that follow smgpu_iterate (DESIGN.md "Mesh quality", 10.10 - 10.14): the quality
-// history, the guard on it, the tangle constraint, the quality constraint.  Host code; included by smgpu.hip once, inside its extern "C", in front of
+// quality_loop.hpp -- the mesh quality features that follow smgpu_iterate (DESIGN.md "Mesh quality", 10.10 - 10.19): the quality
+// history, the guard on it, the tangle constraint, the quality constraint (its six setters: qualityConstraintSet; its eight
+// getters: qualityConstraintRecords / qualityConstraintState).  Host code; included by smgpu.hip once, inside its extern "C", in front of
 // iterateBody, which calls into it.  State: smgpu_handle::qt, qg, tg, qc (quality_state.hpp), numbered by smgpu_handle::iterCount.
 // ---- the quality history (kernels_quality_trace.hpp, 10.10) ----
 // the running number of the points the engine holds, and how many of the next n iterations are due a record
@@ -475,9 +476,10 @@ int smgpu_tangle_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done) {
 }
 
 // ---- the quality constraint (kernels_quality_constraint.hpp, DESIGN.md "Mesh quality", 10.14) ----
-// the limits of 10.16 as the kernels take them: NULL limits, and which criteria a set of limits switches on
-static const smgpu_quality_constraint_limits kQcLimitsDefault{65.0, 4.0, 20.0, 2, -1e30, -1.0, -1.0, 0.0, 0.0, 0.0};
-static QcMore qualityConstraintMore(const smgpu_quality_constraint_limits& l) {
+// NULL limits of every entry (the narrower entries' defaults are its heads), and the limits of 10.16 as the kernels take them:
+// which criteria a set of limits switches on
+static const smgpu_quality_constraint_limits_all kQcLimitsDefault{65.0, 4.0, 20.0, 2, -1e30, -1.0, -1.0, 0.0, 0.0, 0.0, 180.0, 0.0, 0.0, 0.0};
+static QcMore qualityConstraintMore(const smgpu_quality_constraint_limits_all& l) {
     return QcMore{l.minTetQuality, l.minTwist, l.minTriangleTwist, l.minFaceWeight, l.minVolRatio, l.minDeterminant, motionThresholds(nullptr).k,
                   l.minTetQuality > -1e30 ? 1 : 0, l.minTwist > -1.0 ? 1 : 0, l.minTriangleTwist > -1.0 ? 1 : 0,
                   l.minFaceWeight > 0.0 ? 1 : 0, l.minVolRatio > 0.0 ? 1 : 0, l.minDeterminant > 0.0 ? 1 : 0};
@@ -485,12 +487,12 @@ static QcMore qualityConstraintMore(const smgpu_quality_constraint_limits& l) {
 // the limits of 10.18 as the kernels take them, and maxConcave as given (the state's); sinConcave exactly as
 // qualityGeomThresholds() (quality_reports.hpp) forms the geometry report's sine
 struct QcShapeLimits { QcShape k; double maxConcave; };
-static QcShapeLimits qualityConstraintShape(double maxConcave, double minFlatness, double minVol, double minArea) {
-    return QcShapeLimits{QcShape{std::sin(maxConcave * (SMGPU_PI / 180.0)), minFlatness, minArea, minVol, maxConcave < 180.0 ? 1 : 0, minFlatness > 0.0 ? 1 : 0,
-                                 minArea > 0.0 ? 1 : 0, minVol > 0.0 ? 1 : 0},
-                         maxConcave};
+static QcShapeLimits qualityConstraintShape(const smgpu_quality_constraint_limits_all& l) {
+    return QcShapeLimits{QcShape{std::sin(l.maxConcave * (SMGPU_PI / 180.0)), l.minFlatness, l.minArea, l.minVol, l.maxConcave < 180.0 ? 1 : 0, l.minFlatness > 0.0 ? 1 : 0,
+                                 l.minArea > 0.0 ? 1 : 0, l.minVol > 0.0 ? 1 : 0},
+                         l.maxConcave};
 }
-static const QcShapeLimits kQcShapeOff = qualityConstraintShape(180.0, 0.0, 0.0, 0.0);
+static const QcShapeLimits kQcShapeOff = qualityConstraintShape(kQcLimitsDefault);
 static int qualityConstraintOff(smgpu_handle* h) {
     h->qc.on = false;
     h->qc.more = qualityConstraintMore(kQcLimitsDefault);
@@ -703,10 +705,9 @@ static int qualityConstraintAllocate(smgpu_handle* h, const smgpu_quality_constr
     return 0;
 }
 
-// the three entries of the serial constraint: name names the one called, in its refusals; more: the limits of 10.16 (all off
-// under smgpu_set_quality_constraint); shape: those of 10.18 (all off under the two older entries)
-static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgpu_quality_constraint_params& prm, const QcMore& more,
-                                   const QcShapeLimits& shape = kQcShapeOff) {
+// the serial form (qualityConstraintSet below dispatches the six entries): name names the entry called, in its refusals; more: the
+// limits of 10.16 (all off under smgpu_set_quality_constraint); shape: those of 10.18 (all off under the two older entries)
+static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgpu_quality_constraint_params& prm, const QcMore& more, const QcShapeLimits& shape) {
     const std::string api(name);
     if (qualityConstraintRefusals(h, api, prm, more, shape, false, nullptr)) return 1;
     if (h->iterOpen) return fail(api + ": between smgpu_iter_begin and smgpu_iter_end");
@@ -726,64 +727,50 @@ static int qualityConstraintEnable(smgpu_handle* h, const char* name, const smgp
     q.on = true;
     return 0;
 }
-int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint_params* p, int32_t on) {
-    if (!h) return fail("null handle");
-    HIP_OK(hipSetDevice(h->device));
-    if (!on) return qualityConstraintOff(h);
-    const smgpu_quality_constraint_params prm = p ? *p : smgpu_quality_constraint_params{65.0, 4.0, 20.0, 2};
-    return qualityConstraintEnable(h, "smgpu_set_quality_constraint", prm, qualityConstraintMore(kQcLimitsDefault));
-}
-int smgpu_set_quality_constraint_limits(smgpu_handle* h, const smgpu_quality_constraint_limits* p, int32_t on) {
-    if (!h) return fail("null handle");
-    HIP_OK(hipSetDevice(h->device));
-    if (!on) return qualityConstraintOff(h);
-    const smgpu_quality_constraint_limits l = p ? *p : kQcLimitsDefault;
-    return qualityConstraintEnable(h, "smgpu_set_quality_constraint_limits", smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
-                                   qualityConstraintMore(l));
-}
-// 10.18's limits: the head of the struct is smgpu_quality_constraint_limits at its offsets
-static_assert(offsetof(smgpu_quality_constraint_limits_all, passes) == offsetof(smgpu_quality_constraint_limits, passes) &&
-              offsetof(smgpu_quality_constraint_limits_all, minTetQuality) == offsetof(smgpu_quality_constraint_limits, minTetQuality) &&
-              offsetof(smgpu_quality_constraint_limits_all, minDeterminant) == offsetof(smgpu_quality_constraint_limits, minDeterminant) &&
-              offsetof(smgpu_quality_constraint_limits_all, maxConcave) == sizeof(smgpu_quality_constraint_limits),
-              "smgpu_quality_constraint_limits is the head of smgpu_quality_constraint_limits_all");
-static_assert(offsetof(smgpu_quality_constraint_state_all, nExemptDeterminantCells) == offsetof(smgpu_quality_constraint_state_full, nExemptDeterminantCells) &&
-              offsetof(smgpu_quality_constraint_state_all, maxConcave) == sizeof(smgpu_quality_constraint_state_full),
-              "smgpu_quality_constraint_state_full is the head of smgpu_quality_constraint_state_all");
-static const smgpu_quality_constraint_limits_all kQcLimitsAllDefault{65.0, 4.0, 20.0, 2, -1e30, -1.0, -1.0, 0.0, 0.0, 0.0, 180.0, 0.0, 0.0, 0.0};
-static smgpu_quality_constraint_limits qualityConstraintHead(const smgpu_quality_constraint_limits_all& l) {
-    return smgpu_quality_constraint_limits{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes, l.minTetQuality, l.minTwist, l.minTriangleTwist,
-                                           l.minFaceWeight, l.minVolRatio, l.minDeterminant};
-}
-int smgpu_set_quality_constraint_limits_all(smgpu_handle* h, const smgpu_quality_constraint_limits_all* p, int32_t on) {
-    if (!h) return fail("null handle");
-    HIP_OK(hipSetDevice(h->device));
-    if (!on) return qualityConstraintOff(h);
-    const smgpu_quality_constraint_limits_all l = p ? *p : kQcLimitsAllDefault;
-    return qualityConstraintEnable(h, "smgpu_set_quality_constraint_limits_all",
-                                   smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
-                                   qualityConstraintMore(qualityConstraintHead(l)), qualityConstraintShape(l.maxConcave, l.minFlatness, l.minVol, l.minArea));
-}
+// The getters.  Every record in the slab and the one state are the widest (10.19's); a narrower getter answers with their head
+// (quality_state.hpp, QC_HEAD_OF).  api names the entry called, in its refusals.
 static int qualityConstraintCoupledFlush(smgpu_handle* h);
-int smgpu_get_quality_constraint_records_all(smgpu_handle* h, smgpu_quality_constraint_record_all* out, int64_t cap, int64_t* n) {
+extern "C++" {
+template <class Rec>
+static int qualityConstraintRecords(smgpu_handle* h, Rec* out, int64_t cap, int64_t* n, const char* api) {
     if (!h || !n) return fail("null argument");
-    if (h->qc.coupled) {
-        if (h->qc.k >= 0) return fail("smgpu_get_quality_constraint_records_all: between the passes of an iteration (smgpu_quality_constraint_pass_begin / _end)");
+    if (h->qc.coupled) {   // the records of the chunk in use are still on the device
+        if (h->qc.k >= 0) return fail(std::string(api) + ": between the passes of an iteration (smgpu_quality_constraint_pass_begin / _end)");
         HIP_OK(hipSetDevice(h->device));
         if (qualityConstraintCoupledFlush(h)) return 1;
     }
-    return h->qc.slab.drainHeads(out, cap, n, "smgpu_get_quality_constraint_records_all");
+    return h->qc.slab.drainHeads(out, cap, n, api);
 }
-int smgpu_get_quality_constraint_state_all(smgpu_handle* h, smgpu_quality_constraint_state_all* out) {
+// while the constraint is off, or enabled with its exempt faces not taken yet, the counts and the running number read 0
+template <class State>
+static int qualityConstraintState(smgpu_handle* h, State* out) {
     if (!h || !out) return fail("null argument");
-    smgpu_quality_constraint_state_full s{};
-    if (smgpu_get_quality_constraint_state_full(h, &s)) return 1;
     const QualityConstraintHost& q = h->qc;
-    *out = smgpu_quality_constraint_state_all{s.on, s.passes, s.maxNonOrtho, s.maxInternalSkewness, s.maxBoundarySkewness, s.nExemptCells, s.nExemptFaces, s.iteration,
-                                              s.minTetQuality, s.minTwist, s.minTriangleTwist, s.minFaceWeight, s.minVolRatio, s.minDeterminant,
-                                              s.nExemptDeterminantCells, q.maxConcave, q.shape.minFlat, q.shape.minVol, q.shape.minArea, s.on ? q.nExemptVol : 0};
+    const bool on = q.on && !q.pending;
+    const int64_t number = q.coupled ? q.count : h->iterCount - q.since;
+    *out = qcHead<State>(smgpu_quality_constraint_state_scaled{
+        on ? 1 : 0, q.prm.passes, q.prm.maxNonOrtho, q.prm.maxInternalSkewness, q.prm.maxBoundarySkewness, on ? q.nExemptCells : 0, on ? q.nExemptFaces : 0, on ? number : 0,
+        q.more.minTet, q.more.minTwist, q.more.minTri, q.more.minWeight, q.more.minRatio, q.more.minDet, on ? q.nExemptDet : 0,
+        q.maxConcave, q.shape.minFlat, q.shape.minVol, q.shape.minArea, on ? q.nExemptVol : 0, q.scaling.scalePasses, q.scaling.nSmoothScale, q.scaling.errorReduction});
     return 0;
 }
+}
+int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n) {
+    return qualityConstraintRecords(h, out, cap, n, "smgpu_get_quality_constraint_records");
+}
+int smgpu_get_quality_constraint_records_full(smgpu_handle* h, smgpu_quality_constraint_record_full* out, int64_t cap, int64_t* n) {
+    return qualityConstraintRecords(h, out, cap, n, "smgpu_get_quality_constraint_records_full");
+}
+int smgpu_get_quality_constraint_records_all(smgpu_handle* h, smgpu_quality_constraint_record_all* out, int64_t cap, int64_t* n) {
+    return qualityConstraintRecords(h, out, cap, n, "smgpu_get_quality_constraint_records_all");
+}
+int smgpu_get_quality_constraint_records_scaled(smgpu_handle* h, smgpu_quality_constraint_record_scaled* out, int64_t cap, int64_t* n) {
+    return qualityConstraintRecords(h, out, cap, n, "smgpu_get_quality_constraint_records_scaled");
+}
+int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint_state* out) { return qualityConstraintState(h, out); }
+int smgpu_get_quality_constraint_state_full(smgpu_handle* h, smgpu_quality_constraint_state_full* out) { return qualityConstraintState(h, out); }
+int smgpu_get_quality_constraint_state_all(smgpu_handle* h, smgpu_quality_constraint_state_all* out) { return qualityConstraintState(h, out); }
+int smgpu_get_quality_constraint_state_scaled(smgpu_handle* h, smgpu_quality_constraint_state_scaled* out) { return qualityConstraintState(h, out); }
 // 10.19: the scaling passes of the serial constraint.  Their memory is the constraint's own second block: allocated here, freed
 // here with scalePasses = 0 and by everything that switches the constraint off (QualityConstraintHost::release)
 int smgpu_set_quality_constraint_scaling(smgpu_handle* h, const smgpu_quality_constraint_scaling* p) {
@@ -817,62 +804,6 @@ int smgpu_set_quality_constraint_scaling(smgpu_handle* h, const smgpu_quality_co
     q.nScale = (long long)nScale;
     q.maxGrid = std::max(1, envInt("SMGPU_QS_MAX_GRID", kQsMaxGrid));   // (tests: several trips per lane on a small mesh)
     q.scaling = prm;
-    return 0;
-}
-int smgpu_get_quality_constraint_records_scaled(smgpu_handle* h, smgpu_quality_constraint_record_scaled* out, int64_t cap, int64_t* n) {
-    if (!h || !n) return fail("null argument");
-    if (h->qc.coupled) {
-        if (h->qc.k >= 0) return fail("smgpu_get_quality_constraint_records_scaled: between the passes of an iteration (smgpu_quality_constraint_pass_begin / _end)");
-        HIP_OK(hipSetDevice(h->device));
-        if (qualityConstraintCoupledFlush(h)) return 1;
-    }
-    return h->qc.slab.drain(out, cap, n, "smgpu_get_quality_constraint_records_scaled");
-}
-int smgpu_get_quality_constraint_state_scaled(smgpu_handle* h, smgpu_quality_constraint_state_scaled* out) {
-    if (!h || !out) return fail("null argument");
-    smgpu_quality_constraint_state_all s{};
-    if (smgpu_get_quality_constraint_state_all(h, &s)) return 1;
-    const smgpu_quality_constraint_scaling& c = h->qc.scaling;
-    *out = smgpu_quality_constraint_state_scaled{s.on, s.passes, s.maxNonOrtho, s.maxInternalSkewness, s.maxBoundarySkewness, s.nExemptCells, s.nExemptFaces, s.iteration,
-                                                 s.minTetQuality, s.minTwist, s.minTriangleTwist, s.minFaceWeight, s.minVolRatio, s.minDeterminant,
-                                                 s.nExemptDeterminantCells, s.maxConcave, s.minFlatness, s.minVol, s.minArea, s.nExemptVolumeCells,
-                                                 c.scalePasses, c.nSmoothScale, c.errorReduction};
-    return 0;
-}
-int smgpu_get_quality_constraint_records(smgpu_handle* h, smgpu_quality_constraint_record* out, int64_t cap, int64_t* n) {
-    if (!h || !n) return fail("null argument");
-    if (h->qc.coupled) {   // the records of the chunk in use are still on the device
-        if (h->qc.k >= 0) return fail("smgpu_get_quality_constraint_records: between the passes of an iteration (smgpu_quality_constraint_pass_begin / _end)");
-        HIP_OK(hipSetDevice(h->device));
-        if (qualityConstraintCoupledFlush(h)) return 1;
-    }
-    return h->qc.slab.drainHeads(out, cap, n, "smgpu_get_quality_constraint_records");
-}
-int smgpu_get_quality_constraint_records_full(smgpu_handle* h, smgpu_quality_constraint_record_full* out, int64_t cap, int64_t* n) {
-    if (!h || !n) return fail("null argument");
-    if (h->qc.coupled) {
-        if (h->qc.k >= 0) return fail("smgpu_get_quality_constraint_records_full: between the passes of an iteration (smgpu_quality_constraint_pass_begin / _end)");
-        HIP_OK(hipSetDevice(h->device));
-        if (qualityConstraintCoupledFlush(h)) return 1;
-    }
-    return h->qc.slab.drainHeads(out, cap, n, "smgpu_get_quality_constraint_records_full");
-}
-int smgpu_get_quality_constraint_state_full(smgpu_handle* h, smgpu_quality_constraint_state_full* out) {
-    if (!h || !out) return fail("null argument");
-    smgpu_quality_constraint_state s{};
-    if (smgpu_get_quality_constraint_state(h, &s)) return 1;
-    const QcMore& m = h->qc.more;
-    *out = smgpu_quality_constraint_state_full{s.on, s.passes, s.maxNonOrtho, s.maxInternalSkewness, s.maxBoundarySkewness, s.nExemptCells, s.nExemptFaces, s.iteration,
-                                               m.minTet, m.minTwist, m.minTri, m.minWeight, m.minRatio, m.minDet, s.on ? h->qc.nExemptDet : 0};
-    return 0;
-}
-int smgpu_get_quality_constraint_state(smgpu_handle* h, smgpu_quality_constraint_state* out) {
-    if (!h || !out) return fail("null argument");
-    const QualityConstraintHost& q = h->qc;
-    const bool on = q.on && !q.pending;
-    const int64_t number = q.coupled ? q.count : h->iterCount - q.since;
-    *out = smgpu_quality_constraint_state{on ? 1 : 0, q.prm.passes, q.prm.maxNonOrtho, q.prm.maxInternalSkewness, q.prm.maxBoundarySkewness,
-                                          on ? q.nExemptCells : 0, on ? q.nExemptFaces : 0, on ? number : 0};
     return 0;
 }
 
@@ -921,13 +852,12 @@ static int qualityConstraintCoupledVerdicts(smgpu_handle* h, bool enabling, QcDe
     return checkDeviceError(h);
 }
 
-// the two entries of the coupled constraint, as qualityConstraintEnable is the serial pair's: name names the one called, in its
-// refusals; full: smgpu_set_quality_constraint_limits_coupled (10.17) with the limits of 10.16 in more and its two volume buffers
-// in d; else more is all off and d's tail null
+// the coupled form (qualityConstraintSet below dispatches the six entries): name names the entry called, in its refusals, serial
+// the entry a serial engine takes; full: one of the two entries with volume buffers in d (10.17, 10.18), which the refusal of the
+// other coupled entry names; else more is all off and d's tail null
 static int qualityConstraintCoupledEnable(smgpu_handle* h, const char* name, bool full, const smgpu_quality_constraint_params& prm, const QcMore& more,
-                                          const smgpu_quality_constraint_halo_desc_full* d, const QcShapeLimits& shape = kQcShapeOff, const char* serial = nullptr) {
+                                          const smgpu_quality_constraint_halo_desc_full* d, const QcShapeLimits& shape, const char* serial) {
     const std::string api(name);
-    if (!serial) serial = full ? "smgpu_set_quality_constraint_limits" : "smgpu_set_quality_constraint";
     if (qualityConstraintRefusals(h, api, prm, more, shape, true, serial)) return 1;
     if (h->qc.on && h->qc.coupled && h->qc.full != full)
         return fail(api + ": the quality constraint is on through " + (full ? "smgpu_set_quality_constraint_coupled" : "smgpu_set_quality_constraint_limits_coupled") +
@@ -966,42 +896,40 @@ static int qualityConstraintCoupledEnable(smgpu_handle* h, const char* name, boo
     q.on = true;
     return 0;
 }
-int smgpu_set_quality_constraint_coupled(smgpu_handle* h, const smgpu_quality_constraint_params* p, const smgpu_quality_constraint_halo_desc* d, int32_t on) {
+// The six entries.  What one asks for: the widest limits, the name of the entry called, and for a coupled entry the name of the
+// entry a serial engine takes (NULL: a serial entry) and `full`.  Each widens its limits over the defaults (NULL: the defaults;
+// a narrower struct is the head of the widest, quality_state.hpp), names itself, and goes through the one body.
+struct QcRequest { smgpu_quality_constraint_limits_all l; const char *name, *serial; bool full; };
+static int qualityConstraintSet(smgpu_handle* h, int32_t on, const QcRequest& r, const smgpu_quality_constraint_halo_desc_full* d) {
     if (!h) return fail("null handle");
     HIP_OK(hipSetDevice(h->device));
     if (!on) return qualityConstraintOff(h);
-    const smgpu_quality_constraint_params prm = p ? *p : smgpu_quality_constraint_params{65.0, 4.0, 20.0, 2};
-    smgpu_quality_constraint_halo_desc_full df{};
-    if (d) df = smgpu_quality_constraint_halo_desc_full{d->sendT, d->recvT, d->sendCc, d->recvCc, d->coupling, nullptr, nullptr};
-    return qualityConstraintCoupledEnable(h, "smgpu_set_quality_constraint_coupled", false, prm, qualityConstraintMore(kQcLimitsDefault), d ? &df : nullptr);
+    const smgpu_quality_constraint_params prm = qcHead<smgpu_quality_constraint_params>(r.l);
+    if (r.serial) return qualityConstraintCoupledEnable(h, r.name, r.full, prm, qualityConstraintMore(r.l), d, qualityConstraintShape(r.l), r.serial);
+    return qualityConstraintEnable(h, r.name, prm, qualityConstraintMore(r.l), qualityConstraintShape(r.l));
 }
-static_assert(offsetof(smgpu_quality_constraint_halo_desc_full, sendT) == offsetof(smgpu_quality_constraint_halo_desc, sendT) &&
-              offsetof(smgpu_quality_constraint_halo_desc_full, recvT) == offsetof(smgpu_quality_constraint_halo_desc, recvT) &&
-              offsetof(smgpu_quality_constraint_halo_desc_full, sendCc) == offsetof(smgpu_quality_constraint_halo_desc, sendCc) &&
-              offsetof(smgpu_quality_constraint_halo_desc_full, recvCc) == offsetof(smgpu_quality_constraint_halo_desc, recvCc) &&
-              offsetof(smgpu_quality_constraint_halo_desc_full, coupling) == offsetof(smgpu_quality_constraint_halo_desc, coupling) &&
-              offsetof(smgpu_quality_constraint_halo_desc_full, sendVc) == sizeof(smgpu_quality_constraint_halo_desc),
-              "smgpu_quality_constraint_halo_desc is the head of the full descriptor");
+int smgpu_set_quality_constraint(smgpu_handle* h, const smgpu_quality_constraint_params* p, int32_t on) {
+    return qualityConstraintSet(h, on, QcRequest{qcWiden(p, kQcLimitsDefault), "smgpu_set_quality_constraint", nullptr, false}, nullptr);
+}
+int smgpu_set_quality_constraint_limits(smgpu_handle* h, const smgpu_quality_constraint_limits* p, int32_t on) {
+    return qualityConstraintSet(h, on, QcRequest{qcWiden(p, kQcLimitsDefault), "smgpu_set_quality_constraint_limits", nullptr, false}, nullptr);
+}
+int smgpu_set_quality_constraint_limits_all(smgpu_handle* h, const smgpu_quality_constraint_limits_all* p, int32_t on) {
+    return qualityConstraintSet(h, on, QcRequest{qcWiden(p, kQcLimitsDefault), "smgpu_set_quality_constraint_limits_all", nullptr, false}, nullptr);
+}
+int smgpu_set_quality_constraint_coupled(smgpu_handle* h, const smgpu_quality_constraint_params* p, const smgpu_quality_constraint_halo_desc* d, int32_t on) {
+    const smgpu_quality_constraint_halo_desc_full df = qcWiden(d, smgpu_quality_constraint_halo_desc_full{});
+    return qualityConstraintSet(h, on, QcRequest{qcWiden(p, kQcLimitsDefault), "smgpu_set_quality_constraint_coupled", "smgpu_set_quality_constraint", false},
+                                d ? &df : nullptr);
+}
 int smgpu_set_quality_constraint_limits_coupled(smgpu_handle* h, const smgpu_quality_constraint_limits* p, const smgpu_quality_constraint_halo_desc_full* d,
                                                 int32_t on) {
-    if (!h) return fail("null handle");
-    HIP_OK(hipSetDevice(h->device));
-    if (!on) return qualityConstraintOff(h);
-    const smgpu_quality_constraint_limits l = p ? *p : kQcLimitsDefault;
-    return qualityConstraintCoupledEnable(h, "smgpu_set_quality_constraint_limits_coupled", true,
-                                          smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
-                                          qualityConstraintMore(l), d);
+    return qualityConstraintSet(h, on, QcRequest{qcWiden(p, kQcLimitsDefault), "smgpu_set_quality_constraint_limits_coupled", "smgpu_set_quality_constraint_limits", true}, d);
 }
 int smgpu_set_quality_constraint_limits_all_coupled(smgpu_handle* h, const smgpu_quality_constraint_limits_all* p, const smgpu_quality_constraint_halo_desc_full* d,
                                                     int32_t on) {
-    if (!h) return fail("null handle");
-    HIP_OK(hipSetDevice(h->device));
-    if (!on) return qualityConstraintOff(h);
-    const smgpu_quality_constraint_limits_all l = p ? *p : kQcLimitsAllDefault;
-    return qualityConstraintCoupledEnable(h, "smgpu_set_quality_constraint_limits_all_coupled", true,
-                                          smgpu_quality_constraint_params{l.maxNonOrtho, l.maxInternalSkewness, l.maxBoundarySkewness, l.passes},
-                                          qualityConstraintMore(qualityConstraintHead(l)), d, qualityConstraintShape(l.maxConcave, l.minFlatness, l.minVol, l.minArea),
-                                          "smgpu_set_quality_constraint_limits_all");
+    return qualityConstraintSet(h, on, QcRequest{qcWiden(p, kQcLimitsDefault), "smgpu_set_quality_constraint_limits_all_coupled", "smgpu_set_quality_constraint_limits_all", true},
+                                d);
 }
 int smgpu_quality_constraint_coupled_exempt(smgpu_handle* h) {
     if (!h) return fail("null handle");

@@ -199,6 +199,64 @@ struct TangleHost {
     void release() { block.release(); slab.release(); coupled = passOpen = slabFresh = false; k = -1; slabUsed = 0; }
 };
 
+// The tiered structs of the quality constraint (include/smgpu.h, 10.14 - 10.19): every narrower struct is the head of the next
+// wider one.  quality_loop.hpp relies on it: a setter widens its argument by copying it over the head of the widest defaults, a
+// getter answers with the head of the widest struct.  QC_HEAD_OF asserts it completely: the fields listed tile the narrow
+// struct with nothing between them but alignment (none is left out), each has the same offset and size in the wide one, and the
+// first field the wide one adds sits at sizeof(narrow).
+struct QcFieldAt { size_t narrow, wide, size, wideSize; };
+template <size_t N>
+constexpr bool qcHeadOf(const QcFieldAt (&f)[N], size_t narrowSize, size_t narrowAlign, size_t firstAdded) {
+    size_t end = 0;
+    for (size_t i = 0; i < N; ++i) {
+        const size_t a = f[i].size < narrowAlign ? f[i].size : narrowAlign;   // scalars and pointers: aligned to their size
+        if (f[i].narrow != (end + a - 1) / a * a || f[i].wide != f[i].narrow || f[i].wideSize != f[i].size) return false;
+        end = f[i].narrow + f[i].size;
+    }
+    return (end + narrowAlign - 1) / narrowAlign * narrowAlign == narrowSize && firstAdded == narrowSize;
+}
+#define QC_FIELD(N, W, f) {offsetof(N, f), offsetof(W, f), sizeof(N::f), sizeof(W::f)},
+#define QC_HEAD_OF(N, W, FIELDS, added)                                                                                        \
+    static_assert([] { constexpr QcFieldAt at[] = {FIELDS(QC_FIELD, N, W)}; return qcHeadOf(at, sizeof(N), alignof(N), offsetof(W, added)); }(), \
+                  #N " is the head of " #W)
+#define QC_PARAMS_FIELDS(X, N, W) X(N, W, maxNonOrtho) X(N, W, maxInternalSkewness) X(N, W, maxBoundarySkewness) X(N, W, passes)
+#define QC_LIMITS_FIELDS(X, N, W)                                                                                              \
+    QC_PARAMS_FIELDS(X, N, W) X(N, W, minTetQuality) X(N, W, minTwist) X(N, W, minTriangleTwist) X(N, W, minFaceWeight) X(N, W, minVolRatio) X(N, W, minDeterminant)
+#define QC_RECORD_FIELDS(X, N, W)                                                                                              \
+    X(N, W, iteration) X(N, W, passes) X(N, W, fullRevert) X(N, W, nBadCells) X(N, W, nPointsReverted) X(N, W, nTangledCells) X(N, W, nNonOrthoFaces) X(N, W, nSkewFaces)
+#define QC_RECORD_FULL_FIELDS(X, N, W)                                                                                         \
+    QC_RECORD_FIELDS(X, N, W) X(N, W, nLowTetFaces) X(N, W, nLowTwistFaces) X(N, W, nLowTriangleTwistFaces) X(N, W, nLowWeightFaces) X(N, W, nLowVolRatioFaces) X(N, W, nUnderdeterminedCells)
+#define QC_RECORD_ALL_FIELDS(X, N, W) QC_RECORD_FULL_FIELDS(X, N, W) X(N, W, nConcaveFaces) X(N, W, nWarpedFaces) X(N, W, nSmallAreaFaces) X(N, W, nSmallVolumeCells)
+#define QC_STATE_FIELDS(X, N, W)                                                                                               \
+    X(N, W, on) X(N, W, passes) X(N, W, maxNonOrtho) X(N, W, maxInternalSkewness) X(N, W, maxBoundarySkewness) X(N, W, nExemptCells) X(N, W, nExemptFaces) X(N, W, iteration)
+#define QC_STATE_FULL_FIELDS(X, N, W)                                                                                          \
+    QC_STATE_FIELDS(X, N, W) X(N, W, minTetQuality) X(N, W, minTwist) X(N, W, minTriangleTwist) X(N, W, minFaceWeight) X(N, W, minVolRatio) X(N, W, minDeterminant) X(N, W, nExemptDeterminantCells)
+#define QC_STATE_ALL_FIELDS(X, N, W) QC_STATE_FULL_FIELDS(X, N, W) X(N, W, maxConcave) X(N, W, minFlatness) X(N, W, minVol) X(N, W, minArea) X(N, W, nExemptVolumeCells)
+#define QC_HALO_FIELDS(X, N, W) X(N, W, sendT) X(N, W, recvT) X(N, W, sendCc) X(N, W, recvCc) X(N, W, coupling)
+QC_HEAD_OF(smgpu_quality_constraint_params, smgpu_quality_constraint_limits, QC_PARAMS_FIELDS, minTetQuality);
+QC_HEAD_OF(smgpu_quality_constraint_limits, smgpu_quality_constraint_limits_all, QC_LIMITS_FIELDS, maxConcave);
+QC_HEAD_OF(smgpu_quality_constraint_record, smgpu_quality_constraint_record_full, QC_RECORD_FIELDS, nLowTetFaces);
+QC_HEAD_OF(smgpu_quality_constraint_record_full, smgpu_quality_constraint_record_all, QC_RECORD_FULL_FIELDS, nConcaveFaces);
+QC_HEAD_OF(smgpu_quality_constraint_record_all, smgpu_quality_constraint_record_scaled, QC_RECORD_ALL_FIELDS, nScalePasses);
+QC_HEAD_OF(smgpu_quality_constraint_state, smgpu_quality_constraint_state_full, QC_STATE_FIELDS, minTetQuality);
+QC_HEAD_OF(smgpu_quality_constraint_state_full, smgpu_quality_constraint_state_all, QC_STATE_FULL_FIELDS, maxConcave);
+QC_HEAD_OF(smgpu_quality_constraint_state_all, smgpu_quality_constraint_state_scaled, QC_STATE_ALL_FIELDS, scalePasses);
+QC_HEAD_OF(smgpu_quality_constraint_halo_desc, smgpu_quality_constraint_halo_desc_full, QC_HALO_FIELDS, sendVc);
+// the head of `wide` as the narrower struct Head, and a narrower struct (NULL: nothing) over the head of `wide`
+template <class Head, class Wide>
+static Head qcHead(const Wide& wide) {
+    static_assert(sizeof(Head) <= sizeof(Wide), "a head is no longer than the struct");
+    Head out;
+    std::memcpy(&out, &wide, sizeof(Head));
+    return out;
+}
+template <class Wide, class Head>
+static Wide qcWiden(const Head* head, Wide wide) {
+    static_assert(sizeof(Head) <= sizeof(Wide), "a head is no longer than the struct");
+    if (head) std::memcpy(&wide, head, sizeof(Head));
+    return wide;
+}
+
 // The quality constraint (smgpu_set_quality_constraint, kernels_quality_constraint.hpp): allocated at enabling.  exemptCell /
 // cellFlag / tangled: one byte per cell; exemptFace: one per face; marks: one per point (rounded up to whole words); cellCtr / acc: the
 // cell centres and the stop word of its geometry launches, with and without tiles

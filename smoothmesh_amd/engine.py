@@ -246,6 +246,24 @@ class QualityConstraintStateAll(QualityConstraintStateFull):
     nExemptVolumeCells: int = 0
 
 
+# the entries of include/smgpu.h by tier: the three limits only (10.14), with the six (10.16), with the four (10.18); a coupled
+# entry is the serial one's name + "_coupled"
+_QC_ENTRIES = (("smgpu_set_quality_constraint", _ffi.QualityConstraintParams), ("smgpu_set_quality_constraint_limits", _ffi.QualityConstraintLimits),
+               ("smgpu_set_quality_constraint_limits_all", _ffi.QualityConstraintLimitsAll))
+
+
+def quality_constraint_request(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, limits, least=0):
+    """(ctypes struct, tier) of the entry of _QC_ENTRIES a set of limits takes: the narrowest that holds every limit given (not
+    None), and none below `least`; a limit that is None goes in at its off value.  limits: by name, those of
+    QUALITY_CONSTRAINT_LIMITS_OFF and QUALITY_CONSTRAINT_LIMITS_ALL_OFF"""
+    off = {**QUALITY_CONSTRAINT_LIMITS_OFF, **QUALITY_CONSTRAINT_LIMITS_ALL_OFF}
+    given = {k for k, v in limits.items() if v is not None}
+    tier = max(least, 2 if given & set(QUALITY_CONSTRAINT_LIMITS_ALL_OFF) else 1 if given else 0)
+    ctype = _QC_ENTRIES[tier][1]
+    more = {k: off[k] if limits.get(k) is None else float(limits[k]) for k, _ in ctype._fields_[4:]}
+    return ctype(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more), tier
+
+
 @dataclass
 class QualityConstraintRecordScaled(QualityConstraintRecordAll):
     """smgpu_quality_constraint_record_scaled (DESIGN.md "Mesh quality", 10.19): QualityConstraintRecordAll, then the marked passes
@@ -483,6 +501,22 @@ class SmoothEngine:
         if rc:
             raise SmgpuError(self._lib.smgpu_last_error().decode())
 
+    def _drain(self, getter, ctype, record):
+        """the pending records behind `getter` (a count call, then the read, which clears them) as `record` dataclasses"""
+        n = C.c_int64(0)
+        self._check(getter(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        buf = (ctype * n.value)()
+        self._check(getter(self._h, buf, n.value, C.byref(n)))
+        return [record(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+
+    def _read_state(self, getter, ctype, state):
+        """the struct behind `getter` as a `state` dataclass, `on` a bool"""
+        s = ctype()
+        self._check(getter(self._h, C.byref(s)))
+        return state(**{f: bool(s.on) if f == "on" else getattr(s, f) for f, _ in s._fields_})
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.smgpu_destroy(self._h)
@@ -707,13 +741,7 @@ class SmoothEngine:
 
     def quality_trace(self) -> list:
         """The pending records of the quality history, in ascending iteration; clears them."""
-        n = C.c_int64(0)
-        self._check(self._lib.smgpu_get_quality_trace(self._h, None, 0, C.byref(n)))
-        if n.value == 0:
-            return []
-        buf = (_ffi.QualityTraceRecord * n.value)()
-        self._check(self._lib.smgpu_get_quality_trace(self._h, buf, n.value, C.byref(n)))
-        return [QualityTraceRecord(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+        return self._drain(self._lib.smgpu_get_quality_trace, _ffi.QualityTraceRecord, QualityTraceRecord)
 
     def set_quality_guard(self, criteria=("nonPositiveVolume", "wrongOriented"), refine=True):
         """Guard on the quality history (include/smgpu.h, smgpu_set_quality_guard); needs set_quality_trace first.  The points now
@@ -785,18 +813,10 @@ class SmoothEngine:
 
     def tangle_records(self) -> list:
         """The pending records of the tangle constraint, one per iteration that ran, in ascending iteration; clears them."""
-        n = C.c_int64(0)
-        self._check(self._lib.smgpu_get_tangle_records(self._h, None, 0, C.byref(n)))
-        if n.value == 0:
-            return []
-        buf = (_ffi.TangleRecord * n.value)()
-        self._check(self._lib.smgpu_get_tangle_records(self._h, buf, n.value, C.byref(n)))
-        return [TangleRecord(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+        return self._drain(self._lib.smgpu_get_tangle_records, _ffi.TangleRecord, TangleRecord)
 
     def tangle_state(self) -> TangleState:
-        s = _ffi.TangleState()
-        self._check(self._lib.smgpu_get_tangle_state(self._h, C.byref(s)))
-        return TangleState(on=bool(s.on), passes=s.passes, nExemptCells=s.nExemptCells, iteration=s.iteration)
+        return self._read_state(self._lib.smgpu_get_tangle_state, _ffi.TangleState, TangleState)
 
     def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
                                minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
@@ -817,8 +837,10 @@ class SmoothEngine:
         None the call goes through the entry it went through before.
         scalePasses > 0 then switches the scaling passes on: set_quality_constraint_scaling with the three
         keywords; if that is refused the constraint is left off.  With scalePasses = 0 the call is what it was."""
-        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, minTetQuality, minTwist, minTriangleTwist,
-                                        minFaceWeight, minVolRatio, minDeterminant, maxConcave, minFlatness, minVol, minArea)
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes,
+                                        dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
+                                             minVolRatio=minVolRatio, minDeterminant=minDeterminant, maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol,
+                                             minArea=minArea))
         if scalePasses != 0:
             try:
                 self.set_quality_constraint_scaling(scalePasses, errorReduction, nSmoothScale)
@@ -835,25 +857,16 @@ class SmoothEngine:
         p = _ffi.QualityConstraintScaling(int(scalePasses), int(nSmoothScale), float(errorReduction))
         self._check(self._lib.smgpu_set_quality_constraint_scaling(self._h, C.byref(p)))
 
-    def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, minTetQuality, minTwist, minTriangleTwist,
-                                   minFaceWeight, minVolRatio, minDeterminant, maxConcave, minFlatness, minVol, minArea):
-        """the entry of include/smgpu.h a set of limits takes: the narrowest that holds every limit given"""
-        more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
-                    minVolRatio=minVolRatio, minDeterminant=minDeterminant)
-        last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
-        if any(v is not None for v in last.values()):
-            more = {k: QUALITY_CONSTRAINT_LIMITS_OFF[k] if v is None else float(v) for k, v in more.items()}
-            last = {k: QUALITY_CONSTRAINT_LIMITS_ALL_OFF[k] if v is None else float(v) for k, v in last.items()}
-            p = _ffi.QualityConstraintLimitsAll(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more, **last)
-            self._check(self._lib.smgpu_set_quality_constraint_limits_all(self._h, C.byref(p), 1))
-            return
-        if all(v is None for v in more.values()):
-            p = _ffi.QualityConstraintParams(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes))
-            self._check(self._lib.smgpu_set_quality_constraint(self._h, C.byref(p), 1))
-            return
-        more = {k: QUALITY_CONSTRAINT_LIMITS_OFF[k] if v is None else float(v) for k, v in more.items()}
-        p = _ffi.QualityConstraintLimits(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more)
-        self._check(self._lib.smgpu_set_quality_constraint_limits(self._h, C.byref(p), 1))
+    def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, limits, least=0, coupled=None):
+        """through the entry of include/smgpu.h the limits take (quality_constraint_request); coupled: the arguments of
+        _coupled_desc, for the coupled entry of the same tier"""
+        p, tier = quality_constraint_request(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, limits, least)
+        name = _QC_ENTRIES[tier][0]
+        if coupled is None:
+            self._check(getattr(self._lib, name)(self._h, C.byref(p), 1))
+        else:
+            d = self._coupled_desc(tier > 0, *coupled)
+            self._check(getattr(self._lib, name + "_coupled")(self._h, C.byref(p), C.byref(d), 1))
 
     def clear_quality_constraint(self):
         """Switch the quality constraint (either form) off; discards unread records."""
@@ -866,14 +879,7 @@ class SmoothEngine:
         sendCc / recvCc: of 3 doubles per processor face, all the caller's.  Returns with sendCc packed at the current points: the
         caller moves it to the neighbours' recvCc and calls quality_constraint_coupled_exempt.  The passes are the caller's too:
         quality_constraint_pass_begin / _pass_faces / _pass_end behind every iter_end."""
-        rank, pats = coupling
-        st = np.array([p[0] for p in pats], np.int32)
-        sz = np.array([p[1] for p in pats], np.int32)
-        nb = np.array([p[2] for p in pats], np.int32)
-        c = _ffi.QualityCoupling(int(rank), len(pats), _p(st, _ffi.c_i32p), _p(sz, _ffi.c_i32p), _p(nb, _ffi.c_i32p))
-        p = _ffi.QualityConstraintParams(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes))
-        d = _ffi.QualityConstraintHaloDesc(sendT or None, recvT or None, sendCc or None, recvCc or None, C.pointer(c))
-        self._check(self._lib.smgpu_set_quality_constraint_coupled(self._h, C.byref(p), C.byref(d), 1))
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, {}, coupled=(coupling, sendT, recvT, sendCc, recvCc))
 
     def set_quality_constraint_limits_coupled(self, coupling, sendT, recvT, sendCc, recvCc, sendVc=0, recvVc=0, maxNonOrtho=65.0,
                                               maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None, minTwist=None,
@@ -883,23 +889,11 @@ class SmoothEngine:
         DESIGN.md "Mesh quality", 10.17; None: off).  sendVc / recvVc: raw device addresses of one double per processor face, needed
         while minVolRatio is on: the call returns with sendVc packed next to sendCc, the caller moves both, and so behind every
         quality_constraint_pass_begin."""
-        rank, pats = coupling
-        st = np.array([p[0] for p in pats], np.int32)
-        sz = np.array([p[1] for p in pats], np.int32)
-        nb = np.array([p[2] for p in pats], np.int32)
-        c = _ffi.QualityCoupling(int(rank), len(pats), _p(st, _ffi.c_i32p), _p(sz, _ffi.c_i32p), _p(nb, _ffi.c_i32p))
-        more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
-                    minVolRatio=minVolRatio, minDeterminant=minDeterminant)
-        more = {k: QUALITY_CONSTRAINT_LIMITS_OFF[k] if v is None else float(v) for k, v in more.items()}
-        d = _ffi.QualityConstraintHaloDescFull(sendT or None, recvT or None, sendCc or None, recvCc or None, C.pointer(c), sendVc or None, recvVc or None)
-        last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
-        if any(v is not None for v in last.values()):   # (DESIGN.md 10.18; with all four None: the entry of 10.17, as before)
-            last = {k: QUALITY_CONSTRAINT_LIMITS_ALL_OFF[k] if v is None else float(v) for k, v in last.items()}
-            p = _ffi.QualityConstraintLimitsAll(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more, **last)
-            self._check(self._lib.smgpu_set_quality_constraint_limits_all_coupled(self._h, C.byref(p), C.byref(d), 1))
-            return
-        p = _ffi.QualityConstraintLimits(float(maxNonOrtho), float(maxInternalSkewness), float(maxBoundarySkewness), int(passes), **more)
-        self._check(self._lib.smgpu_set_quality_constraint_limits_coupled(self._h, C.byref(p), C.byref(d), 1))
+        # (DESIGN.md 10.18: with the last four all None the entry of 10.17, as before)
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes,
+                                        dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
+                                             minVolRatio=minVolRatio, minDeterminant=minDeterminant, maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol,
+                                             minArea=minArea), least=1, coupled=(coupling, sendT, recvT, sendCc, recvCc, sendVc, recvVc))
 
     def quality_constraint_coupled_exempt(self):
         """the face verdicts of the enabling evaluation, with the neighbours' cell centres in recvCc, become the exempt faces"""
@@ -924,34 +918,18 @@ class SmoothEngine:
     def quality_constraint_records(self) -> list:
         """The pending records of the quality constraint (QualityConstraintRecordAll), one per iteration that ran, in ascending
         iteration; clears them."""
-        n = C.c_int64(0)
-        self._check(self._lib.smgpu_get_quality_constraint_records_all(self._h, None, 0, C.byref(n)))
-        if n.value == 0:
-            return []
-        buf = (_ffi.QualityConstraintRecordAll * n.value)()
-        self._check(self._lib.smgpu_get_quality_constraint_records_all(self._h, buf, n.value, C.byref(n)))
-        return [QualityConstraintRecordAll(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+        return self._drain(self._lib.smgpu_get_quality_constraint_records_all, _ffi.QualityConstraintRecordAll, QualityConstraintRecordAll)
 
     def quality_constraint_records_scaled(self) -> list:
         """quality_constraint_records() with the three fields of DESIGN.md 10.19 (QualityConstraintRecordScaled); the two getters
         drain the same pending list."""
-        n = C.c_int64(0)
-        self._check(self._lib.smgpu_get_quality_constraint_records_scaled(self._h, None, 0, C.byref(n)))
-        if n.value == 0:
-            return []
-        buf = (_ffi.QualityConstraintRecordScaled * n.value)()
-        self._check(self._lib.smgpu_get_quality_constraint_records_scaled(self._h, buf, n.value, C.byref(n)))
-        return [QualityConstraintRecordScaled(**{f: getattr(r, f) for f, _ in r._fields_}) for r in buf[:n.value]]
+        return self._drain(self._lib.smgpu_get_quality_constraint_records_scaled, _ffi.QualityConstraintRecordScaled, QualityConstraintRecordScaled)
 
     def quality_constraint_state_scaled(self) -> QualityConstraintStateScaled:
-        s = _ffi.QualityConstraintStateScaled()
-        self._check(self._lib.smgpu_get_quality_constraint_state_scaled(self._h, C.byref(s)))
-        return QualityConstraintStateScaled(on=bool(s.on), **{f: getattr(s, f) for f, _ in s._fields_ if f != "on"})
+        return self._read_state(self._lib.smgpu_get_quality_constraint_state_scaled, _ffi.QualityConstraintStateScaled, QualityConstraintStateScaled)
 
     def quality_constraint_state(self) -> QualityConstraintStateAll:
-        s = _ffi.QualityConstraintStateAll()
-        self._check(self._lib.smgpu_get_quality_constraint_state_all(self._h, C.byref(s)))
-        return QualityConstraintStateAll(on=bool(s.on), **{f: getattr(s, f) for f, _ in s._fields_ if f != "on"})
+        return self._read_state(self._lib.smgpu_get_quality_constraint_state_all, _ffi.QualityConstraintStateAll, QualityConstraintStateAll)
 
     def quality_field(self, name) -> np.ndarray:
         """Per-element quality field in polyMesh order: one of QUALITY_FIELDS (non-orthogonality in degrees, 0 on boundary faces)."""
@@ -1048,15 +1026,29 @@ class SmoothEngine:
                 pats.append((int(p.startFace), int(p.nFaces), int(p.neighbProcNo)))
         return (0 if rank is None else int(rank)), pats
 
+    @staticmethod
+    def _coupling(coupling):
+        """quality_coupling()'s answer as smgpu_quality_coupling; the struct keeps the three arrays it points to alive"""
+        rank, pats = coupling
+        c = _ffi.QualityCoupling(int(rank), len(pats))
+        c._keep = [np.array([p[i] for p in pats], np.int32) for i in range(3)]
+        c.patchStart, c.patchSize, c.neighbRank = (_p(a, _ffi.c_i32p) for a in c._keep)
+        return c
+
+    def _coupled_desc(self, full, coupling, sendT, recvT, sendCc, recvCc, sendVc=0, recvVc=0):
+        """the halo descriptor of a coupled quality constraint entry (full: with the volume buffers of 10.17); it keeps the
+        coupling it points to alive"""
+        c = self._coupling(coupling)
+        bufs = [a or None for a in (sendT, recvT, sendCc, recvCc)]
+        d = _ffi.QualityConstraintHaloDescFull(*bufs, C.pointer(c), sendVc or None, recvVc or None) if full else _ffi.QualityConstraintHaloDesc(*bufs, C.pointer(c))
+        d._keep = c
+        return d
+
     def quality_coupled_pack(self, coupling, sendCc) -> int:
         """smgpu_quality_coupled_pack: geometry of the current points, then the owner cell centre of every processor face (patch
         order) into the device buffer at address sendCc (3 doubles per face; 0 when there are none).  Returns the number of
         processor faces."""
-        rank, pats = coupling
-        st = np.array([p[0] for p in pats], np.int32)
-        sz = np.array([p[1] for p in pats], np.int32)
-        nb = np.array([p[2] for p in pats], np.int32)
-        c = _ffi.QualityCoupling(int(rank), len(pats), _p(st, _ffi.c_i32p), _p(sz, _ffi.c_i32p), _p(nb, _ffi.c_i32p))
+        c = self._coupling(coupling)
         n = C.c_int64()
         self._check(self._lib.smgpu_quality_coupled_pack(self._h, C.byref(c), C.c_void_p(sendCc or None), C.byref(n)))
         return n.value

@@ -328,7 +328,201 @@ class _RankState:
                               sendL=self.sendL.data_ptr(), recvL=rL)
 
 
-class DistributedSmoother:
+class _ConstraintDriver:
+    """The tangle constraint (include/smgpu.h smgpu_set_tangle_constraint_coupled) and the quality constraint
+    (smgpu_set_quality_constraint_coupled, 10.15; its further limits, 10.17, 10.18) on a decomposed mesh, written once for the two
+    smoothers below.  A smoother provides: _rank_states() (the _RankState of every rank this process drives: one, or all),
+    _move_marks() (exchange T), _pair_couplings(couplings) and _move_cc() (sendCc -> the neighbours' recvCc, and Vc with it),
+    _sum_counts(values) (a vector of counts summed over the ranks), _all_ranks(mine) (one entry per rank of the job from this
+    process's), _agree_on_error(err) (every rank raises when any has an error) and, where an error inside a pass has to wait for
+    the other ranks, _guarded(call)."""
+    _tangle_err = None            # what _guarded has caught on this rank, carried to the next reduction
+
+    def _guarded(self, call, *args):
+        """a call into an engine inside a pass; one process holds every rank: an error is everyone's at once"""
+        return call(*args)
+
+    def set_tangle_constraint(self, passes=2):
+        """From now on iterate() puts the points of every cell that its move turned bad back, on every rank that holds them:
+        behind every iter_end, up to `passes` marked passes (the marks of shared points travel like exchange F) and then the
+        full revert, under a verdict on the all-rank count (one all_reduce per pass).  Every rank calls it."""
+        torch = self.torch
+        if self.quality_passes is not None:
+            raise RuntimeError("set_tangle_constraint: the quality constraint is on, and it contains this one; clear_quality_constraint first")
+        self.tangle_passes = None
+        for st in self._rank_states():
+            st.sendT = torch.zeros(max(st.t.nSend, 1), dtype=torch.int32, device=self.device)
+            st.recvT = torch.zeros(max(st.t.nRecv, 1), dtype=torch.int32, device=self.device)
+            st.eng.set_tangle_constraint_coupled(st.sendT.data_ptr(), st.recvT.data_ptr(), passes)
+        self.tangle_passes = int(passes)
+
+    def clear_tangle_constraint(self):
+        self.tangle_passes = None
+        for st in self._rank_states():
+            st.eng.clear_tangle_constraint()
+
+    def _summed_state(self, reader, counts):
+        """the first rank's state with the fields `counts` summed over the ranks"""
+        ss = [getattr(st.eng, reader)() for st in self._rank_states()]
+        for name, v in zip(counts, self._sum_counts([sum(getattr(s, name) for s in ss) for name in counts])):
+            setattr(ss[0], name, v)
+        return ss[0]
+
+    def _records(self, reader, combine, per_rank):
+        everyone = self._all_ranks([getattr(st.eng, reader)() for st in self._rank_states()])
+        return everyone if per_rank else combine(everyone)
+
+    def tangle_state(self):
+        """TangleState of the decomposed mesh: nExemptCells summed over the ranks.  A collective."""
+        return self._summed_state("tangle_state", ("nExemptCells",))
+
+    def tangle_records(self, per_rank=False):
+        """The pending records, cleared by the read: those of the undecomposed mesh (combine_tangle_records), or with per_rank
+        one list per rank.  A collective: every rank calls it and gets the same answer."""
+        return self._records("tangle_records", combine_tangle_records, per_rank)
+
+    def _constraint_passes(self):
+        """the passes of the iteration iter_end has just closed, of whichever constraint is on.  Tangle constraint (10.13): per
+        pass one host read (the rank's count), one all_reduce of {count, failed} and, while cells are bad and the pass is not
+        the last, exchange T (the host's exchange under every transport: no kernel stores marks into a peer).  Quality constraint
+        (10.15): in front of the count the owner cell centres of the processor faces move like the coupled report's slices, so a
+        pass waits for its engine twice.  A rank on which a call of a pass fails keeps the error (_guarded), goes on answering the
+        collectives without touching its engine, and reports failed = 1 in the next reduction; every rank then raises through
+        _agree_on_error.  The host knows the verdict itself, so a failed rank leaves the loop when the others do."""
+        if self.tangle_passes is not None:
+            name, passes, faces = "tangle", self.tangle_passes, False
+        elif self.quality_passes is not None:
+            name, passes, faces = "quality", self.quality_passes, True
+        else:
+            return
+        engines = [st.eng for st in self._rank_states()]
+        for k in range(passes + 1):
+            if faces:
+                for eng in engines:
+                    self._guarded(eng.quality_constraint_pass_begin)
+                self._move_cc()
+                nb = sum([self._guarded(eng.quality_constraint_pass_faces) or 0 for eng in engines])
+            else:
+                nb = sum([self._guarded(eng.tangle_pass_begin) or 0 for eng in engines])
+            total, failed = self._sum_counts([nb, 0 if self._tangle_err is None else 1])
+            if failed:
+                err, self._tangle_err = self._tangle_err, None
+                self._agree_on_error(err if err is not None else RuntimeError(f"another rank failed inside a pass of the {name} constraint (see its message)"))
+            if total > 0 and k < passes:
+                self._move_marks()
+            for eng in engines:   # (a failure here is carried to the next reduction or agreement point)
+                self._guarded(eng.quality_constraint_pass_end if faces else eng.tangle_pass_end, total)
+            if total == 0 or k == passes:
+                return
+
+    def set_quality_constraint_limits(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
+                                      minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None):
+        """set_quality_constraint with the six further limits of engine.set_quality_constraint (None: off), on the global mesh
+        (smgpu_set_quality_constraint_limits_coupled, DESIGN.md 10.17): a processor face takes the internal branch of every face
+        criterion with the neighbour rank's cell centre and cell volume, a cell's determinant runs over its internal and its
+        processor faces.  With minVolRatio on the owner cells' volumes travel with the cell centres.  Every rank calls it, with
+        the same limits.  (The scaling passes of DESIGN.md 10.19 are a serial engine's: this entry keeps its signature and does
+        not know their keywords; set_quality_constraint and set_quality_constraint_limits_all take and refuse them.)"""
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes,
+                                        dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist,
+                                             minFaceWeight=minFaceWeight, minVolRatio=minVolRatio, minDeterminant=minDeterminant))
+
+    def set_quality_constraint_limits_all(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
+                                          minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
+                                          maxConcave=None, minFlatness=None, minVol=None, minArea=None, scalePasses=0, errorReduction=0.75, nSmoothScale=4):
+        """set_quality_constraint_limits with the last four limits of engine.set_quality_constraint behind the six (None: off;
+        smgpu_set_quality_constraint_limits_all_coupled, DESIGN.md 10.18): the keyword arguments that read_mesh_quality_dict
+        returns.  The four are local to a rank: a processor face is judged on the rank's own vertex order, and nothing more
+        travels.  With all four None the engine is called as set_quality_constraint_limits calls it.  Every rank calls it, with
+        the same limits.  scalePasses > 0 is refused (DESIGN.md 10.19: a serial engine's)."""
+        _refuse_scaling(scalePasses, errorReduction, nSmoothScale)
+        more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
+                    minVolRatio=minVolRatio, minDeterminant=minDeterminant)
+        last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
+        if any(v is not None for v in last.values()):
+            more.update(last)
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more)
+
+    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
+        """From now on iterate() also keeps face non-orthogonality and skewness under the limits (engine.set_quality_constraint's
+        parameters), on the global mesh: a processor face is judged as the internal face it is, with the neighbour rank's cell
+        centre, which travels once per pass like the coupled report's; marks and verdict as set_tangle_constraint.  Every rank
+        calls it (a collective: the exempt faces need one exchange).  more: the limits of engine.set_quality_constraint that a
+        decomposed mesh does not take (DESIGN.md 10.16): one that is on is a ValueError, and so is scalePasses > 0 (10.19)."""
+        _refuse_scaling(**{k: more.pop(k) for k in ("scalePasses", "errorReduction", "nSmoothScale") if k in more})
+        _refuse_more_limits(more)
+        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, None)
+
+    def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more):
+        """the body of set_quality_constraint (more = None: smgpu_set_quality_constraint_coupled) and of
+        set_quality_constraint_limits (more: the six limits by name, smgpu_set_quality_constraint_limits_coupled) and _limits_all
+        (more: with the four of 10.18 where one is given, smgpu_set_quality_constraint_limits_all_coupled): the buffers of every
+        rank, then the two-step enable"""
+        torch = self.torch
+        if self.tangle_passes is not None:
+            raise RuntimeError("set_quality_constraint: the tangle constraint is on, and this constraint contains it; clear_tangle_constraint first")
+        states = self._rank_states()
+        couplings = [st.eng.quality_coupling(st.t.rank) for st in states]
+        self._pair_couplings(couplings)
+        for st, c in zip(states, couplings):
+            n = sum(p[1] for p in c[1])
+            st.qcCoupling = c
+            st.sendT = torch.zeros(max(st.t.nSend, 1), dtype=torch.int32, device=self.device)
+            st.recvT = torch.zeros(max(st.t.nRecv, 1), dtype=torch.int32, device=self.device)
+            st.sendCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
+            st.recvCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
+            st.sendVc = st.recvVc = None
+            if _wants_volumes(more):
+                st.sendVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
+                st.recvVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
+        self.quality_passes = None
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)         # the buffers are zeroed before the engines' streams write them
+        self._enable_engines((maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes), more)
+        self.quality_passes = int(passes)
+
+    def _enable_engines(self, limits, more):
+        """the two-step enable: every engine's call, which leaves sendCc (and sendVc) packed at the current points; their move;
+        every engine's exempt faces.  Behind each step the ranks agree on an error"""
+        torch, err = self.torch, None
+        try:
+            for st in self._rank_states():
+                bufs = [t.data_ptr() for t in (st.sendT, st.recvT, st.sendCc, st.recvCc)]
+                if more is None:
+                    st.eng.set_quality_constraint_coupled(st.qcCoupling, *bufs, *limits)
+                else:
+                    st.eng.set_quality_constraint_limits_coupled(st.qcCoupling, *bufs, 0 if st.sendVc is None else st.sendVc.data_ptr(),
+                                                                 0 if st.recvVc is None else st.recvVc.data_ptr(), *limits, **more)
+        except Exception as ex:  # noqa: BLE001 -- re-raised below, on every rank
+            err = ex
+        self._agree_on_error(err)
+        self._move_cc()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        try:
+            for st in self._rank_states():
+                st.eng.quality_constraint_coupled_exempt()
+        except Exception as ex:  # noqa: BLE001
+            err = ex
+        self._agree_on_error(err)
+
+    def clear_quality_constraint(self):
+        self.quality_passes = None
+        for st in self._rank_states():
+            st.eng.clear_quality_constraint()
+
+    def quality_constraint_state(self):
+        """QualityConstraintState of the decomposed mesh: nExemptCells, nExemptFaces and the two further exempt counts summed over
+        the ranks (a processor face counts on one side).  A collective."""
+        return self._summed_state("quality_constraint_state", ("nExemptCells", "nExemptFaces", "nExemptDeterminantCells", "nExemptVolumeCells"))
+
+    def quality_constraint_records(self, per_rank=False):
+        """The pending records, cleared by the read: those of the undecomposed mesh (combine_quality_constraint_records), or with
+        per_rank one list per rank.  A collective: every rank calls it and gets the same answer."""
+        return self._records("quality_constraint_records", combine_quality_constraint_records, per_rank)
+
+
+class DistributedSmoother(_ConstraintDriver):
     """The reference's loop (SM.C:2257-2437) on this rank's sub-domain, in step with all other ranks."""
 
     def __init__(self, sub, device=0, engine_factory=None, torch_device=None, probe_slots=0, overlap=False):
@@ -386,7 +580,6 @@ class DistributedSmoother:
         self.direct = self._open_direct(engine_factory is None)
         self.tangle_passes = None     # set_tangle_constraint: the passes behind every iter_end
         self.quality_passes = None    # set_quality_constraint: likewise (the two constraints exclude each other)
-        self._tangle_err = None
 
     def _open_push(self):
         """exchange the IPC handles and slot counts, map the peers' buffers, describe them to the engine"""
@@ -784,93 +977,40 @@ class DistributedSmoother:
     def get_points(self):
         return self.engine.get_points()
 
-    # -- the tangle constraint on the decomposed mesh (include/smgpu.h smgpu_set_tangle_constraint_coupled) --
-    def set_tangle_constraint(self, passes=2):
-        """From now on iterate() puts the points of every cell that its move turned bad back, on every rank that holds them:
-        behind every iter_end, up to `passes` marked passes (the marks of shared points travel like exchange F) and then the
-        full revert, under a verdict on the all-rank count (one all_reduce per pass).  Every rank calls it."""
-        torch, st = self.torch, self.state
-        if self.quality_passes is not None:
-            raise RuntimeError("set_tangle_constraint: the quality constraint is on, and it contains this one; clear_quality_constraint first")
-        st.sendT = torch.zeros(max(self.tables.nSend, 1), dtype=torch.int32, device=self.device)
-        st.recvT = torch.zeros(max(self.tables.nRecv, 1), dtype=torch.int32, device=self.device)
-        self.tangle_passes = None
-        self.engine.set_tangle_constraint_coupled(st.sendT.data_ptr(), st.recvT.data_ptr(), passes)
-        self.tangle_passes = int(passes)
+    # -- the hooks of _ConstraintDriver: this rank's engine, the other ranks through the process group --
+    def _rank_states(self):
+        return [self.state]
 
-    def clear_tangle_constraint(self):
-        self.tangle_passes = None
-        self.engine.clear_tangle_constraint()
-
-    def tangle_state(self):
-        """TangleState of the decomposed mesh: nExemptCells summed over the ranks.  A collective."""
-        s = self.engine.tangle_state()
-        t = self.torch.tensor([s.nExemptCells], dtype=self.torch.int64, device="cpu" if self._staged() else self.device)
-        if self.world > 1:
-            self.dist.all_reduce(t)
-        s.nExemptCells = int(t.item())
-        return s
-
-    def tangle_records(self, per_rank=False):
-        """The pending records, cleared by the read: those of the undecomposed mesh (combine_tangle_records), or with per_rank
-        one list per rank.  A collective: every rank calls it and gets the same answer."""
-        mine = self.engine.tangle_records()
-        everyone = [None] * self.world
-        if self.world > 1:
-            self.dist.all_gather_object(everyone, mine)
-        else:
-            everyone = [mine]
-        return everyone if per_rank else combine_tangle_records(everyone)
-
-    def _constraint_passes(self):
-        """the passes of the iteration iter_end has just closed, of whichever constraint is on.  Tangle constraint (10.13): per
-        pass one host read (the rank's count), one all_reduce of {count, failed} and, while cells are bad and the pass is not
-        the last, exchange T (the host's exchange under every transport: no kernel stores marks into a peer).  Quality constraint
-        (10.15): in front of the count the owner cell centres of the processor faces move like the coupled report's slices, so a
-        pass waits for its engine twice.  A rank on which a call of a pass fails keeps the error, goes on answering the
-        collectives without touching its engine, and reports failed = 1 in the next reduction; every rank then raises through
-        _agree_on_error.  The host knows the verdict itself, so a failed rank leaves the loop when the others do."""
-        if self.tangle_passes is not None:
-            name, passes, faces = "tangle", self.tangle_passes, False
-        elif self.quality_passes is not None:
-            name, passes, faces = "quality", self.quality_passes, True
-        else:
-            return
-        torch, st, eng = self.torch, self.state, self.engine
-        dev = "cpu" if (self._staged() or self.device.type == "cpu") else self.device
-
-        def guarded(call):
-            if self._tangle_err is None:
-                try:
-                    return call()
-                except Exception as ex:  # noqa: BLE001 -- re-raised below, on every rank
-                    self._tangle_err = ex
-            return 0
-
-        for k in range(passes + 1):
-            if faces:
-                guarded(eng.quality_constraint_pass_begin)
-                self._move_cc()
-                nb = guarded(eng.quality_constraint_pass_faces)
-            else:
-                nb = guarded(eng.tangle_pass_begin)
-            v = torch.tensor([nb or 0, 0 if self._tangle_err is None else 1], dtype=torch.int64, device=dev)
-            if self.world > 1:
-                self.dist.all_reduce(v)
-            total, failed = (int(x) for x in v.tolist())
-            if failed:
-                err, self._tangle_err = self._tangle_err, None
-                self._agree_on_error(err if err is not None else RuntimeError(f"another rank failed inside a pass of the {name} constraint (see its message)"))
-            if total > 0 and k < passes:
-                self._a2a(st.recvT, st.sendT, host=True)
+    def _guarded(self, call, *args):
+        """a call into this rank's engine inside a pass: left out while the rank carries an error; a failure is kept for the next
+        reduction, where every rank learns of it"""
+        if self._tangle_err is None:
             try:
-                (eng.quality_constraint_pass_end if faces else eng.tangle_pass_end)(total)
-            except Exception as ex:  # noqa: BLE001 -- carried to the next reduction or agreement point
+                return call(*args)
+            except Exception as ex:  # noqa: BLE001 -- re-raised through _agree_on_error, on every rank
                 self._tangle_err = ex
-            if total == 0 or k == passes:
-                return
+        return 0
 
-    # -- the quality constraint on the decomposed mesh (include/smgpu.h smgpu_set_quality_constraint_coupled, DESIGN.md 10.15) --
+    def _sum_counts(self, values):
+        v = self.torch.tensor(values, dtype=self.torch.int64, device="cpu" if self._staged() else self.device)
+        if self.world > 1:
+            self.dist.all_reduce(v)
+        return [int(x) for x in v.tolist()]
+
+    def _all_ranks(self, mine):
+        if self.world <= 1:
+            return mine
+        everyone = [None] * self.world
+        self.dist.all_gather_object(everyone, mine[0])
+        return everyone
+
+    def _move_marks(self):
+        self._a2a(self.state.recvT, self.state.sendT, host=True)
+
+    def _pair_couplings(self, couplings):
+        if self.world <= 1 and couplings[0][1]:
+            raise RuntimeError("mesh quality: a single rank with processor patches")
+
     def _move_cc(self):
         """sendCc -> the neighbours' recvCc: the paired-patch exchange of the coupled report (a collective: every rank takes part,
         with or without processor patches)"""
@@ -879,115 +1019,6 @@ class DistributedSmoother:
             st.recvCc.copy_(self._quality_swap(st.qcCoupling[1], st.sendCc, 3))
             if getattr(st, "sendVc", None) is not None:         # (10.17: the owner cells' volumes ride the same move)
                 st.recvVc.copy_(self._quality_swap(st.qcCoupling[1], st.sendVc, 1))
-
-    def set_quality_constraint_limits(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
-                                      minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None):
-        """set_quality_constraint with the six further limits of engine.set_quality_constraint (None: off), on the global mesh
-        (smgpu_set_quality_constraint_limits_coupled, DESIGN.md 10.17): a processor face takes the internal branch of every face
-        criterion with the neighbour rank's cell centre and cell volume, a cell's determinant runs over its internal and its
-        processor faces.  With minVolRatio on the owner cells' volumes travel with the cell centres.  Every rank calls it, with
-        the same limits.  (The scaling passes of DESIGN.md 10.19 are a serial engine's: this entry keeps its signature and does
-        not know their keywords; set_quality_constraint and set_quality_constraint_limits_all take and refuse them.)"""
-        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes,
-                                        dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist,
-                                             minFaceWeight=minFaceWeight, minVolRatio=minVolRatio, minDeterminant=minDeterminant))
-
-    def set_quality_constraint_limits_all(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
-                                          minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
-                                          maxConcave=None, minFlatness=None, minVol=None, minArea=None, scalePasses=0, errorReduction=0.75, nSmoothScale=4):
-        """set_quality_constraint_limits with the last four limits of engine.set_quality_constraint behind the six (None: off;
-        smgpu_set_quality_constraint_limits_all_coupled, DESIGN.md 10.18): the keyword arguments that read_mesh_quality_dict
-        returns.  The four are local to a rank: a processor face is judged on the rank's own vertex order, and nothing more
-        travels.  With all four None the engine is called as set_quality_constraint_limits calls it.  Every rank calls it, with
-        the same limits.  scalePasses > 0 is refused (DESIGN.md 10.19: a serial engine's)."""
-        _refuse_scaling(scalePasses, errorReduction, nSmoothScale)
-        more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
-                    minVolRatio=minVolRatio, minDeterminant=minDeterminant)
-        last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
-        if any(v is not None for v in last.values()):
-            more.update(last)
-        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more)
-
-    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
-        """From now on iterate() also keeps face non-orthogonality and skewness under the limits (engine.set_quality_constraint's
-        parameters), on the global mesh: a processor face is judged as the internal face it is, with the neighbour rank's cell
-        centre, which travels once per pass like the coupled report's; marks and verdict as set_tangle_constraint.  Every rank
-        calls it (a collective: the exempt faces need one exchange).  more: the limits of engine.set_quality_constraint that a
-        decomposed mesh does not take (DESIGN.md 10.16): one that is on is a ValueError, and so is scalePasses > 0 (10.19)."""
-        _refuse_scaling(**{k: more.pop(k) for k in ("scalePasses", "errorReduction", "nSmoothScale") if k in more})
-        _refuse_more_limits(more)
-        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, None)
-
-    def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more):
-        """the body of set_quality_constraint (more = None: smgpu_set_quality_constraint_coupled) and of
-        set_quality_constraint_limits (more: the six limits by name, smgpu_set_quality_constraint_limits_coupled) and _limits_all
-        (more: with the four of 10.18 where one is given, smgpu_set_quality_constraint_limits_all_coupled)"""
-        torch, st, eng = self.torch, self.state, self.engine
-        if self.tangle_passes is not None:
-            raise RuntimeError("set_quality_constraint: the tangle constraint is on, and this constraint contains it; clear_tangle_constraint first")
-        coupling = eng.quality_coupling(self.rank)
-        if self.world <= 1 and coupling[1]:
-            raise RuntimeError("mesh quality: a single rank with processor patches")
-        n = sum(p[1] for p in coupling[1])
-        st.qcCoupling = coupling
-        st.sendT = torch.zeros(max(self.tables.nSend, 1), dtype=torch.int32, device=self.device)
-        st.recvT = torch.zeros(max(self.tables.nRecv, 1), dtype=torch.int32, device=self.device)
-        st.sendCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
-        st.recvCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
-        st.sendVc = st.recvVc = None
-        if _wants_volumes(more):
-            st.sendVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
-            st.recvVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
-        self.quality_passes = None
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)         # the buffers are zeroed before the engine's stream writes them
-        err = None
-        try:
-            if more is None:
-                eng.set_quality_constraint_coupled(coupling, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
-                                                   maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes)
-            else:
-                eng.set_quality_constraint_limits_coupled(coupling, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
-                                                          0 if st.sendVc is None else st.sendVc.data_ptr(), 0 if st.recvVc is None else st.recvVc.data_ptr(),
-                                                          maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, **more)
-        except Exception as ex:  # noqa: BLE001 -- re-raised below, on every rank
-            err = ex
-        self._agree_on_error(err)
-        self._move_cc()
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
-        try:
-            eng.quality_constraint_coupled_exempt()
-        except Exception as ex:  # noqa: BLE001
-            err = ex
-        self._agree_on_error(err)
-        self.quality_passes = int(passes)
-
-    def clear_quality_constraint(self):
-        self.quality_passes = None
-        self.engine.clear_quality_constraint()
-
-    def quality_constraint_state(self):
-        """QualityConstraintState of the decomposed mesh: nExemptCells and nExemptFaces summed over the ranks (a processor face
-        counts on one side).  A collective."""
-        s = self.engine.quality_constraint_state()
-        t = self.torch.tensor([s.nExemptCells, s.nExemptFaces, s.nExemptDeterminantCells, s.nExemptVolumeCells], dtype=self.torch.int64,
-                              device="cpu" if self._staged() else self.device)
-        if self.world > 1:
-            self.dist.all_reduce(t)
-        s.nExemptCells, s.nExemptFaces, s.nExemptDeterminantCells, s.nExemptVolumeCells = (int(x) for x in t.tolist())
-        return s
-
-    def quality_constraint_records(self, per_rank=False):
-        """The pending records, cleared by the read: those of the undecomposed mesh (combine_quality_constraint_records), or with
-        per_rank one list per rank.  A collective: every rank calls it and gets the same answer."""
-        mine = self.engine.quality_constraint_records()
-        everyone = [None] * self.world
-        if self.world > 1:
-            self.dist.all_gather_object(everyone, mine)
-        else:
-            everyone = [mine]
-        return everyone if per_rank else combine_quality_constraint_records(everyone)
 
     def _quality_exchange(self, volumes=False):
         """pack, then every processor patch's owner cell centres to the neighbour and theirs back (one all_to_all_single, staged
@@ -1108,7 +1139,7 @@ class DistributedSmoother:
         return self._quality_field("motion", name)
 
 
-class LocalMultiSmoother:
+class LocalMultiSmoother(_ConstraintDriver):
     """All sub-domains in ONE process on ONE device (engines side by side), the exchange done by
     device-side tensor indexing instead of RCCL.  Exercises every device-side piece of the multi-rank
     path (pack / combine / or kernels, slot tables) on a single GPU."""
@@ -1223,56 +1254,27 @@ class LocalMultiSmoother:
     def get_points(self):
         return [st.eng.get_points() for st in self.states]
 
-    # -- the tangle constraint on the decomposed mesh (include/smgpu.h smgpu_set_tangle_constraint_coupled) --
-    def set_tangle_constraint(self, passes=2):
-        """as DistributedSmoother.set_tangle_constraint; the marks of shared points move by the device-side copies of the exchanges"""
-        torch = self.torch
-        if self.quality_passes is not None:
-            raise RuntimeError("set_tangle_constraint: the quality constraint is on, and it contains this one; clear_quality_constraint first")
-        self.tangle_passes = None
-        for st in self.states:
-            st.sendT = torch.zeros(max(st.t.nSend, 1), dtype=torch.int32, device=self.device)
-            st.recvT = torch.zeros(max(st.t.nRecv, 1), dtype=torch.int32, device=self.device)
-            st.eng.set_tangle_constraint_coupled(st.sendT.data_ptr(), st.recvT.data_ptr(), passes)
-        self.tangle_passes = int(passes)
+    # -- the hooks of _ConstraintDriver: every rank is here, what travels moves by device-side copies --
+    def _rank_states(self):
+        return self.states
 
-    def clear_tangle_constraint(self):
-        self.tangle_passes = None
-        for st in self.states:
-            st.eng.clear_tangle_constraint()
+    def _sum_counts(self, values):
+        return values
 
-    def tangle_state(self):
-        """TangleState of the decomposed mesh: nExemptCells summed over the ranks"""
-        ss = [st.eng.tangle_state() for st in self.states]
-        ss[0].nExemptCells = sum(s.nExemptCells for s in ss)
-        return ss[0]
+    def _all_ranks(self, mine):
+        return mine
 
-    def tangle_records(self, per_rank=False):
-        """The pending records, cleared by the read: those of the undecomposed mesh, or with per_rank one list per rank"""
-        everyone = [st.eng.tangle_records() for st in self.states]
-        return everyone if per_rank else combine_tangle_records(everyone)
+    def _agree_on_error(self, err=None):
+        if err is not None:
+            raise err
 
-    def _constraint_passes(self):
-        """the passes of the iteration iter_end has just closed on every engine, of whichever constraint is on: the verdict on the
-        summed count; under the quality constraint the cell centres of the processor faces move in front of the count"""
-        faces = self.quality_passes is not None
-        passes = self.quality_passes if faces else self.tangle_passes
-        if passes is None:
-            return
-        for k in range(passes + 1):
-            if faces:
-                for st in self.states:
-                    st.eng.quality_constraint_pass_begin()
-                self._move_cc()
-                total = sum([st.eng.quality_constraint_pass_faces() for st in self.states])
-            else:
-                total = sum([st.eng.tangle_pass_begin() for st in self.states])
-            if total > 0 and k < passes:
-                self._exchange("T")
-            if all([(st.eng.quality_constraint_pass_end if faces else st.eng.tangle_pass_end)(total) for st in self.states]):
-                return
+    def _move_marks(self):
+        self._exchange("T")
 
-    # -- the quality constraint on the decomposed mesh (include/smgpu.h smgpu_set_quality_constraint_coupled, DESIGN.md 10.15) --
+    def _pair_couplings(self, couplings):
+        from .quality import paired_offsets
+        self.ccCopies = paired_offsets(couplings)
+
     def _move_cc(self):
         """every engine's sendCc -> its neighbours' recvCc by device-side copies, as the coupled report's local_exchange; the
         buffers are the constraint's own, not the report's"""
@@ -1281,90 +1283,13 @@ class LocalMultiSmoother:
             if getattr(self.states[i], "sendVc", None) is not None:         # (10.17: the owner cells' volumes ride the same move)
                 self.states[i].recvVc[off:off + size].copy_(self.states[j].sendVc[ooff:ooff + size])
 
-    def set_quality_constraint_limits(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
-                                      minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None):
-        """as DistributedSmoother.set_quality_constraint_limits; cell centres, volumes and marks move by device-side copies"""
-        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes,
-                                        dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist,
-                                             minFaceWeight=minFaceWeight, minVolRatio=minVolRatio, minDeterminant=minDeterminant))
-
-    def set_quality_constraint_limits_all(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, minTetQuality=None,
-                                          minTwist=None, minTriangleTwist=None, minFaceWeight=None, minVolRatio=None, minDeterminant=None,
-                                          maxConcave=None, minFlatness=None, minVol=None, minArea=None, scalePasses=0, errorReduction=0.75, nSmoothScale=4):
-        """as DistributedSmoother.set_quality_constraint_limits_all; nothing more moves for the four"""
-        _refuse_scaling(scalePasses, errorReduction, nSmoothScale)
-        more = dict(minTetQuality=minTetQuality, minTwist=minTwist, minTriangleTwist=minTriangleTwist, minFaceWeight=minFaceWeight,
-                    minVolRatio=minVolRatio, minDeterminant=minDeterminant)
-        last = dict(maxConcave=maxConcave, minFlatness=minFlatness, minVol=minVol, minArea=minArea)
-        if any(v is not None for v in last.values()):
-            more.update(last)
-        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more)
-
-    def set_quality_constraint(self, maxNonOrtho=65.0, maxInternalSkewness=4.0, maxBoundarySkewness=20.0, passes=2, **more):
-        """as DistributedSmoother.set_quality_constraint; cell centres and marks move by device-side copies"""
-        _refuse_scaling(**{k: more.pop(k) for k in ("scalePasses", "errorReduction", "nSmoothScale") if k in more})
-        _refuse_more_limits(more)
-        self._enable_quality_constraint(maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, None)
-
-    def _enable_quality_constraint(self, maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes, more):
-        """as DistributedSmoother._enable_quality_constraint"""
-        from .quality import paired_offsets
-        torch = self.torch
-        if self.tangle_passes is not None:
-            raise RuntimeError("set_quality_constraint: the tangle constraint is on, and this constraint contains it; clear_tangle_constraint first")
-        self.quality_passes = None
-        couplings = [st.eng.quality_coupling(r) for r, st in enumerate(self.states)]
-        self.ccCopies = paired_offsets(couplings)
-        for st, c in zip(self.states, couplings):
-            n = sum(p[1] for p in c[1])
-            st.sendT = torch.zeros(max(st.t.nSend, 1), dtype=torch.int32, device=self.device)
-            st.recvT = torch.zeros(max(st.t.nRecv, 1), dtype=torch.int32, device=self.device)
-            st.sendCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
-            st.recvCc = torch.zeros((max(n, 1), 3), dtype=torch.float64, device=self.device)
-            st.sendVc = st.recvVc = None
-            if _wants_volumes(more):
-                st.sendVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
-                st.recvVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)         # the buffers are zeroed before the engines' streams write them
+    def _enable_engines(self, limits, more):
+        """a failing enable leaves the constraint off on every engine"""
         try:
-            for st, c in zip(self.states, couplings):
-                if more is None:
-                    st.eng.set_quality_constraint_coupled(c, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
-                                                          maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes)
-                else:
-                    st.eng.set_quality_constraint_limits_coupled(c, st.sendT.data_ptr(), st.recvT.data_ptr(), st.sendCc.data_ptr(), st.recvCc.data_ptr(),
-                                                                 0 if st.sendVc is None else st.sendVc.data_ptr(),
-                                                                 0 if st.recvVc is None else st.recvVc.data_ptr(), maxNonOrtho, maxInternalSkewness,
-                                                                 maxBoundarySkewness, passes, **more)
-            self._move_cc()
-            if self.device.type == "cuda":
-                torch.cuda.synchronize(self.device)
-            for st in self.states:
-                st.eng.quality_constraint_coupled_exempt()
+            super()._enable_engines(limits, more)
         except Exception:
             self.clear_quality_constraint()
             raise
-        self.quality_passes = int(passes)
-
-    def clear_quality_constraint(self):
-        self.quality_passes = None
-        for st in self.states:
-            st.eng.clear_quality_constraint()
-
-    def quality_constraint_state(self):
-        """QualityConstraintState of the decomposed mesh: nExemptCells and nExemptFaces summed over the ranks"""
-        ss = [st.eng.quality_constraint_state() for st in self.states]
-        ss[0].nExemptCells = sum(s.nExemptCells for s in ss)
-        ss[0].nExemptFaces = sum(s.nExemptFaces for s in ss)
-        ss[0].nExemptDeterminantCells = sum(s.nExemptDeterminantCells for s in ss)
-        ss[0].nExemptVolumeCells = sum(s.nExemptVolumeCells for s in ss)
-        return ss[0]
-
-    def quality_constraint_records(self, per_rank=False):
-        """The pending records, cleared by the read: those of the undecomposed mesh, or with per_rank one list per rank"""
-        everyone = [st.eng.quality_constraint_records() for st in self.states]
-        return everyone if per_rank else combine_quality_constraint_records(everyone)
 
     # The reports of the decomposed mesh at the current points (smoothmesh_amd/quality.py, DESIGN.md 10.4, 10.5, 10.8, 10.9): the cell
     # centres (and volumes) of the processor faces move between the engines' buffers by device-side copies.  Ids are global where

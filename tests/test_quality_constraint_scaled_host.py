@@ -170,3 +170,37 @@ def test_decomposed_smoothers_refuse_the_scaling_keywords_by_name(cls):
             call(scalePasses=0, errorReduction=0.5, nSmoothScale=1)
     with pytest.raises(TypeError, match="scalePass"):
         smoother.set_quality_constraint(scalePass=2)
+
+
+def test_every_tiered_struct_is_the_head_of_the_next():
+    """The library widens a setter's argument over the head of the widest limits and answers a getter with the head of the widest
+    record or state (smoothmesh_amd/csrc/quality_state.hpp asserts the C layouts): in the ctypes mirrors, too, every field of a
+    narrower struct has its name, type and offset in the wider one, and the wider one's own fields start where the narrower ends"""
+    from smoothmesh_amd import _ffi
+    chains = (("QualityConstraintParams", "QualityConstraintLimits", "QualityConstraintLimitsAll"),
+              ("QualityConstraintRecord", "QualityConstraintRecordFull", "QualityConstraintRecordAll", "QualityConstraintRecordScaled"),
+              ("QualityConstraintState", "QualityConstraintStateFull", "QualityConstraintStateAll", "QualityConstraintStateScaled"),
+              ("QualityConstraintHaloDesc", "QualityConstraintHaloDescFull"))
+    for chain in chains:
+        for narrow, wide in zip(chain, chain[1:]):
+            n, w = getattr(_ffi, narrow), getattr(_ffi, wide)
+            assert len(w._fields_) > len(n._fields_) and w._fields_[:len(n._fields_)] == n._fields_, (narrow, wide)
+            for name, _ in n._fields_:
+                assert (getattr(w, name).offset, getattr(w, name).size) == (getattr(n, name).offset, getattr(n, name).size), (narrow, wide, name)
+            assert getattr(w, w._fields_[len(n._fields_)][0]).offset == C.sizeof(n), (narrow, wide)
+
+
+def test_the_constraint_methods_of_the_two_smoothers_have_one_owner():
+    """every public method of the tangle and the quality constraint is written once, on the base the two smoothers share: the same
+    function and so the same signature, and neither class defines one of its own.  No device, no process group"""
+    import inspect
+    from smoothmesh_amd.halo import DistributedSmoother, LocalMultiSmoother
+    methods = ("set_tangle_constraint", "clear_tangle_constraint", "tangle_state", "tangle_records", "set_quality_constraint",
+               "set_quality_constraint_limits", "set_quality_constraint_limits_all", "clear_quality_constraint", "quality_constraint_state",
+               "quality_constraint_records")
+    shared = [b for b in DistributedSmoother.__mro__[1:] if b in LocalMultiSmoother.__mro__[1:] and b is not object]
+    assert shared, "no shared base"
+    for m in methods:
+        assert inspect.signature(getattr(DistributedSmoother, m)) == inspect.signature(getattr(LocalMultiSmoother, m)), m
+        assert m not in vars(DistributedSmoother) and m not in vars(LocalMultiSmoother), m
+        assert getattr(DistributedSmoother, m) is getattr(LocalMultiSmoother, m) and any(m in vars(b) for b in shared), m
