@@ -712,6 +712,66 @@ int smgpu_set_quality_constraint_scaling(smgpu_handle* h, const smgpu_quality_co
 int smgpu_get_quality_constraint_records_scaled(smgpu_handle* h, smgpu_quality_constraint_record_scaled* out, int64_t cap, int64_t* n);
 int smgpu_get_quality_constraint_state_scaled(smgpu_handle* h, smgpu_quality_constraint_state_scaled* out);
 
+/* ---- scaling passes on a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.20) ------------------------------------
+ * 10.19 read on the GLOBAL mesh, for an engine whose halo is configured and whose coupled quality constraint is on (through any of
+ * its three coupled entries).  Notation of 10.19 (x, L, s_p, S, P, r, n) and 10.15.  Off (the state after every
+ * smgpu_set_quality_constraint*_coupled): every launch, record and bit of a decomposed run is what it is without this section.
+ * WHAT CROSSES THE RANKS.
+ *   1. Marks and verdict travel exactly as in 10.15; a pass runs for k = 0 .. S+P.  The host knows k: a marked pass scales
+ *      (k < S), reverts (S <= k < S+P) or is the full revert (k == S+P).
+ *   2. Mark -> scale.  Behind the OR of the shared points' marks every rank applies s <- s r, s <- 0, or s <- 0 for all, to its own
+ *      copy of the scale field.  The combined marks and r are the same on every sharer: copies of a shared point's scale stay
+ *      bit-identical (an invariant).
+ *   3. The sweep s_p <- min(s_p, 0.5 s_p + 0.5 (sum_q s_q) / deg_p) runs over the neighbours of p in the WHOLE mesh.
+ *      Shared points are named by (global id, component) as the halo's tables name them.  COUNTED EDGE: a row entry (p, q) of rank
+ *      R is counted iff R is the lowest rank whose sub-domain holds the edge pq; an entry with an unshared end is always counted.
+ *      PARTIAL SUM: part_R(p), the left fold from 0.0 in rank R's row order over the counted entries of p's row (0.0 when none is).
+ *      TOTAL: the left fold from 0.0 of part_R(p) over the sharers of p in ascending rank (the order of combOffsets / combSlots,
+ *      -1: this rank).  DEGREE: deg_p, the counted entries of p over all ranks, formed once by the caller.  One correctly rounded
+ *      division, no contraction, Jacobi between two fields, n sweeps behind every marked pass, none behind the full revert.  An
+ *      unshared point is 10.19's.  One double per send slot travels per sweep: exchange S, laid out like exchange T.
+ *   4. The accepted points are 10.19's item 3 on every rank.
+ * RECORDS.  smgpu_quality_constraint_record_scaled per rank and iteration: passes, fullRevert and nScalePasses are global values;
+ * nPointsReverted and nPointsScaled the rank's own, a shared point counting on its master only (10.13); minScale the rank's own
+ * minimum.  Combined: sums, and min for minScale.  The state carries the three parameters as in the serial form.
+ * EQUIVALENCES.  S = 0: 10.15 / 10.17 / 10.18 by bits and launches.  A single sub-domain without processor patches: the serial
+ * scaled run (10.19), bit for bit.  S > 0, r = 0, n = 0: the accepted points of the coupled constraint with passes = S + P.
+ * Against the undecomposed mesh the row orders and the fold over the ranks differ: the serial run to rounding, not to the bit.
+ * A CLEAN ITERATION (summed count 0 at k = 0) adds no launch, wait, exchange or byte to 10.15's.
+ *
+ * smgpu_set_quality_constraint_scaling_coupled(h, p, c): p as 10.19's (NULL or scalePasses = 0: off, frees L and the two scale
+ * fields; c is then not read).  c: the caller's tables, copied during the call, and its exchange buffers, used until scaling is
+ * switched off.  Clearing or re-enabling the constraint switches scaling off; smgpu_halo_configure stays refused while the
+ * constraint is on.
+ * THE CALLS OF A PASS while scaling is on, on every rank (a call out of order is an error):
+ *   smgpu_quality_constraint_pass_begin, the move of Cc, _pass_faces, the sum of the counts: as 10.15.
+ *   sum == 0:  smgpu_quality_constraint_pass_end(0) closes the record.  Nothing else is called.
+ *   sum > 0:   k < S+P: the host moves sendT -> recvT.  Then
+ *     smgpu_quality_constraint_pass_scale(sum)   combines the marks (k < S+P), at the iteration's first such pass keeps L and
+ *                             fills s = 1, applies mark -> scale, queues the local half of sweep 0 (k < S+P and n > 0) and
+ *                             returns with sendS complete.
+ *     n times (k < S+P):      the host moves sendS -> recvS as exchange T; smgpu_quality_constraint_pass_sweep finishes the sweep
+ *                             (the shared points' totals), queues the next one's local half and returns with sendS complete.
+ *     smgpu_quality_constraint_pass_end(sum)     the accepted points, the counts; k == S+P: the record closes, *done = 1.
+ *   Refused: _pass_scale when scaling is off, without _pass_faces, twice in a pass, with sum <= 0; _pass_sweep without _pass_scale
+ *   or when no sweep is due; _pass_end with sum > 0 without _pass_scale, with another sum than _pass_scale got, or with sweeps due.
+ * REFUSED by smgpu_set_quality_constraint_scaling_coupled, by name: scalePasses < 0, errorReduction outside 0 <= r < 1 (and NaN),
+ * nSmoothScale < 0; an engine without a halo (smgpu_set_quality_constraint_scaling is its form, and keeps refusing an engine with
+ * one); boundary point smoothing; the coupled tangle constraint; the coupled quality constraint off, or its exempt faces not taken;
+ * between smgpu_iter_begin and smgpu_iter_end; with the passes of an iteration due; scalePasses + passes above 2147483647; a null
+ * table or buffer that is needed; a table out of range.
+ * Memory, outside deviceBytes, held while scaling is on: 10.19's 40 bytes per point, 20 bytes per shared point and 4 per counted
+ * row entry; the caller owns sendS / recvS. */
+typedef struct smgpu_quality_scale_coupling {
+    const int32_t* rowOffsets;              /* nShared + 1: CSR over the shared points, in the halo's order */
+    const int32_t* rowPoints;               /* the counted neighbours of each shared point: local point ids, in row order */
+    const int32_t* sharedDeg;               /* nShared: the degree of each shared point in the whole mesh */
+    void *sendS, *recvS;                    /* device, nSend / nRecv doubles, moved by the caller like sendT / recvT */
+} smgpu_quality_scale_coupling;
+int smgpu_set_quality_constraint_scaling_coupled(smgpu_handle* h, const smgpu_quality_constraint_scaling* p, const smgpu_quality_scale_coupling* c);
+int smgpu_quality_constraint_pass_scale(smgpu_handle* h, int64_t nBadGlobal);               /* after smgpu_quality_constraint_pass_faces */
+int smgpu_quality_constraint_pass_sweep(smgpu_handle* h);
+
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):
  *   1. smgpu_quality_coupled_pack: the geometry of the current points (the loop's own launch, uncounted), then the owner cell

@@ -212,6 +212,11 @@ class QualityConstraintStateScaled(C.Structure):
     _fields_ = QualityConstraintStateAll._fields_ + QualityConstraintScaling._fields_
 
 
+class QualityScaleCoupling(C.Structure):
+    """smgpu_quality_scale_coupling: the counted rows and degrees of the shared points, the buffers of exchange S"""
+    _fields_ = [("rowOffsets", c_i32p), ("rowPoints", c_i32p), ("sharedDeg", c_i32p), ("sendS", C.c_void_p), ("recvS", C.c_void_p)]
+
+
 class TangleHaloDesc(C.Structure):
     """smgpu_tangle_halo_desc"""
     _fields_ = [("sendT", C.c_void_p), ("recvT", C.c_void_p)]
@@ -361,6 +366,9 @@ SYMBOLS = {
     "smgpu_set_quality_constraint_scaling": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintScaling)]),
     "smgpu_get_quality_constraint_records_scaled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintRecordScaled), C.c_int64, C.POINTER(C.c_int64)]),
     "smgpu_get_quality_constraint_state_scaled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintStateScaled)]),
+    "smgpu_set_quality_constraint_scaling_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintScaling), C.POINTER(QualityScaleCoupling)]),
+    "smgpu_quality_constraint_pass_scale": (C.c_int, [C.c_void_p, C.c_int64]),
+    "smgpu_quality_constraint_pass_sweep": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_coupled_exempt": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_begin": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_faces": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

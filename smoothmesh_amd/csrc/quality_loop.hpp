@@ -953,6 +953,8 @@ static void qualityConstraintCoupledIterEnd(smgpu_handle* h, const double* x) {
     h->qc.k = 0;
     h->qc.reverting = 0;
     h->qc.stage = 0;
+    h->qc.kept = false;                         // (10.20: the scale state does not outlive an iteration)
+    h->qc.nScaleRan = h->qc.sweepsDue = 0;
 }
 int smgpu_quality_constraint_pass_begin(smgpu_handle* h) {
     if (!h) return fail("null handle");
@@ -989,10 +991,12 @@ int smgpu_quality_constraint_pass_faces(smgpu_handle* h, int64_t* nBadLocal) {
     *nBadLocal = qd.t.badNow;
     return 0;
 }
+static int qualityConstraintPassEndScaled(smgpu_handle* h, int64_t nBadGlobal, int32_t* done);
 int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32_t* done) {
     if (!h || !done) return fail("null argument");
     QualityConstraintHost& q = h->qc;
     if (!q.coupled) return fail("smgpu_quality_constraint_pass_end: the coupled quality constraint is not on (smgpu_set_quality_constraint_coupled)");
+    if (q.scaleCoupled) return qualityConstraintPassEndScaled(h, nBadGlobal, done);   // 10.20, below
     if (q.stage != 2 || q.k < 0) return fail("smgpu_quality_constraint_pass_end without smgpu_quality_constraint_pass_faces");
     if (nBadGlobal < 0) return fail("smgpu_quality_constraint_pass_end: nBadGlobal < 0");
     HIP_OK(hipSetDevice(h->device));
@@ -1017,3 +1021,188 @@ int smgpu_quality_constraint_pass_end(smgpu_handle* h, int64_t nBadGlobal, int32
     return 0;
 }
 
+// ---- the scaling passes of the coupled form (kernels_quality_scale_coupled.hpp, DESIGN.md "Mesh quality", 10.20) ----
+// 10.19's scale field on every rank, driven by the host like the passes of 10.15: the pass runs to S + P, and between the move of
+// T and smgpu_quality_constraint_pass_end stand smgpu_quality_constraint_pass_scale and, per sweep, _pass_sweep behind the host's
+// move of S.  The memory is the constraint's second block, as the serial form's.
+int smgpu_set_quality_constraint_scaling_coupled(smgpu_handle* h, const smgpu_quality_constraint_scaling* p, const smgpu_quality_scale_coupling* c) {
+    if (!h) return fail("null handle");
+    const std::string api("smgpu_set_quality_constraint_scaling_coupled");
+    const smgpu_quality_constraint_scaling prm = p ? *p : smgpu_quality_constraint_scaling{0, 4, 0.75};
+    if (prm.scalePasses < 0) return fail(api + ": scalePasses < 0");
+    if (!(prm.errorReduction >= 0.0 && prm.errorReduction < 1.0)) return fail(api + ": errorReduction is outside 0 <= errorReduction < 1");
+    if (prm.nSmoothScale < 0) return fail(api + ": nSmoothScale < 0");
+    if (!h->haloOn) return fail(api + ": the engine has no halo (smgpu_halo_configure); a serial engine takes smgpu_set_quality_constraint_scaling");
+    if (h->bndOn) return fail(api + ": not available on an engine with boundary point smoothing (nor is the quality constraint)");
+    if (h->tg.on)
+        return fail(api + ": the coupled tangle constraint is on (smgpu_set_tangle_constraint_coupled), and it has no scaling passes; the coupled quality "
+                    "constraint with its three criteria off is the tangle constraint");
+    QualityConstraintHost& q = h->qc;
+    if (!q.on || !q.coupled) return fail(api + ": the coupled quality constraint is off (smgpu_set_quality_constraint_coupled); switch it on first");
+    if (q.pending) return fail(api + ": the exempt faces have not been taken (smgpu_quality_constraint_coupled_exempt)");
+    if (h->iterOpen) return fail(api + ": between smgpu_iter_begin and smgpu_iter_end");
+    if (q.k >= 0) return fail(api + ": the passes of an iteration are due (smgpu_quality_constraint_pass_begin / _end)");
+    if ((int64_t)prm.scalePasses + (int64_t)q.prm.passes > 0x7fffffffLL) return fail(api + ": scalePasses + passes is above 2147483647");
+    const int nS = h->nShared, nP = h->mv.nPoints;
+    std::vector<int> rowOff, rowPt, deg;
+    if (prm.scalePasses > 0) {
+        if (!c || (nS > 0 && (!c->rowOffsets || !c->sharedDeg))) return fail(api + ": null table");
+        if ((h->nSend && !c->sendS) || (h->nRecv && !c->recvS)) return fail(api + ": null exchange buffer");
+        rowOff.assign((size_t)nS + 1, 0);
+        deg.assign((size_t)std::max(1, nS), 0);
+        for (int i = 0; i <= nS && nS > 0; ++i) rowOff[(size_t)i] = c->rowOffsets[i];
+        if (rowOff[0] != 0) return fail(api + ": rowOffsets does not start at 0");
+        for (int i = 0; i < nS; ++i) {
+            if (rowOff[(size_t)i + 1] < rowOff[(size_t)i]) return fail(api + ": rowOffsets decreases");
+            deg[(size_t)i] = c->sharedDeg[i];
+            if (deg[(size_t)i] < rowOff[(size_t)i + 1] - rowOff[(size_t)i]) return fail(api + ": sharedDeg is below the counted entries of a row");
+        }
+        const int nE = rowOff[(size_t)nS];
+        if (nE > 0 && !c->rowPoints) return fail(api + ": null table");
+        rowPt.assign((size_t)std::max(1, nE), 0);
+        for (int k = 0; k < nE; ++k) {
+            rowPt[(size_t)k] = c->rowPoints[k];
+            if (rowPt[(size_t)k] < 0 || rowPt[(size_t)k] >= nP) return fail(api + ": rowPoints out of range");
+        }
+    }
+    HIP_OK(hipSetDevice(h->device));
+    if (q.scaleBlock.live()) {
+        HIP_OK(hipStreamSynchronize(h->stream));
+        q.releaseScaling();
+    }
+    if (prm.scalePasses == 0) return 0;
+    const size_t nPts = (size_t)std::max(1, nP), nScale = (nPts + 1) & ~(size_t)1;
+    if (q.scaleBlock.alloc(&q.L, 3 * nPts) || q.scaleBlock.alloc(&q.scaleA, nScale) || q.scaleBlock.alloc(&q.scaleB, nScale) ||
+        q.scaleBlock.alloc(&q.scRowOff, rowOff.size()) || q.scaleBlock.alloc(&q.scRowPt, rowPt.size()) || q.scaleBlock.alloc(&q.scDeg, deg.size()) ||
+        q.scaleBlock.alloc(&q.scPart, (size_t)std::max(1, nS))) {
+        const int rc = q.scaleBlock.failed("the quality constraint's scaling passes");
+        q.releaseScaling();
+        return rc;
+    }
+    // (the host vectors live until the wait below)
+    hipError_t e = hipMemcpyAsync(q.scRowOff, rowOff.data(), sizeof(int) * rowOff.size(), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(q.scRowPt, rowPt.data(), sizeof(int) * rowPt.size(), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(q.scDeg, deg.data(), sizeof(int) * deg.size(), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        q.releaseScaling();
+        return fail(api + ": " + hipGetErrorString(e));
+    }
+    q.nScale = (long long)nScale;
+    q.maxGrid = std::max(1, envInt("SMGPU_QS_MAX_GRID", kQsMaxGrid));
+    q.sendS = (double*)c->sendS; q.recvS = (double*)c->recvS;
+    q.scaling = prm;
+    q.scaleCoupled = true;
+    return 0;
+}
+// the local half of a sweep: 10.19's sweep over every point from the rank's rows, and the partial sums of the shared points from
+// the same field into scPart and sendS
+static void qualityConstraintSweepHalf(smgpu_handle* h) {
+    QualityConstraintHost& q = h->qc;
+    const int nP = h->mv.nPoints, gPoint = std::max(1, (int)std::min<int64_t>(q.maxGrid, ((int64_t)nP + kQsBlock - 1) / kQsBlock));
+    hipLaunchKernelGGL(k_qs_sweep, dim3(gPoint), dim3(kQsBlock), 0, h->stream, h->mv, (const double*)q.sCur, q.sNext, (const QcDev*)q.dev, (const smgpu_iter_stats*)nullptr);
+    if (h->nShared > 0) {
+        const int gShared = std::max(1, (int)std::min<int64_t>(q.maxGrid, ((int64_t)h->nShared + kQsBlock - 1) / kQsBlock));
+        hipLaunchKernelGGL(k_qsc_partial, dim3(gShared), dim3(kQsBlock), 0, h->stream, h->nShared, (const int*)q.scRowOff, (const int*)q.scRowPt, (const double*)q.sCur,
+                           q.scPart, (const int*)h->dSendOff, (const int*)h->dSendSlots, q.sendS);
+    }
+}
+int smgpu_quality_constraint_pass_scale(smgpu_handle* h, int64_t nBadGlobal) {
+    if (!h) return fail("null handle");
+    QualityConstraintHost& q = h->qc;
+    if (!q.coupled) return fail("smgpu_quality_constraint_pass_scale: the coupled quality constraint is not on (smgpu_set_quality_constraint_coupled)");
+    if (!q.scaleCoupled) return fail("smgpu_quality_constraint_pass_scale: the scaling passes are off (smgpu_set_quality_constraint_scaling_coupled)");
+    if (q.stage == 3) return fail("smgpu_quality_constraint_pass_scale: called twice in one pass");
+    if (q.stage != 2 || q.k < 0) return fail("smgpu_quality_constraint_pass_scale without smgpu_quality_constraint_pass_faces");
+    if (nBadGlobal <= 0) return fail("smgpu_quality_constraint_pass_scale: nBadGlobal <= 0 (a clean pass goes to smgpu_quality_constraint_pass_end)");
+    HIP_OK(hipSetDevice(h->device));
+    const int nP = h->mv.nPoints, S = q.scaling.scalePasses, total = S + q.prm.passes;
+    const bool full = q.k == total;
+    if (!full) {
+        if (computeAfterExch(h)) return 1;      // exchange T has been enqueued by the host
+        if (h->nShared > 0 && h->nRecv > 0)
+            hipLaunchKernelGGL(k_tangle_combine, dim3((h->nShared + kTangleBlock - 1) / kTangleBlock), dim3(kTangleBlock), 0, h->stream, h->nShared,
+                               (const int*)h->dSharedLocal, (const int*)h->dCombOff, (const int*)h->dCombSlots, (const int*)q.recvT, q.marks);
+    }
+    if (!q.kept) {                              // the iteration's first pass that is not clean
+        const long long nL = 3 * (long long)nP;
+        const int gKeep = (int)std::max<long long>(1, ((nL >> 1) + (long long)kGuardBlock * kGuardPer - 1) / ((long long)kGuardBlock * kGuardPer));
+        q.sCur = q.scaleA; q.sNext = q.scaleB;
+        hipLaunchKernelGGL(k_qs_keep, dim3(gKeep), dim3(kGuardBlock), 0, h->stream, (const double*)h->st.ptsCur, q.L, nL, q.sCur, q.nScale, (const QcDev*)q.dev,
+                           (const smgpu_iter_stats*)nullptr);
+        q.kept = true;
+    }
+    const int gWord = std::max(1, (int)((((int64_t)nP + 3) / 4 + kQsBlock - 1) / kQsBlock));
+    hipLaunchKernelGGL(k_qs_mark, dim3(gWord), dim3(kQsBlock), 0, h->stream, q.marks, q.sCur, nP, q.scaling.errorReduction,
+                       full ? (int)kQsFull : (q.k < S ? (int)kQsScale : (int)kQsZero), (const QcDev*)q.dev, (const smgpu_iter_stats*)nullptr);
+    q.sweepsDue = full ? 0 : q.scaling.nSmoothScale;
+    if (!full) {
+        ++q.reverting;
+        if (q.k < S) ++q.nScaleRan;
+    }
+    if (q.sweepsDue > 0) qualityConstraintSweepHalf(h);
+    HIP_OK(hipGetLastError());
+    q.scaleBad = nBadGlobal;
+    q.stage = 3;
+    return q.sweepsDue > 0 ? checkDeviceError(h) : 0;     // sendS is the host's to move
+}
+int smgpu_quality_constraint_pass_sweep(smgpu_handle* h) {
+    if (!h) return fail("null handle");
+    QualityConstraintHost& q = h->qc;
+    if (!q.coupled) return fail("smgpu_quality_constraint_pass_sweep: the coupled quality constraint is not on (smgpu_set_quality_constraint_coupled)");
+    if (!q.scaleCoupled) return fail("smgpu_quality_constraint_pass_sweep: the scaling passes are off (smgpu_set_quality_constraint_scaling_coupled)");
+    if (q.stage != 3 || q.k < 0) return fail("smgpu_quality_constraint_pass_sweep without smgpu_quality_constraint_pass_scale");
+    if (q.sweepsDue <= 0) return fail("smgpu_quality_constraint_pass_sweep: no sweep of the pass is due (nSmoothScale of them follow a marked pass, none the full revert)");
+    HIP_OK(hipSetDevice(h->device));
+    if (computeAfterExch(h)) return 1;          // exchange S has been enqueued by the host
+    if (h->nShared > 0) {
+        const int gShared = std::max(1, (int)std::min<int64_t>(q.maxGrid, ((int64_t)h->nShared + kQsBlock - 1) / kQsBlock));
+        hipLaunchKernelGGL(k_qsc_combine, dim3(gShared), dim3(kQsBlock), 0, h->stream, h->nShared, (const int*)h->dSharedLocal, (const int*)h->dCombOff,
+                           (const int*)h->dCombSlots, (const double*)q.scPart, (const double*)q.recvS, (const int*)q.scDeg, (const double*)q.sCur, q.sNext);
+    }
+    std::swap(q.sCur, q.sNext);
+    --q.sweepsDue;
+    if (q.sweepsDue > 0) qualityConstraintSweepHalf(h);
+    HIP_OK(hipGetLastError());
+    return q.sweepsDue > 0 ? checkDeviceError(h) : 0;
+}
+// smgpu_quality_constraint_pass_end while the scaling passes are on: a clean pass closes as before, through k_qc_close's twin;
+// one with bad cells applies the scale field smgpu_quality_constraint_pass_scale and the sweeps have left
+static int qualityConstraintPassEndScaled(smgpu_handle* h, int64_t nBadGlobal, int32_t* done) {
+    QualityConstraintHost& q = h->qc;
+    if (q.k < 0 || (q.stage != 2 && q.stage != 3)) return fail("smgpu_quality_constraint_pass_end without smgpu_quality_constraint_pass_faces");
+    if (nBadGlobal < 0) return fail("smgpu_quality_constraint_pass_end: nBadGlobal < 0");
+    if (nBadGlobal > 0 && q.stage != 3) return fail("smgpu_quality_constraint_pass_end: the scaling passes are on and cells are bad; smgpu_quality_constraint_pass_scale comes first");
+    if (q.stage == 3 && nBadGlobal != q.scaleBad) return fail("smgpu_quality_constraint_pass_end: nBadGlobal differs from the one given to smgpu_quality_constraint_pass_scale");
+    if (q.stage == 3 && q.sweepsDue > 0)
+        return fail("smgpu_quality_constraint_pass_end: " + std::to_string(q.sweepsDue) + " sweeps of the pass are due (smgpu_quality_constraint_pass_sweep)");
+    HIP_OK(hipSetDevice(h->device));
+    smgpu_quality_constraint_record_scaled* rec = nullptr;
+    if (q.slab.slot(q.slabUsed, &rec)) return 1;
+    const int nP = h->mv.nPoints, total = q.scaling.scalePasses + q.prm.passes;
+    const bool full = nBadGlobal > 0 && q.k == total;
+    if (nBadGlobal > 0) {
+        const int gPoint = std::max(1, (int)std::min<int64_t>(q.maxGrid, ((int64_t)nP + kQsBlock - 1) / kQsBlock));
+        hipLaunchKernelGGL(k_qsc_open, dim3(1), dim3(64), 0, h->stream, rec);
+        hipLaunchKernelGGL(k_qsc_apply, dim3(gPoint), dim3(kQsBlock), 0, h->stream, q.x, (const double*)q.L, h->st.ptsCur, (const double*)q.sCur, nP,
+                           (const int*)h->dSharedSlot, (const uint8_t*)q.counted, rec);
+        // points moved: the geometry smgpu_iter_ahead left for the next iteration is that of other points
+        h->geomAheadDone = false;
+        h->q.epoch++;
+    }
+    const bool close = nBadGlobal == 0 || full;
+    if (close) {
+        QcCounts c{};
+        for (int i = 0; i < 14; ++i) c.n[i] = (long long)q.n0[i];
+        hipLaunchKernelGGL(k_qsc_close, dim3(1), dim3(64), 0, h->stream, rec, (long long)(q.count + 1), q.reverting, full ? 1 : 0, c, q.nScaleRan, q.kept ? 0 : 1);
+        ++q.count;
+        ++q.slabUsed;
+        q.k = -1;
+        q.kept = false;
+        q.nScaleRan = 0;
+    } else ++q.k;
+    q.stage = 0;
+    *done = close ? 1 : 0;
+    HIP_OK(hipGetLastError());
+    return 0;
+}

@@ -282,7 +282,22 @@ struct QualityConstraintHost {
     double *L = nullptr, *scaleA = nullptr, *scaleB = nullptr;
     long long nScale = 0;
     int maxGrid = 8192;                     // workgroups of a sweep / apply launch at most (kQsMaxGrid; SMGPU_QS_MAX_GRID)
-    void releaseScaling() { scaleBlock.release(); scaling = smgpu_quality_constraint_scaling{0, 4, 0.75}; nScale = 0; }
+    // the scaling passes of the coupled form (10.20, smgpu_set_quality_constraint_scaling_coupled, kernels_quality_scale_coupled.hpp):
+    // the same parameters, L and scale fields, in the same block, and with them the caller's tables of the shared points -- scRowOff /
+    // scRowPt: the counted neighbours of every shared point (CSR, local ids, row order), scDeg: its degree in the whole mesh -- the
+    // partial sums of a sweep (scPart, one double per shared point) and the caller's exchange buffers (sendS / recvS, device,
+    // nSend / nRecv doubles).  State of the iteration in hand: kept (L and s = 1 are this iteration's), sCur / sNext (which field
+    // is current), sweepsDue (sweep calls the pass in hand still waits for), nScaleRan (marked passes with k < S so far); stage 3:
+    // behind smgpu_quality_constraint_pass_scale
+    bool scaleCoupled = false, kept = false;
+    int *scRowOff = nullptr, *scRowPt = nullptr, *scDeg = nullptr;
+    double *scPart = nullptr, *sendS = nullptr, *recvS = nullptr, *sCur = nullptr, *sNext = nullptr;
+    int sweepsDue = 0, nScaleRan = 0;
+    int64_t scaleBad = 0;
+    void releaseScaling() {
+        scaleBlock.release(); scaling = smgpu_quality_constraint_scaling{0, 4, 0.75}; nScale = 0;
+        scaleCoupled = kept = false; sendS = recvS = sCur = sNext = nullptr; sweepsDue = nScaleRan = 0;
+    }
     // the limits of 10.16 (smgpu_set_quality_constraint_limits, kernels_quality_limits.hpp).  faceMore: a new face criterion is
     // on; cellMore: minVolRatio or minDeterminant is; with neither the launches are 10.14's.  vol, exemptDet: allocated with
     // cellMore, 8 bytes and 1 byte per cell

@@ -28,6 +28,7 @@
 #include "kernels_quality_constraint.hpp"
 #include "kernels_quality_limits.hpp"
 #include "kernels_quality_scale.hpp"
+#include "kernels_quality_scale_coupled.hpp"
 #include "boundary.hpp"
 #include "tiles.hpp"
 #include "topology.hpp"

@@ -915,6 +915,29 @@ class SmoothEngine:
         self._check(self._lib.smgpu_quality_constraint_pass_end(self._h, int(nBadGlobal), C.byref(done)))
         return bool(done.value)
 
+    def set_quality_constraint_scaling_coupled(self, rowOffsets, rowPoints, sharedDeg, sendS, recvS, scalePasses=0, errorReduction=0.75, nSmoothScale=4):
+        """The scaling passes of the coupled quality constraint (include/smgpu.h, smgpu_set_quality_constraint_scaling_coupled;
+        DESIGN.md "Mesh quality", 10.20), valid while it is on.  rowOffsets / rowPoints: the counted neighbours of every shared
+        point (CSR in the halo's order, local ids, row order), sharedDeg: its degree in the whole mesh (halo.scale_tables builds
+        them); sendS / recvS: raw device addresses (ints) of nSend / nRecv doubles the caller owns and moves like sendT / recvT.
+        scalePasses = 0 switches the scaling off and frees its memory (the tables and buffers are then not read and may be None / 0).  The passes
+        are the caller's: quality_constraint_pass_scale and _pass_sweep between the move of T and quality_constraint_pass_end."""
+        p = _ffi.QualityConstraintScaling(int(scalePasses), int(nSmoothScale), float(errorReduction))
+        if rowOffsets is None:                # (scalePasses = 0: nothing else is read)
+            self._check(self._lib.smgpu_set_quality_constraint_scaling_coupled(self._h, C.byref(p), None))
+            return
+        off, pts, deg = (np.ascontiguousarray(a, dtype=np.int32) for a in (rowOffsets, rowPoints, sharedDeg))
+        c = _ffi.QualityScaleCoupling(_p(off, _ffi.c_i32p), _p(pts, _ffi.c_i32p), _p(deg, _ffi.c_i32p), sendS or None, recvS or None)
+        self._check(self._lib.smgpu_set_quality_constraint_scaling_coupled(self._h, C.byref(p), C.byref(c)))
+
+    def quality_constraint_pass_scale(self, nBadGlobal):
+        """behind the move of T in a pass with bad cells, scaling on: the marks become scales, sweep 0's local half; sendS is packed"""
+        self._check(self._lib.smgpu_quality_constraint_pass_scale(self._h, int(nBadGlobal)))
+
+    def quality_constraint_pass_sweep(self):
+        """behind the move of S: finishes the sweep in hand on the shared points and queues the next one's local half"""
+        self._check(self._lib.smgpu_quality_constraint_pass_sweep(self._h))
+
     def quality_constraint_records(self) -> list:
         """The pending records of the quality constraint (QualityConstraintRecordAll), one per iteration that ran, in ascending
         iteration; clears them."""

@@ -77,6 +77,80 @@ class HaloTables:
         self.combSlots = np.array([s for p in per for s in p], dtype=np.int32) if nsh else np.zeros(0, np.int32)
 
 
+def scale_edge_info(tables, pointPoints):
+    """What a rank tells the others for the scaling passes of a decomposed mesh (DESIGN.md "Mesh quality", 10.20), from its
+    HaloTables and its pointPoints rows (offsets, values): dict(names: (nShared, 2) the shared points as (sharedGlobal,
+    sharedComp); unshared: per shared point the row entries whose other end is not shared -- they lie on this rank alone and are
+    always counted; keys: (m, 4) the edges between two shared points that this sub-domain holds, each once, as (global, comp) of
+    the lower name then of the higher)."""
+    i, _, j = _shared_rows(tables, pointPoints)
+    names = np.stack([np.asarray(tables.sharedGlobal, np.int64), np.asarray(tables.sharedComp, np.int64)], axis=1).reshape(-1, 2)
+    unshared = np.bincount(i[j < 0], minlength=len(names)).astype(np.int64)
+    keys = _edge_keys(names, i[j >= 0], j[j >= 0])
+    return dict(names=names, unshared=unshared, keys=np.unique(keys, axis=0) if len(keys) else keys)
+
+
+def scale_tables(tables, pointPoints, infos):
+    """The set-up tables of smgpu_set_quality_constraint_scaling_coupled for rank tables.rank: infos[r] =
+    scale_edge_info of rank r, for every rank.  Returns (rowOffsets, rowPoints, sharedDeg), int32: a CSR over the shared points
+    holding the COUNTED neighbours' local ids in row order -- a row entry (p, q) is counted iff this is the lowest rank whose
+    sub-domain holds the edge pq; an entry with an unshared end is always counted -- and the number of counted entries of every
+    shared point over all ranks, its degree in the whole mesh."""
+    rank = tables.rank
+    i, q, j = _shared_rows(tables, pointPoints)
+    names = infos[rank]["names"]
+    nsh = len(names)
+    both = j >= 0
+    lower = set()
+    for r in range(rank):
+        lower.update(map(tuple, infos[r]["keys"].tolist()))
+    counted = np.ones(len(i), bool)
+    if both.any():
+        mine = _edge_keys(names, i[both], j[both])
+        counted[both] = np.fromiter((tuple(k) not in lower for k in mine.tolist()), bool, len(mine))
+    rowOffsets = np.zeros(nsh + 1, np.int32)
+    np.cumsum(np.bincount(i[counted], minlength=nsh), out=rowOffsets[1:])
+    rowPoints = q[counted].astype(np.int32)                      # (i ascends and a row keeps its order: the CSR's order)
+    # the degree: the entries with an unshared end on every rank that holds the point, and every edge between two shared points once
+    deg = {}
+    for info in infos:
+        for name, u in zip(map(tuple, info["names"].tolist()), info["unshared"].tolist()):
+            deg[name] = deg.get(name, 0) + int(u)
+    edges = set()
+    for info in infos:
+        edges.update(map(tuple, info["keys"].tolist()))
+    for a, b, c, d in edges:
+        if (a, b) in deg:
+            deg[(a, b)] += 1
+        if (c, d) in deg:
+            deg[(c, d)] += 1
+    sharedDeg = np.array([deg[n] for n in map(tuple, names.tolist())], dtype=np.int32).reshape(-1)
+    return rowOffsets, rowPoints, sharedDeg
+
+
+def _shared_rows(tables, pointPoints):
+    """the pointPoints rows of a rank's shared points, flattened in the order of its HaloTables and in row order: (shared index of
+    the row, local id of the neighbour, shared index of the neighbour or -1)"""
+    off, val = (np.asarray(a, np.int64) for a in pointPoints)
+    sl = np.asarray(tables.sharedLocal, np.int64)
+    n = off[sl + 1] - off[sl]
+    start = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    flat = np.repeat(off[sl] - start[:-1], n) + np.arange(start[-1])
+    i = np.repeat(np.arange(len(sl)), n)
+    q = val[flat]
+    slot = np.full(len(off) - 1, -1, np.int64)
+    slot[sl] = np.arange(len(sl))
+    return i, q, slot[q]
+
+
+def _edge_keys(names, i, j):
+    """(m, 4): the names of the two ends of every edge (i, j) between shared points, the lower name first"""
+    a, b = names[i], names[j]
+    swap = (a[:, 0] > b[:, 0]) | ((a[:, 0] == b[:, 0]) & (a[:, 1] > b[:, 1]))
+    lo, hi = np.where(swap[:, None], b, a), np.where(swap[:, None], a, b)
+    return np.concatenate([lo, hi], axis=1).reshape(-1, 4)
+
+
 def own_fold_default():
     """the syncTools::syncPointList model (include/smgpu.h smgpu_set_sync_variant): False = the master's fold handed to every
     sharer (default), True = every sharer folds onto its own value (SMGPU_SYNC_VARIANT=own, the engine reads the same variable)"""
@@ -243,6 +317,21 @@ def combine_quality_constraint_records(per_rank):
     return out
 
 
+def combine_quality_constraint_records_scaled(per_rank):
+    """combine_quality_constraint_records for the scaled records (DESIGN.md "Mesh quality", 10.20): nScalePasses is a global value
+    like passes and fullRevert, minScale the minimum of the ranks', every other field a sum"""
+    import dataclasses
+    out = []
+    shared = ("iteration", "passes", "fullRevert", "nScalePasses")
+    for recs in zip(*per_rank):
+        r0 = recs[0]
+        assert all(tuple(getattr(r, f) for f in shared) == tuple(getattr(r0, f) for f in shared) for r in recs), recs
+        counts = [f.name for f in dataclasses.fields(r0) if f.name not in shared + ("minScale",)]
+        out.append(type(r0)(**{f: getattr(r0, f) for f in shared}, minScale=min(r.minScale for r in recs), **{f: sum(getattr(r, f) for r in recs) for f in counts}))
+    assert all(len(r) == len(per_rank[0]) for r in per_rank)
+    return out
+
+
 def l_view(t, width):
     """the exchange-L records in use: `width` doubles per slot, packed from the start of the (slots, L_DOUBLES) buffer"""
     n = t.shape[0]
@@ -332,11 +421,13 @@ class _ConstraintDriver:
     """The tangle constraint (include/smgpu.h smgpu_set_tangle_constraint_coupled) and the quality constraint
     (smgpu_set_quality_constraint_coupled, 10.15; its further limits, 10.17, 10.18) on a decomposed mesh, written once for the two
     smoothers below.  A smoother provides: _rank_states() (the _RankState of every rank this process drives: one, or all),
-    _move_marks() (exchange T), _pair_couplings(couplings) and _move_cc() (sendCc -> the neighbours' recvCc, and Vc with it),
+    _move_marks() (exchange T), _move_scales() (exchange S, 10.20), _pair_couplings(couplings) and _move_cc() (sendCc -> the neighbours' recvCc, and Vc with it),
     _sum_counts(values) (a vector of counts summed over the ranks), _all_ranks(mine) (one entry per rank of the job from this
     process's), _agree_on_error(err) (every rank raises when any has an error) and, where an error inside a pass has to wait for
     the other ranks, _guarded(call)."""
     _tangle_err = None            # what _guarded has caught on this rank, carried to the next reduction
+    scale_passes = 0              # set_quality_constraint_scaling: S, the scaling passes in front of the reverting ones (0: off)
+    scale_sweeps = 0              # ... and n, the sweeps behind every marked pass
 
     def _guarded(self, call, *args):
         """a call into an engine inside a pass; one process holds every rank: an error is everyone's at once"""
@@ -395,6 +486,10 @@ class _ConstraintDriver:
             name, passes, faces = "quality", self.quality_passes, True
         else:
             return
+        # (10.20: with the scaling passes on, S of them stand in front of the reverting ones; between the move of T and pass_end
+        # every engine turns the marks into scales and, per sweep, the partial sums of the shared points travel as exchange S)
+        S = self.scale_passes if faces else 0
+        passes += S
         engines = [st.eng for st in self._rank_states()]
         for k in range(passes + 1):
             if faces:
@@ -410,6 +505,13 @@ class _ConstraintDriver:
                 self._agree_on_error(err if err is not None else RuntimeError(f"another rank failed inside a pass of the {name} constraint (see its message)"))
             if total > 0 and k < passes:
                 self._move_marks()
+            if total > 0 and S > 0:
+                for eng in engines:
+                    self._guarded(eng.quality_constraint_pass_scale, total)
+                for _ in range(self.scale_sweeps if k < passes else 0):
+                    self._move_scales()
+                    for eng in engines:
+                        self._guarded(eng.quality_constraint_pass_sweep)
             for eng in engines:   # (a failure here is carried to the next reduction or agreement point)
                 self._guarded(eng.quality_constraint_pass_end if faces else eng.tangle_pass_end, total)
             if total == 0 or k == passes:
@@ -476,6 +578,7 @@ class _ConstraintDriver:
                 st.sendVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
                 st.recvVc = torch.zeros(max(n, 1), dtype=torch.float64, device=self.device)
         self.quality_passes = None
+        self.scale_passes = self.scale_sweeps = 0       # (enabling switches the engines' scaling passes off)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)         # the buffers are zeroed before the engines' streams write them
         self._enable_engines((maxNonOrtho, maxInternalSkewness, maxBoundarySkewness, passes), more)
@@ -506,8 +609,54 @@ class _ConstraintDriver:
             err = ex
         self._agree_on_error(err)
 
+    def set_quality_constraint_scaling(self, scalePasses=0, errorReduction=0.75, nSmoothScale=4):
+        """The scaling passes of the quality constraint on the decomposed mesh (smgpu_set_quality_constraint_scaling_coupled,
+        DESIGN.md "Mesh quality", 10.20), valid while the constraint is on: engine.set_quality_constraint_scaling's parameters,
+        read on the global mesh -- the sweep of a shared point runs over its neighbours on every rank, their partial sums
+        travelling once per sweep.  scalePasses = 0 switches them off.  A collective: every rank calls it, with the same
+        values; the counted rows and degrees of the shared points are built from every rank's pointPoints rows (scale_tables).
+        An error on any rank is raised on every rank and leaves the scaling off on all of them."""
+        if self.quality_passes is None:
+            raise RuntimeError("set_quality_constraint_scaling: the quality constraint is off; set_quality_constraint first")
+        torch, states = self.torch, self._rank_states()
+        S, n = int(scalePasses), int(nSmoothScale)
+        self.scale_passes = self.scale_sweeps = 0
+        pp = []
+        if S > 0:
+            from .engine import HostTopology
+            pp = [HostTopology(st.sub.mesh).addressing("pointPoints") for st in states]
+        # (set-up only, answered by every rank: the edges between shared points that each sub-domain holds)
+        infos = self._all_ranks([scale_edge_info(st.t, p) for st, p in zip(states, pp)] if S > 0 else [None] * len(states))
+        err = None
+        try:
+            for st, p in zip(states, pp):
+                st.scaleTables = scale_tables(st.t, p, infos)
+                st.sendS = torch.zeros(max(st.t.nSend, 1), dtype=torch.float64, device=self.device)
+                st.recvS = torch.zeros(max(st.t.nRecv, 1), dtype=torch.float64, device=self.device)
+            if S > 0 and self.device.type == "cuda":
+                torch.cuda.synchronize(self.device)     # the buffers are zeroed before the engines' streams write them
+            for st in states:
+                if S > 0:
+                    st.eng.set_quality_constraint_scaling_coupled(*st.scaleTables, st.sendS.data_ptr(), st.recvS.data_ptr(), S, errorReduction, n)
+                else:
+                    st.eng.set_quality_constraint_scaling_coupled(None, None, None, 0, 0, S, errorReduction, n)
+        except Exception as ex:  # noqa: BLE001 -- re-raised below, on every rank
+            err = ex
+        try:
+            self._agree_on_error(err)
+        except Exception:
+            for st in states:
+                try:
+                    st.eng.set_quality_constraint_scaling_coupled(None, None, None, 0, 0, 0)
+                except Exception:  # noqa: BLE001 -- the first error is the one to report
+                    pass
+            raise
+        if S > 0:
+            self.scale_passes, self.scale_sweeps = S, n
+
     def clear_quality_constraint(self):
         self.quality_passes = None
+        self.scale_passes = self.scale_sweeps = 0
         for st in self._rank_states():
             st.eng.clear_quality_constraint()
 
@@ -520,6 +669,16 @@ class _ConstraintDriver:
         """The pending records, cleared by the read: those of the undecomposed mesh (combine_quality_constraint_records), or with
         per_rank one list per rank.  A collective: every rank calls it and gets the same answer."""
         return self._records("quality_constraint_records", combine_quality_constraint_records, per_rank)
+
+
+    def quality_constraint_records_scaled(self, per_rank=False):
+        """quality_constraint_records with the three fields of the scaling passes: combined by
+        combine_quality_constraint_records_scaled.  The two getters drain the same pending lists.  A collective."""
+        return self._records("quality_constraint_records_scaled", combine_quality_constraint_records_scaled, per_rank)
+
+    def quality_constraint_state_scaled(self):
+        """quality_constraint_state with scalePasses, nSmoothScale and errorReduction, the same on every rank.  A collective."""
+        return self._summed_state("quality_constraint_state_scaled", ("nExemptCells", "nExemptFaces", "nExemptDeterminantCells", "nExemptVolumeCells"))
 
 
 class DistributedSmoother(_ConstraintDriver):
@@ -1007,6 +1166,9 @@ class DistributedSmoother(_ConstraintDriver):
     def _move_marks(self):
         self._a2a(self.state.recvT, self.state.sendT, host=True)
 
+    def _move_scales(self):
+        self._a2a(self.state.recvS, self.state.sendS, host=True)
+
     def _pair_couplings(self, couplings):
         if self.world <= 1 and couplings[0][1]:
             raise RuntimeError("mesh quality: a single rank with processor patches")
@@ -1270,6 +1432,9 @@ class LocalMultiSmoother(_ConstraintDriver):
 
     def _move_marks(self):
         self._exchange("T")
+
+    def _move_scales(self):
+        self._exchange("S")
 
     def _pair_couplings(self, couplings):
         from .quality import paired_offsets
