@@ -254,8 +254,12 @@ __device__ __forceinline__ bool findLine(const BndView& b, int* __restrict__ sta
     // (leaves too, as -(16 * first + count) - 1); a popped leaf loads its (at most four) triangles in one batch and
     // tests them.  Lanes of a wave that are at different places of their descents still meet at these two program
     // points, instead of serialising leaf visits inside the child loop.
-    // boxes entered beyond the best hit so far cannot hold a nearer (or equal, lower-id) one: the limit follows the hits
-    double tLimit = 1.0 + 1e-6;
+    // Every box the segment touches is opened, also those entered beyond the best hit so far: a limit that follows the
+    // hits assumes that a triangle's parameter agrees with where its box lies on the segment, and for a segment in a
+    // triangle's own plane it does not (|det| ~ 1e-20 is still far above ROOTVSMALL, u, v and t are then quotients of
+    // rounding errors, and such a triangle can "hit" at t = 0 from a box entered at t = 0.19).  The oracle tests every
+    // triangle and takes that hit; so must the traversal (tests/test_gpu_boundary_edges.py, the in-plane segments).
+    const double tLimit = 1.0 + 1e-6;
     int sp = 0;
     if (b.nNodes > 0) stack[kBlock * sp++] = 0;
     while (sp > 0) {
@@ -310,7 +314,6 @@ __device__ __forceinline__ bool findLine(const BndView& b, int* __restrict__ sta
                 if (!(t <= 1.0)) continue;   // treeDataTriSurface::findIntersectOp: inter.distance() <= 1
                 if (bestId == 0x7fffffff || t < best || (t == best && ids[k] < bestId)) { best = t; bestId = ids[k]; hitPoint = pt; }
             }
-            if (bestId != 0x7fffffff) tLimit = fmin(tLimit, best + 1e-6 * (1.0 + fabs(best)));
         }
     }
     return bestId != 0x7fffffff;
