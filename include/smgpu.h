@@ -772,6 +772,31 @@ int smgpu_set_quality_constraint_scaling_coupled(smgpu_handle* h, const smgpu_qu
 int smgpu_quality_constraint_pass_scale(smgpu_handle* h, int64_t nBadGlobal);               /* after smgpu_quality_constraint_pass_faces */
 int smgpu_quality_constraint_pass_sweep(smgpu_handle* h);
 
+/* ---- the constraints and the guard with boundary point smoothing (DESIGN.md "Mesh quality", 10.21) ---------------------------
+ * smgpu_set_boundary_revert(h, 1) is the opt-in under which smgpu_set_tangle_constraint, smgpu_set_quality_constraint, _limits,
+ * _limits_all (all thirteen limits) and smgpu_set_quality_guard accept a serial engine with boundary point smoothing
+ * (smgpu_set_boundary_smoothing), with or without layers.  Default 0: every refusal of 10.11, 10.12 and 10.14 stands as it was.
+ * The switch launches nothing and allocates nothing: with it on and nothing armed the loop is the loop without it.
+ *
+ * THE CONTRACT.  10.12 and 10.14 hold unchanged with these additions:
+ *   - x' is the loop's result INCLUDING everything boundary point smoothing does: the projection to corners, feature edges and
+ *     the target surface, the prismatic projection, the step clamp and the restore.  A boundary point is a point like any other:
+ *     marked by a bad cell it goes back to x_p bitwise, off the place the projection gave it.
+ *   - THE POINT NORMALS ARE LOOP STATE, NOT POINT STATE.  They are blended once at the start of every iteration that runs, from
+ *     the normals as they are and the boundary faces at the points that iteration starts from.  A marked pass or a full revert
+ *     never puts them back: the next iteration blends from the current normals and the faces at the ACCEPTED points.
+ *   - The sharp-edge flags, the feature edge projections and the inner-neighbour coordinates are recomputed by every iteration
+ *     from the points it starts from; the corner and feature lists are fixed at set-up.  They need nothing.
+ *   - The guard goes back across iterations, so its snapshot and its restore carry the point normals whenever boundary point
+ *     smoothing (or layers) is on: a restored run replays the iterations bit for bit.
+ *   - residual and nFrozenPoints stay the loop's own, as in 10.12.
+ * Refused: an engine with a halo (the coupled entries keep refusing boundary point smoothing); on -> off while a constraint is on
+ * or the guard armed over boundary point smoothing.  Unchanged: smgpu_set_boundary_smoothing stays refused while a constraint is
+ * on or the guard armed (the exempt bytes and the snapshot are sized and evaluated at enabling); the scaling passes (10.19) stay
+ * refused with boundary point smoothing -- a scaled boundary point leaves the target surface. */
+int smgpu_set_boundary_revert(smgpu_handle* h, int32_t on);   /* default 0 */
+int smgpu_get_boundary_revert(smgpu_handle* h, int32_t* on);
+
 /* ---- the same report for a sub-domain of a decomposed mesh (DESIGN.md "Mesh quality", 10.4) -----------------------------
  * Step-wise; the host moves the buffers between the calls, with or without a halo (not between smgpu_iter_begin and _end):
  *   1. smgpu_quality_coupled_pack: the geometry of the current points (the loop's own launch, uncounted), then the owner cell

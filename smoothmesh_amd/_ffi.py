@@ -369,6 +369,8 @@ SYMBOLS = {
     "smgpu_set_quality_constraint_scaling_coupled": (C.c_int, [C.c_void_p, C.POINTER(QualityConstraintScaling), C.POINTER(QualityScaleCoupling)]),
     "smgpu_quality_constraint_pass_scale": (C.c_int, [C.c_void_p, C.c_int64]),
     "smgpu_quality_constraint_pass_sweep": (C.c_int, [C.c_void_p]),
+    "smgpu_set_boundary_revert": (C.c_int, [C.c_void_p, C.c_int32]),
+    "smgpu_get_boundary_revert": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "smgpu_quality_constraint_coupled_exempt": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_begin": (C.c_int, [C.c_void_p]),
     "smgpu_quality_constraint_pass_faces": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -100,7 +100,7 @@ const char* kValueOptions[] = {"time", "centroidalIters", "maxStepLength", "relS
                                "meshQuality", "qualityInterval", "qualityGuard", "qualityGuardRefine", "tangleConstraint", "tanglePasses",
                                "qualityConstraint", "maxNonOrtho", "maxInternalSkewness", "maxBoundarySkewness", "qualityConstraintPasses",
                                "minTetQuality", "minTwist", "minTriangleTwist", "minFaceWeight", "minVolRatio", "minDeterminant",
-                               "maxConcave", "minFlatness", "minVol", "minArea", "meshQualityDict", "scalePasses", "errorReduction", "nSmoothScale"};
+                               "maxConcave", "minFlatness", "minVol", "minArea", "meshQualityDict", "scalePasses", "errorReduction", "nSmoothScale", "boundaryRevert"};
 
 Options parseArgs(int argc, char** argv) {
     Options o;
@@ -146,6 +146,9 @@ Options parseArgs(int argc, char** argv) {
                       "        the values come from the options only, never from meshQualityDict)\n"
                       "       [-layerPatches '(p1 \"re.*\")' -layerMaxBlendingFraction x -layerEdgeLength x -layerExpansionRatio x\n"
                       "        -minLayers n -maxLayers n]\n"
+                      "       [-boundaryRevert b] (with -tangleConstraint, -qualityConstraint or -qualityGuard on a case with boundary point smoothing:\n"
+                      "        a boundary point of a bad cell goes back off its projection like any other point; the point normals are never reverted;\n"
+                      "        serial runs only, not with -scalePasses > 0)\n"
                       "       [-smoothingPatches '(p1 \"re.*\")' -internalSmoothingBlendingFraction x]   (boundary point smoothing, with\n"
                       "        constant/geometry/targetSurfaces.obj + initEdges.obj [+ targetEdges.obj])\n"
                       "Move internal mesh points to increase mesh quality (MI355X engine)");
@@ -651,6 +654,13 @@ int main(int argc, char** argv) {
     if (qualityConstraint && (qcPasses < 0 || qcPasses > 0x7fffffffL)) fatal("qualityConstraintPasses must be between 0 and 2147483647");
     if (qualityConstraint && (qcMaxNonOrtho != qcMaxNonOrtho || qcMaxInternalSkewness != qcMaxInternalSkewness || qcMaxBoundarySkewness != qcMaxBoundarySkewness))
         fatal("-maxNonOrtho, -maxInternalSkewness and -maxBoundarySkewness must be numbers");
+    // -boundaryRevert: the opt-in of DESIGN.md 10.21 (smgpu_set_boundary_revert): the two constraints and the guard on a case with
+    // boundary point smoothing
+    const bool boundaryRevert = opt.getB("boundaryRevert", false);
+    if (boundaryRevert && opt.parallel)
+        fatal("-boundaryRevert is not available with -parallel: the constraints and the guard it opens to boundary point smoothing are their serial forms");
+    if (boundaryRevert && !tangleConstraint && !qualityConstraint && !qualityGuard)
+        fatal("-boundaryRevert needs -tangleConstraint true, -qualityConstraint true or -qualityGuard true: it says what they do to a boundary point");
     // SMOOTHMESH_TIMELINE=1: where this process's wall time goes, one stderr line per stage (seconds since main started)
     const bool timeline = std::getenv("SMOOTHMESH_TIMELINE") && std::atoi(std::getenv("SMOOTHMESH_TIMELINE")) > 0;
     auto mark = [&](const char* what) { if (timeline) std::fprintf(stderr, "[smoothMesh %8.3f s] %s\n", secondsSince(t0), what); };
@@ -831,15 +841,20 @@ int main(int argc, char** argv) {
                                      anySmoothingPatch;
     if (doBoundarySmoothing) OUTS("Enabled boundary point smoothing\n");
     else OUT("Boundary point smoothing is disabled. Missing smoothingPatches, or one or both of files:\n%s\n%s\n\n", targetSurfacesFile.c_str(), initEdgesFile.c_str());
-    if (qualityGuard && doBoundarySmoothing)
+    if (qualityGuard && doBoundarySmoothing && !boundaryRevert)
         fatal("-qualityGuard is not available with boundary point smoothing: the point normals it blends from iteration to iteration and "
-              "its corner lists are not part of the guard's snapshot (run without -smoothingPatches, or without the guard)");
-    if (tangleConstraint && doBoundarySmoothing)
+              "its corner lists are not part of the guard's snapshot (run without -smoothingPatches, or without the guard); "
+              "-boundaryRevert true opts in to DESIGN.md 10.21's contract");
+    if (tangleConstraint && doBoundarySmoothing && !boundaryRevert)
         fatal("-tangleConstraint is not available with boundary point smoothing: it rewrites the boundary points from state that a reverted "
-              "iteration would leave ahead of the points (run without -smoothingPatches, or without the constraint)");
-    if (qualityConstraint && doBoundarySmoothing)
+              "iteration would leave ahead of the points (run without -smoothingPatches, or without the constraint); "
+              "-boundaryRevert true opts in to DESIGN.md 10.21's contract");
+    if (qualityConstraint && doBoundarySmoothing && !boundaryRevert)
         fatal("-qualityConstraint is not available with boundary point smoothing: it rewrites the boundary points from state that a reverted "
-              "iteration would leave ahead of the points (run without -smoothingPatches, or without the constraint)");
+              "iteration would leave ahead of the points (run without -smoothingPatches, or without the constraint); "
+              "-boundaryRevert true opts in to DESIGN.md 10.21's contract");
+    if (qcScalePasses > 0 && doBoundarySmoothing)
+        fatal("-scalePasses: scaling passes with boundary point smoothing are not available (a scaled boundary point leaves the target surface)");
     if (doLayerTreatment && !doBoundarySmoothing)   // SM.C:2095-2098
         OUTS("WARNING: Boundary layer treatment will be done without boundary point smoothing. This can result in distorted boundary cells.\n");
 
@@ -1367,6 +1382,10 @@ int main(int argc, char** argv) {
     double timeValue = startIsConstant ? 0.0 : startValue;
     // -tangleConstraint: the engine's own constraint (include/smgpu.h, smgpu_set_tangle_constraint), enabled on the
     // initial points with everything set up, in front of the guard: the guard judges what the constraint accepts
+    if (boundaryRevert) {
+        check(smgpu_set_boundary_revert(R[0].h, 1), "smgpu_set_boundary_revert");
+        OUTS("Boundary revert: on");
+    }
     std::vector<smgpu_tangle_record> tangle;
     if (tangleConstraint) {
         const smgpu_tangle_params tp{(int32_t)tanglePasses};

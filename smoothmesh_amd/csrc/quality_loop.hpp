@@ -99,6 +99,24 @@ int smgpu_get_quality_trace(smgpu_handle* h, smgpu_quality_trace_record* out, in
     return h->qt.slab.drain(out, cap, n, "smgpu_get_quality_trace");
 }
 
+// ---- the boundary revert switch (DESIGN.md "Mesh quality", 10.21) ----
+// The opt-in under which the serial tangle constraint, the serial quality constraint and the guard accept an engine with boundary
+// point smoothing.  It is a decision about the contract, not a mode of the loop: the loop launches what it launches without it.
+int smgpu_set_boundary_revert(smgpu_handle* h, int32_t on) {
+    if (!h) return fail("null handle");
+    if (h->haloOn) return fail("smgpu_set_boundary_revert: not available on an engine with a halo (the coupled constraints refuse boundary point smoothing)");
+    if (!on && h->bndOn && (h->tg.on || h->qc.on || h->qg.armed))
+        return fail(std::string("smgpu_set_boundary_revert: ") + (h->tg.on ? "the tangle constraint is on" : h->qc.on ? "the quality constraint is on" : "the quality guard is armed") +
+                    " over boundary point smoothing, which only the switch allows; switch that off first");
+    h->bndRevert = on != 0;
+    return 0;
+}
+int smgpu_get_boundary_revert(smgpu_handle* h, int32_t* on) {
+    if (!h || !on) return fail("null argument");
+    *on = h->bndRevert ? 1 : 0;
+    return 0;
+}
+
 // ---- the guard on the quality history (kernels_quality_guard.hpp, DESIGN.md "Mesh quality", 10.11) ----
 static int qualityGuardDisarm(smgpu_handle* h, bool release) {
     h->qg.armed = false;
@@ -111,10 +129,13 @@ static int qualityGuardDisarm(smgpu_handle* h, bool release) {
     return 0;
 }
 // the per-point state an iteration carries to the next (State's non-const pointers that an iteration reads before it writes them:
-// ptsCur, and layerNormal with layers) between the engine and the snapshot, on the engine's stream
+// ptsCur, and layerNormal with layers or with boundary point smoothing, whose k_bnd_normals blends it once per iteration) between
+// the engine and the snapshot, on the engine's stream.  Of BndView's non-const members flags (BF_SHARP), featSum and featCnt are
+// written by every iteration before it reads them (10.21).
+static bool guardCarriesNormals(const smgpu_handle* h) { return (h->layersOn || h->bndOn) && h->st.layerNormal; }
 static int qualityGuardCopy(smgpu_handle* h, bool restore, int64_t number, bool needGood) {
     const long long n = 3 * (long long)h->mv.nPoints;
-    const bool normals = h->layersOn && h->qg.normal && h->st.layerNormal;
+    const bool normals = guardCarriesNormals(h) && h->qg.normal;
     const double *s0 = restore ? h->qg.pts : h->st.ptsCur, *s1 = normals ? (restore ? h->qg.normal : h->st.layerNormal) : nullptr;
     double *d0 = restore ? h->st.ptsCur : h->qg.pts, *d1 = normals ? (restore ? h->st.layerNormal : h->qg.normal) : nullptr;
     const int grid = (int)std::max<long long>(1, ((n >> 1) + (long long)kGuardBlock * kGuardPer - 1) / ((long long)kGuardBlock * kGuardPer));
@@ -180,7 +201,7 @@ int smgpu_set_quality_guard(smgpu_handle* h, const smgpu_quality_guard_params* p
     const uint32_t all = SMGPU_GUARD_NONPOSITIVE_VOLUME | SMGPU_GUARD_WRONG_ORIENTED | SMGPU_GUARD_ERROR_NONORTH;
     if (prm.criteria == 0 || (prm.criteria & ~all)) return fail("smgpu_set_quality_guard: criteria must be a non-empty combination of SMGPU_GUARD_NONPOSITIVE_VOLUME, _WRONG_ORIENTED and _ERROR_NONORTH");
     if (h->haloOn) return fail(kQualityHaloRefusal);
-    if (h->bndOn)
+    if (h->bndOn && !h->bndRevert)
         return fail("smgpu_set_quality_guard: not available on an engine with boundary point smoothing (its point normals are a running blend across the "
                     "iterations and its corner lists are host state, neither of which the guard's snapshot holds)");
     if (h->qt.interval <= 0) return fail("smgpu_set_quality_guard: the guard judges the records of the quality trace; switch it on first (smgpu_set_quality_trace)");
@@ -191,7 +212,7 @@ int smgpu_set_quality_guard(smgpu_handle* h, const smgpu_quality_guard_params* p
     QualityGuardHost& g = h->qg;
     const size_t n = 3 * (size_t)std::max(1, h->mv.nPoints);
     if (g.block.alloc(&g.dev, 1) || g.block.alloc(&g.rec, 1) || g.block.alloc(&g.pts, n) ||
-        (h->layersOn && h->st.layerNormal && g.block.alloc(&g.normal, n)))
+        (guardCarriesNormals(h) && g.block.alloc(&g.normal, n)))
         return g.block.failed("the quality guard");
     HIP_OK(hipMemsetAsync(h->qg.dev, 0, sizeof(GuardDev), h->stream));
     HIP_OK(hipMemsetAsync(h->qg.rec, 0, sizeof(smgpu_quality_trace_record), h->stream));
@@ -288,7 +309,7 @@ int smgpu_set_tangle_constraint(smgpu_handle* h, const smgpu_tangle_params* p, i
     const smgpu_tangle_params prm = p ? *p : smgpu_tangle_params{2};
     if (prm.passes < 0) return fail("smgpu_set_tangle_constraint: passes < 0");
     if (h->haloOn) return fail(kQualityHaloRefusal);
-    if (h->bndOn)
+    if (h->bndOn && !h->bndRevert)
         return fail("smgpu_set_tangle_constraint: not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
                     "points from state that a reverted iteration would leave ahead of the points)");
     if (h->qc.on) return fail("smgpu_set_tangle_constraint: the quality constraint is on (smgpu_set_quality_constraint), and it contains this one; switch it off first");
@@ -664,7 +685,7 @@ static int qualityConstraintRefusals(smgpu_handle* h, const std::string& api, co
     if (shape.maxConcave < 0.0) return fail(api + ": maxConcave < 0");
     if (!coupled && h->haloOn) return fail(kQualityHaloRefusal);
     if (coupled && !h->haloOn) return fail(api + ": the engine has no halo (smgpu_halo_configure); a serial engine takes " + serial);
-    if (h->bndOn)
+    if (h->bndOn && (coupled || !h->bndRevert))
         return fail(api + ": not available on an engine with boundary point smoothing (it rewrites the proposals of the boundary "
                     "points from state that a reverted iteration would leave ahead of the points)");
     if (h->tg.on)
@@ -781,6 +802,9 @@ int smgpu_set_quality_constraint_scaling(smgpu_handle* h, const smgpu_quality_co
     if (!(prm.errorReduction >= 0.0 && prm.errorReduction < 1.0)) return fail(api + ": errorReduction is outside 0 <= errorReduction < 1");
     if (prm.nSmoothScale < 0) return fail(api + ": nSmoothScale < 0");
     if (h->haloOn) return fail(api + ": not available on an engine with a halo (the coupled form of the quality constraint has no scaling passes)");
+    if (h->bndOn && h->bndRevert)
+        return fail(api + ": not available on an engine with boundary point smoothing: scaling passes with boundary point smoothing are not available (a scaled "
+                    "boundary point leaves the target surface)");
     if (h->bndOn) return fail(api + ": not available on an engine with boundary point smoothing (nor is the quality constraint)");
     if (h->tg.on)
         return fail(api + ": the tangle constraint is on (smgpu_set_tangle_constraint), and it has no scaling passes; the quality constraint with its "
@@ -1033,6 +1057,9 @@ int smgpu_set_quality_constraint_scaling_coupled(smgpu_handle* h, const smgpu_qu
     if (!(prm.errorReduction >= 0.0 && prm.errorReduction < 1.0)) return fail(api + ": errorReduction is outside 0 <= errorReduction < 1");
     if (prm.nSmoothScale < 0) return fail(api + ": nSmoothScale < 0");
     if (!h->haloOn) return fail(api + ": the engine has no halo (smgpu_halo_configure); a serial engine takes smgpu_set_quality_constraint_scaling");
+    if (h->bndOn && h->bndRevert)
+        return fail(api + ": not available on an engine with boundary point smoothing: scaling passes with boundary point smoothing are not available (a scaled "
+                    "boundary point leaves the target surface)");
     if (h->bndOn) return fail(api + ": not available on an engine with boundary point smoothing (nor is the quality constraint)");
     if (h->tg.on)
         return fail(api + ": the coupled tangle constraint is on (smgpu_set_tangle_constraint_coupled), and it has no scaling passes; the coupled quality "

@@ -213,6 +213,7 @@ struct smgpu_handle {
     bool layersOn = false;     // smgpu_set_layers
     bool packTiles = true;     // SMGPU_PACK_TILES=0: exchange A packed by the per-point kernel (k_halo_packA)
     bool bndOn = false;        // smgpu_set_boundary_smoothing
+    bool bndRevert = false;    // smgpu_set_boundary_revert: the constraints and the guard accept bndOn (10.21)
     hipStream_t bndSide = nullptr;   // k_bnd_normals / k_bnd_feature run next to the geometry kernel
     hipEvent_t evBndFork = nullptr, evBndJoin = nullptr;
     bool bndPreInFlight = false;

@@ -749,7 +749,7 @@ class SmoothEngine:
         exceeds the baseline's stops the loop on the device; the iterate() call that meets it returns the iterations that ran,
         the tripping one included, and leaves the engine at the last good state: the last traced iteration that passed, or with
         `refine` the exact last iteration that passes.  The guard then disarms itself.  criteria=None disarms.  Refused on an
-        engine with a halo or with boundary point smoothing."""
+        engine with a halo, and with boundary point smoothing unless set_boundary_revert() opted in."""
         if criteria is None:
             self._check(self._lib.smgpu_set_quality_guard(self._h, None, 0))
             return
@@ -779,11 +779,25 @@ class SmoothEngine:
         of their own: no refining, the guard stays armed, the trace's running number becomes snapshotIteration."""
         self._check(self._lib.smgpu_quality_guard_restore(self._h))
 
+    def set_boundary_revert(self, on=True):
+        """The opt-in under which the serial tangle constraint, the serial quality constraint (every limit) and the quality guard
+        accept an engine with boundary point smoothing (include/smgpu.h, smgpu_set_boundary_revert; DESIGN.md "Mesh quality",
+        10.21): a boundary point marked by a bad cell goes back like any other, off the place its projection gave it; the point
+        normals are the loop's and are never reverted; the guard's snapshot carries them.  Launches and allocates nothing.
+        Refused on an engine with a halo, and off while a constraint or the guard is on over boundary point smoothing."""
+        self._check(self._lib.smgpu_set_boundary_revert(self._h, 1 if on else 0))
+
+    def boundary_revert(self) -> bool:
+        on = C.c_int32(0)
+        self._check(self._lib.smgpu_get_boundary_revert(self._h, C.byref(on)))
+        return bool(on.value)
+
     def set_tangle_constraint(self, passes=2):
         """Tangle constraint (include/smgpu.h, smgpu_set_tangle_constraint): from now on iterate() puts the points of every cell
         that an iteration turned bad -- non-positive volume or a wrongly oriented face, by the report's measure -- back where the
         iteration found them, in up to `passes` marked passes and then a full revert of the iteration.  Cells bad at the current
-        points are exempt.  Adds no synchronisation to the loop.  Refused on an engine with a halo or with boundary point smoothing."""
+        points are exempt.  Adds no synchronisation to the loop.  Refused on an engine with a halo, and with boundary point smoothing
+        unless set_boundary_revert() opted in."""
         p = _ffi.TangleParams(int(passes))
         self._check(self._lib.smgpu_set_tangle_constraint(self._h, C.byref(p), 1))
 
@@ -826,8 +840,8 @@ class SmoothEngine:
         faces (<= 0: off).  From now on iterate() puts the points of every cell that an iteration turned bad -- by the tangle
         constraint's measure, or as the owner or neighbour of a face over a limit -- back where the iteration found them, in up to
         `passes` marked passes and then a full revert.  Cells and faces bad at the current points are exempt.  Adds no
-        synchronisation to the loop.  Refused on an engine with a halo, with boundary point smoothing, or with the tangle
-        constraint on.
+        synchronisation to the loop.  Refused on an engine with a halo, with boundary point smoothing (unless set_boundary_revert()
+        opted in), or with the tangle constraint on.
         The six further limits (smgpu_set_quality_constraint_limits; None: off) make a face bad whose face-centre
         tet quality, twist, triangle twist, interpolation weight or volume ratio lies under them, and a cell whose determinant
         does, by the measures of mesh_quality_motion / mesh_quality_geometry; with all six None the call is what it was.
